@@ -20,11 +20,15 @@ set, waits for them and exits with their worst code.  It never replaces a proces
 initialised the GPU.  A rank whose process group does not have N members exits non-zero.
 
 Rank 0 prints ONE JSON line.  Its contract fields are the headline region (fixed-step RK4, float32: the
-integrator BASELINE.json's north star names).  `production_path` is a second timed region of the same
-frame, same K and W, with the integrator the reference itself runs (`python image_lens.py --a 0.9` ->
-metrics.py:1128-1132 -> DP45 float64, metrics.py:419-567; the product's plugin default), with its own
-roofline and its own CPU baseline.  `projected_ranks` (N = 1): what each rank of a 2 / 4 / 8 GPU run
-renders, one rank at a time on this GPU -- a projection, labelled as one.
+integrator BASELINE.json's north star names).  A plain run does only that: set-up, W warm-up frames, the
+K timed frames, the line.  Everything else is measured with `--full`:
+  production_path  a second timed region of the same frame, same K and W, with the integrator the reference
+                itself runs (`python image_lens.py --a 0.9` -> metrics.py:1128-1132 -> DP45 float64,
+                metrics.py:419-567; the product's plugin default), with its own roofline and its own CPU baseline.
+  projected_ranks  (N = 1) what each rank of a 2 / 4 / 8 GPU run renders, one rank at a time on this GPU --
+                a projection, labelled as one.
+  pipelined, chain_floor, end_to_end_ms, cpu_baseline  (--extras / --no-cpu-baseline choose among them).
+Two fields explained (`roofline` is in a plain run's line too: it needs this run's counters and a committed count):
   roofline      the integrate kernel against the FP32 VALU ISSUE peak, from the work it executed:
                 wave-instructions per launch (rocprofv3 SQ_INSTS_VALU for this workload and this
                 build, profiles/valu_counts.json, scaled by the loop iterations the kernel counted
@@ -35,6 +39,11 @@ renders, one rank at a time on this GPU -- a projection, labelled as one.
                 the kernel does not execute, is reported beside it as `algorithmic_as_written`.
   cpu_baseline  the oracle (CPU port of the reference algorithm, float64, OpenMP) compiled
                 -O3 -march=native on this host, on a strided subsample of the same frame.
+`--dump-outputs DIR` writes what the last timed frame computed (rank 0), as float32 .npy files: `rgba` (the
+RGBA8 frame the gather hands rank 0) and, with one rank, that rank's `final_alpha`, `escaped` and `winding`, each
+at the pixels of `pixel_index` (float64 flat indices: all of them up to 2^20 pixels, else a seeded sample of 2^20).
+The library's final_alpha is NaN where a ray did not escape; the dump writes 0 there and 0 in `escaped` (1 elsewhere),
+so every file is finite.
 """
 import argparse
 import json
@@ -82,7 +91,7 @@ def parse(argv=None):
     ap.add_argument("--no-production-path", action="store_true",
                     help="skip the second timed region (the same frame with the reference's production integrator, DP45 float64)")
     ap.add_argument("--extras", default="pipelined,production,chain,e2e,projection",
-                    help="which of the extras to run (comma list; --no-extras = none): pipelined (the K frames again, 3 in flight), "
+                    help="which of the extras --full runs (comma list; --no-extras = none): pipelined (the K frames again, 3 in flight), "
                          "production (second timed region, DP45 float64), chain (longest ray alone), e2e (host-pointer frame), "
                          "projection (each rank of 2 / 4 / 8 alone on this GPU)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target wall time of each CPU baseline leg")
@@ -111,7 +120,48 @@ def parse(argv=None):
     ap.add_argument("--backend", default=None, help="process-group backend (default nccl = RCCL; tests use gloo)")
     ap.add_argument("--stub-render", action="store_true",
                     help="CPU rehearsal of the launcher / gather path: no GPU, rows filled by a formula (tests only)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline region: the extras (--extras / --no-extras / "
+                         "--no-production-path choose which) and the CPU baselines (unless --no-cpu-baseline). "
+                         "Without it a run times the headline region only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed frames, write what the last one computed as DIR/<name>.npy (float32 / float64, "
+                         f"at most {DUMP_PIXELS} pixels per array: a seeded sample of a larger frame)")
+    a = ap.parse_args(argv)
+    if a.dump_outputs and a.steps < 1:
+        ap.error("--dump-outputs needs --steps >= 1: it writes what the last timed step computed")
+    return a
+
+
+DUMP_PIXELS = 1 << 20      # 2^20 pixels x (7 float32 + 1 float64) = 36 MiB at most
+
+
+def dump_sample_index(n, seed=0):
+    """Flat pixel indices that --dump-outputs writes: every pixel when n <= DUMP_PIXELS, else one seeded pixel out of
+    each of DUMP_PIXELS equal runs of pixels (the same pixels for the same arguments, run after run)."""
+    import numpy as np
+    if n <= DUMP_PIXELS:
+        return np.arange(n, dtype=np.int64)
+    stride = n // DUMP_PIXELS
+    return np.arange(DUMP_PIXELS, dtype=np.int64) * stride + np.random.default_rng(seed).integers(0, stride, DUMP_PIXELS)
+
+
+def split_final_alpha(fa):
+    """final_alpha is NaN where the ray did not escape (ltrace.h): -> (final_alpha with 0 there, escaped 1 / 0), both
+    float32 and finite, the same information."""
+    import torch
+    escaped = torch.isfinite(fa)
+    return torch.where(escaped, fa, torch.zeros_like(fa)), escaped.to(torch.float32)
+
+
+def write_outputs(out_dir, arrays):
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64) or not np.isfinite(a).all():
+            raise ValueError(f"--dump-outputs: {name} must be finite float32 / float64")
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    print(f"bench.py: wrote {', '.join(sorted(arrays))} to {out_dir}", file=sys.stderr, flush=True)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -296,6 +346,10 @@ def stub_main(args, world, rank):
         r = torch.arange(size)
         expect = ((r[:, None, None] * 131 + torch.arange(size)[None, :, None] * 7 + torch.arange(4)[None, None, :] * 3) % 251)
         ok = bool(torch.equal(full, expect.to(torch.uint8)))
+        if args.dump_outputs:
+            idx = dump_sample_index(size * size)
+            write_outputs(args.dump_outputs, {"rgba": full.reshape(-1, 4)[torch.from_numpy(idx)].to(torch.float32).numpy(),
+                                              "pixel_index": idx.astype("float64")})
         print(json.dumps({"metric": "Mrays/s", "value": 0.0, "unit": "Mrays/s", "n_gpus": world, "stub": True,
                           "rccl_world": dist.get_world_size() if world > 1 else 1, "frame_ok": ok,
                           "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed * 1e3 / max(args.steps, 1), 3)}),
@@ -477,8 +531,10 @@ def main(argv=None):
         balance_used = "cost" if owner is not None else "cyclic (cost-weighted table unavailable: fell back)"
     if owner is not None:
         rows_max = max(len(ltrace.owned_rows(size, rb, owner, p)) for p in range(n_parts))
+        my_rows = len(ltrace.owned_rows(size, rb, owner, part))
     else:
         rows_max = max(ltrace.local_rows(size, rb, n_parts, p) for p in range(n_parts))
+        my_rows = ltrace.local_rows(size, rb, n_parts, part)
 
     d_stats = torch.zeros(ltrace.STAT_WORDS, dtype=torch.int64, device=dev)
     d_bg = None
@@ -494,7 +550,22 @@ def main(argv=None):
     # --------------------------------------------------------------------------------------------
     # one timed region: W warm-up frames, then K frames between barrier + synchronize on both sides
     # --------------------------------------------------------------------------------------------
-    def run_region(integ, prec, K, Wu, F, pipelined_extra):
+    def dump_last_frame(b, frame):
+        """--dump-outputs: what the last timed frame left in its buffers.  `frame` is the RGBA8 frame the gather handed
+        rank 0; with one rank its rows are this rank's rows, which are also the valid rows of fa / winding."""
+        rows = size if world > 1 else my_rows
+        idx_np = dump_sample_index(rows * size)
+        idx = torch.from_numpy(idx_np).to(dev)
+        arrays = {"rgba": frame[:rows].reshape(-1, 4).index_select(0, idx).to(torch.float32)}
+        if world == 1:
+            arrays["final_alpha"], arrays["escaped"] = split_final_alpha(b["fa"][:rows].reshape(-1).index_select(0, idx))
+            # the library writes winding as uint16 into this int16 buffer
+            arrays["winding"] = (b["w"][:rows].reshape(-1).index_select(0, idx).to(torch.int32) & 0xFFFF).to(torch.float32)
+        arrays = {k: v.cpu().numpy() for k, v in arrays.items()}
+        arrays["pixel_index"] = idx_np.astype(np.float64)
+        write_outputs(args.dump_outputs, arrays)
+
+    def run_region(integ, prec, K, Wu, F, pipelined_extra, dump=False):
         def make_sets(nf):
             out = []
             for f in range(nf):
@@ -544,10 +615,12 @@ def main(argv=None):
         fence()
         t0 = time.perf_counter()
         for i in range(K):
-            step(i, i, sets)
+            last = step(i, i, sets)
         fence()
         elapsed = time.perf_counter() - t0
         tm = ltrace.timing_collect()
+        if dump and rank == 0:
+            dump_last_frame(sets[(K - 1) % len(sets)], last)
 
         steps = max(K, 1)
         render_ms = sum(ev[3 * i].elapsed_time(ev[3 * i + 1]) for i in range(K)) / steps
@@ -713,8 +786,10 @@ def main(argv=None):
         return res
 
     F = max(1, args.frames_in_flight)
-    extras = set() if args.no_extras else {x.strip() for x in args.extras.split(",") if x.strip()}
-    H = run_region(args.integrator, args.precision, args.steps, args.warmup, F, args.pipelined_extra if "pipelined" in extras else 0)
+    extras = set() if (args.no_extras or not args.full) else {x.strip() for x in args.extras.split(",") if x.strip()}
+    cpu_baselines = args.full and not args.no_cpu_baseline and world == 1
+    H = run_region(args.integrator, args.precision, args.steps, args.warmup, F, args.pipelined_extra if "pipelined" in extras else 0,
+                   dump=bool(args.dump_outputs))
 
     # ---- the reference's production path (metrics.py:419-567 via :1128-1132: DP45, float64), same frame, same K and W.
     # It is what `python image_lens.py --a 0.9` integrates with and what the plugin surface defaults to (metrics.py of
@@ -784,7 +859,7 @@ def main(argv=None):
             out["end_to_end_ms"] = e2e
         if proj:
             out["projected_ranks"] = proj
-        if not args.no_cpu_baseline and world == 1:
+        if cpu_baselines:
             out["cpu_baseline"] = cpu_baseline(args, fov, args.integrator)
         if P is not None:
             proof, pworkload, pkey = roofline_of(P)
@@ -803,7 +878,7 @@ def main(argv=None):
                     "ranks": {"integrate_ms": [round(r[1], 3) for r in P["per_rank"]],
                               "render_ms": [round(r[3], 3) for r in P["per_rank"]],
                               "gather_ms": [round(r[4], 3) for r in P["per_rank"]]}}
-            if not args.no_cpu_baseline and world == 1:
+            if cpu_baselines:
                 prod["cpu_baseline"] = cpu_baseline(args, fov, "dp45")
             out["production_path"] = prod
         print(json.dumps(out), flush=True)

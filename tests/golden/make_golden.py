@@ -445,7 +445,7 @@ RAY_SETS = [
 
 def verify(todo):
     """The committed fixtures are what the reference under LT_REFERENCE computes today: regenerate, compare, write nothing
-    into the tree.  (tests/test_oracle_golden.py runs this where the reference is present.)"""
+    into the tree.  Run by hand where the reference is present: the suite itself reads nothing outside the repository."""
     global OUT_DIR
     import tempfile
     makers = {"F1": f1_rhs, "F2": f2_ic, "F6": f6_psi, "F7": f7_scalars, "F8": f8_ivp, "F9": f9_shadow, "F10": f10_dense, "F4": f4_lookup}

@@ -1,5 +1,5 @@
 """bench.py on the GPU box, as the driver runs it (a subprocess: torch is imported before the library there):
-the JSON contract, the executed-work roofline (frac <= 1 by construction), the extras."""
+the JSON contract, the executed-work roofline (frac <= 1 by construction), the extras (--full), --dump-outputs."""
 import json
 import os
 import subprocess
@@ -22,7 +22,7 @@ def _bench(args, timeout=600):
 
 
 def test_north_star_line_has_the_contract_fields_and_an_honest_roofline():
-    d = _bench(["--steps", "3", "--warmup", "1", "--cpu-seconds", "2"])
+    d = _bench(["--full", "--steps", "3", "--warmup", "1", "--cpu-seconds", "2"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -69,12 +69,47 @@ def test_north_star_line_has_the_contract_fields_and_an_honest_roofline():
 
 
 def test_other_workloads_and_flags():
-    d = _bench(["--size", "1024", "--metric", "schwarzschild", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"])
+    d = _bench(["--full", "--size", "1024", "--metric", "schwarzschild", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"])
     assert d["config"]["workload"].startswith("schwarzschild_a0.0_shadow_1024x1024") and d["roofline"]["frac"] is None
     d = _bench(["--size", "1024", "--r-obs", "100", "--background", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extras"])
     assert d["config"]["workload"].endswith("_lensed_background") and d["config"]["bg_sampling"] == "global" and "pipelined" not in d
-    d = _bench(["--size", "1024", "--frames-in-flight", "2", "--steps", "4", "--warmup", "2", "--no-cpu-baseline"])
+    d = _bench(["--full", "--size", "1024", "--frames-in-flight", "2", "--steps", "4", "--warmup", "2", "--no-cpu-baseline"])
     assert d["config"]["frames_in_flight"] == 2
     d = _bench(["--size", "1024", "--emulate-parts", "4", "--emulate-part", "3", "--steps", "2", "--warmup", "1",
                 "--no-cpu-baseline", "--no-extras"])
     assert d["config"]["rays_per_frame"] == 1024 * 256 and "emulated rank 3" in d["config"]["row_partition"]
+
+
+def test_plain_run_is_the_headline_only_and_dumps_what_it_computed(tmp_path):
+    """A plain run times the headline region and nothing else; --dump-outputs writes what its last timed frame computed,
+    the same arrays from run to run, and the same as lt_render gives for that frame."""
+    import numpy as np
+    import ltrace
+    args = ["--size", "1024", "--steps", "2", "--warmup", "1"]
+    runs = []
+    for k in range(2):
+        d = _bench(args + ["--dump-outputs", str(tmp_path / f"out{k}")])
+        assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["dtype"] == "f32" and d["higher_is_better"] is True
+        assert abs(d["value"] - d["config"]["rays_per_frame"] / d["ms_per_step"] / 1e3) < 0.01 * d["value"]
+        for k_ in ("pipelined", "production_path", "chain_floor", "end_to_end_ms", "projected_ranks", "cpu_baseline"):
+            assert k_ not in d, k_
+        runs.append({n: np.load(tmp_path / f"out{k}" / f"{n}.npy") for n in ("rgba", "final_alpha", "escaped", "winding", "pixel_index")})
+    for n, a in runs[0].items():
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all() and np.array_equal(a, runs[1][n]), n
+    assert np.array_equal(runs[0]["pixel_index"], np.arange(1024 * 1024))      # a frame of 2^20 pixels is written whole
+    fov = np.radians(40.0)
+    cam = ltrace.Camera(1024, 1024, fov, fov, 0.0, 0.0, 50.0, np.pi / 2)
+    met = ltrace.Metric(ltrace.METRIC_KERR, 0, 1.0, 0.9)
+    ref = ltrace.render(cam, met, ltrace.default_opts(integrator="rk4", precision=32, schedule="direct"),
+                        want=("fa", "winding", "rgba"))
+    fa = ref["fa"].reshape(-1)                     # NaN where the ray did not escape: 0 in the dump, escaped = 0
+    assert np.array_equal(runs[0]["escaped"], np.isfinite(fa).astype(np.float32)) and 0 < runs[0]["escaped"].sum() < fa.size
+    assert np.array_equal(runs[0]["final_alpha"], np.where(np.isfinite(fa), fa, 0).astype(np.float32))
+    assert np.array_equal(runs[0]["winding"], ref["winding"].reshape(-1).astype(np.float32))
+    assert np.array_equal(runs[0]["rgba"], ref["rgba"].reshape(-1, 4).astype(np.float32))
+    # a larger frame is sampled: at most 2^20 pixels, seeded, the same pixels every run
+    d = _bench(["--steps", "1", "--warmup", "1", "--dump-outputs", str(tmp_path / "big")])
+    assert all(np.isfinite(np.load(tmp_path / "big" / f)).all() for f in os.listdir(tmp_path / "big"))
+    idx = np.load(tmp_path / "big" / "pixel_index.npy")
+    assert d["steps"] == 1 and idx.size == 1 << 20 and idx.max() < 4096 * 4096 and np.all(np.diff(idx) > 0)
+    assert sum(os.path.getsize(tmp_path / "big" / f) for f in os.listdir(tmp_path / "big")) <= 64 << 20

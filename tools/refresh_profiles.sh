@@ -14,17 +14,17 @@ if [ "${1:-}" = measure ]; then
     mkdir -p $G/pc_tmp && cp $G/pmc_counts/valu_counts.json $G/pmc_counts/hbm_traffic.json profiles/ 2>/dev/null  # so that the lines below carry frac / traffic
     bash tools/prof.sh direct > $G/prof_direct.log 2>&1                      # plain / traced / plain + SQ counters, north-star frame
     PROF_PMC=0 bash tools/prof.sh dp45_exact --integrator dp45_exact --precision 64 > $G/prof_dp45_exact.log 2>&1
-    python3 bench.py --steps 20 --warmup 5 > $G/bench_default.json 2>$G/bench_default.err   # the driver's command line
-    echo "driver line done"; tail -c 300 $G/bench_default.json
+    python3 bench.py --full --steps 20 --warmup 5 > $G/bench_default.json 2>$G/bench_default.err   # the default frame, every extra
+    echo "default line done"; tail -c 300 $G/bench_default.json
     [ -n "$QUICK" ] && exit 0
     bash tools/prof.sh queue --schedule queue > $G/prof_queue.log 2>&1
     PROF_PMC=0 bash tools/prof.sh dp45 --integrator dp45 --precision 64 > $G/prof_dp45.log 2>&1
     bash tools/prof.sh imagelens --r-obs 100 --background > $G/prof_imagelens.log 2>&1
     echo prof done
-    python3 bench.py --schedule queue --no-cpu-baseline --extras pipelined > $G/bench_queue.json 2>/dev/null
-    python3 bench.py --integrator dp45 --precision 64 --no-cpu-baseline --extras pipelined > $G/bench_dp45.json 2>/dev/null
-    python3 bench.py --r-obs 100 --background --no-cpu-baseline --extras pipelined,chain > $G/bench_imagelens.json 2>/dev/null
-    python3 bench.py --size 2048 --no-cpu-baseline > $G/bench_2048.json 2>/dev/null
+    python3 bench.py --full --schedule queue --no-cpu-baseline --extras pipelined > $G/bench_queue.json 2>/dev/null
+    python3 bench.py --full --integrator dp45 --precision 64 --no-cpu-baseline --extras pipelined > $G/bench_dp45.json 2>/dev/null
+    python3 bench.py --full --r-obs 100 --background --no-cpu-baseline --extras pipelined,chain > $G/bench_imagelens.json 2>/dev/null
+    python3 bench.py --full --size 2048 --no-cpu-baseline > $G/bench_2048.json 2>/dev/null
     echo bench done
     bash tools/all_configs.sh > $G/all_configs.txt 2>&1
     bash tools/pipeline_bench.sh > $G/pipeline.txt 2>&1
