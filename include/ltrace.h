@@ -52,6 +52,7 @@ extern "C" {
 #define LT_STATUS_ESCAPED 1
 #define LT_STATUS_CAPTURED (-1)
 #define LT_STATUS_INVALID 0
+#define LT_STATUS_DISK 2 /* lt_render_disk / lt_trace_batch_kerr_disk only: the ray ended on the accretion disk */
 
 /* Pinhole camera of image_lens.py:133-152 / :193-208 (pixel corners, no +0.5).
  * psi = (pitch_up, yaw_right) BH offset in radians, image_lens.py:21-61. */
@@ -115,6 +116,7 @@ typedef struct lt_opts {
 #define LT_STAT_CLK_TICKS 9  /* 100 MHz real-time ticks (s_memrealtime) over the same lifetimes        */
 #define LT_STAT_BG_TILES_LDS 10    /* epilogue, lensed background: 256-pixel groups whose source texels were staged in LDS */
 #define LT_STAT_BG_TILES_GLOBAL 11 /* ... and groups that fell back to the per-pixel global gather                  */
+#define LT_STAT_DISK 12            /* lt_render_disk_dev: rays that ended on the accretion disk                        */
 #define LT_STAT_WORDS 16
 
 typedef struct lt_stats {
@@ -302,6 +304,63 @@ int lt_dense_predict_lengths(const lt_metric *metric, const lt_dense_opts *opts,
                              uint16_t *out_key);
 /* Device probe of the 8-D right-hand side for parity tests: states (n, 8) -> out (n, 8), host pointers. */
 int lt_rhs8_probe(const lt_metric *metric, const double *states, int64_t n, double *out);
+
+/* ---- thin Keplerian accretion disk ------------------------------------------------------------------- *
+ * The frame of lt_render with a geometrically thin, optically thick disk in the equatorial plane theta = pi/2,   *
+ * r_in <= r <= r_out.  Kerr only (a Schwarzschild hole is Kerr with a = 0).                                      *
+ *                                                                                                               *
+ * Material moves on circular equatorial geodesics orbiting in +phi (prograde for a > 0, retrograde for a < 0):   *
+ *   Omega = sqrt(M) / (r^(3/2) + a sqrt(M)),                                                                     *
+ *   u^t   = (r^(3/2) + a sqrt(M)) / (r^(3/4) sqrt(r^(3/2) - 3 M r^(1/2) + 2 a sqrt(M)))   (signed a).            *
+ * r_in <= 0 means the ISCO of that orbit direction (Bardeen-Press-Teukolsky, lt_kerr_isco); otherwise the call  *
+ * requires r_isco <= r_in < r_out < r_obs (LT_ERR_INVALID_ARG).                                                  *
+ *                                                                                                               *
+ * Hit: backward from the camera, the first strict sign change of theta - pi/2 between two consecutive accepted  *
+ * states of the integrator whose crossing point has r_in <= r <= r_out.  Landing exactly on pi/2 from off the    *
+ * plane counts as a crossing; a ray that lies in the plane (p_theta = 0) never hits; crossings outside the       *
+ * annulus do not stop the ray.  The crossing point is the root of theta = pi/2 on the cubic Hermite interpolant  *
+ * of the step in lambda (derivatives from the Kerr right-hand side at both ends); r, phi and the momenta are    *
+ * interpolated on the same cubic.  A step that both crosses the disk and ends the ray by capture or escape is     *
+ * tested between the previous state and the step's terminal (interpolated) state: the disk wins if the crossing  *
+ * lies on that segment.  The ray then ends with status LT_STATUS_DISK.                                           *
+ *                                                                                                               *
+ * Redshift: the camera's ray has E = -p_t = 1 and xi = p_phi; it stands for the photon the camera receives (the   *
+ * convention of the background lookup), so g = nu_obs / nu_em = 1 / (u^t (1 - Omega xi)), in float64.           *
+ * Shading, from the float32 (r_hit, g) of the disk output:                                                      *
+ *   I = exposure g^4 (r_in / r)^q,  s = g (r_in / r)^(3/4),                                                      *
+ *   ramp(s) = (clamp(2s, 0, 1), clamp(2s - 0.5, 0, 1), clamp(2s - 1, 0, 1)),  rgb = clamp(I ramp(s), 0, 1);      *
+ * with a 1-channel background the disk value is the mean of the three.  Disk pixels occlude the background; every *
+ * other pixel is exactly lt_render's pixel of the same camera with tb_symmetry = 0.                             */
+typedef struct lt_disk {
+    double r_in;     /* <= 0: the ISCO                  */
+    double r_out;    /* 20                              */
+    double q;        /* emissivity index, 3             */
+    double exposure; /* 1                               */
+    int32_t flags, reserved; /* 0 */
+} lt_disk;
+void lt_default_disk(lt_disk *d);
+/* ISCO radius of the circular equatorial orbit in +phi (prograde for a > 0); host only, works without a GPU.
+ * NaN unless M > 0 and |a| <= M. */
+double lt_kerr_isco(double M, double a);
+
+/* lt_render_dev with the disk.  Outputs as there, plus
+ *   d_disk (R, W, 3) float32 (r_hit, phi_hit in [0, 2 pi), g), NaN where the ray missed the disk.
+ * Disk pixels: fa = NaN, winding = half orbits up to the hit, status = LT_STATUS_DISK.  Stats also count
+ * LT_STAT_DISK.  Partitions (n_parts, part, block_owner) as in lt_render_dev; tb_symmetry is ignored (every row is
+ * traced).  LT_ERR_UNSUPPORTED for LT_METRIC_SCHWARZSCHILD and for LT_SCHED_QUEUE. */
+int lt_render_disk_dev(const lt_camera *cam, const lt_metric *metric, const lt_opts *opts, const lt_disk *disk,
+                       const float *d_bg, int32_t bg_channels, float *d_fa, uint16_t *d_w, int8_t *d_status,
+                       uint32_t *d_steps, float *d_disk, float *d_rgb, uint8_t *d_rgba, uint64_t *d_stats);
+/* The same with HOST pointers, staged like lt_render. */
+int lt_render_disk(const lt_camera *cam, const lt_metric *metric, const lt_opts *opts, const lt_disk *disk,
+                   const float *bg, int32_t bg_channels, float *out_fa, uint16_t *out_w, int8_t *out_status,
+                   uint32_t *out_steps, float *out_disk, float *out_rgb, uint8_t *out_rgba, lt_stats *stats);
+/* lt_trace_batch_kerr with the disk (direct schedule): out_disk (n, 3) float64 (r_hit, phi_hit, g), NaN off the
+ * disk; out_status LT_STATUS_DISK on it.  HOST pointers; out_status / out_disk / out_rhs_evals may be NULL. */
+int lt_trace_batch_kerr_disk(double M, double a, double r_obs, const double *alphas, const double *thetas,
+                             double theta_obs, double lambda_max, const uint8_t *axis_refines, int integrator,
+                             int precision, const lt_disk *disk, int64_t n, double *out_fa, int64_t *out_w,
+                             int8_t *out_status, double *out_disk, uint32_t *out_rhs_evals);
 
 /* Sum of HIP-event times (ms) of the prologue / integrate / epilogue kernels over all
  * lt_render_dev calls made with opts->timing != 0 since the last collect; *calls = how many.

@@ -5,6 +5,7 @@
 // HIP events.  No CPU compute path exists: without a GPU the entry points fail.
 #include "../../include/ltrace.h"
 #include "lt_kernels.hpp"
+#include "lt_disk.hpp"
 #ifdef LT_PROBES
 #include "lt_probe.hpp"
 #endif
@@ -666,9 +667,22 @@ static int check_opts(const lt_metric *metric, lt_opts *o)
     return LT_OK;
 }
 
+// The thin disk of lt_render_disk (lt_api_disk.inc): resolved parameters and the extra output.
+struct DiskParams {
+    double r_in, r_out, q, exposure; // r_in resolved (the ISCO when the caller asked for it)
+    float *d_disk;                   // (R, W, 3) float32 or NULL
+};
+template <typename T>
+static int launch_integrate_disk(const MetricConsts &mc, const lt_opts &o, double lambda_max, const Workspace &w,
+                                 int64_t n_q, hipStream_t s, uint64_t *kstats, const DiskParams &dp);
+static int launch_epilogue_disk(const CamConsts &c, const MetricConsts &mc, const lt_opts &o, const Workspace &w,
+                                const FrameOut &fo, uint64_t *d_stats, hipStream_t s, const DiskParams &dp);
+
+// disk == NULL: the frame path.  Else the disk frame (lt_render_disk_dev): every row traced, the disk kernels.
 static int render_dev_impl(const lt_camera *cam, const lt_metric *metric, const lt_opts *opts, const float *d_bg,
                            int32_t bg_channels, float *d_fa, uint16_t *d_w, int8_t *d_status, uint32_t *d_steps,
-                           float *d_rgb, uint8_t *d_rgba, uint64_t *d_stats, const EventQuad *own_events)
+                           float *d_rgb, uint8_t *d_rgba, uint64_t *d_stats, const EventQuad *own_events,
+                           const DiskParams *disk = nullptr)
 {
     int rc = require_device();
     if (rc) return rc;
@@ -716,7 +730,7 @@ static int render_dev_impl(const lt_camera *cam, const lt_metric *metric, const 
         c.refine_thresh = o.axis_refine_frac * (m > 1e-12 ? m : 1e-12);
     }
     // top/bottom symmetry exactly when the reference applies it (image_lens.py:218-220)
-    c.use_tb = o.tb_symmetry && metric->kind == LT_METRIC_KERR &&
+    c.use_tb = !disk && o.tb_symmetry && metric->kind == LT_METRIC_KERR &&
                fabs(cam->theta_obs - M_PI / 2) <= 1e-8 + 1e-5 * (M_PI / 2) && fabs(cam->psi_y) <= 1e-8;
     if (c.use_tb && (o.n_parts != 1 || o.block_owner)) return fail(LT_ERR_UNSUPPORTED, "tb_symmetry needs n_parts == 1 and no block_owner table");
     c.trace_rows = c.use_tb ? (c.H + 1) / 2 : c.rows_local;
@@ -800,10 +814,20 @@ static int render_dev_impl(const lt_camera *cam, const lt_metric *metric, const 
     else k_prologue_camera<double><<<gq, 256, 0, s>>>(c, mc, (double4 *)ic, n_q);
     HIP_TRY(hipGetLastError());
     if ((rc = tm.mark(1, s))) return rc;
-    rc = o.precision == 32 ? launch_integrate<float>(mc, o, lambda_max, w, n_q, s, d_stats)
-                           : launch_integrate<double>(mc, o, lambda_max, w, n_q, s, d_stats);
+    if (disk)
+        rc = o.precision == 32 ? launch_integrate_disk<float>(mc, o, lambda_max, w, n_q, s, d_stats, *disk)
+                               : launch_integrate_disk<double>(mc, o, lambda_max, w, n_q, s, d_stats, *disk);
+    else
+        rc = o.precision == 32 ? launch_integrate<float>(mc, o, lambda_max, w, n_q, s, d_stats)
+                               : launch_integrate<double>(mc, o, lambda_max, w, n_q, s, d_stats);
     if (rc) return rc;
     if ((rc = tm.mark(2, s))) return rc;
+    if (disk) {
+        if ((rc = launch_epilogue_disk(c, mc, o, w, fo, d_stats, s, *disk))) return rc;
+        if ((rc = tm.mark(3, s))) return rc;
+        tm.finish();
+        return LT_OK;
+    }
     // background tiles staged in LDS when a background is lensed (opts->bg_sampling)
     const bool lds_path = o.bg_sampling == LT_BG_LDS_TILES && d_bg && (d_rgb || d_rgba);
     if (lds_path) {
@@ -877,9 +901,11 @@ static int copy_out(hipStream_t s, const std::vector<OutCopy> &outs)
     return LT_OK;
 }
 
-extern "C" int lt_render(const lt_camera *cam, const lt_metric *metric, const lt_opts *opts, const float *bg,
-                         int32_t bg_channels, float *out_fa, uint16_t *out_w, int8_t *out_status, uint32_t *out_steps,
-                         float *out_rgb, uint8_t *out_rgba, lt_stats *stats)
+// lt_render, and with `disk` lt_render_disk (out_disk: (R, W, 3) float32 host array or NULL)
+static int render_host_impl(const lt_camera *cam, const lt_metric *metric, const lt_opts *opts, const float *bg,
+                            int32_t bg_channels, float *out_fa, uint16_t *out_w, int8_t *out_status, uint32_t *out_steps,
+                            float *out_rgb, uint8_t *out_rgba, lt_stats *stats, const DiskParams *disk = nullptr,
+                            float *out_disk = nullptr)
 {
     int rc = require_device();
     if (rc) return rc;
@@ -904,6 +930,7 @@ extern "C" int lt_render(const lt_camera *cam, const lt_metric *metric, const lt
     size_t o_fa = out_fa ? cv.take(n * 4) : 0, o_w = out_w ? cv.take(n * 2) : 0, o_st = out_status ? cv.take(n) : 0;
     size_t o_steps = out_steps ? cv.take(n * 4) : 0, o_rgb = out_rgb ? cv.take(n * nch * 4) : 0;
     size_t o_rgba = out_rgba ? cv.take(n * 4) : 0;
+    size_t o_disk = (disk && out_disk) ? cv.take(n * 3 * 4) : 0;
     if ((rc = grow(sl->dev, cv.off, s))) return rc;
     char *base = (char *)sl->dev.p;
     auto at = [&](bool want, size_t off) -> void * { return want ? (void *)(base + off) : nullptr; };
@@ -911,10 +938,12 @@ extern "C" int lt_render(const lt_camera *cam, const lt_metric *metric, const lt
     HIP_TRY(hipMemsetAsync(base + o_stats, 0, LT_STAT_WORDS * 8, s));
     if ((rc = slot_events(sl))) return rc;
     o.timing = 0; // private events: concurrent lt_render_dev(timing = 1) callers keep theirs
+    DiskParams dp{};
+    if (disk) { dp = *disk; dp.d_disk = (float *)at(out_disk != nullptr, o_disk); }
     rc = render_dev_impl(cam, metric, &o, (const float *)at(bg != nullptr, o_bg), bg_channels, (float *)at(out_fa, o_fa),
                          (uint16_t *)at(out_w, o_w), (int8_t *)at(out_status, o_st), (uint32_t *)at(out_steps, o_steps),
                          (float *)at(out_rgb, o_rgb), (uint8_t *)at(out_rgba, o_rgba), (uint64_t *)(base + o_stats),
-                         &sl->own);
+                         &sl->own, disk ? &dp : nullptr);
     if (rc) return rc;
     lt_stats st;
     memset(&st, 0, sizeof(st));
@@ -926,6 +955,7 @@ extern "C" int lt_render(const lt_camera *cam, const lt_metric *metric, const lt
     if (out_status) outs.push_back({out_status, base + o_st, n});
     if (out_steps) outs.push_back({out_steps, base + o_steps, n * 4});
     if (out_rgb) outs.push_back({out_rgb, base + o_rgb, n * nch * 4});
+    if (disk && out_disk) outs.push_back({out_disk, base + o_disk, n * 3 * 4});
     if ((rc = copy_out(s, outs))) return rc;
     HIP_TRY(hipMemcpyAsync(st.counters, base + o_stats, LT_STAT_WORDS * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -936,6 +966,13 @@ extern "C" int lt_render(const lt_camera *cam, const lt_metric *metric, const lt
     }
     if (stats) *stats = st;
     return LT_OK;
+}
+
+extern "C" int lt_render(const lt_camera *cam, const lt_metric *metric, const lt_opts *opts, const float *bg,
+                         int32_t bg_channels, float *out_fa, uint16_t *out_w, int8_t *out_status, uint32_t *out_steps,
+                         float *out_rgb, uint8_t *out_rgba, lt_stats *stats)
+{
+    return render_host_impl(cam, metric, opts, bg, bg_channels, out_fa, out_w, out_status, out_steps, out_rgb, out_rgba, stats);
 }
 
 // ---- one frame on several devices from one process ----------------------------------------------
@@ -1069,9 +1106,10 @@ extern "C" int lt_render_multi(const lt_camera *cam, const lt_metric *metric, co
 // ---------------------------------------------------------------------------------------------
 // array-in / array-out twins
 // ---------------------------------------------------------------------------------------------
+// disk != NULL: lt_trace_batch_kerr_disk (out_disk (n, 3) float64 or NULL)
 static int trace_batch(const MetricConsts &mc, lt_opts &o, double lambda_max, const double *alphas, const double *thetas,
                        const uint8_t *refines, int64_t n, double *out_fa, int64_t *out_w, int8_t *out_status,
-                       uint32_t *out_evals)
+                       uint32_t *out_evals, const DiskParams *disk = nullptr, double *out_disk = nullptr)
 {
     int rc;
     if (n < 0) return fail(LT_ERR_INVALID_ARG, "negative ray count");
@@ -1092,6 +1130,7 @@ static int trace_batch(const MetricConsts &mc, lt_opts &o, double lambda_max, co
     Carver cv;
     size_t o_al = cv.take(n * 8), o_th = thetas ? cv.take(n * 8) : 0, o_ref = refines ? cv.take(n) : 0;
     size_t o_fa = cv.take(n * 8), o_w = cv.take(n * 8), o_st = out_status ? cv.take(n) : 0, o_ev = out_evals ? cv.take(n * 4) : 0;
+    size_t o_disk = (disk && out_disk) ? cv.take(n * 3 * 8) : 0;
     if ((rc = grow(sl->dev, cv.off, s))) return rc;
     char *base = (char *)sl->dev.p;
     const double *d_al = (const double *)(base + o_al);
@@ -1101,6 +1140,7 @@ static int trace_batch(const MetricConsts &mc, lt_opts &o, double lambda_max, co
     int64_t *d_w = (int64_t *)(base + o_w);
     int8_t *d_st = out_status ? (int8_t *)(base + o_st) : nullptr;
     uint32_t *d_ev = out_evals ? (uint32_t *)(base + o_ev) : nullptr;
+    double *d_disk = (disk && out_disk) ? (double *)(base + o_disk) : nullptr;
     HIP_TRY(hipMemcpyAsync((void *)d_al, alphas, n * 8, hipMemcpyHostToDevice, s));
     if (thetas) HIP_TRY(hipMemcpyAsync((void *)d_th, thetas, n * 8, hipMemcpyHostToDevice, s));
     if (refines) HIP_TRY(hipMemcpyAsync((void *)d_ref, refines, n, hipMemcpyHostToDevice, s));
@@ -1108,11 +1148,21 @@ static int trace_batch(const MetricConsts &mc, lt_opts &o, double lambda_max, co
     if (o.precision == 32) k_prologue_arrays<float><<<gq, 256, 0, s>>>(mc, d_al, d_th, d_ref, n, (float4 *)ic, n_q);
     else k_prologue_arrays<double><<<gq, 256, 0, s>>>(mc, d_al, d_th, d_ref, n, (double4 *)ic, n_q);
     HIP_TRY(hipGetLastError());
-    rc = o.precision == 32 ? launch_integrate<float>(mc, o, lambda_max, w, n_q, s, nullptr)
-                           : launch_integrate<double>(mc, o, lambda_max, w, n_q, s, nullptr);
+    if (disk)
+        rc = o.precision == 32 ? launch_integrate_disk<float>(mc, o, lambda_max, w, n_q, s, nullptr, *disk)
+                               : launch_integrate_disk<double>(mc, o, lambda_max, w, n_q, s, nullptr, *disk);
+    else
+        rc = o.precision == 32 ? launch_integrate<float>(mc, o, lambda_max, w, n_q, s, nullptr)
+                               : launch_integrate<double>(mc, o, lambda_max, w, n_q, s, nullptr);
     if (rc) return rc;
     unsigned gn = (unsigned)((n + 255) / 256);
-    if (o.precision == 32)
+    if (disk) {
+        const DiskShade ds{mc.M, mc.a, disk->r_in, disk->q, disk->exposure};
+        if (o.precision == 32)
+            k_epilogue_arrays_disk<float><<<gn, 256, 0, s>>>(mc, ds, (const float4 *)fin0, (const float4 *)fin1, n, d_fa, d_w, d_st, d_disk, d_ev);
+        else
+            k_epilogue_arrays_disk<double><<<gn, 256, 0, s>>>(mc, ds, (const double4 *)fin0, (const double4 *)fin1, n, d_fa, d_w, d_st, d_disk, d_ev);
+    } else if (o.precision == 32)
         k_epilogue_arrays<float><<<gn, 256, 0, s>>>(mc, (const float4 *)fin0, (const float4 *)fin1, n, d_fa, d_w, d_st, d_ev);
     else
         k_epilogue_arrays<double><<<gn, 256, 0, s>>>(mc, (const double4 *)fin0, (const double4 *)fin1, n, d_fa, d_w, d_st, d_ev);
@@ -1121,6 +1171,7 @@ static int trace_batch(const MetricConsts &mc, lt_opts &o, double lambda_max, co
     HIP_TRY(hipMemcpyAsync(out_w, d_w, n * 8, hipMemcpyDeviceToHost, s));
     if (out_status) HIP_TRY(hipMemcpyAsync(out_status, d_st, n, hipMemcpyDeviceToHost, s));
     if (out_evals) HIP_TRY(hipMemcpyAsync(out_evals, d_ev, n * 4, hipMemcpyDeviceToHost, s));
+    if (d_disk) HIP_TRY(hipMemcpyAsync(out_disk, d_disk, n * 3 * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return LT_OK;
 }
@@ -1390,3 +1441,4 @@ extern "C" int lt_piece_probe(int piece, int waves_per_simd, int iters, double *
 
 #include "lt_api_stages.inc"
 #include "lt_api_dense.inc"
+#include "lt_api_disk.inc"

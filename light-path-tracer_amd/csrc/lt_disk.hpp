@@ -1,0 +1,420 @@
+// lt_disk.hpp -- the thin Keplerian accretion disk of lt_render_disk (include/ltrace.h): the disk variant of the direct
+// integrate kernel (K2) and its epilogue (K3).  K1 is the frame path's prologue, unchanged.
+//
+// The disk lies in the equatorial plane between r_in and r_out.  A ray (traced backward from the camera) hits it at the
+// first strict sign change of theta - pi/2 between two consecutive accepted states whose crossing point has
+// r_in <= r <= r_out; crossings outside the annulus do not stop it.  The crossing point is found on the cubic Hermite
+// interpolant of the step in lambda, with the derivatives from the Kerr right-hand side at both ends (two extra
+// evaluations, once per hit ray), and replaces the ray's final state; the event is EV_DISK.
+//
+// Nothing here changes a step: the disk kernel calls the integrators' own advance() and streak(), and only looks at the
+// states they produce.  A lane's arithmetic never depends on which rays share its wavefront (lt_device.hpp), so a ray
+// that misses the disk ends with the same bits as in k_kerr_direct, and its pixel is the frame path's pixel.
+// Disk parameters travel as a kernel argument of their own (DiskConsts): KerrConsts and the existing kernels are untouched.
+#pragma once
+#include "lt_kernels.hpp"
+
+namespace lt {
+
+enum : int { EV_DISK = 5 };
+constexpr int STATUS_DISK = 2; // LT_STATUS_DISK
+
+template <typename T> struct DiskConsts {
+    T r_in, r_out;
+    T inv_rp2; // 1 / r_plus^2: bound on the radial speed, disk_vmax
+};
+
+// Upper bound on |dr/dlambda| of the ray anywhere outside the horizon.  With E = 1, Sigma^2 (dr/dlambda)^2 = R(r) =
+// P^2 - Delta K with K >= 0 (Carter) and Delta > 0, so |dr/dlambda| <= |P| / Sigma <= (r^2 + a^2 + |a L|) / r^2
+// <= 1 + (a^2 + |a L|) / r_plus^2.  Per ray (it depends on L); the callers double it for the drift off the null shell.
+template <typename T> __device__ __forceinline__ T disk_vmax(const KerrConsts<T> &k, const DiskConsts<T> &d, const RayConsts<T> &rc)
+{
+    return M<T>::fma(M<T>::fma(M<T>::abs(k.a), M<T>::abs(rc.L), k.a2), d.inv_rp2, T(1));
+}
+
+// The step length of the attempt advance() is about to make, per integrator (the same value advance() computes; needed
+// only on a lane that crossed the plane) and an upper bound on it.
+template <typename Integ> struct DiskStepLen;
+template <typename T> struct DiskStepLen<Rk4<T>> {
+    static __device__ __forceinline__ T h(const KerrConsts<T> &k, const RayConsts<T> &rc, const RayState<T> &s)
+    {
+        T h = kerr_rk4_h(k, rc, s.y.r, k.lambda_max - s.lam);
+        return s.h_retry > T(0) ? s.h_retry : h;
+    }
+    static __device__ __forceinline__ T bound(const RayConsts<T> &rc, const RayState<T> &) { return rc.hb; }
+};
+template <typename T, bool E> struct DiskStepLen<Dp45<T, E>> {
+    static __device__ __forceinline__ T h(const KerrConsts<T> &k, const RayConsts<T> &, const Dp45State<T> &s)
+    {
+        return M<T>::min(s.h, k.lambda_max - s.lam);
+    }
+    static __device__ __forceinline__ T bound(const RayConsts<T> &, const Dp45State<T> &s) { return s.h; }
+};
+
+// Cubic Hermite on the step [0, 1] (lambda = lam0 + t h): value and d/dt from the end values and h * derivatives.
+template <typename T> __device__ __forceinline__ T hermite(T y0, T hd0, T y1, T hd1, T t)
+{
+    const T t2 = t * t, t3 = t2 * t;
+    const T h01 = M<T>::fma(T(-2), t3, T(3) * t2), h10 = t3 - T(2) * t2 + t, h11 = t3 - t2;
+    return y0 + h01 * (y1 - y0) + h10 * hd0 + h11 * hd1; // h00 y0 + h01 y1 with h00 = 1 - h01
+}
+template <typename T> __device__ __forceinline__ T hermite_dt(T y0, T hd0, T y1, T hd1, T t)
+{
+    const T t2 = t * t;
+    return (T(6) * t - T(6) * t2) * (y1 - y0) + (T(3) * t2 - T(4) * t + T(1)) * hd0 + (T(3) * t2 - T(2) * t) * hd1;
+}
+
+// The crossing of the plane on the step y0 -> y1 of length h, searched on [0, t_end] (t_end < 1: the step was cut at a
+// capture / escape radius, the ray ended at t_end).  True, and the crossing state in `hit`, if the crossing point lies
+// in the annulus.  Per lane; runs only on lanes whose states straddle the plane near the annulus.
+template <typename T>
+__device__ __forceinline__ bool disk_crossing(const KerrConsts<T> &k, const DiskConsts<T> &d, const RayConsts<T> &rc,
+                                           const State5<T> &y0, const State5<T> &y1, T h, T t_end, State5<T> &hit)
+{
+    const T HALF_PI = T(1.5707963267948966);
+    T f0[5], f1[5];
+    kerr_rhs(k, rc, y0.r, y0.th, y0.pr, y0.pth, f0[0], f0[1], f0[2], f0[3], f0[4]);
+    kerr_rhs(k, rc, y1.r, y1.th, y1.pr, y1.pth, f1[0], f1[1], f1[2], f1[3], f1[4]);
+    for (int i = 0; i < 5; ++i) { f0[i] *= h; f1[i] *= h; }
+    auto g = [&](T t) { return hermite(y0.th, f0[1], y1.th, f1[1], t) - HALF_PI; };
+    T lo = T(0), hi = t_end;
+    T glo = y0.th - HALF_PI, ghi = g(hi);
+    if (!((glo < T(0) && ghi >= T(0)) || (glo > T(0) && ghi <= T(0)))) return false; // the cubic does not cross on [0, t_end]
+    // Newton from the chord's root, kept inside the bracket (bisection where a Newton step leaves it)
+    T t = ghi == T(0) ? hi : lo + (hi - lo) * (glo / (glo - ghi));
+    for (int it = 0; it < 12; ++it) {
+        const T gt = g(t);
+        if (gt == T(0)) break;
+        if ((gt < T(0)) == (glo < T(0))) { lo = t; glo = gt; } else { hi = t; }
+        const T dg = hermite_dt(y0.th, f0[1], y1.th, f1[1], t);
+        T tn = t - gt / dg;
+        if (!(tn > lo && tn < hi)) tn = T(0.5) * (lo + hi);
+        if (M<T>::abs(tn - t) <= T(sizeof(T) == 4 ? 4.8e-7 : 8.9e-16)) { t = tn; break; }
+        t = tn;
+    }
+    hit.r = hermite(y0.r, f0[0], y1.r, f1[0], t);
+    hit.th = HALF_PI;
+    hit.ph = hermite(y0.ph, f0[2], y1.ph, f1[2], t);
+    hit.pr = hermite(y0.pr, f0[3], y1.pr, f1[3], t);
+    hit.pth = hermite(y0.pth, f0[4], y1.pth, f1[4], t);
+    return (hit.r >= d.r_in) & (hit.r <= d.r_out);
+}
+
+// One iteration of Integ with the disk test behind it.  The common path adds a sign test of theta - pi/2 on both states,
+// a min / max of their radii against the annulus widened by the largest radial move of the step, and ONE wave-uniform
+// branch.  `vmax2`: twice disk_vmax of the ray.
+template <typename T, typename Integ>
+__device__ __forceinline__ int disk_advance(const KerrConsts<T> &k, const DiskConsts<T> &d, const RayConsts<T> &rc,
+                                            T vmax2, typename Integ::State &s)
+{
+    const T HALF_PI = T(1.5707963267948966);
+    const typename Integ::State before = s;
+    int ev = Integ::advance(k, rc, s);
+    const T z0 = before.y.th - HALF_PI, z1 = s.y.th - HALF_PI;
+    // (a state that did not move -- retry, range end, failure -- has z1 == z0: no sign change)
+    const bool cross = ((z0 < T(0)) & (z1 >= T(0))) | ((z0 > T(0)) & (z1 <= T(0)));
+    // the crossing point of a step lies within (step length) x (largest radial speed) of both ends
+    const T pad = DiskStepLen<Integ>::bound(rc, before) * vmax2;
+    const bool near = (M<T>::min(before.y.r, s.y.r) <= d.r_out + pad) & (M<T>::max(before.y.r, s.y.r) >= d.r_in - pad);
+    const bool cand = cross & near;
+    if (__builtin_expect(wave_any(cand), 0)) {
+        if (cand) {
+            const T h = DiskStepLen<Integ>::h(k, rc, before);
+            State5<T> y1 = s.y, hit;
+            T t_end = T(1);
+            if (ev == EV_CAPTURED || ev == EV_ESCAPED) {
+                // the integrator ended the ray on the chord of this step at the capture / escape radius: retake the full
+                // step (for RK4 the same step; for DP45 an RK4 step of the same length stands in, near enough to place a
+                // crossing that in practice never happens there: r_in >= r_isco lies well outside 1.01 r_plus) and search
+                // up to the chord fraction the ray ended at
+                y1 = kerr_rk4_step(k, rc, before.y, h);
+                const T target = ev == EV_CAPTURED ? k.r_capture : k.r_escape;
+                const T denom = y1.r - before.y.r;
+                t_end = denom == T(0) ? T(1) : M<T>::min(M<T>::max((target - before.y.r) / denom, T(0)), T(1));
+            }
+            if (disk_crossing(k, d, rc, before.y, y1, h, t_end, hit)) {
+                s.y = hit;
+                ev = EV_DISK;
+            }
+        }
+    }
+    return ev;
+}
+
+// Direct schedule with the disk: k_kerr_direct's tile loop, persistent tile queue and ghost-lane phase, line for line,
+// with Integ::advance replaced by disk_advance and the far-field streak gated (below).  (A separate kernel rather than a
+// template parameter of k_kerr_direct: that kernel's code and name stay exactly what they were.)
+//
+// The streak gate.  kerr_rk4_streak takes up to 64 steps with no test but r >= rc4 at the end of each; here it runs with
+// rc4 raised, per lane, to r_gate = r_out + 2 h_base vmax2.  Every step it takes then starts and ends at r >= r_gate,
+// and within one step of length h_base the ray (and the Hermite cubic of the step, whose excursion beyond its ends is
+// at most 0.15 h (|r'_0| + |r'_1|)) stays within h_base vmax2 of either end: above r_out, so no streak step can hold a
+// hit.  Wherever the gate fails the ray steps through disk_advance.  The streak's steps are the general iteration's
+// arithmetic (lt_device.hpp), so the gate changes no bit of any state.
+template <typename T, typename Integ>
+__global__ void __launch_bounds__(256, Integ::MIN_WAVES_PER_SIMD) k_kerr_disk(KerrConsts<T> k_in, DiskConsts<T> d,
+                                                       const typename Vec4<T>::type *__restrict__ ic,
+                                                       typename Vec4<T>::type *__restrict__ fin0,
+                                                       typename Vec4<T>::type *__restrict__ fin1, int64_t n_q,
+                                                       uint32_t long_iters, uint64_t *__restrict__ kstats,
+                                                       unsigned long long *__restrict__ head)
+{
+    KerrConsts<T> k = k_in;
+    pin_consts(k);
+    const int lane = (int)(threadIdx.x & 63u);
+    int64_t tile = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    for (;;) {
+    if (head) {
+        unsigned long long w = 0;
+        if (lane == 0) w = atomicAdd(head, 1ull);
+        tile = (int64_t)(((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(w >> 32)) << 32) |
+                         (uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)w));
+    }
+    const int64_t q = tile * 64 + lane;
+    if (q >= n_q) return;
+    WaveMeter meter;
+    meter.begin(kstats, tile);
+    typename Vec4<T>::type rec = ic[q];
+    int flags = (int)rec.w;
+    typename Integ::State st;
+    st.y.r = k.r_obs; st.y.th = k.theta_obs; st.y.ph = T(0); st.y.pr = rec.x; st.y.pth = rec.y;
+    st.steps = 0;
+    int ev = (flags & FLAG_PAD) ? EV_PAD : EV_INVALID;
+    uint32_t wave_iters = 0;
+    bool raised = false;
+    RayConsts<T> rc = make_ray_consts(k, rec.z, (flags & FLAG_REFINE) != 0);
+    T vmax2 = T(2) * disk_vmax(k, d, rc);
+    KerrConsts<T> kg = k; // the streak's constants: rc4 raised to the gate radius
+    kg.rc4 = M<T>::max(k.rc4, M<T>::fma(T(2) * rc.hb, vmax2, d.r_out));
+    if (flags & FLAG_OK) {
+        Integ::start(k, rc, st, rec.x, rec.y);
+        uint32_t it = 0;
+        do {
+            it += Integ::streak(kg, rc, st, 64u);
+            ev = disk_advance<T, Integ>(k, d, rc, vmax2, st);
+            ++it;
+            if (Integ::GHOST_LANES) {
+                if (it >= long_iters) break;
+            } else if (it >= long_iters && !raised) {
+                __builtin_amdgcn_s_setprio(3);
+                raised = true;
+            }
+        } while (ev == EV_RUNNING);
+        wave_iters = it;
+    }
+    uint32_t steps = st.steps;
+    bool real = ev == EV_RUNNING;
+    if (Integ::GHOST_LANES && wave_any(real)) {
+        __builtin_amdgcn_s_setprio(3);
+        raised = true;
+        if (!real) store_fin<T>(fin0, fin1, q, st.y.r, st.y.th, st.y.ph, st.y.pr, st.y.pth, rec.z, ev, steps);
+        uint32_t lead = (uint32_t)__builtin_ctzll(__builtin_amdgcn_ballot_w64(real));
+        uint32_t it = (uint32_t)__builtin_amdgcn_readlane((int)wave_iters, (int)lead);
+        bool sync = true;
+        for (;;) {
+            if (sync) {
+                lead = (uint32_t)__builtin_ctzll(__builtin_amdgcn_ballot_w64(real));
+                take_from_lane(st, lead, !real);
+                take_from_lane(rc, lead, !real);
+                vmax2 = T(2) * disk_vmax(k, d, rc);
+                kg.rc4 = M<T>::max(k.rc4, M<T>::fma(T(2) * rc.hb, vmax2, d.r_out));
+                sync = false;
+            }
+            it += Integ::streak_lone(kg, rc, st, 64u);
+            int e = disk_advance<T, Integ>(k, d, rc, vmax2, st);
+            ++it;
+            if (wave_any(e != EV_RUNNING)) {
+                if (real & (e != EV_RUNNING)) {
+                    steps = st.steps;
+                    store_fin<T>(fin0, fin1, q, st.y.r, st.y.th, st.y.ph, st.y.pr, st.y.pth, rec.z, e, steps);
+                    real = false;
+                }
+                if (!wave_any(real)) break;
+                sync = true;
+            }
+        }
+        wave_iters = it;
+    } else {
+        store_fin<T>(fin0, fin1, q, st.y.r, st.y.th, st.y.ph, st.y.pr, st.y.pth, rec.z, ev, steps);
+    }
+    meter.end(kstats, wave_iters);
+    if (!head) return;
+    if (__builtin_amdgcn_ballot_w64(raised)) __builtin_amdgcn_s_setprio(0);
+    }
+}
+
+// ---- K3 ---------------------------------------------------------------------------------------------------------------
+// Shading constants of the disk (float64; r_in is the resolved inner edge).
+struct DiskShade {
+    double M, a, r_in, q, exposure;
+};
+
+// g = nu_obs / nu_em = 1 / (u^t (1 - Omega xi)) for the circular equatorial geodesic at r orbiting in +phi:
+// Omega = sqrt(M) / (r^1.5 + a sqrt(M)), u^t = (r^1.5 + a sqrt(M)) / (r^0.75 sqrt(r^1.5 - 3 M r^0.5 + 2 a sqrt(M))).
+__device__ __forceinline__ double disk_redshift(double M_, double a, double r, double xi)
+{
+    const double sM = sqrt(M_), sr = sqrt(r), r15 = r * sr;
+    const double num = r15 + a * sM;
+    const double omega = sM / num;
+    const double ut = num / (sqrt(r15) * sqrt(r15 - 3.0 * M_ * sr + 2.0 * a * sM));
+    return 1.0 / (ut * (1.0 - omega * xi));
+}
+
+// I = exposure g^4 (r_in / r)^q, s = g (r_in / r)^(3/4), rgb = clamp(I ramp(s), 0, 1),
+// ramp(s) = (clamp(2s, 0, 1), clamp(2s - 0.5, 0, 1), clamp(2s - 1, 0, 1)); one channel: the mean of the three.
+// Evaluated from the float32 values the caller gets in d_disk, so that the colour is a function of what is stored.
+__device__ __forceinline__ void disk_shade(const DiskShade &ds, float r32, float g32, int nch, float *rgb)
+{
+    const double r = (double)r32, g = (double)g32;
+    const double x = ds.r_in / r, g2 = g * g;
+    const double I = ds.exposure * (g2 * g2) * pow(x, ds.q);
+    const double s = g * pow(x, 0.75);
+    double c[3];
+    for (int i = 0; i < 3; ++i) {
+        const double ramp = fmin(fmax(2.0 * s - 0.5 * i, 0.0), 1.0);
+        c[i] = fmin(fmax(I * ramp, 0.0), 1.0);
+    }
+    if (nch == 1) rgb[0] = (float)((c[0] + c[1] + c[2]) / 3.0);
+    else { rgb[0] = (float)c[0]; rgb[1] = (float)c[1]; rgb[2] = (float)c[2]; }
+}
+
+// phi wrapped to [0, 2 pi)
+__device__ __forceinline__ double wrap_2pi(double ph)
+{
+    const double TWO_PI = 6.283185307179586;
+    double w = ph - TWO_PI * floor(ph * (1.0 / TWO_PI));
+    return (w >= TWO_PI || w < 0.0) ? 0.0 : w;
+}
+
+// Counters of the disk epilogue: the frame path's six plus the disk rays, in word 6 of the workgroup's partial set
+// (k_stats_reduce_disk moves it to LT_STAT_DISK).
+__device__ __forceinline__ void flush_stats_disk(uint64_t *stats, const StatAcc &a, bool disk, const MetricConsts &m)
+{
+    if (!stats) return;
+    __shared__ unsigned long long sh[7];
+    if (threadIdx.x < 7) sh[threadIdx.x] = 0;
+    __syncthreads();
+    uint32_t st = a.counted ? a.steps : 0u;
+    for (int off = 32; off > 0; off >>= 1) st += __shfl_xor(st, off, 64);
+    const unsigned long long rays = (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(a.counted));
+    const unsigned long long v[7] = {rays, st, rays * (unsigned long long)m.evals_fixed + (unsigned long long)st * (unsigned long long)m.evals_per_step,
+                                     (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(a.esc)),
+                                     (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(a.cap)),
+                                     (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(a.inv)),
+                                     (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(disk))};
+    if ((threadIdx.x & 63) == 0)
+        for (int i = 0; i < 7; ++i) if (v[i]) atomicAdd(&sh[i], v[i]);
+    __syncthreads();
+    unsigned long long *set = (unsigned long long *)stats + (size_t)((blockIdx.x + blockIdx.y * gridDim.x) % STAT_SLOTS) * 8;
+    if (threadIdx.x < 7 && sh[threadIdx.x]) atomicAdd(&set[threadIdx.x], sh[threadIdx.x]);
+}
+
+#ifndef LT_KERNEL_TEMPLATES_ONLY
+// k_stats_reduce with word 6 going to LT_STAT_DISK
+__global__ void __launch_bounds__(STAT_SLOTS) k_stats_reduce_disk(unsigned long long *__restrict__ partials,
+                                                                  unsigned long long *__restrict__ stats)
+{
+    unsigned long long *set = partials + (size_t)threadIdx.x * 8;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        unsigned long long v = wave_sum(set[i]);
+        set[i] = 0;
+        const int dst = i < 6 ? i : (i == 6 ? 12 : 11);
+        if (threadIdx.x == 0 && v) atomicAdd(&stats[dst], v);
+    }
+}
+#endif
+
+// One pixel per work-item, as k_epilogue_frame (global-gather background sampling).  EV_DISK records get the redshift
+// and the disk colour; every other record goes through load_result / shade exactly as there.  disk_out (R, W, 3) float32
+// (r_hit, phi_hit in [0, 2 pi), g), NaN where the ray missed the disk; may be NULL.
+template <typename T, bool HAS_BG>
+__global__ void __launch_bounds__(EPILOGUE_BLOCK) k_epilogue_disk(CamConsts c, MetricConsts m, DiskShade ds,
+                                                                  const typename Vec4<T>::type *__restrict__ fin0,
+                                                                  const typename Vec4<T>::type *__restrict__ fin1, FrameOut o,
+                                                                  float *__restrict__ disk_out)
+{
+    const int lrow = (int)blockIdx.y, ix = (int)(blockIdx.x * EPILOGUE_BLOCK + threadIdx.x);
+    const int64_t p = (int64_t)lrow * c.W + ix;
+    StatAcc acc;
+    bool on_disk = false;
+    if (ix < c.W) {
+        const int64_t q = pixel_to_q(c, ix, lrow);
+        const typename Vec4<T>::type v0 = fin0[q], v1 = fin1[q];
+        RayResult res;
+        float rgb[3];
+        int nch = (HAS_BG && o.bg) ? o.bg_c : 3;
+        float d3[3] = {__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf("")};
+        long long wl;
+        if ((int)v1.z == EV_DISK) {
+            on_disk = true;
+            const double ph = (double)v0.z;
+            res.status = STATUS_DISK;
+            res.fa = __builtin_nan("");
+            res.n_half = half_orbits(ph);
+            res.steps = (uint32_t)v1.w;
+            d3[0] = (float)v0.x;
+            d3[1] = (float)wrap_2pi(ph);
+            d3[2] = (float)disk_redshift(ds.M, ds.a, (double)v0.x, (double)v1.y);
+            disk_shade(ds, d3[0], d3[2], nch, rgb);
+        } else {
+            load_result<T>(m, fin0, fin1, q, res);
+        }
+        acc.add(res);
+        const float fa32 = (res.status == 1) ? (float)res.fa : __builtin_nanf("");
+        wl = res.n_half < 0 ? 0 : (res.n_half > 65535 ? 65535 : res.n_half);
+        if (o.fa) o.fa[p] = fa32;
+        if (o.w) o.w[p] = (uint16_t)wl;
+        if (o.status) o.status[p] = (int8_t)res.status;
+        if (o.steps) o.steps[p] = res.steps;
+        if (disk_out) { disk_out[p * 3] = d3[0]; disk_out[p * 3 + 1] = d3[1]; disk_out[p * 3 + 2] = d3[2]; }
+        if (o.rgb || o.rgba) {
+            if (!on_disk) shade<HAS_BG>(c, o, ix, local_to_global_row(c, lrow), fa32, (int)wl, rgb, nch);
+            if (o.rgb) for (int ch = 0; ch < nch; ++ch) o.rgb[p * nch + ch] = rgb[ch];
+            if (o.rgba) {
+                uchar4 px;
+                px.x = (uint8_t)(rgb[0] * 255.0f);
+                px.y = (uint8_t)(rgb[nch == 1 ? 0 : 1] * 255.0f);
+                px.z = (uint8_t)(rgb[nch == 1 ? 0 : 2] * 255.0f);
+                px.w = 255;
+                reinterpret_cast<uchar4 *>(o.rgba)[p] = px;
+            }
+        }
+    }
+    flush_stats_disk(o.stats, acc, on_disk, m);
+}
+
+// Epilogue of lt_trace_batch_kerr_disk: k_epilogue_arrays plus out_disk (n, 3) float64 (r_hit, phi_hit, g), NaN off the disk.
+template <typename T>
+__global__ void __launch_bounds__(256) k_epilogue_arrays_disk(MetricConsts m, DiskShade ds, const typename Vec4<T>::type *__restrict__ fin0,
+                                                              const typename Vec4<T>::type *__restrict__ fin1, int64_t n,
+                                                              double *__restrict__ out_fa, int64_t *__restrict__ out_w,
+                                                              int8_t *__restrict__ out_status, double *__restrict__ out_disk,
+                                                              uint32_t *__restrict__ out_evals)
+{
+    int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (q >= n) return;
+    const typename Vec4<T>::type v0 = fin0[q], v1 = fin1[q];
+    RayResult res;
+    const double NaN = __builtin_nan("");
+    double d3[3] = {NaN, NaN, NaN};
+    if ((int)v1.z == EV_DISK) {
+        res.status = STATUS_DISK;
+        res.fa = NaN;
+        res.n_half = half_orbits((double)v0.z);
+        res.steps = (uint32_t)v1.w;
+        res.evals = (uint32_t)m.evals_fixed + res.steps * (uint32_t)m.evals_per_step;
+        d3[0] = (double)v0.x;
+        d3[1] = wrap_2pi((double)v0.z);
+        d3[2] = disk_redshift(ds.M, ds.a, (double)v0.x, (double)v1.y);
+    } else {
+        load_result<T>(m, fin0, fin1, q, res);
+    }
+    out_fa[q] = (res.status == 1) ? res.fa : NaN;
+    out_w[q] = res.n_half;
+    if (out_status) out_status[q] = (int8_t)res.status;
+    if (out_disk) { out_disk[q * 3] = d3[0]; out_disk[q * 3 + 1] = d3[1]; out_disk[q * 3 + 2] = d3[2]; }
+    if (out_evals) out_evals[q] = res.evals;
+}
+
+} // namespace lt

@@ -210,11 +210,13 @@ def render_lensed_image(source_image, alpha_lookup, final_alpha_lookup, winding_
 
 def render_frame(source_image, metric, r_obs, fov, psi=(0.0, 0.0), theta_obs=np.pi / 2, integrator=None,
                  precision=None, schedule=None, tb_symmetry=False, render_loop_around=False,
-                 want=("fa", "winding", "rgb"), gpus=1, devices=None):
+                 want=("fa", "winding", "rgb"), gpus=1, devices=None, disk=None):
     """Fused path (lt_render): all three stages in one GPU call.  source_image None -> shadow render
     (escaped = white).  Returns dict with 'fa', 'winding', 'rgb', ... and 'stats'.
     gpus > 1: the frame's rows are split block-cyclically over that many devices of this node
-    (lt_render_multi; the reference's top/bottom mirror needs the whole frame on one device)."""
+    (lt_render_multi; the reference's top/bottom mirror needs the whole frame on one device).
+    disk: a thin accretion disk (disk.ThinDisk or ltrace.Disk) -> lt_render_disk on one GPU, every row traced, plus
+    'disk' (H, W, 3) (r_hit, phi_hit, g); a spherically symmetric metric is traced as Kerr with a = 0."""
     if source_image is None:
         raise ValueError("render_frame needs a background; for a shadow use black_hole_shadow.render_traced")
     source_image = np.asarray(source_image)
@@ -224,7 +226,7 @@ def render_frame(source_image, metric, r_obs, fov, psi=(0.0, 0.0), theta_obs=np.
         # the colour planes are what is lensed here
         source_image = source_image[..., :3]
     shape = source_image.shape[:2]
-    kerr = not metric.is_spherically_symmetric
+    kerr = not metric.is_spherically_symmetric or disk is not None
     met = ltrace.Metric(ltrace.METRIC_KERR if kerr else ltrace.METRIC_SCHWARZSCHILD, 0, float(metric.M),
                         float(getattr(metric, "a", 0.0)))
     opts = ltrace.default_opts(
@@ -234,6 +236,11 @@ def render_frame(source_image, metric, r_obs, fov, psi=(0.0, 0.0), theta_obs=np.
         tb_symmetry=int(bool(tb_symmetry)), loop_around=int(bool(render_loop_around)),
         axis_refine_frac=Y_AXIS_REFINE_FRAC)
     cam = _camera(shape, fov, psi, r_obs, theta_obs)
+    if disk is not None:
+        if gpus and gpus > 1:
+            raise ValueError("the accretion disk renders on one GPU (gpus == 1)")
+        d = disk.to_lt() if hasattr(disk, "to_lt") else disk
+        return ltrace.render_disk(cam, met, opts, d, background=source_image, want=tuple(want) + ("disk",))
     if gpus and gpus > 1:
         if tb_symmetry:
             raise ValueError("tb_symmetry (the reference's top/bottom mirror) needs gpus == 1")
@@ -325,11 +332,13 @@ def save_lookup_cache(path, key, final_alpha, winding):
 def main(metric=None, M=1.0, a=0.0, r_obs_mult=100.0, psi=(0.0, 0.0), vertical_fov_deg=40.0,
          image_path="image.jpg", output_path="lensed_image.png", synthetic=None, staged=False,
          integrator=None, precision=None, schedule=None, gpus=1, full_trace=False, dedup_alpha=False,
-         lookup_cache=None):
+         lookup_cache=None, theta_obs_deg=90.0, disk=None):
     """`lookup_cache`: path of an .npz (the reference's .gitignore names `lookup_cache.npz`, it never wrote one): the
     final_alpha / winding lookups of this metric, observer and camera are stored there and reused by the next call with
     the same settings -- a new background then costs one colouring pass (lt_shade) instead of a trace.
-    `dedup_alpha`: staged path, spherically symmetric metrics: trace distinct alphas only (precompute_final_alpha_lookup)."""
+    `dedup_alpha`: staged path, spherically symmetric metrics: trace distinct alphas only (precompute_final_alpha_lookup).
+    `theta_obs_deg`: the observer's inclination (fused path; 90 = equatorial, as the reference).  `disk`: a thin
+    accretion disk (disk.ThinDisk) in the picture (fused path, one GPU, every row traced)."""
     import matplotlib.image as mpimg
 
     if metric is None:
@@ -363,8 +372,11 @@ def main(metric=None, M=1.0, a=0.0, r_obs_mult=100.0, psi=(0.0, 0.0), vertical_f
              "inside FOV" if abs(bh_y) <= np.tan(fov[1] / 2) and abs(bh_x) <= np.tan(fov[0] / 2) else "outside FOV")
     print(f"BH screen offset: psi_y={np.degrees(psi[0]):.4f} deg, psi_x={np.degrees(psi[1]):.4f} deg ({where})")
 
+    theta_obs = np.radians(theta_obs_deg)
+    if (disk is not None or theta_obs_deg != 90.0) and (staged or lookup_cache):
+        raise ValueError("--disk / --theta-obs need the fused path (no --staged, no --lookup-cache)")
     rgba8 = None
-    mirror = (not full_trace) and gpus <= 1 and not metric.is_spherically_symmetric and abs(psi[0]) <= 1e-8
+    mirror = (disk is None) and (not full_trace) and gpus <= 1 and not metric.is_spherically_symmetric and abs(psi[0]) <= 1e-8
     # (the staged path mirrors whenever the reference does, the fused one unless --full-trace / several GPUs)
     mirrored = (not metric.is_spherically_symmetric and abs(psi[0]) <= 1e-8) if staged else mirror
     cache_key = _lookup_cache_key(metric, r_obs, (height, width), fov, psi, mirrored) if lookup_cache else None
@@ -400,8 +412,13 @@ def main(metric=None, M=1.0, a=0.0, r_obs_mult=100.0, psi=(0.0, 0.0), vertical_f
         print(f"Fused GPU render (pixel -> ray -> colour) on {max(gpus, 1)} GPU(s); rows: "
               + ("top half traced, bottom half mirrored as in the reference" if mirror else "every row traced"))
         t0 = perf_counter()
+        extra = {} if theta_obs_deg == 90.0 else dict(theta_obs=theta_obs)
+        if disk is not None:
+            extra["disk"] = disk
+            print(f"Accretion disk: r_in = {disk.inner_edge(metric.M, getattr(metric, 'a', 0.0)):.4f} M, "
+                  f"r_out = {disk.r_out} M, q = {disk.q}, exposure = {disk.exposure}, theta_obs = {theta_obs_deg} deg")
         out = render_frame(img, metric, r_obs, fov, psi=psi, tb_symmetry=mirror,
-                           want=("rgb", "rgba") + (("fa", "winding") if lookup_cache else ()), gpus=gpus)
+                           want=("rgb", "rgba") + (("fa", "winding") if lookup_cache else ()), gpus=gpus, **extra)
         timings["render"] = perf_counter() - t0
         if lookup_cache:
             save_lookup_cache(lookup_cache, cache_key, np.asarray(out["fa"]), np.asarray(out["winding"]))
@@ -443,8 +460,19 @@ if __name__ == "__main__":
     ap.add_argument("--gpus", type=int, default=1, help="split the frame's rows over this many GPUs of the node")
     ap.add_argument("--full-trace", action="store_true",
                     help="trace every row instead of the reference's top-half trace + mirror (Kerr, equatorial observer)")
+    ap.add_argument("--theta-obs", type=float, default=90.0, help="observer inclination in deg (default: 90, equatorial)")
+    ap.add_argument("--disk", action="store_true", help="draw a thin Keplerian accretion disk (Kerr; every row traced)")
+    ap.add_argument("--disk-rin", type=float, default=None, help="disk inner edge in M (default: the ISCO)")
+    ap.add_argument("--disk-rout", type=float, default=20.0, help="disk outer edge in M (default: 20)")
+    ap.add_argument("--disk-q", type=float, default=3.0, help="emissivity index q of I ~ (r_in / r)^q (default: 3)")
+    ap.add_argument("--disk-exposure", type=float, default=1.0, help="disk brightness scale (default: 1)")
     args = ap.parse_args()
+    disk = None
+    if args.disk:
+        from disk import ThinDisk
+        disk = ThinDisk(r_in=args.disk_rin, r_out=args.disk_rout, q=args.disk_q, exposure=args.disk_exposure)
     main(M=args.M, a=args.a, r_obs_mult=args.r_obs, psi=(np.radians(args.psi_y), np.radians(args.psi_x)),
          vertical_fov_deg=args.fov_v, image_path=args.image, output_path=args.output, synthetic=args.synthetic,
          staged=args.staged, integrator=args.integrator, precision=args.precision, schedule=args.schedule,
-         gpus=args.gpus, full_trace=args.full_trace, dedup_alpha=args.dedup_alpha, lookup_cache=args.lookup_cache)
+         gpus=args.gpus, full_trace=args.full_trace, dedup_alpha=args.dedup_alpha, lookup_cache=args.lookup_cache,
+         theta_obs_deg=args.theta_obs, disk=disk)

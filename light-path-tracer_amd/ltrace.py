@@ -20,6 +20,8 @@ SCHED_DIRECT, SCHED_QUEUE = 0, 1
 STAT_RAYS, STAT_STEPS, STAT_RHS_EVALS, STAT_ESCAPED, STAT_CAPTURED, STAT_INVALID = range(6)
 STAT_WAVE_ITERS, STAT_WAVES, STAT_CLK_CYCLES, STAT_CLK_TICKS = 6, 7, 8, 9
 STAT_BG_TILES_LDS, STAT_BG_TILES_GLOBAL = 10, 11
+STAT_DISK = 12
+STATUS_DISK = 2
 STAT_WORDS = 16
 
 INTEGRATORS = {"dp45": INTEGRATOR_DP45, "rk4": INTEGRATOR_RK4, "dp45_exact": INTEGRATOR_DP45_EXACT}
@@ -60,6 +62,12 @@ class DenseOpts(C.Structure):
                 ("rtol", C.c_double), ("atol", C.c_double), ("max_step", C.c_double),
                 ("max_points", C.c_int64), ("max_attempts", C.c_int32), ("length_binning", C.c_int32),
                 ("stream", C.c_void_p)]
+
+
+class Disk(C.Structure):
+    """lt_disk: thin Keplerian accretion disk (r_in <= 0: the ISCO)."""
+    _fields_ = [("r_in", C.c_double), ("r_out", C.c_double), ("q", C.c_double), ("exposure", C.c_double),
+                ("flags", C.c_int32), ("reserved", C.c_int32)]
 
 
 TRACK_RANGE_END, TRACK_CAPTURE_EVENT, TRACK_ESCAPE_EVENT, TRACK_FAILED, TRACK_ATTEMPT_LIMIT = 0, 1, 2, -1, -2
@@ -115,6 +123,17 @@ SIGNATURES = {
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lt_rhs8_probe": (C.c_int, [C.POINTER(Metric), C.c_void_p, C.c_int64, C.c_void_p]),
     "lt_dense_predict_lengths": (C.c_int, [C.POINTER(Metric), C.POINTER(DenseOpts), C.c_void_p, C.c_int64, C.c_void_p]),
+    "lt_default_disk": (None, [C.POINTER(Disk)]),
+    "lt_kerr_isco": (C.c_double, [C.c_double, C.c_double]),
+    "lt_render_disk_dev": (C.c_int, [C.POINTER(Camera), C.POINTER(Metric), C.POINTER(Opts), C.POINTER(Disk), C.c_void_p,
+                                     C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p]),
+    "lt_render_disk": (C.c_int, [C.POINTER(Camera), C.POINTER(Metric), C.POINTER(Opts), C.POINTER(Disk), C.c_void_p,
+                                 C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.POINTER(Stats)]),
+    "lt_trace_batch_kerr_disk": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_double,
+                                           C.c_double, C.c_void_p, C.c_int, C.c_int, C.POINTER(Disk), C.c_int64,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 
@@ -511,3 +530,78 @@ def shutdown():
             globals()['_pinned_pooled'] = 0
         for addr in blocks:
             _lib.lt_host_free(C.c_void_p(addr))
+
+
+# ---- thin accretion disk (lt_render_disk) ---------------------------------------------------------------------------
+def default_disk(**kw):
+    """lt_disk with the library's defaults (r_in = ISCO, r_out = 20, q = 3, exposure = 1); keywords override.
+    r_in=None means the ISCO."""
+    d = Disk()
+    load().lt_default_disk(C.byref(d))
+    for k, v in kw.items():
+        if k == "r_in" and v is None:
+            v = 0.0
+        setattr(d, k, v)
+    return d
+
+
+def kerr_isco(M, a):
+    """ISCO radius of the circular equatorial orbit in +phi (lt_kerr_isco; host only)."""
+    return float(load().lt_kerr_isco(float(M), float(a)))
+
+
+def render_disk(cam, metric, opts, disk, background=None,
+                want=("fa", "winding", "status", "steps", "rgb", "rgba", "disk")):
+    """Host-pointer frame render with the accretion disk (lt_render_disk).  As render(), plus 'disk':
+    (rows, W, 3) float32 (r_hit, phi_hit, g), NaN off the disk; stats gain 'disk' (rays that ended on it)."""
+    if opts.block_owner:
+        rows = len(owned_rows(cam.height, opts.row_block or 16, opts._owner_keep, opts.part))
+    else:
+        rows = local_rows(cam.height, opts.row_block or 16, opts.n_parts or 1, opts.part)
+    if rows < 0 or cam.width <= 0:
+        raise LtraceError(ERR_INVALID_ARG, f"bad frame {cam.width}x{cam.height} or partition {opts.part}/{opts.n_parts}")
+    bg, nch, gray = _background(cam, background)
+    out = _frame_outputs(rows, cam.width, nch, gray, want)
+    if "disk" in want:
+        out["disk"] = pinned_empty((rows, cam.width, 3), np.float32)
+    st = Stats()
+    _check(load().lt_render_disk(C.byref(cam), C.byref(metric), C.byref(opts), C.byref(disk), _np_ptr(bg), nch,
+                                 _np_ptr(out.get("fa")), _np_ptr(out.get("winding")), _np_ptr(out.get("status")),
+                                 _np_ptr(out.get("steps")), _np_ptr(out.get("disk")), _np_ptr(out.get("rgb")),
+                                 _np_ptr(out.get("rgba")), C.byref(st)))
+    out["stats"] = stats_dict(st.counters, st.prologue_ms, st.integrate_ms, st.epilogue_ms)
+    out["stats"]["disk"] = int(st.counters[STAT_DISK])
+    return out
+
+
+def render_disk_dev(cam, metric, opts, disk, d_bg=0, bg_channels=3, d_fa=0, d_w=0, d_status=0, d_steps=0, d_disk=0,
+                    d_rgb=0, d_rgba=0, d_stats=0):
+    """Device-pointer form of render_disk (lt_render_disk_dev); pointers are integers, 0 = NULL.  Asynchronous."""
+    p = lambda x: C.c_void_p(x) if x else None
+    _check(load().lt_render_disk_dev(C.byref(cam), C.byref(metric), C.byref(opts), C.byref(disk), p(d_bg), bg_channels,
+                                     p(d_fa), p(d_w), p(d_status), p(d_steps), p(d_disk), p(d_rgb), p(d_rgba), p(d_stats)))
+
+
+def trace_batch_kerr_disk(M, a, r_obs, alphas, thetas, theta_obs, lambda_max, disk, axis_refines=None,
+                          integrator=INTEGRATOR_RK4, precision=32):
+    """Batch twin with the accretion disk (lt_trace_batch_kerr_disk) ->
+    dict(fa (n,) f64, winding (n,) i64, status (n,) i8, disk (n, 3) f64 (r_hit, phi_hit, g), rhs_evals (n,) u32)."""
+    al = np.ascontiguousarray(alphas, dtype=np.float64)
+    th = np.ascontiguousarray(thetas, dtype=np.float64)
+    n = al.size
+    if th.size != n:
+        raise ValueError("alphas and thetas differ in length")
+    ar = None
+    if axis_refines is not None:
+        ar = np.ascontiguousarray(axis_refines).astype(np.uint8)
+        if ar.size != n:
+            raise ValueError("axis_refines has the wrong length")
+    if isinstance(integrator, str):
+        integrator = INTEGRATORS[integrator]
+    out = dict(fa=np.empty(n), winding=np.empty(n, dtype=np.int64), status=np.empty(n, dtype=np.int8),
+               disk=np.empty((n, 3)), rhs_evals=np.empty(n, dtype=np.uint32))
+    _check(load().lt_trace_batch_kerr_disk(M, a, r_obs, _np_ptr(al), _np_ptr(th), theta_obs, lambda_max, _np_ptr(ar),
+                                           integrator, precision, C.byref(disk), n, _np_ptr(out["fa"]),
+                                           _np_ptr(out["winding"]), _np_ptr(out["status"]), _np_ptr(out["disk"]),
+                                           _np_ptr(out["rhs_evals"])))
+    return out

@@ -283,6 +283,18 @@ class Kerr(Metric):
                                 precision=self.precision, schedule=self.schedule, out_status=st)
         return _single(fa, nh, st)
 
+    def isco(self):
+        """ISCO radius of the circular equatorial orbit in +phi (prograde for a > 0; lt_kerr_isco)."""
+        return ltrace.kerr_isco(self.M, self.a)
+
+    def trace_rays_batch_disk(self, r_obs, alphas, thetas, theta_obs, disk, axis_refines=None):
+        """trace_rays_batch with a thin accretion disk (disk.ThinDisk or ltrace.Disk), direct schedule ->
+        dict(fa, winding, status (2 = on the disk), disk (n, 3) float64 (r_hit, phi_hit, g), rhs_evals)."""
+        d = disk.to_lt() if hasattr(disk, "to_lt") else disk
+        return ltrace.trace_batch_kerr_disk(self.M, self.a, r_obs, alphas, thetas, theta_obs, self._lambda_max(r_obs), d,
+                                            axis_refines=axis_refines, integrator=self.integrator,
+                                            precision=self.precision)
+
     def trace_rays_batch(self, r_obs, alphas, thetas, theta_obs, axis_refines, out_fa, out_w):
         """In place, like the reference (metrics.py:1128-1132)."""
         if not (out_fa.flags.c_contiguous and out_w.flags.c_contiguous):
