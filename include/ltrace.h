@@ -117,6 +117,8 @@ typedef struct lt_opts {
 #define LT_STAT_BG_TILES_LDS 10    /* epilogue, lensed background: 256-pixel groups whose source texels were staged in LDS */
 #define LT_STAT_BG_TILES_GLOBAL 11 /* ... and groups that fell back to the per-pixel global gather                  */
 #define LT_STAT_DISK 12            /* lt_render_disk_dev: rays that ended on the accretion disk                        */
+                                   /* (lt_render_disk_images_dev: rays with at least one hit)                          */
+#define LT_STAT_DISK_HITS 13       /* lt_render_disk_images_dev: hits of the optically thin disk, all rays              */
 #define LT_STAT_WORDS 16
 
 typedef struct lt_stats {
@@ -361,6 +363,53 @@ int lt_trace_batch_kerr_disk(double M, double a, double r_obs, const double *alp
                              double theta_obs, double lambda_max, const uint8_t *axis_refines, int integrator,
                              int precision, const lt_disk *disk, int64_t n, double *out_fa, int64_t *out_w,
                              int8_t *out_status, double *out_disk, uint32_t *out_rhs_evals);
+
+/* ---- optically thin disk: every image of the disk --------------------------------------------------- *
+ * The disk of lt_render_disk (same annulus, orbit, r_in resolution, refusals and redshift g), but it emits and does *
+ * not absorb: a ray records its crossings and keeps going, so the picture shows the higher-order images (light     *
+ * that went round the hole once or more before it left the disk: the photon ring) as well as the direct one.       *
+ *                                                                                                               *
+ * Hit: every strict sign change of theta - pi/2 between two consecutive accepted states whose crossing point      *
+ * lies in [r_in, r_out], found exactly as lt_render_disk finds its first one (same Hermite refinement, same       *
+ * handling of a step that also ends the ray by capture or escape).  The ray's state and event are left as the     *
+ * integrator produced them: fa, winding, status and steps are lt_render's (tb_symmetry = 0) on every pixel, and   *
+ * stats words 0-5 are lt_render's.  Slot j holds the (j+1)-th hit along the backward ray; the call keeps the first *
+ * max_images hits (1 <= max_images <= LT_DISK_MAX_IMAGES) and counts all of them.  Slot 0 is lt_render_disk's hit, *
+ * bit for bit, and a ray has a hit exactly where lt_render_disk gives LT_STATUS_DISK.                             *
+ *                                                                                                               *
+ * Colour, float64: base = lt_render's shaded pixel of the same camera with tb_symmetry = 0, or 0 without a         *
+ * background (the shadow render's white sky would saturate every escaped pixel).  Each stored hit adds, from the   *
+ * float32 (r, g) of its slot and with s and ramp as in lt_render_disk,                                            *
+ *   E_j = exposure g^4 (r_in / r)^q ramp(s)   (unclamped; a 1-channel background takes the mean of the three),     *
+ *   rgb = clamp(base + sum_j E_j, 0, 1): base first, then the slots in order, then rounded to float32.            *
+ * A pixel without a stored hit is base itself, so with a background it is lt_render's pixel.  With one hit over a  *
+ * black base, below saturation, the colour equals lt_render_disk's disk colour exactly.  RGBA8 as everywhere.     */
+#define LT_DISK_MAX_IMAGES 8
+
+/* lt_render_disk_dev with the optically thin disk.  Outputs as lt_render_dev, plus
+ *   d_images (R, W, max_images, 3) float32 (r_hit, phi_hit in [0, 2 pi), g), NaN in unused slots (may be NULL);
+ *   d_n_hits (R, W) uint8: the ray's hits, saturating at 255 (may be NULL).
+ * Stats: words 0-5 as lt_render_dev, LT_STAT_DISK rays with at least one hit, LT_STAT_DISK_HITS all hits.
+ * RK4 float32 / float64, DP45 and DP45-exact float64.  Partitions as lt_render_disk_dev; tb_symmetry is ignored.
+ * LT_ERR_UNSUPPORTED for LT_METRIC_SCHWARZSCHILD and LT_SCHED_QUEUE; LT_ERR_INVALID_ARG for max_images outside
+ * [1, LT_DISK_MAX_IMAGES] and as lt_render_disk_dev for the disk. */
+int lt_render_disk_images_dev(const lt_camera *cam, const lt_metric *metric, const lt_opts *opts, const lt_disk *disk,
+                              int32_t max_images, const float *d_bg, int32_t bg_channels, float *d_fa, uint16_t *d_w,
+                              int8_t *d_status, uint32_t *d_steps, float *d_images, uint8_t *d_n_hits, float *d_rgb,
+                              uint8_t *d_rgba, uint64_t *d_stats);
+/* The same with HOST pointers, staged like lt_render_disk. */
+int lt_render_disk_images(const lt_camera *cam, const lt_metric *metric, const lt_opts *opts, const lt_disk *disk,
+                          int32_t max_images, const float *bg, int32_t bg_channels, float *out_fa, uint16_t *out_w,
+                          int8_t *out_status, uint32_t *out_steps, float *out_images, uint8_t *out_n_hits,
+                          float *out_rgb, uint8_t *out_rgba, lt_stats *stats);
+/* lt_trace_batch_kerr with the optically thin disk (direct schedule): out_images (n, max_images, 3) float64
+ * (r_hit, phi_hit in [0, 2 pi), g), NaN in unused slots; out_n_hits (n) int32, every hit of the ray.  out_status is
+ * lt_trace_batch_kerr's.  HOST pointers; out_status / out_images / out_n_hits / out_rhs_evals may be NULL. */
+int lt_trace_batch_kerr_disk_images(double M, double a, double r_obs, const double *alphas, const double *thetas,
+                                    double theta_obs, double lambda_max, const uint8_t *axis_refines, int integrator,
+                                    int precision, const lt_disk *disk, int32_t max_images, int64_t n, double *out_fa,
+                                    int64_t *out_w, int8_t *out_status, double *out_images, int32_t *out_n_hits,
+                                    uint32_t *out_rhs_evals);
 
 /* Sum of HIP-event times (ms) of the prologue / integrate / epilogue kernels over all
  * lt_render_dev calls made with opts->timing != 0 since the last collect; *calls = how many.

@@ -6,6 +6,7 @@
 #include "../../include/ltrace.h"
 #include "lt_kernels.hpp"
 #include "lt_disk.hpp"
+#include "lt_disk_images.hpp"
 #ifdef LT_PROBES
 #include "lt_probe.hpp"
 #endif
@@ -98,6 +99,7 @@ struct StreamSlot {
     Grow dev;    // lt_render / batch twins: device-side inputs and outputs
     Grow dense;  // lt_integrate_dense_dev, length-binned launch: histogram, cursors, keys, permutation
     Grow blocks; // block-owner table mode: this partition's block list on the device
+    Grow disk_img; // lt_render_disk_images / its batch twin: the integrate kernel's hit records and counts
     std::vector<int32_t> blocks_host; // what `blocks` holds (skip the upload when unchanged)
     EventQuad own{}; // lt_render's private timing events (created on first use)
     bool own_ok = false;
@@ -252,6 +254,7 @@ extern "C" int lt_release_stream(void *stream)
     release(found->dev);
     release(found->dense);
     release(found->blocks);
+    release(found->disk_img);
     if (found->own_ok) for (auto &e : found->own.e) (void)hipEventDestroy(e);
     delete found;
     return LT_OK;
@@ -269,7 +272,7 @@ extern "C" int lt_shutdown(void)
         (void)hipSetDevice(d);
         (void)hipDeviceSynchronize();
         for (StreamSlot *sl : c.slots) {
-            release(sl->ws); release(sl->dev); release(sl->dense); release(sl->blocks);
+            release(sl->ws); release(sl->dev); release(sl->dense); release(sl->blocks); release(sl->disk_img);
             if (sl->own_ok) for (auto &e : sl->own.e) (void)hipEventDestroy(e);
             delete sl;
         }
@@ -667,16 +670,29 @@ static int check_opts(const lt_metric *metric, lt_opts *o)
     return LT_OK;
 }
 
-// The thin disk of lt_render_disk (lt_api_disk.inc): resolved parameters and the extra output.
+// The thin disk of lt_render_disk (lt_api_disk.inc): resolved parameters and the extra output.  max_images > 0: the
+// optically thin disk of lt_render_disk_images (lt_api_disk_images.inc) and its outputs.
 struct DiskParams {
     double r_in, r_out, q, exposure; // r_in resolved (the ISCO when the caller asked for it)
     float *d_disk;                   // (R, W, 3) float32 or NULL
+    int max_images = 0;              // slots kept per ray; 0: the opaque disk
+    float *d_images = nullptr;       // (R, W, max_images, 3) float32 or NULL
+    uint8_t *d_n_hits = nullptr;     // (R, W) or NULL
 };
 template <typename T>
 static int launch_integrate_disk(const MetricConsts &mc, const lt_opts &o, double lambda_max, const Workspace &w,
                                  int64_t n_q, hipStream_t s, uint64_t *kstats, const DiskParams &dp);
 static int launch_epilogue_disk(const CamConsts &c, const MetricConsts &mc, const lt_opts &o, const Workspace &w,
                                 const FrameOut &fo, uint64_t *d_stats, hipStream_t s, const DiskParams &dp);
+template <typename T>
+static int launch_integrate_disk_images(const MetricConsts &mc, const lt_opts &o, double lambda_max, const Workspace &w,
+                                        int64_t n_q, hipStream_t s, uint64_t *kstats, const DiskParams &dp);
+static int launch_epilogue_disk_images(const CamConsts &c, const MetricConsts &mc, const lt_opts &o, const Workspace &w,
+                                       int64_t n_q, const FrameOut &fo, uint64_t *d_stats, hipStream_t s,
+                                       const DiskParams &dp);
+static int launch_epilogue_arrays_disk_images(const MetricConsts &mc, const lt_opts &o, const Workspace &w, int64_t n,
+                                              int64_t n_q, double *d_fa, int64_t *d_w, int8_t *d_st, uint32_t *d_ev,
+                                              double *d_images, int32_t *d_n_hits, hipStream_t s, const DiskParams &dp);
 
 // disk == NULL: the frame path.  Else the disk frame (lt_render_disk_dev): every row traced, the disk kernels.
 static int render_dev_impl(const lt_camera *cam, const lt_metric *metric, const lt_opts *opts, const float *d_bg,
@@ -814,7 +830,10 @@ static int render_dev_impl(const lt_camera *cam, const lt_metric *metric, const 
     else k_prologue_camera<double><<<gq, 256, 0, s>>>(c, mc, (double4 *)ic, n_q);
     HIP_TRY(hipGetLastError());
     if ((rc = tm.mark(1, s))) return rc;
-    if (disk)
+    if (disk && disk->max_images)
+        rc = o.precision == 32 ? launch_integrate_disk_images<float>(mc, o, lambda_max, w, n_q, s, d_stats, *disk)
+                               : launch_integrate_disk_images<double>(mc, o, lambda_max, w, n_q, s, d_stats, *disk);
+    else if (disk)
         rc = o.precision == 32 ? launch_integrate_disk<float>(mc, o, lambda_max, w, n_q, s, d_stats, *disk)
                                : launch_integrate_disk<double>(mc, o, lambda_max, w, n_q, s, d_stats, *disk);
     else
@@ -823,7 +842,9 @@ static int render_dev_impl(const lt_camera *cam, const lt_metric *metric, const 
     if (rc) return rc;
     if ((rc = tm.mark(2, s))) return rc;
     if (disk) {
-        if ((rc = launch_epilogue_disk(c, mc, o, w, fo, d_stats, s, *disk))) return rc;
+        rc = disk->max_images ? launch_epilogue_disk_images(c, mc, o, w, n_q, fo, d_stats, s, *disk)
+                              : launch_epilogue_disk(c, mc, o, w, fo, d_stats, s, *disk);
+        if (rc) return rc;
         if ((rc = tm.mark(3, s))) return rc;
         tm.finish();
         return LT_OK;
@@ -901,11 +922,12 @@ static int copy_out(hipStream_t s, const std::vector<OutCopy> &outs)
     return LT_OK;
 }
 
-// lt_render, and with `disk` lt_render_disk (out_disk: (R, W, 3) float32 host array or NULL)
+// lt_render, and with `disk` lt_render_disk (out_disk: (R, W, 3) float32 host array or NULL) or, with
+// disk->max_images > 0, lt_render_disk_images (out_images (R, W, max_images, 3) float32, out_n_hits (R, W), or NULL)
 static int render_host_impl(const lt_camera *cam, const lt_metric *metric, const lt_opts *opts, const float *bg,
                             int32_t bg_channels, float *out_fa, uint16_t *out_w, int8_t *out_status, uint32_t *out_steps,
                             float *out_rgb, uint8_t *out_rgba, lt_stats *stats, const DiskParams *disk = nullptr,
-                            float *out_disk = nullptr)
+                            float *out_disk = nullptr, float *out_images = nullptr, uint8_t *out_n_hits = nullptr)
 {
     int rc = require_device();
     if (rc) return rc;
@@ -931,6 +953,8 @@ static int render_host_impl(const lt_camera *cam, const lt_metric *metric, const
     size_t o_steps = out_steps ? cv.take(n * 4) : 0, o_rgb = out_rgb ? cv.take(n * nch * 4) : 0;
     size_t o_rgba = out_rgba ? cv.take(n * 4) : 0;
     size_t o_disk = (disk && out_disk) ? cv.take(n * 3 * 4) : 0;
+    const size_t n_img = disk ? n * (size_t)disk->max_images * 3 : 0;
+    size_t o_img = (disk && out_images) ? cv.take(n_img * 4) : 0, o_hits = (disk && out_n_hits) ? cv.take(n) : 0;
     if ((rc = grow(sl->dev, cv.off, s))) return rc;
     char *base = (char *)sl->dev.p;
     auto at = [&](bool want, size_t off) -> void * { return want ? (void *)(base + off) : nullptr; };
@@ -939,7 +963,12 @@ static int render_host_impl(const lt_camera *cam, const lt_metric *metric, const
     if ((rc = slot_events(sl))) return rc;
     o.timing = 0; // private events: concurrent lt_render_dev(timing = 1) callers keep theirs
     DiskParams dp{};
-    if (disk) { dp = *disk; dp.d_disk = (float *)at(out_disk != nullptr, o_disk); }
+    if (disk) {
+        dp = *disk;
+        dp.d_disk = (float *)at(out_disk != nullptr, o_disk);
+        dp.d_images = (float *)at(out_images != nullptr, o_img);
+        dp.d_n_hits = (uint8_t *)at(out_n_hits != nullptr, o_hits);
+    }
     rc = render_dev_impl(cam, metric, &o, (const float *)at(bg != nullptr, o_bg), bg_channels, (float *)at(out_fa, o_fa),
                          (uint16_t *)at(out_w, o_w), (int8_t *)at(out_status, o_st), (uint32_t *)at(out_steps, o_steps),
                          (float *)at(out_rgb, o_rgb), (uint8_t *)at(out_rgba, o_rgba), (uint64_t *)(base + o_stats),
@@ -956,6 +985,8 @@ static int render_host_impl(const lt_camera *cam, const lt_metric *metric, const
     if (out_steps) outs.push_back({out_steps, base + o_steps, n * 4});
     if (out_rgb) outs.push_back({out_rgb, base + o_rgb, n * nch * 4});
     if (disk && out_disk) outs.push_back({out_disk, base + o_disk, n * 3 * 4});
+    if (disk && out_images) outs.push_back({out_images, base + o_img, n_img * 4});
+    if (disk && out_n_hits) outs.push_back({out_n_hits, base + o_hits, n});
     if ((rc = copy_out(s, outs))) return rc;
     HIP_TRY(hipMemcpyAsync(st.counters, base + o_stats, LT_STAT_WORDS * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -1106,10 +1137,12 @@ extern "C" int lt_render_multi(const lt_camera *cam, const lt_metric *metric, co
 // ---------------------------------------------------------------------------------------------
 // array-in / array-out twins
 // ---------------------------------------------------------------------------------------------
-// disk != NULL: lt_trace_batch_kerr_disk (out_disk (n, 3) float64 or NULL)
+// disk != NULL: lt_trace_batch_kerr_disk (out_disk (n, 3) float64 or NULL), or with disk->max_images > 0
+// lt_trace_batch_kerr_disk_images (out_images (n, max_images, 3) float64, out_n_hits (n) int32, or NULL)
 static int trace_batch(const MetricConsts &mc, lt_opts &o, double lambda_max, const double *alphas, const double *thetas,
                        const uint8_t *refines, int64_t n, double *out_fa, int64_t *out_w, int8_t *out_status,
-                       uint32_t *out_evals, const DiskParams *disk = nullptr, double *out_disk = nullptr)
+                       uint32_t *out_evals, const DiskParams *disk = nullptr, double *out_disk = nullptr,
+                       double *out_images = nullptr, int32_t *out_n_hits = nullptr)
 {
     int rc;
     if (n < 0) return fail(LT_ERR_INVALID_ARG, "negative ray count");
@@ -1131,6 +1164,8 @@ static int trace_batch(const MetricConsts &mc, lt_opts &o, double lambda_max, co
     size_t o_al = cv.take(n * 8), o_th = thetas ? cv.take(n * 8) : 0, o_ref = refines ? cv.take(n) : 0;
     size_t o_fa = cv.take(n * 8), o_w = cv.take(n * 8), o_st = out_status ? cv.take(n) : 0, o_ev = out_evals ? cv.take(n * 4) : 0;
     size_t o_disk = (disk && out_disk) ? cv.take(n * 3 * 8) : 0;
+    const size_t n_img = disk ? (size_t)n * (size_t)disk->max_images * 3 : 0;
+    size_t o_img = (disk && out_images) ? cv.take(n_img * 8) : 0, o_hits = (disk && out_n_hits) ? cv.take(n * 4) : 0;
     if ((rc = grow(sl->dev, cv.off, s))) return rc;
     char *base = (char *)sl->dev.p;
     const double *d_al = (const double *)(base + o_al);
@@ -1141,6 +1176,8 @@ static int trace_batch(const MetricConsts &mc, lt_opts &o, double lambda_max, co
     int8_t *d_st = out_status ? (int8_t *)(base + o_st) : nullptr;
     uint32_t *d_ev = out_evals ? (uint32_t *)(base + o_ev) : nullptr;
     double *d_disk = (disk && out_disk) ? (double *)(base + o_disk) : nullptr;
+    double *d_img = (disk && out_images) ? (double *)(base + o_img) : nullptr;
+    int32_t *d_hits = (disk && out_n_hits) ? (int32_t *)(base + o_hits) : nullptr;
     HIP_TRY(hipMemcpyAsync((void *)d_al, alphas, n * 8, hipMemcpyHostToDevice, s));
     if (thetas) HIP_TRY(hipMemcpyAsync((void *)d_th, thetas, n * 8, hipMemcpyHostToDevice, s));
     if (refines) HIP_TRY(hipMemcpyAsync((void *)d_ref, refines, n, hipMemcpyHostToDevice, s));
@@ -1148,7 +1185,10 @@ static int trace_batch(const MetricConsts &mc, lt_opts &o, double lambda_max, co
     if (o.precision == 32) k_prologue_arrays<float><<<gq, 256, 0, s>>>(mc, d_al, d_th, d_ref, n, (float4 *)ic, n_q);
     else k_prologue_arrays<double><<<gq, 256, 0, s>>>(mc, d_al, d_th, d_ref, n, (double4 *)ic, n_q);
     HIP_TRY(hipGetLastError());
-    if (disk)
+    if (disk && disk->max_images)
+        rc = o.precision == 32 ? launch_integrate_disk_images<float>(mc, o, lambda_max, w, n_q, s, nullptr, *disk)
+                               : launch_integrate_disk_images<double>(mc, o, lambda_max, w, n_q, s, nullptr, *disk);
+    else if (disk)
         rc = o.precision == 32 ? launch_integrate_disk<float>(mc, o, lambda_max, w, n_q, s, nullptr, *disk)
                                : launch_integrate_disk<double>(mc, o, lambda_max, w, n_q, s, nullptr, *disk);
     else
@@ -1156,7 +1196,9 @@ static int trace_batch(const MetricConsts &mc, lt_opts &o, double lambda_max, co
                                : launch_integrate<double>(mc, o, lambda_max, w, n_q, s, nullptr);
     if (rc) return rc;
     unsigned gn = (unsigned)((n + 255) / 256);
-    if (disk) {
+    if (disk && disk->max_images) {
+        if ((rc = launch_epilogue_arrays_disk_images(mc, o, w, n, n_q, d_fa, d_w, d_st, d_ev, d_img, d_hits, s, *disk))) return rc;
+    } else if (disk) {
         const DiskShade ds{mc.M, mc.a, disk->r_in, disk->q, disk->exposure};
         if (o.precision == 32)
             k_epilogue_arrays_disk<float><<<gn, 256, 0, s>>>(mc, ds, (const float4 *)fin0, (const float4 *)fin1, n, d_fa, d_w, d_st, d_disk, d_ev);
@@ -1172,6 +1214,8 @@ static int trace_batch(const MetricConsts &mc, lt_opts &o, double lambda_max, co
     if (out_status) HIP_TRY(hipMemcpyAsync(out_status, d_st, n, hipMemcpyDeviceToHost, s));
     if (out_evals) HIP_TRY(hipMemcpyAsync(out_evals, d_ev, n * 4, hipMemcpyDeviceToHost, s));
     if (d_disk) HIP_TRY(hipMemcpyAsync(out_disk, d_disk, n * 3 * 8, hipMemcpyDeviceToHost, s));
+    if (d_img) HIP_TRY(hipMemcpyAsync(out_images, d_img, n_img * 8, hipMemcpyDeviceToHost, s));
+    if (d_hits) HIP_TRY(hipMemcpyAsync(out_n_hits, d_hits, n * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return LT_OK;
 }
@@ -1442,3 +1486,4 @@ extern "C" int lt_piece_probe(int piece, int waves_per_simd, int iters, double *
 #include "lt_api_stages.inc"
 #include "lt_api_dense.inc"
 #include "lt_api_disk.inc"
+#include "lt_api_disk_images.inc"

@@ -8,6 +8,9 @@ the (r_hit, phi_hit, g) the renderer returns.
     u^t   = (r^1.5 + a sqrt(M)) / (r^0.75 sqrt(r^1.5 - 3 M r^0.5 + 2 a sqrt(M)))
     g     = 1 / (u^t (1 - Omega xi))                                           (E = 1, xi = p_phi of the camera's ray)
     I     = exposure g^4 (r_in / r)^q,  s = g (r_in / r)^0.75,  rgb = clamp(I ramp(s), 0, 1)
+
+The optically thin disk (TransparentDisk; lt_render_disk_images) keeps every crossing of the annulus and adds the light
+of the first max_images of them to the pixel: rgb = clamp(base + sum_j I_j ramp(s_j), 0, 1) (shade_images).
 """
 from dataclasses import dataclass
 from typing import Optional
@@ -32,6 +35,14 @@ class ThinDisk:
 
     def inner_edge(self, M, a):
         return isco(M, a) if self.r_in is None or self.r_in <= 0 else float(self.r_in)
+
+
+@dataclass
+class TransparentDisk(ThinDisk):
+    """The same disk, optically thin: it emits and does not absorb, so a ray records every crossing of the annulus and
+    goes on (lt_render_disk_images).  The picture then shows the higher-order images -- the photon ring -- as well as
+    the direct one.  max_images: how many hits per ray are kept (1 ... 8)."""
+    max_images: int = 3
 
 
 def isco(M, a):
@@ -78,3 +89,30 @@ def shade(r, g, r_in, q=3.0, exposure=1.0, channels=3):
     if channels == 1:
         return ((rgb[..., 0] + rgb[..., 1] + rgb[..., 2]) / 3.0).astype(np.float32)
     return rgb.astype(np.float32)
+
+
+def shade_images(base, images, n_hits, r_in, q=3.0, exposure=1.0, channels=3):
+    """Colour of the optically thin disk's renderer, float32, restated: base (..., 3) or (...) for a 1-channel background
+    (the pixel without the disk; 0 for a render without background), images (..., max_images, 3) (r_hit, phi_hit, g),
+    n_hits (...).  Each stored hit j < min(n_hits, max_images) adds E_j = exposure g^4 (r_in / r)^q ramp(s), unclamped
+    (1 channel: the mean of the three); rgb = clamp(base + sum_j E_j, 0, 1), summed in float64, base first, then the
+    slots in order, then rounded to float32.  A pixel without a stored hit keeps base."""
+    images = np.asarray(images)
+    m = images.shape[-2]
+    ns = np.minimum(np.asarray(n_hits).astype(np.int64), m)
+    base = np.asarray(base, dtype=np.float32)
+    acc = base.astype(np.float64)
+    for j in range(m):
+        on = ns > j
+        r = np.where(on, images[..., j, 0].astype(np.float64), 1.0)
+        g = np.where(on, images[..., j, 2].astype(np.float64), 0.0)
+        x = r_in / r
+        intensity = exposure * g ** 4 * x ** q
+        s = g * x ** 0.75
+        e = np.stack([intensity * np.clip(2.0 * s - 0.5 * i, 0.0, 1.0) for i in range(3)], axis=-1)
+        if channels == 1:
+            acc = np.where(on, acc + (e[..., 0] + e[..., 1] + e[..., 2]) / 3.0, acc)
+        else:
+            acc = np.where(on[..., None], acc + e, acc)
+    lit = ns > 0 if channels == 1 else (ns > 0)[..., None]
+    return np.where(lit, np.clip(acc, 0.0, 1.0).astype(np.float32), base)

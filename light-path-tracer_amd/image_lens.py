@@ -216,7 +216,9 @@ def render_frame(source_image, metric, r_obs, fov, psi=(0.0, 0.0), theta_obs=np.
     gpus > 1: the frame's rows are split block-cyclically over that many devices of this node
     (lt_render_multi; the reference's top/bottom mirror needs the whole frame on one device).
     disk: a thin accretion disk (disk.ThinDisk or ltrace.Disk) -> lt_render_disk on one GPU, every row traced, plus
-    'disk' (H, W, 3) (r_hit, phi_hit, g); a spherically symmetric metric is traced as Kerr with a = 0."""
+    'disk' (H, W, 3) (r_hit, phi_hit, g); a spherically symmetric metric is traced as Kerr with a = 0.
+    An optically thin disk (disk.TransparentDisk: anything with a max_images) -> lt_render_disk_images instead, plus
+    'disk_images' (H, W, max_images, 3) (r_hit, phi_hit, g) of the first hits along the ray and 'disk_hits' (H, W)."""
     if source_image is None:
         raise ValueError("render_frame needs a background; for a shadow use black_hole_shadow.render_traced")
     source_image = np.asarray(source_image)
@@ -240,6 +242,12 @@ def render_frame(source_image, metric, r_obs, fov, psi=(0.0, 0.0), theta_obs=np.
         if gpus and gpus > 1:
             raise ValueError("the accretion disk renders on one GPU (gpus == 1)")
         d = disk.to_lt() if hasattr(disk, "to_lt") else disk
+        max_images = getattr(disk, "max_images", None)
+        if max_images is not None:
+            out = ltrace.render_disk_images(cam, met, opts, d, max_images=max_images, background=source_image,
+                                            want=tuple(want) + ("images", "n_hits"))
+            out["disk_images"], out["disk_hits"] = out.pop("images"), out.pop("n_hits")
+            return out
         return ltrace.render_disk(cam, met, opts, d, background=source_image, want=tuple(want) + ("disk",))
     if gpus and gpus > 1:
         if tb_symmetry:
@@ -338,7 +346,8 @@ def main(metric=None, M=1.0, a=0.0, r_obs_mult=100.0, psi=(0.0, 0.0), vertical_f
     the same settings -- a new background then costs one colouring pass (lt_shade) instead of a trace.
     `dedup_alpha`: staged path, spherically symmetric metrics: trace distinct alphas only (precompute_final_alpha_lookup).
     `theta_obs_deg`: the observer's inclination (fused path; 90 = equatorial, as the reference).  `disk`: a thin
-    accretion disk (disk.ThinDisk) in the picture (fused path, one GPU, every row traced)."""
+    accretion disk (disk.ThinDisk, or disk.TransparentDisk for the optically thin one with its higher-order images) in
+    the picture (fused path, one GPU, every row traced)."""
     import matplotlib.image as mpimg
 
     if metric is None:
@@ -416,7 +425,8 @@ def main(metric=None, M=1.0, a=0.0, r_obs_mult=100.0, psi=(0.0, 0.0), vertical_f
         if disk is not None:
             extra["disk"] = disk
             print(f"Accretion disk: r_in = {disk.inner_edge(metric.M, getattr(metric, 'a', 0.0)):.4f} M, "
-                  f"r_out = {disk.r_out} M, q = {disk.q}, exposure = {disk.exposure}, theta_obs = {theta_obs_deg} deg")
+                  f"r_out = {disk.r_out} M, q = {disk.q}, exposure = {disk.exposure}, theta_obs = {theta_obs_deg} deg"
+                  + (f", optically thin: up to {disk.max_images} images per ray" if hasattr(disk, "max_images") else ""))
         out = render_frame(img, metric, r_obs, fov, psi=psi, tb_symmetry=mirror,
                            want=("rgb", "rgba") + (("fa", "winding") if lookup_cache else ()), gpus=gpus, **extra)
         timings["render"] = perf_counter() - t0
@@ -466,9 +476,16 @@ if __name__ == "__main__":
     ap.add_argument("--disk-rout", type=float, default=20.0, help="disk outer edge in M (default: 20)")
     ap.add_argument("--disk-q", type=float, default=3.0, help="emissivity index q of I ~ (r_in / r)^q (default: 3)")
     ap.add_argument("--disk-exposure", type=float, default=1.0, help="disk brightness scale (default: 1)")
+    ap.add_argument("--disk-images", type=int, default=None, metavar="N",
+                    help="optically thin disk: add the light of the first N (1 ... 8) images of the disk along each ray, "
+                         "the photon ring included (implies --disk)")
     args = ap.parse_args()
     disk = None
-    if args.disk:
+    if args.disk_images is not None:
+        from disk import TransparentDisk
+        disk = TransparentDisk(r_in=args.disk_rin, r_out=args.disk_rout, q=args.disk_q, exposure=args.disk_exposure,
+                               max_images=args.disk_images)
+    elif args.disk:
         from disk import ThinDisk
         disk = ThinDisk(r_in=args.disk_rin, r_out=args.disk_rout, q=args.disk_q, exposure=args.disk_exposure)
     main(M=args.M, a=args.a, r_obs_mult=args.r_obs, psi=(np.radians(args.psi_y), np.radians(args.psi_x)),

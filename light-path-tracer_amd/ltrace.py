@@ -21,6 +21,8 @@ STAT_RAYS, STAT_STEPS, STAT_RHS_EVALS, STAT_ESCAPED, STAT_CAPTURED, STAT_INVALID
 STAT_WAVE_ITERS, STAT_WAVES, STAT_CLK_CYCLES, STAT_CLK_TICKS = 6, 7, 8, 9
 STAT_BG_TILES_LDS, STAT_BG_TILES_GLOBAL = 10, 11
 STAT_DISK = 12
+STAT_DISK_HITS = 13
+DISK_MAX_IMAGES = 8
 STATUS_DISK = 2
 STAT_WORDS = 16
 
@@ -134,6 +136,16 @@ SIGNATURES = {
     "lt_trace_batch_kerr_disk": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_double,
                                            C.c_double, C.c_void_p, C.c_int, C.c_int, C.POINTER(Disk), C.c_int64,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lt_render_disk_images_dev": (C.c_int, [C.POINTER(Camera), C.POINTER(Metric), C.POINTER(Opts), C.POINTER(Disk),
+                                            C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lt_render_disk_images": (C.c_int, [C.POINTER(Camera), C.POINTER(Metric), C.POINTER(Opts), C.POINTER(Disk),
+                                        C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
+    "lt_trace_batch_kerr_disk_images": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
+                                                  C.c_double, C.c_double, C.c_void_p, C.c_int, C.c_int, C.POINTER(Disk),
+                                                  C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p]),
 }
 
 
@@ -604,4 +616,79 @@ def trace_batch_kerr_disk(M, a, r_obs, alphas, thetas, theta_obs, lambda_max, di
                                            integrator, precision, C.byref(disk), n, _np_ptr(out["fa"]),
                                            _np_ptr(out["winding"]), _np_ptr(out["status"]), _np_ptr(out["disk"]),
                                            _np_ptr(out["rhs_evals"])))
+    return out
+
+
+# ---- optically thin disk: every image (lt_render_disk_images) ------------------------------------------------------
+def _frame_rows(cam, opts):
+    if opts.block_owner:
+        rows = len(owned_rows(cam.height, opts.row_block or 16, opts._owner_keep, opts.part))
+    else:
+        rows = local_rows(cam.height, opts.row_block or 16, opts.n_parts or 1, opts.part)
+    if rows < 0 or cam.width <= 0:
+        raise LtraceError(ERR_INVALID_ARG, f"bad frame {cam.width}x{cam.height} or partition {opts.part}/{opts.n_parts}")
+    return rows
+
+
+def render_disk_images(cam, metric, opts, disk, max_images=3, background=None,
+                       want=("fa", "winding", "status", "steps", "rgb", "rgba", "images", "n_hits")):
+    """Host-pointer frame render with the optically thin disk (lt_render_disk_images).  As render(), plus 'images':
+    (rows, W, max_images, 3) float32 (r_hit, phi_hit, g) of the first max_images hits along the ray, NaN in unused
+    slots, and 'n_hits': (rows, W) uint8, every hit of the ray (saturating at 255); stats gain 'disk' (rays with a hit)
+    and 'disk_hits' (all hits).  fa / winding / status / steps are render()'s."""
+    rows = _frame_rows(cam, opts)
+    bg, nch, gray = _background(cam, background)
+    out = _frame_outputs(rows, cam.width, nch, gray, want)
+    if "images" in want:
+        out["images"] = pinned_empty((rows, cam.width, int(max_images), 3), np.float32)
+    if "n_hits" in want:
+        out["n_hits"] = pinned_empty((rows, cam.width), np.uint8)
+    st = Stats()
+    _check(load().lt_render_disk_images(C.byref(cam), C.byref(metric), C.byref(opts), C.byref(disk), int(max_images),
+                                        _np_ptr(bg), nch, _np_ptr(out.get("fa")), _np_ptr(out.get("winding")),
+                                        _np_ptr(out.get("status")), _np_ptr(out.get("steps")), _np_ptr(out.get("images")),
+                                        _np_ptr(out.get("n_hits")), _np_ptr(out.get("rgb")), _np_ptr(out.get("rgba")),
+                                        C.byref(st)))
+    out["stats"] = stats_dict(st.counters, st.prologue_ms, st.integrate_ms, st.epilogue_ms)
+    out["stats"]["disk"] = int(st.counters[STAT_DISK])
+    out["stats"]["disk_hits"] = int(st.counters[STAT_DISK_HITS])
+    return out
+
+
+def render_disk_images_dev(cam, metric, opts, disk, max_images=3, d_bg=0, bg_channels=3, d_fa=0, d_w=0, d_status=0,
+                           d_steps=0, d_images=0, d_n_hits=0, d_rgb=0, d_rgba=0, d_stats=0):
+    """Device-pointer form of render_disk_images (lt_render_disk_images_dev); pointers are integers, 0 = NULL.
+    Asynchronous."""
+    p = lambda x: C.c_void_p(x) if x else None
+    _check(load().lt_render_disk_images_dev(C.byref(cam), C.byref(metric), C.byref(opts), C.byref(disk), int(max_images),
+                                            p(d_bg), bg_channels, p(d_fa), p(d_w), p(d_status), p(d_steps), p(d_images),
+                                            p(d_n_hits), p(d_rgb), p(d_rgba), p(d_stats)))
+
+
+def trace_batch_kerr_disk_images(M, a, r_obs, alphas, thetas, theta_obs, lambda_max, disk, max_images=3,
+                                 axis_refines=None, integrator=INTEGRATOR_RK4, precision=32):
+    """Batch twin with the optically thin disk (lt_trace_batch_kerr_disk_images) -> dict(fa (n,) f64, winding (n,) i64,
+    status (n,) i8 (trace_batch_kerr's), images (n, max_images, 3) f64 (r_hit, phi_hit, g), NaN in unused slots,
+    n_hits (n,) i32, rhs_evals (n,) u32)."""
+    al = np.ascontiguousarray(alphas, dtype=np.float64)
+    th = np.ascontiguousarray(thetas, dtype=np.float64)
+    n = al.size
+    if th.size != n:
+        raise ValueError("alphas and thetas differ in length")
+    ar = None
+    if axis_refines is not None:
+        ar = np.ascontiguousarray(axis_refines).astype(np.uint8)
+        if ar.size != n:
+            raise ValueError("axis_refines has the wrong length")
+    if isinstance(integrator, str):
+        integrator = INTEGRATORS[integrator]
+    m = int(max_images)
+    out = dict(fa=np.empty(n), winding=np.empty(n, dtype=np.int64), status=np.empty(n, dtype=np.int8),
+               images=np.empty((n, max(m, 0), 3)), n_hits=np.empty(n, dtype=np.int32),
+               rhs_evals=np.empty(n, dtype=np.uint32))
+    _check(load().lt_trace_batch_kerr_disk_images(M, a, r_obs, _np_ptr(al), _np_ptr(th), theta_obs, lambda_max,
+                                                  _np_ptr(ar), integrator, precision, C.byref(disk), m, n,
+                                                  _np_ptr(out["fa"]), _np_ptr(out["winding"]), _np_ptr(out["status"]),
+                                                  _np_ptr(out["images"]), _np_ptr(out["n_hits"]),
+                                                  _np_ptr(out["rhs_evals"])))
     return out

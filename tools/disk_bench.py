@@ -1,7 +1,9 @@
 """Cost of the accretion disk on the integrate kernel: a 4096^2 frame (Kerr a = 0.9, r_obs = 50, theta_obs = 80 deg,
-vfov 40 deg) rendered with the disk (r_out = 20, r_in = ISCO; lt_render_disk) and without it (lt_render, same camera,
-every row traced), for RK4 float32 and DP45 (exact controller) float64.  Reports Mrays/s of the frame, the integrate
-kernel's HIP-event time (median of --reps after one warm-up) and the fraction of pixels on the disk; no gate.
+vfov 40 deg) rendered with the disk (r_out = 20, r_in = ISCO; lt_render_disk), with the optically thin disk keeping
+3 images per ray (lt_render_disk_images) and without a disk (lt_render, same camera, every row traced), for RK4
+float32 and DP45 (exact controller) float64.  Reports Mrays/s of the frame, the integrate kernel's HIP-event time
+(median of --reps after one warm-up), the fraction of pixels on the disk and, for the thin disk, the fraction with a
+higher-order image and the hits per ray; no gate.
 
     python tools/disk_bench.py [--size 4096] [--reps 5] [--out profiles/disk_bench_<build>.json]
 """
@@ -38,7 +40,9 @@ def main():
         o = ltrace.default_opts(integrator=integ, precision=prec, tb_symmetry=0)
         row = {}
         for name, call in (("plain", lambda: ltrace.render(cam, met, o, want=want)),
-                           ("disk", lambda: ltrace.render_disk(cam, met, o, disk, want=want))):
+                           ("disk", lambda: ltrace.render_disk(cam, met, o, disk, want=want)),
+                           ("images", lambda: ltrace.render_disk_images(cam, met, o, disk, max_images=3,
+                                                                        want=want + ("n_hits",)))):
             call()
             ms, wall, out = [], [], None
             for _ in range(args.reps):
@@ -52,7 +56,13 @@ def main():
                              steps_per_ray=round(out["stats"]["steps"] / out["stats"]["rays"], 2))
             if name == "disk":
                 row["disk_fraction"] = round(float((out["status"] == ltrace.STATUS_DISK).mean()), 4)
+            if name == "images":
+                row["images"]["epilogue_ms"] = round(float(out["stats"]["epilogue_ms"]), 4)
+                row["images"]["hit_fraction"] = round(float((out["n_hits"] > 0).mean()), 4)
+                row["images"]["higher_order_fraction"] = round(float((out["n_hits"] > 1).mean()), 4)
+                row["images"]["hits_per_ray"] = round(out["stats"]["disk_hits"] / out["stats"]["rays"], 4)
         row["integrate_ratio"] = round(row["disk"]["integrate_ms"] / row["plain"]["integrate_ms"], 4)
+        row["images_integrate_ratio"] = round(row["images"]["integrate_ms"] / row["plain"]["integrate_ms"], 4)
         res["configs"][f"{integ}_f{prec}"] = row
         print(integ, prec, json.dumps(row), flush=True)
     out = args.out or os.path.join(ROOT, "profiles", f"disk_bench_{res['build']}.json")
