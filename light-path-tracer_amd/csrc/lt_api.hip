@@ -563,6 +563,57 @@ template <auto Kernel> static int resident_slots()
     return slots;
 }
 
+// The kernels of the direct schedule, by integrator: the plain frame path and the two disks (lt_disk.hpp, lt_disk_images.hpp).
+template <typename T> struct PlainKernels { template <typename Integ> static constexpr auto kernel = &k_kerr_direct<T, Integ>; };
+template <typename T> struct DiskKernels { template <typename Integ> static constexpr auto kernel = &k_kerr_disk<T, Integ>; };
+template <typename T> struct DiskImagesKernels { template <typename Integ> static constexpr auto kernel = &k_kerr_disk_images<T, Integ>; };
+template <typename Integ> struct IntegTag { using type = Integ; };
+
+// The switches of the direct schedule, read once.
+struct DirectTuning {
+    // LT_D_LONG: steps after which a wavefront is "long" (ghost lanes, lone-wave step form, issue priority).  384: with the
+    // packed lone-wave step of round 2 an earlier switch pays on chain-bound launches -- 2048^2 4.19 -> 4.10 ms, one rank
+    // of 8 4.00 -> 3.95, of 4 4.18 -> 4.12 -- and leaves the 4096^2 frame where it was (10.75 / 10.73 ms); 128 costs that
+    // frame 1.5 % (profiles/r03_xcd_clock.txt, tools/scratch/d_long_sweep.sh)
+    int long_iters;
+    // LT_D_PERSIST: tiles are handed out from a queue head to a grid that fills the chip once (direct_tiles); 0, or wider
+    // workgroups: one workgroup per tile, as in round 1.
+    int persist;
+};
+static const DirectTuning &direct_tuning()
+{
+    static const DirectTuning t{env_int("LT_D_LONG", 384), env_int("LT_D_PERSIST", 1)};
+    return t;
+}
+
+// One launch of the direct schedule (direct_tiles, lt_kernels.hpp): picks the integrator's kernel of the family `Kernels`,
+// sizes the grid, zeroes the queue head and calls launch(kernel, grid, long_iters, head), which adds the family's own
+// arguments.  `block`: work-items per workgroup (64 everywhere but under LT_K2_BLOCK on the plain frame path).
+template <typename T, typename Kernels, typename Launch>
+static int launch_direct(const lt_opts &o, const Workspace &w, int64_t n_q, hipStream_t s, int block, Launch launch)
+{
+    const bool exact = o.integrator == LT_INTEGRATOR_DP45_EXACT;
+    const bool dp45 = o.integrator == LT_INTEGRATOR_DP45 || exact;
+    if (dp45 && sizeof(T) != 8) return fail(LT_ERR_UNSUPPORTED, "DP45 needs precision 64");
+    const DirectTuning &tune = direct_tuning();
+    auto go = [&](auto integ, int long_it) -> int {
+        constexpr auto kernel = Kernels::template kernel<typename decltype(integ)::type>;
+        unsigned grid = (unsigned)((n_q + block - 1) / block);
+        unsigned long long *head = nullptr;
+        const int slots = tune.persist && block == 64 ? resident_slots<kernel>() : 0;
+        if (slots > 0 && (unsigned)slots < grid) { grid = (unsigned)slots; head = w.head; } // (a launch that fits the chip needs no queue)
+        if (head) HIP_TRY(hipMemsetAsync(head, 0, sizeof(unsigned long long), s));
+        launch(kernel, grid, (uint32_t)long_it, head);
+        HIP_TRY(hipGetLastError());
+        return LT_OK;
+    };
+    if constexpr (sizeof(T) == 8) { // "long" is measured in step attempts: DP45 rays take ~50, not ~150
+        if (exact) return go(IntegTag<Dp45<T, true>>{}, tune.long_iters / 3);
+        if (dp45) return go(IntegTag<Dp45<T>>{}, tune.long_iters / 3);
+    }
+    return go(IntegTag<Rk4<T>>{}, tune.long_iters);
+}
+
 template <typename T>
 static int launch_integrate(const MetricConsts &mc, const lt_opts &o, double lambda_max, const Workspace &w,
                             int64_t n_q, hipStream_t s, uint64_t *kstats)
@@ -580,40 +631,14 @@ static int launch_integrate(const MetricConsts &mc, const lt_opts &o, double lam
         if (dp45 && sizeof(T) != 8) return fail(LT_ERR_UNSUPPORTED, "DP45 needs precision 64");
         StampDump sd;
         if (o.schedule == LT_SCHED_DIRECT) {
+            // wider workgroups and the per-wave stamps (StampDump) exist on this path only, not for the disks
             static const int k2_block = [] { int b = env_int("LT_K2_BLOCK", 64);
                                              return (b == 64 || b == 128 || b == 256) ? b : 64; }();
-            unsigned kgrid = (unsigned)((n_q + k2_block - 1) / k2_block);
-            // steps after which a wavefront is "long" (ghost lanes, lone-wave step form, issue priority).  384: with the packed
-            // lone-wave step of round 2 an earlier switch pays on chain-bound launches -- 2048^2 4.19 -> 4.10 ms, one rank of 8
-            // 4.00 -> 3.95, of 4 4.18 -> 4.12 -- and leaves the 4096^2 frame where it was (10.75 / 10.73 ms); 128 costs that
-            // frame 1.5 % (profiles/r03_xcd_clock.txt, tools/scratch/d_long_sweep.sh)
-            static const int long_iters = env_int("LT_D_LONG", 384);
-            // Tiles are handed out from a queue head to a grid that fills the chip once (k_kerr_direct); LT_D_PERSIST=0
-            // or wider workgroups: one workgroup per tile, as in round 1.
-            static const int persist = env_int("LT_D_PERSIST", 1);
-            unsigned long long *head = nullptr;
-            auto resident_grid = [&](int slots) { // (a launch that fits the chip needs no queue)
-                if (slots > 0 && (unsigned)slots < kgrid) { kgrid = (unsigned)slots; head = w.head; }
-            };
-            const bool want_queue_head = persist && k2_block == 64;
             if ((rc = sd.begin((size_t)(n_q / 64)))) return rc;
-            if constexpr (sizeof(T) == 8) {
-                if (dp45 && !exact) {
-                    if (want_queue_head) resident_grid(resident_slots<k_kerr_direct<T, Dp45<T>>>());
-                    if (head) HIP_TRY(hipMemsetAsync(head, 0, sizeof(unsigned long long), s));
-                    k_kerr_direct<T, Dp45<T>><<<kgrid, k2_block, 0, s>>>(k, (const V *)w.ic, (V *)w.fin0, (V *)w.fin1, n_q, (uint32_t)(long_iters / 3), sd.dev, kstats, head);
-                }
-                if (exact) {
-                    if (want_queue_head) resident_grid(resident_slots<k_kerr_direct<T, Dp45<T, true>>>());
-                    if (head) HIP_TRY(hipMemsetAsync(head, 0, sizeof(unsigned long long), s));
-                    k_kerr_direct<T, Dp45<T, true>><<<kgrid, k2_block, 0, s>>>(k, (const V *)w.ic, (V *)w.fin0, (V *)w.fin1, n_q, (uint32_t)(long_iters / 3), sd.dev, kstats, head);
-                }
-            }
-            if (!dp45) {
-                if (want_queue_head) resident_grid(resident_slots<k_kerr_direct<T, Rk4<T>>>());
-                if (head) HIP_TRY(hipMemsetAsync(head, 0, sizeof(unsigned long long), s));
-                k_kerr_direct<T, Rk4<T>><<<kgrid, k2_block, 0, s>>>(k, (const V *)w.ic, (V *)w.fin0, (V *)w.fin1, n_q, (uint32_t)long_iters, sd.dev, kstats, head);
-            }
+            rc = launch_direct<T, PlainKernels<T>>(o, w, n_q, s, k2_block, [&](auto kernel, unsigned kgrid, uint32_t long_iters, unsigned long long *head) {
+                kernel<<<kgrid, k2_block, 0, s>>>(k, (const V *)w.ic, (V *)w.fin0, (V *)w.fin1, n_q, long_iters, sd.dev, kstats, head);
+            });
+            if (rc) return rc;
         } else {
             int cus;
             if ((rc = cu_count(&cus))) return rc;
@@ -679,20 +704,24 @@ struct DiskParams {
     float *d_images = nullptr;       // (R, W, max_images, 3) float32 or NULL
     uint8_t *d_n_hits = nullptr;     // (R, W) or NULL
 };
+// The hit records of the thin disk, resolved once per call (get_disk_records) and handed to its launches.
+struct DiskRecordsBuf {
+    void *img = nullptr;      // Vec2<T> [max_images][n_q]
+    uint32_t *hits = nullptr; // [n_q]
+};
+static int get_disk_records(hipStream_t s, int64_t n_q, size_t elem, const DiskParams *disk, DiskRecordsBuf *recs);
 template <typename T>
-static int launch_integrate_disk(const MetricConsts &mc, const lt_opts &o, double lambda_max, const Workspace &w,
-                                 int64_t n_q, hipStream_t s, uint64_t *kstats, const DiskParams &dp);
+static int launch_integrate_disk(const MetricConsts &mc, const lt_opts &o, double lambda_max, const Workspace &w, int64_t n_q,
+                                 hipStream_t s, uint64_t *kstats, const DiskParams &dp, const DiskRecordsBuf &recs);
 static int launch_epilogue_disk(const CamConsts &c, const MetricConsts &mc, const lt_opts &o, const Workspace &w,
                                 const FrameOut &fo, uint64_t *d_stats, hipStream_t s, const DiskParams &dp);
-template <typename T>
-static int launch_integrate_disk_images(const MetricConsts &mc, const lt_opts &o, double lambda_max, const Workspace &w,
-                                        int64_t n_q, hipStream_t s, uint64_t *kstats, const DiskParams &dp);
 static int launch_epilogue_disk_images(const CamConsts &c, const MetricConsts &mc, const lt_opts &o, const Workspace &w,
                                        int64_t n_q, const FrameOut &fo, uint64_t *d_stats, hipStream_t s,
-                                       const DiskParams &dp);
+                                       const DiskParams &dp, const DiskRecordsBuf &recs);
 static int launch_epilogue_arrays_disk_images(const MetricConsts &mc, const lt_opts &o, const Workspace &w, int64_t n,
                                               int64_t n_q, double *d_fa, int64_t *d_w, int8_t *d_st, uint32_t *d_ev,
-                                              double *d_images, int32_t *d_n_hits, hipStream_t s, const DiskParams &dp);
+                                              double *d_images, int32_t *d_n_hits, hipStream_t s, const DiskParams &dp,
+                                              const DiskRecordsBuf &recs);
 
 // disk == NULL: the frame path.  Else the disk frame (lt_render_disk_dev): every row traced, the disk kernels.
 static int render_dev_impl(const lt_camera *cam, const lt_metric *metric, const lt_opts *opts, const float *d_bg,
@@ -816,6 +845,8 @@ static int render_dev_impl(const lt_camera *cam, const lt_metric *metric, const 
     size_t elem = o.precision == 32 ? sizeof(float) : sizeof(double);
     Workspace w;
     if ((rc = get_workspace(s, (size_t)n_q, elem, &w))) return rc;
+    DiskRecordsBuf recs;
+    if ((rc = get_disk_records(s, n_q, elem, disk, &recs))) return rc;
     void *ic = w.ic, *fin0 = w.fin0, *fin1 = w.fin1;
     Timer tm;
     if ((rc = tm.begin(o.timing != 0, own_events))) return rc;
@@ -830,19 +861,16 @@ static int render_dev_impl(const lt_camera *cam, const lt_metric *metric, const 
     else k_prologue_camera<double><<<gq, 256, 0, s>>>(c, mc, (double4 *)ic, n_q);
     HIP_TRY(hipGetLastError());
     if ((rc = tm.mark(1, s))) return rc;
-    if (disk && disk->max_images)
-        rc = o.precision == 32 ? launch_integrate_disk_images<float>(mc, o, lambda_max, w, n_q, s, d_stats, *disk)
-                               : launch_integrate_disk_images<double>(mc, o, lambda_max, w, n_q, s, d_stats, *disk);
-    else if (disk)
-        rc = o.precision == 32 ? launch_integrate_disk<float>(mc, o, lambda_max, w, n_q, s, d_stats, *disk)
-                               : launch_integrate_disk<double>(mc, o, lambda_max, w, n_q, s, d_stats, *disk);
+    if (disk)
+        rc = o.precision == 32 ? launch_integrate_disk<float>(mc, o, lambda_max, w, n_q, s, d_stats, *disk, recs)
+                               : launch_integrate_disk<double>(mc, o, lambda_max, w, n_q, s, d_stats, *disk, recs);
     else
         rc = o.precision == 32 ? launch_integrate<float>(mc, o, lambda_max, w, n_q, s, d_stats)
                                : launch_integrate<double>(mc, o, lambda_max, w, n_q, s, d_stats);
     if (rc) return rc;
     if ((rc = tm.mark(2, s))) return rc;
     if (disk) {
-        rc = disk->max_images ? launch_epilogue_disk_images(c, mc, o, w, n_q, fo, d_stats, s, *disk)
+        rc = disk->max_images ? launch_epilogue_disk_images(c, mc, o, w, n_q, fo, d_stats, s, *disk, recs)
                               : launch_epilogue_disk(c, mc, o, w, fo, d_stats, s, *disk);
         if (rc) return rc;
         if ((rc = tm.mark(3, s))) return rc;
@@ -867,7 +895,7 @@ static int render_dev_impl(const lt_camera *cam, const lt_metric *metric, const 
             else k_epilogue_frame<double, false><<<ge, EPILOGUE_BLOCK, 0, s>>>(c, mc, (const double4 *)fin0, (const double4 *)fin1, fo);
         }
     }
-    if (d_stats) k_stats_reduce<<<1, STAT_SLOTS, 0, s>>>(w.partials, (unsigned long long *)d_stats);
+    if (d_stats) k_stats_reduce<<<1, STAT_SLOTS, 0, s>>>(w.partials, (unsigned long long *)d_stats, LT_STAT_BG_TILES_LDS, LT_STAT_BG_TILES_GLOBAL);
     HIP_TRY(hipGetLastError());
     if ((rc = tm.mark(3, s))) return rc;
     tm.finish();
@@ -1157,6 +1185,8 @@ static int trace_batch(const MetricConsts &mc, lt_opts &o, double lambda_max, co
     hipStream_t s = nullptr;
     Workspace w;
     if ((rc = get_workspace(s, (size_t)n_q, elem, &w))) return rc;
+    DiskRecordsBuf recs;
+    if ((rc = get_disk_records(s, n_q, elem, disk, &recs))) return rc;
     void *ic = w.ic, *fin0 = w.fin0, *fin1 = w.fin1;
     StreamSlot *sl;
     if ((rc = get_slot(s, &sl))) return rc;
@@ -1185,19 +1215,16 @@ static int trace_batch(const MetricConsts &mc, lt_opts &o, double lambda_max, co
     if (o.precision == 32) k_prologue_arrays<float><<<gq, 256, 0, s>>>(mc, d_al, d_th, d_ref, n, (float4 *)ic, n_q);
     else k_prologue_arrays<double><<<gq, 256, 0, s>>>(mc, d_al, d_th, d_ref, n, (double4 *)ic, n_q);
     HIP_TRY(hipGetLastError());
-    if (disk && disk->max_images)
-        rc = o.precision == 32 ? launch_integrate_disk_images<float>(mc, o, lambda_max, w, n_q, s, nullptr, *disk)
-                               : launch_integrate_disk_images<double>(mc, o, lambda_max, w, n_q, s, nullptr, *disk);
-    else if (disk)
-        rc = o.precision == 32 ? launch_integrate_disk<float>(mc, o, lambda_max, w, n_q, s, nullptr, *disk)
-                               : launch_integrate_disk<double>(mc, o, lambda_max, w, n_q, s, nullptr, *disk);
+    if (disk)
+        rc = o.precision == 32 ? launch_integrate_disk<float>(mc, o, lambda_max, w, n_q, s, nullptr, *disk, recs)
+                               : launch_integrate_disk<double>(mc, o, lambda_max, w, n_q, s, nullptr, *disk, recs);
     else
         rc = o.precision == 32 ? launch_integrate<float>(mc, o, lambda_max, w, n_q, s, nullptr)
                                : launch_integrate<double>(mc, o, lambda_max, w, n_q, s, nullptr);
     if (rc) return rc;
     unsigned gn = (unsigned)((n + 255) / 256);
     if (disk && disk->max_images) {
-        if ((rc = launch_epilogue_arrays_disk_images(mc, o, w, n, n_q, d_fa, d_w, d_st, d_ev, d_img, d_hits, s, *disk))) return rc;
+        if ((rc = launch_epilogue_arrays_disk_images(mc, o, w, n, n_q, d_fa, d_w, d_st, d_ev, d_img, d_hits, s, *disk, recs))) return rc;
     } else if (disk) {
         const DiskShade ds{mc.M, mc.a, disk->r_in, disk->q, disk->exposure};
         if (o.precision == 32)

@@ -49,44 +49,24 @@ static int resolve_disk(const lt_metric *metric, double r_obs, int schedule, con
     return LT_OK;
 }
 
+// The integrate launch of both disks: the direct schedule of launch_integrate (launch_direct) with the disk's kernels,
+// 64-wide workgroups, no stamps.  dp.max_images > 0: the thin disk, which also gets its records (recs).
 template <typename T>
-static int launch_integrate_disk(const MetricConsts &mc, const lt_opts &o, double lambda_max, const Workspace &w,
-                                 int64_t n_q, hipStream_t s, uint64_t *kstats, const DiskParams &dp)
+static int launch_integrate_disk(const MetricConsts &mc, const lt_opts &o, double lambda_max, const Workspace &w, int64_t n_q,
+                                 hipStream_t s, uint64_t *kstats, const DiskParams &dp, const DiskRecordsBuf &recs)
 {
     using V = typename Vec4<T>::type;
+    using V2 = typename Vec2<T>::type;
     const KerrConsts<T> k = make_kerr<T>(mc, lambda_max, o.h_max);
     const DiskConsts<T> d{(T)dp.r_in, (T)dp.r_out, (T)(1.0 / (mc.r_plus * mc.r_plus))};
-    const bool exact = o.integrator == LT_INTEGRATOR_DP45_EXACT;
-    const bool dp45 = o.integrator == LT_INTEGRATOR_DP45 || exact;
-    if (dp45 && sizeof(T) != 8) return fail(LT_ERR_UNSUPPORTED, "DP45 needs precision 64");
-    // as the direct schedule of launch_integrate: 64-wide workgroups, a grid that fills the chip once and tiles handed
-    // out from the queue head (LT_D_PERSIST=0: one workgroup per tile), "long" after LT_D_LONG iterations
-    static const int long_iters = env_int("LT_D_LONG", 384);
-    static const int persist = env_int("LT_D_PERSIST", 1);
-    unsigned kgrid = (unsigned)((n_q + 63) / 64);
-    unsigned long long *head = nullptr;
-    auto resident_grid = [&](int slots) {
-        if (persist && slots > 0 && (unsigned)slots < kgrid) { kgrid = (unsigned)slots; head = w.head; }
-    };
-    if constexpr (sizeof(T) == 8) {
-        if (dp45 && !exact) {
-            resident_grid(resident_slots<k_kerr_disk<T, Dp45<T>>>());
-            if (head) HIP_TRY(hipMemsetAsync(head, 0, sizeof(unsigned long long), s));
-            k_kerr_disk<T, Dp45<T>><<<kgrid, 64, 0, s>>>(k, d, (const V *)w.ic, (V *)w.fin0, (V *)w.fin1, n_q, (uint32_t)(long_iters / 3), kstats, head);
-        }
-        if (exact) {
-            resident_grid(resident_slots<k_kerr_disk<T, Dp45<T, true>>>());
-            if (head) HIP_TRY(hipMemsetAsync(head, 0, sizeof(unsigned long long), s));
-            k_kerr_disk<T, Dp45<T, true>><<<kgrid, 64, 0, s>>>(k, d, (const V *)w.ic, (V *)w.fin0, (V *)w.fin1, n_q, (uint32_t)(long_iters / 3), kstats, head);
-        }
-    }
-    if (!dp45) {
-        resident_grid(resident_slots<k_kerr_disk<T, Rk4<T>>>());
-        if (head) HIP_TRY(hipMemsetAsync(head, 0, sizeof(unsigned long long), s));
-        k_kerr_disk<T, Rk4<T>><<<kgrid, 64, 0, s>>>(k, d, (const V *)w.ic, (V *)w.fin0, (V *)w.fin1, n_q, (uint32_t)long_iters, kstats, head);
-    }
-    HIP_TRY(hipGetLastError());
-    return LT_OK;
+    if (dp.max_images)
+        return launch_direct<T, DiskImagesKernels<T>>(o, w, n_q, s, 64, [&](auto kernel, unsigned grid, uint32_t long_iters, unsigned long long *head) {
+            kernel<<<grid, 64, 0, s>>>(k, d, (const V *)w.ic, (V *)w.fin0, (V *)w.fin1, n_q, long_iters, kstats, head, (V2 *)recs.img,
+                                       recs.hits, dp.max_images);
+        });
+    return launch_direct<T, DiskKernels<T>>(o, w, n_q, s, 64, [&](auto kernel, unsigned grid, uint32_t long_iters, unsigned long long *head) {
+        kernel<<<grid, 64, 0, s>>>(k, d, (const V *)w.ic, (V *)w.fin0, (V *)w.fin1, n_q, long_iters, kstats, head);
+    });
 }
 
 static int launch_epilogue_disk(const CamConsts &c, const MetricConsts &mc, const lt_opts &o, const Workspace &w,
@@ -102,7 +82,8 @@ static int launch_epilogue_disk(const CamConsts &c, const MetricConsts &mc, cons
         if (has_bg) k_epilogue_disk<double, true><<<ge, EPILOGUE_BLOCK, 0, s>>>(c, mc, ds, (const double4 *)w.fin0, (const double4 *)w.fin1, fo, dp.d_disk);
         else k_epilogue_disk<double, false><<<ge, EPILOGUE_BLOCK, 0, s>>>(c, mc, ds, (const double4 *)w.fin0, (const double4 *)w.fin1, fo, dp.d_disk);
     }
-    if (d_stats) k_stats_reduce_disk<<<1, STAT_SLOTS, 0, s>>>(w.partials, (unsigned long long *)d_stats);
+    // (this epilogue fills no word 7: its destination is the frame path's)
+    if (d_stats) k_stats_reduce<<<1, STAT_SLOTS, 0, s>>>(w.partials, (unsigned long long *)d_stats, LT_STAT_DISK, LT_STAT_BG_TILES_GLOBAL);
     HIP_TRY(hipGetLastError());
     return LT_OK;
 }

@@ -13,79 +13,26 @@ static int check_max_images(int32_t max_images)
 
 // The integrate kernel's hit records of (current device, stream): Vec2<T> [max_images][n_q], then the counts
 // uint32 [n_q].  A buffer of its own, so that the frame workspace keeps its layout; the integrate kernel writes every
-// count and the epilogues read only the slots below it, so nothing here is zeroed.  The integrate launch and the
-// epilogue of one call ask for the same size and get the same pointers.
-static int get_disk_records(hipStream_t s, int64_t n_q, size_t elem, int max_images, void **img, uint32_t **hits)
+// count and the epilogues read only the slots below it, so nothing here is zeroed.  Nothing to do without a thin disk.
+static int get_disk_records(hipStream_t s, int64_t n_q, size_t elem, const DiskParams *disk, DiskRecordsBuf *recs)
 {
+    if (!disk || !disk->max_images) return LT_OK;
     StreamSlot *sl;
     int rc = get_slot(s, &sl);
     if (rc) return rc;
-    const size_t img_bytes = (size_t)max_images * (size_t)n_q * 2 * elem;
+    const size_t img_bytes = (size_t)disk->max_images * (size_t)n_q * 2 * elem;
     if ((rc = grow(sl->disk_img, img_bytes + (size_t)n_q * sizeof(uint32_t), s))) return rc;
-    *img = sl->disk_img.p;
-    *hits = (uint32_t *)((char *)sl->disk_img.p + img_bytes);
-    return LT_OK;
-}
-
-template <typename T>
-static int launch_integrate_disk_images(const MetricConsts &mc, const lt_opts &o, double lambda_max, const Workspace &w,
-                                        int64_t n_q, hipStream_t s, uint64_t *kstats, const DiskParams &dp)
-{
-    using V = typename Vec4<T>::type;
-    using V2 = typename Vec2<T>::type;
-    const KerrConsts<T> k = make_kerr<T>(mc, lambda_max, o.h_max);
-    const DiskConsts<T> d{(T)dp.r_in, (T)dp.r_out, (T)(1.0 / (mc.r_plus * mc.r_plus))};
-    const bool exact = o.integrator == LT_INTEGRATOR_DP45_EXACT;
-    const bool dp45 = o.integrator == LT_INTEGRATOR_DP45 || exact;
-    if (dp45 && sizeof(T) != 8) return fail(LT_ERR_UNSUPPORTED, "DP45 needs precision 64");
-    void *img = nullptr;
-    uint32_t *hits = nullptr;
-    int rc = get_disk_records(s, n_q, sizeof(T), dp.max_images, &img, &hits);
-    if (rc) return rc;
-    // grid, tile queue and "long" threshold as launch_integrate_disk
-    static const int long_iters = env_int("LT_D_LONG", 384);
-    static const int persist = env_int("LT_D_PERSIST", 1);
-    unsigned kgrid = (unsigned)((n_q + 63) / 64);
-    unsigned long long *head = nullptr;
-    auto resident_grid = [&](int slots) {
-        if (persist && slots > 0 && (unsigned)slots < kgrid) { kgrid = (unsigned)slots; head = w.head; }
-    };
-    if constexpr (sizeof(T) == 8) {
-        if (dp45 && !exact) {
-            resident_grid(resident_slots<k_kerr_disk_images<T, Dp45<T>>>());
-            if (head) HIP_TRY(hipMemsetAsync(head, 0, sizeof(unsigned long long), s));
-            k_kerr_disk_images<T, Dp45<T>><<<kgrid, 64, 0, s>>>(k, d, (const V *)w.ic, (V *)w.fin0, (V *)w.fin1, n_q, (uint32_t)(long_iters / 3),
-                                                                kstats, head, (V2 *)img, hits, dp.max_images);
-        }
-        if (exact) {
-            resident_grid(resident_slots<k_kerr_disk_images<T, Dp45<T, true>>>());
-            if (head) HIP_TRY(hipMemsetAsync(head, 0, sizeof(unsigned long long), s));
-            k_kerr_disk_images<T, Dp45<T, true>><<<kgrid, 64, 0, s>>>(k, d, (const V *)w.ic, (V *)w.fin0, (V *)w.fin1, n_q,
-                                                                      (uint32_t)(long_iters / 3), kstats, head, (V2 *)img, hits,
-                                                                      dp.max_images);
-        }
-    }
-    if (!dp45) {
-        resident_grid(resident_slots<k_kerr_disk_images<T, Rk4<T>>>());
-        if (head) HIP_TRY(hipMemsetAsync(head, 0, sizeof(unsigned long long), s));
-        k_kerr_disk_images<T, Rk4<T>><<<kgrid, 64, 0, s>>>(k, d, (const V *)w.ic, (V *)w.fin0, (V *)w.fin1, n_q, (uint32_t)long_iters,
-                                                           kstats, head, (V2 *)img, hits, dp.max_images);
-    }
-    HIP_TRY(hipGetLastError());
+    recs->img = sl->disk_img.p;
+    recs->hits = (uint32_t *)((char *)sl->disk_img.p + img_bytes);
     return LT_OK;
 }
 
 static int launch_epilogue_disk_images(const CamConsts &c, const MetricConsts &mc, const lt_opts &o, const Workspace &w,
                                        int64_t n_q, const FrameOut &fo, uint64_t *d_stats, hipStream_t s,
-                                       const DiskParams &dp)
+                                       const DiskParams &dp, const DiskRecordsBuf &recs)
 {
-    const size_t elem = o.precision == 32 ? sizeof(float) : sizeof(double);
-    void *img = nullptr;
-    uint32_t *hits = nullptr;
-    int rc = get_disk_records(s, n_q, elem, dp.max_images, &img, &hits);
-    if (rc) return rc;
     const DiskShade ds{mc.M, mc.a, dp.r_in, dp.q, dp.exposure};
-    const DiskImagesOut di{img, hits, n_q, dp.max_images, dp.d_images, dp.d_n_hits};
+    const DiskImagesOut di{recs.img, recs.hits, n_q, dp.max_images, dp.d_images, dp.d_n_hits};
     const bool has_bg = fo.bg != nullptr && (fo.rgb || fo.rgba);
     const dim3 ge((unsigned)((c.W + EPILOGUE_BLOCK - 1) / EPILOGUE_BLOCK), (unsigned)c.rows_local);
     if (o.precision == 32) {
@@ -95,28 +42,24 @@ static int launch_epilogue_disk_images(const CamConsts &c, const MetricConsts &m
         if (has_bg) k_epilogue_disk_images<double, true><<<ge, EPILOGUE_BLOCK, 0, s>>>(c, mc, ds, (const double4 *)w.fin0, (const double4 *)w.fin1, fo, di);
         else k_epilogue_disk_images<double, false><<<ge, EPILOGUE_BLOCK, 0, s>>>(c, mc, ds, (const double4 *)w.fin0, (const double4 *)w.fin1, fo, di);
     }
-    if (d_stats) k_stats_reduce_disk_images<<<1, STAT_SLOTS, 0, s>>>(w.partials, (unsigned long long *)d_stats);
+    if (d_stats) k_stats_reduce<<<1, STAT_SLOTS, 0, s>>>(w.partials, (unsigned long long *)d_stats, LT_STAT_DISK, LT_STAT_DISK_HITS);
     HIP_TRY(hipGetLastError());
     return LT_OK;
 }
 
 static int launch_epilogue_arrays_disk_images(const MetricConsts &mc, const lt_opts &o, const Workspace &w, int64_t n,
                                               int64_t n_q, double *d_fa, int64_t *d_w, int8_t *d_st, uint32_t *d_ev,
-                                              double *d_images, int32_t *d_n_hits, hipStream_t s, const DiskParams &dp)
+                                              double *d_images, int32_t *d_n_hits, hipStream_t s, const DiskParams &dp,
+                                              const DiskRecordsBuf &recs)
 {
-    const size_t elem = o.precision == 32 ? sizeof(float) : sizeof(double);
-    void *img = nullptr;
-    uint32_t *hits = nullptr;
-    int rc = get_disk_records(s, n_q, elem, dp.max_images, &img, &hits);
-    if (rc) return rc;
     const DiskShade ds{mc.M, mc.a, dp.r_in, dp.q, dp.exposure};
     const unsigned gn = (unsigned)((n + 255) / 256);
     if (o.precision == 32)
         k_epilogue_arrays_disk_images<float><<<gn, 256, 0, s>>>(mc, ds, (const float4 *)w.fin0, (const float4 *)w.fin1, n, d_fa, d_w, d_st, d_ev,
-                                                                (const float2 *)img, hits, n_q, dp.max_images, d_images, d_n_hits);
+                                                                (const float2 *)recs.img, recs.hits, n_q, dp.max_images, d_images, d_n_hits);
     else
         k_epilogue_arrays_disk_images<double><<<gn, 256, 0, s>>>(mc, ds, (const double4 *)w.fin0, (const double4 *)w.fin1, n, d_fa, d_w, d_st, d_ev,
-                                                                 (const double2 *)img, hits, n_q, dp.max_images, d_images, d_n_hits);
+                                                                 (const double2 *)recs.img, recs.hits, n_q, dp.max_images, d_images, d_n_hits);
     HIP_TRY(hipGetLastError());
     return LT_OK;
 }

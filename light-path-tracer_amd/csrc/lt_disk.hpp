@@ -1,5 +1,7 @@
-// lt_disk.hpp -- the thin Keplerian accretion disk of lt_render_disk (include/ltrace.h): the disk variant of the direct
-// integrate kernel (K2) and its epilogue (K3).  K1 is the frame path's prologue, unchanged.
+// lt_disk.hpp -- the thin Keplerian accretion disk of lt_render_disk (include/ltrace.h): the disk test behind an
+// integrator's iteration (disk_advance), the disk's hooks into the tile loop of the direct schedule (DiskStep; the loop
+// itself is direct_tiles, lt_kernels.hpp, shared with the plain frame path), the kernel k_kerr_disk (K2) and its
+// epilogues (K3).  K1 is the frame path's prologue, unchanged.
 //
 // The disk lies in the equatorial plane between r_in and r_out.  A ray (traced backward from the camera) hits it at the
 // first strict sign change of theta - pi/2 between two consecutive accepted states whose crossing point has
@@ -7,10 +9,10 @@
 // interpolant of the step in lambda, with the derivatives from the Kerr right-hand side at both ends (two extra
 // evaluations, once per hit ray), and replaces the ray's final state; the event is EV_DISK.
 //
-// Nothing here changes a step: the disk kernel calls the integrators' own advance() and streak(), and only looks at the
+// Nothing here changes a step: the disk's hooks call the integrators' own advance() and streak(), and only look at the
 // states they produce.  A lane's arithmetic never depends on which rays share its wavefront (lt_device.hpp), so a ray
 // that misses the disk ends with the same bits as in k_kerr_direct, and its pixel is the frame path's pixel.
-// Disk parameters travel as a kernel argument of their own (DiskConsts): KerrConsts and the existing kernels are untouched.
+// Disk parameters travel as a kernel argument of their own (DiskConsts), not in KerrConsts.
 #pragma once
 #include "lt_kernels.hpp"
 
@@ -102,10 +104,12 @@ __device__ __forceinline__ bool disk_crossing(const KerrConsts<T> &k, const Disk
 
 // One iteration of Integ with the disk test behind it.  The common path adds a sign test of theta - pi/2 on both states,
 // a min / max of their radii against the annulus widened by the largest radial move of the step, and ONE wave-uniform
-// branch.  `vmax2`: twice disk_vmax of the ray.
-template <typename T, typename Integ>
+// branch.  `vmax2`: twice disk_vmax of the ray.  A crossing inside the annulus, on a lane with `act` set, goes to
+// `on_hit(s, hit, ev)`, which returns the iteration's event: the opaque disk ends the ray there, the thin one records
+// the point and lets the ray go on.
+template <typename T, typename Integ, typename OnHit>
 __device__ __forceinline__ int disk_advance(const KerrConsts<T> &k, const DiskConsts<T> &d, const RayConsts<T> &rc,
-                                            T vmax2, typename Integ::State &s)
+                                            T vmax2, typename Integ::State &s, bool act, OnHit on_hit)
 {
     const T HALF_PI = T(1.5707963267948966);
     const typename Integ::State before = s;
@@ -132,18 +136,14 @@ __device__ __forceinline__ int disk_advance(const KerrConsts<T> &k, const DiskCo
                 const T denom = y1.r - before.y.r;
                 t_end = denom == T(0) ? T(1) : M<T>::min(M<T>::max((target - before.y.r) / denom, T(0)), T(1));
             }
-            if (disk_crossing(k, d, rc, before.y, y1, h, t_end, hit)) {
-                s.y = hit;
-                ev = EV_DISK;
-            }
+            if (disk_crossing(k, d, rc, before.y, y1, h, t_end, hit) & act) ev = on_hit(s, hit, ev);
         }
     }
     return ev;
 }
 
-// Direct schedule with the disk: k_kerr_direct's tile loop, persistent tile queue and ghost-lane phase, line for line,
-// with Integ::advance replaced by disk_advance and the far-field streak gated (below).  (A separate kernel rather than a
-// template parameter of k_kerr_direct: that kernel's code and name stay exactly what they were.)
+// The disk's hooks into the tile loop of the direct schedule (direct_tiles, lt_kernels.hpp): disk_advance in place of
+// Integ::advance, with the crossing point taking the ray's place, and the far-field streak gated.
 //
 // The streak gate.  kerr_rk4_streak takes up to 64 steps with no test but r >= rc4 at the end of each; here it runs with
 // rc4 raised, per lane, to r_gate = r_out + 2 h_base vmax2.  Every step it takes then starts and ends at r >= r_gate,
@@ -151,6 +151,30 @@ __device__ __forceinline__ int disk_advance(const KerrConsts<T> &k, const DiskCo
 // at most 0.15 h (|r'_0| + |r'_1|)) stays within h_base vmax2 of either end: above r_out, so no streak step can hold a
 // hit.  Wherever the gate fails the ray steps through disk_advance.  The streak's steps are the general iteration's
 // arithmetic (lt_device.hpp), so the gate changes no bit of any state.
+template <typename T, typename Integ> struct DiskStep {
+    DiskConsts<T> d;
+    struct Lane {
+        T vmax2;          // twice disk_vmax of the lane's ray
+        KerrConsts<T> kg; // the streak's constants: rc4 raised to the gate radius
+    };
+    __device__ __forceinline__ void begin_tile(Lane &l, const KerrConsts<T> &k) { l.kg = k; }
+    __device__ __forceinline__ void bind(Lane &l, const KerrConsts<T> &k, const RayConsts<T> &rc)
+    {
+        l.vmax2 = T(2) * disk_vmax(k, d, rc);
+        l.kg.rc4 = M<T>::max(k.rc4, M<T>::fma(T(2) * rc.hb, l.vmax2, d.r_out));
+    }
+    __device__ __forceinline__ const KerrConsts<T> &streak_consts(const Lane &l, const KerrConsts<T> &) const { return l.kg; }
+    __device__ __forceinline__ int advance(Lane &l, const KerrConsts<T> &k, const RayConsts<T> &rc, typename Integ::State &st, int64_t, bool)
+    {
+        return disk_advance<T, Integ>(k, d, rc, l.vmax2, st, true, [](typename Integ::State &s, const State5<T> &hit, int) {
+            s.y = hit;
+            return (int)EV_DISK;
+        });
+    }
+    __device__ __forceinline__ void stored(Lane &, int64_t) {}
+};
+
+// (A kernel of its own rather than a template parameter of k_kerr_direct: that kernel's code and name stay what they were.)
 template <typename T, typename Integ>
 __global__ void __launch_bounds__(256, Integ::MIN_WAVES_PER_SIMD) k_kerr_disk(KerrConsts<T> k_in, DiskConsts<T> d,
                                                        const typename Vec4<T>::type *__restrict__ ic,
@@ -159,88 +183,9 @@ __global__ void __launch_bounds__(256, Integ::MIN_WAVES_PER_SIMD) k_kerr_disk(Ke
                                                        uint32_t long_iters, uint64_t *__restrict__ kstats,
                                                        unsigned long long *__restrict__ head)
 {
-    KerrConsts<T> k = k_in;
-    pin_consts(k);
-    const int lane = (int)(threadIdx.x & 63u);
-    int64_t tile = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    for (;;) {
-    if (head) {
-        unsigned long long w = 0;
-        if (lane == 0) w = atomicAdd(head, 1ull);
-        tile = (int64_t)(((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(w >> 32)) << 32) |
-                         (uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)w));
-    }
-    const int64_t q = tile * 64 + lane;
-    if (q >= n_q) return;
-    WaveMeter meter;
-    meter.begin(kstats, tile);
-    typename Vec4<T>::type rec = ic[q];
-    int flags = (int)rec.w;
-    typename Integ::State st;
-    st.y.r = k.r_obs; st.y.th = k.theta_obs; st.y.ph = T(0); st.y.pr = rec.x; st.y.pth = rec.y;
-    st.steps = 0;
-    int ev = (flags & FLAG_PAD) ? EV_PAD : EV_INVALID;
-    uint32_t wave_iters = 0;
-    bool raised = false;
-    RayConsts<T> rc = make_ray_consts(k, rec.z, (flags & FLAG_REFINE) != 0);
-    T vmax2 = T(2) * disk_vmax(k, d, rc);
-    KerrConsts<T> kg = k; // the streak's constants: rc4 raised to the gate radius
-    kg.rc4 = M<T>::max(k.rc4, M<T>::fma(T(2) * rc.hb, vmax2, d.r_out));
-    if (flags & FLAG_OK) {
-        Integ::start(k, rc, st, rec.x, rec.y);
-        uint32_t it = 0;
-        do {
-            it += Integ::streak(kg, rc, st, 64u);
-            ev = disk_advance<T, Integ>(k, d, rc, vmax2, st);
-            ++it;
-            if (Integ::GHOST_LANES) {
-                if (it >= long_iters) break;
-            } else if (it >= long_iters && !raised) {
-                __builtin_amdgcn_s_setprio(3);
-                raised = true;
-            }
-        } while (ev == EV_RUNNING);
-        wave_iters = it;
-    }
-    uint32_t steps = st.steps;
-    bool real = ev == EV_RUNNING;
-    if (Integ::GHOST_LANES && wave_any(real)) {
-        __builtin_amdgcn_s_setprio(3);
-        raised = true;
-        if (!real) store_fin<T>(fin0, fin1, q, st.y.r, st.y.th, st.y.ph, st.y.pr, st.y.pth, rec.z, ev, steps);
-        uint32_t lead = (uint32_t)__builtin_ctzll(__builtin_amdgcn_ballot_w64(real));
-        uint32_t it = (uint32_t)__builtin_amdgcn_readlane((int)wave_iters, (int)lead);
-        bool sync = true;
-        for (;;) {
-            if (sync) {
-                lead = (uint32_t)__builtin_ctzll(__builtin_amdgcn_ballot_w64(real));
-                take_from_lane(st, lead, !real);
-                take_from_lane(rc, lead, !real);
-                vmax2 = T(2) * disk_vmax(k, d, rc);
-                kg.rc4 = M<T>::max(k.rc4, M<T>::fma(T(2) * rc.hb, vmax2, d.r_out));
-                sync = false;
-            }
-            it += Integ::streak_lone(kg, rc, st, 64u);
-            int e = disk_advance<T, Integ>(k, d, rc, vmax2, st);
-            ++it;
-            if (wave_any(e != EV_RUNNING)) {
-                if (real & (e != EV_RUNNING)) {
-                    steps = st.steps;
-                    store_fin<T>(fin0, fin1, q, st.y.r, st.y.th, st.y.ph, st.y.pr, st.y.pth, rec.z, e, steps);
-                    real = false;
-                }
-                if (!wave_any(real)) break;
-                sync = true;
-            }
-        }
-        wave_iters = it;
-    } else {
-        store_fin<T>(fin0, fin1, q, st.y.r, st.y.th, st.y.ph, st.y.pr, st.y.pth, rec.z, ev, steps);
-    }
-    meter.end(kstats, wave_iters);
-    if (!head) return;
-    if (__builtin_amdgcn_ballot_w64(raised)) __builtin_amdgcn_s_setprio(0);
-    }
+    DiskStep<T, Integ> step;
+    step.d = d;
+    direct_tiles<T, Integ>(k_in, step, ic, fin0, fin1, n_q, long_iters, nullptr, kstats, head);
 }
 
 // ---- K3 ---------------------------------------------------------------------------------------------------------------
@@ -260,20 +205,24 @@ __device__ __forceinline__ double disk_redshift(double M_, double a, double r, d
     return 1.0 / (ut * (1.0 - omega * xi));
 }
 
-// I = exposure g^4 (r_in / r)^q, s = g (r_in / r)^(3/4), rgb = clamp(I ramp(s), 0, 1),
-// ramp(s) = (clamp(2s, 0, 1), clamp(2s - 0.5, 0, 1), clamp(2s - 1, 0, 1)); one channel: the mean of the three.
-// Evaluated from the float32 values the caller gets in d_disk, so that the colour is a function of what is stored.
-__device__ __forceinline__ void disk_shade(const DiskShade &ds, float r32, float g32, int nch, float *rgb)
+// Light of one point of the disk, unclamped: E = I ramp(s) with I = exposure g^4 (r_in / r)^q, s = g (r_in / r)^(3/4),
+// ramp(s) = (clamp(2s, 0, 1), clamp(2s - 0.5, 0, 1), clamp(2s - 1, 0, 1)).  Evaluated in float64 from the float32 (r, g)
+// the caller gets in d_disk / d_images, so that the colour is a function of what is stored.
+__device__ __forceinline__ void disk_emission(const DiskShade &ds, float r32, float g32, double *e)
 {
     const double r = (double)r32, g = (double)g32;
     const double x = ds.r_in / r, g2 = g * g;
     const double I = ds.exposure * (g2 * g2) * pow(x, ds.q);
     const double s = g * pow(x, 0.75);
+    for (int i = 0; i < 3; ++i) e[i] = I * fmin(fmax(2.0 * s - 0.5 * i, 0.0), 1.0);
+}
+
+// Colour of a pixel of the opaque disk: rgb = clamp(E, 0, 1); one channel: the mean of the three.
+__device__ __forceinline__ void disk_shade(const DiskShade &ds, float r32, float g32, int nch, float *rgb)
+{
     double c[3];
-    for (int i = 0; i < 3; ++i) {
-        const double ramp = fmin(fmax(2.0 * s - 0.5 * i, 0.0), 1.0);
-        c[i] = fmin(fmax(I * ramp, 0.0), 1.0);
-    }
+    disk_emission(ds, r32, g32, c);
+    for (int i = 0; i < 3; ++i) c[i] = fmin(fmax(c[i], 0.0), 1.0);
     if (nch == 1) rgb[0] = (float)((c[0] + c[1] + c[2]) / 3.0);
     else { rgb[0] = (float)c[0]; rgb[1] = (float)c[1]; rgb[2] = (float)c[2]; }
 }
@@ -285,45 +234,6 @@ __device__ __forceinline__ double wrap_2pi(double ph)
     double w = ph - TWO_PI * floor(ph * (1.0 / TWO_PI));
     return (w >= TWO_PI || w < 0.0) ? 0.0 : w;
 }
-
-// Counters of the disk epilogue: the frame path's six plus the disk rays, in word 6 of the workgroup's partial set
-// (k_stats_reduce_disk moves it to LT_STAT_DISK).
-__device__ __forceinline__ void flush_stats_disk(uint64_t *stats, const StatAcc &a, bool disk, const MetricConsts &m)
-{
-    if (!stats) return;
-    __shared__ unsigned long long sh[7];
-    if (threadIdx.x < 7) sh[threadIdx.x] = 0;
-    __syncthreads();
-    uint32_t st = a.counted ? a.steps : 0u;
-    for (int off = 32; off > 0; off >>= 1) st += __shfl_xor(st, off, 64);
-    const unsigned long long rays = (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(a.counted));
-    const unsigned long long v[7] = {rays, st, rays * (unsigned long long)m.evals_fixed + (unsigned long long)st * (unsigned long long)m.evals_per_step,
-                                     (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(a.esc)),
-                                     (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(a.cap)),
-                                     (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(a.inv)),
-                                     (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(disk))};
-    if ((threadIdx.x & 63) == 0)
-        for (int i = 0; i < 7; ++i) if (v[i]) atomicAdd(&sh[i], v[i]);
-    __syncthreads();
-    unsigned long long *set = (unsigned long long *)stats + (size_t)((blockIdx.x + blockIdx.y * gridDim.x) % STAT_SLOTS) * 8;
-    if (threadIdx.x < 7 && sh[threadIdx.x]) atomicAdd(&set[threadIdx.x], sh[threadIdx.x]);
-}
-
-#ifndef LT_KERNEL_TEMPLATES_ONLY
-// k_stats_reduce with word 6 going to LT_STAT_DISK
-__global__ void __launch_bounds__(STAT_SLOTS) k_stats_reduce_disk(unsigned long long *__restrict__ partials,
-                                                                  unsigned long long *__restrict__ stats)
-{
-    unsigned long long *set = partials + (size_t)threadIdx.x * 8;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        unsigned long long v = wave_sum(set[i]);
-        set[i] = 0;
-        const int dst = i < 6 ? i : (i == 6 ? 12 : 11);
-        if (threadIdx.x == 0 && v) atomicAdd(&stats[dst], v);
-    }
-}
-#endif
 
 // One pixel per work-item, as k_epilogue_frame (global-gather background sampling).  EV_DISK records get the redshift
 // and the disk colour; every other record goes through load_result / shade exactly as there.  disk_out (R, W, 3) float32
@@ -371,17 +281,10 @@ __global__ void __launch_bounds__(EPILOGUE_BLOCK) k_epilogue_disk(CamConsts c, M
         if (o.rgb || o.rgba) {
             if (!on_disk) shade<HAS_BG>(c, o, ix, local_to_global_row(c, lrow), fa32, (int)wl, rgb, nch);
             if (o.rgb) for (int ch = 0; ch < nch; ++ch) o.rgb[p * nch + ch] = rgb[ch];
-            if (o.rgba) {
-                uchar4 px;
-                px.x = (uint8_t)(rgb[0] * 255.0f);
-                px.y = (uint8_t)(rgb[nch == 1 ? 0 : 1] * 255.0f);
-                px.z = (uint8_t)(rgb[nch == 1 ? 0 : 2] * 255.0f);
-                px.w = 255;
-                reinterpret_cast<uchar4 *>(o.rgba)[p] = px;
-            }
+            if (o.rgba) store_rgba(o, p, rgb, nch);
         }
     }
-    flush_stats_disk(o.stats, acc, on_disk, m);
+    flush_stats<7>(o.stats, acc, m, on_disk); // word 6: the rays that ended on the disk (-> LT_STAT_DISK)
 }
 
 // Epilogue of lt_trace_batch_kerr_disk: k_epilogue_arrays plus out_disk (n, 3) float64 (r_hit, phi_hit, g), NaN off the disk.

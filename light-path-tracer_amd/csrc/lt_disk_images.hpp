@@ -1,5 +1,6 @@
-// lt_disk_images.hpp -- the optically thin disk of lt_render_disk_images (include/ltrace.h): the integrate kernel that
-// records every crossing of the annulus and lets the ray go on, and its epilogues.  K1 is the frame path's prologue.
+// lt_disk_images.hpp -- the optically thin disk of lt_render_disk_images (include/ltrace.h): the hooks into the shared
+// tile loop (DiskImagesStep; direct_tiles, lt_kernels.hpp) that record every crossing of the annulus and let the ray go
+// on, the kernel k_kerr_disk_images, and its epilogues.  K1 is the frame path's prologue.
 //
 // Same disk as lt_disk.hpp (same crossing test, same refinement on the step's cubic Hermite, same redshift), but a hit
 // changes neither the ray's state nor its event: the lane writes (r, phi) of the crossing into slot j of a slot-major
@@ -17,55 +18,35 @@ template <> struct Vec2<double> { using type = double2; };
 
 constexpr int DISK_MAX_IMAGES = 8; // LT_DISK_MAX_IMAGES
 
-// Where the lane's hits go: img[j * n_q + q] for slot j < max_images.  Wave-uniform but for q.
-template <typename T> struct DiskRecords {
+// The thin disk's hooks into the tile loop (direct_tiles, lt_kernels.hpp): DiskStep's streak gate (its proof is per step:
+// it never needed the ray to stop) and disk test, with the crossing recorded instead of taking the ray's place.  A hit
+// goes to img[n * n_q + q] for n < max_images and is counted in n, the lane's hit count for the tile's ray; only a real
+// lane records (a ghost lane is a bitwise twin of the lead ray, whose hits are the lead's own, written by the lead).
+// hits[q]: the ray's hit count, stored with its final record.
+template <typename T, typename Integ> struct DiskImagesStep : DiskStep<T, Integ> {
     typename Vec2<T>::type *img;
+    uint32_t *hits;
     int64_t n_q;
     int max_images;
+    struct Lane : DiskStep<T, Integ>::Lane {
+        uint32_t n; // hits of the tile's ray so far
+    };
+    __device__ __forceinline__ void begin_tile(Lane &l, const KerrConsts<T> &k) { DiskStep<T, Integ>::begin_tile(l, k); l.n = 0; }
+    __device__ __forceinline__ int advance(Lane &l, const KerrConsts<T> &k, const RayConsts<T> &rc, typename Integ::State &st, int64_t q, bool real)
+    {
+        return disk_advance<T, Integ>(k, this->d, rc, l.vmax2, st, real, [&](typename Integ::State &, const State5<T> &hit, int ev) {
+            if (l.n < (uint32_t)max_images) {
+                typename Vec2<T>::type v;
+                v.x = hit.r; v.y = hit.ph;
+                img[(int64_t)l.n * n_q + q] = v;
+            }
+            ++l.n;
+            return ev;
+        });
+    }
+    __device__ __forceinline__ void stored(Lane &l, int64_t q) { hits[q] = l.n; }
 };
 
-// disk_advance with the crossing recorded instead of taking the ray's place.  `rec`: this lane writes records (false
-// on a ghost lane: a bitwise twin of the lead ray, whose hits are the lead's own).  `n`: the lane's hit count.
-template <typename T, typename Integ>
-__device__ __forceinline__ int disk_advance_images(const KerrConsts<T> &k, const DiskConsts<T> &d, const RayConsts<T> &rc,
-                                                   T vmax2, typename Integ::State &s, const DiskRecords<T> &out,
-                                                   int64_t q, bool rec, uint32_t &n)
-{
-    const T HALF_PI = T(1.5707963267948966);
-    const typename Integ::State before = s;
-    const int ev = Integ::advance(k, rc, s);
-    const T z0 = before.y.th - HALF_PI, z1 = s.y.th - HALF_PI;
-    const bool cross = ((z0 < T(0)) & (z1 >= T(0))) | ((z0 > T(0)) & (z1 <= T(0)));
-    const T pad = DiskStepLen<Integ>::bound(rc, before) * vmax2;
-    const bool near = (M<T>::min(before.y.r, s.y.r) <= d.r_out + pad) & (M<T>::max(before.y.r, s.y.r) >= d.r_in - pad);
-    const bool cand = cross & near;
-    if (__builtin_expect(wave_any(cand), 0)) {
-        if (cand) {
-            // (as disk_advance: a step that ends the ray by capture / escape is searched up to where the ray ended)
-            const T h = DiskStepLen<Integ>::h(k, rc, before);
-            State5<T> y1 = s.y, hit;
-            T t_end = T(1);
-            if (ev == EV_CAPTURED || ev == EV_ESCAPED) {
-                y1 = kerr_rk4_step(k, rc, before.y, h);
-                const T target = ev == EV_CAPTURED ? k.r_capture : k.r_escape;
-                const T denom = y1.r - before.y.r;
-                t_end = denom == T(0) ? T(1) : M<T>::min(M<T>::max((target - before.y.r) / denom, T(0)), T(1));
-            }
-            if (disk_crossing(k, d, rc, before.y, y1, h, t_end, hit) & rec) {
-                if (n < (uint32_t)out.max_images) {
-                    typename Vec2<T>::type v;
-                    v.x = hit.r; v.y = hit.ph;
-                    out.img[(int64_t)n * out.n_q + q] = v;
-                }
-                ++n;
-            }
-        }
-    }
-    return ev;
-}
-
-// k_kerr_disk with disk_advance_images: the same tile queue, streak gate (its proof is per step: it never needed the
-// ray to stop) and ghost-lane phase.  hits[q]: the ray's hit count, stored with its final record.
 template <typename T, typename Integ>
 __global__ void __launch_bounds__(256, Integ::MIN_WAVES_PER_SIMD) k_kerr_disk_images(KerrConsts<T> k_in, DiskConsts<T> d,
                                                        const typename Vec4<T>::type *__restrict__ ic,
@@ -76,152 +57,13 @@ __global__ void __launch_bounds__(256, Integ::MIN_WAVES_PER_SIMD) k_kerr_disk_im
                                                        typename Vec2<T>::type *__restrict__ img, uint32_t *__restrict__ hits,
                                                        int max_images)
 {
-    KerrConsts<T> k = k_in;
-    pin_consts(k);
-    const DiskRecords<T> out{img, n_q, max_images};
-    const int lane = (int)(threadIdx.x & 63u);
-    int64_t tile = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    for (;;) {
-    if (head) {
-        unsigned long long w = 0;
-        if (lane == 0) w = atomicAdd(head, 1ull);
-        tile = (int64_t)(((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(w >> 32)) << 32) |
-                         (uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)w));
-    }
-    const int64_t q = tile * 64 + lane;
-    if (q >= n_q) return;
-    WaveMeter meter;
-    meter.begin(kstats, tile);
-    typename Vec4<T>::type rec = ic[q];
-    int flags = (int)rec.w;
-    typename Integ::State st;
-    st.y.r = k.r_obs; st.y.th = k.theta_obs; st.y.ph = T(0); st.y.pr = rec.x; st.y.pth = rec.y;
-    st.steps = 0;
-    int ev = (flags & FLAG_PAD) ? EV_PAD : EV_INVALID;
-    uint32_t wave_iters = 0, n = 0;
-    bool raised = false;
-    RayConsts<T> rc = make_ray_consts(k, rec.z, (flags & FLAG_REFINE) != 0);
-    T vmax2 = T(2) * disk_vmax(k, d, rc);
-    KerrConsts<T> kg = k; // the streak's constants: rc4 raised to the gate radius
-    kg.rc4 = M<T>::max(k.rc4, M<T>::fma(T(2) * rc.hb, vmax2, d.r_out));
-    if (flags & FLAG_OK) {
-        Integ::start(k, rc, st, rec.x, rec.y);
-        uint32_t it = 0;
-        do {
-            it += Integ::streak(kg, rc, st, 64u);
-            ev = disk_advance_images<T, Integ>(k, d, rc, vmax2, st, out, q, true, n);
-            ++it;
-            if (Integ::GHOST_LANES) {
-                if (it >= long_iters) break;
-            } else if (it >= long_iters && !raised) {
-                __builtin_amdgcn_s_setprio(3);
-                raised = true;
-            }
-        } while (ev == EV_RUNNING);
-        wave_iters = it;
-    }
-    uint32_t steps = st.steps;
-    bool real = ev == EV_RUNNING;
-    if (Integ::GHOST_LANES && wave_any(real)) {
-        __builtin_amdgcn_s_setprio(3);
-        raised = true;
-        if (!real) {
-            store_fin<T>(fin0, fin1, q, st.y.r, st.y.th, st.y.ph, st.y.pr, st.y.pth, rec.z, ev, steps);
-            hits[q] = n;
-        }
-        uint32_t lead = (uint32_t)__builtin_ctzll(__builtin_amdgcn_ballot_w64(real));
-        uint32_t it = (uint32_t)__builtin_amdgcn_readlane((int)wave_iters, (int)lead);
-        bool sync = true;
-        for (;;) {
-            if (sync) {
-                lead = (uint32_t)__builtin_ctzll(__builtin_amdgcn_ballot_w64(real));
-                take_from_lane(st, lead, !real);
-                take_from_lane(rc, lead, !real);
-                vmax2 = T(2) * disk_vmax(k, d, rc);
-                kg.rc4 = M<T>::max(k.rc4, M<T>::fma(T(2) * rc.hb, vmax2, d.r_out));
-                sync = false;
-            }
-            it += Integ::streak_lone(kg, rc, st, 64u);
-            // only a real lane records: a ghost's hits are its lead's, written by the lead
-            int e = disk_advance_images<T, Integ>(k, d, rc, vmax2, st, out, q, real, n);
-            ++it;
-            if (wave_any(e != EV_RUNNING)) {
-                if (real & (e != EV_RUNNING)) {
-                    steps = st.steps;
-                    store_fin<T>(fin0, fin1, q, st.y.r, st.y.th, st.y.ph, st.y.pr, st.y.pth, rec.z, e, steps);
-                    hits[q] = n;
-                    real = false;
-                }
-                if (!wave_any(real)) break;
-                sync = true;
-            }
-        }
-        wave_iters = it;
-    } else {
-        store_fin<T>(fin0, fin1, q, st.y.r, st.y.th, st.y.ph, st.y.pr, st.y.pth, rec.z, ev, steps);
-        hits[q] = n;
-    }
-    meter.end(kstats, wave_iters);
-    if (!head) return;
-    if (__builtin_amdgcn_ballot_w64(raised)) __builtin_amdgcn_s_setprio(0);
-    }
+    DiskImagesStep<T, Integ> step;
+    step.d = d;
+    step.img = img; step.hits = hits; step.n_q = n_q; step.max_images = max_images;
+    direct_tiles<T, Integ>(k_in, step, ic, fin0, fin1, n_q, long_iters, nullptr, kstats, head);
 }
 
 // ---- K3 ---------------------------------------------------------------------------------------------------------------
-// Light of one stored hit, unclamped: E = exposure g^4 (r_in / r)^q ramp(s), s = g (r_in / r)^(3/4), float64 from the
-// float32 (r, g) the caller gets -- disk_shade's arithmetic without its clamp to [0, 1].
-__device__ __forceinline__ void disk_emission(const DiskShade &ds, float r32, float g32, double *e)
-{
-    const double r = (double)r32, g = (double)g32;
-    const double x = ds.r_in / r, g2 = g * g;
-    const double I = ds.exposure * (g2 * g2) * pow(x, ds.q);
-    const double s = g * pow(x, 0.75);
-    for (int i = 0; i < 3; ++i) e[i] = I * fmin(fmax(2.0 * s - 0.5 * i, 0.0), 1.0);
-}
-
-// Counters of the images epilogue: the frame path's six, the rays with at least one hit (word 6) and all hits
-// (word 7) of the workgroup's partial set; k_stats_reduce_disk_images moves them to LT_STAT_DISK / LT_STAT_DISK_HITS.
-__device__ __forceinline__ void flush_stats_disk_images(uint64_t *stats, const StatAcc &a, uint32_t hits, const MetricConsts &m)
-{
-    if (!stats) return;
-    __shared__ unsigned long long sh[8];
-    if (threadIdx.x < 8) sh[threadIdx.x] = 0;
-    __syncthreads();
-    uint32_t st = a.counted ? a.steps : 0u, nh = a.counted ? hits : 0u;
-    for (int off = 32; off > 0; off >>= 1) {
-        st += __shfl_xor(st, off, 64);
-        nh += __shfl_xor(nh, off, 64);
-    }
-    const unsigned long long rays = (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(a.counted));
-    const unsigned long long v[8] = {rays, st, rays * (unsigned long long)m.evals_fixed + (unsigned long long)st * (unsigned long long)m.evals_per_step,
-                                     (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(a.esc)),
-                                     (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(a.cap)),
-                                     (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(a.inv)),
-                                     (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(a.counted && hits > 0)),
-                                     (unsigned long long)nh};
-    if ((threadIdx.x & 63) == 0)
-        for (int i = 0; i < 8; ++i) if (v[i]) atomicAdd(&sh[i], v[i]);
-    __syncthreads();
-    unsigned long long *set = (unsigned long long *)stats + (size_t)((blockIdx.x + blockIdx.y * gridDim.x) % STAT_SLOTS) * 8;
-    if (threadIdx.x < 8 && sh[threadIdx.x]) atomicAdd(&set[threadIdx.x], sh[threadIdx.x]);
-}
-
-#ifndef LT_KERNEL_TEMPLATES_ONLY
-// k_stats_reduce with word 6 going to LT_STAT_DISK and word 7 to LT_STAT_DISK_HITS
-__global__ void __launch_bounds__(STAT_SLOTS) k_stats_reduce_disk_images(unsigned long long *__restrict__ partials,
-                                                                         unsigned long long *__restrict__ stats)
-{
-    unsigned long long *set = partials + (size_t)threadIdx.x * 8;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        unsigned long long v = wave_sum(set[i]);
-        set[i] = 0;
-        const int dst = i < 6 ? i : (i == 6 ? 12 : 13);
-        if (threadIdx.x == 0 && v) atomicAdd(&stats[dst], v);
-    }
-}
-#endif
-
 // Outputs of the images epilogue beyond FrameOut: images (R, W, max_images, 3) float32 (r_hit, phi_hit in [0, 2 pi), g),
 // NaN in unused slots; n_hits (R, W) saturating at 255.  Either may be NULL.
 struct DiskImagesOut {
@@ -286,16 +128,10 @@ __global__ void __launch_bounds__(EPILOGUE_BLOCK) k_epilogue_disk_images(CamCons
         }
         if (ns > 0) for (int ch = 0; ch < 3; ++ch) rgb[ch] = (float)fmin(fmax(sum[ch], 0.0), 1.0);
         if (o.rgb) for (int ch = 0; ch < nch; ++ch) o.rgb[p * nch + ch] = rgb[ch];
-        if (o.rgba) {
-            uchar4 px;
-            px.x = (uint8_t)(rgb[0] * 255.0f);
-            px.y = (uint8_t)(rgb[nch == 1 ? 0 : 1] * 255.0f);
-            px.z = (uint8_t)(rgb[nch == 1 ? 0 : 2] * 255.0f);
-            px.w = 255;
-            reinterpret_cast<uchar4 *>(o.rgba)[p] = px;
-        }
+        if (o.rgba) store_rgba(o, p, rgb, nch);
     }
-    flush_stats_disk_images(o.stats, acc, nh, m);
+    // words 6, 7: the rays with at least one hit and all hits (-> LT_STAT_DISK, LT_STAT_DISK_HITS)
+    flush_stats<8>(o.stats, acc, m, nh > 0, nh);
 }
 
 // Epilogue of lt_trace_batch_kerr_disk_images: k_epilogue_arrays plus out_images (n, max_images, 3) float64

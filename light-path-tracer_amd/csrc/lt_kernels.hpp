@@ -397,12 +397,35 @@ template <typename S> __device__ __forceinline__ void take_from_lane(S &s, uint3
 // chip idle on average -- and every finished wave left its slot empty until the dispatcher had set up the next one
 // (4.7 of 5 slots occupied).  A wave that takes the next tile itself does neither.  `head` == nullptr: one tile per
 // workgroup, tile = workgroup index (the batch twins' short launches, LT_D_PERSIST=0).
-template <typename T, typename Integ>
-__global__ void __launch_bounds__(256, Integ::MIN_WAVES_PER_SIMD) k_kerr_direct(KerrConsts<T> k_in, const typename Vec4<T>::type *__restrict__ ic,
-                                                         typename Vec4<T>::type *__restrict__ fin0,
-                                                         typename Vec4<T>::type *__restrict__ fin1, int64_t n_q,
-                                                         uint32_t long_iters, uint4 *__restrict__ stamps,
-                                                         uint64_t *__restrict__ kstats, unsigned long long *__restrict__ head)
+//
+// The loop is shared by the kernels of the direct schedule (k_kerr_direct here, k_kerr_disk, k_kerr_disk_images); what
+// they do differently is in `step`, a policy object passed by value (the kernel's own arguments), and in its Step::Lane,
+// what it keeps per ray next to `st` and `rc` (declared where they are: the order of the locals decides the compiler's
+// register assignment, and with it whether a kernel's code is what it was before the loop was shared):
+//   step.begin_tile(ls, k)                  start of a tile
+//   step.bind(ls, k, rc)                    the ray's constants exist: after make_ray_consts and after every ghost resync
+//   step.streak_consts(ls, k)               the constants the far-field streak runs with
+//   step.advance(ls, k, rc, st, q, real)    one general iteration; `real` is false on a ghost lane
+//   step.stored(ls, q)                      the lane has just stored the final record of ray q
+// PlainStep is the plain frame path: Integ's own iteration and nothing else.
+template <typename T, typename Integ> struct PlainStep {
+    struct Lane {};
+    __device__ __forceinline__ void begin_tile(Lane &, const KerrConsts<T> &) {}
+    __device__ __forceinline__ void bind(Lane &, const KerrConsts<T> &, const RayConsts<T> &) {}
+    __device__ __forceinline__ const KerrConsts<T> &streak_consts(const Lane &, const KerrConsts<T> &k) const { return k; }
+    __device__ __forceinline__ int advance(Lane &, const KerrConsts<T> &k, const RayConsts<T> &rc, typename Integ::State &st, int64_t, bool)
+    {
+        return Integ::advance(k, rc, st);
+    }
+    __device__ __forceinline__ void stored(Lane &, int64_t) {}
+};
+
+template <typename T, typename Integ, typename Step>
+__device__ __forceinline__ void direct_tiles(const KerrConsts<T> &k_in, Step step, const typename Vec4<T>::type *__restrict__ ic,
+                                             typename Vec4<T>::type *__restrict__ fin0,
+                                             typename Vec4<T>::type *__restrict__ fin1, int64_t n_q, uint32_t long_iters,
+                                             uint4 *__restrict__ stamps, uint64_t *__restrict__ kstats,
+                                             unsigned long long *__restrict__ head)
 {
     KerrConsts<T> k = k_in;
     pin_consts(k);
@@ -429,13 +452,16 @@ __global__ void __launch_bounds__(256, Integ::MIN_WAVES_PER_SIMD) k_kerr_direct(
     uint32_t wave_iters = 0; // loop iterations this wave issued (streak attempts + general iterations)
     bool raised = false;     // wave-uniform: the wave has raised its issue priority for this tile
     RayConsts<T> rc = make_ray_consts(k, rec.z, (flags & FLAG_REFINE) != 0);
+    typename Step::Lane ls;
+    step.begin_tile(ls, k);
+    step.bind(ls, k, rc);
     if (flags & FLAG_OK) {
         Integ::start(k, rc, st, rec.x, rec.y);
         // The iteration counter is uniform over the lanes still in the loop (SGPR), so the checks on it cost no VALU.
         uint32_t it = 0;
         do {
-            it += Integ::streak(k, rc, st, 64u);
-            ev = Integ::advance(k, rc, st);
+            it += Integ::streak(step.streak_consts(ls, k), rc, st, 64u);
+            ev = step.advance(ls, k, rc, st, q, true);
             ++it;
             if (Integ::GHOST_LANES) {
                 if (it >= long_iters) break;
@@ -454,7 +480,10 @@ __global__ void __launch_bounds__(256, Integ::MIN_WAVES_PER_SIMD) k_kerr_direct(
     if (Integ::GHOST_LANES && wave_any(real)) {
         __builtin_amdgcn_s_setprio(3);
         raised = true;
-        if (!real) store_fin<T>(fin0, fin1, q, st.y.r, st.y.th, st.y.ph, st.y.pr, st.y.pth, rec.z, ev, steps);
+        if (!real) {
+            store_fin<T>(fin0, fin1, q, st.y.r, st.y.th, st.y.ph, st.y.pr, st.y.pth, rec.z, ev, steps);
+            step.stored(ls, q);
+        }
         uint32_t lead = (uint32_t)__builtin_ctzll(__builtin_amdgcn_ballot_w64(real));
         uint32_t it = (uint32_t)__builtin_amdgcn_readlane((int)wave_iters, (int)lead); // every running lane holds the same count
         bool sync = true;
@@ -463,15 +492,18 @@ __global__ void __launch_bounds__(256, Integ::MIN_WAVES_PER_SIMD) k_kerr_direct(
                 lead = (uint32_t)__builtin_ctzll(__builtin_amdgcn_ballot_w64(real));
                 take_from_lane(st, lead, !real);
                 take_from_lane(rc, lead, !real);
+                step.bind(ls, k, rc);
                 sync = false;
             }
-            it += Integ::streak_lone(k, rc, st, 64u);
-            int e = Integ::advance(k, rc, st);
+            it += Integ::streak_lone(step.streak_consts(ls, k), rc, st, 64u);
+            // (only a real lane may write: a ghost's results are its lead's, written by the lead)
+            int e = step.advance(ls, k, rc, st, q, real);
             ++it;
             if (wave_any(e != EV_RUNNING)) {
                 if (real & (e != EV_RUNNING)) {
                     steps = st.steps;
                     store_fin<T>(fin0, fin1, q, st.y.r, st.y.th, st.y.ph, st.y.pr, st.y.pth, rec.z, e, steps);
+                    step.stored(ls, q);
                     real = false;
                 }
                 if (!wave_any(real)) break;
@@ -481,12 +513,23 @@ __global__ void __launch_bounds__(256, Integ::MIN_WAVES_PER_SIMD) k_kerr_direct(
         wave_iters = it;
     } else {
         store_fin<T>(fin0, fin1, q, st.y.r, st.y.th, st.y.ph, st.y.pr, st.y.pth, rec.z, ev, steps);
+        step.stored(ls, q);
     }
     meter.end(kstats, wave_iters);
     if (stamps) write_stamp(stamps, tile, t0, steps, c0);
     if (!head) return;
     if (__builtin_amdgcn_ballot_w64(raised)) __builtin_amdgcn_s_setprio(0); // back to the bulk's priority for the next tile
     }
+}
+
+template <typename T, typename Integ>
+__global__ void __launch_bounds__(256, Integ::MIN_WAVES_PER_SIMD) k_kerr_direct(KerrConsts<T> k_in, const typename Vec4<T>::type *__restrict__ ic,
+                                                         typename Vec4<T>::type *__restrict__ fin0,
+                                                         typename Vec4<T>::type *__restrict__ fin1, int64_t n_q,
+                                                         uint32_t long_iters, uint4 *__restrict__ stamps,
+                                                         uint64_t *__restrict__ kstats, unsigned long long *__restrict__ head)
+{
+    direct_tiles<T, Integ>(k_in, PlainStep<T, Integ>{}, ic, fin0, fin1, n_q, long_iters, stamps, kstats, head);
 }
 
 // Queue schedule: persistent wavefronts.  The grid is sized to fill the chip once (blocks = CUs x
@@ -745,36 +788,49 @@ struct StatAcc {
 // measurable.  k_stats_reduce folds the sets into the caller's counters and zeroes them for the next frame.
 constexpr int STAT_SLOTS = 64;
 
-__device__ __forceinline__ void flush_stats(uint64_t *stats, const StatAcc &a, const MetricConsts &m)
+// N words of the set: the frame path's six, then what the disk epilogues count per work-item -- word 6 the rays with
+// `flag` set (the ray ended on the disk / has a hit), word 7 the sum of `hits`.  Both are zero on a work-item
+// without a ray.
+template <int N = 6>
+__device__ __forceinline__ void flush_stats(uint64_t *stats, const StatAcc &a, const MetricConsts &m, bool flag = false,
+                                            uint32_t hits = 0)
 {
+    static_assert(N >= 6 && N <= 8, "six words, plus up to two of the disk");
     if (!stats) return;
-    __shared__ unsigned long long sh[6];
-    if (threadIdx.x < 6) sh[threadIdx.x] = 0;
+    __shared__ unsigned long long sh[N];
+    if (threadIdx.x < N) sh[threadIdx.x] = 0;
     __syncthreads();
     uint32_t st = a.counted ? a.steps : 0u;
-    for (int off = 32; off > 0; off >>= 1) st += __shfl_xor(st, off, 64); // (<= 64 x 200 000 steps: fits)
+    for (int off = 32; off > 0; off >>= 1) {
+        st += __shfl_xor(st, off, 64); // (<= 64 x 200 000 steps: fits)
+        if (N > 7) hits += __shfl_xor(hits, off, 64);
+    }
     const unsigned long long rays = (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(a.counted));
-    const unsigned long long v[6] = {rays, st, rays * (unsigned long long)m.evals_fixed + (unsigned long long)st * (unsigned long long)m.evals_per_step,
+    const unsigned long long v[8] = {rays, st, rays * (unsigned long long)m.evals_fixed + (unsigned long long)st * (unsigned long long)m.evals_per_step,
                                      (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(a.esc)),
                                      (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(a.cap)),
-                                     (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(a.inv))};
+                                     (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(a.inv)),
+                                     (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(flag)), (unsigned long long)hits};
     if ((threadIdx.x & 63) == 0)
-        for (int i = 0; i < 6; ++i) if (v[i]) atomicAdd(&sh[i], v[i]);
+        for (int i = 0; i < N; ++i) if (v[i]) atomicAdd(&sh[i], v[i]);
     __syncthreads();
     unsigned long long *set = (unsigned long long *)stats + (size_t)((blockIdx.x + blockIdx.y * gridDim.x) % STAT_SLOTS) * 8;
-    if (threadIdx.x < 6 && sh[threadIdx.x]) atomicAdd(&set[threadIdx.x], sh[threadIdx.x]);
+    if (threadIdx.x < N && sh[threadIdx.x]) atomicAdd(&set[threadIdx.x], sh[threadIdx.x]);
 }
 
 #ifndef LT_KERNEL_TEMPLATES_ONLY
-// one wavefront: lane l holds set l; six wave sums; lane 0 adds them to the caller's counters; the sets go back to zero
-__global__ void __launch_bounds__(STAT_SLOTS) k_stats_reduce(unsigned long long *__restrict__ partials, unsigned long long *__restrict__ stats)
+// one wavefront: lane l holds set l; eight wave sums; lane 0 adds them to the caller's counters; the sets go back to zero.
+// Words 0-5 go to counters 0-5; words 6 and 7 mean what the epilogue that filled them says, so it names their counters:
+// LT_STAT_BG_TILES_LDS / _GLOBAL for the frame path, LT_STAT_DISK (and LT_STAT_DISK_HITS) for the disks.
+__global__ void __launch_bounds__(STAT_SLOTS) k_stats_reduce(unsigned long long *__restrict__ partials, unsigned long long *__restrict__ stats,
+                                                             int dst6, int dst7)
 {
     unsigned long long *set = partials + (size_t)threadIdx.x * 8;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         unsigned long long v = wave_sum(set[i]);
         set[i] = 0;
-        const int dst = i < 6 ? i : i + 4; // 6, 7: tiles staged in LDS / served by the global gather (LT_STAT_BG_TILES_*)
+        const int dst = i < 6 ? i : (i == 6 ? dst6 : dst7);
         if (threadIdx.x == 0 && v) atomicAdd(&stats[dst], v);
     }
 }
@@ -858,6 +914,17 @@ __device__ __forceinline__ void shade(const CamConsts &c, const FrameOut &o, int
     }
 }
 
+// Pixel p of the RGBA8 output, matplotlib imsave: (x * 255).astype(uint8) in float32, alpha 255; gray on one channel.
+__device__ __forceinline__ void store_rgba(const FrameOut &o, int64_t p, const float *rgb, int nch)
+{
+    uchar4 px;
+    px.x = (uint8_t)(rgb[0] * 255.0f);
+    px.y = (uint8_t)(rgb[nch == 1 ? 0 : 1] * 255.0f);
+    px.z = (uint8_t)(rgb[nch == 1 ? 0 : 2] * 255.0f);
+    px.w = 255;
+    reinterpret_cast<uchar4 *>(o.rgba)[p] = px;
+}
+
 // One pixel per work-item, the partition's pixels in row-major order: every output array is written fully coalesced
 // whatever order the integrate kernel finished the rays in.  (Rounds 1-2 ran a grid-stride loop over 4 096 workgroups to
 // keep the counters' atomics few; inside the loop the compiler held 166 registers -- three waves per SIMD -- for a body
@@ -891,14 +958,7 @@ __global__ void __launch_bounds__(EPILOGUE_BLOCK) k_epilogue_frame(CamConsts c, 
             int grow = local_to_global_row(c, lrow);
             shade<HAS_BG>(c, o, ix, grow, fa32, (int)wl, rgb, nch);
             if (o.rgb) for (int ch = 0; ch < nch; ++ch) o.rgb[p * nch + ch] = rgb[ch];
-            if (o.rgba) { // matplotlib imsave: (x * 255).astype(uint8) in float32, alpha 255
-                uchar4 px;
-                px.x = (uint8_t)(rgb[0] * 255.0f);
-                px.y = (uint8_t)(rgb[nch == 1 ? 0 : 1] * 255.0f);
-                px.z = (uint8_t)(rgb[nch == 1 ? 0 : 2] * 255.0f);
-                px.w = 255;
-                reinterpret_cast<uchar4 *>(o.rgba)[p] = px;
-            }
+            if (o.rgba) store_rgba(o, p, rgb, nch);
         }
     }
     flush_stats(o.stats, acc, m);
@@ -990,14 +1050,7 @@ __global__ void __launch_bounds__(256, 3) k_epilogue_frame_lds(CamConsts c, Metr
         if (threadIdx.x == 0 && any) { if (fits) ++staged; else ++fallback; }
         if (active) {
             if (o.rgb) for (int ch = 0; ch < pn; ++ch) o.rgb[p * pn + ch] = rgb[ch];
-            if (o.rgba) { // matplotlib imsave: (x * 255).astype(uint8) in float32, alpha 255
-                uchar4 px;
-                px.x = (uint8_t)(rgb[0] * 255.0f);
-                px.y = (uint8_t)(rgb[pn == 1 ? 0 : 1] * 255.0f);
-                px.z = (uint8_t)(rgb[pn == 1 ? 0 : 2] * 255.0f);
-                px.w = 255;
-                reinterpret_cast<uchar4 *>(o.rgba)[p] = px;
-            }
+            if (o.rgba) store_rgba(o, p, rgb, pn);
         }
     }
     if (o.stats && threadIdx.x == 0 && (staged | fallback)) { // words 6, 7 of the workgroup's partial set -> LT_STAT_BG_TILES_LDS / _GLOBAL
