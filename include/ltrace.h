@@ -416,6 +416,13 @@ int lt_trace_batch_kerr_disk_images(double M, double a, double r_obs, const doub
  * Synchronises on the recorded events. */
 int lt_timing_collect(double *prologue_ms, double *integrate_ms, double *epilogue_ms, int32_t *calls);
 
+/* The ray records the camera prologue writes depend on the camera, the metric, the row partition and the precision
+ * only, and stay in the (device, stream) workspace: a frame whose inputs equal those of the frame before it on the same
+ * stream reuses them instead of running the prologue again (LT_IC_REUSE=0 in the environment: never).  Every frame still
+ * traces and shades every ray.  *hits = frames that reused their records, *misses = frames that ran the prologue, both
+ * since the library was loaded, over all devices and streams; either may be NULL.  Needs no device. */
+void lt_ic_reuse_counts(uint64_t *hits, uint64_t *misses);
+
 #ifdef __cplusplus
 }
 #endif

@@ -93,9 +93,38 @@ struct Grow { // grow-only device allocation
     size_t bytes = 0;
 };
 
+// What the ray records `ic` of a slot's workspace hold: every input k_prologue_camera reads, by value.  A frame whose
+// key equals the slot's skips that launch -- the kernel would overwrite the records with the bytes they already hold.
+// Only the records are reused: every frame still traces every ray and shades every pixel (K2, K3).
+//   * Writers of `ic` are k_prologue_camera (render_dev_impl, which sets the key) and k_prologue_arrays (trace_batch);
+//     the integrate kernels -- direct, queue and Schwarzschild, ghost lanes included, and both disks -- take `ic` as a
+//     pointer to const and only load from it.
+//   * Invalidation: get_workspace() clears the key for every caller and reports whether the buffer was replaced;
+//     render_dev_impl sets it again once its prologue is enqueued, and clears it on any error return after that.
+//     Releasing a slot deletes the key with it.
+//   * Ordering: key and buffer belong to one StreamSlot, and all work of a slot is ordered by its stream, so a key set
+//     at enqueue time describes the records every later launch on that stream will see.  Key accesses hold g_mu.
+struct IcKey {
+    bool valid = false;
+    CamConsts cam{};              // zero-filled before its members are set, block_list cleared: compared with memcmp
+    bool has_blocks = false;      // CamConsts::block_list != NULL ...
+    std::vector<int32_t> blocks;  // ... and the host copy of what it points to
+    int kind = 0, obs_ok = 0;     // MetricConsts: the members K1 reads
+    double metric[15] = {};
+    size_t elem = 0;              // record element size (float / double)
+    int64_t n_q = 0;
+    bool same(const IcKey &o) const
+    {
+        return valid && o.valid && memcmp(&cam, &o.cam, sizeof(cam)) == 0 && has_blocks == o.has_blocks && blocks == o.blocks &&
+               kind == o.kind && obs_ok == o.obs_ok && memcmp(metric, o.metric, sizeof(metric)) == 0 && elem == o.elem &&
+               n_q == o.n_q;
+    }
+};
+
 struct StreamSlot {
     hipStream_t stream = nullptr;
     Grow ws;     // ray records of lt_render_dev / the batch twins
+    IcKey ic_key; // what ws's `ic` holds (valid == false: nothing a frame may reuse)
     Grow dev;    // lt_render / batch twins: device-side inputs and outputs
     Grow dense;  // lt_integrate_dense_dev, length-binned launch: histogram, cursors, keys, permutation
     Grow blocks; // block-owner table mode: this partition's block list on the device
@@ -186,14 +215,25 @@ static void release(Grow &g)
 constexpr size_t WS_CTRL_BYTES = 256 + (size_t)STAT_SLOTS * 8 * sizeof(unsigned long long);
 struct Workspace { unsigned long long *head; unsigned long long *partials; void *ic, *fin0, *fin1; };
 
-static int get_workspace(hipStream_t stream, size_t n_q, size_t elem, Workspace *w)
+// Every caller may write records, so the slot's record key (IcKey) is cleared here; the frame path asks for the key the
+// slot held (`held`; invalid when the buffer was replaced) and sets it again itself.
+static int get_workspace(hipStream_t stream, size_t n_q, size_t elem, Workspace *w, StreamSlot **slot = nullptr,
+                         IcKey *held = nullptr)
 {
     StreamSlot *sl;
     int rc = get_slot(stream, &sl);
     if (rc) return rc;
+    if (slot) *slot = sl;
+    {
+        std::lock_guard<std::mutex> lk(g_mu);
+        if (held) *held = sl->ic_key;
+        sl->ic_key.valid = false;
+    }
     size_t vec = 4 * elem;
     const void *before = sl->ws.p;
+    const size_t bytes_before = sl->ws.bytes;
     if ((rc = grow(sl->ws, WS_CTRL_BYTES + 3 * n_q * vec, stream))) return rc;
+    if (held && sl->ws.bytes != bytes_before) held->valid = false; // (a replaced buffer may come back at the same address)
     if (sl->ws.p != before) HIP_TRY(hipMemsetAsync(sl->ws.p, 0, WS_CTRL_BYTES, stream)); // a new buffer: control words and partial counters start at zero
     char *base = (char *)sl->ws.p;
     w->head = (unsigned long long *)base;
@@ -214,6 +254,22 @@ static int env_int(const char *name, int dflt)
 {
     const char *e = getenv(name);
     return e ? atoi(e) : dflt;
+}
+
+// LT_IC_REUSE=0: k_prologue_camera runs every frame, as if no key ever matched (A/B measurements, bisecting).
+static bool ic_reuse_enabled()
+{
+    static const bool on = env_int("LT_IC_REUSE", 1) != 0;
+    return on;
+}
+
+// Frames that reused the ray records of their slot / that ran k_prologue_camera, since the library was loaded.
+static uint64_t g_ic_hits = 0, g_ic_misses = 0; // (under g_mu)
+extern "C" void lt_ic_reuse_counts(uint64_t *hits, uint64_t *misses)
+{
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (hits) *hits = g_ic_hits;
+    if (misses) *misses = g_ic_misses;
 }
 
 static int cu_count(int *out)
@@ -844,7 +900,32 @@ static int render_dev_impl(const lt_camera *cam, const lt_metric *metric, const 
 
     size_t elem = o.precision == 32 ? sizeof(float) : sizeof(double);
     Workspace w;
-    if ((rc = get_workspace(s, (size_t)n_q, elem, &w))) return rc;
+    StreamSlot *slot;
+    IcKey held;
+    if ((rc = get_workspace(s, (size_t)n_q, elem, &w, &slot, &held))) return rc; // (the slot's key is now cleared)
+    IcKey key;
+    key.valid = true;
+    memcpy(&key.cam, &c, sizeof(c)); // c was zero-filled before its members were set
+    key.cam.block_list = nullptr;
+    key.has_blocks = c.block_list != nullptr;
+    if (key.has_blocks) key.blocks = owned;
+    key.kind = mc.kind; key.obs_ok = mc.obs_ok;
+    const double mkey[15] = {mc.M, mc.a, mc.r_obs, mc.theta_obs, mc.R_S, mc.obs_sin_th, mc.obs_cos2, mc.obs_sin2, mc.obs_sqrt_Sigma,
+                             mc.obs_sqrt_Delta, mc.obs_g_tt, mc.obs_g_tphi, mc.obs_g_rr, mc.obs_g_thth, mc.obs_g_phiphi};
+    memcpy(key.metric, mkey, sizeof(mkey));
+    key.elem = elem; key.n_q = n_q;
+    const bool reuse = ic_reuse_enabled() && key.same(held);
+    // From here on an error return leaves the slot without a key: the guard clears it unless the frame was enqueued whole.
+    struct KeyGuard {
+        StreamSlot *sl;
+        bool ok = false;
+        ~KeyGuard()
+        {
+            if (ok) return;
+            std::lock_guard<std::mutex> lk(g_mu);
+            sl->ic_key.valid = false;
+        }
+    } guard{slot};
     DiskRecordsBuf recs;
     if ((rc = get_disk_records(s, n_q, elem, disk, &recs))) return rc;
     void *ic = w.ic, *fin0 = w.fin0, *fin1 = w.fin1;
@@ -857,9 +938,16 @@ static int render_dev_impl(const lt_camera *cam, const lt_metric *metric, const 
     FrameOut fo{d_bg, bg_channels, d_fa, d_w, d_status, d_steps, d_rgb, d_rgba, d_stats ? (uint64_t *)w.partials : nullptr};
 
     if ((rc = tm.mark(0, s))) return rc;
-    if (o.precision == 32) k_prologue_camera<float><<<gq, 256, 0, s>>>(c, mc, (float4 *)ic, n_q);
-    else k_prologue_camera<double><<<gq, 256, 0, s>>>(c, mc, (double4 *)ic, n_q);
-    HIP_TRY(hipGetLastError());
+    if (!reuse) { // (marks 0 and 1 are recorded either way: a reused prologue reports a time near zero, not a stale one)
+        if (o.precision == 32) k_prologue_camera<float><<<gq, 256, 0, s>>>(c, mc, (float4 *)ic, n_q);
+        else k_prologue_camera<double><<<gq, 256, 0, s>>>(c, mc, (double4 *)ic, n_q);
+        HIP_TRY(hipGetLastError());
+    }
+    {
+        std::lock_guard<std::mutex> lk(g_mu);
+        slot->ic_key = std::move(key);
+        ++(reuse ? g_ic_hits : g_ic_misses);
+    }
     if ((rc = tm.mark(1, s))) return rc;
     if (disk)
         rc = o.precision == 32 ? launch_integrate_disk<float>(mc, o, lambda_max, w, n_q, s, d_stats, *disk, recs)
@@ -875,6 +963,7 @@ static int render_dev_impl(const lt_camera *cam, const lt_metric *metric, const 
         if (rc) return rc;
         if ((rc = tm.mark(3, s))) return rc;
         tm.finish();
+        guard.ok = true;
         return LT_OK;
     }
     // background tiles staged in LDS when a background is lensed (opts->bg_sampling)
@@ -899,6 +988,7 @@ static int render_dev_impl(const lt_camera *cam, const lt_metric *metric, const 
     HIP_TRY(hipGetLastError());
     if ((rc = tm.mark(3, s))) return rc;
     tm.finish();
+    guard.ok = true;
     return LT_OK;
 }
 

@@ -115,6 +115,7 @@ SIGNATURES = {
                                       C.c_int32, C.c_int32, C.c_void_p]),
     "lt_scatter_rows_indexed_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
     "lt_timing_collect": (C.c_int, [_dp, _dp, _dp, C.POINTER(C.c_int32)]),
+    "lt_ic_reuse_counts": (None, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "lt_pixel_angles": (C.c_int, [C.POINTER(Camera), C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lt_shade": (C.c_int, [C.POINTER(Camera), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                            C.c_void_p, C.c_void_p]),
@@ -526,6 +527,13 @@ def timing_collect():
     n = C.c_int32()
     _check(load().lt_timing_collect(C.byref(a), C.byref(b), C.byref(c), C.byref(n)))
     return dict(prologue_ms=a.value, integrate_ms=b.value, epilogue_ms=c.value, calls=n.value)
+
+
+def ic_reuse_counts():
+    """(hits, misses): frames that reused the ray records of their stream / that ran the camera prologue."""
+    h, m = C.c_uint64(), C.c_uint64()
+    load().lt_ic_reuse_counts(C.byref(h), C.byref(m))
+    return int(h.value), int(m.value)
 
 
 def release_stream(stream_ptr):
