@@ -12,12 +12,15 @@
 #endif
 #include "lt_dense.hpp"
 
+#include <array>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
 #include <mutex>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #ifndef LT_BUILD_ID
@@ -209,11 +212,30 @@ static void release(Grow &g)
     g.bytes = 0;
 }
 
+// Everything a slot owns, and the slot.  The caller has drained the slot's stream and taken the slot off its list.
+static void destroy_slot(StreamSlot *sl)
+{
+    for (Grow *g : {&sl->ws, &sl->dev, &sl->dense, &sl->blocks, &sl->disk_img}) release(*g);
+    if (sl->own_ok) for (auto &e : sl->own.e) (void)hipEventDestroy(e);
+    delete sl;
+}
+
 // Workspace layout: 256 B of control words (queue head) | STAT_SLOTS x 8 partial counters of the epilogue | ic[n_q] |
 // fin0[n_q] | fin1[n_q], each a 4-vector of T.  The partial counters are zero between frames (zeroed when the buffer
 // is allocated, and again by k_stats_reduce after it has read them).
 constexpr size_t WS_CTRL_BYTES = 256 + (size_t)STAT_SLOTS * 8 * sizeof(unsigned long long);
-struct Workspace { unsigned long long *head; unsigned long long *partials; void *ic, *fin0, *fin1; };
+struct Workspace {
+    unsigned long long *head, *partials;
+    char *records; // ic, fin0, fin1: n_q records each, of the precision the workspace was asked for
+    size_t n_q;
+    template <typename T> typename Vec4<T>::type *ic() const { return (typename Vec4<T>::type *)records; }
+    template <typename T> typename Vec4<T>::type *fin0() const { return ic<T>() + n_q; }
+    template <typename T> typename Vec4<T>::type *fin1() const { return ic<T>() + 2 * n_q; }
+};
+
+// The one place a precision (32 or 64, check_opts) becomes a type: f(T{}) with T = float or double.
+template <typename F> static auto with_precision(int precision, F f) { return precision == 32 ? f(float{}) : f(double{}); }
+static size_t elem_size(int precision) { return precision == 32 ? sizeof(float) : sizeof(double); }
 
 // Every caller may write records, so the slot's record key (IcKey) is cleared here; the frame path asks for the key the
 // slot held (`held`; invalid when the buffer was replaced) and sets it again itself.
@@ -238,9 +260,8 @@ static int get_workspace(hipStream_t stream, size_t n_q, size_t elem, Workspace 
     char *base = (char *)sl->ws.p;
     w->head = (unsigned long long *)base;
     w->partials = (unsigned long long *)(base + 256);
-    w->ic = base + WS_CTRL_BYTES;
-    w->fin0 = base + WS_CTRL_BYTES + n_q * vec;
-    w->fin1 = base + WS_CTRL_BYTES + 2 * n_q * vec;
+    w->records = base + WS_CTRL_BYTES;
+    w->n_q = n_q;
     return LT_OK;
 }
 
@@ -306,13 +327,7 @@ extern "C" int lt_release_stream(void *stream)
     }
     if (!found) return LT_OK;
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-    release(found->ws);
-    release(found->dev);
-    release(found->dense);
-    release(found->blocks);
-    release(found->disk_img);
-    if (found->own_ok) for (auto &e : found->own.e) (void)hipEventDestroy(e);
-    delete found;
+    destroy_slot(found);
     return LT_OK;
 }
 
@@ -327,11 +342,7 @@ extern "C" int lt_shutdown(void)
         if (c.slots.empty() && c.pool.empty() && c.pending.empty()) continue;
         (void)hipSetDevice(d);
         (void)hipDeviceSynchronize();
-        for (StreamSlot *sl : c.slots) {
-            release(sl->ws); release(sl->dev); release(sl->dense); release(sl->blocks); release(sl->disk_img);
-            if (sl->own_ok) for (auto &e : sl->own.e) (void)hipEventDestroy(e);
-            delete sl;
-        }
+        for (StreamSlot *sl : c.slots) destroy_slot(sl);
         c.slots.clear();
         for (auto &q : c.pending) for (auto &e : q.e) (void)hipEventDestroy(e);
         for (auto &q : c.pool) for (auto &e : q.e) (void)hipEventDestroy(e);
@@ -642,17 +653,28 @@ static const DirectTuning &direct_tuning()
     return t;
 }
 
+// The integrator of a Kerr launch as a type, for both schedules: go(IntegTag<Integ>{}, long_steps).  `long_rk4`: step
+// attempts after which a wavefront counts as long, for RK4 -- DP45 rays take ~50 attempts, not ~150, so a third of it.
+template <typename T, typename Go> static int with_integrator(const lt_opts &o, int long_rk4, Go go)
+{
+    const bool exact = o.integrator == LT_INTEGRATOR_DP45_EXACT;
+    const bool dp45 = o.integrator == LT_INTEGRATOR_DP45 || exact;
+    if (dp45 && sizeof(T) != 8) return fail(LT_ERR_UNSUPPORTED, "DP45 needs precision 64");
+    if constexpr (sizeof(T) == 8) {
+        if (exact) return go(IntegTag<Dp45<T, true>>{}, long_rk4 / 3);
+        if (dp45) return go(IntegTag<Dp45<T>>{}, long_rk4 / 3);
+    }
+    return go(IntegTag<Rk4<T>>{}, long_rk4);
+}
+
 // One launch of the direct schedule (direct_tiles, lt_kernels.hpp): picks the integrator's kernel of the family `Kernels`,
 // sizes the grid, zeroes the queue head and calls launch(kernel, grid, long_iters, head), which adds the family's own
 // arguments.  `block`: work-items per workgroup (64 everywhere but under LT_K2_BLOCK on the plain frame path).
 template <typename T, typename Kernels, typename Launch>
 static int launch_direct(const lt_opts &o, const Workspace &w, int64_t n_q, hipStream_t s, int block, Launch launch)
 {
-    const bool exact = o.integrator == LT_INTEGRATOR_DP45_EXACT;
-    const bool dp45 = o.integrator == LT_INTEGRATOR_DP45 || exact;
-    if (dp45 && sizeof(T) != 8) return fail(LT_ERR_UNSUPPORTED, "DP45 needs precision 64");
     const DirectTuning &tune = direct_tuning();
-    auto go = [&](auto integ, int long_it) -> int {
+    return with_integrator<T>(o, tune.long_iters, [&](auto integ, int long_it) -> int {
         constexpr auto kernel = Kernels::template kernel<typename decltype(integ)::type>;
         unsigned grid = (unsigned)((n_q + block - 1) / block);
         unsigned long long *head = nullptr;
@@ -662,29 +684,20 @@ static int launch_direct(const lt_opts &o, const Workspace &w, int64_t n_q, hipS
         launch(kernel, grid, (uint32_t)long_it, head);
         HIP_TRY(hipGetLastError());
         return LT_OK;
-    };
-    if constexpr (sizeof(T) == 8) { // "long" is measured in step attempts: DP45 rays take ~50, not ~150
-        if (exact) return go(IntegTag<Dp45<T, true>>{}, tune.long_iters / 3);
-        if (dp45) return go(IntegTag<Dp45<T>>{}, tune.long_iters / 3);
-    }
-    return go(IntegTag<Rk4<T>>{}, tune.long_iters);
+    });
 }
 
 template <typename T>
 static int launch_integrate(const MetricConsts &mc, const lt_opts &o, double lambda_max, const Workspace &w,
                             int64_t n_q, hipStream_t s, uint64_t *kstats)
 {
-    using V = typename Vec4<T>::type;
     int rc;
     unsigned grid = (unsigned)((n_q + 255) / 256);
     if (mc.kind == LT_METRIC_SCHWARZSCHILD) {
         SchwConsts<T> k = make_schw<T>(mc, o.phi_max, o.h_max);
-        k_schw_rk4_direct<T><<<grid, 256, 0, s>>>(k, (const V *)w.ic, (V *)w.fin0, (V *)w.fin1, n_q);
+        k_schw_rk4_direct<T><<<grid, 256, 0, s>>>(k, w.ic<T>(), w.fin0<T>(), w.fin1<T>(), n_q);
     } else {
         KerrConsts<T> k = make_kerr<T>(mc, lambda_max, o.h_max);
-        const bool exact = o.integrator == LT_INTEGRATOR_DP45_EXACT;
-        const bool dp45 = o.integrator == LT_INTEGRATOR_DP45 || exact;
-        if (dp45 && sizeof(T) != 8) return fail(LT_ERR_UNSUPPORTED, "DP45 needs precision 64");
         StampDump sd;
         if (o.schedule == LT_SCHED_DIRECT) {
             // wider workgroups and the per-wave stamps (StampDump) exist on this path only, not for the disks
@@ -692,7 +705,7 @@ static int launch_integrate(const MetricConsts &mc, const lt_opts &o, double lam
                                              return (b == 64 || b == 128 || b == 256) ? b : 64; }();
             if ((rc = sd.begin((size_t)(n_q / 64)))) return rc;
             rc = launch_direct<T, PlainKernels<T>>(o, w, n_q, s, k2_block, [&](auto kernel, unsigned kgrid, uint32_t long_iters, unsigned long long *head) {
-                kernel<<<kgrid, k2_block, 0, s>>>(k, (const V *)w.ic, (V *)w.fin0, (V *)w.fin1, n_q, long_iters, sd.dev, kstats, head);
+                kernel<<<kgrid, k2_block, 0, s>>>(k, w.ic<T>(), w.fin0<T>(), w.fin1<T>(), n_q, long_iters, sd.dev, kstats, head);
             });
             if (rc) return rc;
         } else {
@@ -705,22 +718,15 @@ static int launch_integrate(const MetricConsts &mc, const lt_opts &o, double lam
             static const int long_steps = env_int("LT_Q_LONG", 600);
             unsigned qgrid = (unsigned)(cus * bpc);
             if (qgrid > grid) qgrid = grid;
-            HIP_TRY(hipMemsetAsync(w.head, 0, sizeof(unsigned long long), s));
-            if ((rc = sd.begin((size_t)qgrid * 4))) return rc;
-            if constexpr (sizeof(T) == 8) {
-                if (dp45 && !exact) // "long" is measured in step attempts: DP45 rays take ~50, not ~150
-                    k_kerr_queue<T, Dp45<T>><<<qgrid, 256, 0, s>>>(k, (const V *)w.ic, (V *)w.fin0, (V *)w.fin1, (uint64_t)n_q,
-                                                                 w.head, (uint32_t)chunk, (uint32_t)refill_min,
-                                                                 (uint32_t)(long_steps / 3), sd.dev, kstats);
-                if (exact)
-                    k_kerr_queue<T, Dp45<T, true>><<<qgrid, 256, 0, s>>>(k, (const V *)w.ic, (V *)w.fin0, (V *)w.fin1, (uint64_t)n_q,
-                                                                       w.head, (uint32_t)chunk, (uint32_t)refill_min,
-                                                                       (uint32_t)(long_steps / 3), sd.dev, kstats);
-            }
-            if (!dp45)
-                k_kerr_queue<T, Rk4<T>><<<qgrid, 256, 0, s>>>(k, (const V *)w.ic, (V *)w.fin0, (V *)w.fin1, (uint64_t)n_q, w.head,
-                                                            (uint32_t)chunk, (uint32_t)refill_min, (uint32_t)long_steps, sd.dev,
-                                                            kstats);
+            rc = with_integrator<T>(o, long_steps, [&](auto integ, int long_it) -> int {
+                HIP_TRY(hipMemsetAsync(w.head, 0, sizeof(unsigned long long), s));
+                if (int brc = sd.begin((size_t)qgrid * 4)) return brc;
+                k_kerr_queue<T, typename decltype(integ)::type><<<qgrid, 256, 0, s>>>(k, w.ic<T>(), w.fin0<T>(), w.fin1<T>(), (uint64_t)n_q, w.head,
+                                                                                     (uint32_t)chunk, (uint32_t)refill_min, (uint32_t)long_it,
+                                                                                     sd.dev, kstats);
+                return LT_OK;
+            });
+            if (rc) return rc;
         }
         HIP_TRY(hipGetLastError());
         if ((rc = sd.end())) return rc;
@@ -751,6 +757,12 @@ static int check_opts(const lt_metric *metric, lt_opts *o)
     return LT_OK;
 }
 
+// Observer-frame evaluation counts of the adaptive integrators (make_metric leaves RK4's four per step).
+static void count_evals(int integrator, MetricConsts *mc)
+{
+    if (mc->kind == LT_METRIC_KERR && integrator != LT_INTEGRATOR_RK4) { mc->evals_fixed = 1; mc->evals_per_step = 6; }
+}
+
 // The thin disk of lt_render_disk (lt_api_disk.inc): resolved parameters and the extra output.  max_images > 0: the
 // optically thin disk of lt_render_disk_images (lt_api_disk_images.inc) and its outputs.
 struct DiskParams {
@@ -762,9 +774,11 @@ struct DiskParams {
 };
 // The hit records of the thin disk, resolved once per call (get_disk_records) and handed to its launches.
 struct DiskRecordsBuf {
-    void *img = nullptr;      // Vec2<T> [max_images][n_q]
+    void *p = nullptr;        // Vec2<T> [max_images][n_q]
     uint32_t *hits = nullptr; // [n_q]
+    template <typename T> typename Vec2<T>::type *img() const { return (typename Vec2<T>::type *)p; }
 };
+// The disks' launches, defined in lt_api_disk.inc and lt_api_disk_images.inc (which in turn call the frame plumbing below).
 static int get_disk_records(hipStream_t s, int64_t n_q, size_t elem, const DiskParams *disk, DiskRecordsBuf *recs);
 template <typename T>
 static int launch_integrate_disk(const MetricConsts &mc, const lt_opts &o, double lambda_max, const Workspace &w, int64_t n_q,
@@ -772,12 +786,199 @@ static int launch_integrate_disk(const MetricConsts &mc, const lt_opts &o, doubl
 static int launch_epilogue_disk(const CamConsts &c, const MetricConsts &mc, const lt_opts &o, const Workspace &w,
                                 const FrameOut &fo, uint64_t *d_stats, hipStream_t s, const DiskParams &dp);
 static int launch_epilogue_disk_images(const CamConsts &c, const MetricConsts &mc, const lt_opts &o, const Workspace &w,
-                                       int64_t n_q, const FrameOut &fo, uint64_t *d_stats, hipStream_t s,
-                                       const DiskParams &dp, const DiskRecordsBuf &recs);
+                                       const FrameOut &fo, uint64_t *d_stats, hipStream_t s, const DiskParams &dp,
+                                       const DiskRecordsBuf &recs);
 static int launch_epilogue_arrays_disk_images(const MetricConsts &mc, const lt_opts &o, const Workspace &w, int64_t n,
-                                              int64_t n_q, double *d_fa, int64_t *d_w, int8_t *d_st, uint32_t *d_ev,
-                                              double *d_images, int32_t *d_n_hits, hipStream_t s, const DiskParams &dp,
-                                              const DiskRecordsBuf &recs);
+                                              double *d_fa, int64_t *d_w, int8_t *d_st, uint32_t *d_ev, double *d_images,
+                                              int32_t *d_n_hits, hipStream_t s, const DiskParams &dp, const DiskRecordsBuf &recs);
+
+// The three stages of a frame, each launched once in terms of the precision's type.
+static int launch_prologue_camera(const CamConsts &c, const MetricConsts &mc, const lt_opts &o, const Workspace &w, int64_t n_q,
+                                  hipStream_t s)
+{
+    with_precision(o.precision, [&](auto t) {
+        using T = decltype(t);
+        k_prologue_camera<T><<<(unsigned)((n_q + 255) / 256), 256, 0, s>>>(c, mc, w.ic<T>(), n_q);
+    });
+    HIP_TRY(hipGetLastError());
+    return LT_OK;
+}
+
+// The integrate launch of a frame or a batch: with `disk` the disk's kernels, else the plain ones.
+static int launch_integrate_any(const MetricConsts &mc, const lt_opts &o, double lambda_max, const Workspace &w, int64_t n_q,
+                                hipStream_t s, uint64_t *kstats, const DiskParams *disk, const DiskRecordsBuf &recs)
+{
+    if (disk)
+        return with_precision(o.precision, [&](auto t) {
+            return launch_integrate_disk<decltype(t)>(mc, o, lambda_max, w, n_q, s, kstats, *disk, recs);
+        });
+    return with_precision(o.precision, [&](auto t) { return launch_integrate<decltype(t)>(mc, o, lambda_max, w, n_q, s, kstats); });
+}
+
+// The launch shape the three per-pixel frame epilogues share: launch(T{}, std::bool_constant<HAS_BG>{}, grid), one
+// workgroup of EPILOGUE_BLOCK pixels of one row.
+template <typename Launch> static void launch_epilogue_rows(const CamConsts &c, const lt_opts &o, const FrameOut &fo, Launch launch)
+{
+    const bool has_bg = fo.bg != nullptr && (fo.rgb || fo.rgba);
+    const dim3 ge((unsigned)((c.W + EPILOGUE_BLOCK - 1) / EPILOGUE_BLOCK), (unsigned)c.rows_local);
+    with_precision(o.precision, [&](auto t) {
+        if (has_bg) launch(t, std::true_type{}, ge);
+        else launch(t, std::false_type{}, ge);
+    });
+}
+
+static int launch_epilogue_frame(const CamConsts &c, const MetricConsts &mc, const lt_opts &o, const Workspace &w,
+                                 const FrameOut &fo, uint64_t *d_stats, hipStream_t s)
+{
+    // background tiles staged in LDS when a background is lensed (opts->bg_sampling)
+    if (o.bg_sampling == LT_BG_LDS_TILES && fo.bg && (fo.rgb || fo.rgba)) {
+        const unsigned gp = (unsigned)((int64_t)((c.W + 15) / 16) * ((c.rows_local + 15) / 16)); // one 16x16 tile per workgroup
+        with_precision(o.precision, [&](auto t) {
+            using T = decltype(t);
+            k_epilogue_frame_lds<T><<<gp, 256, 0, s>>>(c, mc, w.fin0<T>(), w.fin1<T>(), fo);
+        });
+    } else {
+        launch_epilogue_rows(c, o, fo, [&](auto t, auto bg, dim3 ge) {
+            using T = decltype(t);
+            k_epilogue_frame<T, decltype(bg)::value><<<ge, EPILOGUE_BLOCK, 0, s>>>(c, mc, w.fin0<T>(), w.fin1<T>(), fo);
+        });
+    }
+    if (d_stats) k_stats_reduce<<<1, STAT_SLOTS, 0, s>>>(w.partials, (unsigned long long *)d_stats, LT_STAT_BG_TILES_LDS, LT_STAT_BG_TILES_GLOBAL);
+    HIP_TRY(hipGetLastError());
+    return LT_OK;
+}
+
+// Pinhole, psi frame and the axis-refine columns' threshold of a camera (image_lens.py:138-139, :210-214), into a
+// zero-filled CamConsts.  Returns whether the hole lies in front of the camera.
+static bool camera_pinhole(const lt_camera *cam, double axis_refine_frac, CamConsts *c)
+{
+    memset(c, 0, sizeof(*c));
+    c->W = cam->width; c->H = cam->height;
+    c->half_W = c->W / 2.0; c->half_H = c->H / 2.0;
+    c->fx = (c->W / 2.0) / tan(cam->hfov / 2);
+    c->fy = (c->H / 2.0) / tan(cam->vfov / 2);
+    bool front;
+    psi_frame(cam->psi_y, cam->psi_x, c->d, c->ex, c->ey, &front);
+    if (front) {
+        c->bh_x_cam = c->d[0] / c->d[2];
+        double x_lo = fabs((0 - c->half_W) / c->fx - c->bh_x_cam), x_hi = fabs((c->W - 1 - c->half_W) / c->fx - c->bh_x_cam);
+        double m = x_lo > x_hi ? x_lo : x_hi;
+        c->refine_thresh = axis_refine_frac * (m > 1e-12 ? m : 1e-12);
+    }
+    return front;
+}
+
+// The camera block of one partition's frame: host arithmetic only.  `owned` / `rows_owned`: the partition's row blocks
+// (partition_blocks); `disk`: a disk frame, which traces every row.  The caller adds block_list.  A partition without
+// rows (rows_local <= 0) is no error: its block is left without tiles.
+static int make_camera(const lt_camera *cam, int kind, const lt_opts &o, const MetricConsts &mc, const std::vector<int32_t> &owned,
+                       int64_t rows_owned, bool disk, CamConsts *out)
+{
+    CamConsts &c = *out;
+    const bool front = camera_pinhole(cam, o.axis_refine_frac, &c);
+    c.row_block = o.row_block; c.n_parts = o.n_parts; c.part = o.part;
+    c.rows_local = (int)rows_owned;
+    c.loop_around = o.loop_around;
+    c.refine_on = front && kind == LT_METRIC_KERR;
+    // top/bottom symmetry exactly when the reference applies it (image_lens.py:218-220)
+    c.use_tb = !disk && o.tb_symmetry && kind == LT_METRIC_KERR &&
+               fabs(cam->theta_obs - M_PI / 2) <= 1e-8 + 1e-5 * (M_PI / 2) && fabs(cam->psi_y) <= 1e-8;
+    if (c.use_tb && (o.n_parts != 1 || o.block_owner)) return fail(LT_ERR_UNSUPPORTED, "tb_symmetry needs n_parts == 1 and no block_owner table");
+    c.trace_rows = c.use_tb ? (c.H + 1) / 2 : c.rows_local;
+    c.tiles_x = (c.W + 7) / 8;
+    if (c.rows_local <= 0) return LT_OK;
+    if (c.rows_local > 65535) // (the epilogue's launch grid carries the row in its y dimension; checked before anything is launched)
+        return fail(LT_ERR_UNSUPPORTED, "a partition of %d rows exceeds the epilogue's launch grid (65535 rows): split it (n_parts)", c.rows_local);
+    const int tiles_y = (c.trace_rows + 7) / 8;
+    c.tiles_y = tiles_y;
+    // "hot" tile rectangle, queued first: bounds the critical curve (largest impact parameter of a spherical photon
+    // orbit: the retrograde equatorial one for Kerr, 3 sqrt(3) M for a = 0), + margin
+    if (!front || kind != LT_METRIC_KERR) return LT_OK;
+    double a = mc.a, M_ = mc.M;
+    double b_max = 3.0 * sqrt(3.0) * M_;
+    if (a != 0.0) { // Bardeen: r_ret = 2M (1 + cos(2/3 acos(|a|/M))), xi(r) as in metrics.py:886-887
+        double aa = fabs(a);
+        double r_ph = 2.0 * M_ * (1.0 + cos(2.0 / 3.0 * acos(aa / M_)));
+        double Dl = r_ph * r_ph - 2.0 * M_ * r_ph + aa * aa;
+        double xi = (r_ph * r_ph + aa * aa) / aa - 2.0 * r_ph * Dl / (aa * (r_ph - M_));
+        if (fabs(xi) > b_max) b_max = fabs(xi);
+    }
+    b_max = 1.05 * b_max + 0.3 * M_;
+    double f0 = 1.0 - 2.0 * M_ / cam->r_obs;
+    double sin_al = f0 > 0 ? b_max * sqrt(f0) / cam->r_obs : 1.0;
+    if (!(sin_al < 0.98)) return LT_OK;
+    double tan_al = sin_al / sqrt(1.0 - sin_al * sin_al);
+    double bx = c.d[0] / c.d[2] * c.fx + c.half_W, by = c.d[1] / c.d[2] * c.fy + c.half_H; // BH pixel
+    double rx = tan_al * c.fx + 8.0, ry = tan_al * c.fy + 8.0;                             // pixels
+    auto clampi = [](double v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : (int)v); };
+    c.hot_x0 = clampi(floor((bx - rx) / 8.0), 0, c.tiles_x);
+    c.hot_x1 = clampi(ceil((bx + rx) / 8.0), 0, c.tiles_x);
+    // rows: global pixel rows -> this partition's local rows (block-cyclic: about 1/n_parts of them)
+    double ly0 = (by - ry) / o.n_parts - o.row_block, ly1 = (by + ry) / o.n_parts + o.row_block;
+    if (o.block_owner) { // any assignment: local rows of the first / last owned block that touches the band
+        ly0 = 1e18; ly1 = -1.0;
+        for (size_t i = 0; i < owned.size(); ++i) {
+            double g0 = (double)owned[i] * o.row_block, g1 = g0 + o.row_block;
+            if (g1 < by - ry || g0 > by + ry) continue;
+            if ((double)i * o.row_block < ly0) ly0 = (double)i * o.row_block;
+            ly1 = (double)(i + 1) * o.row_block;
+        }
+        if (ly1 < 0) ly0 = ly1 = 0.0;
+    }
+    c.hot_y0 = clampi(floor(ly0 / 8.0), 0, tiles_y);
+    c.hot_y1 = clampi(ceil(ly1 / 8.0), 0, tiles_y);
+    if (c.hot_x1 <= c.hot_x0 || c.hot_y1 <= c.hot_y0) c.hot_x0 = c.hot_x1 = c.hot_y0 = c.hot_y1 = 0;
+    // spin-axis strip: +-16 px around the column the BH projects to; then move the rectangle's column range onto the grid with the strip removed
+    c.strip_x0 = clampi(floor((bx - 16.0) / 8.0), 0, c.tiles_x);
+    c.strip_x1 = clampi(ceil((bx + 16.0) / 8.0), 0, c.tiles_x);
+    if (c.strip_x1 < c.strip_x0) c.strip_x1 = c.strip_x0;
+    int sw = c.strip_x1 - c.strip_x0;
+    auto compact = [&](int x) { return x <= c.strip_x0 ? x : (x - sw > c.strip_x0 ? x - sw : c.strip_x0); };
+    c.hot_x0 = compact(c.hot_x0);
+    c.hot_x1 = compact(c.hot_x1);
+    if (c.hot_x1 <= c.hot_x0) c.hot_x0 = c.hot_x1 = c.hot_y0 = c.hot_y1 = 0;
+    return LT_OK;
+}
+
+// Block-owner table mode: the partition's block list on the device (uploaded once: again only when it changes).
+static int upload_block_list(hipStream_t s, const std::vector<int32_t> &owned, const int32_t **d_list)
+{
+    StreamSlot *sl;
+    int rc = get_slot(s, &sl);
+    if (rc) return rc;
+    if (sl->blocks_host != owned || !sl->blocks.p) {
+        if ((rc = grow(sl->blocks, owned.size() * sizeof(int32_t), s))) return rc;
+        HIP_TRY(hipStreamSynchronize(s)); // frames in flight on this stream still read the old list
+        HIP_TRY(hipMemcpy(sl->blocks.p, owned.data(), owned.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        sl->blocks_host = owned;
+    }
+    *d_list = (const int32_t *)sl->blocks.p;
+    return LT_OK;
+}
+
+// What k_prologue_camera would read for this frame (IcKey).
+static IcKey make_ic_key(const CamConsts &c, const std::vector<int32_t> &owned, const MetricConsts &mc, size_t elem, int64_t n_q)
+{
+    IcKey key;
+    key.valid = true;
+    memcpy(&key.cam, &c, sizeof(c)); // c was zero-filled before its members were set
+    key.cam.block_list = nullptr;
+    key.has_blocks = c.block_list != nullptr;
+    if (key.has_blocks) key.blocks = owned;
+    key.kind = mc.kind; key.obs_ok = mc.obs_ok;
+    const double mkey[15] = {mc.M, mc.a, mc.r_obs, mc.theta_obs, mc.R_S, mc.obs_sin_th, mc.obs_cos2, mc.obs_sin2, mc.obs_sqrt_Sigma,
+                             mc.obs_sqrt_Delta, mc.obs_g_tt, mc.obs_g_tphi, mc.obs_g_rr, mc.obs_g_thth, mc.obs_g_phiphi};
+    memcpy(key.metric, mkey, sizeof(mkey));
+    key.elem = elem; key.n_q = n_q;
+    return key;
+}
+
+// Leaves the slot without a record key unless the frame was enqueued whole (ok).
+struct KeyGuard {
+    StreamSlot *sl;
+    bool ok = false;
+    ~KeyGuard() { if (ok) return; std::lock_guard<std::mutex> lk(g_mu); sl->ic_key.valid = false; }
+};
 
 // disk == NULL: the frame path.  Else the disk frame (lt_render_disk_dev): every row traced, the disk kernels.
 static int render_dev_impl(const lt_camera *cam, const lt_metric *metric, const lt_opts *opts, const float *d_bg,
@@ -794,198 +995,54 @@ static int render_dev_impl(const lt_camera *cam, const lt_metric *metric, const 
     if ((rc = check_opts(metric, &o))) return rc;
     MetricConsts mc;
     if ((rc = make_metric(metric, cam->r_obs, cam->theta_obs, o.h_max, &mc))) return rc;
-    if (metric->kind == LT_METRIC_KERR && o.integrator != LT_INTEGRATOR_RK4) { mc.evals_fixed = 1; mc.evals_per_step = 6; }
+    count_evals(o.integrator, &mc);
 
-    CamConsts c;
-    memset(&c, 0, sizeof(c));
-    c.W = cam->width; c.H = cam->height;
-    c.row_block = o.row_block; c.n_parts = o.n_parts; c.part = o.part;
     hipStream_t s = (hipStream_t)o.stream;
     std::vector<int32_t> owned;
     int64_t rows_owned = 0;
-    if ((rc = partition_blocks(c.H, o, &owned, &rows_owned))) return rc;
-    c.rows_local = (int)rows_owned;
-    c.block_list = nullptr;
-    if (o.block_owner && !owned.empty()) { // the partition's block list goes to the device (once: re-uploaded only when it changes)
-        StreamSlot *sl;
-        if ((rc = get_slot(s, &sl))) return rc;
-        if (sl->blocks_host != owned || !sl->blocks.p) {
-            if ((rc = grow(sl->blocks, owned.size() * sizeof(int32_t), s))) return rc;
-            HIP_TRY(hipStreamSynchronize(s)); // frames in flight on this stream still read the old list
-            HIP_TRY(hipMemcpy(sl->blocks.p, owned.data(), owned.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-            sl->blocks_host = owned;
-        }
-        c.block_list = (const int32_t *)sl->blocks.p;
-    }
-    c.loop_around = o.loop_around;
-    c.half_W = c.W / 2.0; c.half_H = c.H / 2.0;
-    c.fx = (c.W / 2.0) / tan(cam->hfov / 2); // image_lens.py:138-139
-    c.fy = (c.H / 2.0) / tan(cam->vfov / 2);
-    bool front;
-    psi_frame(cam->psi_y, cam->psi_x, c.d, c.ex, c.ey, &front);
-    c.refine_on = front && metric->kind == LT_METRIC_KERR;
-    if (front) { // image_lens.py:210-214
-        c.bh_x_cam = c.d[0] / c.d[2];
-        double x_lo = fabs((0 - c.half_W) / c.fx - c.bh_x_cam), x_hi = fabs((c.W - 1 - c.half_W) / c.fx - c.bh_x_cam);
-        double m = x_lo > x_hi ? x_lo : x_hi;
-        c.refine_thresh = o.axis_refine_frac * (m > 1e-12 ? m : 1e-12);
-    }
-    // top/bottom symmetry exactly when the reference applies it (image_lens.py:218-220)
-    c.use_tb = !disk && o.tb_symmetry && metric->kind == LT_METRIC_KERR &&
-               fabs(cam->theta_obs - M_PI / 2) <= 1e-8 + 1e-5 * (M_PI / 2) && fabs(cam->psi_y) <= 1e-8;
-    if (c.use_tb && (o.n_parts != 1 || o.block_owner)) return fail(LT_ERR_UNSUPPORTED, "tb_symmetry needs n_parts == 1 and no block_owner table");
-    c.trace_rows = c.use_tb ? (c.H + 1) / 2 : c.rows_local;
-    c.tiles_x = (c.W + 7) / 8;
+    if ((rc = partition_blocks(cam->height, o, &owned, &rows_owned))) return rc;
+    const int32_t *block_list = nullptr;
+    if (o.block_owner && !owned.empty() && (rc = upload_block_list(s, owned, &block_list))) return rc;
+    CamConsts c;
+    if ((rc = make_camera(cam, metric->kind, o, mc, owned, rows_owned, disk != nullptr, &c))) return rc;
+    c.block_list = block_list;
     if (c.rows_local <= 0) return LT_OK; // a partition may own no rows
-    if (c.rows_local > 65535) // (the epilogue's launch grid carries the row in its y dimension; checked before anything is launched)
-        return fail(LT_ERR_UNSUPPORTED, "a partition of %d rows exceeds the epilogue's launch grid (65535 rows): split it (n_parts)", c.rows_local);
-    int tiles_y = (c.trace_rows + 7) / 8;
-    c.tiles_y = tiles_y;
-    { // "hot" tile rectangle, queued first: bounds the critical curve (largest impact parameter of a
-      // spherical photon orbit: the retrograde equatorial one for Kerr, 3 sqrt(3) M for a = 0), + margin
-        c.hot_x0 = c.hot_x1 = c.hot_y0 = c.hot_y1 = 0;
-        c.strip_x0 = c.strip_x1 = 0;
-        if (front && metric->kind == LT_METRIC_KERR) {
-            double a = mc.a, M_ = mc.M;
-            double b_max = 3.0 * sqrt(3.0) * M_;
-            if (a != 0.0) { // Bardeen: r_ret = 2M (1 + cos(2/3 acos(|a|/M))), xi(r) as in metrics.py:886-887
-                double aa = fabs(a);
-                double r_ph = 2.0 * M_ * (1.0 + cos(2.0 / 3.0 * acos(aa / M_)));
-                double Dl = r_ph * r_ph - 2.0 * M_ * r_ph + aa * aa;
-                double xi = (r_ph * r_ph + aa * aa) / aa - 2.0 * r_ph * Dl / (aa * (r_ph - M_));
-                if (fabs(xi) > b_max) b_max = fabs(xi);
-            }
-            b_max = 1.05 * b_max + 0.3 * M_;
-            double f0 = 1.0 - 2.0 * M_ / cam->r_obs;
-            double sin_al = f0 > 0 ? b_max * sqrt(f0) / cam->r_obs : 1.0;
-            if (sin_al < 0.98) {
-                double tan_al = sin_al / sqrt(1.0 - sin_al * sin_al);
-                double bx = c.d[0] / c.d[2] * c.fx + c.half_W, by = c.d[1] / c.d[2] * c.fy + c.half_H; // BH pixel
-                double rx = tan_al * c.fx + 8.0, ry = tan_al * c.fy + 8.0;                             // pixels
-                auto clampi = [](double v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : (int)v); };
-                c.hot_x0 = clampi(floor((bx - rx) / 8.0), 0, c.tiles_x);
-                c.hot_x1 = clampi(ceil((bx + rx) / 8.0), 0, c.tiles_x);
-                // rows: global pixel rows -> this partition's local rows (block-cyclic: about 1/n_parts of them)
-                double ly0 = (by - ry) / o.n_parts - o.row_block, ly1 = (by + ry) / o.n_parts + o.row_block;
-                if (o.block_owner) { // any assignment: local rows of the first / last owned block that touches the band
-                    ly0 = 1e18; ly1 = -1.0;
-                    for (size_t i = 0; i < owned.size(); ++i) {
-                        double g0 = (double)owned[i] * o.row_block, g1 = g0 + o.row_block;
-                        if (g1 < by - ry || g0 > by + ry) continue;
-                        if ((double)i * o.row_block < ly0) ly0 = (double)i * o.row_block;
-                        ly1 = (double)(i + 1) * o.row_block;
-                    }
-                    if (ly1 < 0) ly0 = ly1 = 0.0;
-                }
-                c.hot_y0 = clampi(floor(ly0 / 8.0), 0, tiles_y);
-                c.hot_y1 = clampi(ceil(ly1 / 8.0), 0, tiles_y);
-                if (c.hot_x1 <= c.hot_x0 || c.hot_y1 <= c.hot_y0) c.hot_x0 = c.hot_x1 = c.hot_y0 = c.hot_y1 = 0;
-                // spin-axis strip: +-16 px around the column the BH projects to; then move the rectangle's
-                // column range onto the grid with the strip removed
-                c.strip_x0 = clampi(floor((bx - 16.0) / 8.0), 0, c.tiles_x);
-                c.strip_x1 = clampi(ceil((bx + 16.0) / 8.0), 0, c.tiles_x);
-                if (c.strip_x1 < c.strip_x0) c.strip_x1 = c.strip_x0;
-                int sw = c.strip_x1 - c.strip_x0;
-                auto compact = [&](int x) { return x <= c.strip_x0 ? x : (x - sw > c.strip_x0 ? x - sw : c.strip_x0); };
-                c.hot_x0 = compact(c.hot_x0);
-                c.hot_x1 = compact(c.hot_x1);
-                if (c.hot_x1 <= c.hot_x0) c.hot_x0 = c.hot_x1 = c.hot_y0 = c.hot_y1 = 0;
-            }
-        }
-    }
-    int64_t n_q = (int64_t)c.tiles_x * tiles_y * 64;
+    int64_t n_q = (int64_t)c.tiles_x * c.tiles_y * 64;
     if (n_q / 64 >= (int64_t)1 << 31) // (the prologue decodes a tile's queue position in 32 bits; 2^31 tiles of records would be 6 TB)
-        return fail(LT_ERR_INVALID_ARG, "frame of %d x %d tiles: more than 2^31 - 1", c.tiles_x, tiles_y);
+        return fail(LT_ERR_INVALID_ARG, "frame of %d x %d tiles: more than 2^31 - 1", c.tiles_x, c.tiles_y);
     double lambda_max = fmax(5000.0, 6.0 * cam->r_obs); // metrics.py:1132
 
-    size_t elem = o.precision == 32 ? sizeof(float) : sizeof(double);
+    const size_t elem = elem_size(o.precision);
     Workspace w;
     StreamSlot *slot;
     IcKey held;
     if ((rc = get_workspace(s, (size_t)n_q, elem, &w, &slot, &held))) return rc; // (the slot's key is now cleared)
-    IcKey key;
-    key.valid = true;
-    memcpy(&key.cam, &c, sizeof(c)); // c was zero-filled before its members were set
-    key.cam.block_list = nullptr;
-    key.has_blocks = c.block_list != nullptr;
-    if (key.has_blocks) key.blocks = owned;
-    key.kind = mc.kind; key.obs_ok = mc.obs_ok;
-    const double mkey[15] = {mc.M, mc.a, mc.r_obs, mc.theta_obs, mc.R_S, mc.obs_sin_th, mc.obs_cos2, mc.obs_sin2, mc.obs_sqrt_Sigma,
-                             mc.obs_sqrt_Delta, mc.obs_g_tt, mc.obs_g_tphi, mc.obs_g_rr, mc.obs_g_thth, mc.obs_g_phiphi};
-    memcpy(key.metric, mkey, sizeof(mkey));
-    key.elem = elem; key.n_q = n_q;
+    IcKey key = make_ic_key(c, owned, mc, elem, n_q);
     const bool reuse = ic_reuse_enabled() && key.same(held);
-    // From here on an error return leaves the slot without a key: the guard clears it unless the frame was enqueued whole.
-    struct KeyGuard {
-        StreamSlot *sl;
-        bool ok = false;
-        ~KeyGuard()
-        {
-            if (ok) return;
-            std::lock_guard<std::mutex> lk(g_mu);
-            sl->ic_key.valid = false;
-        }
-    } guard{slot};
+    KeyGuard guard{slot}; // from here on an error return leaves the slot without a key
     DiskRecordsBuf recs;
     if ((rc = get_disk_records(s, n_q, elem, disk, &recs))) return rc;
-    void *ic = w.ic, *fin0 = w.fin0, *fin1 = w.fin1;
     Timer tm;
     if ((rc = tm.begin(o.timing != 0, own_events))) return rc;
-    unsigned gq = (unsigned)((n_q + 255) / 256);
-    unsigned gp = 0;
     // the epilogue adds its counters into STAT_SLOTS partial sets (workgroup index mod STAT_SLOTS) of the workspace; one
     // small launch behind it folds them into the caller's counters
     FrameOut fo{d_bg, bg_channels, d_fa, d_w, d_status, d_steps, d_rgb, d_rgba, d_stats ? (uint64_t *)w.partials : nullptr};
 
     if ((rc = tm.mark(0, s))) return rc;
-    if (!reuse) { // (marks 0 and 1 are recorded either way: a reused prologue reports a time near zero, not a stale one)
-        if (o.precision == 32) k_prologue_camera<float><<<gq, 256, 0, s>>>(c, mc, (float4 *)ic, n_q);
-        else k_prologue_camera<double><<<gq, 256, 0, s>>>(c, mc, (double4 *)ic, n_q);
-        HIP_TRY(hipGetLastError());
-    }
+    // (marks 0 and 1 are recorded either way: a reused prologue reports a time near zero, not a stale one)
+    if (!reuse && (rc = launch_prologue_camera(c, mc, o, w, n_q, s))) return rc;
     {
         std::lock_guard<std::mutex> lk(g_mu);
         slot->ic_key = std::move(key);
         ++(reuse ? g_ic_hits : g_ic_misses);
     }
     if ((rc = tm.mark(1, s))) return rc;
-    if (disk)
-        rc = o.precision == 32 ? launch_integrate_disk<float>(mc, o, lambda_max, w, n_q, s, d_stats, *disk, recs)
-                               : launch_integrate_disk<double>(mc, o, lambda_max, w, n_q, s, d_stats, *disk, recs);
-    else
-        rc = o.precision == 32 ? launch_integrate<float>(mc, o, lambda_max, w, n_q, s, d_stats)
-                               : launch_integrate<double>(mc, o, lambda_max, w, n_q, s, d_stats);
-    if (rc) return rc;
+    if ((rc = launch_integrate_any(mc, o, lambda_max, w, n_q, s, d_stats, disk, recs))) return rc;
     if ((rc = tm.mark(2, s))) return rc;
-    if (disk) {
-        rc = disk->max_images ? launch_epilogue_disk_images(c, mc, o, w, n_q, fo, d_stats, s, *disk, recs)
-                              : launch_epilogue_disk(c, mc, o, w, fo, d_stats, s, *disk);
-        if (rc) return rc;
-        if ((rc = tm.mark(3, s))) return rc;
-        tm.finish();
-        guard.ok = true;
-        return LT_OK;
-    }
-    // background tiles staged in LDS when a background is lensed (opts->bg_sampling)
-    const bool lds_path = o.bg_sampling == LT_BG_LDS_TILES && d_bg && (d_rgb || d_rgba);
-    if (lds_path) {
-        int64_t n16 = (int64_t)((c.W + 15) / 16) * ((c.rows_local + 15) / 16);
-        gp = (unsigned)n16; // one 16x16 tile per workgroup
-        if (o.precision == 32) k_epilogue_frame_lds<float><<<gp, 256, 0, s>>>(c, mc, (const float4 *)fin0, (const float4 *)fin1, fo);
-        else k_epilogue_frame_lds<double><<<gp, 256, 0, s>>>(c, mc, (const double4 *)fin0, (const double4 *)fin1, fo);
-    } else {
-        const bool has_bg = d_bg != nullptr && (d_rgb || d_rgba);
-        const dim3 ge((unsigned)((c.W + EPILOGUE_BLOCK - 1) / EPILOGUE_BLOCK), (unsigned)c.rows_local);
-        if (o.precision == 32) {
-            if (has_bg) k_epilogue_frame<float, true><<<ge, EPILOGUE_BLOCK, 0, s>>>(c, mc, (const float4 *)fin0, (const float4 *)fin1, fo);
-            else k_epilogue_frame<float, false><<<ge, EPILOGUE_BLOCK, 0, s>>>(c, mc, (const float4 *)fin0, (const float4 *)fin1, fo);
-        } else {
-            if (has_bg) k_epilogue_frame<double, true><<<ge, EPILOGUE_BLOCK, 0, s>>>(c, mc, (const double4 *)fin0, (const double4 *)fin1, fo);
-            else k_epilogue_frame<double, false><<<ge, EPILOGUE_BLOCK, 0, s>>>(c, mc, (const double4 *)fin0, (const double4 *)fin1, fo);
-        }
-    }
-    if (d_stats) k_stats_reduce<<<1, STAT_SLOTS, 0, s>>>(w.partials, (unsigned long long *)d_stats, LT_STAT_BG_TILES_LDS, LT_STAT_BG_TILES_GLOBAL);
-    HIP_TRY(hipGetLastError());
+    if (!disk) rc = launch_epilogue_frame(c, mc, o, w, fo, d_stats, s);
+    else if (disk->max_images) rc = launch_epilogue_disk_images(c, mc, o, w, fo, d_stats, s, *disk, recs);
+    else rc = launch_epilogue_disk(c, mc, o, w, fo, d_stats, s, *disk);
+    if (rc) return rc;
     if ((rc = tm.mark(3, s))) return rc;
     tm.finish();
     guard.ok = true;
@@ -1026,19 +1083,89 @@ extern "C" int lt_host_free(void *p)
     return LT_OK;
 }
 
-// Device -> host for a list of outputs: one asynchronous copy each, straight into the caller's memory.  Into
-// pinned memory (lt_host_alloc) that is a DMA at PCIe rate (measured 55 GB/s: 1.2 ms for a 4096^2 RGBA8 frame).
-// Into pageable memory the HIP runtime pins the destination pages on the fly: 14 ms for the same 64 MiB the first
-// time a buffer is used, 1.2 ms when the same buffer is passed again (tools/scratch/hostmem_probe.cpp).  A staging
-// scheme of our own (pinned bounce buffer + host copy threads) was built and measured slower than that.
-struct OutCopy { void *dst; const void *src; size_t bytes; };
+// The device-side copies of a host-pointer call's arrays: pieces of the slot's ONE grow-only `dev` buffer, so nothing is
+// allocated per call once it has reached the frame size.  A call declares each array once -- host pointer, element
+// count and size, direction; a null host pointer declares nothing: its device pointer is null and its copies are skipped --, commits
+// (one grow, then the inputs' copies in the order declared), asks for device pointers and fetches the outputs.
+//
+// Device -> host is one asynchronous copy per output, straight into the caller's memory.  Into pinned memory
+// (lt_host_alloc) that is a DMA at PCIe rate (measured 55 GB/s: 1.2 ms for a 4096^2 RGBA8 frame).  Into pageable memory
+// the HIP runtime pins the destination pages on the fly: 14 ms for the same 64 MiB the first time a buffer is used,
+// 1.2 ms when the same buffer is passed again (tools/scratch/hostmem_probe.cpp).  A staging scheme of our own (pinned
+// bounce buffer + host copy threads) was built and measured slower than that.
+struct Staging {
+    static constexpr int MAX_PIECES = 12;
+    struct Piece { void *host; size_t count, unit, off; bool input; }; // `count` elements of `unit` bytes
+    StreamSlot *sl = nullptr; hipStream_t s = nullptr; // (set by commit)
+    Carver cv;
+    Piece pieces[MAX_PIECES];
+    int n_pieces = 0;
+    bool overflow = false; // more than MAX_PIECES declared: commit() refuses
+    int add(const void *host, size_t count, size_t unit, bool input)
+    {
+        if (n_pieces == MAX_PIECES) { overflow = true; return 0; }
+        pieces[n_pieces] = {(void *)host, count, unit, host ? cv.take(count * unit) : 0, input};
+        return n_pieces++;
+    }
+    int in(const void *host, size_t count, size_t unit) { return add(host, count, unit, true); }
+    int out(void *host, size_t count, size_t unit) { return add(host, count, unit, false); }
+    int commit(hipStream_t stream)
+    {
+        if (overflow) return fail(LT_ERR_INVALID_ARG, "Staging: more than %d arrays declared", MAX_PIECES);
+        s = stream;
+        int rc = get_slot(s, &sl);
+        if (rc || (rc = grow(sl->dev, cv.off, s))) return rc;
+        for (int i = 0; i < n_pieces; ++i)
+            if (pieces[i].input && pieces[i].host)
+                HIP_TRY(hipMemcpyAsync(dev<char>(i), pieces[i].host, pieces[i].count * pieces[i].unit, hipMemcpyHostToDevice, s));
+        return LT_OK;
+    }
+    template <typename P> P *dev(int i) const { return pieces[i].host ? (P *)((char *)sl->dev.p + pieces[i].off) : nullptr; }
+    // `count` elements of piece i, from its element `dev_first` on, to element `host_first` of the host array
+    int fetch(int i, size_t host_first, size_t dev_first, size_t count) const
+    {
+        const Piece &pc = pieces[i];
+        if (pc.host && count)
+            HIP_TRY(hipMemcpyAsync((char *)pc.host + host_first * pc.unit, dev<char>(i) + dev_first * pc.unit, count * pc.unit,
+                                   hipMemcpyDeviceToHost, s));
+        return LT_OK;
+    }
+    int fetch(int i) const { return fetch(i, 0, 0, pieces[i].count); }
+};
 
-static int copy_out(hipStream_t s, const std::vector<OutCopy> &outs)
-{
-    for (const OutCopy &o : outs)
-        if (o.bytes) HIP_TRY(hipMemcpyAsync(o.dst, o.src, o.bytes, hipMemcpyDeviceToHost, s));
-    return LT_OK;
-}
+// The arrays of one lt_render call (or of one partition of lt_render_multi) in the slot's buffer: `n` pixels of the
+// partition, the background of the whole frame, the counters into st->counters.
+struct FrameStaging : Staging {
+    int stats, bg, fa, w, status, steps, rgb, rgba;
+    void declare(lt_stats *st, const float *h_bg, int32_t bg_channels, size_t n_full, size_t n, float *out_fa, uint16_t *out_w,
+                 int8_t *out_status, uint32_t *out_steps, float *out_rgb, uint8_t *out_rgba)
+    {
+        stats = out(st->counters, LT_STAT_WORDS, 8);
+        bg = in(h_bg, n_full, bg_channels * sizeof(float));
+        fa = out(out_fa, n, 4); w = out(out_w, n, 2); status = out(out_status, n, 1);
+        steps = out(out_steps, n, 4); rgb = out(out_rgb, n, (h_bg ? bg_channels : 3) * 4);
+        rgba = out(out_rgba, n, 4);
+    }
+    // Once committed: zeroes the counters and renders with the slot's private timing events (concurrent
+    // lt_render_dev(timing = 1) callers keep theirs).  dp: a disk with its device-side outputs, or NULL.
+    int render(const lt_camera *cam, const lt_metric *metric, lt_opts o, int32_t bg_channels, const DiskParams *dp)
+    {
+        int rc;
+        HIP_TRY(hipMemsetAsync(dev<char>(stats), 0, LT_STAT_WORDS * 8, s));
+        if ((rc = slot_events(sl))) return rc;
+        o.timing = 0;
+        return render_dev_impl(cam, metric, &o, dev<const float>(bg), bg_channels, dev<float>(fa), dev<uint16_t>(w), dev<int8_t>(status),
+                               dev<uint32_t>(steps), dev<float>(rgb), dev<uint8_t>(rgba), dev<uint64_t>(stats), &sl->own, dp);
+    }
+    // small and first to be consumed go first; the framebuffer follows
+    std::array<int, 6> fetch_order() const { return {rgba, fa, w, status, steps, rgb}; }
+    // the three stage times of the frame this slot rendered last (after its stream was synchronised)
+    int times(float ms[3]) const
+    {
+        for (int i = 0; i < 3; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], sl->own.e[i], sl->own.e[i + 1]));
+        return LT_OK;
+    }
+};
 
 // lt_render, and with `disk` lt_render_disk (out_disk: (R, W, 3) float32 host array or NULL) or, with
 // disk->max_images > 0, lt_render_disk_images (out_images (R, W, max_images, 3) float32, out_n_hits (R, W), or NULL)
@@ -1056,61 +1183,26 @@ static int render_host_impl(const lt_camera *cam, const lt_metric *metric, const
     int64_t rows = 0;
     if ((rc = partition_blocks(cam->height, o, nullptr, &rows))) return rc;
     if (bg && bg_channels != 1 && bg_channels != 3) return fail(LT_ERR_INVALID_ARG, "bg_channels must be 1 or 3");
-    size_t n = (size_t)rows * cam->width;
-    size_t n_full = (size_t)cam->height * cam->width;
-    int nch = bg ? bg_channels : 3;
-    hipStream_t s = (hipStream_t)o.stream;
-    StreamSlot *sl;
-    if ((rc = get_slot(s, &sl))) return rc;
-    // device-side inputs / outputs: pieces of ONE grow-only buffer of this (device, stream) -- nothing is
-    // allocated per call once it has reached the frame size
-    Carver cv;
-    size_t o_stats = cv.take(LT_STAT_WORDS * 8);
-    size_t o_bg = bg ? cv.take(n_full * bg_channels * sizeof(float)) : 0;
-    size_t o_fa = out_fa ? cv.take(n * 4) : 0, o_w = out_w ? cv.take(n * 2) : 0, o_st = out_status ? cv.take(n) : 0;
-    size_t o_steps = out_steps ? cv.take(n * 4) : 0, o_rgb = out_rgb ? cv.take(n * nch * 4) : 0;
-    size_t o_rgba = out_rgba ? cv.take(n * 4) : 0;
-    size_t o_disk = (disk && out_disk) ? cv.take(n * 3 * 4) : 0;
-    const size_t n_img = disk ? n * (size_t)disk->max_images * 3 : 0;
-    size_t o_img = (disk && out_images) ? cv.take(n_img * 4) : 0, o_hits = (disk && out_n_hits) ? cv.take(n) : 0;
-    if ((rc = grow(sl->dev, cv.off, s))) return rc;
-    char *base = (char *)sl->dev.p;
-    auto at = [&](bool want, size_t off) -> void * { return want ? (void *)(base + off) : nullptr; };
-    if (bg) HIP_TRY(hipMemcpyAsync(base + o_bg, bg, n_full * bg_channels * sizeof(float), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(base + o_stats, 0, LT_STAT_WORDS * 8, s));
-    if ((rc = slot_events(sl))) return rc;
-    o.timing = 0; // private events: concurrent lt_render_dev(timing = 1) callers keep theirs
+    const size_t n = (size_t)rows * cam->width;
+    lt_stats st;
+    memset(&st, 0, sizeof(st));
+    FrameStaging fs;
+    fs.declare(&st, bg, bg_channels, (size_t)cam->height * cam->width, n, out_fa, out_w, out_status, out_steps, out_rgb, out_rgba);
+    const int i_disk = fs.out(out_disk, n, 3 * 4);
+    const int i_img = fs.out(out_images, n, disk ? (size_t)disk->max_images * 3 * 4 : 0), i_hits = fs.out(out_n_hits, n, 1);
+    if ((rc = fs.commit((hipStream_t)o.stream))) return rc;
     DiskParams dp{};
     if (disk) {
         dp = *disk;
-        dp.d_disk = (float *)at(out_disk != nullptr, o_disk);
-        dp.d_images = (float *)at(out_images != nullptr, o_img);
-        dp.d_n_hits = (uint8_t *)at(out_n_hits != nullptr, o_hits);
+        dp.d_disk = fs.dev<float>(i_disk); dp.d_images = fs.dev<float>(i_img); dp.d_n_hits = fs.dev<uint8_t>(i_hits);
     }
-    rc = render_dev_impl(cam, metric, &o, (const float *)at(bg != nullptr, o_bg), bg_channels, (float *)at(out_fa, o_fa),
-                         (uint16_t *)at(out_w, o_w), (int8_t *)at(out_status, o_st), (uint32_t *)at(out_steps, o_steps),
-                         (float *)at(out_rgb, o_rgb), (uint8_t *)at(out_rgba, o_rgba), (uint64_t *)(base + o_stats),
-                         &sl->own, disk ? &dp : nullptr);
-    if (rc) return rc;
-    lt_stats st;
-    memset(&st, 0, sizeof(st));
-    std::vector<OutCopy> outs;
-    // small and first to be consumed go first; the framebuffer(s) follow
-    if (out_rgba) outs.push_back({out_rgba, base + o_rgba, n * 4});
-    if (out_fa) outs.push_back({out_fa, base + o_fa, n * 4});
-    if (out_w) outs.push_back({out_w, base + o_w, n * 2});
-    if (out_status) outs.push_back({out_status, base + o_st, n});
-    if (out_steps) outs.push_back({out_steps, base + o_steps, n * 4});
-    if (out_rgb) outs.push_back({out_rgb, base + o_rgb, n * nch * 4});
-    if (disk && out_disk) outs.push_back({out_disk, base + o_disk, n * 3 * 4});
-    if (disk && out_images) outs.push_back({out_images, base + o_img, n_img * 4});
-    if (disk && out_n_hits) outs.push_back({out_n_hits, base + o_hits, n});
-    if ((rc = copy_out(s, outs))) return rc;
-    HIP_TRY(hipMemcpyAsync(st.counters, base + o_stats, LT_STAT_WORDS * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    if ((rc = fs.render(cam, metric, o, bg_channels, disk ? &dp : nullptr))) return rc;
+    for (int i : fs.fetch_order()) if ((rc = fs.fetch(i))) return rc;
+    if ((rc = fs.fetch(i_disk)) || (rc = fs.fetch(i_img)) || (rc = fs.fetch(i_hits)) || (rc = fs.fetch(fs.stats))) return rc;
+    HIP_TRY(hipStreamSynchronize(fs.s));
     if (rows > 0) {
         float ms[3] = {0, 0, 0};
-        for (int i = 0; i < 3; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], sl->own.e[i], sl->own.e[i + 1]));
+        if ((rc = fs.times(ms))) return rc;
         st.prologue_ms = ms[0]; st.integrate_ms = ms[1]; st.epilogue_ms = ms[2];
     }
     if (stats) *stats = st;
@@ -1161,9 +1253,8 @@ extern "C" int lt_render_multi(const lt_camera *cam, const lt_metric *metric, co
     HIP_TRY(hipGetDevice(&keep));
     struct Restore { int d; ~Restore() { (void)hipSetDevice(d); } } restore{keep};
 
-    const int W = cam->width, H = cam->height, nch = bg ? bg_channels : 3;
-    const size_t n_full = (size_t)W * H;
-    struct Part { hipStream_t s; StreamSlot *sl; char *base; int64_t rows; size_t o_stats, o_fa, o_w, o_st, o_steps, o_rgb, o_rgba; };
+    const int W = cam->width, H = cam->height;
+    struct Part { FrameStaging fs; int64_t rows; };
     std::vector<Part> parts((size_t)n_gpus);
     std::vector<lt_stats> each((size_t)n_gpus); // destination of asynchronous copies: must outlive the drain below
     // Any return before the end leaves kernels and device-to-host copies of other partitions in flight, writing the
@@ -1171,42 +1262,23 @@ extern "C" int lt_render_multi(const lt_camera *cam, const lt_metric *metric, co
     struct Drain {
         std::vector<std::pair<int, hipStream_t>> used;
         bool done = false;
-        ~Drain()
-        {
-            if (done) return;
-            for (auto &u : used) { (void)hipSetDevice(u.first); (void)hipStreamSynchronize(u.second); }
-        }
+        ~Drain() { if (!done) for (auto &u : used) { (void)hipSetDevice(u.first); (void)hipStreamSynchronize(u.second); } }
     } drain;
     // 1. launch every partition (asynchronous): all devices compute at the same time
     for (int p = 0; p < n_gpus; ++p) {
         Part &P = parts[(size_t)p];
+        hipStream_t ps;
         HIP_TRY(hipSetDevice(dev[(size_t)p]));
-        if ((rc = multi_stream(dev[(size_t)p], p, &P.s))) return rc;
-        drain.used.push_back({dev[(size_t)p], P.s});
-        if ((rc = get_slot(P.s, &P.sl))) return rc;
+        if ((rc = multi_stream(dev[(size_t)p], p, &ps))) return rc;
+        drain.used.push_back({dev[(size_t)p], ps});
         P.rows = lt_local_rows(H, o.row_block, n_gpus, p);
-        size_t n = (size_t)P.rows * W;
-        Carver cv;
-        P.o_stats = cv.take(LT_STAT_WORDS * 8);
-        size_t o_bg = bg ? cv.take(n_full * bg_channels * sizeof(float)) : 0;
-        P.o_fa = out_fa ? cv.take(n * 4) : 0; P.o_w = out_w ? cv.take(n * 2) : 0; P.o_st = out_status ? cv.take(n) : 0;
-        P.o_steps = out_steps ? cv.take(n * 4) : 0; P.o_rgb = out_rgb ? cv.take(n * nch * 4) : 0;
-        P.o_rgba = out_rgba ? cv.take(n * 4) : 0;
-        if ((rc = grow(P.sl->dev, cv.off, P.s))) return rc;
-        P.base = (char *)P.sl->dev.p;
-        char *base = P.base;
-        auto at = [&](bool want, size_t off) -> void * { return want ? (void *)(base + off) : nullptr; };
-        if (bg) HIP_TRY(hipMemcpyAsync(base + o_bg, bg, n_full * bg_channels * sizeof(float), hipMemcpyHostToDevice, P.s));
-        HIP_TRY(hipMemsetAsync(base + P.o_stats, 0, LT_STAT_WORDS * 8, P.s));
-        if ((rc = slot_events(P.sl))) return rc;
+        memset(&each[(size_t)p], 0, sizeof(lt_stats));
+        P.fs.declare(&each[(size_t)p], bg, bg_channels, (size_t)W * H, (size_t)P.rows * W, out_fa, out_w, out_status, out_steps,
+                     out_rgb, out_rgba);
         lt_opts op = o;
-        op.n_parts = n_gpus; op.part = p; op.stream = (void *)P.s; op.timing = 0;
+        op.n_parts = n_gpus; op.part = p; op.stream = (void *)ps;
         op.block_owner = nullptr; op.n_blocks = 0; // lt_render_multi partitions block-cyclically
-        rc = render_dev_impl(cam, metric, &op, (const float *)at(bg != nullptr, o_bg), bg_channels, (float *)at(out_fa, P.o_fa),
-                             (uint16_t *)at(out_w, P.o_w), (int8_t *)at(out_status, P.o_st), (uint32_t *)at(out_steps, P.o_steps),
-                             (float *)at(out_rgb, P.o_rgb), (uint8_t *)at(out_rgba, P.o_rgba), (uint64_t *)(base + P.o_stats),
-                             &P.sl->own);
-        if (rc) return rc;
+        if ((rc = P.fs.commit(ps)) || (rc = P.fs.render(cam, metric, op, bg_channels, nullptr))) return rc;
     }
     // 2. every device copies its row blocks to their place in the caller's full-frame arrays
     lt_stats total;
@@ -1214,34 +1286,23 @@ extern "C" int lt_render_multi(const lt_camera *cam, const lt_metric *metric, co
     for (int p = 0; p < n_gpus; ++p) {
         Part &P = parts[(size_t)p];
         HIP_TRY(hipSetDevice(dev[(size_t)p]));
-        std::vector<OutCopy> outs;
-        auto rows_of = [&](void *dst, size_t off, size_t px_bytes) {
-            if (!dst) return;
-            size_t row_bytes = (size_t)W * px_bytes;
-            for (int64_t l0 = 0; l0 < P.rows; l0 += o.row_block) {
+        for (int i : P.fs.fetch_order()) {
+            for (int64_t l0 = 0; l0 < P.rows; l0 += o.row_block) { // (elements are pixels: W of them per row)
                 int64_t g0 = lt_global_row(l0, o.row_block, n_gpus, p);
                 int64_t nr = P.rows - l0 < o.row_block ? P.rows - l0 : o.row_block;
-                outs.push_back({(char *)dst + (size_t)g0 * row_bytes, P.base + off + (size_t)l0 * row_bytes, (size_t)nr * row_bytes});
+                if ((rc = P.fs.fetch(i, (size_t)g0 * W, (size_t)l0 * W, (size_t)nr * W))) return rc;
             }
-        };
-        rows_of(out_rgba, P.o_rgba, 4);
-        rows_of(out_fa, P.o_fa, 4);
-        rows_of(out_w, P.o_w, 2);
-        rows_of(out_status, P.o_st, 1);
-        rows_of(out_steps, P.o_steps, 4);
-        rows_of(out_rgb, P.o_rgb, (size_t)nch * 4);
-        if ((rc = copy_out(P.s, outs))) return rc;
-        memset(&each[(size_t)p], 0, sizeof(lt_stats));
-        HIP_TRY(hipMemcpyAsync(each[(size_t)p].counters, P.base + P.o_stats, LT_STAT_WORDS * 8, hipMemcpyDeviceToHost, P.s));
+        }
+        if ((rc = P.fs.fetch(P.fs.stats))) return rc;
     }
     for (int p = 0; p < n_gpus; ++p) {
         Part &P = parts[(size_t)p];
         HIP_TRY(hipSetDevice(dev[(size_t)p]));
-        HIP_TRY(hipStreamSynchronize(P.s));
+        HIP_TRY(hipStreamSynchronize(P.fs.s));
         for (int i = 0; i < LT_STAT_WORDS; ++i) total.counters[i] += each[(size_t)p].counters[i];
         if (P.rows > 0) {
             float ms[3] = {0, 0, 0};
-            for (int i = 0; i < 3; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], P.sl->own.e[i], P.sl->own.e[i + 1]));
+            if ((rc = P.fs.times(ms))) return rc;
             if (ms[0] > total.prologue_ms) total.prologue_ms = ms[0];
             if (ms[1] > total.integrate_ms) total.integrate_ms = ms[1];
             if (ms[2] > total.epilogue_ms) total.epilogue_ms = ms[2];
@@ -1268,7 +1329,7 @@ static int trace_batch(const MetricConsts &mc, lt_opts &o, double lambda_max, co
     if (!alphas || !out_fa || !out_w) return fail(LT_ERR_INVALID_ARG, "null alphas / out_fa / out_w");
     if (mc.kind == LT_METRIC_KERR && !thetas) return fail(LT_ERR_INVALID_ARG, "Kerr needs thetas");
     int64_t n_q = (n + 63) / 64 * 64;
-    size_t elem = o.precision == 32 ? sizeof(float) : sizeof(double);
+    const size_t elem = elem_size(o.precision);
     // The twins are synchronous calls on the default stream, like the reference's ("no async").  Records
     // and staging buffers belong to the (device, default stream) slot, so they never alias what an lt_render_dev
     // call on another stream is using, and nothing is allocated per call once they have grown.
@@ -1277,62 +1338,41 @@ static int trace_batch(const MetricConsts &mc, lt_opts &o, double lambda_max, co
     if ((rc = get_workspace(s, (size_t)n_q, elem, &w))) return rc;
     DiskRecordsBuf recs;
     if ((rc = get_disk_records(s, n_q, elem, disk, &recs))) return rc;
-    void *ic = w.ic, *fin0 = w.fin0, *fin1 = w.fin1;
-    StreamSlot *sl;
-    if ((rc = get_slot(s, &sl))) return rc;
-    Carver cv;
-    size_t o_al = cv.take(n * 8), o_th = thetas ? cv.take(n * 8) : 0, o_ref = refines ? cv.take(n) : 0;
-    size_t o_fa = cv.take(n * 8), o_w = cv.take(n * 8), o_st = out_status ? cv.take(n) : 0, o_ev = out_evals ? cv.take(n * 4) : 0;
-    size_t o_disk = (disk && out_disk) ? cv.take(n * 3 * 8) : 0;
-    const size_t n_img = disk ? (size_t)n * (size_t)disk->max_images * 3 : 0;
-    size_t o_img = (disk && out_images) ? cv.take(n_img * 8) : 0, o_hits = (disk && out_n_hits) ? cv.take(n * 4) : 0;
-    if ((rc = grow(sl->dev, cv.off, s))) return rc;
-    char *base = (char *)sl->dev.p;
-    const double *d_al = (const double *)(base + o_al);
-    const double *d_th = thetas ? (const double *)(base + o_th) : nullptr;
-    const uint8_t *d_ref = refines ? (const uint8_t *)(base + o_ref) : nullptr;
-    double *d_fa = (double *)(base + o_fa);
-    int64_t *d_w = (int64_t *)(base + o_w);
-    int8_t *d_st = out_status ? (int8_t *)(base + o_st) : nullptr;
-    uint32_t *d_ev = out_evals ? (uint32_t *)(base + o_ev) : nullptr;
-    double *d_disk = (disk && out_disk) ? (double *)(base + o_disk) : nullptr;
-    double *d_img = (disk && out_images) ? (double *)(base + o_img) : nullptr;
-    int32_t *d_hits = (disk && out_n_hits) ? (int32_t *)(base + o_hits) : nullptr;
-    HIP_TRY(hipMemcpyAsync((void *)d_al, alphas, n * 8, hipMemcpyHostToDevice, s));
-    if (thetas) HIP_TRY(hipMemcpyAsync((void *)d_th, thetas, n * 8, hipMemcpyHostToDevice, s));
-    if (refines) HIP_TRY(hipMemcpyAsync((void *)d_ref, refines, n, hipMemcpyHostToDevice, s));
-    unsigned gq = (unsigned)((n_q + 255) / 256);
-    if (o.precision == 32) k_prologue_arrays<float><<<gq, 256, 0, s>>>(mc, d_al, d_th, d_ref, n, (float4 *)ic, n_q);
-    else k_prologue_arrays<double><<<gq, 256, 0, s>>>(mc, d_al, d_th, d_ref, n, (double4 *)ic, n_q);
+    Staging st;
+    const int i_al = st.in(alphas, n, 8), i_th = st.in(thetas, n, 8), i_ref = st.in(refines, n, 1);
+    const int i_fa = st.out(out_fa, n, 8), i_w = st.out(out_w, n, 8), i_st = st.out(out_status, n, 1), i_ev = st.out(out_evals, n, 4);
+    const int i_disk = st.out(out_disk, n, 3 * 8);
+    const int i_img = st.out(out_images, n, disk ? (size_t)disk->max_images * 3 * 8 : 0), i_hits = st.out(out_n_hits, n, 4);
+    if ((rc = st.commit(s))) return rc;
+    double *d_fa = st.dev<double>(i_fa); int64_t *d_w = st.dev<int64_t>(i_w);
+    int8_t *d_st = st.dev<int8_t>(i_st); uint32_t *d_ev = st.dev<uint32_t>(i_ev);
+    with_precision(o.precision, [&](auto t) {
+        using T = decltype(t);
+        k_prologue_arrays<T><<<(unsigned)((n_q + 255) / 256), 256, 0, s>>>(mc, st.dev<const double>(i_al), st.dev<const double>(i_th),
+                                                                          st.dev<const uint8_t>(i_ref), n, w.ic<T>(), n_q);
+    });
     HIP_TRY(hipGetLastError());
-    if (disk)
-        rc = o.precision == 32 ? launch_integrate_disk<float>(mc, o, lambda_max, w, n_q, s, nullptr, *disk, recs)
-                               : launch_integrate_disk<double>(mc, o, lambda_max, w, n_q, s, nullptr, *disk, recs);
-    else
-        rc = o.precision == 32 ? launch_integrate<float>(mc, o, lambda_max, w, n_q, s, nullptr)
-                               : launch_integrate<double>(mc, o, lambda_max, w, n_q, s, nullptr);
-    if (rc) return rc;
-    unsigned gn = (unsigned)((n + 255) / 256);
+    if ((rc = launch_integrate_any(mc, o, lambda_max, w, n_q, s, nullptr, disk, recs))) return rc;
     if (disk && disk->max_images) {
-        if ((rc = launch_epilogue_arrays_disk_images(mc, o, w, n, n_q, d_fa, d_w, d_st, d_ev, d_img, d_hits, s, *disk, recs))) return rc;
-    } else if (disk) {
-        const DiskShade ds{mc.M, mc.a, disk->r_in, disk->q, disk->exposure};
-        if (o.precision == 32)
-            k_epilogue_arrays_disk<float><<<gn, 256, 0, s>>>(mc, ds, (const float4 *)fin0, (const float4 *)fin1, n, d_fa, d_w, d_st, d_disk, d_ev);
+        if ((rc = launch_epilogue_arrays_disk_images(mc, o, w, n, d_fa, d_w, d_st, d_ev, st.dev<double>(i_img), st.dev<int32_t>(i_hits), s,
+                                                     *disk, recs)))
+            return rc;
+    } else {
+        const unsigned gn = (unsigned)((n + 255) / 256);
+        if (disk)
+            with_precision(o.precision, [&](auto t) {
+                using T = decltype(t);
+                k_epilogue_arrays_disk<T><<<gn, 256, 0, s>>>(mc, DiskShade{mc.M, mc.a, disk->r_in, disk->q, disk->exposure}, w.fin0<T>(),
+                                                             w.fin1<T>(), n, d_fa, d_w, d_st, st.dev<double>(i_disk), d_ev);
+            });
         else
-            k_epilogue_arrays_disk<double><<<gn, 256, 0, s>>>(mc, ds, (const double4 *)fin0, (const double4 *)fin1, n, d_fa, d_w, d_st, d_disk, d_ev);
-    } else if (o.precision == 32)
-        k_epilogue_arrays<float><<<gn, 256, 0, s>>>(mc, (const float4 *)fin0, (const float4 *)fin1, n, d_fa, d_w, d_st, d_ev);
-    else
-        k_epilogue_arrays<double><<<gn, 256, 0, s>>>(mc, (const double4 *)fin0, (const double4 *)fin1, n, d_fa, d_w, d_st, d_ev);
+            with_precision(o.precision, [&](auto t) {
+                using T = decltype(t);
+                k_epilogue_arrays<T><<<gn, 256, 0, s>>>(mc, w.fin0<T>(), w.fin1<T>(), n, d_fa, d_w, d_st, d_ev);
+            });
+    }
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out_fa, d_fa, n * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(out_w, d_w, n * 8, hipMemcpyDeviceToHost, s));
-    if (out_status) HIP_TRY(hipMemcpyAsync(out_status, d_st, n, hipMemcpyDeviceToHost, s));
-    if (out_evals) HIP_TRY(hipMemcpyAsync(out_evals, d_ev, n * 4, hipMemcpyDeviceToHost, s));
-    if (d_disk) HIP_TRY(hipMemcpyAsync(out_disk, d_disk, n * 3 * 8, hipMemcpyDeviceToHost, s));
-    if (d_img) HIP_TRY(hipMemcpyAsync(out_images, d_img, n_img * 8, hipMemcpyDeviceToHost, s));
-    if (d_hits) HIP_TRY(hipMemcpyAsync(out_n_hits, d_hits, n * 4, hipMemcpyDeviceToHost, s));
+    for (int i : {i_fa, i_w, i_st, i_ev, i_disk, i_img, i_hits}) if ((rc = st.fetch(i))) return rc;
     HIP_TRY(hipStreamSynchronize(s));
     return LT_OK;
 }
@@ -1352,6 +1392,18 @@ extern "C" int lt_trace_batch_schw(double M, double r_obs, const double *alphas,
     return trace_batch(mc, o, 0.0, alphas, nullptr, nullptr, n, out_fa, out_w, out_status, out_rhs_evals);
 }
 
+// What the Kerr batch twins share: default options with the caller's three, the checks, the metric block.
+static int kerr_batch_setup(const lt_metric *m, double r_obs, double theta_obs, int integrator, int precision, int schedule,
+                            lt_opts *o, MetricConsts *mc)
+{
+    int rc;
+    lt_default_opts(o);
+    o->integrator = integrator; o->precision = precision; o->schedule = schedule;
+    if ((rc = check_opts(m, o)) || (rc = make_metric(m, r_obs, theta_obs, 0.0, mc))) return rc;
+    count_evals(integrator, mc);
+    return LT_OK;
+}
+
 extern "C" int lt_trace_batch_kerr(double M, double a, double r_obs, const double *alphas, const double *thetas,
                                    double theta_obs, double lambda_max, const uint8_t *axis_refines, int integrator,
                                    int precision, int schedule, int64_t n, double *out_fa, int64_t *out_w,
@@ -1361,12 +1413,8 @@ extern "C" int lt_trace_batch_kerr(double M, double a, double r_obs, const doubl
     if (rc) return rc;
     lt_metric m{LT_METRIC_KERR, 0, M, a};
     lt_opts o;
-    lt_default_opts(&o);
-    o.integrator = integrator; o.precision = precision; o.schedule = schedule;
-    if ((rc = check_opts(&m, &o))) return rc;
     MetricConsts mc;
-    if ((rc = make_metric(&m, r_obs, theta_obs, 0.0, &mc))) return rc;
-    if (integrator != LT_INTEGRATOR_RK4) { mc.evals_fixed = 1; mc.evals_per_step = 6; }
+    if ((rc = kerr_batch_setup(&m, r_obs, theta_obs, integrator, precision, schedule, &o, &mc))) return rc;
     return trace_batch(mc, o, lambda_max, alphas, thetas, axis_refines, n, out_fa, out_w, out_status, out_rhs_evals);
 }
 
@@ -1383,13 +1431,11 @@ extern "C" int lt_kerr_rhs_probe(double M, double a, const double *states, const
     if ((rc = ds.alloc(n * 40)) || (rc = dp.alloc(n * 8)) || (rc = dout.alloc(n * 40))) return rc;
     HIP_TRY(hipMemcpy(ds.p, states, n * 40, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dp.p, p_phi, n * 8, hipMemcpyHostToDevice));
-    unsigned g = (unsigned)((n + 63) / 64);
-    if (precision == 32)
-        k_kerr_rhs_probe<float><<<g, 64>>>(make_kerr<float>(mc, 5000.0, 1.0), (const double *)ds.p, (const double *)dp.p, n,
-                                           (double *)dout.p);
-    else
-        k_kerr_rhs_probe<double><<<g, 64>>>(make_kerr<double>(mc, 5000.0, 1.0), (const double *)ds.p, (const double *)dp.p,
-                                            n, (double *)dout.p);
+    with_precision(precision, [&](auto t) {
+        using T = decltype(t);
+        k_kerr_rhs_probe<T><<<(unsigned)((n + 63) / 64), 64>>>(make_kerr<T>(mc, 5000.0, 1.0), (const double *)ds.p, (const double *)dp.p, n,
+                                                               (double *)dout.p);
+    });
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(out, dout.p, n * 40, hipMemcpyDeviceToHost));
     return LT_OK;
@@ -1435,169 +1481,7 @@ extern "C" int lt_scatter_rows_indexed_dev(const void *d_rows, void *d_full, con
 }
 
 #ifdef LT_PROBES
-// Diagnostic microbenchmarks (tools/issue_probe.py, lone_step.py ...): compiled only into the probe build
-// (`python __graft_entry__.py --probes` -> lib/libltrace_probes.so), never into the product library.
-extern "C" int lt_valu_peak_probe(int mode, int iters, double *tflops)
-{
-    int rc = require_device();
-    if (rc) return rc;
-    DevBuf sink;
-    if ((rc = sink.alloc(64))) return rc;
-    hipDeviceProp_t prop;
-    int dev;
-    HIP_TRY(hipGetDevice(&dev));
-    HIP_TRY(hipGetDeviceProperties(&prop, dev));
-    unsigned grid = (unsigned)prop.multiProcessorCount * 8; // 8 blocks of 256 = 32 waves per CU
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
-    k_valu_probe<<<grid, 256>>>(mode, 16, (float *)sink.p); // warm-up
-    HIP_TRY(hipEventRecord(e0, 0));
-    k_valu_probe<<<grid, 256>>>(mode, iters, (float *)sink.p);
-    HIP_TRY(hipEventRecord(e1, 0));
-    HIP_TRY(hipEventSynchronize(e1));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    double fma_per_lane = (double)iters * 64.0 * (mode == 1 ? 2.0 : 1.0);
-    double flops = fma_per_lane * 2.0 * 256.0 * grid;
-    if (tflops) *tflops = flops / (ms * 1e-3) / 1e12;
-    return LT_OK;
-}
-
-// VALU issue-cost probe: instruction class `index` (see lt_probe.hpp), `waves_per_simd` resident waves
-// per SIMD (1..8) on every CU.  Reports the kernel time and the number of wave-instructions each SIMD
-// issued, i.e. ns per wave-instruction per SIMD (multiply by the shader clock for cycles).
-extern "C" int lt_valu_issue_probe(int index, int waves_per_simd, int iters, int constant_data, char *name_out,
-                                   int name_len, double *ns_per_instr, double *clock_mhz)
-{
-    int rc = require_device();
-    if (rc) return rc;
-    if (index < 0 || index >= g_n_probes) return fail(LT_ERR_INVALID_ARG, "probe index %d out of range [0,%d)", index, g_n_probes);
-    if (waves_per_simd < 1 || waves_per_simd > 8) return fail(LT_ERR_INVALID_ARG, "waves_per_simd must be 1..8");
-    const ProbeEntry &pe = g_probes[index];
-    if (name_out && name_len > 0) snprintf(name_out, (size_t)name_len, "%s", pe.name);
-    int cus;
-    if ((rc = cu_count(&cus))) return rc;
-    DevBuf sink;
-    if ((rc = sink.alloc(64))) return rc;
-    unsigned grid = (unsigned)(cus * waves_per_simd);
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
-    float sc = constant_data ? 0.0f : 0.999f;
-    pe.kernel<<<grid, 256>>>(8, sc, (float *)sink.p);
-    HIP_TRY(hipEventRecord(e0, 0));
-    pe.kernel<<<grid, 256>>>(iters, sc, (float *)sink.p);
-    HIP_TRY(hipEventRecord(e1, 0));
-    HIP_TRY(hipEventSynchronize(e1));
-    HIP_TRY(hipGetLastError());
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    double instr_per_simd = (double)iters * 64.0 * pe.instr_per_body * waves_per_simd; // 8 bodies x 8 chains
-    if (ns_per_instr) *ns_per_instr = ms * 1e6 / instr_per_simd;
-    unsigned long long h[4] = {0, 0, 0, 0};
-    HIP_TRY(hipMemcpy(h, sink.p, sizeof(h), hipMemcpyDeviceToHost));
-    if (clock_mhz) *clock_mhz = h[3] ? (double)h[2] / (double)h[3] * 100.0 : 0.0; // s_memtime / s_memrealtime(100 MHz)
-    return LT_OK;
-}
-
-extern "C" int lt_valu_issue_probe_count(void) { return g_n_probes; }
-
-// RK4-step issue probe: `iters` steps of the Kerr RK4 step per lane at `waves_per_simd` resident waves
-// per SIMD.  Returns shader cycles per step per wave-slot-on-a-SIMD (i.e. elapsed cycles x
-// waves_per_simd / iters ... divided back out: cycles one SIMD spends per wave-step) and the clock.
-extern "C" int lt_rk4_step_probe(int precision, int waves_per_simd, int iters, double *cycles_per_wave_step,
-                                 double *clock_mhz)
-{
-    int rc = require_device();
-    if (rc) return rc;
-    if (waves_per_simd < 1 || waves_per_simd > 8) return fail(LT_ERR_INVALID_ARG, "waves_per_simd must be 1..8");
-    lt_metric m{LT_METRIC_KERR, 0, 1.0, 0.9};
-    MetricConsts mc;
-    if ((rc = make_metric(&m, 50.0, M_PI / 2, 0.0, &mc))) return rc;
-    int cus;
-    if ((rc = cu_count(&cus))) return rc;
-    DevBuf out;
-    if ((rc = out.alloc(256))) return rc;
-    unsigned grid = (unsigned)(cus * waves_per_simd);
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
-    for (int rep = 0; rep < 2; ++rep) {
-        if (rep) HIP_TRY(hipEventRecord(e0, 0));
-        if (precision == 32)
-            k_probe_rk4_step<float><<<grid, 256>>>(make_kerr<float>(mc, 5000.0, 1.0), rep ? iters : 16, 0.01f, (float *)out.p);
-        else
-            k_probe_rk4_step<double><<<grid, 256>>>(make_kerr<double>(mc, 5000.0, 1.0), rep ? iters : 16, 0.01, (double *)out.p);
-    }
-    HIP_TRY(hipEventRecord(e1, 0));
-    HIP_TRY(hipEventSynchronize(e1));
-    HIP_TRY(hipGetLastError());
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    // the in-kernel stamps come from the oldest wave, which wins issue arbitration: use them for the
-    // clock only, and the launch's wall time for the throughput
-    unsigned long long h[2] = {0, 0};
-    HIP_TRY(hipMemcpy(h, out.p, sizeof(h), hipMemcpyDeviceToHost));
-    double mhz = h[1] ? (double)h[0] / (double)h[1] * 100.0 : 0.0;
-    if (clock_mhz) *clock_mhz = mhz;
-    if (cycles_per_wave_step) *cycles_per_wave_step = (double)ms * 1e-3 * mhz * 1e6 / ((double)iters * waves_per_simd);
-    return LT_OK;
-}
-
-// Piece probe (diagnostic): PIECE 0 sincos, 1 right-hand side without sincos, 2 the same without the
-// reciprocal, 3 the two polynomials alone; 4 evaluations per loop iteration.  Returns SIMD cycles per
-// evaluation per wave.
-#include "lt_probe_pieces.hpp"
-extern "C" int lt_piece_probe(int piece, int waves_per_simd, int iters, double *cycles_per_eval, double *clock_mhz)
-{
-    int rc = require_device();
-    if (rc) return rc;
-    lt_metric m{LT_METRIC_KERR, 0, 1.0, 0.9};
-    MetricConsts mc;
-    if ((rc = make_metric(&m, 50.0, M_PI / 2, 0.0, &mc))) return rc;
-    int cus;
-    if ((rc = cu_count(&cus))) return rc;
-    DevBuf out;
-    if ((rc = out.alloc(256))) return rc;
-    unsigned grid = (unsigned)(cus * waves_per_simd);
-    KerrConsts<float> k = make_kerr<float>(mc, 5000.0, 1.0);
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
-    for (int rep = 0; rep < 2; ++rep) {
-        int it = rep ? iters : 16;
-        if (rep) HIP_TRY(hipEventRecord(e0, 0));
-        if (piece == 0) k_probe_piece<0><<<grid, 256>>>(k, it, (float *)out.p);
-        else if (piece == 1) k_probe_piece<1><<<grid, 256>>>(k, it, (float *)out.p);
-        else if (piece == 2) k_probe_piece<2><<<grid, 256>>>(k, it, (float *)out.p);
-        else if (piece == 3) k_probe_piece<3><<<grid, 256>>>(k, it, (float *)out.p);
-        else if (piece == 4) k_probe_piece<4><<<grid, 256>>>(k, it, (float *)out.p);
-        else if (piece == 5) k_probe_piece<5><<<grid, 256>>>(k, it, (float *)out.p);
-        else if (piece == 6) k_probe_piece<6><<<grid, 256>>>(k, it, (float *)out.p);
-        else k_probe_piece<7><<<grid, 256>>>(k, it, (float *)out.p);
-    }
-    HIP_TRY(hipEventRecord(e1, 0));
-    HIP_TRY(hipEventSynchronize(e1));
-    HIP_TRY(hipGetLastError());
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    unsigned long long h[2] = {0, 0};
-    HIP_TRY(hipMemcpy(h, out.p, sizeof(h), hipMemcpyDeviceToHost));
-    double mhz = h[1] ? (double)h[0] / (double)h[1] * 100.0 : 0.0;
-    if (clock_mhz) *clock_mhz = mhz;
-    if (cycles_per_eval) *cycles_per_eval = (double)ms * 1e-3 * mhz * 1e6 / ((double)iters * 4.0 * waves_per_simd);
-    return LT_OK;
-}
-
+#include "lt_api_probes.inc"
 #endif // LT_PROBES
 
 #include "lt_api_stages.inc"

@@ -25,7 +25,9 @@ extern "C" void lt_default_disk(lt_disk *d)
 }
 
 // Refusals and the resolved inner edge.  `schedule`: LT_SCHED_* of the call (the queue schedule has no disk variant).
-static int resolve_disk(const lt_metric *metric, double r_obs, int schedule, const lt_disk *disk, DiskParams *dp)
+// max_images: NULL for the opaque disk, else the optically thin disk's slots per ray.
+static int resolve_disk(const lt_metric *metric, double r_obs, int schedule, const lt_disk *disk, const int32_t *max_images,
+                        DiskParams *dp)
 {
     if (!metric || !disk) return fail(LT_ERR_INVALID_ARG, "null metric / disk");
     if (metric->kind != LT_METRIC_KERR)
@@ -46,7 +48,30 @@ static int resolve_disk(const lt_metric *metric, double r_obs, int schedule, con
     dp->q = disk->q;
     dp->exposure = disk->exposure;
     dp->d_disk = nullptr;
+    if (!max_images) return LT_OK;
+    if (*max_images < 1 || *max_images > DISK_MAX_IMAGES)
+        return fail(LT_ERR_INVALID_ARG, "max_images %d not in [1, %d]", (int)*max_images, DISK_MAX_IMAGES);
+    dp->max_images = *max_images;
     return LT_OK;
+}
+
+// What the disk frame entry points do before the frame plumbing takes over.
+static int disk_frame_setup(const lt_camera *cam, const lt_metric *metric, const lt_opts *opts, const lt_disk *disk,
+                            const int32_t *max_images, DiskParams *dp)
+{
+    int rc = require_device();
+    if (rc) return rc;
+    if (!cam || !opts) return fail(LT_ERR_INVALID_ARG, "null camera / opts");
+    return resolve_disk(metric, cam->r_obs, opts->schedule, disk, max_images, dp);
+}
+
+// ... and the batch twins: the disk first, then lt_trace_batch_kerr's set-up on the direct schedule.
+static int disk_batch_setup(const lt_metric *m, double r_obs, double theta_obs, int integrator, int precision, const lt_disk *disk,
+                            const int32_t *max_images, DiskParams *dp, lt_opts *o, MetricConsts *mc)
+{
+    int rc = require_device();
+    if (rc || (rc = resolve_disk(m, r_obs, LT_SCHED_DIRECT, disk, max_images, dp))) return rc;
+    return kerr_batch_setup(m, r_obs, theta_obs, integrator, precision, LT_SCHED_DIRECT, o, mc);
 }
 
 // The integrate launch of both disks: the direct schedule of launch_integrate (launch_direct) with the disk's kernels,
@@ -55,17 +80,15 @@ template <typename T>
 static int launch_integrate_disk(const MetricConsts &mc, const lt_opts &o, double lambda_max, const Workspace &w, int64_t n_q,
                                  hipStream_t s, uint64_t *kstats, const DiskParams &dp, const DiskRecordsBuf &recs)
 {
-    using V = typename Vec4<T>::type;
-    using V2 = typename Vec2<T>::type;
     const KerrConsts<T> k = make_kerr<T>(mc, lambda_max, o.h_max);
     const DiskConsts<T> d{(T)dp.r_in, (T)dp.r_out, (T)(1.0 / (mc.r_plus * mc.r_plus))};
     if (dp.max_images)
         return launch_direct<T, DiskImagesKernels<T>>(o, w, n_q, s, 64, [&](auto kernel, unsigned grid, uint32_t long_iters, unsigned long long *head) {
-            kernel<<<grid, 64, 0, s>>>(k, d, (const V *)w.ic, (V *)w.fin0, (V *)w.fin1, n_q, long_iters, kstats, head, (V2 *)recs.img,
-                                       recs.hits, dp.max_images);
+            kernel<<<grid, 64, 0, s>>>(k, d, w.ic<T>(), w.fin0<T>(), w.fin1<T>(), n_q, long_iters, kstats, head, recs.img<T>(), recs.hits,
+                                       dp.max_images);
         });
     return launch_direct<T, DiskKernels<T>>(o, w, n_q, s, 64, [&](auto kernel, unsigned grid, uint32_t long_iters, unsigned long long *head) {
-        kernel<<<grid, 64, 0, s>>>(k, d, (const V *)w.ic, (V *)w.fin0, (V *)w.fin1, n_q, long_iters, kstats, head);
+        kernel<<<grid, 64, 0, s>>>(k, d, w.ic<T>(), w.fin0<T>(), w.fin1<T>(), n_q, long_iters, kstats, head);
     });
 }
 
@@ -73,15 +96,10 @@ static int launch_epilogue_disk(const CamConsts &c, const MetricConsts &mc, cons
                                 const FrameOut &fo, uint64_t *d_stats, hipStream_t s, const DiskParams &dp)
 {
     const DiskShade ds{mc.M, mc.a, dp.r_in, dp.q, dp.exposure};
-    const bool has_bg = fo.bg != nullptr && (fo.rgb || fo.rgba);
-    const dim3 ge((unsigned)((c.W + EPILOGUE_BLOCK - 1) / EPILOGUE_BLOCK), (unsigned)c.rows_local);
-    if (o.precision == 32) {
-        if (has_bg) k_epilogue_disk<float, true><<<ge, EPILOGUE_BLOCK, 0, s>>>(c, mc, ds, (const float4 *)w.fin0, (const float4 *)w.fin1, fo, dp.d_disk);
-        else k_epilogue_disk<float, false><<<ge, EPILOGUE_BLOCK, 0, s>>>(c, mc, ds, (const float4 *)w.fin0, (const float4 *)w.fin1, fo, dp.d_disk);
-    } else {
-        if (has_bg) k_epilogue_disk<double, true><<<ge, EPILOGUE_BLOCK, 0, s>>>(c, mc, ds, (const double4 *)w.fin0, (const double4 *)w.fin1, fo, dp.d_disk);
-        else k_epilogue_disk<double, false><<<ge, EPILOGUE_BLOCK, 0, s>>>(c, mc, ds, (const double4 *)w.fin0, (const double4 *)w.fin1, fo, dp.d_disk);
-    }
+    launch_epilogue_rows(c, o, fo, [&](auto t, auto bg, dim3 ge) {
+        using T = decltype(t);
+        k_epilogue_disk<T, decltype(bg)::value><<<ge, EPILOGUE_BLOCK, 0, s>>>(c, mc, ds, w.fin0<T>(), w.fin1<T>(), fo, dp.d_disk);
+    });
     // (this epilogue fills no word 7: its destination is the frame path's)
     if (d_stats) k_stats_reduce<<<1, STAT_SLOTS, 0, s>>>(w.partials, (unsigned long long *)d_stats, LT_STAT_DISK, LT_STAT_BG_TILES_GLOBAL);
     HIP_TRY(hipGetLastError());
@@ -92,11 +110,9 @@ extern "C" int lt_render_disk_dev(const lt_camera *cam, const lt_metric *metric,
                                   const float *d_bg, int32_t bg_channels, float *d_fa, uint16_t *d_w, int8_t *d_status,
                                   uint32_t *d_steps, float *d_disk, float *d_rgb, uint8_t *d_rgba, uint64_t *d_stats)
 {
-    int rc = require_device();
-    if (rc) return rc;
-    if (!cam || !opts) return fail(LT_ERR_INVALID_ARG, "null camera / opts");
     DiskParams dp;
-    if ((rc = resolve_disk(metric, cam->r_obs, opts->schedule, disk, &dp))) return rc;
+    int rc = disk_frame_setup(cam, metric, opts, disk, nullptr, &dp);
+    if (rc) return rc;
     dp.d_disk = d_disk;
     return render_dev_impl(cam, metric, opts, d_bg, bg_channels, d_fa, d_w, d_status, d_steps, d_rgb, d_rgba, d_stats,
                            nullptr, &dp);
@@ -106,11 +122,9 @@ extern "C" int lt_render_disk(const lt_camera *cam, const lt_metric *metric, con
                               const float *bg, int32_t bg_channels, float *out_fa, uint16_t *out_w, int8_t *out_status,
                               uint32_t *out_steps, float *out_disk, float *out_rgb, uint8_t *out_rgba, lt_stats *stats)
 {
-    int rc = require_device();
-    if (rc) return rc;
-    if (!cam || !opts) return fail(LT_ERR_INVALID_ARG, "null camera / opts");
     DiskParams dp;
-    if ((rc = resolve_disk(metric, cam->r_obs, opts->schedule, disk, &dp))) return rc;
+    int rc = disk_frame_setup(cam, metric, opts, disk, nullptr, &dp);
+    if (rc) return rc;
     return render_host_impl(cam, metric, opts, bg, bg_channels, out_fa, out_w, out_status, out_steps, out_rgb, out_rgba, stats,
                             &dp, out_disk);
 }
@@ -120,18 +134,12 @@ extern "C" int lt_trace_batch_kerr_disk(double M, double a, double r_obs, const 
                                         int precision, const lt_disk *disk, int64_t n, double *out_fa, int64_t *out_w,
                                         int8_t *out_status, double *out_disk, uint32_t *out_rhs_evals)
 {
-    int rc = require_device();
-    if (rc) return rc;
     lt_metric m{LT_METRIC_KERR, 0, M, a};
     DiskParams dp;
-    if ((rc = resolve_disk(&m, r_obs, LT_SCHED_DIRECT, disk, &dp))) return rc;
     lt_opts o;
-    lt_default_opts(&o);
-    o.integrator = integrator; o.precision = precision; o.schedule = LT_SCHED_DIRECT;
-    if ((rc = check_opts(&m, &o))) return rc;
     MetricConsts mc;
-    if ((rc = make_metric(&m, r_obs, theta_obs, 0.0, &mc))) return rc;
-    if (integrator != LT_INTEGRATOR_RK4) { mc.evals_fixed = 1; mc.evals_per_step = 6; }
+    int rc = disk_batch_setup(&m, r_obs, theta_obs, integrator, precision, disk, nullptr, &dp, &o, &mc);
+    if (rc) return rc;
     return trace_batch(mc, o, lambda_max, alphas, thetas, axis_refines, n, out_fa, out_w, out_status, out_rhs_evals, &dp,
                        out_disk);
 }

@@ -46,23 +46,11 @@ __global__ void __launch_bounds__(256) k_shade_lookup(CamConsts c, FrameOut o, c
 static int make_camera_only(const lt_camera *cam, double axis_refine_frac, CamConsts *c)
 {
     if (!cam || cam->width <= 0 || cam->height <= 0) return fail(LT_ERR_INVALID_ARG, "bad camera");
-    memset(c, 0, sizeof(*c));
-    c->W = cam->width; c->H = cam->height;
+    const bool front = camera_pinhole(cam, axis_refine_frac, c); // (zero-fills *c first)
+    c->refine_on = front;
     c->rows_local = c->trace_rows = c->H;
     c->row_block = c->H; c->n_parts = 1; c->part = 0;
     c->tiles_x = (c->W + 7) / 8; c->tiles_y = (c->H + 7) / 8;
-    c->half_W = c->W / 2.0; c->half_H = c->H / 2.0;
-    c->fx = (c->W / 2.0) / tan(cam->hfov / 2);
-    c->fy = (c->H / 2.0) / tan(cam->vfov / 2);
-    bool front;
-    psi_frame(cam->psi_y, cam->psi_x, c->d, c->ex, c->ey, &front);
-    c->refine_on = front;
-    if (front) {
-        c->bh_x_cam = c->d[0] / c->d[2];
-        double x_lo = fabs((0 - c->half_W) / c->fx - c->bh_x_cam), x_hi = fabs((c->W - 1 - c->half_W) / c->fx - c->bh_x_cam);
-        double m = x_lo > x_hi ? x_lo : x_hi;
-        c->refine_thresh = axis_refine_frac * (m > 1e-12 ? m : 1e-12);
-    }
     return LT_OK;
 }
 
