@@ -411,6 +411,90 @@ int lt_trace_batch_kerr_disk_images(double M, double a, double r_obs, const doub
                                     int64_t *out_w, int8_t *out_status, double *out_images, int32_t *out_n_hits,
                                     uint32_t *out_rhs_evals);
 
+/* ---- supersampled (anti-aliased) frames, resolved on the GPU ------------------------------------------- *
+ * Every frame above is one ray per pixel, taken at the pixel's corner.  These entry points trace S x S rays per       *
+ * pixel and write only the resolved pixels: nothing of the S^2 times larger frame crosses PCIe or stays in memory.    *
+ *                                                                                                               *
+ * Fine frame.  For a camera (W, H, hfov, vfov, psi, r_obs, theta_obs) and samples = S (1 <= S <= LT_AA_MAX_SAMPLES)  *
+ * the fine frame is the same camera with width = W S and height = H S.  The camera model uses pixel corners,        *
+ * x_cam = (ix - W/2) / fx, so fine pixel (y S + j, x S + i) is sub-sample (j, i) of output pixel (y, x), and          *
+ * sub-sample (0, 0) is the ray lt_render traces for that pixel.  There is no new camera arithmetic.                  *
+ *                                                                                                               *
+ * Modes.  The colour of a fine pixel is the colour an existing entry point gives the fine frame:                     *
+ *   LT_AA_PLAIN        lt_render_dev with tb_symmetry = 0 (opts->tb_symmetry is ignored);                              *
+ *   LT_AA_DISK         lt_render_disk_dev with `disk`;                                                                *
+ *   LT_AA_DISK_IMAGES  lt_render_disk_images_dev with `disk` and aa->max_images.                                      *
+ *                                                                                                               *
+ * Background.  d_bg is a full FINE-size image (H S, W S, bg_channels), the whole frame on every partition, or NULL      *
+ * (the mode's render without a background).  A fine pixel looks its texel up with the fine frame's own W S, H S,      *
+ * exactly as the mode's entry point does when it is given the fine camera and this image.                            *
+ *                                                                                                               *
+ * Resolve.  For every output pixel and channel: take the float32 colour the mode's epilogue writes for each of the    *
+ * pixel's S^2 fine pixels; add them in float64 in row-major order -- j outer, i inner -- starting from 0.0; divide    *
+ * by (double)(S S); round to float32.  RGBA8 follows from that float32 as everywhere: (x 255) truncated, alpha 255.   *
+ * So rgb is, bit for bit, that box filter of the rgb the mode's entry point returns for the fine frame, and with      *
+ * samples = 1 it is that entry point's rgb / rgba themselves.                                                         *
+ *                                                                                                               *
+ * Coverage.  d_cover (R, W, 4) uint8: how many of the pixel's S^2 sub-rays escaped, were captured, were invalid,       *
+ * and hit the disk.  LT_AA_DISK: slot 3 counts status LT_STATUS_DISK and the four slots sum to S^2.                   *
+ * LT_AA_DISK_IMAGES: slot 3 counts the rays with at least one hit and the first three slots sum to S^2.               *
+ * LT_AA_PLAIN: slot 3 is 0.                                                                                          *
+ *                                                                                                               *
+ * Stats.  Words 0-5, LT_STAT_DISK and LT_STAT_DISK_HITS are the fine frame's (rays = S^2 R W); so are the integrate    *
+ * kernel's words 6-9.  Kernel times are summed over the bands.                                                       *
+ *                                                                                                               *
+ * Partitions.  n_parts, part, row_block and block_owner refer to OUTPUT rows, and outputs are (R, W) compact with     *
+ * R = lt_local_rows(H, ...) as everywhere.  A partition's fine rows are the fine frame's partition with row blocks    *
+ * of row_block S rows and the same table.                                                                            *
+ *                                                                                                               *
+ * Bands.  A call renders its rows in bands of aa->band_rows output rows (a multiple of row_block; a partition's rows *
+ * in its local order): prologue, the mode's integrate kernel and the resolve epilogue run band after band on the      *
+ * stream, so the (device, stream) workspace never holds more than one band's ray records.  band_rows = 0: automatic,  *
+ * the largest band whose records (three 4-vectors of the precision per ray of the fine tiles, plus the thin disk's    *
+ * slots) fit LT_AA_BAND_BYTES; a band never has more than 65535 fine rows.  Results do not depend on the banding.      *
+ * A call of several bands uploads the partition's block list once, like a block_owner table (a wait for the stream   *
+ * the first time, none when the same call is repeated), and every band reads its piece of it.  The ray records are   *
+ * reused as for lt_render_dev: a one-band call repeated with equal inputs on a stream reuses its own, and whatever   *
+ * call follows on the stream sees the key of the last band rendered, which is a fine-frame key.                      *
+ *                                                                                                               *
+ * Refusals.  samples outside [1, LT_AA_MAX_SAMPLES], an unknown mode, a disk mode with disk = NULL, band_rows < 0 or   *
+ * not a multiple of row_block: LT_ERR_INVALID_ARG.  The mode's own refusals apply unchanged (LT_METRIC_SCHWARZSCHILD  *
+ * or LT_SCHED_QUEUE with a disk mode: LT_ERR_UNSUPPORTED; the disk's parameters as lt_render_disk_dev); the plain     *
+ * mode accepts what lt_render_dev accepts.  No GPU: LT_ERR_NO_DEVICE.                                                 */
+#define LT_AA_PLAIN 0
+#define LT_AA_DISK 1
+#define LT_AA_DISK_IMAGES 2
+#define LT_AA_MAX_SAMPLES 8
+#define LT_AA_BAND_BYTES ((int64_t)2 << 30) /* 2 GiB: the record budget of an automatic band (a 4096^2 fine frame in
+                                               float32 is 0.75 GiB and stays one band; 8192^2 becomes two) */
+
+typedef struct lt_aa {
+    int32_t samples;    /* S: S x S rays per pixel, 1 ... LT_AA_MAX_SAMPLES (2) */
+    int32_t mode;       /* LT_AA_*                                                */
+    int32_t max_images; /* LT_AA_DISK_IMAGES: slots per ray (3)                   */
+    int32_t band_rows;  /* output rows per band; 0 = automatic                    */
+} lt_aa;
+void lt_default_aa(lt_aa *a);
+
+/* DEVICE pointers (any output may be NULL = not wanted), sized for R = the partition's output rows:
+ *   d_bg    (H S, W S, bg_channels) float32 or NULL;  bg_channels 1 or 3
+ *   d_rgb   (R, W, bg_channels or 3) float32          d_rgba (R, W, 4) uint8
+ *   d_cover (R, W, 4) uint8                           d_stats LT_STAT_WORDS uint64, ACCUMULATED into
+ * disk: NULL for LT_AA_PLAIN.  Asynchronous on opts->stream; opts->timing as lt_render_dev, one record per band. */
+int lt_render_aa_dev(const lt_camera *cam, const lt_metric *metric, const lt_opts *opts, const lt_aa *aa,
+                     const lt_disk *disk, const float *d_bg, int32_t bg_channels, float *d_rgb, uint8_t *d_rgba,
+                     uint8_t *d_cover, uint64_t *d_stats);
+/* The same with HOST pointers, staged like lt_render: the fine-size background goes in, only the resolved outputs
+ * come back.  stats may be NULL. */
+int lt_render_aa(const lt_camera *cam, const lt_metric *metric, const lt_opts *opts, const lt_aa *aa,
+                 const lt_disk *disk, const float *bg, int32_t bg_channels, float *out_rgb, uint8_t *out_rgba,
+                 uint8_t *out_cover, lt_stats *stats);
+/* What a call with these arguments would do, from host arithmetic alone (needs no device): returns the bytes of ray
+ * records its largest band needs in the (device, stream) workspace, or a negative LT_ERR_* with the call's refusals;
+ * *band_rows = output rows per band, *n_bands = bands of this partition (either may be NULL). */
+int64_t lt_aa_band_bytes(const lt_camera *cam, const lt_metric *metric, const lt_opts *opts, const lt_aa *aa,
+                         const lt_disk *disk, int32_t *band_rows, int32_t *n_bands);
+
 /* Sum of HIP-event times (ms) of the prologue / integrate / epilogue kernels over all
  * lt_render_dev calls made with opts->timing != 0 since the last collect; *calls = how many.
  * Synchronises on the recorded events. */

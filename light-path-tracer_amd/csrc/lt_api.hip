@@ -7,11 +7,13 @@
 #include "lt_kernels.hpp"
 #include "lt_disk.hpp"
 #include "lt_disk_images.hpp"
+#include "lt_aa.hpp"
 #ifdef LT_PROBES
 #include "lt_probe.hpp"
 #endif
 #include "lt_dense.hpp"
 
+#include <algorithm>
 #include <array>
 #include <cmath>
 #include <cstdarg>
@@ -135,6 +137,7 @@ struct StreamSlot {
     std::vector<int32_t> blocks_host; // what `blocks` holds (skip the upload when unchanged)
     EventQuad own{}; // lt_render's private timing events (created on first use)
     bool own_ok = false;
+    std::vector<EventQuad> aa_events; // lt_render_aa's: one quad per band, grown to the most bands a call had
 };
 
 struct Ctx {
@@ -217,6 +220,7 @@ static void destroy_slot(StreamSlot *sl)
 {
     for (Grow *g : {&sl->ws, &sl->dev, &sl->dense, &sl->blocks, &sl->disk_img}) release(*g);
     if (sl->own_ok) for (auto &e : sl->own.e) (void)hipEventDestroy(e);
+    for (auto &q : sl->aa_events) for (auto &e : q.e) (void)hipEventDestroy(e);
     delete sl;
 }
 
@@ -792,6 +796,22 @@ static int launch_epilogue_arrays_disk_images(const MetricConsts &mc, const lt_o
                                               double *d_fa, int64_t *d_w, int8_t *d_st, uint32_t *d_ev, double *d_images,
                                               int32_t *d_n_hits, hipStream_t s, const DiskParams &dp, const DiskRecordsBuf &recs);
 
+// A band of a supersampled frame (lt_api_aa.inc): the frame render_dev_impl is given is the band of the FINE frame, and
+// the resolve epilogue of lt_aa.hpp takes the place of the mode's own, writing d_rgb / d_rgba / d_cover as the band's
+// OUTPUT rows.
+struct AaBand {
+    int samples, mode; // S; LT_AA_*
+    int W;             // output width
+    int64_t rows;      // output rows of the band
+    uint8_t *d_cover;  // (rows, W, 4) or NULL
+    // A call of several bands: the partition's row blocks (ascending), of which the band is `count` from `first` on.  The
+    // whole list is uploaded once per call and every band points into it.  NULL: the band is the partition of `opts`.
+    const std::vector<int32_t> *blocks;
+    size_t first, count;
+};
+static int launch_epilogue_aa(const CamConsts &c, const MetricConsts &mc, const lt_opts &o, const Workspace &w, const FrameOut &fo,
+                              uint64_t *d_stats, hipStream_t s, const DiskParams *disk, const DiskRecordsBuf &recs, const AaBand &aa);
+
 // The three stages of a frame, each launched once in terms of the precision's type.
 static int launch_prologue_camera(const CamConsts &c, const MetricConsts &mc, const lt_opts &o, const Workspace &w, int64_t n_q,
                                   hipStream_t s)
@@ -869,10 +889,11 @@ static bool camera_pinhole(const lt_camera *cam, double axis_refine_frac, CamCon
 }
 
 // The camera block of one partition's frame: host arithmetic only.  `owned` / `rows_owned`: the partition's row blocks
-// (partition_blocks); `disk`: a disk frame, which traces every row.  The caller adds block_list.  A partition without
+// (partition_blocks), `listed`: they are given as a list (a block_owner table, a band); `disk`: a disk frame, which
+// traces every row.  The caller adds block_list.  A partition without
 // rows (rows_local <= 0) is no error: its block is left without tiles.
 static int make_camera(const lt_camera *cam, int kind, const lt_opts &o, const MetricConsts &mc, const std::vector<int32_t> &owned,
-                       int64_t rows_owned, bool disk, CamConsts *out)
+                       int64_t rows_owned, bool listed, bool disk, CamConsts *out)
 {
     CamConsts &c = *out;
     const bool front = camera_pinhole(cam, o.axis_refine_frac, &c);
@@ -883,7 +904,7 @@ static int make_camera(const lt_camera *cam, int kind, const lt_opts &o, const M
     // top/bottom symmetry exactly when the reference applies it (image_lens.py:218-220)
     c.use_tb = !disk && o.tb_symmetry && kind == LT_METRIC_KERR &&
                fabs(cam->theta_obs - M_PI / 2) <= 1e-8 + 1e-5 * (M_PI / 2) && fabs(cam->psi_y) <= 1e-8;
-    if (c.use_tb && (o.n_parts != 1 || o.block_owner)) return fail(LT_ERR_UNSUPPORTED, "tb_symmetry needs n_parts == 1 and no block_owner table");
+    if (c.use_tb && (o.n_parts != 1 || listed)) return fail(LT_ERR_UNSUPPORTED, "tb_symmetry needs n_parts == 1 and no block_owner table");
     c.trace_rows = c.use_tb ? (c.H + 1) / 2 : c.rows_local;
     c.tiles_x = (c.W + 7) / 8;
     if (c.rows_local <= 0) return LT_OK;
@@ -915,7 +936,7 @@ static int make_camera(const lt_camera *cam, int kind, const lt_opts &o, const M
     c.hot_x1 = clampi(ceil((bx + rx) / 8.0), 0, c.tiles_x);
     // rows: global pixel rows -> this partition's local rows (block-cyclic: about 1/n_parts of them)
     double ly0 = (by - ry) / o.n_parts - o.row_block, ly1 = (by + ry) / o.n_parts + o.row_block;
-    if (o.block_owner) { // any assignment: local rows of the first / last owned block that touches the band
+    if (listed) { // any assignment: local rows of the first / last owned block that touches the band
         ly0 = 1e18; ly1 = -1.0;
         for (size_t i = 0; i < owned.size(); ++i) {
             double g0 = (double)owned[i] * o.row_block, g1 = g0 + o.row_block;
@@ -981,10 +1002,11 @@ struct KeyGuard {
 };
 
 // disk == NULL: the frame path.  Else the disk frame (lt_render_disk_dev): every row traced, the disk kernels.
+// aa != NULL: a band of a supersampled frame, resolved by k_epilogue_aa instead of the mode's epilogue.
 static int render_dev_impl(const lt_camera *cam, const lt_metric *metric, const lt_opts *opts, const float *d_bg,
                            int32_t bg_channels, float *d_fa, uint16_t *d_w, int8_t *d_status, uint32_t *d_steps,
                            float *d_rgb, uint8_t *d_rgba, uint64_t *d_stats, const EventQuad *own_events,
-                           const DiskParams *disk = nullptr)
+                           const DiskParams *disk = nullptr, const AaBand *aa = nullptr)
 {
     int rc = require_device();
     if (rc) return rc;
@@ -1000,11 +1022,18 @@ static int render_dev_impl(const lt_camera *cam, const lt_metric *metric, const 
     hipStream_t s = (hipStream_t)o.stream;
     std::vector<int32_t> owned;
     int64_t rows_owned = 0;
-    if ((rc = partition_blocks(cam->height, o, &owned, &rows_owned))) return rc;
     const int32_t *block_list = nullptr;
-    if (o.block_owner && !owned.empty() && (rc = upload_block_list(s, owned, &block_list))) return rc;
+    if (aa && aa->blocks) { // (the list is the same for every band of the call: uploaded by the first, found unchanged by the others)
+        if ((rc = upload_block_list(s, *aa->blocks, &block_list))) return rc;
+        block_list += aa->first;
+        owned.assign(aa->blocks->begin() + (long)aa->first, aa->blocks->begin() + (long)(aa->first + aa->count));
+        rows_owned = aa->rows * aa->samples;
+    } else {
+        if ((rc = partition_blocks(cam->height, o, &owned, &rows_owned))) return rc;
+        if (o.block_owner && !owned.empty() && (rc = upload_block_list(s, owned, &block_list))) return rc;
+    }
     CamConsts c;
-    if ((rc = make_camera(cam, metric->kind, o, mc, owned, rows_owned, disk != nullptr, &c))) return rc;
+    if ((rc = make_camera(cam, metric->kind, o, mc, owned, rows_owned, block_list != nullptr, disk != nullptr, &c))) return rc;
     c.block_list = block_list;
     if (c.rows_local <= 0) return LT_OK; // a partition may own no rows
     int64_t n_q = (int64_t)c.tiles_x * c.tiles_y * 64;
@@ -1039,7 +1068,8 @@ static int render_dev_impl(const lt_camera *cam, const lt_metric *metric, const 
     if ((rc = tm.mark(1, s))) return rc;
     if ((rc = launch_integrate_any(mc, o, lambda_max, w, n_q, s, d_stats, disk, recs))) return rc;
     if ((rc = tm.mark(2, s))) return rc;
-    if (!disk) rc = launch_epilogue_frame(c, mc, o, w, fo, d_stats, s);
+    if (aa) rc = launch_epilogue_aa(c, mc, o, w, fo, d_stats, s, disk, recs, *aa);
+    else if (!disk) rc = launch_epilogue_frame(c, mc, o, w, fo, d_stats, s);
     else if (disk->max_images) rc = launch_epilogue_disk_images(c, mc, o, w, fo, d_stats, s, *disk, recs);
     else rc = launch_epilogue_disk(c, mc, o, w, fo, d_stats, s, *disk);
     if (rc) return rc;
@@ -1488,3 +1518,4 @@ extern "C" int lt_scatter_rows_indexed_dev(const void *d_rows, void *d_full, con
 #include "lt_api_dense.inc"
 #include "lt_api_disk.inc"
 #include "lt_api_disk_images.inc"
+#include "lt_api_aa.inc"

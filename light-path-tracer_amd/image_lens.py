@@ -210,7 +210,7 @@ def render_lensed_image(source_image, alpha_lookup, final_alpha_lookup, winding_
 
 def render_frame(source_image, metric, r_obs, fov, psi=(0.0, 0.0), theta_obs=np.pi / 2, integrator=None,
                  precision=None, schedule=None, tb_symmetry=False, render_loop_around=False,
-                 want=("fa", "winding", "rgb"), gpus=1, devices=None, disk=None):
+                 want=("fa", "winding", "rgb"), gpus=1, devices=None, disk=None, samples=None):
     """Fused path (lt_render): all three stages in one GPU call.  source_image None -> shadow render
     (escaped = white).  Returns dict with 'fa', 'winding', 'rgb', ... and 'stats'.
     gpus > 1: the frame's rows are split block-cyclically over that many devices of this node
@@ -218,7 +218,11 @@ def render_frame(source_image, metric, r_obs, fov, psi=(0.0, 0.0), theta_obs=np.
     disk: a thin accretion disk (disk.ThinDisk or ltrace.Disk) -> lt_render_disk on one GPU, every row traced, plus
     'disk' (H, W, 3) (r_hit, phi_hit, g); a spherically symmetric metric is traced as Kerr with a = 0.
     An optically thin disk (disk.TransparentDisk: anything with a max_images) -> lt_render_disk_images instead, plus
-    'disk_images' (H, W, max_images, 3) (r_hit, phi_hit, g) of the first hits along the ray and 'disk_hits' (H, W)."""
+    'disk_images' (H, W, max_images, 3) (r_hit, phi_hit, g) of the first hits along the ray and 'disk_hits' (H, W).
+    samples: S -> lt_render_aa: S x S rays per pixel resolved on the GPU (anti-aliasing).  source_image is then the
+    FINE-size background (H S, W S[, 3]) and the frame is (H, W); the result holds 'rgb', 'rgba', 'cover' (H, W, 4)
+    (sub-rays escaped / captured / invalid / on the disk) and 'stats' only, with no disk, a ThinDisk or a
+    TransparentDisk; one GPU, every row traced."""
     if source_image is None:
         raise ValueError("render_frame needs a background; for a shadow use black_hole_shadow.render_traced")
     source_image = np.asarray(source_image)
@@ -237,6 +241,19 @@ def render_frame(source_image, metric, r_obs, fov, psi=(0.0, 0.0), theta_obs=np.
         schedule=schedule or getattr(metric, "schedule", "direct"),
         tb_symmetry=int(bool(tb_symmetry)), loop_around=int(bool(render_loop_around)),
         axis_refine_frac=Y_AXIS_REFINE_FRAC)
+    if samples is not None:
+        S = int(samples)
+        if gpus and gpus > 1:
+            raise ValueError("a supersampled frame renders on one GPU (gpus == 1)")
+        if S < 1 or shape[0] % S or shape[1] % S:
+            raise ValueError(f"samples={S}: the background must be the fine frame, (H * samples, W * samples); got {shape}")
+        cam = _camera((shape[0] // S, shape[1] // S), fov, psi, r_obs, theta_obs)
+        d = None if disk is None else (disk.to_lt() if hasattr(disk, "to_lt") else disk)
+        max_images = getattr(disk, "max_images", None)
+        mode = "plain" if disk is None else ("disk" if max_images is None else "disk_images")
+        aa = ltrace.default_aa(samples=S, mode=mode, **({} if max_images is None else dict(max_images=int(max_images))))
+        return ltrace.render_aa(cam, met, opts, aa, disk=d, background=source_image,
+                                want=tuple(w for w in tuple(want) + ("cover",) if w in ("rgb", "rgba", "cover")))
     cam = _camera(shape, fov, psi, r_obs, theta_obs)
     if disk is not None:
         if gpus and gpus > 1:
@@ -340,14 +357,16 @@ def save_lookup_cache(path, key, final_alpha, winding):
 def main(metric=None, M=1.0, a=0.0, r_obs_mult=100.0, psi=(0.0, 0.0), vertical_fov_deg=40.0,
          image_path="image.jpg", output_path="lensed_image.png", synthetic=None, staged=False,
          integrator=None, precision=None, schedule=None, gpus=1, full_trace=False, dedup_alpha=False,
-         lookup_cache=None, theta_obs_deg=90.0, disk=None):
+         lookup_cache=None, theta_obs_deg=90.0, disk=None, samples=None):
     """`lookup_cache`: path of an .npz (the reference's .gitignore names `lookup_cache.npz`, it never wrote one): the
     final_alpha / winding lookups of this metric, observer and camera are stored there and reused by the next call with
     the same settings -- a new background then costs one colouring pass (lt_shade) instead of a trace.
     `dedup_alpha`: staged path, spherically symmetric metrics: trace distinct alphas only (precompute_final_alpha_lookup).
     `theta_obs_deg`: the observer's inclination (fused path; 90 = equatorial, as the reference).  `disk`: a thin
     accretion disk (disk.ThinDisk, or disk.TransparentDisk for the optically thin one with its higher-order images) in
-    the picture (fused path, one GPU, every row traced)."""
+    the picture (fused path, one GPU, every row traced).  `samples`: S x S rays per pixel, resolved on the GPU (fused
+    path, one GPU, every row traced): a synthetic background is generated at the fine size (W S x H S), one read from a
+    file is repeated S times along both axes, so the picture has the size asked for / the file's size."""
     import matplotlib.image as mpimg
 
     if metric is None:
@@ -358,8 +377,11 @@ def main(metric=None, M=1.0, a=0.0, r_obs_mult=100.0, psi=(0.0, 0.0), vertical_f
     t_total = perf_counter()
 
     t0 = perf_counter()
+    S = 1 if samples is None else int(samples)
+    if S < 1:
+        raise ValueError("--samples must be at least 1")
     if synthetic:
-        img = synthetic_background(int(synthetic[1]), int(synthetic[0]))
+        img = synthetic_background(int(synthetic[1]) * S, int(synthetic[0]) * S)
     else:
         img = mpimg.imread(image_path)
         if img.dtype == np.uint8:
@@ -367,8 +389,10 @@ def main(metric=None, M=1.0, a=0.0, r_obs_mult=100.0, psi=(0.0, 0.0), vertical_f
         if img.ndim == 3 and img.shape[2] == 4:
             print("Background has an alpha channel: lensing its RGB planes (see render_frame)")
             img = np.ascontiguousarray(img[..., :3])
+        if samples is not None:
+            img = np.repeat(np.repeat(img, S, axis=0), S, axis=1)
     timings["load_image"] = perf_counter() - t0
-    height, width = img.shape[:2]
+    height, width = img.shape[0] // S, img.shape[1] // S
     print(f"Image: {width}x{height}")
 
     r_obs = r_obs_mult * metric.M
@@ -382,10 +406,10 @@ def main(metric=None, M=1.0, a=0.0, r_obs_mult=100.0, psi=(0.0, 0.0), vertical_f
     print(f"BH screen offset: psi_y={np.degrees(psi[0]):.4f} deg, psi_x={np.degrees(psi[1]):.4f} deg ({where})")
 
     theta_obs = np.radians(theta_obs_deg)
-    if (disk is not None or theta_obs_deg != 90.0) and (staged or lookup_cache):
-        raise ValueError("--disk / --theta-obs need the fused path (no --staged, no --lookup-cache)")
+    if (disk is not None or theta_obs_deg != 90.0 or samples is not None) and (staged or lookup_cache):
+        raise ValueError("--disk / --theta-obs / --samples need the fused path (no --staged, no --lookup-cache)")
     rgba8 = None
-    mirror = (disk is None) and (not full_trace) and gpus <= 1 and not metric.is_spherically_symmetric and abs(psi[0]) <= 1e-8
+    mirror = (disk is None) and samples is None and (not full_trace) and gpus <= 1 and not metric.is_spherically_symmetric and abs(psi[0]) <= 1e-8
     # (the staged path mirrors whenever the reference does, the fused one unless --full-trace / several GPUs)
     mirrored = (not metric.is_spherically_symmetric and abs(psi[0]) <= 1e-8) if staged else mirror
     cache_key = _lookup_cache_key(metric, r_obs, (height, width), fov, psi, mirrored) if lookup_cache else None
@@ -427,6 +451,9 @@ def main(metric=None, M=1.0, a=0.0, r_obs_mult=100.0, psi=(0.0, 0.0), vertical_f
             print(f"Accretion disk: r_in = {disk.inner_edge(metric.M, getattr(metric, 'a', 0.0)):.4f} M, "
                   f"r_out = {disk.r_out} M, q = {disk.q}, exposure = {disk.exposure}, theta_obs = {theta_obs_deg} deg"
                   + (f", optically thin: up to {disk.max_images} images per ray" if hasattr(disk, "max_images") else ""))
+        if samples is not None:
+            extra["samples"] = S
+            print(f"Supersampling: {S} x {S} rays per pixel, resolved on the GPU")
         out = render_frame(img, metric, r_obs, fov, psi=psi, tb_symmetry=mirror,
                            want=("rgb", "rgba") + (("fa", "winding") if lookup_cache else ()), gpus=gpus, **extra)
         timings["render"] = perf_counter() - t0
@@ -447,7 +474,8 @@ def main(metric=None, M=1.0, a=0.0, r_obs_mult=100.0, psi=(0.0, 0.0), vertical_f
     return lensed
 
 
-if __name__ == "__main__":
+def build_parser():
+    """The command line of `python image_lens.py`."""
     import argparse
     ap = argparse.ArgumentParser()
     ap.add_argument("--M", type=float, default=1.0, help="BH mass")
@@ -479,7 +507,14 @@ if __name__ == "__main__":
     ap.add_argument("--disk-images", type=int, default=None, metavar="N",
                     help="optically thin disk: add the light of the first N (1 ... 8) images of the disk along each ray, "
                          "the photon ring included (implies --disk)")
-    args = ap.parse_args()
+    ap.add_argument("--samples", type=int, default=None, metavar="S",
+                    help="anti-aliasing: trace S x S rays per pixel (1 ... 8) and resolve them on the GPU; with --synthetic "
+                         "the background is generated at the fine size, a background file is repeated S times per axis")
+    return ap
+
+
+if __name__ == "__main__":
+    args = build_parser().parse_args()
     disk = None
     if args.disk_images is not None:
         from disk import TransparentDisk
@@ -492,4 +527,4 @@ if __name__ == "__main__":
          vertical_fov_deg=args.fov_v, image_path=args.image, output_path=args.output, synthetic=args.synthetic,
          staged=args.staged, integrator=args.integrator, precision=args.precision, schedule=args.schedule,
          gpus=args.gpus, full_trace=args.full_trace, dedup_alpha=args.dedup_alpha, lookup_cache=args.lookup_cache,
-         theta_obs_deg=args.theta_obs, disk=disk)
+         theta_obs_deg=args.theta_obs, disk=disk, samples=args.samples)

@@ -72,6 +72,15 @@ class Disk(C.Structure):
                 ("flags", C.c_int32), ("reserved", C.c_int32)]
 
 
+class AA(C.Structure):
+    """lt_aa: supersampling (samples x samples rays per pixel; band_rows 0 = automatic)."""
+    _fields_ = [("samples", C.c_int32), ("mode", C.c_int32), ("max_images", C.c_int32), ("band_rows", C.c_int32)]
+
+
+AA_PLAIN, AA_DISK, AA_DISK_IMAGES = 0, 1, 2
+AA_MAX_SAMPLES = 8
+AA_BAND_BYTES = 2 << 30
+
 TRACK_RANGE_END, TRACK_CAPTURE_EVENT, TRACK_ESCAPE_EVENT, TRACK_FAILED, TRACK_ATTEMPT_LIMIT = 0, 1, 2, -1, -2
 
 
@@ -147,6 +156,13 @@ SIGNATURES = {
                                                   C.c_double, C.c_double, C.c_void_p, C.c_int, C.c_int, C.POINTER(Disk),
                                                   C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                   C.c_void_p, C.c_void_p]),
+    "lt_default_aa": (None, [C.POINTER(AA)]),
+    "lt_render_aa_dev": (C.c_int, [C.POINTER(Camera), C.POINTER(Metric), C.POINTER(Opts), C.POINTER(AA), C.POINTER(Disk),
+                                   C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lt_render_aa": (C.c_int, [C.POINTER(Camera), C.POINTER(Metric), C.POINTER(Opts), C.POINTER(AA), C.POINTER(Disk),
+                               C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
+    "lt_aa_band_bytes": (C.c_int64, [C.POINTER(Camera), C.POINTER(Metric), C.POINTER(Opts), C.POINTER(AA), C.POINTER(Disk),
+                                     C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
 }
 
 
@@ -700,3 +716,70 @@ def trace_batch_kerr_disk_images(M, a, r_obs, alphas, thetas, theta_obs, lambda_
                                                   _np_ptr(out["images"]), _np_ptr(out["n_hits"]),
                                                   _np_ptr(out["rhs_evals"])))
     return out
+
+
+# ---- supersampled frames (lt_render_aa) ---------------------------------------------------------------------------
+AA_MODES = {"plain": AA_PLAIN, "disk": AA_DISK, "disk_images": AA_DISK_IMAGES}
+
+
+def default_aa(**kw):
+    """lt_aa with the library's defaults (samples = 2, plain mode, 3 images, automatic bands); keywords override."""
+    a = AA()
+    load().lt_default_aa(C.byref(a))
+    for k, v in kw.items():
+        if k == "mode" and isinstance(v, str):
+            v = AA_MODES[v]
+        setattr(a, k, v)
+    return a
+
+
+def _fine_background(cam, samples, background):
+    if background is None:
+        return None, 3, False
+    bg = np.ascontiguousarray(background, dtype=np.float32)
+    # (a sample count the library refuses is left for it to refuse)
+    if 1 <= samples <= AA_MAX_SAMPLES and bg.shape[:2] != (cam.height * samples, cam.width * samples):
+        raise ValueError("background must have the fine frame's size: (height * samples, width * samples)")
+    nch = 1 if bg.ndim == 2 else bg.shape[2]
+    if nch not in (1, 3):
+        raise ValueError("background must be grayscale or RGB")
+    return bg, nch, bg.ndim == 2
+
+
+def render_aa(cam, metric, opts, aa, disk=None, background=None, want=("rgb", "rgba", "cover")):
+    """Host-pointer supersampled frame (lt_render_aa): aa.samples^2 rays per pixel, resolved on the GPU.  background:
+    the FINE-size image (H * samples, W * samples[, 3]) or None.  disk: an ltrace.Disk for the disk modes.  Returns
+    'rgb' (rows, W[, 3]) float32, 'rgba' (rows, W, 4) uint8, 'cover' (rows, W, 4) uint8 (sub-rays escaped / captured /
+    invalid / on the disk) in pinned memory, and 'stats' (the fine frame's counters; kernel times summed over bands)."""
+    rows = _frame_rows(cam, opts)
+    bg, nch, gray = _fine_background(cam, int(aa.samples), background)
+    out = _frame_outputs(rows, cam.width, nch, gray, [w for w in want if w in ("rgb", "rgba")])
+    if "cover" in want:
+        out["cover"] = pinned_empty((rows, cam.width, 4), np.uint8)
+    st = Stats()
+    _check(load().lt_render_aa(C.byref(cam), C.byref(metric), C.byref(opts), C.byref(aa),
+                               None if disk is None else C.byref(disk), _np_ptr(bg), nch, _np_ptr(out.get("rgb")),
+                               _np_ptr(out.get("rgba")), _np_ptr(out.get("cover")), C.byref(st)))
+    out["stats"] = stats_dict(st.counters, st.prologue_ms, st.integrate_ms, st.epilogue_ms)
+    out["stats"]["disk"] = int(st.counters[STAT_DISK])
+    out["stats"]["disk_hits"] = int(st.counters[STAT_DISK_HITS])
+    return out
+
+
+def render_aa_dev(cam, metric, opts, aa, disk=None, d_bg=0, bg_channels=3, d_rgb=0, d_rgba=0, d_cover=0, d_stats=0):
+    """Device-pointer form of render_aa (lt_render_aa_dev); pointers are integers, 0 = NULL.  Asynchronous."""
+    p = lambda x: C.c_void_p(x) if x else None
+    _check(load().lt_render_aa_dev(C.byref(cam), C.byref(metric), C.byref(opts), C.byref(aa),
+                                   None if disk is None else C.byref(disk), p(d_bg), bg_channels, p(d_rgb), p(d_rgba),
+                                   p(d_cover), p(d_stats)))
+
+
+def aa_band_bytes(cam, metric, opts, aa, disk=None):
+    """(bytes of ray records the largest band needs, output rows per band, bands) of a render_aa call (lt_aa_band_bytes;
+    host arithmetic, no GPU needed)."""
+    rows, bands = C.c_int32(), C.c_int32()
+    n = int(load().lt_aa_band_bytes(C.byref(cam), C.byref(metric), C.byref(opts), C.byref(aa),
+                                    None if disk is None else C.byref(disk), C.byref(rows), C.byref(bands)))
+    if n < 0:
+        _check(n)
+    return n, int(rows.value), int(bands.value)
