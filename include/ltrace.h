@@ -119,6 +119,7 @@ typedef struct lt_opts {
 #define LT_STAT_DISK 12            /* lt_render_disk_dev: rays that ended on the accretion disk                        */
                                    /* (lt_render_disk_images_dev: rays with at least one hit)                          */
 #define LT_STAT_DISK_HITS 13       /* lt_render_disk_images_dev: hits of the optically thin disk, all rays              */
+#define LT_STAT_AA_REFINED 14      /* lt_render_aa_adaptive_dev: pixels that were refined (traced at samples_hi)         */
 #define LT_STAT_WORDS 16
 
 typedef struct lt_stats {
@@ -494,6 +495,81 @@ int lt_render_aa(const lt_camera *cam, const lt_metric *metric, const lt_opts *o
  * *band_rows = output rows per band, *n_bands = bands of this partition (either may be NULL). */
 int64_t lt_aa_band_bytes(const lt_camera *cam, const lt_metric *metric, const lt_opts *opts, const lt_aa *aa,
                          const lt_disk *disk, int32_t *band_rows, int32_t *n_bands);
+
+/* ---- adaptive supersampling: refine only the pixels on an edge ---------------------------------------- *
+ * lt_render_aa traces S x S rays for EVERY pixel; almost everywhere they agree.  These entry points render the frame *
+ * at samples_lo, find the pixels that lie on an edge from that pass's own outputs, and trace only those at samples_hi. *
+ * No ray is new: every pixel of the result is a pixel of one of two lt_render_aa frames.                             *
+ *                                                                                                               *
+ * Write LO for what lt_render_aa returns with samples = S_lo and a background of (H S_lo, W S_lo), HI for            *
+ * samples = S_hi and a background of (H S_hi, W S_hi); camera, metric, opts, mode and disk are the call's.           *
+ *                                                                                                               *
+ * Refined pixels.  A pixel p is refined when any of these holds, N(p) being its 3 x 3 neighbourhood clipped to the   *
+ * frame, p itself excluded:                                                                                     *
+ *   mixed     LO.cover[p] has more than one non-zero slot.  LT_AA_PLAIN and LT_AA_DISK look at slots 0-3;             *
+ *             LT_AA_DISK_IMAGES, whose slot 3 overlaps the others, looks at slots 0-2, or flags                      *
+ *             0 < LO.cover[p][3] < S_lo^2;                                                                      *
+ *   edge      some n in N(p) has LO.cover[n] != LO.cover[p], compared as 4 bytes;                                    *
+ *   contrast  contrast >= 0, and some n in N(p) and some channel has fabsf(LO.rgb[p][ch] - LO.rgb[n][ch]) > contrast *
+ *             in float32 (a difference equal to contrast does not count).  This finds what cover cannot see: the    *
+ *             photon ring, where a 1-hit pixel lies next to a 2-hit pixel, winding-colour seams, a background that   *
+ *             aliases.  contrast < 0 switches the test off.                                                      *
+ *                                                                                                               *
+ * Outputs.  rgb, rgba and cover are HI's at refined pixels and LO's elsewhere, bit for bit.  level (H, W) uint8 is    *
+ * S_hi where the pixel was refined and S_lo elsewhere: a pixel's cover slots sum to level^2 (LT_AA_DISK_IMAGES: its   *
+ * first three slots do).  With S_lo = 1 every unrefined pixel is exactly the mode's own one-ray pixel.  Nothing       *
+ * depends on the order in which refined pixels are found, on band_rows or on chunk_pixels.                           *
+ *                                                                                                               *
+ * Stats.  Words 0-5, LT_STAT_DISK and LT_STAT_DISK_HITS are the base pass's plus the refined rays', so               *
+ * rays = S_lo^2 W H + S_hi^2 N; LT_STAT_AA_REFINED is N, the number of refined pixels.  Kernel times are summed over   *
+ * the base pass's bands and the refined pass's chunks; the kernel that applies the three tests counts as prologue.   *
+ *                                                                                                               *
+ * Passes.  The base pass is lt_render_aa_dev's, in bands of band_rows.  The refined pixels are then traced in chunks *
+ * of chunk_pixels pixels (0: automatic, the most pixels whose S_hi^2 ray records each fit LT_AA_BAND_BYTES), each a    *
+ * prologue, the mode's integrate kernel and a resolve epilogue that overwrites the listed pixels.  The refined pass  *
+ * overwrites the ray records of the (device, stream) workspace: the frame that follows on the stream reuses nothing. *
+ *                                                                                                               *
+ * Partitions.  The 3 x 3 test reads rows a partition does not own: n_parts != 1 and a block_owner table are refused   *
+ * with LT_ERR_UNSUPPORTED.                                                                                      *
+ *                                                                                                               *
+ * Other refusals.  samples_lo outside [1, 4], samples_hi outside (samples_lo, LT_AA_MAX_SAMPLES], a NaN contrast, a    *
+ * negative chunk_pixels, one background without the other, a frame of more than 2^31 - 1 pixels: LT_ERR_INVALID_ARG. *
+ * Everything else is refused as lt_render_aa refuses it: the mode's own refusals, band_rows, a disk mode without a    *
+ * disk.  No GPU: LT_ERR_NO_DEVICE.                                                                               */
+typedef struct lt_aa_adaptive {
+    int32_t samples_lo;   /* base pass: S_lo x S_lo rays for every pixel, 1 ... 4   (1) */
+    int32_t samples_hi;   /* refined pixels: S_hi x S_hi rays, S_lo < S_hi <= LT_AA_MAX_SAMPLES (4) */
+    int32_t mode;         /* LT_AA_*                                                   */
+    int32_t max_images;   /* LT_AA_DISK_IMAGES (3)                                      */
+    int32_t band_rows;    /* base pass, as lt_aa.band_rows; 0 = automatic              */
+    int32_t chunk_pixels; /* refined pass: pixels per chunk; 0 = automatic (records within LT_AA_BAND_BYTES) */
+    float   contrast;     /* colour test threshold; < 0: off (default 0.0625f)         */
+    int32_t reserved;
+} lt_aa_adaptive;
+void lt_default_aa_adaptive(lt_aa_adaptive *a);
+
+/* DEVICE pointers (any output may be NULL = not wanted; what the refinement tests read of the base pass -- cover,
+ * and rgb when contrast >= 0 -- then lives in the library's own buffers of the stream):
+ *   d_bg_lo (H S_lo, W S_lo, bg_channels), d_bg_hi (H S_hi, W S_hi, bg_channels) float32: both NULL or both given
+ *   d_rgb (H, W, bg_channels or 3) float32   d_rgba (H, W, 4) uint8   d_cover (H, W, 4) uint8   d_level (H, W) uint8
+ *   d_stats LT_STAT_WORDS uint64, ACCUMULATED into
+ * Enqueued on opts->stream, but NOT asynchronous: the call waits for its stream ONCE, between the passes, to read the
+ * number of refined pixels -- the refined pass's launch sizes need it (so it cannot be captured into a graph); what it
+ * enqueues after that is not waited for.  opts->timing as lt_render_dev: one record per band, one for the flag kernel, one
+ * per chunk. */
+int lt_render_aa_adaptive_dev(const lt_camera *cam, const lt_metric *metric, const lt_opts *opts, const lt_aa_adaptive *adaptive,
+                              const lt_disk *disk, const float *d_bg_lo, const float *d_bg_hi, int32_t bg_channels,
+                              float *d_rgb, uint8_t *d_rgba, uint8_t *d_cover, uint8_t *d_level, uint64_t *d_stats);
+/* The same with HOST pointers, staged like lt_render_aa: the two backgrounds go in, only the resolved outputs come
+ * back.  stats may be NULL. */
+int lt_render_aa_adaptive(const lt_camera *cam, const lt_metric *metric, const lt_opts *opts, const lt_aa_adaptive *adaptive,
+                          const lt_disk *disk, const float *bg_lo, const float *bg_hi, int32_t bg_channels, float *out_rgb,
+                          uint8_t *out_rgba, uint8_t *out_cover, uint8_t *out_level, lt_stats *stats);
+/* What a call with these arguments would do, from host arithmetic alone (needs no device): 0, or the call's refusal.
+ * *base_band_bytes = bytes of ray records the base pass's largest band needs, *chunk_pixels = refined pixels per chunk
+ * (either may be NULL). */
+int lt_aa_adaptive_plan(const lt_camera *cam, const lt_metric *metric, const lt_opts *opts, const lt_aa_adaptive *adaptive,
+                        const lt_disk *disk, int64_t *base_band_bytes, int64_t *chunk_pixels);
 
 /* Sum of HIP-event times (ms) of the prologue / integrate / epilogue kernels over all
  * lt_render_dev calls made with opts->timing != 0 since the last collect; *calls = how many.

@@ -60,3 +60,50 @@ def cover(fine_status, fine_n_hits, samples, mode):
                 n += what[j::S, i::S]
         out[..., slot] = n
     return out
+
+
+# ---- adaptive supersampling (include/ltrace.h, "adaptive supersampling") -------------------------------------------
+def refine_mask(cover, rgb, samples_lo, mode, contrast):
+    """(H, W) bool: the pixels lt_render_aa_adaptive refines, from the base pass's cover (H, W, 4) uint8 and rgb
+    (H, W[, C]) float32 (rgb may be None when contrast < 0).  A pixel p is refined when, N(p) being its 3 x 3
+    neighbourhood clipped to the frame without p itself,
+      mixed     cover[p] has more than one non-zero slot (PLAIN, DISK: slots 0-3; DISK_IMAGES: slots 0-2, or
+                0 < cover[p][3] < samples_lo^2);
+      edge      some n in N(p) has cover[n] != cover[p] (all four bytes);
+      contrast  contrast >= 0 and some n in N(p) and some channel has |rgb[p] - rgb[n]| > contrast in float32."""
+    cv = np.asarray(cover)
+    if cv.dtype != np.uint8 or cv.ndim != 3 or cv.shape[2] != 4:
+        raise ValueError("cover is (H, W, 4) uint8")
+    H, W = cv.shape[:2]
+    S2 = int(samples_lo) ** 2
+    if mode == DISK_IMAGES:
+        mask = ((cv[..., :3] != 0).sum(axis=2) > 1) | ((cv[..., 3] > 0) & (cv[..., 3] < S2))
+    else:
+        mask = (cv != 0).sum(axis=2) > 1
+    contrast = np.float32(contrast)
+    colour = None
+    if contrast >= 0:
+        colour = np.asarray(rgb)
+        if colour.dtype != np.float32 or colour.shape[:2] != (H, W):
+            raise ValueError("rgb is (H, W[, C]) float32 of the cover's frame")
+        colour = colour.reshape(H, W, -1)
+    for dy in (-1, 0, 1):
+        for dx in (-1, 0, 1):
+            if dy == 0 and dx == 0:
+                continue
+            # p runs over the pixels whose neighbour (y + dy, x + dx) lies inside the frame
+            ys, xs = slice(max(0, -dy), H - max(0, dy)), slice(max(0, -dx), W - max(0, dx))
+            yn, xn = slice(max(0, dy), H - max(0, -dy)), slice(max(0, dx), W - max(0, -dx))
+            hit = np.any(cv[ys, xs] != cv[yn, xn], axis=2)
+            if colour is not None:
+                hit |= np.any(np.abs(colour[ys, xs] - colour[yn, xn]) > contrast, axis=2)
+            mask[ys, xs] |= hit
+    return mask
+
+
+def compose(mask, lo, hi):
+    """The adaptive frame's array: hi where mask (H, W) is set, lo elsewhere (arrays of (H, W[, C]), same dtype)."""
+    lo, hi, mask = np.asarray(lo), np.asarray(hi), np.asarray(mask, dtype=bool)
+    if lo.shape != hi.shape or lo.dtype != hi.dtype or lo.shape[:2] != mask.shape:
+        raise ValueError("lo and hi are two frames of the mask's size")
+    return np.where(mask.reshape(mask.shape + (1,) * (lo.ndim - 2)), hi, lo)

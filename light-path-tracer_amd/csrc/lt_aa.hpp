@@ -27,8 +27,9 @@ struct AaOut {
     uint8_t *cover; // (rows, W, 4): the pixel's sub-rays that escaped, were captured, were invalid, hit the disk; or NULL
 };
 
-// One sub-sample: the colour the mode's epilogue writes for fine pixel (ix, lrow) of the band, the ray for the counters
-// (acc), whether it counts as on the disk (the ray ended there / has a hit) and its hits.
+// One sub-sample: the colour the mode's epilogue writes for fine pixel (ix, lrow) of the band, whose ray record is q
+// (pixel_to_q of the band for k_epilogue_aa, the list position for k_epilogue_aa_list of lt_aa_adaptive.hpp), the ray for
+// the counters (acc), whether it counts as on the disk (the ray ended there / has a hit) and its hits.
 //   AA_PLAIN        k_epilogue_frame (tb_symmetry = 0)
 //   AA_DISK         k_epilogue_disk
 //   AA_DISK_IMAGES  k_epilogue_disk_images
@@ -37,10 +38,9 @@ template <typename T, int MODE, bool HAS_BG>
 __device__ __forceinline__ void aa_sample(const CamConsts &c, const MetricConsts &m, const DiskShade &ds,
                                           const typename Vec4<T>::type *__restrict__ fin0,
                                           const typename Vec4<T>::type *__restrict__ fin1, const FrameOut &o,
-                                          const DiskImagesOut &di, int ix, int lrow, bool colour, float *rgb, int &nch,
-                                          StatAcc &acc, bool &on_disk, uint32_t &nh)
+                                          const DiskImagesOut &di, int64_t q, int ix, int lrow, bool colour, float *rgb,
+                                          int &nch, StatAcc &acc, bool &on_disk, uint32_t &nh)
 {
-    const int64_t q = pixel_to_q(c, ix, lrow);
     RayResult res;
     nch = (HAS_BG && o.bg) ? o.bg_c : 3;
     if constexpr (MODE == AA_DISK) {
@@ -91,6 +91,7 @@ __device__ __forceinline__ void aa_sample(const CamConsts &c, const MetricConsts
     acc.add(res);
 }
 
+// (k_epilogue_aa_list of lt_aa_adaptive.hpp restates this kernel's two phases over list entries: change both together.)
 // c: the camera block of the band of the FINE frame (c.W = aa.W S columns, c.rows_local = gridDim.y S rows); o: its
 // background (fine size) and the partial counter sets, with rgb / rgba the band's OUTPUT rows; grid = (segments of
 // P = AA_BLOCK / S^2 output pixels, output rows of the band).
@@ -113,7 +114,8 @@ __global__ void __launch_bounds__(AA_BLOCK) k_epilogue_aa(CamConsts c, MetricCon
     if (pl < P && x < aa.W) {
         const int j = k / S, i = k - j * S;
         float rgb[3] = {0.0f, 0.0f, 0.0f};
-        aa_sample<T, MODE, HAS_BG>(c, m, ds, fin0, fin1, o, di, x * S + i, y * S + j, colour, rgb, nch, acc, on_disk, nh);
+        aa_sample<T, MODE, HAS_BG>(c, m, ds, fin0, fin1, o, di, pixel_to_q(c, x * S + i, y * S + j), x * S + i, y * S + j, colour, rgb, nch,
+                                   acc, on_disk, nh);
         sh_rgb[t][0] = rgb[0]; sh_rgb[t][1] = rgb[1]; sh_rgb[t][2] = rgb[2];
         sh_class[t] = (uint8_t)((acc.esc ? 0 : acc.cap ? 1 : acc.inv ? 2 : 3) | (on_disk ? 4 : 0));
     }

@@ -8,6 +8,7 @@
 #include "lt_disk.hpp"
 #include "lt_disk_images.hpp"
 #include "lt_aa.hpp"
+#include "lt_aa_adaptive.hpp"
 #ifdef LT_PROBES
 #include "lt_probe.hpp"
 #endif
@@ -138,6 +139,8 @@ struct StreamSlot {
     EventQuad own{}; // lt_render's private timing events (created on first use)
     bool own_ok = false;
     std::vector<EventQuad> aa_events; // lt_render_aa's: one quad per band, grown to the most bands a call had
+    Grow aa_list;    // lt_render_aa_adaptive: the count (first 256 bytes) and the list of refined pixels
+    Grow aa_scratch; // ... and the base pass's cover / rgb when the caller did not ask for them
 };
 
 struct Ctx {
@@ -218,7 +221,7 @@ static void release(Grow &g)
 // Everything a slot owns, and the slot.  The caller has drained the slot's stream and taken the slot off its list.
 static void destroy_slot(StreamSlot *sl)
 {
-    for (Grow *g : {&sl->ws, &sl->dev, &sl->dense, &sl->blocks, &sl->disk_img}) release(*g);
+    for (Grow *g : {&sl->ws, &sl->dev, &sl->dense, &sl->blocks, &sl->disk_img, &sl->aa_list, &sl->aa_scratch}) release(*g);
     if (sl->own_ok) for (auto &e : sl->own.e) (void)hipEventDestroy(e);
     for (auto &q : sl->aa_events) for (auto &e : q.e) (void)hipEventDestroy(e);
     delete sl;
@@ -1519,3 +1522,4 @@ extern "C" int lt_scatter_rows_indexed_dev(const void *d_rows, void *d_full, con
 #include "lt_api_disk.inc"
 #include "lt_api_disk_images.inc"
 #include "lt_api_aa.inc"
+#include "lt_api_aa_adaptive.inc"

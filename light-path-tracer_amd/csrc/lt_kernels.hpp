@@ -245,6 +245,7 @@ __device__ __forceinline__ void store_ic(typename Vec4<T>::type *ic, int64_t q, 
 }
 
 // ---- K1: camera prologue -------------------------------------------------------------------
+// (k_prologue_aa_list of lt_aa_adaptive.hpp restates this kernel's body for a list of pixels: change both together.)
 template <typename T>
 __global__ void __launch_bounds__(256) k_prologue_camera(CamConsts c, MetricConsts m,
                                                          typename Vec4<T>::type *__restrict__ ic, int64_t n_q)

@@ -210,7 +210,7 @@ def render_lensed_image(source_image, alpha_lookup, final_alpha_lookup, winding_
 
 def render_frame(source_image, metric, r_obs, fov, psi=(0.0, 0.0), theta_obs=np.pi / 2, integrator=None,
                  precision=None, schedule=None, tb_symmetry=False, render_loop_around=False,
-                 want=("fa", "winding", "rgb"), gpus=1, devices=None, disk=None, samples=None):
+                 want=("fa", "winding", "rgb"), gpus=1, devices=None, disk=None, samples=None, adaptive=None, contrast=None):
     """Fused path (lt_render): all three stages in one GPU call.  source_image None -> shadow render
     (escaped = white).  Returns dict with 'fa', 'winding', 'rgb', ... and 'stats'.
     gpus > 1: the frame's rows are split block-cyclically over that many devices of this node
@@ -222,9 +222,24 @@ def render_frame(source_image, metric, r_obs, fov, psi=(0.0, 0.0), theta_obs=np.
     samples: S -> lt_render_aa: S x S rays per pixel resolved on the GPU (anti-aliasing).  source_image is then the
     FINE-size background (H S, W S[, 3]) and the frame is (H, W); the result holds 'rgb', 'rgba', 'cover' (H, W, 4)
     (sub-rays escaped / captured / invalid / on the disk) and 'stats' only, with no disk, a ThinDisk or a
-    TransparentDisk; one GPU, every row traced."""
+    TransparentDisk; one GPU, every row traced.
+    adaptive: S_lo (with samples = S_hi > S_lo) -> lt_render_aa_adaptive: S_lo x S_lo rays for every pixel, S_hi x S_hi
+    only for the pixels on an edge (mixed cover, a neighbour of another cover, or a colour step above `contrast`;
+    contrast None: the library's default, negative: the colour test off).  source_image is then the PAIR of backgrounds
+    (at (H S_lo, W S_lo[, 3]), at (H S_hi, W S_hi[, 3])), and the result gains 'level' (H, W) (the samples per axis each
+    pixel got) and stats['refined']."""
     if source_image is None:
         raise ValueError("render_frame needs a background; for a shadow use black_hole_shadow.render_traced")
+    source_lo = None
+    if adaptive is not None:
+        if samples is None:
+            raise ValueError("adaptive=S_lo needs samples=S_hi")
+        if not (isinstance(source_image, (tuple, list)) and len(source_image) == 2):
+            raise ValueError("adaptive: the background is the pair (at the S_lo fine size, at the S_hi fine size)")
+        source_lo = np.asarray(source_image[0])
+        if source_lo.ndim == 3 and source_lo.shape[2] == 4:
+            source_lo = source_lo[..., :3]
+        source_image = source_image[1]
     source_image = np.asarray(source_image)
     if source_image.ndim == 3 and source_image.shape[2] == 4:
         # RGBA input (a PNG background): the reference's renderer cannot colour winding pixels of a 4-channel image
@@ -251,7 +266,18 @@ def render_frame(source_image, metric, r_obs, fov, psi=(0.0, 0.0), theta_obs=np.
         d = None if disk is None else (disk.to_lt() if hasattr(disk, "to_lt") else disk)
         max_images = getattr(disk, "max_images", None)
         mode = "plain" if disk is None else ("disk" if max_images is None else "disk_images")
-        aa = ltrace.default_aa(samples=S, mode=mode, **({} if max_images is None else dict(max_images=int(max_images))))
+        more = {} if max_images is None else dict(max_images=int(max_images))
+        if adaptive is not None:
+            S_lo = int(adaptive)
+            if S_lo < 1 or source_lo.shape[:2] != (cam.height * S_lo, cam.width * S_lo):
+                raise ValueError(f"adaptive={S_lo}: the first background must be (H * adaptive, W * adaptive) = "
+                                 f"{(cam.height * max(S_lo, 0), cam.width * max(S_lo, 0))}; got {source_lo.shape[:2]}")
+            if contrast is not None:
+                more["contrast"] = float(contrast)
+            ad = ltrace.default_aa_adaptive(samples_lo=S_lo, samples_hi=S, mode=mode, **more)
+            return ltrace.render_aa_adaptive(cam, met, opts, ad, disk=d, background_lo=source_lo, background_hi=source_image,
+                                             want=tuple(w for w in tuple(want) + ("cover", "level") if w in ("rgb", "rgba", "cover", "level")))
+        aa = ltrace.default_aa(samples=S, mode=mode, **more)
         return ltrace.render_aa(cam, met, opts, aa, disk=d, background=source_image,
                                 want=tuple(w for w in tuple(want) + ("cover",) if w in ("rgb", "rgba", "cover")))
     cam = _camera(shape, fov, psi, r_obs, theta_obs)
@@ -357,7 +383,7 @@ def save_lookup_cache(path, key, final_alpha, winding):
 def main(metric=None, M=1.0, a=0.0, r_obs_mult=100.0, psi=(0.0, 0.0), vertical_fov_deg=40.0,
          image_path="image.jpg", output_path="lensed_image.png", synthetic=None, staged=False,
          integrator=None, precision=None, schedule=None, gpus=1, full_trace=False, dedup_alpha=False,
-         lookup_cache=None, theta_obs_deg=90.0, disk=None, samples=None):
+         lookup_cache=None, theta_obs_deg=90.0, disk=None, samples=None, adaptive=None, contrast=None):
     """`lookup_cache`: path of an .npz (the reference's .gitignore names `lookup_cache.npz`, it never wrote one): the
     final_alpha / winding lookups of this metric, observer and camera are stored there and reused by the next call with
     the same settings -- a new background then costs one colouring pass (lt_shade) instead of a trace.
@@ -366,7 +392,9 @@ def main(metric=None, M=1.0, a=0.0, r_obs_mult=100.0, psi=(0.0, 0.0), vertical_f
     accretion disk (disk.ThinDisk, or disk.TransparentDisk for the optically thin one with its higher-order images) in
     the picture (fused path, one GPU, every row traced).  `samples`: S x S rays per pixel, resolved on the GPU (fused
     path, one GPU, every row traced): a synthetic background is generated at the fine size (W S x H S), one read from a
-    file is repeated S times along both axes, so the picture has the size asked for / the file's size."""
+    file is repeated S times along both axes, so the picture has the size asked for / the file's size.  `adaptive`: S_lo
+    (with `samples` = S_hi): S_lo x S_lo rays for every pixel and S_hi x S_hi only where the picture has an edge
+    (render_frame); the background is generated, or repeated, at both fine sizes.  `contrast`: its colour threshold."""
     import matplotlib.image as mpimg
 
     if metric is None:
@@ -380,8 +408,13 @@ def main(metric=None, M=1.0, a=0.0, r_obs_mult=100.0, psi=(0.0, 0.0), vertical_f
     S = 1 if samples is None else int(samples)
     if S < 1:
         raise ValueError("--samples must be at least 1")
+    if adaptive is not None and (samples is None or not 1 <= int(adaptive) < S):
+        raise ValueError("--adaptive S_LO needs --samples S_HI with 1 <= S_LO < S_HI")
+    img_lo = None
     if synthetic:
         img = synthetic_background(int(synthetic[1]) * S, int(synthetic[0]) * S)
+        if adaptive is not None:
+            img_lo = synthetic_background(int(synthetic[1]) * int(adaptive), int(synthetic[0]) * int(adaptive))
     else:
         img = mpimg.imread(image_path)
         if img.dtype == np.uint8:
@@ -389,6 +422,8 @@ def main(metric=None, M=1.0, a=0.0, r_obs_mult=100.0, psi=(0.0, 0.0), vertical_f
         if img.ndim == 3 and img.shape[2] == 4:
             print("Background has an alpha channel: lensing its RGB planes (see render_frame)")
             img = np.ascontiguousarray(img[..., :3])
+        if adaptive is not None:
+            img_lo = np.repeat(np.repeat(img, int(adaptive), axis=0), int(adaptive), axis=1)
         if samples is not None:
             img = np.repeat(np.repeat(img, S, axis=0), S, axis=1)
     timings["load_image"] = perf_counter() - t0
@@ -407,7 +442,7 @@ def main(metric=None, M=1.0, a=0.0, r_obs_mult=100.0, psi=(0.0, 0.0), vertical_f
 
     theta_obs = np.radians(theta_obs_deg)
     if (disk is not None or theta_obs_deg != 90.0 or samples is not None) and (staged or lookup_cache):
-        raise ValueError("--disk / --theta-obs / --samples need the fused path (no --staged, no --lookup-cache)")
+        raise ValueError("--disk / --theta-obs / --samples / --adaptive need the fused path (no --staged, no --lookup-cache)")
     rgba8 = None
     mirror = (disk is None) and samples is None and (not full_trace) and gpus <= 1 and not metric.is_spherically_symmetric and abs(psi[0]) <= 1e-8
     # (the staged path mirrors whenever the reference does, the fused one unless --full-trace / several GPUs)
@@ -454,12 +489,17 @@ def main(metric=None, M=1.0, a=0.0, r_obs_mult=100.0, psi=(0.0, 0.0), vertical_f
         if samples is not None:
             extra["samples"] = S
             print(f"Supersampling: {S} x {S} rays per pixel, resolved on the GPU")
-        out = render_frame(img, metric, r_obs, fov, psi=psi, tb_symmetry=mirror,
+        if adaptive is not None:
+            extra.update(adaptive=int(adaptive), contrast=contrast)
+            print(f"Adaptive: {int(adaptive)} x {int(adaptive)} rays for every pixel, {S} x {S} where the picture has an edge")
+        out = render_frame(img if adaptive is None else (img_lo, img), metric, r_obs, fov, psi=psi, tb_symmetry=mirror,
                            want=("rgb", "rgba") + (("fa", "winding") if lookup_cache else ()), gpus=gpus, **extra)
         timings["render"] = perf_counter() - t0
         if lookup_cache:
             save_lookup_cache(lookup_cache, cache_key, np.asarray(out["fa"]), np.asarray(out["winding"]))
         timings["gpu_integrate_ms"] = out["stats"]["integrate_ms"]
+        if adaptive is not None:
+            print(f"Refined pixels: {out['stats']['refined']:,} of {height * width:,} ({100.0 * out['stats']['refined'] / (height * width):.2f} %)")
         lensed, total, traced = out["rgb"], height * width, out["stats"]["rays"]   # mirrored rows are copies, not rays
         rgba8 = out["rgba"] if lensed.ndim == 3 else None
 
@@ -510,6 +550,12 @@ def build_parser():
     ap.add_argument("--samples", type=int, default=None, metavar="S",
                     help="anti-aliasing: trace S x S rays per pixel (1 ... 8) and resolve them on the GPU; with --synthetic "
                          "the background is generated at the fine size, a background file is repeated S times per axis")
+    ap.add_argument("--adaptive", type=int, default=None, metavar="S_LO",
+                    help="with --samples S_HI: trace S_LO x S_LO rays (1 ... 4) for every pixel and S_HI x S_HI only for the "
+                         "pixels on an edge (of the shadow, the disk, the photon ring)")
+    ap.add_argument("--contrast", type=float, default=None, metavar="T",
+                    help="--adaptive: refine a pixel whose colour differs from a neighbour's by more than T in a channel "
+                         "(default 0.0625; negative: off)")
     return ap
 
 
@@ -527,4 +573,4 @@ if __name__ == "__main__":
          vertical_fov_deg=args.fov_v, image_path=args.image, output_path=args.output, synthetic=args.synthetic,
          staged=args.staged, integrator=args.integrator, precision=args.precision, schedule=args.schedule,
          gpus=args.gpus, full_trace=args.full_trace, dedup_alpha=args.dedup_alpha, lookup_cache=args.lookup_cache,
-         theta_obs_deg=args.theta_obs, disk=disk, samples=args.samples)
+         theta_obs_deg=args.theta_obs, disk=disk, samples=args.samples, adaptive=args.adaptive, contrast=args.contrast)

@@ -22,6 +22,7 @@ STAT_WAVE_ITERS, STAT_WAVES, STAT_CLK_CYCLES, STAT_CLK_TICKS = 6, 7, 8, 9
 STAT_BG_TILES_LDS, STAT_BG_TILES_GLOBAL = 10, 11
 STAT_DISK = 12
 STAT_DISK_HITS = 13
+STAT_AA_REFINED = 14
 DISK_MAX_IMAGES = 8
 STATUS_DISK = 2
 STAT_WORDS = 16
@@ -75,6 +76,13 @@ class Disk(C.Structure):
 class AA(C.Structure):
     """lt_aa: supersampling (samples x samples rays per pixel; band_rows 0 = automatic)."""
     _fields_ = [("samples", C.c_int32), ("mode", C.c_int32), ("max_images", C.c_int32), ("band_rows", C.c_int32)]
+
+
+class AAAdaptive(C.Structure):
+    """lt_aa_adaptive: samples_lo^2 rays for every pixel, samples_hi^2 for the pixels on an edge (contrast < 0: the
+    colour test is off; band_rows / chunk_pixels 0 = automatic)."""
+    _fields_ = [("samples_lo", C.c_int32), ("samples_hi", C.c_int32), ("mode", C.c_int32), ("max_images", C.c_int32),
+                ("band_rows", C.c_int32), ("chunk_pixels", C.c_int32), ("contrast", C.c_float), ("reserved", C.c_int32)]
 
 
 AA_PLAIN, AA_DISK, AA_DISK_IMAGES = 0, 1, 2
@@ -163,6 +171,15 @@ SIGNATURES = {
                                C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
     "lt_aa_band_bytes": (C.c_int64, [C.POINTER(Camera), C.POINTER(Metric), C.POINTER(Opts), C.POINTER(AA), C.POINTER(Disk),
                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "lt_default_aa_adaptive": (None, [C.POINTER(AAAdaptive)]),
+    "lt_render_aa_adaptive_dev": (C.c_int, [C.POINTER(Camera), C.POINTER(Metric), C.POINTER(Opts), C.POINTER(AAAdaptive),
+                                            C.POINTER(Disk), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lt_render_aa_adaptive": (C.c_int, [C.POINTER(Camera), C.POINTER(Metric), C.POINTER(Opts), C.POINTER(AAAdaptive),
+                                        C.POINTER(Disk), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
+    "lt_aa_adaptive_plan": (C.c_int, [C.POINTER(Camera), C.POINTER(Metric), C.POINTER(Opts), C.POINTER(AAAdaptive),
+                                      C.POINTER(Disk), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
 }
 
 
@@ -783,3 +800,66 @@ def aa_band_bytes(cam, metric, opts, aa, disk=None):
     if n < 0:
         _check(n)
     return n, int(rows.value), int(bands.value)
+
+
+# ---- adaptive supersampling (lt_render_aa_adaptive) ---------------------------------------------------------------
+def default_aa_adaptive(**kw):
+    """lt_aa_adaptive with the library's defaults (samples_lo = 1, samples_hi = 4, plain mode, 3 images, automatic
+    bands and chunks, contrast = 0.0625); keywords override."""
+    a = AAAdaptive()
+    load().lt_default_aa_adaptive(C.byref(a))
+    for k, v in kw.items():
+        if k == "mode" and isinstance(v, str):
+            v = AA_MODES[v]
+        setattr(a, k, v)
+    return a
+
+
+def render_aa_adaptive(cam, metric, opts, adaptive, disk=None, background_lo=None, background_hi=None,
+                       want=("rgb", "rgba", "cover", "level")):
+    """Host-pointer adaptively supersampled frame (lt_render_aa_adaptive): adaptive.samples_lo^2 rays for every pixel,
+    adaptive.samples_hi^2 for the pixels on an edge.  background_lo / background_hi: the images at the two fine sizes,
+    (H * samples_lo, W * samples_lo[, 3]) and (H * samples_hi, W * samples_hi[, 3]), or both None.  Returns 'rgb',
+    'rgba', 'cover' as render_aa, 'level' (H, W) uint8 (the samples per axis each pixel got) and 'stats' with
+    'refined', the number of refined pixels."""
+    rows = _frame_rows(cam, opts)
+    if (background_lo is None) != (background_hi is None):
+        raise ValueError("background_lo and background_hi are both None or both given")
+    bg_lo, nch, gray = _fine_background(cam, int(adaptive.samples_lo), background_lo)
+    bg_hi, nch_hi, gray_hi = _fine_background(cam, int(adaptive.samples_hi), background_hi)
+    if (nch, gray) != (nch_hi, gray_hi):
+        raise ValueError("background_lo and background_hi differ in their channels")
+    out = _frame_outputs(rows, cam.width, nch, gray, [w for w in want if w in ("rgb", "rgba")])
+    if "cover" in want:
+        out["cover"] = pinned_empty((rows, cam.width, 4), np.uint8)
+    if "level" in want:
+        out["level"] = pinned_empty((rows, cam.width), np.uint8)
+    st = Stats()
+    _check(load().lt_render_aa_adaptive(C.byref(cam), C.byref(metric), C.byref(opts), C.byref(adaptive),
+                                        None if disk is None else C.byref(disk), _np_ptr(bg_lo), _np_ptr(bg_hi), nch,
+                                        _np_ptr(out.get("rgb")), _np_ptr(out.get("rgba")), _np_ptr(out.get("cover")),
+                                        _np_ptr(out.get("level")), C.byref(st)))
+    out["stats"] = stats_dict(st.counters, st.prologue_ms, st.integrate_ms, st.epilogue_ms)
+    out["stats"]["disk"] = int(st.counters[STAT_DISK])
+    out["stats"]["disk_hits"] = int(st.counters[STAT_DISK_HITS])
+    out["stats"]["refined"] = int(st.counters[STAT_AA_REFINED])
+    return out
+
+
+def render_aa_adaptive_dev(cam, metric, opts, adaptive, disk=None, d_bg_lo=0, d_bg_hi=0, bg_channels=3, d_rgb=0, d_rgba=0,
+                           d_cover=0, d_level=0, d_stats=0):
+    """Device-pointer form of render_aa_adaptive (lt_render_aa_adaptive_dev); pointers are integers, 0 = NULL.  Waits
+    for opts.stream once, between the two passes."""
+    p = lambda x: C.c_void_p(x) if x else None
+    _check(load().lt_render_aa_adaptive_dev(C.byref(cam), C.byref(metric), C.byref(opts), C.byref(adaptive),
+                                            None if disk is None else C.byref(disk), p(d_bg_lo), p(d_bg_hi), bg_channels,
+                                            p(d_rgb), p(d_rgba), p(d_cover), p(d_level), p(d_stats)))
+
+
+def aa_adaptive_plan(cam, metric, opts, adaptive, disk=None):
+    """(bytes of ray records the base pass's largest band needs, refined pixels per chunk) of a render_aa_adaptive call
+    (lt_aa_adaptive_plan; host arithmetic, no GPU needed); raises with the call's refusals."""
+    nbytes, chunk = C.c_int64(), C.c_int64()
+    _check(load().lt_aa_adaptive_plan(C.byref(cam), C.byref(metric), C.byref(opts), C.byref(adaptive),
+                                      None if disk is None else C.byref(disk), C.byref(nbytes), C.byref(chunk)))
+    return int(nbytes.value), int(chunk.value)
