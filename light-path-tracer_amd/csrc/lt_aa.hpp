@@ -20,15 +20,22 @@ constexpr int AA_PLAIN = 0, AA_DISK = 1, AA_DISK_IMAGES = 2; // LT_AA_*
 constexpr int AA_MAX_SAMPLES = 8;                            // LT_AA_MAX_SAMPLES
 constexpr int AA_BLOCK = 256;
 
-// The band's outputs, (rows, W) of OUTPUT pixels from the band's first row on; the colour goes to FrameOut's rgb / rgba.
+// Row-segment addressing of the resolve (AaListOut of lt_aa_adaptive.hpp is the other): slot x of row blockIdx.y of the
+// launch is output pixel (x, y) of the band, sub-sample (i, j) of it is the band's record of fine pixel (x S + i, y S + j),
+// and the result goes to y W + x of the band's outputs -- (rows, W) of OUTPUT pixels from the band's first row on; the
+// colour goes to FrameOut's rgb / rgba.
 struct AaOut {
     int samples;    // S
     int W;          // output width: the fine frame's is W S
     uint8_t *cover; // (rows, W, 4): the pixel's sub-rays that escaped, were captured, were invalid, hit the disk; or NULL
+    __device__ __forceinline__ bool live(int x) const { return x < W; }
+    __device__ __forceinline__ void pixel(int n, int &x, int &y) const { x = n; y = (int)blockIdx.y; }
+    __device__ __forceinline__ int64_t record(const CamConsts &c, int, int, int ix, int lrow) const { return pixel_to_q(c, ix, lrow); }
+    __device__ __forceinline__ int64_t out(int x) const { return (int64_t)blockIdx.y * W + x; }
 };
 
 // One sub-sample: the colour the mode's epilogue writes for fine pixel (ix, lrow) of the band, whose ray record is q
-// (pixel_to_q of the band for k_epilogue_aa, the list position for k_epilogue_aa_list of lt_aa_adaptive.hpp), the ray for
+// (Addr::record of aa_resolve below), the ray for
 // the counters (acc), whether it counts as on the disk (the ray ended there / has a hit) and its hits.
 //   AA_PLAIN        k_epilogue_frame (tb_symmetry = 0)
 //   AA_DISK         k_epilogue_disk
@@ -91,38 +98,39 @@ __device__ __forceinline__ void aa_sample(const CamConsts &c, const MetricConsts
     acc.add(res);
 }
 
-// (k_epilogue_aa_list of lt_aa_adaptive.hpp restates this kernel's two phases over list entries: change both together.)
-// c: the camera block of the band of the FINE frame (c.W = aa.W S columns, c.rows_local = gridDim.y S rows); o: its
-// background (fine size) and the partial counter sets, with rgb / rgba the band's OUTPUT rows; grid = (segments of
-// P = AA_BLOCK / S^2 output pixels, output rows of the band).
-template <typename T, int MODE, bool HAS_BG>
-__global__ void __launch_bounds__(AA_BLOCK) k_epilogue_aa(CamConsts c, MetricConsts m, DiskShade ds,
-                                                          const typename Vec4<T>::type *__restrict__ fin0,
-                                                          const typename Vec4<T>::type *__restrict__ fin1, FrameOut o,
-                                                          DiskImagesOut di, AaOut aa)
+// The resolve, both phases, of a workgroup of AA_BLOCK: slot n = blockIdx.x P + pl of the launch (P = AA_BLOCK / S^2 slots
+// per workgroup) is an output pixel by Addr's rule -- AaOut above or AaListOut of lt_aa_adaptive.hpp, resolved at compile
+// time: live(n), pixel(n) -> (x, y), record(c, n, k, ix, lrow) -> the sub-sample's ray record, out(n) -> where the result goes.
+template <typename T, int MODE, bool HAS_BG, typename Addr>
+__device__ __forceinline__ void aa_resolve(const CamConsts &c, const MetricConsts &m, const DiskShade &ds,
+                                           const typename Vec4<T>::type *__restrict__ fin0,
+                                           const typename Vec4<T>::type *__restrict__ fin1, const FrameOut &o,
+                                           const DiskImagesOut &di, const Addr &aa)
 {
     __shared__ float sh_rgb[AA_BLOCK][3];
     __shared__ uint8_t sh_class[AA_BLOCK]; // bits 0-1: escaped / captured / invalid / none of them; bit 2: on the disk
     const int S = aa.samples, S2 = S * S, P = AA_BLOCK / S2;
-    const int t = (int)threadIdx.x, pl = t / S2, k = t - pl * S2; // pixel of the group, sub-sample (row-major)
-    const int y = (int)blockIdx.y, x = (int)blockIdx.x * P + pl;
+    const int t = (int)threadIdx.x, pl = t / S2, k = t - pl * S2; // slot of the group, sub-sample (row-major)
+    const int n = (int)blockIdx.x * P + pl;
     const bool colour = o.rgb || o.rgba;
     StatAcc acc;
     bool on_disk = false;
     uint32_t nh = 0;
     int nch = (HAS_BG && o.bg) ? o.bg_c : 3;
-    if (pl < P && x < aa.W) {
+    if (pl < P && aa.live(n)) {
+        int x, y;
+        aa.pixel(n, x, y);
         const int j = k / S, i = k - j * S;
         float rgb[3] = {0.0f, 0.0f, 0.0f};
-        aa_sample<T, MODE, HAS_BG>(c, m, ds, fin0, fin1, o, di, pixel_to_q(c, x * S + i, y * S + j), x * S + i, y * S + j, colour, rgb, nch,
-                                   acc, on_disk, nh);
+        aa_sample<T, MODE, HAS_BG>(c, m, ds, fin0, fin1, o, di, aa.record(c, n, k, x * S + i, y * S + j), x * S + i, y * S + j, colour, rgb,
+                                   nch, acc, on_disk, nh);
         sh_rgb[t][0] = rgb[0]; sh_rgb[t][1] = rgb[1]; sh_rgb[t][2] = rgb[2];
         sh_class[t] = (uint8_t)((acc.esc ? 0 : acc.cap ? 1 : acc.inv ? 2 : 3) | (on_disk ? 4 : 0));
     }
     __syncthreads();
-    const int xo = (int)blockIdx.x * P + t; // the output pixel this work-item resolves
-    if (t < P && xo < aa.W) {
-        const int64_t p = (int64_t)y * aa.W + xo;
+    const int no = (int)blockIdx.x * P + t; // the slot this work-item resolves
+    if (t < P && aa.live(no)) {
+        const int64_t p = aa.out(no);
         double sum[3] = {0.0, 0.0, 0.0};
         uint32_t esc = 0, cap = 0, inv = 0, disk = 0;
         for (int s = t * S2; s < (t + 1) * S2; ++s) {
@@ -145,6 +153,18 @@ __global__ void __launch_bounds__(AA_BLOCK) k_epilogue_aa(CamConsts c, MetricCon
     }
     // words 6, 7: the rays on the disk / with a hit, and all hits (-> LT_STAT_DISK, LT_STAT_DISK_HITS)
     flush_stats<8>(o.stats, acc, m, on_disk, nh);
+}
+
+// c: the camera block of the band of the FINE frame (c.W = aa.W S columns, c.rows_local = gridDim.y S rows); o: its
+// background (fine size) and the partial counter sets, with rgb / rgba the band's OUTPUT rows; grid = (segments of
+// P = AA_BLOCK / S^2 output pixels, output rows of the band).
+template <typename T, int MODE, bool HAS_BG>
+__global__ void __launch_bounds__(AA_BLOCK) k_epilogue_aa(CamConsts c, MetricConsts m, DiskShade ds,
+                                                          const typename Vec4<T>::type *__restrict__ fin0,
+                                                          const typename Vec4<T>::type *__restrict__ fin1, FrameOut o,
+                                                          DiskImagesOut di, AaOut aa)
+{
+    aa_resolve<T, MODE, HAS_BG>(c, m, ds, fin0, fin1, o, di, aa);
 }
 
 } // namespace lt

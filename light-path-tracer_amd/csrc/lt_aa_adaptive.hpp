@@ -7,11 +7,9 @@
 //                          to a device list;
 //   k_prologue_aa_list     the initial records of the S_hi x S_hi sub-samples of a chunk of that list: ray q = k S_hi^2 + t
 //                          is sub-sample (t / S_hi, t % S_hi) of list pixel k = (y, x), which is fine pixel
-//                          (x S_hi + i, y S_hi + j) of the S_hi fine camera -- k_prologue_camera's body, statement for statement;
-//   k_epilogue_aa_list     k_epilogue_aa's two phases (aa_sample, then the ordered float64 sum) over list entries instead
-//                          of a row segment, overwriting rgb / rgba / cover at the listed pixels.
-// The two bodies are restated here, not shared with the kernels they come from, so that those compile to exactly what
-// they were; the identity tests of the feature compare the two statements bit for bit.
+//                          (x S_hi + i, y S_hi + j) of the S_hi fine camera -- k_prologue_camera's store_camera_ray;
+//   k_epilogue_aa_list     the resolve of lt_aa.hpp (aa_resolve) over list entries instead of a row segment, overwriting
+//                          rgb / rgba / cover at the listed pixels.
 //
 // One ray per work-item everywhere, as in lt_aa.hpp and for its reason.  Nothing depends on the order of the list: each
 // entry's rays are a function of the entry alone and its outputs go to the entry's own pixel.
@@ -94,85 +92,36 @@ __global__ void __launch_bounds__(256) k_prologue_aa_list(CamConsts c, MetricCon
     const uint32_t p = list[k], y = p / (uint32_t)W, x = p - y * (uint32_t)W;
     const uint32_t j = t / (uint32_t)S, i = t - j * (uint32_t)S;
     const int ix = (int)(x * (uint32_t)S + i), grow = (int)(y * (uint32_t)S + j);
-    double alpha, theta = 0.0;
-    if (m.kind == 0) alpha = pixel_alpha(c, ix, grow); // a spherically symmetric metric never looks at theta
-    else pixel_angles(c, ix, grow, alpha, theta);
-    int flags = 0;
-    if (c.refine_on) {
-        double x_cam = ((double)ix - c.half_W) / c.fx;
-        if (fabs(x_cam - c.bh_x_cam) <= c.refine_thresh) flags |= FLAG_REFINE;
-    }
-    if (m.kind == 0) {
-        double w0;
-        if (schw_initial_w(m, alpha, w0)) flags |= FLAG_OK;
-        store_ic<T>(ic, q, w0, 0, 0, flags);
-    } else {
-        double p_r, p_th, p_phi;
-        if (kerr_initial_momenta(m, alpha, theta, p_r, p_th, p_phi)) flags |= FLAG_OK;
-        store_ic<T>(ic, q, p_r, p_th, p_phi, flags);
-    }
+    store_camera_ray<T>(c, m, ic, q, ix, grow);
 }
 
+// List addressing of the resolve (AaOut of lt_aa.hpp is the other): slot e of the launch is the chunk's entry e, its
+// sub-sample k is record e S^2 + k, and the result overwrites the entry's pixel of the WHOLE output frame.
 struct AaListOut {
     int samples;          // S_hi
     int W;                // output width
     uint8_t *cover;       // (H, W, 4) of the whole frame, or NULL
     const uint32_t *list; // the chunk's entries: output pixel y W + x
     int n;                // ... and how many
+    __device__ __forceinline__ bool live(int e) const { return e < n; }
+    __device__ __forceinline__ void pixel(int e, int &x, int &y) const
+    {
+        const uint32_t p = list[e], py = p / (uint32_t)W;
+        y = (int)py; x = (int)(p - py * (uint32_t)W);
+    }
+    __device__ __forceinline__ int64_t record(const CamConsts &, int e, int k, int, int) const { return (int64_t)e * (samples * samples) + k; }
+    __device__ __forceinline__ int64_t out(int e) const { return (int64_t)list[e]; }
 };
 
 // c, o: as k_prologue_aa_list's camera and k_epilogue_aa's FrameOut (the background at S_hi fine size; rgb / rgba the
-// WHOLE output frame).  A workgroup takes P = AA_BLOCK / S^2 list entries; entry e's sub-sample k is record e S^2 + k.
+// WHOLE output frame).  grid = groups of P = AA_BLOCK / S^2 list entries.
 template <typename T, int MODE, bool HAS_BG>
 __global__ void __launch_bounds__(AA_BLOCK) k_epilogue_aa_list(CamConsts c, MetricConsts m, DiskShade ds,
                                                                const typename Vec4<T>::type *__restrict__ fin0,
                                                                const typename Vec4<T>::type *__restrict__ fin1, FrameOut o,
                                                                DiskImagesOut di, AaListOut aa)
 {
-    __shared__ float sh_rgb[AA_BLOCK][3];
-    __shared__ uint8_t sh_class[AA_BLOCK]; // as k_epilogue_aa
-    const int S = aa.samples, S2 = S * S, P = AA_BLOCK / S2;
-    const int t = (int)threadIdx.x, pl = t / S2, k = t - pl * S2; // entry of the group, sub-sample (row-major)
-    const int e = (int)blockIdx.x * P + pl;
-    const bool colour = o.rgb || o.rgba;
-    StatAcc acc;
-    bool on_disk = false;
-    uint32_t nh = 0;
-    int nch = (HAS_BG && o.bg) ? o.bg_c : 3;
-    if (pl < P && e < aa.n) {
-        const uint32_t p = aa.list[e], y = p / (uint32_t)aa.W, x = p - y * (uint32_t)aa.W;
-        const int j = k / S, i = k - j * S;
-        float rgb[3] = {0.0f, 0.0f, 0.0f};
-        aa_sample<T, MODE, HAS_BG>(c, m, ds, fin0, fin1, o, di, (int64_t)e * S2 + k, (int)x * S + i, (int)y * S + j, colour, rgb, nch, acc,
-                                   on_disk, nh);
-        sh_rgb[t][0] = rgb[0]; sh_rgb[t][1] = rgb[1]; sh_rgb[t][2] = rgb[2];
-        sh_class[t] = (uint8_t)((acc.esc ? 0 : acc.cap ? 1 : acc.inv ? 2 : 3) | (on_disk ? 4 : 0));
-    }
-    __syncthreads();
-    const int eo = (int)blockIdx.x * P + t; // the entry this work-item resolves
-    if (t < P && eo < aa.n) {
-        const int64_t p = (int64_t)aa.list[eo];
-        double sum[3] = {0.0, 0.0, 0.0};
-        uint32_t esc = 0, cap = 0, inv = 0, disk = 0;
-        for (int s = t * S2; s < (t + 1) * S2; ++s) {
-            sum[0] += (double)sh_rgb[s][0]; sum[1] += (double)sh_rgb[s][1]; sum[2] += (double)sh_rgb[s][2];
-            const uint32_t cl = sh_class[s];
-            esc += (cl & 3) == 0; cap += (cl & 3) == 1; inv += (cl & 3) == 2;
-            disk += cl >> 2;
-        }
-        if (colour) {
-            const double s2 = (double)S2;
-            const float rgb[3] = {(float)(sum[0] / s2), (float)(sum[1] / s2), (float)(sum[2] / s2)};
-            if (o.rgb) for (int ch = 0; ch < nch; ++ch) o.rgb[p * nch + ch] = rgb[ch];
-            if (o.rgba) store_rgba(o, p, rgb, nch);
-        }
-        if (aa.cover) {
-            uchar4 cv;
-            cv.x = (uint8_t)esc; cv.y = (uint8_t)cap; cv.z = (uint8_t)inv; cv.w = (uint8_t)disk;
-            reinterpret_cast<uchar4 *>(aa.cover)[p] = cv;
-        }
-    }
-    flush_stats<8>(o.stats, acc, m, on_disk, nh);
+    aa_resolve<T, MODE, HAS_BG>(c, m, ds, fin0, fin1, o, di, aa);
 }
 
 } // namespace lt

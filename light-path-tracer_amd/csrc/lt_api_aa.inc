@@ -26,6 +26,7 @@ struct AaPlan {
     int band_blocks = 1;        // row blocks per band
     int n_bands = 0;
     size_t band_bytes = 0;      // ray records of the largest band
+    lt_camera fine{};           // the camera of the fine frame
 };
 
 // Output rows of row block b of a frame of `height` rows.
@@ -33,6 +34,30 @@ static int64_t block_rows(int64_t b, int row_block, int height)
 {
     const int64_t r0 = b * row_block, r1 = r0 + row_block;
     return (r1 < height ? r1 : height) - r0;
+}
+
+// The ray records of one ray: three 4-vectors, plus the thin disk's slots and count.
+static size_t aa_ray_bytes(int precision, int mode, int max_images)
+{
+    const size_t elem = elem_size(precision);
+    return 3 * 4 * elem + (mode == LT_AA_DISK_IMAGES ? (size_t)max_images * 2 * elem + sizeof(uint32_t) : 0);
+}
+
+// The fine frame's camera: `cam` with W S x H S pixels, refused when a side does not fit 31 bits.
+static int aa_fine_camera(const lt_camera *cam, int S, lt_camera *fine)
+{
+    if ((int64_t)cam->width * S > INT32_MAX || (int64_t)cam->height * S > INT32_MAX)
+        return fail(LT_ERR_INVALID_ARG, "fine frame of %d x %d pixels times %d", cam->width, cam->height, S);
+    *fine = *cam;
+    fine->width = cam->width * S;
+    fine->height = cam->height * S;
+    return LT_OK;
+}
+
+static int aa_check_bg_channels(const float *bg, int32_t bg_channels)
+{
+    if (bg && bg_channels != 1 && bg_channels != 3) return fail(LT_ERR_INVALID_ARG, "bg_channels must be 1 or 3");
+    return LT_OK;
 }
 
 // Refusals in the order the header gives them: samples and mode, then the mode's own, then lt_render_dev's.
@@ -50,8 +75,7 @@ static int aa_plan(const lt_camera *cam, const lt_metric *metric, const lt_opts 
         return rc;
     if (cam->width <= 0 || cam->height <= 0) return fail(LT_ERR_INVALID_ARG, "empty frame %dx%d", cam->width, cam->height);
     const int S = aa->samples;
-    if ((int64_t)cam->width * S > INT32_MAX || (int64_t)cam->height * S > INT32_MAX)
-        return fail(LT_ERR_INVALID_ARG, "fine frame of %d x %d pixels times %d", cam->width, cam->height, S);
+    if ((rc = aa_fine_camera(cam, S, &p->fine))) return rc;
     p->o = *opts;
     if ((rc = check_opts(metric, &p->o))) return rc;
     lt_opts &o = p->o;
@@ -60,9 +84,8 @@ static int aa_plan(const lt_camera *cam, const lt_metric *metric, const lt_opts 
     if ((rc = partition_blocks(cam->height, o, &p->owned, &p->rows))) return rc;
     if (aa->band_rows < 0 || aa->band_rows % o.row_block)
         return fail(LT_ERR_INVALID_ARG, "band_rows %d is not a multiple of row_block %d", (int)aa->band_rows, o.row_block);
-    // ray records of one band: three 4-vectors per ray of the padded fine tiles, plus the thin disk's slots and count
-    const size_t elem = elem_size(o.precision);
-    const size_t per_ray = 3 * 4 * elem + (aa->mode == LT_AA_DISK_IMAGES ? (size_t)aa->max_images * 2 * elem + sizeof(uint32_t) : 0);
+    // ray records of one band: every ray of the padded fine tiles
+    const size_t per_ray = aa_ray_bytes(o.precision, aa->mode, aa->max_images);
     const size_t fine_cols = ((size_t)cam->width * S + 7) / 8 * 8;
     auto bytes_of = [&](int64_t blocks) { return (((size_t)blocks * o.row_block * S + 7) / 8 * 8) * fine_cols * per_ray; };
     int64_t blocks = aa->band_rows ? aa->band_rows / o.row_block : (int64_t)p->owned.size();
@@ -92,6 +115,39 @@ extern "C" int64_t lt_aa_band_bytes(const lt_camera *cam, const lt_metric *metri
     return (int64_t)p.band_bytes;
 }
 
+// The resolve launch of both supersampling paths: k_epilogue_aa over `grid` for the row-segment addressing (AaOut),
+// k_epilogue_aa_list for the list addressing (AaListOut), on the records of `w` / `recs`, and the fold of the counters.
+template <typename Addr>
+static int launch_aa_resolve(const CamConsts &c, const MetricConsts &mc, const lt_opts &o, int aa_mode, const Workspace &w,
+                             const FrameOut &fo, uint64_t *d_stats, hipStream_t s, const DiskParams *disk, const DiskRecordsBuf &recs,
+                             const Addr &ao, dim3 grid)
+{
+    DiskShade ds{};
+    DiskImagesOut di{};
+    if (disk) ds = DiskShade{mc.M, mc.a, disk->r_in, disk->q, disk->exposure};
+    if (disk && disk->max_images) di = DiskImagesOut{recs.p, recs.hits, (int64_t)w.n_q, disk->max_images, nullptr, nullptr};
+    const bool has_bg = fo.bg != nullptr && (fo.rgb || fo.rgba);
+    auto launch = [&](auto t, auto mode, auto bg) {
+        using T = decltype(t);
+        constexpr int MODE = decltype(mode)::value;
+        constexpr bool BG = decltype(bg)::value;
+        if constexpr (std::is_same<Addr, AaOut>::value) k_epilogue_aa<T, MODE, BG><<<grid, AA_BLOCK, 0, s>>>(c, mc, ds, w.fin0<T>(), w.fin1<T>(), fo, di, ao);
+        else k_epilogue_aa_list<T, MODE, BG><<<grid, AA_BLOCK, 0, s>>>(c, mc, ds, w.fin0<T>(), w.fin1<T>(), fo, di, ao);
+    };
+    with_precision(o.precision, [&](auto t) {
+        auto with_bg = [&](auto mode) {
+            if (has_bg) launch(t, mode, std::true_type{});
+            else launch(t, mode, std::false_type{});
+        };
+        if (aa_mode == LT_AA_PLAIN) with_bg(std::integral_constant<int, AA_PLAIN>{});
+        else if (aa_mode == LT_AA_DISK) with_bg(std::integral_constant<int, AA_DISK>{});
+        else with_bg(std::integral_constant<int, AA_DISK_IMAGES>{});
+    });
+    if (d_stats) k_stats_reduce<<<1, STAT_SLOTS, 0, s>>>(w.partials, (unsigned long long *)d_stats, LT_STAT_DISK, LT_STAT_DISK_HITS);
+    HIP_TRY(hipGetLastError());
+    return LT_OK;
+}
+
 static int launch_epilogue_aa(const CamConsts &c, const MetricConsts &mc, const lt_opts &o, const Workspace &w, const FrameOut &fo,
                               uint64_t *d_stats, hipStream_t s, const DiskParams *disk, const DiskRecordsBuf &recs, const AaBand &aa)
 {
@@ -100,30 +156,9 @@ static int launch_epilogue_aa(const CamConsts &c, const MetricConsts &mc, const 
         (int64_t)c.tiles_x * c.tiles_y * 64 != (int64_t)w.n_q)
         return fail(LT_ERR_INVALID_ARG, "supersampling: band of %d x %d fine pixels for %d x %lld output pixels times %d", c.W,
                     c.rows_local, aa.W, (long long)aa.rows, aa.samples);
-    DiskShade ds{};
-    DiskImagesOut di{};
-    if (disk) ds = DiskShade{mc.M, mc.a, disk->r_in, disk->q, disk->exposure};
-    if (disk && disk->max_images) di = DiskImagesOut{recs.p, recs.hits, (int64_t)w.n_q, disk->max_images, nullptr, nullptr};
-    const AaOut ao{aa.samples, aa.W, aa.d_cover};
-    const bool has_bg = fo.bg != nullptr && (fo.rgb || fo.rgba);
     const int per_group = AA_BLOCK / (aa.samples * aa.samples); // output pixels of a workgroup
-    const dim3 grid((unsigned)((aa.W + per_group - 1) / per_group), (unsigned)aa.rows);
-    auto launch = [&](auto t, auto mode, auto bg) {
-        using T = decltype(t);
-        k_epilogue_aa<T, decltype(mode)::value, decltype(bg)::value><<<grid, AA_BLOCK, 0, s>>>(c, mc, ds, w.fin0<T>(), w.fin1<T>(), fo, di, ao);
-    };
-    with_precision(o.precision, [&](auto t) {
-        auto with_bg = [&](auto mode) {
-            if (has_bg) launch(t, mode, std::true_type{});
-            else launch(t, mode, std::false_type{});
-        };
-        if (aa.mode == LT_AA_PLAIN) with_bg(std::integral_constant<int, AA_PLAIN>{});
-        else if (aa.mode == LT_AA_DISK) with_bg(std::integral_constant<int, AA_DISK>{});
-        else with_bg(std::integral_constant<int, AA_DISK_IMAGES>{});
-    });
-    if (d_stats) k_stats_reduce<<<1, STAT_SLOTS, 0, s>>>(w.partials, (unsigned long long *)d_stats, LT_STAT_DISK, LT_STAT_DISK_HITS);
-    HIP_TRY(hipGetLastError());
-    return LT_OK;
+    return launch_aa_resolve(c, mc, o, aa.mode, w, fo, d_stats, s, disk, recs, AaOut{aa.samples, aa.W, aa.d_cover},
+                             dim3((unsigned)((aa.W + per_group - 1) / per_group), (unsigned)aa.rows));
 }
 
 // The bands of a planned call, one after the other on the call's stream.  own: one private timing quad per band
@@ -132,12 +167,10 @@ static int aa_render_bands(const lt_camera *cam, const lt_metric *metric, const 
                            int32_t bg_channels, float *d_rgb, uint8_t *d_rgba, uint8_t *d_cover, uint64_t *d_stats,
                            const EventQuad *own)
 {
-    if (d_bg && bg_channels != 1 && bg_channels != 3) return fail(LT_ERR_INVALID_ARG, "bg_channels must be 1 or 3");
+    int rc = aa_check_bg_channels(d_bg, bg_channels);
+    if (rc) return rc;
     const int S = aa->samples, W = cam->width;
     const int nch = d_bg ? bg_channels : 3;
-    lt_camera fine = *cam;
-    fine.width = W * S;
-    fine.height = cam->height * S;
     lt_opts o = p.o;
     o.row_block = p.o.row_block * S;
     int64_t row0 = 0; // output rows of the bands before this one
@@ -146,9 +179,9 @@ static int aa_render_bands(const lt_camera *cam, const lt_metric *metric, const 
         int64_t rows = 0;
         for (size_t i = i0; i < i1; ++i) rows += block_rows(p.owned[i], p.o.row_block, cam->height);
         const AaBand band{S, aa->mode, W, rows, d_cover ? d_cover + row0 * W * 4 : nullptr, p.n_bands > 1 ? &p.owned : nullptr, i0, i1 - i0};
-        int rc = render_dev_impl(&fine, metric, &o, d_bg, bg_channels, nullptr, nullptr, nullptr, nullptr,
-                                 d_rgb ? d_rgb + row0 * W * nch : nullptr, d_rgba ? d_rgba + row0 * W * 4 : nullptr, d_stats,
-                                 own ? own + b : nullptr, p.has_disk ? &p.dp : nullptr, &band);
+        rc = render_dev_impl(&p.fine, metric, &o, d_bg, bg_channels, nullptr, nullptr, nullptr, nullptr,
+                             d_rgb ? d_rgb + row0 * W * nch : nullptr, d_rgba ? d_rgba + row0 * W * 4 : nullptr, d_stats,
+                             own ? own + b : nullptr, p.has_disk ? &p.dp : nullptr, &band);
         if (rc) return rc;
         row0 += rows;
     }
@@ -166,7 +199,7 @@ extern "C" int lt_render_aa_dev(const lt_camera *cam, const lt_metric *metric, c
     return aa_render_bands(cam, metric, aa, p, d_bg, bg_channels, d_rgb, d_rgba, d_cover, d_stats, nullptr);
 }
 
-// One private timing quad per band, kept by the slot (grown to the most bands a call had).
+// One private timing quad per launch group of a host-pointer call (a band; the adaptive call's flag kernel and chunks), kept by the slot (grown to the most bands a call had).
 static int aa_slot_events(StreamSlot *sl, int n_bands)
 {
     while ((int)sl->aa_events.size() < n_bands) {
@@ -181,6 +214,17 @@ static int aa_slot_events(StreamSlot *sl, int n_bands)
     return LT_OK;
 }
 
+// The kernel times of the slot's first n quads, added to st: after the wait that follows their launches.
+static int aa_add_times(const StreamSlot *sl, int n, lt_stats *st)
+{
+    for (int b = 0; b < n; ++b) {
+        float ms[3] = {0, 0, 0};
+        for (int i = 0; i < 3; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], sl->aa_events[(size_t)b].e[i], sl->aa_events[(size_t)b].e[i + 1]));
+        st->prologue_ms += ms[0]; st->integrate_ms += ms[1]; st->epilogue_ms += ms[2];
+    }
+    return LT_OK;
+}
+
 extern "C" int lt_render_aa(const lt_camera *cam, const lt_metric *metric, const lt_opts *opts, const lt_aa *aa,
                             const lt_disk *disk, const float *bg, int32_t bg_channels, float *out_rgb, uint8_t *out_rgba,
                             uint8_t *out_cover, lt_stats *stats)
@@ -189,7 +233,7 @@ extern "C" int lt_render_aa(const lt_camera *cam, const lt_metric *metric, const
     if (rc) return rc;
     AaPlan p;
     if ((rc = aa_plan(cam, metric, opts, aa, disk, &p))) return rc;
-    if (bg && bg_channels != 1 && bg_channels != 3) return fail(LT_ERR_INVALID_ARG, "bg_channels must be 1 or 3");
+    if ((rc = aa_check_bg_channels(bg, bg_channels))) return rc;
     const size_t S = (size_t)aa->samples, n = (size_t)p.rows * cam->width;
     lt_stats st;
     memset(&st, 0, sizeof(st));
@@ -206,11 +250,7 @@ extern "C" int lt_render_aa(const lt_camera *cam, const lt_metric *metric, const
         return rc;
     for (int i : {i_rgba, i_cover, i_rgb, i_stats}) if ((rc = sg.fetch(i))) return rc;
     HIP_TRY(hipStreamSynchronize(sg.s));
-    for (int b = 0; b < p.n_bands; ++b) { // kernel times are summed over the bands
-        float ms[3] = {0, 0, 0};
-        for (int i = 0; i < 3; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], sg.sl->aa_events[(size_t)b].e[i], sg.sl->aa_events[(size_t)b].e[i + 1]));
-        st.prologue_ms += ms[0]; st.integrate_ms += ms[1]; st.epilogue_ms += ms[2];
-    }
+    if ((rc = aa_add_times(sg.sl, p.n_bands, &st))) return rc; // kernel times are summed over the bands
     if (stats) *stats = st;
     return LT_OK;
 }

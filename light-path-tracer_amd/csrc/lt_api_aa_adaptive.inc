@@ -22,6 +22,7 @@ struct AaAdaptivePlan {
     AaPlan base;              // the base pass: lt_render_aa with `lo`
     lt_aa lo{};
     int64_t chunk_pixels = 0; // refined pixels per chunk
+    lt_camera fine_hi{};      // the camera of the S_hi fine frame
 };
 
 // Refusals in the order the header gives them: the adaptive fields, then lt_render_aa's for the base pass, the S_hi fine
@@ -39,16 +40,14 @@ static int aa_adaptive_plan(const lt_camera *cam, const lt_metric *metric, const
     p->lo = lt_aa{ad->samples_lo, ad->mode, ad->max_images, ad->band_rows};
     if ((rc = aa_plan(cam, metric, opts, &p->lo, disk, &p->base))) return rc;
     const int S = ad->samples_hi;
-    if ((int64_t)cam->width * S > INT32_MAX || (int64_t)cam->height * S > INT32_MAX)
-        return fail(LT_ERR_INVALID_ARG, "fine frame of %d x %d pixels times %d", cam->width, cam->height, S);
+    if ((rc = aa_fine_camera(cam, S, &p->fine_hi))) return rc;
     if ((int64_t)cam->width * cam->height > INT32_MAX) // (the list holds 32-bit pixel indices)
         return fail(LT_ERR_INVALID_ARG, "a frame of %d x %d pixels: more than 2^31 - 1", cam->width, cam->height);
     if (p->base.o.n_parts != 1 || p->base.o.block_owner)
         return fail(LT_ERR_UNSUPPORTED, "adaptive supersampling renders the whole frame: the 3 x 3 test reads rows a partition does not "
                                         "own (n_parts %d%s)", p->base.o.n_parts, p->base.o.block_owner ? ", block_owner table" : "");
     // a chunk's records: per ray what a band's rays need (aa_plan), S_hi^2 rays per pixel, whole wavefronts, < 2^31 of them
-    const size_t elem = elem_size(p->base.o.precision);
-    const size_t per_ray = 3 * 4 * elem + (ad->mode == LT_AA_DISK_IMAGES ? (size_t)ad->max_images * 2 * elem + sizeof(uint32_t) : 0);
+    const size_t per_ray = aa_ray_bytes(p->base.o.precision, ad->mode, ad->max_images);
     const int64_t n_pix = (int64_t)cam->width * cam->height, S2 = (int64_t)S * S;
     int64_t chunk = ad->chunk_pixels ? (int64_t)ad->chunk_pixels : (int64_t)((((size_t)LT_AA_BAND_BYTES / per_ray) & ~(size_t)63) / (size_t)S2);
     chunk = std::min(chunk, ((int64_t)INT32_MAX - 63) / S2);
@@ -70,11 +69,8 @@ extern "C" int lt_aa_adaptive_plan(const lt_camera *cam, const lt_metric *metric
 
 // The S_hi fine camera as ONE partition of the whole frame: local rows are global rows, no tiles (the list kernels take
 // their pixels from the list).  What k_prologue_camera and the epilogues read of a band's block is set as make_camera sets it.
-static void make_list_camera(const lt_camera *cam, int S, int kind, const lt_opts &o, CamConsts *c)
+static void make_list_camera(const lt_camera &fine, int kind, const lt_opts &o, CamConsts *c)
 {
-    lt_camera fine = *cam;
-    fine.width = cam->width * S;
-    fine.height = cam->height * S;
     const bool front = camera_pinhole(&fine, o.axis_refine_frac, c);
     c->row_block = o.row_block; c->n_parts = 1; c->part = 0;
     c->rows_local = c->trace_rows = fine.height;
@@ -110,32 +106,19 @@ static int aa_refine_chunk(const CamConsts &c, const MetricConsts &mc, const lt_
     if ((rc = tm.mark(1, s))) return rc;
     if ((rc = launch_integrate_any(mc, o, lambda_max, w, n_q, s, d_stats, disk, recs))) return rc;
     if ((rc = tm.mark(2, s))) return rc;
-    DiskShade ds{};
-    DiskImagesOut di{};
-    if (disk) ds = DiskShade{mc.M, mc.a, disk->r_in, disk->q, disk->exposure};
-    if (disk && disk->max_images) di = DiskImagesOut{recs.p, recs.hits, (int64_t)w.n_q, disk->max_images, nullptr, nullptr};
-    const AaListOut ao{S, W, d_cover, d_list, n};
-    const bool has_bg = fo.bg != nullptr && (fo.rgb || fo.rgba);
     const int per_group = AA_BLOCK / S2; // list entries of a workgroup
-    const unsigned grid = (unsigned)((n + per_group - 1) / per_group);
-    auto launch = [&](auto t, auto mode, auto bg) {
-        using T = decltype(t);
-        k_epilogue_aa_list<T, decltype(mode)::value, decltype(bg)::value><<<grid, AA_BLOCK, 0, s>>>(c, mc, ds, w.fin0<T>(), w.fin1<T>(), fo, di, ao);
-    };
-    with_precision(o.precision, [&](auto t) {
-        auto with_bg = [&](auto mode) {
-            if (has_bg) launch(t, mode, std::true_type{});
-            else launch(t, mode, std::false_type{});
-        };
-        if (ad->mode == LT_AA_PLAIN) with_bg(std::integral_constant<int, AA_PLAIN>{});
-        else if (ad->mode == LT_AA_DISK) with_bg(std::integral_constant<int, AA_DISK>{});
-        else with_bg(std::integral_constant<int, AA_DISK_IMAGES>{});
-    });
-    if (d_stats) k_stats_reduce<<<1, STAT_SLOTS, 0, s>>>(w.partials, (unsigned long long *)d_stats, LT_STAT_DISK, LT_STAT_DISK_HITS);
-    HIP_TRY(hipGetLastError());
+    if ((rc = launch_aa_resolve(c, mc, o, ad->mode, w, fo, d_stats, s, disk, recs, AaListOut{S, W, d_cover, d_list, n},
+                                dim3((unsigned)((n + per_group - 1) / per_group)))))
+        return rc;
     if ((rc = tm.mark(3, s))) return rc;
     tm.finish();
     return LT_OK;
+}
+
+static int aa_check_backgrounds(const float *bg_lo, const float *bg_hi, int32_t bg_channels)
+{
+    if ((bg_lo == nullptr) != (bg_hi == nullptr)) return fail(LT_ERR_INVALID_ARG, "the two backgrounds are both NULL or both given");
+    return aa_check_bg_channels(bg_lo, bg_channels);
 }
 
 // A planned call on device pointers.  quads: the host call's -- the launches are timed with private quads of the slot
@@ -146,9 +129,8 @@ static int aa_adaptive_run(const lt_camera *cam, const lt_metric *metric, const 
                            const float *d_bg_lo, const float *d_bg_hi, int32_t bg_channels, float *d_rgb, uint8_t *d_rgba,
                            uint8_t *d_cover, uint8_t *d_level, uint64_t *d_stats, int *quads)
 {
-    int rc;
-    if ((d_bg_lo == nullptr) != (d_bg_hi == nullptr)) return fail(LT_ERR_INVALID_ARG, "the two backgrounds are both NULL or both given");
-    if (d_bg_lo && bg_channels != 1 && bg_channels != 3) return fail(LT_ERR_INVALID_ARG, "bg_channels must be 1 or 3");
+    int rc = aa_check_backgrounds(d_bg_lo, d_bg_hi, bg_channels);
+    if (rc) return rc;
     const lt_opts &o = p.base.o;
     hipStream_t s = (hipStream_t)o.stream;
     const int W = cam->width, H = cam->height, nch = d_bg_lo ? bg_channels : 3;
@@ -203,7 +185,7 @@ static int aa_adaptive_run(const lt_camera *cam, const lt_metric *metric, const 
     if ((rc = make_metric(metric, cam->r_obs, cam->theta_obs, o.h_max, &mc))) return rc;
     count_evals(o.integrator, &mc);
     CamConsts c;
-    make_list_camera(cam, ad->samples_hi, metric->kind, o, &c);
+    make_list_camera(p.fine_hi, metric->kind, o, &c);
     const double lambda_max = fmax(5000.0, 6.0 * cam->r_obs); // metrics.py:1132
     const int64_t n_chunks = ((int64_t)n_refined + p.chunk_pixels - 1) / p.chunk_pixels;
     if (quads && (rc = aa_slot_events(sl, n_bands + 1 + (int)n_chunks))) return rc;
@@ -236,8 +218,7 @@ extern "C" int lt_render_aa_adaptive(const lt_camera *cam, const lt_metric *metr
     if (rc) return rc;
     AaAdaptivePlan p;
     if ((rc = aa_adaptive_plan(cam, metric, opts, ad, disk, &p))) return rc;
-    if ((bg_lo == nullptr) != (bg_hi == nullptr)) return fail(LT_ERR_INVALID_ARG, "the two backgrounds are both NULL or both given");
-    if (bg_lo && bg_channels != 1 && bg_channels != 3) return fail(LT_ERR_INVALID_ARG, "bg_channels must be 1 or 3");
+    if ((rc = aa_check_backgrounds(bg_lo, bg_hi, bg_channels))) return rc;
     const size_t n = (size_t)cam->width * cam->height, s_lo = (size_t)ad->samples_lo, s_hi = (size_t)ad->samples_hi;
     lt_stats st;
     memset(&st, 0, sizeof(st));
@@ -255,11 +236,7 @@ extern "C" int lt_render_aa_adaptive(const lt_camera *cam, const lt_metric *metr
         return rc;
     for (int i : {i_rgba, i_cover, i_level, i_rgb, i_stats}) if ((rc = sg.fetch(i))) return rc;
     HIP_TRY(hipStreamSynchronize(sg.s));
-    for (int b = 0; b < quads; ++b) { // kernel times are summed over bands, the flag kernel and chunks
-        float ms[3] = {0, 0, 0};
-        for (int i = 0; i < 3; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], sg.sl->aa_events[(size_t)b].e[i], sg.sl->aa_events[(size_t)b].e[i + 1]));
-        st.prologue_ms += ms[0]; st.integrate_ms += ms[1]; st.epilogue_ms += ms[2];
-    }
+    if ((rc = aa_add_times(sg.sl, quads, &st))) return rc; // kernel times are summed over bands, the flag kernel and chunks
     if (stats) *stats = st;
     return LT_OK;
 }

@@ -244,18 +244,12 @@ __device__ __forceinline__ void store_ic(typename Vec4<T>::type *ic, int64_t q, 
     ic[q] = v;
 }
 
-// ---- K1: camera prologue -------------------------------------------------------------------
-// (k_prologue_aa_list of lt_aa_adaptive.hpp restates this kernel's body for a list of pixels: change both together.)
+// Record q of the camera ray through pixel (ix, grow) of the whole frame: what a camera prologue does once it has decoded
+// its pixel (k_prologue_camera from the tile queue, k_prologue_aa_list of lt_aa_adaptive.hpp from a list of pixels).
 template <typename T>
-__global__ void __launch_bounds__(256) k_prologue_camera(CamConsts c, MetricConsts m,
-                                                         typename Vec4<T>::type *__restrict__ ic, int64_t n_q)
+__device__ __forceinline__ void store_camera_ray(const CamConsts &c, const MetricConsts &m, typename Vec4<T>::type *ic,
+                                                 int64_t q, int ix, int grow)
 {
-    int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (q >= n_q) return;
-    int ix, lrow, tile_row;
-    q_to_pixel(c, q, ix, lrow, tile_row);
-    if (ix >= c.W || lrow >= c.trace_rows) { store_ic<T>(ic, q, 0, 0, 0, FLAG_PAD); return; }
-    int grow = tile_to_global_row(c, tile_row, lrow);
     double alpha, theta = 0.0;
     if (m.kind == 0) alpha = pixel_alpha(c, ix, grow); // a spherically symmetric metric never looks at theta
     else pixel_angles(c, ix, grow, alpha, theta);
@@ -273,6 +267,19 @@ __global__ void __launch_bounds__(256) k_prologue_camera(CamConsts c, MetricCons
         if (kerr_initial_momenta(m, alpha, theta, p_r, p_th, p_phi)) flags |= FLAG_OK;
         store_ic<T>(ic, q, p_r, p_th, p_phi, flags);
     }
+}
+
+// ---- K1: camera prologue -------------------------------------------------------------------
+template <typename T>
+__global__ void __launch_bounds__(256) k_prologue_camera(CamConsts c, MetricConsts m,
+                                                         typename Vec4<T>::type *__restrict__ ic, int64_t n_q)
+{
+    int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (q >= n_q) return;
+    int ix, lrow, tile_row;
+    q_to_pixel(c, q, ix, lrow, tile_row);
+    if (ix >= c.W || lrow >= c.trace_rows) { store_ic<T>(ic, q, 0, 0, 0, FLAG_PAD); return; }
+    store_camera_ray<T>(c, m, ic, q, ix, tile_to_global_row(c, tile_row, lrow));
 }
 
 // ---- K1': prologue for caller-supplied (alpha, theta, refine) arrays (batch twins) ---------

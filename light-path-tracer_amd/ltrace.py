@@ -250,6 +250,11 @@ def _np_ptr(a):
     return None if a is None else C.c_void_p(a.ctypes.data)
 
 
+def _p(x):
+    """A device address given as an integer (tensor.data_ptr()); 0 = NULL."""
+    return C.c_void_p(x) if x else None
+
+
 def _out(a, dtype, n, name):
     if a is None:
         return None
@@ -539,20 +544,19 @@ def render_dev(cam, metric, opts, d_bg=0, bg_channels=3, d_fa=0, d_w=0, d_status
                d_stats=0):
     """Device-pointer frame render (lt_render_dev); pointers are integers (tensor.data_ptr()), 0 = NULL.
     Asynchronous on opts.stream."""
-    p = lambda x: C.c_void_p(x) if x else None
-    _check(load().lt_render_dev(C.byref(cam), C.byref(metric), C.byref(opts), p(d_bg), bg_channels, p(d_fa), p(d_w),
-                                p(d_status), p(d_steps), p(d_rgb), p(d_rgba), p(d_stats)))
+    _check(load().lt_render_dev(C.byref(cam), C.byref(metric), C.byref(opts), _p(d_bg), bg_channels, _p(d_fa), _p(d_w),
+                                _p(d_status), _p(d_steps), _p(d_rgb), _p(d_rgba), _p(d_stats)))
 
 
 def scatter_rows_dev(d_part, d_full, height, width, elem_bytes, row_block, n_parts, part, stream=0):
     _check(load().lt_scatter_rows_dev(C.c_void_p(d_part), C.c_void_p(d_full), height, width, elem_bytes, row_block,
-                                      n_parts, part, C.c_void_p(stream) if stream else None))
+                                      n_parts, part, _p(stream)))
 
 
 def scatter_rows_indexed_dev(d_rows, d_full, d_row_index, n_rows, height, row_bytes, stream=0):
     """Source row i (device, row_bytes each) -> row d_row_index[i] (device int64) of the full frame; one launch."""
     _check(load().lt_scatter_rows_indexed_dev(C.c_void_p(d_rows), C.c_void_p(d_full), C.c_void_p(d_row_index), n_rows, height,
-                                              row_bytes, C.c_void_p(stream) if stream else None))
+                                              row_bytes, _p(stream)))
 
 
 def timing_collect():
@@ -571,7 +575,7 @@ def ic_reuse_counts():
 
 def release_stream(stream_ptr):
     """Free the library's buffers of (current device, stream) -- before the stream is destroyed."""
-    _check(load().lt_release_stream(C.c_void_p(stream_ptr) if stream_ptr else None))
+    _check(load().lt_release_stream(_p(stream_ptr)))
 
 
 def shutdown():
@@ -630,9 +634,8 @@ def render_disk(cam, metric, opts, disk, background=None,
 def render_disk_dev(cam, metric, opts, disk, d_bg=0, bg_channels=3, d_fa=0, d_w=0, d_status=0, d_steps=0, d_disk=0,
                     d_rgb=0, d_rgba=0, d_stats=0):
     """Device-pointer form of render_disk (lt_render_disk_dev); pointers are integers, 0 = NULL.  Asynchronous."""
-    p = lambda x: C.c_void_p(x) if x else None
-    _check(load().lt_render_disk_dev(C.byref(cam), C.byref(metric), C.byref(opts), C.byref(disk), p(d_bg), bg_channels,
-                                     p(d_fa), p(d_w), p(d_status), p(d_steps), p(d_disk), p(d_rgb), p(d_rgba), p(d_stats)))
+    _check(load().lt_render_disk_dev(C.byref(cam), C.byref(metric), C.byref(opts), C.byref(disk), _p(d_bg), bg_channels,
+                                     _p(d_fa), _p(d_w), _p(d_status), _p(d_steps), _p(d_disk), _p(d_rgb), _p(d_rgba), _p(d_stats)))
 
 
 def trace_batch_kerr_disk(M, a, r_obs, alphas, thetas, theta_obs, lambda_max, disk, axis_refines=None,
@@ -700,10 +703,9 @@ def render_disk_images_dev(cam, metric, opts, disk, max_images=3, d_bg=0, bg_cha
                            d_steps=0, d_images=0, d_n_hits=0, d_rgb=0, d_rgba=0, d_stats=0):
     """Device-pointer form of render_disk_images (lt_render_disk_images_dev); pointers are integers, 0 = NULL.
     Asynchronous."""
-    p = lambda x: C.c_void_p(x) if x else None
     _check(load().lt_render_disk_images_dev(C.byref(cam), C.byref(metric), C.byref(opts), C.byref(disk), int(max_images),
-                                            p(d_bg), bg_channels, p(d_fa), p(d_w), p(d_status), p(d_steps), p(d_images),
-                                            p(d_n_hits), p(d_rgb), p(d_rgba), p(d_stats)))
+                                            _p(d_bg), bg_channels, _p(d_fa), _p(d_w), _p(d_status), _p(d_steps), _p(d_images),
+                                            _p(d_n_hits), _p(d_rgb), _p(d_rgba), _p(d_stats)))
 
 
 def trace_batch_kerr_disk_images(M, a, r_obs, alphas, thetas, theta_obs, lambda_max, disk, max_images=3,
@@ -739,15 +741,19 @@ def trace_batch_kerr_disk_images(M, a, r_obs, alphas, thetas, theta_obs, lambda_
 AA_MODES = {"plain": AA_PLAIN, "disk": AA_DISK, "disk_images": AA_DISK_IMAGES}
 
 
-def default_aa(**kw):
-    """lt_aa with the library's defaults (samples = 2, plain mode, 3 images, automatic bands); keywords override."""
-    a = AA()
-    load().lt_default_aa(C.byref(a))
+def _aa_keywords(a, kw):
     for k, v in kw.items():
         if k == "mode" and isinstance(v, str):
             v = AA_MODES[v]
         setattr(a, k, v)
     return a
+
+
+def default_aa(**kw):
+    """lt_aa with the library's defaults (samples = 2, plain mode, 3 images, automatic bands); keywords override."""
+    a = AA()
+    load().lt_default_aa(C.byref(a))
+    return _aa_keywords(a, kw)
 
 
 def _fine_background(cam, samples, background):
@@ -763,6 +769,24 @@ def _fine_background(cam, samples, background):
     return bg, nch, bg.ndim == 2
 
 
+def _aa_render(fn, cam, metric, opts, aa, disk, rows, bgs, nch, gray, want, planes):
+    """The host-pointer call fn of render_aa / render_aa_adaptive: 'rgb', 'rgba' and the uint8 `planes` (name -> trailing
+    shape, in the call's order) that `want` names, in pinned memory, and 'stats' with the disk's counters; and the
+    call's Stats."""
+    out = _frame_outputs(rows, cam.width, nch, gray, [w for w in want if w in ("rgb", "rgba")])
+    for name, tail in planes.items():
+        if name in want:
+            out[name] = pinned_empty((rows, cam.width) + tail, np.uint8)
+    st = Stats()
+    _check(fn(C.byref(cam), C.byref(metric), C.byref(opts), C.byref(aa), None if disk is None else C.byref(disk),
+              *[_np_ptr(bg) for bg in bgs], nch, _np_ptr(out.get("rgb")), _np_ptr(out.get("rgba")),
+              *[_np_ptr(out.get(name)) for name in planes], C.byref(st)))
+    out["stats"] = stats_dict(st.counters, st.prologue_ms, st.integrate_ms, st.epilogue_ms)
+    out["stats"]["disk"] = int(st.counters[STAT_DISK])
+    out["stats"]["disk_hits"] = int(st.counters[STAT_DISK_HITS])
+    return out, st
+
+
 def render_aa(cam, metric, opts, aa, disk=None, background=None, want=("rgb", "rgba", "cover")):
     """Host-pointer supersampled frame (lt_render_aa): aa.samples^2 rays per pixel, resolved on the GPU.  background:
     the FINE-size image (H * samples, W * samples[, 3]) or None.  disk: an ltrace.Disk for the disk modes.  Returns
@@ -770,25 +794,15 @@ def render_aa(cam, metric, opts, aa, disk=None, background=None, want=("rgb", "r
     invalid / on the disk) in pinned memory, and 'stats' (the fine frame's counters; kernel times summed over bands)."""
     rows = _frame_rows(cam, opts)
     bg, nch, gray = _fine_background(cam, int(aa.samples), background)
-    out = _frame_outputs(rows, cam.width, nch, gray, [w for w in want if w in ("rgb", "rgba")])
-    if "cover" in want:
-        out["cover"] = pinned_empty((rows, cam.width, 4), np.uint8)
-    st = Stats()
-    _check(load().lt_render_aa(C.byref(cam), C.byref(metric), C.byref(opts), C.byref(aa),
-                               None if disk is None else C.byref(disk), _np_ptr(bg), nch, _np_ptr(out.get("rgb")),
-                               _np_ptr(out.get("rgba")), _np_ptr(out.get("cover")), C.byref(st)))
-    out["stats"] = stats_dict(st.counters, st.prologue_ms, st.integrate_ms, st.epilogue_ms)
-    out["stats"]["disk"] = int(st.counters[STAT_DISK])
-    out["stats"]["disk_hits"] = int(st.counters[STAT_DISK_HITS])
-    return out
+    return _aa_render(load().lt_render_aa, cam, metric, opts, aa, disk, rows, [bg], nch, gray, want,
+                      {"cover": (4,)})[0]
 
 
 def render_aa_dev(cam, metric, opts, aa, disk=None, d_bg=0, bg_channels=3, d_rgb=0, d_rgba=0, d_cover=0, d_stats=0):
     """Device-pointer form of render_aa (lt_render_aa_dev); pointers are integers, 0 = NULL.  Asynchronous."""
-    p = lambda x: C.c_void_p(x) if x else None
     _check(load().lt_render_aa_dev(C.byref(cam), C.byref(metric), C.byref(opts), C.byref(aa),
-                                   None if disk is None else C.byref(disk), p(d_bg), bg_channels, p(d_rgb), p(d_rgba),
-                                   p(d_cover), p(d_stats)))
+                                   None if disk is None else C.byref(disk), _p(d_bg), bg_channels, _p(d_rgb), _p(d_rgba),
+                                   _p(d_cover), _p(d_stats)))
 
 
 def aa_band_bytes(cam, metric, opts, aa, disk=None):
@@ -808,11 +822,7 @@ def default_aa_adaptive(**kw):
     bands and chunks, contrast = 0.0625); keywords override."""
     a = AAAdaptive()
     load().lt_default_aa_adaptive(C.byref(a))
-    for k, v in kw.items():
-        if k == "mode" and isinstance(v, str):
-            v = AA_MODES[v]
-        setattr(a, k, v)
-    return a
+    return _aa_keywords(a, kw)
 
 
 def render_aa_adaptive(cam, metric, opts, adaptive, disk=None, background_lo=None, background_hi=None,
@@ -829,19 +839,8 @@ def render_aa_adaptive(cam, metric, opts, adaptive, disk=None, background_lo=Non
     bg_hi, nch_hi, gray_hi = _fine_background(cam, int(adaptive.samples_hi), background_hi)
     if (nch, gray) != (nch_hi, gray_hi):
         raise ValueError("background_lo and background_hi differ in their channels")
-    out = _frame_outputs(rows, cam.width, nch, gray, [w for w in want if w in ("rgb", "rgba")])
-    if "cover" in want:
-        out["cover"] = pinned_empty((rows, cam.width, 4), np.uint8)
-    if "level" in want:
-        out["level"] = pinned_empty((rows, cam.width), np.uint8)
-    st = Stats()
-    _check(load().lt_render_aa_adaptive(C.byref(cam), C.byref(metric), C.byref(opts), C.byref(adaptive),
-                                        None if disk is None else C.byref(disk), _np_ptr(bg_lo), _np_ptr(bg_hi), nch,
-                                        _np_ptr(out.get("rgb")), _np_ptr(out.get("rgba")), _np_ptr(out.get("cover")),
-                                        _np_ptr(out.get("level")), C.byref(st)))
-    out["stats"] = stats_dict(st.counters, st.prologue_ms, st.integrate_ms, st.epilogue_ms)
-    out["stats"]["disk"] = int(st.counters[STAT_DISK])
-    out["stats"]["disk_hits"] = int(st.counters[STAT_DISK_HITS])
+    out, st = _aa_render(load().lt_render_aa_adaptive, cam, metric, opts, adaptive, disk, rows, [bg_lo, bg_hi], nch, gray,
+                         want, {"cover": (4,), "level": ()})
     out["stats"]["refined"] = int(st.counters[STAT_AA_REFINED])
     return out
 
@@ -850,10 +849,9 @@ def render_aa_adaptive_dev(cam, metric, opts, adaptive, disk=None, d_bg_lo=0, d_
                            d_cover=0, d_level=0, d_stats=0):
     """Device-pointer form of render_aa_adaptive (lt_render_aa_adaptive_dev); pointers are integers, 0 = NULL.  Waits
     for opts.stream once, between the two passes."""
-    p = lambda x: C.c_void_p(x) if x else None
     _check(load().lt_render_aa_adaptive_dev(C.byref(cam), C.byref(metric), C.byref(opts), C.byref(adaptive),
-                                            None if disk is None else C.byref(disk), p(d_bg_lo), p(d_bg_hi), bg_channels,
-                                            p(d_rgb), p(d_rgba), p(d_cover), p(d_level), p(d_stats)))
+                                            None if disk is None else C.byref(disk), _p(d_bg_lo), _p(d_bg_hi), bg_channels,
+                                            _p(d_rgb), _p(d_rgba), _p(d_cover), _p(d_level), _p(d_stats)))
 
 
 def aa_adaptive_plan(cam, metric, opts, adaptive, disk=None):
