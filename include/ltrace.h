@@ -324,8 +324,12 @@ int lt_rhs8_probe(const lt_metric *metric, const double *states, int64_t n, doub
  * annulus do not stop the ray.  The crossing point is the root of theta = pi/2 on the cubic Hermite interpolant  *
  * of the step in lambda (derivatives from the Kerr right-hand side at both ends); r, phi and the momenta are    *
  * interpolated on the same cubic.  A step that both crosses the disk and ends the ray by capture or escape is     *
- * tested between the previous state and the step's terminal (interpolated) state: the disk wins if the crossing  *
- * lies on that segment.  The ray then ends with status LT_STATUS_DISK.                                           *
+ * tested between the previous state and the step's terminal (interpolated) state: the sign change is looked for  *
+ * between those two, the crossing point is the root on the cubic of the FULL step (under DP45 the full step is   *
+ * retaken as one RK4 step of the same length: DP45's own end state is gone by then), and the disk wins if the    *
+ * root lies at or before the fraction of the step at which the ray ended: the capture / escape radius on the     *
+ * chord in r of that full step (under DP45 the retaken step's chord, within the step's error of DP45's own).     *
+ * The ray then ends with status LT_STATUS_DISK.                                                                  *
  *                                                                                                               *
  * Redshift: the camera's ray has E = -p_t = 1 and xi = p_phi; it stands for the photon the camera receives (the   *
  * convention of the background lookup), so g = nu_obs / nu_em = 1 / (u^t (1 - Omega xi)), in float64.           *

@@ -128,9 +128,9 @@ __device__ __forceinline__ int disk_advance(const KerrConsts<T> &k, const DiskCo
             T t_end = T(1);
             if (ev == EV_CAPTURED || ev == EV_ESCAPED) {
                 // the integrator ended the ray on the chord of this step at the capture / escape radius: retake the full
-                // step (for RK4 the same step; for DP45 an RK4 step of the same length stands in, near enough to place a
-                // crossing that in practice never happens there: r_in >= r_isco lies well outside 1.01 r_plus) and search
-                // up to the chord fraction the ray ended at
+                // step (for RK4 the same step; for DP45 an RK4 step of the same length stands in, DP45's own end state
+                // being gone) and search up to the fraction at which that step's chord in r meets the radius.  Rare, not
+                // absent: at a = 0.998 (r_isco = 1.237, capture at 1.074) an h = 0.1 capture step can cross the annulus
                 y1 = kerr_rk4_step(k, rc, before.y, h);
                 const T target = ev == EV_CAPTURED ? k.r_capture : k.r_escape;
                 const T denom = y1.r - before.y.r;

@@ -396,15 +396,147 @@ static int kerr_extract_angle(const real *state, real p_t, real p_phi, real M, r
 static real rmax(real a, real b) { return a > b ? a : b; }
 static real rmin(real a, real b) { return a < b ? a : b; }
 
+/* ------------------------------------------------------------------------ */
+/* Disk twin: the hit rule of include/ltrace.h ("thin Keplerian accretion    */
+/* disk", "optically thin disk") applied to the accepted steps of the two    */
+/* tracers below.  This project's own definition, not a restatement of the   */
+/* reference (which has no disk).  Written from the header's text: every     */
+/* accepted step is tested, there is no radius pre-filter, and the root is   */
+/* found by plain bisection.  The hook only looks at the states; a tracer    */
+/* called without it (hk == NULL) runs the arithmetic it always ran.         */
+/* ------------------------------------------------------------------------ */
+#define LTO_DISK_NC 13 /* doubles per recorded plane crossing, see lto_trace_batch_kerr_disk */
+typedef struct disk_hook {
+    real M, a, r_plus, p_t, p_phi; /* p_t, p_phi: set by the tracer once the initial state exists */
+    real r_in, r_out;
+    real r_capture, r_escape; /* the tracers' terminal radii */
+    int opaque, max_images, is_dp45;
+    int n_hits;
+    real *images;        /* (max_images, 2): r, phi (unwrapped) of the stored hits */
+    int step;            /* accepted steps so far */
+    int n_cross, max_cross, k_path; /* recorded crossings; crossings on the ray's path so far */
+    real *cross;         /* (max_cross, LTO_DISK_NC) */
+    real graze, gscale;  /* min over turning points of |theta - pi/2| e^(-pi k); e^(-pi k) */
+    real hit[5];         /* opaque: the state the ray ended in */
+    uint32_t evals_hit;  /* opaque: the integrator's evaluations up to and including the hit's step */
+} disk_hook;
+
+static real herm(real y0, real hd0, real y1, real hd1, real t)
+{
+    real t2 = t * t, t3 = t2 * t;
+    return (R(2.0) * t3 - R(3.0) * t2 + R(1.0)) * y0 + (t3 - R(2.0) * t2 + t) * hd0
+         + (R(-2.0) * t3 + R(3.0) * t2) * y1 + (t3 - t2) * hd1;
+}
+static real herm_dt(real y0, real hd0, real y1, real hd1, real t)
+{
+    real t2 = t * t;
+    return (R(6.0) * t2 - R(6.0) * t) * y0 + (R(3.0) * t2 - R(4.0) * t + R(1.0)) * hd0
+         + (R(-6.0) * t2 + R(6.0) * t) * y1 + (R(3.0) * t2 - R(2.0) * t) * hd1;
+}
+
+/* One accepted step y0 -> y1 of length h.  terminal: 0, or -1 / 1 if the step also ended the ray by capture / escape at
+ * the fraction frac of its chord.  Returns 1 if the ray ends here (opaque disk, hit). */
+static int disk_step(disk_hook *d, const real *y0, const real *y1_in, real h, int terminal, real frac)
+{
+    const real HALF_PI = LTO_PI / R(2.0);
+    const uint32_t evals_keep = lto_evals; /* the hook's own evaluations are not the integrator's */
+    real y1[5];
+    for (int i = 0; i < 5; ++i) y1[i] = y1_in[i];
+    int step = d->step++;
+    /* the state the step left the ray in: the end of the step, or the terminal (interpolated) state */
+    real th_end = terminal ? y0[1] + frac * (y1[1] - y0[1]) : y1[1];
+    real z0 = y0[1] - HALF_PI, z1 = th_end - HALF_PI;
+    int cross = (z0 < R(0.0) && z1 >= R(0.0)) || (z0 > R(0.0) && z1 <= R(0.0));
+    int turn = (y0[4] < R(0.0) && y1[4] >= R(0.0)) || (y0[4] > R(0.0) && y1[4] <= R(0.0));
+    int ended = 0;
+    if (cross || turn) {
+        real f0[5], f1[5];
+        if (terminal && d->is_dp45 && cross) { /* the header: the full step is retaken as one RK4 step of the same length */
+            real k1[5], k2[5], k3[5], k4[5], tmp[5];
+            rk4_step_kerr(y0, h, d->p_t, d->p_phi, d->M, d->a, d->r_plus, k1, k2, k3, k4, tmp, y1);
+            /* ... and the fraction is the terminal radius on the retaken step's chord in r */
+            real denom = y1[0] - y0[0];
+            frac = (denom == R(0.0)) ? R(1.0)
+                 : clip_scalar(((terminal < 0 ? d->r_capture : d->r_escape) - y0[0]) / denom, R(0.0), R(1.0));
+        }
+        kerr_rhs(y0, d->p_t, d->p_phi, d->M, d->a, d->r_plus, f0);
+        kerr_rhs(y1, d->p_t, d->p_phi, d->M, d->a, d->r_plus, f1);
+        for (int i = 0; i < 5; ++i) { f0[i] *= h; f1[i] *= h; }
+        if (turn && !cross) {
+            /* theta turns inside the step: the extremum of the cubic, by bisection on its derivative */
+            real lo = R(0.0), hi = R(1.0);
+            real glo = herm_dt(y0[1], f0[1], y1[1], f1[1], lo);
+            for (int it = 0; it < 64; ++it) {
+                real mid = R(0.5) * (lo + hi);
+                real gm = herm_dt(y0[1], f0[1], y1[1], f1[1], mid);
+                if ((gm < R(0.0)) == (glo < R(0.0)) && gm != R(0.0)) lo = mid; else hi = mid;
+            }
+            real t = R(0.5) * (lo + hi);
+            real rt = herm(y0[0], f0[0], y1[0], f1[0], t);
+            real zt = M_FABS(herm(y0[1], f0[1], y1[1], f1[1], t) - HALF_PI);
+            /* the smaller of the cubic's extremum and the two ends (the cubic's derivative may not change sign) */
+            zt = rmin(zt, rmin(M_FABS(z0), M_FABS(y1[1] - HALF_PI)));
+            if (rt >= d->r_in - R(1.0) && rt <= d->r_out + R(1.0) && (!terminal || t <= frac))
+                d->graze = rmin(d->graze, zt * d->gscale);
+        }
+        if (cross) {
+            real lo = R(0.0), hi = R(1.0), glo = z0;
+            for (int it = 0; it < 64; ++it) {
+                real mid = R(0.5) * (lo + hi);
+                real gm = herm(y0[1], f0[1], y1[1], f1[1], mid) - HALF_PI;
+                if ((gm < R(0.0)) == (glo < R(0.0)) && gm != R(0.0)) lo = mid; else hi = mid;
+            }
+            real t = R(0.5) * (lo + hi);
+            real c[5], fc[5];
+            for (int i = 0; i < 5; ++i) c[i] = herm(y0[i], f0[i], y1[i], f1[i], t);
+            c[1] = HALF_PI;
+            kerr_rhs(c, d->p_t, d->p_phi, d->M, d->a, d->r_plus, fc);
+            int on_path = !terminal || t <= frac;
+            int is_hit = on_path && c[0] >= d->r_in && c[0] <= d->r_out;
+            if (d->cross && d->n_cross < d->max_cross) {
+                real *o = d->cross + (size_t)d->n_cross * LTO_DISK_NC;
+                o[0] = (real)step; o[1] = t; o[2] = h; o[3] = y0[0]; o[4] = y1[0]; o[5] = c[0]; o[6] = c[2];
+                o[7] = M_FABS(fc[0] / fc[1]); o[8] = M_FABS(fc[2] / fc[1]);
+                o[9] = (real)terminal; o[10] = (real)on_path; o[11] = (real)is_hit; o[12] = frac;
+            }
+            d->n_cross++;
+            if (on_path) { d->k_path++; d->gscale *= R(0.04321391826377226); /* e^-pi */ }
+            if (is_hit) {
+                if (d->n_hits < d->max_images && d->images) {
+                    d->images[2 * d->n_hits] = c[0];
+                    d->images[2 * d->n_hits + 1] = c[2];
+                }
+                d->n_hits++;
+                if (d->opaque) {
+                    for (int i = 0; i < 5; ++i) d->hit[i] = c[i];
+                    d->evals_hit = evals_keep;
+                    ended = 1;
+                }
+            }
+        }
+    }
+    lto_evals = evals_keep;
+    return ended;
+}
+
+/* The opaque disk's end of a ray: status LT_STATUS_DISK, no final angle, the half orbits of phi at the hit. */
+static int disk_end(const disk_hook *d, real *fa_out, int64_t *nh_out)
+{
+    *fa_out = LTO_NAN;
+    *nh_out = (int64_t)floor_div(M_FABS(d->hit[2]), LTO_PI);
+    return 2;
+}
+
 /* metrics.py:419-567, production integrator (DP45, FSAL) */
-static int kerr_trace_dp45(real M, real a, real r_plus, real r_obs, real alpha, real theta,
-                           real theta_obs, real lambda_max, real h_max, int axis_refine,
-                           real *fa_out, int64_t *nh_out)
+static int kerr_trace_dp45_h(real M, real a, real r_plus, real r_obs, real alpha, real theta,
+                             real theta_obs, real lambda_max, real h_max, int axis_refine,
+                             real *fa_out, int64_t *nh_out, disk_hook *hk)
 {
     (void)h_max; /* unused by the reference as well */
     real state[5], p_t, p_phi;
     *fa_out = LTO_NAN; *nh_out = 0;
     if (!kerr_ic(M, a, r_obs, alpha, theta, theta_obs, state, &p_t, &p_phi)) return 0;
+    if (hk) { hk->p_t = p_t; hk->p_phi = p_phi; }
     real r_capture = r_plus * R(1.01);
     real r_escape = r_obs * R(2.0);
     real atol = axis_refine ? R(1e-10) : R(1e-8);
@@ -466,6 +598,7 @@ static int kerr_trace_dp45(real M, real a, real r_plus, real r_obs, real alpha, 
             real denom = r_next - r_prev;
             real frac = (denom == R(0.0)) ? R(1.0) : (r_capture - r_prev) / denom;
             frac = clip_scalar(frac, R(0.0), R(1.0));
+            if (hk && disk_step(hk, state, next_state, h, -1, frac)) return disk_end(hk, fa_out, nh_out);
             for (int i = 0; i < 5; ++i) state[i] = state[i] + frac * (next_state[i] - state[i]);
             lam += frac * h;
             event_status = -1;
@@ -475,11 +608,13 @@ static int kerr_trace_dp45(real M, real a, real r_plus, real r_obs, real alpha, 
             real denom = r_next - r_prev;
             real frac = (denom == R(0.0)) ? R(1.0) : (r_escape - r_prev) / denom;
             frac = clip_scalar(frac, R(0.0), R(1.0));
+            if (hk && disk_step(hk, state, next_state, h, 1, frac)) return disk_end(hk, fa_out, nh_out);
             for (int i = 0; i < 5; ++i) state[i] = state[i] + frac * (next_state[i] - state[i]);
             lam += frac * h;
             event_status = 1;
             break;
         }
+        if (hk && disk_step(hk, state, next_state, h, 0, R(1.0))) return disk_end(hk, fa_out, nh_out);
         for (int i = 0; i < 5; ++i) state[i] = next_state[i];
         for (int i = 0; i < 5; ++i) k1[i] = k7[i];
         lam += h;
@@ -491,13 +626,14 @@ static int kerr_trace_dp45(real M, real a, real r_plus, real r_obs, real alpha, 
 }
 
 /* metrics.py:570-658, fixed-step (radius-banded) RK4 -- the GPU fp32 kernel's spec */
-static int kerr_trace_rk4(real M, real a, real r_plus, real r_obs, real alpha, real theta,
-                          real theta_obs, real lambda_max, real h_max, int axis_refine,
-                          real *fa_out, int64_t *nh_out)
+static int kerr_trace_rk4_h(real M, real a, real r_plus, real r_obs, real alpha, real theta,
+                            real theta_obs, real lambda_max, real h_max, int axis_refine,
+                            real *fa_out, int64_t *nh_out, disk_hook *hk)
 {
     real state[5], p_t, p_phi;
     *fa_out = LTO_NAN; *nh_out = 0;
     if (!kerr_ic(M, a, r_obs, alpha, theta, theta_obs, state, &p_t, &p_phi)) return 0;
+    if (hk) { hk->p_t = p_t; hk->p_phi = p_phi; }
     real r_capture = r_plus * R(1.01);
     real r_escape = r_obs * R(2.0);
     real k1[5], k2[5], k3[5], k4[5], tmp[5], next_state[5];
@@ -527,6 +663,7 @@ static int kerr_trace_rk4(real M, real a, real r_plus, real r_obs, real alpha, r
             real denom = r_next - r_prev;
             real frac = (denom == R(0.0)) ? R(1.0) : (r_capture - r_prev) / denom;
             frac = clip_scalar(frac, R(0.0), R(1.0));
+            if (hk && disk_step(hk, state, next_state, h, -1, frac)) return disk_end(hk, fa_out, nh_out);
             for (int i = 0; i < 5; ++i) state[i] = state[i] + frac * (next_state[i] - state[i]);
             lam += frac * h;
             event_status = -1;
@@ -536,16 +673,35 @@ static int kerr_trace_rk4(real M, real a, real r_plus, real r_obs, real alpha, r
             real denom = r_next - r_prev;
             real frac = (denom == R(0.0)) ? R(1.0) : (r_escape - r_prev) / denom;
             frac = clip_scalar(frac, R(0.0), R(1.0));
+            if (hk && disk_step(hk, state, next_state, h, 1, frac)) return disk_end(hk, fa_out, nh_out);
             for (int i = 0; i < 5; ++i) state[i] = state[i] + frac * (next_state[i] - state[i]);
             lam += frac * h;
             event_status = 1;
             break;
         }
+        if (hk && disk_step(hk, state, next_state, h, 0, R(1.0))) return disk_end(hk, fa_out, nh_out);
         for (int i = 0; i < 5; ++i) state[i] = next_state[i];
         lam += h;
         if (!all_finite5(state)) return 0;
     }
     return kerr_extract_angle(state, p_t, p_phi, M, a, r_capture, event_status, fa_out, nh_out);
+}
+
+
+/* The plain tracers: the loops above without the disk hook. */
+static int kerr_trace_dp45(real M, real a, real r_plus, real r_obs, real alpha, real theta,
+                           real theta_obs, real lambda_max, real h_max, int axis_refine,
+                           real *fa_out, int64_t *nh_out)
+{
+    return kerr_trace_dp45_h(M, a, r_plus, r_obs, alpha, theta, theta_obs, lambda_max, h_max, axis_refine,
+                             fa_out, nh_out, NULL);
+}
+static int kerr_trace_rk4(real M, real a, real r_plus, real r_obs, real alpha, real theta,
+                          real theta_obs, real lambda_max, real h_max, int axis_refine,
+                          real *fa_out, int64_t *nh_out)
+{
+    return kerr_trace_rk4_h(M, a, r_plus, r_obs, alpha, theta, theta_obs, lambda_max, h_max, axis_refine,
+                            fa_out, nh_out, NULL);
 }
 
 /* ------------------------------------------------------------------------ */
@@ -608,6 +764,61 @@ int LTO_NAME(lto_trace_batch_kerr)(real M, real a, real r_obs, const real *alpha
         out_w[i] = nh;
         if (out_status) out_status[i] = (int8_t)s;
         if (out_evals) out_evals[i] = lto_evals;
+    }
+    return 0;
+}
+
+/* lto_trace_batch_kerr with the disk twin (see disk_hook above).  opaque != 0: the ray ends at its first hit (status 2,
+ * fa NaN, winding the half orbits of phi at the hit, evals up to and including the hit's step); otherwise it goes on and
+ * fa / winding / status / evals are lto_trace_batch_kerr's.  Per ray:
+ *   out_xi      p_phi of the ray (for the redshift g, which the caller forms);
+ *   out_images  (max_images, 2): r and UNWRAPPED phi of the first max_images hits, NaN in unused slots;
+ *   out_n_hits  every hit;  out_graze  min over the turning points of theta with r within 1 of the annulus of
+ *               |theta - pi/2| e^(-pi k), k = plane crossings before it (inf if none);
+ *   out_n_cross every sign change found;  out_cross (max_cross, LTO_DISK_NC), one row per sign change, hit or not:
+ *               step index, root t, step length h, r at the step's start, r at its end, r and phi of the crossing,
+ *               |r'/theta'| and |phi'/theta'| there, terminal (-1 capture, 1 escape, 0), on the ray's path (a terminal
+ *               step's root may lie beyond where the ray ended), hit, the terminal fraction.
+ * Any output but out_fa / out_w may be NULL. */
+int LTO_NAME(lto_trace_batch_kerr_disk)(real M, real a, real r_obs, const real *alphas, const real *thetas,
+                                        real theta_obs, real lambda_max, const uint8_t *axis_refines,
+                                        int integrator, int64_t n, real r_in, real r_out, int max_images,
+                                        int opaque, int max_cross, real *out_fa, int64_t *out_w,
+                                        int8_t *out_status, uint32_t *out_evals, real *out_xi, real *out_images,
+                                        int32_t *out_n_hits, real *out_graze, int32_t *out_n_cross,
+                                        real *out_cross)
+{
+    if (M_FABS(a) > M || max_images < 0 || max_cross < 0) return -1;
+    real r_plus = M + M_SQRT(M * M - a * a);
+#pragma omp parallel for schedule(dynamic, 64)
+    for (int64_t i = 0; i < n; ++i) {
+        real fa; int64_t nh;
+        disk_hook hk;
+        memset(&hk, 0, sizeof hk);
+        hk.M = M; hk.a = a; hk.r_plus = r_plus; hk.r_in = r_in; hk.r_out = r_out;
+        hk.r_capture = r_plus * R(1.01); hk.r_escape = r_obs * R(2.0);
+        hk.opaque = opaque; hk.max_images = max_images; hk.is_dp45 = integrator == 0;
+        hk.images = out_images ? out_images + (size_t)i * max_images * 2 : NULL;
+        hk.max_cross = max_cross;
+        hk.cross = out_cross ? out_cross + (size_t)i * max_cross * LTO_DISK_NC : NULL;
+        hk.graze = (real)INFINITY; hk.gscale = R(1.0);
+        if (hk.images) for (int j = 0; j < 2 * max_images; ++j) hk.images[j] = LTO_NAN;
+        if (hk.cross) for (int j = 0; j < max_cross * LTO_DISK_NC; ++j) hk.cross[j] = LTO_NAN;
+        lto_evals = 0;
+        int ar = axis_refines ? (axis_refines[i] != 0) : 0;
+        int s = integrator == 0
+            ? kerr_trace_dp45_h(M, a, r_plus, r_obs, alphas[i], thetas[i], theta_obs, lambda_max,
+                                R(1.0), ar, &fa, &nh, &hk)
+            : kerr_trace_rk4_h(M, a, r_plus, r_obs, alphas[i], thetas[i], theta_obs, lambda_max,
+                               R(1.0), ar, &fa, &nh, &hk);
+        out_fa[i] = (s == 1) ? fa : LTO_NAN;
+        out_w[i] = nh;
+        if (out_status) out_status[i] = (int8_t)s;
+        if (out_evals) out_evals[i] = s == 2 ? hk.evals_hit : lto_evals;
+        if (out_xi) out_xi[i] = hk.p_phi;
+        if (out_n_hits) out_n_hits[i] = hk.n_hits;
+        if (out_graze) out_graze[i] = hk.graze;
+        if (out_n_cross) out_n_cross[i] = hk.n_cross;
     }
     return 0;
 }

@@ -47,6 +47,12 @@ def lib():
                                            _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int8),
                                            C.POINTER(C.c_uint32)]
         L.lto_trace_batch_kerr.restype = C.c_int
+        L.lto_trace_batch_kerr_disk.argtypes = [C.c_double, C.c_double, C.c_double, _dp, _dp, C.c_double, C.c_double,
+                                                C.POINTER(C.c_uint8), C.c_int, C.c_int64, C.c_double, C.c_double,
+                                                C.c_int, C.c_int, C.c_int, _dp, C.POINTER(C.c_int64),
+                                                C.POINTER(C.c_int8), C.POINTER(C.c_uint32), _dp, _dp,
+                                                C.POINTER(C.c_int32), _dp, C.POINTER(C.c_int32), _dp]
+        L.lto_trace_batch_kerr_disk.restype = C.c_int
         L.lto_psi_frame.argtypes = [C.c_double, C.c_double, _dp, _dp, _dp, C.POINTER(C.c_int)]
         L.lto_psi_frame.restype = None
         L.lto_pixel_angles.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
@@ -183,6 +189,65 @@ def trace_batch_kerr(M, a, r_obs, alphas, thetas, theta_obs=np.pi / 2, lambda_ma
     if rc != 0:
         raise ValueError("oracle: |a| exceeds M")
     return fa, w, st, ev
+
+
+# columns of the 'cross' records of trace_batch_kerr_disk (LTO_DISK_NC doubles per plane crossing, lt_oracle.c)
+DISK_CROSS_FIELDS = ("step", "t", "h", "r0", "r1", "r", "phi", "s_r", "s_phi", "terminal", "on_path", "hit", "frac")
+
+
+def trace_batch_kerr_disk(M, a, r_obs, alphas, thetas, theta_obs, lambda_max, r_in, r_out, integrator, max_images,
+                          opaque, axis_refines=None, max_cross=24, redshift=None):
+    """The disk's step-exact twin: the hit rule of include/ltrace.h applied to the accepted steps of the oracle's own
+    RK4 ('rk4') / DP45 ('dp45') tracer, every step tested, the root by bisection (lt_oracle.c, disk_step).  float64.
+    opaque: the ray ends at its first hit (status 2, fa NaN, winding = half orbits of phi at the hit, rhs_evals up to
+    and including that step); otherwise the ray goes on and fa / winding / status / rhs_evals are trace_batch_kerr's.
+    redshift: the function g(M, a, r, xi); None: disk.redshift of the product package.  The twin's g is that closed form
+    of its own r by construction, so it checks where the hit lies, not the redshift formula.
+    -> dict(fa, winding, status, rhs_evals, xi (n,) (the ray's p_phi),
+            images (n, max_images, 3) (r, phi in [0, 2 pi), g = disk.redshift(M, a, r, xi)), NaN in unused slots,
+            n_hits (n,) i32 (every hit),
+            graze (n,): min over the turning points of theta with r within 1 of the annulus of |theta - pi/2| e^(-pi k),
+                        k = plane crossings before it (inf: none),
+            n_cross (n,) i32: sign changes of theta - pi/2 found,
+            cross (n, max_cross, 13): one row per sign change, hit or not, columns DISK_CROSS_FIELDS (NaN rows unused);
+                        'on_path' is 0 where a terminal step's root lies beyond the point the ray ended at)."""
+    if redshift is None:
+        import disk as diskmod  # the project's float64 statement of g (tests put the package directory on sys.path)
+        redshift = diskmod.redshift
+    al = np.ascontiguousarray(alphas, dtype=np.float64)
+    th = np.ascontiguousarray(thetas, dtype=np.float64)
+    n = al.size
+    ar = (np.zeros(n, dtype=np.uint8) if axis_refines is None
+          else np.ascontiguousarray(axis_refines).astype(np.uint8))
+    m, mc = int(max_images), int(max_cross)
+    fa = np.full(n, np.nan)
+    w = np.zeros(n, dtype=np.int64)
+    st = np.zeros(n, dtype=np.int8)
+    ev = np.zeros(n, dtype=np.uint32)
+    xi = np.zeros(n)
+    img = np.full((n, m, 2), np.nan)
+    nh = np.zeros(n, dtype=np.int32)
+    gz = np.full(n, np.inf)
+    nc = np.zeros(n, dtype=np.int32)
+    cr = np.full((n, mc, len(DISK_CROSS_FIELDS)), np.nan)
+    i32 = C.POINTER(C.c_int32)
+    rc = lib().lto_trace_batch_kerr_disk(M, a, r_obs, _ptr(al, _dp), _ptr(th, _dp), theta_obs, lambda_max,
+                                         _ptr(ar, C.POINTER(C.c_uint8)), 0 if integrator == "dp45" else 1, n,
+                                         float(r_in), float(r_out), m, int(bool(opaque)), mc, _ptr(fa, _dp),
+                                         _ptr(w, C.POINTER(C.c_int64)), _ptr(st, C.POINTER(C.c_int8)),
+                                         _ptr(ev, C.POINTER(C.c_uint32)), _ptr(xi, _dp), _ptr(img, _dp), _ptr(nh, i32),
+                                         _ptr(gz, _dp), _ptr(nc, i32), _ptr(cr, _dp))
+    if rc != 0:
+        raise ValueError("oracle: |a| exceeds M, or a negative count")
+    images = np.full((n, m, 3), np.nan)
+    images[..., 0] = img[..., 0]
+    two_pi = 2.0 * np.pi
+    ph = img[..., 1] - two_pi * np.floor(img[..., 1] / two_pi)
+    images[..., 1] = np.where((ph >= two_pi) | (ph < 0.0), 0.0, ph)
+    with np.errstate(invalid="ignore"):
+        images[..., 2] = redshift(M, a, img[..., 0], xi[:, None])
+    return dict(fa=fa, winding=w, status=st, rhs_evals=ev, xi=xi, images=images, n_hits=nh, graze=gz, n_cross=nc,
+                cross=cr)
 
 
 def psi_frame(psi):
