@@ -120,6 +120,8 @@ typedef struct lt_opts {
                                    /* (lt_render_disk_images_dev: rays with at least one hit)                          */
 #define LT_STAT_DISK_HITS 13       /* lt_render_disk_images_dev: hits of the optically thin disk, all rays              */
 #define LT_STAT_AA_REFINED 14      /* lt_render_aa_adaptive_dev: pixels that were refined (traced at samples_hi)         */
+#define LT_STAT_EQ_ITERS 15        /* integrate kernel, float32 RK4: those of LT_STAT_WAVE_ITERS that the far-field streak took in its
+                                      fixed-quadrant loop (lt_set_eq_streak); the only counter the switch changes               */
 #define LT_STAT_WORDS 16
 
 typedef struct lt_stats {
@@ -170,6 +172,17 @@ int lt_trace_batch_kerr(double M, double a, double r_obs, const double *alphas, 
                         double theta_obs, double lambda_max, const uint8_t *axis_refines,
                         int integrator, int precision, int schedule, int64_t n, double *out_fa,
                         int64_t *out_w, int8_t *out_status, uint32_t *out_rhs_evals);
+
+/* The float32 far-field streak's fixed-quadrant loop: on != 0 enables it, 0 disables it, for every Kerr
+ * launch enqueued afterwards (the default: on, or LT_EQ_STREAK=0/1 in the environment when the library is loaded).  It
+ * changes no output and no counter but LT_STAT_EQ_ITERS.  Returns the previous setting. */
+int lt_set_eq_streak(int on);
+
+/* Device probe of the float32 sincos for the tests: every float32 x with bit pattern in [bits_lo, bits_hi] goes through
+ * the general form and through the fixed-quadrant form.  out[0] = values compared, out[1] = values for which either
+ * result differs in any bit, out[2] = values that do not reduce to the quadrant k = 1, out[3] = bit pattern of the
+ * first (lowest) x that differs.  band[0..1] = the band (lo, hi) the streak uses. */
+int lt_sincos_q1_probe(uint32_t bits_lo, uint32_t bits_hi, uint64_t out[4], float band[2]);
 
 /* Device probe of the inlined Kerr right-hand side (metrics.py:221-303) for parity tests:
  * states (n,5) [r, theta, phi, p_r, p_theta], p_phi (n), out (n,5); host pointers, float64 I/O,

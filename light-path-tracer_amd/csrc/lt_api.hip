@@ -16,6 +16,7 @@
 
 #include <algorithm>
 #include <array>
+#include <atomic>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -291,6 +292,26 @@ static bool ic_reuse_enabled()
     return on;
 }
 
+// LT_EQ_STREAK=0 / lt_set_eq_streak(0): the float32 streak's fixed-quadrant loop is never entered (its band is empty), as
+// before it existed (A/B measurements, bisecting, tests/test_gpu_eq_streak.py).  Read by make_kerr for every launch.
+static std::atomic<int> g_eq_streak{-1}; // -1: not yet read from the environment
+static bool eq_streak_enabled()
+{
+    int v = g_eq_streak.load(std::memory_order_relaxed);
+    if (v < 0) {
+        v = env_int("LT_EQ_STREAK", 1) != 0;
+        int unset = -1;
+        if (!g_eq_streak.compare_exchange_strong(unset, v)) v = unset;
+    }
+    return v != 0;
+}
+extern "C" int lt_set_eq_streak(int on)
+{
+    const int before = eq_streak_enabled();
+    g_eq_streak.store(on != 0);
+    return before;
+}
+
 // Frames that reused the ray records of their slot / that ran k_prologue_camera, since the library was loaded.
 static uint64_t g_ic_hits = 0, g_ic_misses = 0; // (under g_mu)
 extern "C" void lt_ic_reuse_counts(uint64_t *hits, uint64_t *misses)
@@ -503,6 +524,10 @@ template <typename T> static KerrConsts<T> make_kerr(const MetricConsts &mc, dou
     k.lambda_max = (T)lambda_max;
     k.h_max = (T)h_max;
     k.rc4 = (T)(mc.r_capture * 4.0); k.rc2 = (T)(mc.r_capture * 2.0); k.rc12 = (T)(mc.r_capture * 1.2);
+    // the fixed-quadrant band of the float32 streak; empty (no angle is inside) with the switch off and for float64
+    const bool eq = sizeof(T) == 4 && eq_streak_enabled();
+    k.eq_lo = eq ? (T)M<float>::EQ_BAND_LO : (T)1;
+    k.eq_hi = eq ? (T)M<float>::EQ_BAND_HI : (T)0;
     return k;
 }
 
@@ -1471,6 +1496,40 @@ extern "C" int lt_kerr_rhs_probe(double M, double a, const double *states, const
     });
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(out, dout.p, n * 40, hipMemcpyDeviceToHost));
+    return LT_OK;
+}
+
+// Every float32 with bit pattern bits_lo + i, i < n, through both forms of M<float>::sincos; out as in lt_sincos_q1_probe.
+__global__ void k_sincos_q1_probe(uint32_t bits_lo, uint32_t n, unsigned long long *__restrict__ out)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t bits = bits_lo + i;
+    const float x = __uint_as_float(bits);
+    float s0, c0, s1, c1;
+    M<float>::sincos(x, s0, c0);
+    M<float>::sincos_q1(x, s1, c1);
+    if ((__float_as_uint(s0) != __float_as_uint(s1)) | (__float_as_uint(c0) != __float_as_uint(c1))) {
+        atomicAdd(&out[1], 1ull);
+        atomicMin(&out[3], (unsigned long long)bits);
+    }
+    if (__builtin_rintf(x * 0.636619772367581343f) != 1.0f) atomicAdd(&out[2], 1ull);
+}
+
+extern "C" int lt_sincos_q1_probe(uint32_t bits_lo, uint32_t bits_hi, uint64_t out[4], float band[2])
+{
+    int rc = require_device();
+    if (rc) return rc;
+    if (!out || bits_hi < bits_lo || bits_hi - bits_lo >= (1u << 30)) return fail(LT_ERR_INVALID_ARG, "bad sincos probe range");
+    const uint32_t n = bits_hi - bits_lo + 1;
+    DevBuf d;
+    if ((rc = d.alloc(4 * sizeof(uint64_t)))) return rc;
+    const uint64_t init[4] = {n, 0, 0, ~0ull};
+    HIP_TRY(hipMemcpy(d.p, init, sizeof(init), hipMemcpyHostToDevice));
+    k_sincos_q1_probe<<<(n + 255) / 256, 256>>>(bits_lo, n, (unsigned long long *)d.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(out, d.p, sizeof(init), hipMemcpyDeviceToHost));
+    if (band) { band[0] = M<float>::EQ_BAND_LO; band[1] = M<float>::EQ_BAND_HI; }
     return LT_OK;
 }
 

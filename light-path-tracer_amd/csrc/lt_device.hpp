@@ -17,6 +17,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+// functions a stand-alone host program can call as well (tools/scratch/eq_sincos_check.hip)
+#define LT_HD __host__ __device__ __forceinline__
+
 namespace lt {
 
 // true if the predicate holds in any active lane: the wave-uniform test behind every fast path.  The builtin
@@ -62,35 +65,53 @@ template <> struct M<float> {
     // sin^2 floored at 1e-15 (metrics.py:236-237): below float resolution unless sin^2 < 1e-8, so an
     // add does the job of the max without leaving the FMA pipe.
     static __device__ __forceinline__ float sin2_floor(float s) { return __builtin_fmaf(s, s, 1e-15f); }
-    // sin and cos of an angle of modest size (|x| < ~1e4; the polar angle of a ray stays within a
-    // few pi).  Cody-Waite reduction by pi/2 in three pieces, single-precision minimax polynomials
-    // on [-pi/4, pi/4], quadrant fix-up with integer ops: ~25 VALU ops for both values, ~1 ulp.
-    static __device__ __forceinline__ void sincos(float x, float &s, float &c)
+    // pi/2 split for the Cody-Waite reduction: 8 + 11 + 24 significant bits
+    static constexpr float PIO2_1 = 1.5703125f, PIO2_2 = 4.837512969970703125e-4f, PIO2_3 = 7.54978995489188e-8f;
+    // sin and cos of a reduced angle: single-precision minimax polynomials on [-pi/4, pi/4]
+    static LT_HD void sincos_reduced(float y, float &sy, float &cy)
     {
-        const float TWO_OVER_PI = 0.636619772367581343f;
-        const float P1 = 1.5703125f; // pi/2 split: 8 + 11 + 24 significant bits
-        const float P2 = 4.837512969970703125e-4f;
-        const float P3 = 7.54978995489188e-8f;
-        float kf = __builtin_rintf(x * TWO_OVER_PI);
-        float y = __builtin_fmaf(-kf, P1, x);
-        y = __builtin_fmaf(-kf, P2, y);
-        y = __builtin_fmaf(-kf, P3, y);
-        int k = (int)kf;
         float z = y * y;
         float ps = __builtin_fmaf(z, -1.9515295891e-4f, 8.3321608736e-3f);
         ps = __builtin_fmaf(ps, z, -1.6666654611e-1f);
-        float sy = __builtin_fmaf(ps * z, y, y);
+        sy = __builtin_fmaf(ps * z, y, y);
         float pc = __builtin_fmaf(z, 2.443315711809948e-5f, -1.388731625493765e-3f);
         pc = __builtin_fmaf(pc, z, 4.166664568298827e-2f);
-        float cy = __builtin_fmaf(pc * z, z, __builtin_fmaf(-0.5f, z, 1.0f));
+        cy = __builtin_fmaf(pc * z, z, __builtin_fmaf(-0.5f, z, 1.0f));
+    }
+    // sin and cos of an angle of modest size (|x| < ~1e4; the polar angle of a ray stays within a
+    // few pi).  Cody-Waite reduction by pi/2 in three pieces, the polynomials above, quadrant fix-up
+    // with integer ops: ~25 VALU ops for both values, ~1 ulp.
+    static LT_HD void sincos(float x, float &s, float &c)
+    {
+        const float TWO_OVER_PI = 0.636619772367581343f;
+        float kf = __builtin_rintf(x * TWO_OVER_PI);
+        float y = __builtin_fmaf(-kf, PIO2_1, x);
+        y = __builtin_fmaf(-kf, PIO2_2, y);
+        y = __builtin_fmaf(-kf, PIO2_3, y);
+        int k = (int)kf;
+        float sy, cy;
+        sincos_reduced(y, sy, cy);
         bool swap = k & 1;
         float ss = swap ? cy : sy;
         float cc = swap ? sy : cy;
         // sign: sin flips for k = 2,3 (mod 4), cos for k = 1,2
         uint32_t sbit = ((uint32_t)k << 30) & 0x80000000u;
         uint32_t cbit = ((uint32_t)(k + 1) << 30) & 0x80000000u;
-        s = __uint_as_float(__float_as_uint(ss) ^ sbit);
-        c = __uint_as_float(__float_as_uint(cc) ^ cbit);
+        s = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, ss) ^ sbit);
+        c = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, cc) ^ cbit);
+    }
+    // The same for an angle known to reduce to the quadrant k = 1 (x within pi/4 of pi/2; callers keep it inside
+    // [EQ_BAND_LO, EQ_BAND_HI]): no multiply by 2/pi, no rint, no quadrant logic -- 14 instructions for 28.  Bit-identical
+    // to sincos there: fma(-1, P, x) is x - P rounded once, k = 1 swaps the two polynomials, leaves the sine's sign and
+    // flips the cosine's (tools/scratch/eq_sincos_check.hip and tests/test_gpu_eq_streak.py compare every float32 of the band).
+    static constexpr float EQ_BAND_LO = 0.80f, EQ_BAND_HI = 2.34f; // strictly inside (pi/4, 3 pi/4) = (0.7854, 2.3562)
+    static LT_HD void sincos_q1(float x, float &s, float &c)
+    {
+        float y = ((x - PIO2_1) - PIO2_2) - PIO2_3;
+        float sy, cy;
+        sincos_reduced(y, sy, cy);
+        s = cy;
+        c = -sy;
     }
     // sin and cos of a SMALL angle (|d| <= 0.25): Taylor, 7 FMA-class instructions, error < 1.3e-8
     static __device__ __forceinline__ void sincos_small(float d, float &s, float &c)
@@ -162,6 +183,8 @@ template <> struct M<double> {
     static __device__ __forceinline__ double min(double a, double b) { return __builtin_fmin(a, b); }
     static __device__ __forceinline__ double sin2_floor(double s) { return __builtin_fmax(s * s, 1e-15); }
     static __device__ __forceinline__ void sincos(double x, double &s, double &c) { sincos_f64(x, s, c); }
+    // (float64 has no fixed-quadrant form: its streak never asks for one)
+    static __device__ __forceinline__ void sincos_q1(double x, double &s, double &c) { sincos_f64(x, s, c); }
     // |d| <= 0.25: Taylor to d^11 / d^12, error < 3e-18
     static __device__ __forceinline__ void sincos_small(double d, double &s, double &c)
     {
@@ -195,6 +218,7 @@ template <typename T> struct KerrConsts {
     T lambda_max;
     T h_max;       // 1.0 (metrics.py:677)
     T rc4, rc2, rc12; // r_capture * 4, * 2, * 1.2 (metrics.py:606-611)
+    T eq_lo, eq_hi;   // polar-angle band of the float32 streak's fixed-quadrant loop (kerr_rk4_streak); lo >= hi: never taken
 };
 
 // A VALU instruction with an SGPR source runs on the half-rate pipe on gfx950 (v_fma_f32 with an
@@ -380,14 +404,18 @@ template <typename T> struct State5 {
 // smallest stage radius and the largest stage offset instead, so that the caller can tell afterwards
 // whether either case occurred (then the unchecked result is wrong for that lane and must be replaced by
 // the checked one) -- one test per step instead of seven, for the same results.
-template <typename T, bool CHECKED>
+//
+// Q1 = true: the caller knows that y.th reduces to the quadrant k = 1 (M<T>::sincos_q1); same bits, fewer instructions.
+template <typename T, bool CHECKED, bool Q1 = false>
 __device__ __forceinline__ State5<T> kerr_rk4_step_impl(const KerrConsts<T> &k, const RayConsts<T> &rc,
                                                         const State5<T> &y, T h, T &min_r, T &max_d)
 {
     T k_r, k_th, k_ph, k_pr, k_pth;
     T a_r, a_th, a_ph, a_pr, a_pth; // running k1 + 2 k2 + 2 k3 + k4
     T s0, c0, s, c;
-    M<T>::sincos(y.th, s0, c0); // the only full sincos of the step; stages rotate it (sincos_shift)
+    // the only full sincos of the step; stages rotate it (sincos_shift)
+    if constexpr (Q1) M<T>::sincos_q1(y.th, s0, c0);
+    else M<T>::sincos(y.th, s0, c0);
     kerr_rhs_sc<T, CHECKED>(k, rc, y.r, s0, c0, y.pr, y.pth, k_r, k_th, k_ph, k_pr, k_pth);
     a_r = k_r; a_th = k_th; a_ph = k_ph; a_pr = k_pr; a_pth = k_pth;
     T hh = T(0.5) * h;
@@ -434,11 +462,11 @@ __device__ __forceinline__ State5<T> kerr_rk4_step(const KerrConsts<T> &k, const
 }
 
 // The branch-free variant; valid for a lane iff min_r > k.r_cut and max_d <= 0.25 (kerr_rk4_step_ok).
-template <typename T>
+template <typename T, bool Q1 = false>
 __device__ __forceinline__ State5<T> kerr_rk4_step_fast(const KerrConsts<T> &k, const RayConsts<T> &rc,
                                                         const State5<T> &y, T h, T &min_r, T &max_d)
 {
-    return kerr_rk4_step_impl<T, false>(k, rc, y, h, min_r, max_d);
+    return kerr_rk4_step_impl<T, false, Q1>(k, rc, y, h, min_r, max_d);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -592,14 +620,14 @@ template <> struct StepCarry<float, true> {
     }
 };
 
-// LONE = true: the packed form where there is one (float32); the scalar step otherwise
-template <typename T, bool LONE>
+// LONE = true: the packed form where there is one (float32); the scalar step otherwise (Q1: its fixed-quadrant form)
+template <typename T, bool LONE, bool Q1 = false>
 __device__ __forceinline__ State5<T> kerr_rk4_step_fast_for(const KerrConsts<T> &k, const RayConsts<T> &rc, const State5<T> &y,
                                                             const StepCarry<T, LONE> &cin, T h, T &min_r, T &max_d,
                                                             StepCarry<T, LONE> &cout)
 {
     if constexpr (LONE && sizeof(T) == 4) return kerr_rk4_step_fast_pk(k, rc, y, cin.cs, h, min_r, max_d, cout.cs);
-    else return kerr_rk4_step_fast(k, rc, y, h, min_r, max_d);
+    else return kerr_rk4_step_fast<T, Q1>(k, rc, y, h, min_r, max_d);
 }
 
 // Step-size rule of the reference's fixed-step RK4 tracer (metrics.py:597-611): h_base, capped in
@@ -648,28 +676,45 @@ template <typename T> __device__ __forceinline__ void ray_start(const KerrConsts
 // it holds keep the step -- lanes are independent, they need not stay in lockstep.  Same arithmetic as the
 // general iteration (kerr_rk4_step_fast, same h), so which of the two paths took a step does not matter.
 // Returns the number of loop iterations (wave-uniform).  LONE: the wave is alone on its SIMD (packed step, above).
-template <typename T, bool LONE = false>
-__device__ __forceinline__ uint32_t kerr_rk4_streak(const KerrConsts<T> &k, const RayConsts<T> &rc, RayState<T> &s,
-                                                    uint32_t max_steps)
+//
+// The loop exists twice.  The camera of a frame sits on or near the equator by default and a ray's polar angle stays
+// within its orbital plane's inclination of pi/2, so most far-field steps start with every lane's angle inside
+// (pi/4, 3 pi/4), where the step's one full sincos needs neither its quadrant logic nor the multiply and rint that
+// find the quadrant (M<float>::sincos_q1: 14 instructions for 28, same bits).  Which loop runs is decided ONCE per
+// call, on the state the streak starts from: if every active lane's angle is inside (k.eq_lo, k.eq_hi), the
+// fixed-quadrant loop (EQ) runs, and `angle still inside the band` joins its continue condition -- tested on the NEW
+// angle, which is the next step's base angle.  Nothing inside a step branches on it.  A lane whose step was ordinary
+// but left the band keeps the step like any other (the selects on leaving look at `good` alone), and the call goes on
+// in the general loop with what is left of max_steps: the wave takes the same attempts in the same order as with the
+// band empty (k.eq_lo >= k.eq_hi: the switch, lt_set_eq_streak), each lane through the same arithmetic with the same
+// h, so no output and no counter but `eq_done` can tell the two loops apart.  Float32, scalar step only: float64 and
+// the packed lone-wave step run the general loop.
+// `eq_done` += the attempts made in the fixed-quadrant loop (wave-uniform).
+
+// The loop itself.  EQ: the fixed-quadrant form.  `done` counts attempts.  True if the loop left before max_steps
+// attempts although every lane's last attempt was ordinary (EQ: some lane left the band; never without EQ).
+template <typename T, bool LONE, bool EQ>
+__device__ __forceinline__ bool kerr_rk4_streak_loop(const KerrConsts<T> &k, const RayConsts<T> &rc, RayState<T> &s,
+                                                     uint32_t max_steps, uint32_t &done)
 {
-    if (wave_any(!((s.y.r >= k.rc4) & (s.h_retry == T(0))))) return 0;
-    uint32_t done = 0;
     // One attempt: from state `from` at affine parameter lam into `to`; true if it was an ordinary far-field step.
     // (predicates are combined with & and |, not && and ||: short-circuit evaluation would turn them into branches)
     // The streak only takes FULL base steps: h = h_base needs remaining >= h_base, i.e. lam <= lambda_max - h_base
     // (the tracer's h = min(h_base, remaining) is then h_base exactly).  A ray within one base step of the range end
     // fails the test and takes its last, shorter step in the general iteration.  With h invariant the step's h / 2 and
     // h / 6, the subtraction and the min leave the loop.
+    // in_band: with EQ, the other half of the continue condition -- the new angle is inside the band.
     const T lam_limit = k.lambda_max - rc.hb;
     auto attempt = [&](const State5<T> &from, const StepCarry<T, LONE> &cfrom, T lam, State5<T> &to, StepCarry<T, LONE> &cto, T &h) -> bool {
         h = rc.hb;
         T min_r, max_d;
-        to = kerr_rk4_step_fast_for<T, LONE>(k, rc, from, cfrom, h, min_r, max_d, cto);
+        to = kerr_rk4_step_fast_for<T, LONE, EQ>(k, rc, from, cfrom, h, min_r, max_d, cto);
         T mag = M<T>::abs(to.r) + M<T>::abs(to.th) + M<T>::abs(to.ph) + M<T>::abs(to.pr) + M<T>::abs(to.pth);
         ++done;
         return (lam <= lam_limit) & M<T>::finite(mag) & (to.r >= k.rc4) & (to.r < k.r_escape) & (min_r > k.r_cut) &
                !(max_d > T(0.25));
     };
+    auto in_band = [&](T th) -> bool { return !EQ | ((th > k.eq_lo) & (th < k.eq_hi)); };
     // The state ping-pongs between two register sets (A = s.y, B) so that accepting an attempt costs no copies:
     // the loop body is two attempts, A -> B and B -> A, each followed by the one wave-uniform test.  On leaving,
     // a lane keeps the attempted state if its own predicate held, its previous state otherwise.
@@ -679,26 +724,46 @@ __device__ __forceinline__ uint32_t kerr_rk4_streak(const KerrConsts<T> &k, cons
     T h;
     for (;;) {
         bool good = attempt(s.y, ca, s.lam, b, cb, h);
-        if (!wave_all(good) | (done >= max_steps)) {
+        if (!wave_all(good & in_band(b.th)) | (done >= max_steps)) {
             s.y.r = good ? b.r : s.y.r; s.y.th = good ? b.th : s.y.th; s.y.ph = good ? b.ph : s.y.ph;
             s.y.pr = good ? b.pr : s.y.pr; s.y.pth = good ? b.pth : s.y.pth;
             s.lam = good ? s.lam + h : s.lam;
             s.steps += good ? 1u : 0u;
-            break;
+            return EQ && wave_all(good) & (done < max_steps);
         }
         s.lam += h;
         ++s.steps;
         good = attempt(b, cb, s.lam, s.y, ca, h);
-        if (!wave_all(good) | (done >= max_steps)) {
+        if (!wave_all(good & in_band(s.y.th)) | (done >= max_steps)) {
             s.y.r = good ? s.y.r : b.r; s.y.th = good ? s.y.th : b.th; s.y.ph = good ? s.y.ph : b.ph;
             s.y.pr = good ? s.y.pr : b.pr; s.y.pth = good ? s.y.pth : b.pth;
             s.lam = good ? s.lam + h : s.lam;
             s.steps += good ? 1u : 0u;
-            break;
+            return EQ && wave_all(good) & (done < max_steps);
         }
         s.lam += h;
         ++s.steps;
     }
+}
+
+template <typename T, bool LONE = false>
+__device__ __forceinline__ uint32_t kerr_rk4_streak(const KerrConsts<T> &k, const RayConsts<T> &rc, RayState<T> &s,
+                                                    uint32_t max_steps, uint32_t &eq_done)
+{
+    if (wave_any(!((s.y.r >= k.rc4) & (s.h_retry == T(0))))) return 0;
+    uint32_t done = 0, eq = 0;
+    bool more = true;
+    if constexpr (!LONE && sizeof(T) == 4) {
+        if (wave_all((s.y.th > k.eq_lo) & (s.y.th < k.eq_hi))) {
+            more = kerr_rk4_streak_loop<T, LONE, true>(k, rc, s, max_steps, done);
+            eq = done;
+        }
+    }
+    if (more) kerr_rk4_streak_loop<T, LONE, false>(k, rc, s, max_steps, done);
+#ifdef LT_EQ_COUNT_ALL // diagnostic build: count EVERY attempt of the scalar float32 streak (the eligible fraction's denominator)
+    if constexpr (!LONE && sizeof(T) == 4) eq = done;
+#endif
+    eq_done += eq;
     return done;
 }
 

@@ -25,15 +25,18 @@ template <typename T> struct Rk4 {
     {
         return kerr_rk4_advance(k, rc, s);
     }
-    // up to max_steps ordinary far-field steps for the whole wave at one branch per step; returns how many
-    static __device__ __forceinline__ uint32_t streak(const KerrConsts<T> &k, const RayConsts<T> &rc, State &s, uint32_t max_steps)
+    // up to max_steps ordinary far-field steps for the whole wave at one branch per step; returns how many, and adds to
+    // eq_done those taken in the streak's fixed-quadrant loop
+    static __device__ __forceinline__ uint32_t streak(const KerrConsts<T> &k, const RayConsts<T> &rc, State &s, uint32_t max_steps,
+                                                      uint32_t &eq_done)
     {
-        return kerr_rk4_streak(k, rc, s, max_steps);
+        return kerr_rk4_streak(k, rc, s, max_steps, eq_done);
     }
     // the same for a wavefront that is alone on its SIMD (ghost-lane phase of the integrate kernels)
     static __device__ __forceinline__ uint32_t streak_lone(const KerrConsts<T> &k, const RayConsts<T> &rc, State &s, uint32_t max_steps)
     {
-        return kerr_rk4_streak<T, true>(k, rc, s, max_steps);
+        uint32_t none = 0; // (the lone-wave form has no fixed-quadrant loop)
+        return kerr_rk4_streak<T, true>(k, rc, s, max_steps, none);
     }
 };
 
@@ -88,7 +91,7 @@ template <typename T, bool EXACT_CTRL = false> struct Dp45 {
         s.steps = 0;
     }
 
-    static __device__ __forceinline__ uint32_t streak(const KerrConsts<T> &, const RayConsts<T> &, State &, uint32_t) { return 0; }
+    static __device__ __forceinline__ uint32_t streak(const KerrConsts<T> &, const RayConsts<T> &, State &, uint32_t, uint32_t &) { return 0; }
     static __device__ __forceinline__ uint32_t streak_lone(const KerrConsts<T> &, const RayConsts<T> &, State &, uint32_t) { return 0; }
 
     // right-hand side at stage state y, whose polar angle is th0 + dth with (s0, c0) = sincos(th0).

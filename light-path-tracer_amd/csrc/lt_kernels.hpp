@@ -338,15 +338,19 @@ struct WaveMeter {
         sample = kstats && (__builtin_amdgcn_readfirstlane((uint32_t)wave) & 63u) == 0u;
         if (sample) { c0 = __builtin_amdgcn_s_memtime(); r0 = __builtin_amdgcn_s_memrealtime(); }
     }
-    __device__ __forceinline__ void end(uint64_t *kstats, uint32_t wave_iters)
+    __device__ __forceinline__ void end(uint64_t *kstats, uint32_t wave_iters, uint32_t eq_iters)
     {
         if (!kstats) return;
         // max over the wave: lanes that finished early stopped counting
-        uint32_t m = wave_iters;
-        for (int off = 32; off > 0; off >>= 1) { uint32_t o = __shfl_xor(m, off, 64); m = o > m ? o : m; }
+        uint32_t m = wave_iters, e = eq_iters;
+        for (int off = 32; off > 0; off >>= 1) {
+            uint32_t o = __shfl_xor(m, off, 64); m = o > m ? o : m;
+            o = __shfl_xor(e, off, 64); e = o > e ? o : e;
+        }
         if ((threadIdx.x & 63) != 0) return;
         atomicAdd((unsigned long long *)&kstats[6], (unsigned long long)m);
         atomicAdd((unsigned long long *)&kstats[7], 1ull);
+        if (e) atomicAdd((unsigned long long *)&kstats[LT_STAT_EQ_ITERS], (unsigned long long)e);
         if (sample) {
             uint64_t c1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
             atomicAdd((unsigned long long *)&kstats[8], (unsigned long long)(c1 - c0));
@@ -458,6 +462,7 @@ __device__ __forceinline__ void direct_tiles(const KerrConsts<T> &k_in, Step ste
     st.steps = 0;
     int ev = (flags & FLAG_PAD) ? EV_PAD : EV_INVALID;
     uint32_t wave_iters = 0; // loop iterations this wave issued (streak attempts + general iterations)
+    uint32_t eq_iters = 0;   // ... and those of them that the streak took in its fixed-quadrant loop
     bool raised = false;     // wave-uniform: the wave has raised its issue priority for this tile
     RayConsts<T> rc = make_ray_consts(k, rec.z, (flags & FLAG_REFINE) != 0);
     typename Step::Lane ls;
@@ -466,9 +471,9 @@ __device__ __forceinline__ void direct_tiles(const KerrConsts<T> &k_in, Step ste
     if (flags & FLAG_OK) {
         Integ::start(k, rc, st, rec.x, rec.y);
         // The iteration counter is uniform over the lanes still in the loop (SGPR), so the checks on it cost no VALU.
-        uint32_t it = 0;
+        uint32_t it = 0, eq = 0;
         do {
-            it += Integ::streak(step.streak_consts(ls, k), rc, st, 64u);
+            it += Integ::streak(step.streak_consts(ls, k), rc, st, 64u, eq);
             ev = step.advance(ls, k, rc, st, q, true);
             ++it;
             if (Integ::GHOST_LANES) {
@@ -482,6 +487,7 @@ __device__ __forceinline__ void direct_tiles(const KerrConsts<T> &k_in, Step ste
         } while (ev == EV_RUNNING);
         // lanes leave the loop one by one; the last one out has counted every iteration the wave issued
         wave_iters = it;
+        eq_iters = eq;
     }
     uint32_t steps = st.steps;
     bool real = ev == EV_RUNNING; // only with ghost lanes: this lane's ray is still running
@@ -523,7 +529,7 @@ __device__ __forceinline__ void direct_tiles(const KerrConsts<T> &k_in, Step ste
         store_fin<T>(fin0, fin1, q, st.y.r, st.y.th, st.y.ph, st.y.pr, st.y.pth, rec.z, ev, steps);
         step.stored(ls, q);
     }
-    meter.end(kstats, wave_iters);
+    meter.end(kstats, wave_iters, eq_iters);
     if (stamps) write_stamp(stamps, tile, t0, steps, c0);
     if (!head) return;
     if (__builtin_amdgcn_ballot_w64(raised)) __builtin_amdgcn_s_setprio(0); // back to the bulk's priority for the next tile
@@ -569,7 +575,7 @@ __global__ void __launch_bounds__(256, Integ::MIN_WAVES_PER_SIMD) k_kerr_queue(K
     bool drained = false;       // wave-uniform: the global queue is empty
     bool have = false;          // this lane holds a live ray
     uint64_t q = 0;
-    uint32_t total_steps = 0, wave_iters = 0;
+    uint32_t total_steps = 0, wave_iters = 0, eq_iters = 0;
     int prio = 0;
     bool synced = false;        // wave-uniform: the ghost lanes shadow the current first live lane
     typename Integ::State st;
@@ -629,7 +635,7 @@ __global__ void __launch_bounds__(256, Integ::MIN_WAVES_PER_SIMD) k_kerr_queue(K
         if (have | ghosting) {
             // a far-field streak only while nothing is waiting for it to end: every lane busy (fewer idle lanes than
             // the refill threshold) or the queue drained
-            if (n_idle < refill_min || drained) wave_iters += Integ::streak(k, rc, st, 16u);
+            if (n_idle < refill_min || drained) wave_iters += Integ::streak(k, rc, st, 16u, eq_iters);
             int ev = Integ::advance(k, rc, st);
             ++wave_iters;
             ended = ev != EV_RUNNING;
@@ -647,7 +653,7 @@ __global__ void __launch_bounds__(256, Integ::MIN_WAVES_PER_SIMD) k_kerr_queue(K
         }
         if (ghosting && wave_any(ended)) synced = false;
     }
-    meter.end(kstats, wave_iters);
+    meter.end(kstats, wave_iters, eq_iters);
     if (stamps) write_stamp(stamps, wave_id, t0, total_steps, c0);
 }
 

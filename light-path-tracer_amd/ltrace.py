@@ -23,6 +23,7 @@ STAT_BG_TILES_LDS, STAT_BG_TILES_GLOBAL = 10, 11
 STAT_DISK = 12
 STAT_DISK_HITS = 13
 STAT_AA_REFINED = 14
+STAT_EQ_ITERS = 15
 DISK_MAX_IMAGES = 8
 STATUS_DISK = 2
 STAT_WORDS = 16
@@ -121,6 +122,8 @@ SIGNATURES = {
                                       C.c_double, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lt_kerr_rhs_probe": (C.c_int, [C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
+    "lt_set_eq_streak": (C.c_int, [C.c_int]),
+    "lt_sincos_q1_probe": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "lt_local_rows": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "lt_global_row": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
     "lt_render_dev": (C.c_int, [C.POINTER(Camera), C.POINTER(Metric), C.POINTER(Opts), C.c_void_p, C.c_int32,
@@ -311,6 +314,21 @@ def kerr_rhs_probe(M, a, states, p_phi, precision=32):
     out = np.empty_like(st)
     _check(load().lt_kerr_rhs_probe(M, a, _np_ptr(st), _np_ptr(pp), st.shape[0], precision, _np_ptr(out)))
     return out
+
+
+def set_eq_streak(on):
+    """Enable / disable the float32 streak's fixed-quadrant loop for the launches that follow; returns the previous setting."""
+    return bool(load().lt_set_eq_streak(int(bool(on))))
+
+
+def sincos_q1_probe(bits_lo, bits_hi):
+    """Both float32 sincos forms on every float32 with bit pattern in [bits_lo, bits_hi], compared on the device:
+    dict(compared, differing, outside_k1, first_differing_bits, band=(lo, hi))."""
+    out = np.zeros(4, dtype=np.uint64)
+    band = np.zeros(2, dtype=np.float32)
+    _check(load().lt_sincos_q1_probe(int(bits_lo), int(bits_hi), _np_ptr(out), _np_ptr(band)))
+    return dict(compared=int(out[0]), differing=int(out[1]), outside_k1=int(out[2]), first_differing_bits=int(out[3]),
+                band=(float(band[0]), float(band[1])))
 
 
 def local_rows(height, row_block, n_parts, part):
@@ -536,7 +554,7 @@ def stats_dict(counters, prologue_ms=0.0, integrate_ms=0.0, epilogue_ms=0.0):
     return dict(rays=c[STAT_RAYS], steps=c[STAT_STEPS], rhs_evals=c[STAT_RHS_EVALS], escaped=c[STAT_ESCAPED],
                 captured=c[STAT_CAPTURED], invalid=c[STAT_INVALID], wave_iters=c[STAT_WAVE_ITERS],
                 waves=c[STAT_WAVES], clock_mhz=clk, bg_tiles_lds=c[STAT_BG_TILES_LDS],
-                bg_tiles_global=c[STAT_BG_TILES_GLOBAL],
+                bg_tiles_global=c[STAT_BG_TILES_GLOBAL], eq_iters=c[STAT_EQ_ITERS],
                 prologue_ms=prologue_ms, integrate_ms=integrate_ms, epilogue_ms=epilogue_ms)
 
 

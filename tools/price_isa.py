@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Price a kernel's hottest loop with the measured gfx950 VALU issue costs (tools/issue_probe.py).
-usage: price_isa.py file.s kernel_substring"""
+usage: price_isa.py file.s kernel_substring [--loops]
+--loops: one line per loop of the kernel (innermost backward-branch spans, largest first) instead of the hottest alone."""
 import re, sys, collections
 s = open(sys.argv[1]).read()
 key = sys.argv[2]
@@ -17,6 +18,18 @@ for i, l in enumerate(body):
     if mm and mm.group(1) in labels and labels[mm.group(1)] < i:
         span = (labels[mm.group(1)], i)
         if best is None or span[1] - span[0] > best[1] - best[0]: best = span
+if '--loops' in sys.argv[3:]:
+    # every backward branch, conditional or not (a rotated loop closes with s_branch), is a loop; nested ones (the tile
+    # loop around the step loops) are listed too
+    spans = sorted({(labels[mm.group(1)], i) for i, l in enumerate(body)
+                    for mm in [re.search(r's_c?branch\w*\s+(\.LBB\S+)', l)] if mm and mm.group(1) in labels and labels[mm.group(1)] < i},
+                   key=lambda sp: sp[0] - sp[1])
+    for a, b in spans:
+        ops = [l.strip().split()[0] for l in body[a:b + 1] if l.strip() and not l.strip().startswith(('.', ';')) and not l.strip().endswith(':')]
+        n_valu = sum(o.startswith('v_') for o in ops)
+        print(f"loop lines {a}-{b}: {len(ops)} instructions, VALU {n_valu}, v_rndne {sum(o.startswith('v_rndne') for o in ops)}, "
+              f"v_cvt {sum(o.startswith('v_cvt') for o in ops)}, v_pk {sum(o.startswith('v_pk_') for o in ops)}")
+    sys.exit(0)
 lo, hi = best
 ins = [l.strip().split()[0] for l in body[lo:hi + 1] if l.strip() and not l.strip().startswith(('.', ';')) and not l.strip().endswith(':')]
 full = lambda l: l
