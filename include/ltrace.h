@@ -429,6 +429,94 @@ int lt_trace_batch_kerr_disk_images(double M, double a, double r_obs, const doub
                                     int64_t *out_w, int8_t *out_status, double *out_images, int32_t *out_n_hits,
                                     uint32_t *out_rhs_evals);
 
+/* ---- hit times and an orbiting hot spot re-shaded from one trace -------------------------------------- *
+ * lt_trace_disk_hits is lt_render_disk_images' trace with one more number per hit: the coordinate time the light   *
+ * needs from the hit to the camera.  With that stored, a picture of something that MOVES on the disk -- here a     *
+ * bright spot on a circular orbit -- at any observer time is a re-shade of the stored hits (lt_shade_hotspot), and  *
+ * a light curve is a reduction over them (lt_hotspot_lightcurve): one trace, then passes of epilogue size.         *
+ *                                                                                                               *
+ * Time.  With the tracers' convention (E = 1, L = p_phi)                                                          *
+ *   dt/dlambda (r, theta) = [ (r^2 + a^2) P / Delta + a (L - a sin^2 theta) ] / Sigma,   P = r^2 + a^2 - a L,      *
+ * positive outside the horizon; the elapsed time is counted from the camera along the backward ray.  It does not  *
+ * feed back into the ray: it is a quadrature over the accepted steps, and no step changes.  Per accepted step      *
+ * y0 -> y1 of length h (a rejected or retried attempt adds nothing)                                                *
+ *   dt_step = h/6 ( t'(y0) + 4 t'(y_m) + t'(y1) ),                                                                 *
+ * y_m the step's cubic Hermite at 1/2: r_m = (r0 + r1)/2 + h/8 (r'0 - r'1), the same for theta, with               *
+ * r' = Delta p_r / Sigma and theta' = p_theta / Sigma: local error O(h^5), RK4's own order.  A hit at the fraction  *
+ * tau of its step (lt_render_disk's Hermite refinement) applies the same rule to [0, tau], with the cubic's states  *
+ * at tau/2 and tau; on a step that also ends the ray, to the retaken full step.  The sum over the steps is a        *
+ * compensated (two-term) sum.  disk.step_time (Python) states the rule in numpy; lt_step_time_probe runs the        *
+ * device's.                                                                                                       *
+ *                                                                                                               *
+ * The timed trace takes every step in the general iteration: the far-field streak, which takes up to 64 steps       *
+ * without showing their ends, is off.  Its steps are the general iteration's arithmetic, so every output the two    *
+ * calls share -- r, phi, g of every slot, n_hits, fa, winding, status, steps, stats words 0-5, LT_STAT_DISK,        *
+ * LT_STAT_DISK_HITS -- equals lt_render_disk_images' bit for bit; only LT_STAT_WAVE_ITERS and LT_STAT_EQ_ITERS       *
+ * may differ.                                                                                                     *
+ *                                                                                                               *
+ * Out of scope: supersampled hot-spot frames, lt_render_multi and the multi-process path.                         */
+
+/* lt_render_disk_images_dev without the colour outputs and with
+ *   d_hits (R, W, max_images, 4) float32 (r_hit, phi_hit in [0, 2 pi), g, elapsed time), NaN in unused slots
+ * in place of d_images.  RK4 float32 / float64, DP45 and DP45-exact float64, direct schedule; partitions, stats and
+ * refusals as lt_render_disk_images_dev. */
+int lt_trace_disk_hits_dev(const lt_camera *cam, const lt_metric *metric, const lt_opts *opts, const lt_disk *disk,
+                           int32_t max_images, float *d_fa, uint16_t *d_w, int8_t *d_status, uint32_t *d_steps,
+                           float *d_hits, uint8_t *d_n_hits, uint64_t *d_stats);
+/* The same with HOST pointers, staged like lt_render_disk_images. */
+int lt_trace_disk_hits(const lt_camera *cam, const lt_metric *metric, const lt_opts *opts, const lt_disk *disk,
+                       int32_t max_images, float *out_fa, uint16_t *out_w, int8_t *out_status, uint32_t *out_steps,
+                       float *out_hits, uint8_t *out_n_hits, lt_stats *stats);
+/* lt_trace_batch_kerr_disk_images with out_hits (n, max_images, 4) float64 in place of out_images. */
+int lt_trace_batch_kerr_disk_hits(double M, double a, double r_obs, const double *alphas, const double *thetas,
+                                  double theta_obs, double lambda_max, const uint8_t *axis_refines, int integrator,
+                                  int precision, const lt_disk *disk, int32_t max_images, int64_t n, double *out_fa,
+                                  int64_t *out_w, int8_t *out_status, double *out_hits, int32_t *out_n_hits,
+                                  uint32_t *out_rhs_evals);
+/* The device's own dt_step on [0, tau] of n steps, for parity tests: p_phi (n), y0 and y1 (n, 4: r, theta, p_r,
+ * p_theta), h (n), tau (n), out (n), all float64 HOST arrays; the arithmetic runs in `precision` (32 or 64). */
+int lt_step_time_probe(const lt_metric *metric, const double *p_phi, const double *y0, const double *y1, const double *h,
+                       const double *tau, int64_t n, int precision, double *out);
+
+/* A spot of Gaussian profile on the circular equatorial orbit of the disk's direction at r_spot, at azimuth phi0 at
+ * coordinate time 0: phi_s(t) = phi0 + Omega(r_spot) t, Omega = sqrt(M) / (r^1.5 + a sqrt(M)). */
+typedef struct lt_hotspot {
+    double r_spot, phi0;
+    double sigma;      /* width of the profile, > 0 (LT_ERR_INVALID_ARG otherwise) */
+    double exposure;   /* brightness scale of the spot, >= 0 */
+    int32_t with_disk; /* nonzero: the stationary disk's light is added as lt_render_disk_images adds it */
+    int32_t reserved;
+} lt_hotspot;
+void lt_default_hotspot(lt_hotspot *spot); /* r_spot 8, phi0 0, sigma 1, exposure 1, with_disk 1 */
+
+/* The frame at observer time t_obs from stored hits: hits (R, W, max_images, 4) float32 and n_hits (R, W) uint8 as
+ * lt_trace_disk_hits wrote them (n_hits NULL: a slot is stored where its r is not NaN).  Per stored slot, in float64
+ * from the float32 record,
+ *   t_em = t_obs - dt,  phi_s = phi0 + Omega(r_spot) t_em,  d^2 = r^2 + r_s^2 - 2 r r_s cos(phi - phi_s),
+ *   w = exp(-d^2 / 2 sigma^2),  E_spot = exposure g^4 w ramp(g),
+ *   rgb = clamp(base + sum_j (with_disk E_j^disk + E_j^spot), 0, 1),
+ * E^disk and ramp as in lt_render_disk_images (the disk's exposure is lt_disk's), base first, then the slots in order,
+ * each slot's disk term before its spot term; a pixel without a stored hit keeps base.  base (R, W, channels) float32
+ * or NULL (black); channels 1 (the mean of the three) or 3; out_rgb (R, W, channels) float32 and out_rgba (R, W, 4)
+ * uint8, written as everywhere, either may be NULL.  With with_disk = 1 and exposure = 0 over a black base the frame
+ * is lt_render_disk_images' rgb bit for bit.  The _dev form takes DEVICE pointers and enqueues on the default stream. */
+int lt_shade_hotspot_dev(const float *d_hits, const uint8_t *d_n_hits, int32_t R, int32_t W, int32_t max_images,
+                         const lt_metric *metric, const lt_disk *disk, const lt_hotspot *spot, double t_obs,
+                         const float *d_base, int32_t channels, float *d_rgb, uint8_t *d_rgba);
+int lt_shade_hotspot(const float *hits, const uint8_t *n_hits, int32_t R, int32_t W, int32_t max_images,
+                     const lt_metric *metric, const lt_disk *disk, const lt_hotspot *spot, double t_obs, const float *base,
+                     int32_t channels, float *out_rgb, uint8_t *out_rgba);
+/* The spot's light curve at t_start + i dt, i < n_times (<= 65535): out (n_times, 3) float64 = per time the sums of e,
+ * e ix and e iy over all pixels (column ix, row iy of the buffer) and stored slots, e the mean of E_spot's channels.
+ * No clamping, no base.  Two-stage reduction in a fixed order without floating-point atomics: the result is bitwise
+ * the same run to run. */
+int lt_hotspot_lightcurve_dev(const float *d_hits, const uint8_t *d_n_hits, int32_t R, int32_t W, int32_t max_images,
+                              const lt_metric *metric, const lt_disk *disk, const lt_hotspot *spot, double t_start, double dt,
+                              int32_t n_times, double *d_out);
+int lt_hotspot_lightcurve(const float *hits, const uint8_t *n_hits, int32_t R, int32_t W, int32_t max_images,
+                          const lt_metric *metric, const lt_disk *disk, const lt_hotspot *spot, double t_start, double dt,
+                          int32_t n_times, double *out);
+
 /* ---- supersampled (anti-aliased) frames, resolved on the GPU ------------------------------------------- *
  * Every frame above is one ray per pixel, taken at the pixel's corner.  These entry points trace S x S rays per       *
  * pixel and write only the resolved pixels: nothing of the S^2 times larger frame crosses PCIe or stays in memory.    *

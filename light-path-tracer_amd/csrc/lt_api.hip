@@ -7,6 +7,8 @@
 #include "lt_kernels.hpp"
 #include "lt_disk.hpp"
 #include "lt_disk_images.hpp"
+#include "lt_hit_time.hpp"
+#include "lt_hotspot.hpp"
 #include "lt_aa.hpp"
 #include "lt_aa_adaptive.hpp"
 #ifdef LT_PROBES
@@ -136,6 +138,8 @@ struct StreamSlot {
     Grow dense;  // lt_integrate_dense_dev, length-binned launch: histogram, cursors, keys, permutation
     Grow blocks; // block-owner table mode: this partition's block list on the device
     Grow disk_img; // lt_render_disk_images / its batch twin: the integrate kernel's hit records and counts
+    Grow disk_time; // lt_trace_disk_hits / its batch twin: the integrate kernel's hit times
+    Grow hotspot;   // lt_hotspot_lightcurve: the first stage's partial sums
     std::vector<int32_t> blocks_host; // what `blocks` holds (skip the upload when unchanged)
     EventQuad own{}; // lt_render's private timing events (created on first use)
     bool own_ok = false;
@@ -222,7 +226,7 @@ static void release(Grow &g)
 // Everything a slot owns, and the slot.  The caller has drained the slot's stream and taken the slot off its list.
 static void destroy_slot(StreamSlot *sl)
 {
-    for (Grow *g : {&sl->ws, &sl->dev, &sl->dense, &sl->blocks, &sl->disk_img, &sl->aa_list, &sl->aa_scratch}) release(*g);
+    for (Grow *g : {&sl->ws, &sl->dev, &sl->dense, &sl->blocks, &sl->disk_img, &sl->disk_time, &sl->hotspot, &sl->aa_list, &sl->aa_scratch}) release(*g);
     if (sl->own_ok) for (auto &e : sl->own.e) (void)hipEventDestroy(e);
     for (auto &q : sl->aa_events) for (auto &e : q.e) (void)hipEventDestroy(e);
     delete sl;
@@ -666,6 +670,7 @@ template <auto Kernel> static int resident_slots()
 template <typename T> struct PlainKernels { template <typename Integ> static constexpr auto kernel = &k_kerr_direct<T, Integ>; };
 template <typename T> struct DiskKernels { template <typename Integ> static constexpr auto kernel = &k_kerr_disk<T, Integ>; };
 template <typename T> struct DiskImagesKernels { template <typename Integ> static constexpr auto kernel = &k_kerr_disk_images<T, Integ>; };
+template <typename T> struct DiskTimedKernels { template <typename Integ> static constexpr auto kernel = &k_kerr_disk_timed<T, Integ>; };
 template <typename Integ> struct IntegTag { using type = Integ; };
 
 // The switches of the direct schedule, read once.
@@ -803,11 +808,14 @@ struct DiskParams {
     int max_images = 0;              // slots kept per ray; 0: the opaque disk
     float *d_images = nullptr;       // (R, W, max_images, 3) float32 or NULL
     uint8_t *d_n_hits = nullptr;     // (R, W) or NULL
+    bool timed = false;              // lt_trace_disk_hits (lt_api_hotspot.inc): d_images is (R, W, max_images, 4), no colour
+    int image_words() const { return timed ? 4 : 3; }
 };
 // The hit records of the thin disk, resolved once per call (get_disk_records) and handed to its launches.
 struct DiskRecordsBuf {
     void *p = nullptr;        // Vec2<T> [max_images][n_q]
     uint32_t *hits = nullptr; // [n_q]
+    void *tim = nullptr;      // the timed trace: T [max_images][n_q]
     template <typename T> typename Vec2<T>::type *img() const { return (typename Vec2<T>::type *)p; }
 };
 // The disks' launches, defined in lt_api_disk.inc and lt_api_disk_images.inc (which in turn call the frame plumbing below).
@@ -1247,7 +1255,7 @@ static int render_host_impl(const lt_camera *cam, const lt_metric *metric, const
     FrameStaging fs;
     fs.declare(&st, bg, bg_channels, (size_t)cam->height * cam->width, n, out_fa, out_w, out_status, out_steps, out_rgb, out_rgba);
     const int i_disk = fs.out(out_disk, n, 3 * 4);
-    const int i_img = fs.out(out_images, n, disk ? (size_t)disk->max_images * 3 * 4 : 0), i_hits = fs.out(out_n_hits, n, 1);
+    const int i_img = fs.out(out_images, n, disk ? (size_t)disk->max_images * disk->image_words() * 4 : 0), i_hits = fs.out(out_n_hits, n, 1);
     if ((rc = fs.commit((hipStream_t)o.stream))) return rc;
     DiskParams dp{};
     if (disk) {
@@ -1400,7 +1408,7 @@ static int trace_batch(const MetricConsts &mc, lt_opts &o, double lambda_max, co
     const int i_al = st.in(alphas, n, 8), i_th = st.in(thetas, n, 8), i_ref = st.in(refines, n, 1);
     const int i_fa = st.out(out_fa, n, 8), i_w = st.out(out_w, n, 8), i_st = st.out(out_status, n, 1), i_ev = st.out(out_evals, n, 4);
     const int i_disk = st.out(out_disk, n, 3 * 8);
-    const int i_img = st.out(out_images, n, disk ? (size_t)disk->max_images * 3 * 8 : 0), i_hits = st.out(out_n_hits, n, 4);
+    const int i_img = st.out(out_images, n, disk ? (size_t)disk->max_images * disk->image_words() * 8 : 0), i_hits = st.out(out_n_hits, n, 4);
     if ((rc = st.commit(s))) return rc;
     double *d_fa = st.dev<double>(i_fa); int64_t *d_w = st.dev<int64_t>(i_w);
     int8_t *d_st = st.dev<int8_t>(i_st); uint32_t *d_ev = st.dev<uint32_t>(i_ev);
@@ -1580,5 +1588,6 @@ extern "C" int lt_scatter_rows_indexed_dev(const void *d_rows, void *d_full, con
 #include "lt_api_dense.inc"
 #include "lt_api_disk.inc"
 #include "lt_api_disk_images.inc"
+#include "lt_api_hotspot.inc"
 #include "lt_api_aa.inc"
 #include "lt_api_aa_adaptive.inc"

@@ -69,9 +69,11 @@ template <typename T> __device__ __forceinline__ T hermite_dt(T y0, T hd0, T y1,
 // The crossing of the plane on the step y0 -> y1 of length h, searched on [0, t_end] (t_end < 1: the step was cut at a
 // capture / escape radius, the ray ended at t_end).  True, and the crossing state in `hit`, if the crossing point lies
 // in the annulus.  Per lane; runs only on lanes whose states straddle the plane near the annulus.
+// `tau`, if given, receives the crossing's fraction of the step (the timed trace of lt_hit_time.hpp integrates up to it).
 template <typename T>
 __device__ __forceinline__ bool disk_crossing(const KerrConsts<T> &k, const DiskConsts<T> &d, const RayConsts<T> &rc,
-                                           const State5<T> &y0, const State5<T> &y1, T h, T t_end, State5<T> &hit)
+                                           const State5<T> &y0, const State5<T> &y1, T h, T t_end, State5<T> &hit,
+                                           T *tau = nullptr)
 {
     const T HALF_PI = T(1.5707963267948966);
     T f0[5], f1[5];
@@ -99,6 +101,7 @@ __device__ __forceinline__ bool disk_crossing(const KerrConsts<T> &k, const Disk
     hit.ph = hermite(y0.ph, f0[2], y1.ph, f1[2], t);
     hit.pr = hermite(y0.pr, f0[3], y1.pr, f1[3], t);
     hit.pth = hermite(y0.pth, f0[4], y1.pth, f1[4], t);
+    if (tau) *tau = t;
     return (hit.r >= d.r_in) & (hit.r <= d.r_out);
 }
 
@@ -106,10 +109,15 @@ __device__ __forceinline__ bool disk_crossing(const KerrConsts<T> &k, const Disk
 // a min / max of their radii against the annulus widened by the largest radial move of the step, and ONE wave-uniform
 // branch.  `vmax2`: twice disk_vmax of the ray.  A crossing inside the annulus, on a lane with `act` set, goes to
 // `on_hit(s, hit, ev)`, which returns the iteration's event: the opaque disk ends the ray there, the thin one records
-// the point and lets the ray go on.
+// the point and lets the ray go on.  `on`, if given, is filled before on_hit runs: the step the hit lies on.
+template <typename T> struct DiskHitStep {
+    State5<T> y1; // the step's end state (a terminal step: the retaken full step's)
+    T h, tau;     // its length and the crossing's fraction of it
+};
 template <typename T, typename Integ, typename OnHit>
 __device__ __forceinline__ int disk_advance(const KerrConsts<T> &k, const DiskConsts<T> &d, const RayConsts<T> &rc,
-                                            T vmax2, typename Integ::State &s, bool act, OnHit on_hit)
+                                            T vmax2, typename Integ::State &s, bool act, OnHit on_hit,
+                                            DiskHitStep<T> *on = nullptr)
 {
     const T HALF_PI = T(1.5707963267948966);
     const typename Integ::State before = s;
@@ -136,7 +144,10 @@ __device__ __forceinline__ int disk_advance(const KerrConsts<T> &k, const DiskCo
                 const T denom = y1.r - before.y.r;
                 t_end = denom == T(0) ? T(1) : M<T>::min(M<T>::max((target - before.y.r) / denom, T(0)), T(1));
             }
-            if (disk_crossing(k, d, rc, before.y, y1, h, t_end, hit) & act) ev = on_hit(s, hit, ev);
+            if (disk_crossing(k, d, rc, before.y, y1, h, t_end, hit, on ? &on->tau : nullptr) & act) {
+                if (on) { on->y1 = y1; on->h = h; }
+                ev = on_hit(s, hit, ev);
+            }
         }
     }
     return ev;

@@ -20,6 +20,7 @@ from time import perf_counter
 
 import json
 import os
+import sys
 
 import numpy as np
 
@@ -301,6 +302,71 @@ def render_frame(source_image, metric, r_obs, fov, psi=(0.0, 0.0), theta_obs=np.
     return ltrace.render(cam, met, opts, background=source_image, want=want)
 
 
+def render_sequence(source_image, metric, r_obs, fov, disk, hotspot, times, shape=None, psi=(0.0, 0.0), theta_obs=np.pi / 2,
+                    integrator=None, precision=None):
+    """A moving picture from ONE trace: an optically thin disk (disk.TransparentDisk) with a hot spot (disk.HotSpot) on a
+    circular orbit, at the observer times `times`.  The rays are traced once with the light-travel time of every hit
+    (lt_trace_disk_hits); each frame is a re-shade of the stored hits (lt_shade_hotspot) over `base`, the lensed
+    source_image (None: black, then `shape` = (H, W) gives the size), and the light curve is a reduction over them
+    (lt_hotspot_lightcurve, at times[0] + i (times[1] - times[0]): the times must be evenly spaced).
+    -> dict(frames (n, H, W[, 3]) float32, rgba (n, H, W, 4) uint8, lightcurve (n, 3) float64, hits, n_hits, stats).
+    One GPU, every row traced, one ray per pixel (no supersampling)."""
+    times = np.asarray(times, dtype=np.float64).ravel()
+    if times.size == 0:
+        raise ValueError("render_sequence needs at least one time")
+    dt = float(times[1] - times[0]) if times.size > 1 else 0.0
+    if times.size > 2 and np.max(np.abs(np.diff(times) - dt)) > 1e-9 * max(abs(dt), 1.0):
+        raise ValueError("render_sequence: the times must be evenly spaced")
+    base = None
+    met = ltrace.Metric(ltrace.METRIC_KERR, 0, float(metric.M), float(getattr(metric, "a", 0.0)))
+    opts = ltrace.default_opts(integrator=integrator or getattr(metric, "integrator", "rk4"),
+                               precision=precision or getattr(metric, "precision", 32), schedule="direct",
+                               tb_symmetry=0, axis_refine_frac=Y_AXIS_REFINE_FRAC)
+    if source_image is not None:
+        source_image = np.asarray(source_image)
+        if source_image.ndim == 3 and source_image.shape[2] == 4:
+            source_image = source_image[..., :3]
+        shape = source_image.shape[:2]
+    cam = _camera(shape, fov, psi, r_obs, theta_obs)
+    if source_image is not None:
+        base = ltrace.render(cam, met, opts, background=source_image, want=("rgb",))["rgb"]
+    d, spot = disk.to_lt(), hotspot.to_lt()
+    m = int(getattr(disk, "max_images", 3))
+    traced = ltrace.trace_disk_hits(cam, met, opts, d, max_images=m, want=("hits", "n_hits"))
+    frames, rgba = [], []
+    for t in times:
+        f = ltrace.shade_hotspot(traced["hits"], traced["n_hits"], met, d, spot, float(t), base=base)
+        frames.append(f["rgb"])
+        rgba.append(f["rgba"])
+    lc = ltrace.hotspot_lightcurve(traced["hits"], traced["n_hits"], met, d, spot, float(times[0]), dt, times.size)
+    return dict(frames=np.stack(frames), rgba=np.stack(rgba), lightcurve=lc, hits=traced["hits"], n_hits=traced["n_hits"],
+                stats=traced["stats"])
+
+
+def main_sequence(args, disk):
+    """--hotspot R PHI0 SIGMA --times T0 DT N: numbered PNGs next to --output and the light curve as .npy."""
+    from disk import HotSpot
+    if not args.synthetic:
+        raise ValueError("--hotspot renders over a black sky at the size given by --synthetic W H")
+    if disk is None or not hasattr(disk, "max_images"):
+        raise ValueError("--hotspot needs --disk-images N")
+    width, height = int(args.synthetic[0]), int(args.synthetic[1])
+    metric = Kerr(M=args.M, a=args.a, integrator=args.integrator, precision=args.precision)
+    vfov = np.radians(args.fov_v)
+    fov = (2 * np.arctan(np.tan(vfov / 2) * width / height), vfov)
+    t0, dt, n = float(args.times[0]), float(args.times[1]), int(args.times[2])
+    spot = HotSpot(r_spot=args.hotspot[0], phi0=args.hotspot[1], sigma=args.hotspot[2], exposure=args.hotspot_exposure)
+    out = render_sequence(None, metric, args.r_obs * metric.M, fov, disk, spot, t0 + dt * np.arange(n), shape=(height, width),
+                          psi=(np.radians(args.psi_y), np.radians(args.psi_x)), theta_obs=np.radians(args.theta_obs))
+    stem = args.output[:-4] if args.output.lower().endswith(".png") else args.output
+    for i in range(n):
+        write_png_rgba8(f"{stem}_{i:04d}.png", out["rgba"][i])
+    np.save(stem + "_lightcurve.npy", out["lightcurve"])
+    print(f"Hot spot: one trace ({out['stats']['integrate_ms']:.2f} ms), {n} frames -> {stem}_0000.png ..., light curve -> "
+          f"{stem}_lightcurve.npy")
+    return out
+
+
 # ---------------------------------------------------------------------------------------------
 # benchmark print, CLI
 # ---------------------------------------------------------------------------------------------
@@ -556,6 +622,12 @@ def build_parser():
     ap.add_argument("--contrast", type=float, default=None, metavar="T",
                     help="--adaptive: refine a pixel whose colour differs from a neighbour's by more than T in a channel "
                          "(default 0.0625; negative: off)")
+    ap.add_argument("--hotspot", type=float, nargs=3, default=None, metavar=("R", "PHI0", "SIGMA"),
+                    help="with --disk-images: a bright spot on the circular orbit at R (azimuth PHI0 rad at t = 0, width SIGMA), "
+                         "re-shaded per --times from one trace; writes numbered PNGs and the light curve as .npy")
+    ap.add_argument("--times", type=float, nargs=3, default=(0.0, 10.0, 8), metavar=("T0", "DT", "N"),
+                    help="--hotspot: N observer times from T0 in steps of DT (in M)")
+    ap.add_argument("--hotspot-exposure", type=float, default=1.0, help="--hotspot: brightness scale of the spot (default: 1)")
     return ap
 
 
@@ -569,6 +641,9 @@ if __name__ == "__main__":
     elif args.disk:
         from disk import ThinDisk
         disk = ThinDisk(r_in=args.disk_rin, r_out=args.disk_rout, q=args.disk_q, exposure=args.disk_exposure)
+    if args.hotspot is not None:
+        main_sequence(args, disk)
+        sys.exit(0)
     main(M=args.M, a=args.a, r_obs_mult=args.r_obs, psi=(np.radians(args.psi_y), np.radians(args.psi_x)),
          vertical_fov_deg=args.fov_v, image_path=args.image, output_path=args.output, synthetic=args.synthetic,
          staged=args.staged, integrator=args.integrator, precision=args.precision, schedule=args.schedule,

@@ -74,6 +74,12 @@ class Disk(C.Structure):
                 ("flags", C.c_int32), ("reserved", C.c_int32)]
 
 
+class HotSpot(C.Structure):
+    """lt_hotspot: a Gaussian spot on the circular equatorial orbit at r_spot (azimuth phi0 at coordinate time 0)."""
+    _fields_ = [("r_spot", C.c_double), ("phi0", C.c_double), ("sigma", C.c_double), ("exposure", C.c_double),
+                ("with_disk", C.c_int32), ("reserved", C.c_int32)]
+
+
 class AA(C.Structure):
     """lt_aa: supersampling (samples x samples rays per pixel; band_rows 0 = automatic)."""
     _fields_ = [("samples", C.c_int32), ("mode", C.c_int32), ("max_images", C.c_int32), ("band_rows", C.c_int32)]
@@ -167,6 +173,29 @@ SIGNATURES = {
                                                   C.c_double, C.c_double, C.c_void_p, C.c_int, C.c_int, C.POINTER(Disk),
                                                   C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                   C.c_void_p, C.c_void_p]),
+    "lt_trace_disk_hits_dev": (C.c_int, [C.POINTER(Camera), C.POINTER(Metric), C.POINTER(Opts), C.POINTER(Disk), C.c_int32,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lt_trace_disk_hits": (C.c_int, [C.POINTER(Camera), C.POINTER(Metric), C.POINTER(Opts), C.POINTER(Disk), C.c_int32,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]),
+    "lt_trace_batch_kerr_disk_hits": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
+                                                C.c_double, C.c_double, C.c_void_p, C.c_int, C.c_int, C.POINTER(Disk),
+                                                C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p]),
+    "lt_step_time_probe": (C.c_int, [C.POINTER(Metric), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_int64, C.c_int, C.c_void_p]),
+    "lt_default_hotspot": (None, [C.POINTER(HotSpot)]),
+    "lt_shade_hotspot_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Metric),
+                                       C.POINTER(Disk), C.POINTER(HotSpot), C.c_double, C.c_void_p, C.c_int32, C.c_void_p,
+                                       C.c_void_p]),
+    "lt_shade_hotspot": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Metric),
+                                   C.POINTER(Disk), C.POINTER(HotSpot), C.c_double, C.c_void_p, C.c_int32, C.c_void_p,
+                                   C.c_void_p]),
+    "lt_hotspot_lightcurve_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Metric),
+                                            C.POINTER(Disk), C.POINTER(HotSpot), C.c_double, C.c_double, C.c_int32,
+                                            C.c_void_p]),
+    "lt_hotspot_lightcurve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Metric),
+                                        C.POINTER(Disk), C.POINTER(HotSpot), C.c_double, C.c_double, C.c_int32,
+                                        C.c_void_p]),
     "lt_default_aa": (None, [C.POINTER(AA)]),
     "lt_render_aa_dev": (C.c_int, [C.POINTER(Camera), C.POINTER(Metric), C.POINTER(Opts), C.POINTER(AA), C.POINTER(Disk),
                                    C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -753,6 +782,142 @@ def trace_batch_kerr_disk_images(M, a, r_obs, alphas, thetas, theta_obs, lambda_
                                                   _np_ptr(out["images"]), _np_ptr(out["n_hits"]),
                                                   _np_ptr(out["rhs_evals"])))
     return out
+
+
+# ---- hit times and the orbiting hot spot (lt_trace_disk_hits, lt_shade_hotspot, lt_hotspot_lightcurve) ------------
+def trace_disk_hits(cam, metric, opts, disk, max_images=3, want=("fa", "winding", "status", "steps", "hits", "n_hits")):
+    """Host-pointer timed trace of the optically thin disk (lt_trace_disk_hits): render_disk_images() without the colour,
+    with 'hits' (rows, W, max_images, 4) float32 (r_hit, phi_hit, g, light-travel time to the camera), NaN in unused
+    slots, in place of 'images'."""
+    rows = _frame_rows(cam, opts)
+    out = _frame_outputs(rows, cam.width, 3, False, [k for k in want if k in ("fa", "winding", "status", "steps")])
+    if "hits" in want:
+        out["hits"] = pinned_empty((rows, cam.width, int(max_images), 4), np.float32)
+    if "n_hits" in want:
+        out["n_hits"] = pinned_empty((rows, cam.width), np.uint8)
+    st = Stats()
+    _check(load().lt_trace_disk_hits(C.byref(cam), C.byref(metric), C.byref(opts), C.byref(disk), int(max_images),
+                                     _np_ptr(out.get("fa")), _np_ptr(out.get("winding")), _np_ptr(out.get("status")),
+                                     _np_ptr(out.get("steps")), _np_ptr(out.get("hits")), _np_ptr(out.get("n_hits")),
+                                     C.byref(st)))
+    out["stats"] = stats_dict(st.counters, st.prologue_ms, st.integrate_ms, st.epilogue_ms)
+    out["stats"]["disk"] = int(st.counters[STAT_DISK])
+    out["stats"]["disk_hits"] = int(st.counters[STAT_DISK_HITS])
+    return out
+
+
+def trace_disk_hits_dev(cam, metric, opts, disk, max_images=3, d_fa=0, d_w=0, d_status=0, d_steps=0, d_hits=0, d_n_hits=0,
+                        d_stats=0):
+    """Device-pointer form of trace_disk_hits (lt_trace_disk_hits_dev); pointers are integers, 0 = NULL.  Asynchronous."""
+    _check(load().lt_trace_disk_hits_dev(C.byref(cam), C.byref(metric), C.byref(opts), C.byref(disk), int(max_images),
+                                         _p(d_fa), _p(d_w), _p(d_status), _p(d_steps), _p(d_hits), _p(d_n_hits), _p(d_stats)))
+
+
+def trace_batch_kerr_disk_hits(M, a, r_obs, alphas, thetas, theta_obs, lambda_max, disk, max_images=3,
+                               axis_refines=None, integrator=INTEGRATOR_RK4, precision=32):
+    """Batch twin of the timed trace (lt_trace_batch_kerr_disk_hits): trace_batch_kerr_disk_images() with 'hits'
+    (n, max_images, 4) f64 (r_hit, phi_hit, g, light-travel time) in place of 'images'."""
+    al = np.ascontiguousarray(alphas, dtype=np.float64)
+    th = np.ascontiguousarray(thetas, dtype=np.float64)
+    n = al.size
+    if th.size != n:
+        raise ValueError("alphas and thetas differ in length")
+    ar = None
+    if axis_refines is not None:
+        ar = np.ascontiguousarray(axis_refines).astype(np.uint8)
+        if ar.size != n:
+            raise ValueError("axis_refines has the wrong length")
+    if isinstance(integrator, str):
+        integrator = INTEGRATORS[integrator]
+    m = int(max_images)
+    out = dict(fa=np.empty(n), winding=np.empty(n, dtype=np.int64), status=np.empty(n, dtype=np.int8),
+               hits=np.empty((n, max(m, 0), 4)), n_hits=np.empty(n, dtype=np.int32),
+               rhs_evals=np.empty(n, dtype=np.uint32))
+    _check(load().lt_trace_batch_kerr_disk_hits(M, a, r_obs, _np_ptr(al), _np_ptr(th), theta_obs, lambda_max,
+                                                _np_ptr(ar), integrator, precision, C.byref(disk), m, n,
+                                                _np_ptr(out["fa"]), _np_ptr(out["winding"]), _np_ptr(out["status"]),
+                                                _np_ptr(out["hits"]), _np_ptr(out["n_hits"]), _np_ptr(out["rhs_evals"])))
+    return out
+
+
+def step_time_probe(metric, p_phi, y0, y1, h, tau=1.0, precision=64):
+    """The device's own step rule (lt_step_time_probe) on n steps: y0, y1 (n, 4) (r, theta, p_r, p_theta); p_phi, h, tau
+    scalars or (n,).  -> (n,) float64."""
+    y0 = np.ascontiguousarray(y0, dtype=np.float64).reshape(-1, 4)
+    y1 = np.ascontiguousarray(y1, dtype=np.float64).reshape(-1, 4)
+    n = y0.shape[0]
+    pp, hh, tt = (np.ascontiguousarray(np.broadcast_to(np.asarray(x, dtype=np.float64), (n,))) for x in (p_phi, h, tau))
+    out = np.empty(n)
+    _check(load().lt_step_time_probe(C.byref(metric), _np_ptr(pp), _np_ptr(y0), _np_ptr(y1), _np_ptr(hh), _np_ptr(tt), n,
+                                     int(precision), _np_ptr(out)))
+    return out
+
+
+def default_hotspot(**kw):
+    """lt_hotspot with the library's defaults (r_spot 8, phi0 0, sigma 1, exposure 1, with_disk 1); keywords override."""
+    h = HotSpot()
+    load().lt_default_hotspot(C.byref(h))
+    for k, v in kw.items():
+        setattr(h, k, v)
+    return h
+
+
+def _hit_arrays(hits, n_hits):
+    hits = np.ascontiguousarray(hits, dtype=np.float32)
+    if hits.ndim != 4 or hits.shape[3] != 4:
+        raise ValueError("hits must be (rows, W, max_images, 4)")
+    nh = None
+    if n_hits is not None:
+        nh = np.ascontiguousarray(n_hits, dtype=np.uint8)
+        if nh.shape != hits.shape[:2]:
+            raise ValueError("n_hits must be (rows, W)")
+    return hits, nh
+
+
+def shade_hotspot(hits, n_hits, metric, disk, spot, t_obs, base=None, channels=None, want=("rgb", "rgba")):
+    """The frame at observer time t_obs from stored hits (lt_shade_hotspot).  base: (rows, W) or (rows, W, 3) float32
+    or None (black; `channels` 1 or 3 then picks the output's shape, default 3).  -> dict(rgb, rgba)."""
+    hits, nh = _hit_arrays(hits, n_hits)
+    R, W, m = hits.shape[:3]
+    b, gray = None, False
+    nch = 3 if channels is None else int(channels)
+    if base is not None:
+        b = np.ascontiguousarray(base, dtype=np.float32)
+        if b.shape[:2] != (R, W):
+            raise ValueError("base must have the hits' rows and width")
+        nch = 1 if b.ndim == 2 else b.shape[2]
+    gray = nch == 1 and (b is None or b.ndim == 2)
+    out = {}
+    if "rgb" in want:
+        out["rgb"] = np.empty((R, W) if gray else (R, W, nch), dtype=np.float32)
+    if "rgba" in want:
+        out["rgba"] = np.empty((R, W, 4), dtype=np.uint8)
+    _check(load().lt_shade_hotspot(_np_ptr(hits), _np_ptr(nh), R, W, m, C.byref(metric), C.byref(disk), C.byref(spot),
+                                   float(t_obs), _np_ptr(b), nch, _np_ptr(out.get("rgb")), _np_ptr(out.get("rgba"))))
+    return out
+
+
+def shade_hotspot_dev(d_hits, d_n_hits, rows, width, max_images, metric, disk, spot, t_obs, d_base=0, channels=3, d_rgb=0,
+                      d_rgba=0):
+    """Device-pointer form of shade_hotspot (lt_shade_hotspot_dev); enqueues on the default stream."""
+    _check(load().lt_shade_hotspot_dev(_p(d_hits), _p(d_n_hits), rows, width, max_images, C.byref(metric), C.byref(disk),
+                                       C.byref(spot), float(t_obs), _p(d_base), channels, _p(d_rgb), _p(d_rgba)))
+
+
+def hotspot_lightcurve(hits, n_hits, metric, disk, spot, t_start, dt, n_times):
+    """The spot's light curve (lt_hotspot_lightcurve) -> (n_times, 3) float64: per time the sums of e, e ix, e iy."""
+    hits, nh = _hit_arrays(hits, n_hits)
+    R, W, m = hits.shape[:3]
+    out = np.empty((int(n_times), 3))
+    _check(load().lt_hotspot_lightcurve(_np_ptr(hits), _np_ptr(nh), R, W, m, C.byref(metric), C.byref(disk), C.byref(spot),
+                                        float(t_start), float(dt), int(n_times), _np_ptr(out)))
+    return out
+
+
+def hotspot_lightcurve_dev(d_hits, d_n_hits, rows, width, max_images, metric, disk, spot, t_start, dt, n_times, d_out):
+    """Device-pointer form of hotspot_lightcurve (lt_hotspot_lightcurve_dev); enqueues on the default stream."""
+    _check(load().lt_hotspot_lightcurve_dev(_p(d_hits), _p(d_n_hits), rows, width, max_images, C.byref(metric),
+                                            C.byref(disk), C.byref(spot), float(t_start), float(dt), int(n_times), _p(d_out)))
 
 
 # ---- supersampled frames (lt_render_aa) ---------------------------------------------------------------------------

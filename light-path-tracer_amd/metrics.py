@@ -295,6 +295,15 @@ class Kerr(Metric):
                                             axis_refines=axis_refines, integrator=self.integrator,
                                             precision=self.precision)
 
+    def trace_rays_batch_disk_hits(self, r_obs, alphas, thetas, theta_obs, disk, max_images=None, axis_refines=None):
+        """trace_rays_batch_disk_images with the light-travel time of every hit: 'hits' (n, max_images, 4) float64
+        (r_hit, phi_hit, g, time from the hit to the camera) in place of 'images' (lt_trace_batch_kerr_disk_hits)."""
+        d = disk.to_lt() if hasattr(disk, "to_lt") else disk
+        m = max_images if max_images is not None else getattr(disk, "max_images", 3)
+        return ltrace.trace_batch_kerr_disk_hits(self.M, self.a, r_obs, alphas, thetas, theta_obs,
+                                                 self._lambda_max(r_obs), d, max_images=m, axis_refines=axis_refines,
+                                                 integrator=self.integrator, precision=self.precision)
+
     def trace_rays_batch_disk_images(self, r_obs, alphas, thetas, theta_obs, disk, max_images=None, axis_refines=None):
         """trace_rays_batch with the optically thin disk (disk.TransparentDisk, or ltrace.Disk with max_images),
         direct schedule -> dict(fa, winding, status (trace_rays_batch's), images (n, max_images, 3) float64
