@@ -126,6 +126,16 @@ def test_partial_steps_add_up():
         assert lam.size == h.size + 1
 
 
+def test_frame_sample_excludes_few():
+    """The sample of tests/test_gpu_hit_time.py::test_frame_times_against_the_truth is drawn and thinned from the truth
+    alone, so its condition -- 150 pixels with a crossing, at most 2 % of them excluded -- is checked here, without a GPU."""
+    import test_gpu_hit_time as g
+    sample, keep = g.frame_sample_kept()
+    assert len(sample) == g.FRAME_SAMPLE and len(keep) >= 0.98 * len(sample)
+    assert len({(iy, ix) for iy, ix, _ in sample}) == len(sample)
+    assert sum(len(t["hits"]) > 1 for _, _, t in keep) >= 5      # slot 1 is compared as well
+
+
 def _hits(seed=3, shape=(12, 10, 3)):
     """A synthetic hit buffer: r in [2, 20], phi in [0, 2 pi), g in [0.2, 1.4], dt in [40, 200]; about a third of the
     slots unused (NaN), leading slots first."""
