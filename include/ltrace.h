@@ -517,6 +517,94 @@ int lt_hotspot_lightcurve(const float *hits, const uint8_t *n_hits, int32_t R, i
                           const lt_metric *metric, const lt_disk *disk, const lt_hotspot *spot, double t_start, double dt,
                           int32_t n_times, double *out);
 
+/* ---- linear polarization of the disk's images and hot-spot Q-U loops --------------------------------------- *
+ * lt_trace_disk_pol is lt_trace_disk_hits' trace with one more record per hit: (q, u, sin zeta, mu), the direction  *
+ * of linear polarization at the camera and two angles at the emitter.  No equation is added to the ray: in Kerr the *
+ * complex Walker-Penrose constant kappa of (k, f) is conserved along a null geodesic, so the polarization at the    *
+ * camera is a closed-form function of the state at the hit and the state at the camera.  The integrate kernel keeps *
+ * (p_r, p_theta) of every stored hit; a float64 epilogue does the rest.                                             *
+ *                                                                                                               *
+ * The photon.  The tracers integrate the backward ray with E = 1, L = p_phi; the photon the camera receives has, at  *
+ * a point of the ray, the covariant momentum k = (-1, -p_r, -p_theta, L) -- the reading under which g uses xi = L.  *
+ *                                                                                                               *
+ * Emitter.  The disk's material: the circular equatorial geodesic in +phi, Omega and u^t as in lt_render_disk.  Its  *
+ * orthonormal frame at the hit (theta = pi/2, Sigma = r^2): e_(r) = (0, sqrt(Delta)/r, 0, 0), e_(z) = -d_theta / r,  *
+ * e_(phi) the unit vector of the t-phi plane orthogonal to u, ~ (-u_phi, 0, 0, u_t), signed so that its phi part is  *
+ * positive.  The field has constant components (b_r, b_phi, b_z) in that frame; only its direction matters.  With    *
+ * k^ the unit spatial part of k in the frame (components on e_(r), e_(phi), e_(z), a right-handed triad):            *
+ *   sin zeta = |k^ x b^|,  f = (k^ x b^) / sin zeta, lifted by the triad (no time part in the frame, so f.k = 0),      *
+ *   mu = |k^ . e_(z)|;  where sin^2 zeta < 1e-24 the record is q = u = sin zeta = 0.                                  *
+ *                                                                                                               *
+ * Transport.  With contravariant components, at (r, theta),                                                       *
+ *   kappa = (A - i B)(r - i a cos theta),                                                                          *
+ *   A = (k^t f^r - k^r f^t) + a sin^2 theta (k^r f^phi - k^phi f^r),                                                *
+ *   B = [ (r^2 + a^2)(k^phi f^theta - k^theta f^phi) - a (k^t f^theta - k^theta f^t) ] sin theta.                    *
+ * One function evaluates it at both ends, so a sign or conjugation convention cancels.                              *
+ *                                                                                                               *
+ * Camera.  The static observer at (r_obs, theta_obs) (LT_ERR_INVALID_ARG where g_tt >= 0 there, or on the axis):     *
+ * e_t ~ d_t, e_r ~ d_r, e_theta ~ d_theta, e_phi ~ d_phi - (g_tphi / g_tt) d_t.  The camera-end momentum is the      *
+ * ray's own initial record and its L.  With n^ the unit spatial direction of k in that tetrad, the screen basis is   *
+ * north e_2 ~ -e_theta + n^theta n^ and e_1 = e_2 x n^ in the right-handed triad (r, theta, phi).  For a camera that  *
+ * looks at the hole with psi = 0, e_1 ~ +e_phi points towards decreasing column index (the rays with L > 0 are at    *
+ * the larger columns) and e_2 towards increasing row index (the rays that leave the camera southward, p_theta > 0,   *
+ * are at the smaller rows).  Real (x, y) solve x kappa(e_1) + y kappa(e_2) = kappa_hit; then                          *
+ *   q = (x^2 - y^2) / (x^2 + y^2) = cos 2 chi,  u = 2 x y / (x^2 + y^2) = sin 2 chi,                                   *
+ * chi the electric vector's angle from e_1 towards e_2.  No angle is stored, so there is no branch cut.               *
+ *                                                                                                               *
+ * Stokes parameters.  Per stored slot, e = the mean of the three channels of the light the slot contributes (the     *
+ * disk's E^disk if with_disk, plus the spot's E_spot, both unclamped):                                              *
+ *   I += e,  Q += Pi sin^2 zeta e q,  U += Pi sin^2 zeta e u,                                                        *
+ * Pi = pol_frac in [0, 1].  Nothing is clamped and there is no base.  disk.polarization / disk.stokes_frame /        *
+ * disk.stokes_lightcurve (Python) state all of it in numpy; lt_polarization_probe runs the device's rule.           *
+ *                                                                                                               *
+ * Out of scope: supersampled polarized frames, lt_render_multi and the multi-process path, circular polarization   *
+ * and Faraday effects.                                                                                            */
+typedef struct lt_bfield {
+    double b_r, b_phi, b_z; /* components in the emitter's frame; not all zero (LT_ERR_INVALID_ARG otherwise) */
+    double pol_frac;        /* Pi, in [0, 1] */
+} lt_bfield;
+void lt_default_bfield(lt_bfield *field); /* (0, 0, 1), pol_frac 0.7 */
+
+/* lt_trace_disk_hits_dev plus d_pol (R, W, max_images, 4) float32 (q, u, sin zeta, mu), NaN in unused slots.  Every
+ * output and stats word it shares with lt_trace_disk_hits_dev equals that call's bit for bit.  Configurations,
+ * partitions and refusals as there. */
+int lt_trace_disk_pol_dev(const lt_camera *cam, const lt_metric *metric, const lt_opts *opts, const lt_disk *disk,
+                          const lt_bfield *field, int32_t max_images, float *d_fa, uint16_t *d_w, int8_t *d_status,
+                          uint32_t *d_steps, float *d_hits, uint8_t *d_n_hits, float *d_pol, uint64_t *d_stats);
+/* The same with HOST pointers. */
+int lt_trace_disk_pol(const lt_camera *cam, const lt_metric *metric, const lt_opts *opts, const lt_disk *disk,
+                      const lt_bfield *field, int32_t max_images, float *out_fa, uint16_t *out_w, int8_t *out_status,
+                      uint32_t *out_steps, float *out_hits, uint8_t *out_n_hits, float *out_pol, lt_stats *stats);
+/* lt_trace_batch_kerr_disk_hits plus out_pol (n, max_images, 4) float64. */
+int lt_trace_batch_kerr_disk_pol(double M, double a, double r_obs, const double *alphas, const double *thetas,
+                                 double theta_obs, double lambda_max, const uint8_t *axis_refines, int integrator,
+                                 int precision, const lt_disk *disk, const lt_bfield *field, int32_t max_images, int64_t n,
+                                 double *out_fa, int64_t *out_w, int8_t *out_status, double *out_hits, int32_t *out_n_hits,
+                                 double *out_pol, uint32_t *out_rhs_evals);
+/* The device's own rule on n synthetic records, for parity tests: p_phi (n), hit (n, 3: r, p_r, p_theta of the backward
+ * ray at the hit), cam (n, 2: its p_r, p_theta at the camera), out (n, 4: q, u, sin zeta, mu), float64 HOST arrays. */
+int lt_polarization_probe(const lt_metric *metric, double r_obs, double theta_obs, const lt_bfield *field,
+                          const double *p_phi, const double *hit, const double *cam, int64_t n, double *out);
+/* The Stokes frame at observer time t_obs from stored records: hits and n_hits as lt_shade_hotspot takes them, pol
+ * (R, W, max_images, 4) float32 as lt_trace_disk_pol wrote it; out_iqu (R, W, 3) float32 = (I, Q, U), summed in float64
+ * over the stored slots in order.  The _dev form takes DEVICE pointers and enqueues on the default stream. */
+int lt_shade_stokes_dev(const float *d_hits, const uint8_t *d_n_hits, const float *d_pol, int32_t R, int32_t W,
+                        int32_t max_images, const lt_metric *metric, const lt_disk *disk, const lt_hotspot *spot,
+                        const lt_bfield *field, double t_obs, float *d_iqu);
+int lt_shade_stokes(const float *hits, const uint8_t *n_hits, const float *pol, int32_t R, int32_t W, int32_t max_images,
+                    const lt_metric *metric, const lt_disk *disk, const lt_hotspot *spot, const lt_bfield *field, double t_obs,
+                    float *out_iqu);
+/* The spot's Stokes light curve at t_start + i dt, i < n_times (<= 65535): out (n_times, 3) float64 = per time the sums
+ * of I, Q, U of the spot alone over all pixels and stored slots.  lt_hotspot_lightcurve's two-stage reduction in its
+ * fixed order, without floating-point atomics: bitwise the same run to run, and column 0 has the bits of
+ * lt_hotspot_lightcurve's column 0. */
+int lt_hotspot_lightcurve_stokes_dev(const float *d_hits, const uint8_t *d_n_hits, const float *d_pol, int32_t R, int32_t W,
+                                     int32_t max_images, const lt_metric *metric, const lt_disk *disk, const lt_hotspot *spot,
+                                     const lt_bfield *field, double t_start, double dt, int32_t n_times, double *d_out);
+int lt_hotspot_lightcurve_stokes(const float *hits, const uint8_t *n_hits, const float *pol, int32_t R, int32_t W,
+                                 int32_t max_images, const lt_metric *metric, const lt_disk *disk, const lt_hotspot *spot,
+                                 const lt_bfield *field, double t_start, double dt, int32_t n_times, double *out);
+
 /* ---- supersampled (anti-aliased) frames, resolved on the GPU ------------------------------------------- *
  * Every frame above is one ray per pixel, taken at the pixel's corner.  These entry points trace S x S rays per       *
  * pixel and write only the resolved pixels: nothing of the S^2 times larger frame crosses PCIe or stays in memory.    *

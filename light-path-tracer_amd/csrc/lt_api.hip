@@ -9,6 +9,7 @@
 #include "lt_disk_images.hpp"
 #include "lt_hit_time.hpp"
 #include "lt_hotspot.hpp"
+#include "lt_polarization.hpp"
 #include "lt_aa.hpp"
 #include "lt_aa_adaptive.hpp"
 #ifdef LT_PROBES
@@ -139,6 +140,7 @@ struct StreamSlot {
     Grow blocks; // block-owner table mode: this partition's block list on the device
     Grow disk_img; // lt_render_disk_images / its batch twin: the integrate kernel's hit records and counts
     Grow disk_time; // lt_trace_disk_hits / its batch twin: the integrate kernel's hit times
+    Grow disk_mom;  // lt_trace_disk_pol / its batch twin: the integrate kernel's hit momenta
     Grow hotspot;   // lt_hotspot_lightcurve: the first stage's partial sums
     std::vector<int32_t> blocks_host; // what `blocks` holds (skip the upload when unchanged)
     EventQuad own{}; // lt_render's private timing events (created on first use)
@@ -226,7 +228,7 @@ static void release(Grow &g)
 // Everything a slot owns, and the slot.  The caller has drained the slot's stream and taken the slot off its list.
 static void destroy_slot(StreamSlot *sl)
 {
-    for (Grow *g : {&sl->ws, &sl->dev, &sl->dense, &sl->blocks, &sl->disk_img, &sl->disk_time, &sl->hotspot, &sl->aa_list, &sl->aa_scratch}) release(*g);
+    for (Grow *g : {&sl->ws, &sl->dev, &sl->dense, &sl->blocks, &sl->disk_img, &sl->disk_time, &sl->disk_mom, &sl->hotspot, &sl->aa_list, &sl->aa_scratch}) release(*g);
     if (sl->own_ok) for (auto &e : sl->own.e) (void)hipEventDestroy(e);
     for (auto &q : sl->aa_events) for (auto &e : q.e) (void)hipEventDestroy(e);
     delete sl;
@@ -671,6 +673,7 @@ template <typename T> struct PlainKernels { template <typename Integ> static con
 template <typename T> struct DiskKernels { template <typename Integ> static constexpr auto kernel = &k_kerr_disk<T, Integ>; };
 template <typename T> struct DiskImagesKernels { template <typename Integ> static constexpr auto kernel = &k_kerr_disk_images<T, Integ>; };
 template <typename T> struct DiskTimedKernels { template <typename Integ> static constexpr auto kernel = &k_kerr_disk_timed<T, Integ>; };
+template <typename T> struct DiskPolKernels { template <typename Integ> static constexpr auto kernel = &k_kerr_disk_pol<T, Integ>; };
 template <typename Integ> struct IntegTag { using type = Integ; };
 
 // The switches of the direct schedule, read once.
@@ -810,12 +813,16 @@ struct DiskParams {
     uint8_t *d_n_hits = nullptr;     // (R, W) or NULL
     bool timed = false;              // lt_trace_disk_hits (lt_api_hotspot.inc): d_images is (R, W, max_images, 4), no colour
     int image_words() const { return timed ? 4 : 3; }
+    bool pol = false;                // lt_trace_disk_pol (lt_api_polarization.inc): the timed trace plus d_pol
+    PolConsts pc{};                  // ... its observer and field
+    void *d_pol = nullptr;           // (R, W, max_images, 4) float32, or (n, max_images, 4) float64 in a batch, or NULL
 };
 // The hit records of the thin disk, resolved once per call (get_disk_records) and handed to its launches.
 struct DiskRecordsBuf {
     void *p = nullptr;        // Vec2<T> [max_images][n_q]
     uint32_t *hits = nullptr; // [n_q]
     void *tim = nullptr;      // the timed trace: T [max_images][n_q]
+    void *mom = nullptr;      // the polarized trace: Vec2<T> [max_images][n_q]
     template <typename T> typename Vec2<T>::type *img() const { return (typename Vec2<T>::type *)p; }
 };
 // The disks' launches, defined in lt_api_disk.inc and lt_api_disk_images.inc (which in turn call the frame plumbing below).
@@ -1238,7 +1245,8 @@ struct FrameStaging : Staging {
 static int render_host_impl(const lt_camera *cam, const lt_metric *metric, const lt_opts *opts, const float *bg,
                             int32_t bg_channels, float *out_fa, uint16_t *out_w, int8_t *out_status, uint32_t *out_steps,
                             float *out_rgb, uint8_t *out_rgba, lt_stats *stats, const DiskParams *disk = nullptr,
-                            float *out_disk = nullptr, float *out_images = nullptr, uint8_t *out_n_hits = nullptr)
+                            float *out_disk = nullptr, float *out_images = nullptr, uint8_t *out_n_hits = nullptr,
+                            float *out_pol = nullptr)
 {
     int rc = require_device();
     if (rc) return rc;
@@ -1256,15 +1264,19 @@ static int render_host_impl(const lt_camera *cam, const lt_metric *metric, const
     fs.declare(&st, bg, bg_channels, (size_t)cam->height * cam->width, n, out_fa, out_w, out_status, out_steps, out_rgb, out_rgba);
     const int i_disk = fs.out(out_disk, n, 3 * 4);
     const int i_img = fs.out(out_images, n, disk ? (size_t)disk->max_images * disk->image_words() * 4 : 0), i_hits = fs.out(out_n_hits, n, 1);
+    const int i_pol = fs.out(out_pol, n, disk ? (size_t)disk->max_images * 16 : 0);
     if ((rc = fs.commit((hipStream_t)o.stream))) return rc;
     DiskParams dp{};
     if (disk) {
         dp = *disk;
         dp.d_disk = fs.dev<float>(i_disk); dp.d_images = fs.dev<float>(i_img); dp.d_n_hits = fs.dev<uint8_t>(i_hits);
+        dp.d_pol = fs.dev<float>(i_pol);
     }
     if ((rc = fs.render(cam, metric, o, bg_channels, disk ? &dp : nullptr))) return rc;
     for (int i : fs.fetch_order()) if ((rc = fs.fetch(i))) return rc;
-    if ((rc = fs.fetch(i_disk)) || (rc = fs.fetch(i_img)) || (rc = fs.fetch(i_hits)) || (rc = fs.fetch(fs.stats))) return rc;
+    if ((rc = fs.fetch(i_disk)) || (rc = fs.fetch(i_img)) || (rc = fs.fetch(i_hits)) || (rc = fs.fetch(i_pol)) ||
+        (rc = fs.fetch(fs.stats)))
+        return rc;
     HIP_TRY(hipStreamSynchronize(fs.s));
     if (rows > 0) {
         float ms[3] = {0, 0, 0};
@@ -1387,7 +1399,7 @@ extern "C" int lt_render_multi(const lt_camera *cam, const lt_metric *metric, co
 static int trace_batch(const MetricConsts &mc, lt_opts &o, double lambda_max, const double *alphas, const double *thetas,
                        const uint8_t *refines, int64_t n, double *out_fa, int64_t *out_w, int8_t *out_status,
                        uint32_t *out_evals, const DiskParams *disk = nullptr, double *out_disk = nullptr,
-                       double *out_images = nullptr, int32_t *out_n_hits = nullptr)
+                       double *out_images = nullptr, int32_t *out_n_hits = nullptr, double *out_pol = nullptr)
 {
     int rc;
     if (n < 0) return fail(LT_ERR_INVALID_ARG, "negative ray count");
@@ -1409,6 +1421,7 @@ static int trace_batch(const MetricConsts &mc, lt_opts &o, double lambda_max, co
     const int i_fa = st.out(out_fa, n, 8), i_w = st.out(out_w, n, 8), i_st = st.out(out_status, n, 1), i_ev = st.out(out_evals, n, 4);
     const int i_disk = st.out(out_disk, n, 3 * 8);
     const int i_img = st.out(out_images, n, disk ? (size_t)disk->max_images * disk->image_words() * 8 : 0), i_hits = st.out(out_n_hits, n, 4);
+    const int i_pol = st.out(out_pol, n, disk ? (size_t)disk->max_images * 32 : 0);
     if ((rc = st.commit(s))) return rc;
     double *d_fa = st.dev<double>(i_fa); int64_t *d_w = st.dev<int64_t>(i_w);
     int8_t *d_st = st.dev<int8_t>(i_st); uint32_t *d_ev = st.dev<uint32_t>(i_ev);
@@ -1419,6 +1432,8 @@ static int trace_batch(const MetricConsts &mc, lt_opts &o, double lambda_max, co
     });
     HIP_TRY(hipGetLastError());
     if ((rc = launch_integrate_any(mc, o, lambda_max, w, n_q, s, nullptr, disk, recs))) return rc;
+    DiskParams dp_batch{};
+    if (disk) { dp_batch = *disk; dp_batch.d_pol = st.dev<double>(i_pol); disk = &dp_batch; }
     if (disk && disk->max_images) {
         if ((rc = launch_epilogue_arrays_disk_images(mc, o, w, n, d_fa, d_w, d_st, d_ev, st.dev<double>(i_img), st.dev<int32_t>(i_hits), s,
                                                      *disk, recs)))
@@ -1438,7 +1453,7 @@ static int trace_batch(const MetricConsts &mc, lt_opts &o, double lambda_max, co
             });
     }
     HIP_TRY(hipGetLastError());
-    for (int i : {i_fa, i_w, i_st, i_ev, i_disk, i_img, i_hits}) if ((rc = st.fetch(i))) return rc;
+    for (int i : {i_fa, i_w, i_st, i_ev, i_disk, i_img, i_hits, i_pol}) if ((rc = st.fetch(i))) return rc;
     HIP_TRY(hipStreamSynchronize(s));
     return LT_OK;
 }
@@ -1589,5 +1604,6 @@ extern "C" int lt_scatter_rows_indexed_dev(const void *d_rows, void *d_full, con
 #include "lt_api_disk.inc"
 #include "lt_api_disk_images.inc"
 #include "lt_api_hotspot.inc"
+#include "lt_api_polarization.inc"
 #include "lt_api_aa.inc"
 #include "lt_api_aa_adaptive.inc"

@@ -82,6 +82,11 @@ static int launch_integrate_disk(const MetricConsts &mc, const lt_opts &o, doubl
 {
     const KerrConsts<T> k = make_kerr<T>(mc, lambda_max, o.h_max);
     const DiskConsts<T> d{(T)dp.r_in, (T)dp.r_out, (T)(1.0 / (mc.r_plus * mc.r_plus))};
+    if (dp.pol)
+        return launch_direct<T, DiskPolKernels<T>>(o, w, n_q, s, 64, [&](auto kernel, unsigned grid, uint32_t long_iters, unsigned long long *head) {
+            kernel<<<grid, 64, 0, s>>>(k, d, w.ic<T>(), w.fin0<T>(), w.fin1<T>(), n_q, long_iters, kstats, head, recs.img<T>(), recs.hits,
+                                       dp.max_images, (T *)recs.tim, (typename Vec2<T>::type *)recs.mom);
+        });
     if (dp.timed)
         return launch_direct<T, DiskTimedKernels<T>>(o, w, n_q, s, 64, [&](auto kernel, unsigned grid, uint32_t long_iters, unsigned long long *head) {
             kernel<<<grid, 64, 0, s>>>(k, d, w.ic<T>(), w.fin0<T>(), w.fin1<T>(), n_q, long_iters, kstats, head, recs.img<T>(), recs.hits,

@@ -21,6 +21,10 @@ static int get_disk_records(hipStream_t s, int64_t n_q, size_t elem, const DiskP
         if ((rc = grow(sl->disk_time, img_bytes / 2, s))) return rc;
         recs->tim = sl->disk_time.p;
     }
+    if (disk->pol) {
+        if ((rc = grow(sl->disk_mom, img_bytes, s))) return rc;
+        recs->mom = sl->disk_mom.p;
+    }
     return LT_OK;
 }
 
@@ -30,6 +34,13 @@ static void launch_epilogue_disk_hits(const CamConsts &c, const MetricConsts &mc
 static void launch_epilogue_arrays_disk_hits(const MetricConsts &mc, const DiskShade &ds, const lt_opts &o, const Workspace &w, int64_t n,
                                              double *d_fa, int64_t *d_w, int8_t *d_st, uint32_t *d_ev, double *d_hits, int32_t *d_n_hits,
                                              hipStream_t s, const DiskParams &dp, const DiskRecordsBuf &recs);
+// ... and the polarized trace's (lt_api_polarization.inc).
+static void launch_epilogue_disk_pol(const CamConsts &c, const MetricConsts &mc, const DiskShade &ds, const lt_opts &o, const Workspace &w,
+                                     const FrameOut &fo, const DiskImagesOut &di, const DiskRecordsBuf &recs, hipStream_t s,
+                                     const DiskParams &dp);
+static void launch_epilogue_arrays_disk_pol(const MetricConsts &mc, const DiskShade &ds, const lt_opts &o, const Workspace &w, int64_t n,
+                                            double *d_fa, int64_t *d_w, int8_t *d_st, uint32_t *d_ev, double *d_hits, int32_t *d_n_hits,
+                                            hipStream_t s, const DiskParams &dp, const DiskRecordsBuf &recs);
 
 static int launch_epilogue_disk_images(const CamConsts &c, const MetricConsts &mc, const lt_opts &o, const Workspace &w,
                                        const FrameOut &fo, uint64_t *d_stats, hipStream_t s, const DiskParams &dp,
@@ -37,7 +48,8 @@ static int launch_epilogue_disk_images(const CamConsts &c, const MetricConsts &m
 {
     const DiskShade ds{mc.M, mc.a, dp.r_in, dp.q, dp.exposure};
     const DiskImagesOut di{recs.p, recs.hits, (int64_t)w.n_q, dp.max_images, dp.d_images, dp.d_n_hits};
-    if (dp.timed) launch_epilogue_disk_hits(c, mc, ds, o, w, fo, di, recs, s);
+    if (dp.pol) launch_epilogue_disk_pol(c, mc, ds, o, w, fo, di, recs, s, dp);
+    else if (dp.timed) launch_epilogue_disk_hits(c, mc, ds, o, w, fo, di, recs, s);
     else launch_epilogue_rows(c, o, fo, [&](auto t, auto bg, dim3 ge) {
         using T = decltype(t);
         k_epilogue_disk_images<T, decltype(bg)::value><<<ge, EPILOGUE_BLOCK, 0, s>>>(c, mc, ds, w.fin0<T>(), w.fin1<T>(), fo, di);
@@ -52,7 +64,8 @@ static int launch_epilogue_arrays_disk_images(const MetricConsts &mc, const lt_o
                                               int32_t *d_n_hits, hipStream_t s, const DiskParams &dp, const DiskRecordsBuf &recs)
 {
     const DiskShade ds{mc.M, mc.a, dp.r_in, dp.q, dp.exposure};
-    if (dp.timed) launch_epilogue_arrays_disk_hits(mc, ds, o, w, n, d_fa, d_w, d_st, d_ev, d_images, d_n_hits, s, dp, recs);
+    if (dp.pol) launch_epilogue_arrays_disk_pol(mc, ds, o, w, n, d_fa, d_w, d_st, d_ev, d_images, d_n_hits, s, dp, recs);
+    else if (dp.timed) launch_epilogue_arrays_disk_hits(mc, ds, o, w, n, d_fa, d_w, d_st, d_ev, d_images, d_n_hits, s, dp, recs);
     else with_precision(o.precision, [&](auto t) {
         using T = decltype(t);
         k_epilogue_arrays_disk_images<T><<<(unsigned)((n + 255) / 256), 256, 0, s>>>(mc, ds, w.fin0<T>(), w.fin1<T>(), n, d_fa, d_w, d_st, d_ev,

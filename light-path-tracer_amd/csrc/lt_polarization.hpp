@@ -1,0 +1,338 @@
+// lt_polarization.hpp -- linear polarization of the thin disk's images (include/ltrace.h, "linear polarization"): the
+// hooks that keep a hit's momenta (DiskPolStep), the kernel k_kerr_disk_pol, the float64 transport of the electric vector
+// from the hit to the camera by the Walker-Penrose constant (pol_camera, pol_record), the epilogues that write it, the
+// probe of the rule, and the Stokes siblings of the hot spot's kernels (k_shade_stokes, k_lightcurve_stokes_partial).
+//
+// No ODE is added: kappa = (A - i B)(r - i a cos theta) of (k, f) is conserved along a null geodesic of Kerr, so f at
+// the camera follows from the state at the hit and the state at the camera in closed form.  The trace is the timed
+// trace's (lt_hit_time.hpp) with one more record per stored hit, (p_r, p_theta), next to (r, phi) and the time.
+#pragma once
+#include "lt_hit_time.hpp"
+#include "lt_hotspot.hpp"
+
+namespace lt {
+
+// ---- K2 ---------------------------------------------------------------------------------------------------------------
+// DiskTimedStep plus mom[n * n_q + q] = (p_r, p_theta) of hit n, slot-major like img and tim and stored where they are:
+// by a real lane only, below max_images.  advance() is DiskTimedStep's, statement by statement, with that one store added
+// (a hook inside DiskTimedStep::advance would have changed k_kerr_disk_timed's code: tools/kernel_diff.sh).
+template <typename T, typename Integ> struct DiskPolStep : DiskTimedStep<T, Integ> {
+    typename Vec2<T>::type *mom;
+    using Lane = typename DiskTimedStep<T, Integ>::Lane;
+    __device__ __forceinline__ int advance(Lane &l, const KerrConsts<T> &k, const RayConsts<T> &rc, typename Integ::State &st, int64_t q, bool real)
+    {
+        const State5<T> y0 = st.y;
+        const T lam0 = st.lam;
+        const T h_try = DiskStepLen<Integ>::h(k, rc, st);
+        if (!l.have) { l.rate = time_rates(k, rc, y0); l.have = true; }
+        const TimeRates<T> d0 = l.rate;
+        DiskHitStep<T> on;
+        const int ev = disk_advance<T, Integ>(k, this->d, rc, l.vmax2, st, real, [&](typename Integ::State &, const State5<T> &hit, int e) {
+            if (l.n < (uint32_t)this->max_images) {
+                const int64_t slot = (int64_t)l.n * this->n_q + q;
+                typename Vec2<T>::type v, p;
+                v.x = hit.r; v.y = hit.ph;
+                p.x = hit.pr; p.y = hit.pth;
+                this->img[slot] = v;
+                mom[slot] = p;
+                const T part = step_time(k, rc, y0, d0, on.y1, time_rates(k, rc, on.y1), on.h, on.tau);
+                this->tim[slot] = l.t_hi + (l.t_lo + part);
+            }
+            ++l.n;
+            return e;
+        }, &on);
+        const T h = st.lam != lam0 ? h_try : T(0);
+        l.rate = time_rates(k, rc, st.y);
+        const T dt = h != T(0) ? step_time(k, rc, y0, d0, st.y, l.rate, h, T(1)) : T(0);
+        const T sum = l.t_hi + dt, bb = sum - l.t_hi;
+        l.t_lo += (l.t_hi - (sum - bb)) + (dt - bb);
+        l.t_hi = sum;
+        return ev;
+    }
+};
+
+// (A kernel of its own, as k_kerr_disk_timed is: every other kernel keeps its code and name.)
+template <typename T, typename Integ>
+__global__ void __launch_bounds__(256, Integ::MIN_WAVES_PER_SIMD) k_kerr_disk_pol(KerrConsts<T> k_in, DiskConsts<T> d,
+                                                       const typename Vec4<T>::type *__restrict__ ic,
+                                                       typename Vec4<T>::type *__restrict__ fin0,
+                                                       typename Vec4<T>::type *__restrict__ fin1, int64_t n_q,
+                                                       uint32_t long_iters, uint64_t *__restrict__ kstats,
+                                                       unsigned long long *__restrict__ head,
+                                                       typename Vec2<T>::type *__restrict__ img, uint32_t *__restrict__ hits,
+                                                       int max_images, T *__restrict__ tim,
+                                                       typename Vec2<T>::type *__restrict__ mom)
+{
+    DiskPolStep<T, Integ> step;
+    step.d = d;
+    step.img = img; step.hits = hits; step.n_q = n_q; step.max_images = max_images; step.tim = tim; step.mom = mom;
+    direct_tiles<T, Integ>(k_in, step, ic, fin0, fin1, n_q, long_iters, nullptr, kstats, head);
+}
+
+// ---- the rule, float64 ----------------------------------------------------------------------------------------------------
+// Written operation by operation as disk.polarization (Python) states it; the compiler contracts multiply-adds, so the two
+// differ by rounding (tests/test_gpu_polarization.py bounds it by float64's own error on the same records).
+struct PolConsts {
+    double M, a;
+    double r_obs, s_obs, c_obs; // the static observer: r, sin theta, cos theta
+    double b[3];                // unit field on (e_r, e_phi, e_z) of the emitter
+};
+
+// Contravariant components of the covector k at (r, theta); s = sin theta, c = cos theta.
+__device__ __forceinline__ void pol_raise(double M_, double a, double r, double s, double c, const double *k, double *out)
+{
+    const double s2 = s * s;
+    const double sigma = r * r + a * a * c * c;
+    const double delta = r * r - 2.0 * M_ * r + a * a;
+    const double sd = sigma * delta;
+    const double x = r * r + a * a;
+    const double gtt = -(x * x - a * a * delta * s2) / sd;
+    const double gtp = -2.0 * M_ * a * r / sd;
+    const double gpp = (delta - a * a * s2) / (sd * s2);
+    out[0] = gtt * k[0] + gtp * k[3];
+    out[1] = delta / sigma * k[1];
+    out[2] = k[2] / sigma;
+    out[3] = gtp * k[0] + gpp * k[3];
+}
+
+// kappa = (A - i B)(r - i a cos theta) of contravariant k, f: one function for both ends, so that a sign or conjugation
+// convention cancels.
+__device__ __forceinline__ void walker_penrose(double a, double r, double s, double c, const double *k, const double *f, double &re, double &im)
+{
+    const double A = (k[0] * f[1] - k[1] * f[0]) + a * s * s * (k[1] * f[3] - k[3] * f[1]);
+    const double B = ((r * r + a * a) * (k[3] * f[2] - k[2] * f[3]) - a * (k[0] * f[2] - k[2] * f[0])) * s;
+    re = A * r - B * a * c;
+    im = -(A * a * c + B * r);
+}
+
+// The camera end of one ray: kappa of the two screen vectors.  North e_2 ~ -e_theta + n^theta n, e_1 = e_2 x n in the
+// right-handed static tetrad (r, theta, phi); pr, pth: the backward ray's momenta at the camera (its ic record).
+struct PolCamera { double k1re, k1im, k2re, k2im; };
+__device__ __forceinline__ PolCamera pol_camera(const PolConsts &pc, double L, double pr, double pth)
+{
+    const double M_ = pc.M, a = pc.a, r = pc.r_obs, s = pc.s_obs, c = pc.c_obs;
+    const double sigma = r * r + a * a * c * c;
+    const double delta = r * r - 2.0 * M_ * r + a * a;
+    const double g_tt = -(1.0 - 2.0 * M_ * r / sigma);
+    const double g_tp = -2.0 * M_ * a * r * s * s / sigma;
+    const double g_pp = (r * r + a * a + 2.0 * M_ * a * a * r * s * s / sigma) * s * s;
+    const double w = -g_tp / g_tt;
+    const double n_phi = sqrt(g_pp - g_tp * g_tp / g_tt);
+    const double e_r = sqrt(delta / sigma), e_th = 1.0 / sqrt(sigma);
+    double n[3] = {-e_r * pr, -e_th * pth, (L - w) / n_phi};
+    const double nn = sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+    for (int i = 0; i < 3; ++i) n[i] = n[i] / nn;
+    double e2[3] = {n[1] * n[0], n[1] * n[1] - 1.0, n[1] * n[2]};
+    const double en = sqrt(e2[0] * e2[0] + e2[1] * e2[1] + e2[2] * e2[2]);
+    for (int i = 0; i < 3; ++i) e2[i] = e2[i] / en;
+    const double e1[3] = {e2[1] * n[2] - e2[2] * n[1], e2[2] * n[0] - e2[0] * n[2], e2[0] * n[1] - e2[1] * n[0]};
+    const double f1[4] = {e1[2] * w / n_phi, e1[0] * e_r, e1[1] * e_th, e1[2] / n_phi};
+    const double f2[4] = {e2[2] * w / n_phi, e2[0] * e_r, e2[1] * e_th, e2[2] / n_phi};
+    const double kc[4] = {-1.0, -pr, -pth, L};
+    double k[4];
+    pol_raise(M_, a, r, s, c, kc, k);
+    PolCamera o;
+    walker_penrose(a, r, s, c, k, f1, o.k1re, o.k1im);
+    walker_penrose(a, r, s, c, k, f2, o.k2re, o.k2im);
+    return o;
+}
+
+// The record of one hit (r, p_r, p_theta of the backward ray at theta = pi / 2): out = (q, u, sin zeta, mu).
+__device__ __forceinline__ void pol_record(const PolConsts &pc, const PolCamera &cam, double L, double r, double pr, double pth, double *out)
+{
+    const double M_ = pc.M, a = pc.a;
+    // the emitter's frame: e_(r) = (0, sqrt(Delta) / r, 0, 0), e_(z) = -d_theta / r, e_(phi) = (ept, 0, 0, epp)
+    const double delta = r * r - 2.0 * M_ * r + a * a;
+    const double g_tt = -(1.0 - 2.0 * M_ / r), g_tp = -2.0 * M_ * a / r, g_pp = r * r + a * a + 2.0 * M_ * a * a / r;
+    const double sM = sqrt(M_), sr = sqrt(r);
+    const double r15 = r * sr;
+    const double om = sM / (r15 + a * sM);
+    const double ut = (r15 + a * sM) / (sqrt(r15) * sqrt(r15 - 3.0 * M_ * sr + 2.0 * a * sM));
+    const double u_t = ut * (g_tt + g_tp * om), u_p = ut * (g_tp + g_pp * om);
+    const double nrm = sqrt(g_tt * u_p * u_p - 2.0 * g_tp * u_p * u_t + g_pp * u_t * u_t);
+    const double er = sqrt(delta) / r, ept = u_p / nrm, epp = -u_t / nrm;
+    // the received photon k = (-1, -p_r, -p_theta, L) on the triad, and f = (k^ x b^) / sin zeta
+    double kr = -er * pr, kp = epp * L - ept, kz = pth / r;
+    const double kn = sqrt(kr * kr + kp * kp + kz * kz);
+    kr = kr / kn; kp = kp / kn; kz = kz / kn;
+    const double cr = kp * pc.b[2] - kz * pc.b[1], cp = kz * pc.b[0] - kr * pc.b[2], cz = kr * pc.b[1] - kp * pc.b[0];
+    const double s2 = cr * cr + cp * cp + cz * cz;
+    out[3] = fabs(kz);
+    if (s2 < 1e-24) { out[0] = out[1] = out[2] = 0.0; return; }
+    const double inv = 1.0 / sqrt(s2);
+    const double fr = cr * inv, fp = cp * inv, fz = cz * inv;
+    const double kc[4] = {-1.0, -pr, -pth, L};
+    double k[4];
+    pol_raise(M_, a, r, 1.0, 0.0, kc, k);
+    const double f[4] = {fp * ept, fr * er, -fz / r, fp * epp};
+    double hre, him;
+    walker_penrose(a, r, 1.0, 0.0, k, f, hre, him);
+    // real (x, y) with x kappa(e_1) + y kappa(e_2) = kappa_hit
+    const double det = cam.k1re * cam.k2im - cam.k2re * cam.k1im;
+    const double x = (hre * cam.k2im - cam.k2re * him) / det;
+    const double y = (cam.k1re * him - hre * cam.k1im) / det;
+    const double n2 = x * x + y * y;
+    out[0] = (x * x - y * y) / n2;
+    out[1] = 2.0 * x * y / n2;
+    out[2] = sqrt(s2);
+}
+
+// ---- K3 ---------------------------------------------------------------------------------------------------------------
+// The polarization records of one ray: slot j -> (q, u, sin zeta, mu), NaN in an unused slot.  Out: float or double.
+template <typename T, typename Out>
+__device__ __forceinline__ void store_pol(const PolConsts &pc, const typename Vec4<T>::type *__restrict__ ic,
+                                          const typename Vec2<T>::type *__restrict__ img, const typename Vec2<T>::type *__restrict__ mom,
+                                          int64_t n_q, int max_images, int64_t q, uint32_t nh, double L, Out *__restrict__ dst)
+{
+    PolCamera cam{};
+    if (nh > 0) {
+        const typename Vec4<T>::type rec = ic[q];
+        cam = pol_camera(pc, L, (double)rec.x, (double)rec.y);
+    }
+    for (int j = 0; j < max_images; ++j) {
+        double v4[4];
+        v4[0] = v4[1] = v4[2] = v4[3] = __builtin_nan("");
+        if ((uint32_t)j < nh) {
+            const typename Vec2<T>::type p = mom[(int64_t)j * n_q + q];
+            pol_record(pc, cam, L, (double)img[(int64_t)j * n_q + q].x, (double)p.x, (double)p.y, v4);
+        }
+        for (int i = 0; i < 4; ++i) dst[j * 4 + i] = (Out)v4[i];
+    }
+}
+
+// Epilogue of lt_trace_disk_pol_dev: k_epilogue_disk_hits plus pol (R, W, max_images, 4) float32.
+template <typename T>
+__global__ void __launch_bounds__(EPILOGUE_BLOCK) k_epilogue_disk_pol(CamConsts c, MetricConsts m, DiskShade ds, PolConsts pc,
+                                                                      const typename Vec4<T>::type *__restrict__ ic,
+                                                                      const typename Vec4<T>::type *__restrict__ fin0,
+                                                                      const typename Vec4<T>::type *__restrict__ fin1, FrameOut o,
+                                                                      DiskImagesOut di, const T *__restrict__ tim,
+                                                                      const typename Vec2<T>::type *__restrict__ mom, float *__restrict__ pol)
+{
+    const int lrow = (int)blockIdx.y, ix = (int)(blockIdx.x * EPILOGUE_BLOCK + threadIdx.x);
+    const int64_t p = (int64_t)lrow * c.W + ix;
+    StatAcc acc;
+    uint32_t nh = 0;
+    if (ix < c.W) {
+        const int64_t q = pixel_to_q(c, ix, lrow);
+        RayResult res;
+        load_result<T>(m, fin0, fin1, q, res);
+        acc.add(res);
+        nh = di.hits[q];
+        const long long wl = res.n_half < 0 ? 0 : (res.n_half > 65535 ? 65535 : res.n_half);
+        if (o.fa) o.fa[p] = (res.status == 1) ? (float)res.fa : __builtin_nanf("");
+        if (o.w) o.w[p] = (uint16_t)wl;
+        if (o.status) o.status[p] = (int8_t)res.status;
+        if (o.steps) o.steps[p] = res.steps;
+        if (di.n_hits) di.n_hits[p] = (uint8_t)(nh > 255u ? 255u : nh);
+        const typename Vec2<T>::type *img = (const typename Vec2<T>::type *)di.img;
+        const double xi = (double)fin1[q].y;
+        if (di.images) store_hits<T, float>(ds, img, tim, di.n_q, di.max_images, q, nh, xi, di.images + p * di.max_images * 4);
+        if (pol) store_pol<T, float>(pc, ic, img, mom, di.n_q, di.max_images, q, nh, xi, pol + p * di.max_images * 4);
+    }
+    flush_stats<8>(o.stats, acc, m, nh > 0, nh);
+}
+
+// Epilogue of lt_trace_batch_kerr_disk_pol: k_epilogue_arrays_disk_hits plus out_pol (n, max_images, 4) float64.
+template <typename T>
+__global__ void __launch_bounds__(256) k_epilogue_arrays_disk_pol(MetricConsts m, DiskShade ds, PolConsts pc,
+                                                                  const typename Vec4<T>::type *__restrict__ ic,
+                                                                  const typename Vec4<T>::type *__restrict__ fin0,
+                                                                  const typename Vec4<T>::type *__restrict__ fin1, int64_t n,
+                                                                  double *__restrict__ out_fa, int64_t *__restrict__ out_w,
+                                                                  int8_t *__restrict__ out_status, uint32_t *__restrict__ out_evals,
+                                                                  const typename Vec2<T>::type *__restrict__ img,
+                                                                  const uint32_t *__restrict__ hits, int64_t n_q, int max_images,
+                                                                  const T *__restrict__ tim, const typename Vec2<T>::type *__restrict__ mom,
+                                                                  double *__restrict__ out_hits, int32_t *__restrict__ out_n_hits,
+                                                                  double *__restrict__ out_pol)
+{
+    int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (q >= n) return;
+    RayResult res;
+    load_result<T>(m, fin0, fin1, q, res);
+    out_fa[q] = (res.status == 1) ? res.fa : __builtin_nan("");
+    out_w[q] = res.n_half;
+    if (out_status) out_status[q] = (int8_t)res.status;
+    if (out_evals) out_evals[q] = res.evals;
+    const uint32_t nh = hits[q];
+    if (out_n_hits) out_n_hits[q] = (int32_t)nh;
+    const double xi = (double)fin1[q].y;
+    if (out_hits) store_hits<T, double>(ds, img, tim, n_q, max_images, q, nh, xi, out_hits + q * max_images * 4);
+    if (out_pol) store_pol<T, double>(pc, ic, img, mom, n_q, max_images, q, nh, xi, out_pol + q * max_images * 4);
+}
+
+// lt_polarization_probe: the rule on n records given as hit (r, p_r, p_theta), camera (p_r, p_theta) and L.
+__global__ void k_polarization_probe(PolConsts pc, const double *__restrict__ L, const double *__restrict__ hit,
+                                     const double *__restrict__ cam, int64_t n, double *__restrict__ out)
+{
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const PolCamera pcam = pol_camera(pc, L[i], cam[i * 2], cam[i * 2 + 1]);
+    double v4[4];
+    pol_record(pc, pcam, L[i], hit[i * 3], hit[i * 3 + 1], hit[i * 3 + 2], v4);
+    for (int c = 0; c < 4; ++c) out[i * 4 + c] = v4[c];
+}
+
+// ---- Stokes siblings of the hot spot's kernels ---------------------------------------------------------------------------
+// Per stored slot, e the mean of the three channels of the slot's light: I += e, Q += w e q, U += w e u with
+// w = Pi sin^2 zeta, from the float32 records (pol: (q, u, sin zeta, mu) per slot), in float64.  No clamp, no base.
+__device__ __forceinline__ double stokes_weight(double pol_frac, const float *prec)
+{
+    return pol_frac * (double)prec[2] * (double)prec[2];
+}
+
+// One pixel per work-item: out (R, W, 3) float32 = (I, Q, U) at t_obs; the light is the disk's (with_disk) plus the spot's.
+__global__ void __launch_bounds__(256) k_shade_stokes(const float *__restrict__ hits, const uint8_t *__restrict__ n_hits,
+                                                      const float *__restrict__ pol, int64_t n_px, int max_images, DiskShade ds,
+                                                      HotspotShade hs, double pol_frac, double t_obs, float *__restrict__ out)
+{
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= n_px) return;
+    const float *rec = hits + p * max_images * 4, *prec = pol + p * max_images * 4;
+    const int ns = stored_slots(rec, n_hits, p, max_images);
+    double sum[3] = {0.0, 0.0, 0.0};
+    for (int j = 0; j < ns; ++j) {
+        double e[3], m;
+        hotspot_emission(hs, t_obs, rec + j * 4, e);
+        m = (e[0] + e[1] + e[2]) / 3.0;
+        if (hs.with_disk) {
+            disk_emission(ds, rec[j * 4], rec[j * 4 + 2], e);
+            m = (e[0] + e[1] + e[2]) / 3.0 + m;
+        }
+        const double w = stokes_weight(pol_frac, prec + j * 4);
+        sum[0] += m; sum[1] += w * (double)prec[j * 4] * m; sum[2] += w * (double)prec[j * 4 + 1] * m;
+    }
+    for (int c = 0; c < 3; ++c) out[p * 3 + c] = (float)sum[c];
+}
+
+// The Stokes light curve of the spot: k_lightcurve_partial's grid, stride and tree (lc_tree) with (I, Q, U) in place of
+// (e, e ix, e iy); the I column is summed exactly as that kernel's column 0, so it has its bits.
+__global__ void __launch_bounds__(256) k_lightcurve_stokes_partial(const float *__restrict__ hits, const uint8_t *__restrict__ n_hits,
+                                                                   const float *__restrict__ pol, int64_t n_px, int max_images,
+                                                                   HotspotShade hs, double pol_frac, double t_start, double dt,
+                                                                   double *__restrict__ partial)
+{
+    __shared__ double sh[256][3];
+    const double t_obs = t_start + dt * (double)blockIdx.y;
+    double v[3] = {0.0, 0.0, 0.0};
+    for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < n_px; p += (int64_t)256 * LC_BLOCKS) {
+        const float *rec = hits + p * max_images * 4, *prec = pol + p * max_images * 4;
+        const int ns = stored_slots(rec, n_hits, p, max_images);
+        double e_px = 0.0, q_px = 0.0, u_px = 0.0;
+        for (int j = 0; j < ns; ++j) {
+            double e[3];
+            hotspot_emission(hs, t_obs, rec + j * 4, e);
+            const double m = (e[0] + e[1] + e[2]) / 3.0;
+            const double w = stokes_weight(pol_frac, prec + j * 4);
+            e_px += m; q_px += w * (double)prec[j * 4] * m; u_px += w * (double)prec[j * 4 + 1] * m;
+        }
+        v[0] += e_px; v[1] += q_px; v[2] += u_px;
+    }
+    lc_tree(sh, v);
+    if (threadIdx.x == 0)
+        for (int c = 0; c < 3; ++c) partial[((int64_t)blockIdx.y * LC_BLOCKS + blockIdx.x) * 3 + c] = sh[0][c];
+}
+// (The second stage is k_lightcurve_final itself: it adds three columns of partials whatever they mean.)
+
+} // namespace lt

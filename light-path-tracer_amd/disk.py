@@ -241,3 +241,178 @@ def lightcurve(M, a, hits, n_hits, spot, times):
         e = np.where(on, (es[..., 0] + es[..., 1] + es[..., 2]) / 3.0, 0.0).sum(axis=-1)
         out[i] = e.sum(), (e * ix).sum(), (e * iy).sum()
     return out
+
+
+# ---- linear polarization (lt_trace_disk_pol, lt_shade_stokes, lt_hotspot_lightcurve_stokes) ------------------------
+@dataclass
+class BField:
+    """Magnetic field with constant components in the disk material's orthonormal frame (e_r, e_phi, e_z; include/ltrace.h,
+    "linear polarization"); only its direction matters.  pol_frac: the polarization fraction Pi in [0, 1]."""
+    b_r: float = 0.0
+    b_phi: float = 0.0
+    b_z: float = 1.0
+    pol_frac: float = 0.7
+
+    def to_lt(self):
+        """The lt_bfield struct of this field (ltrace.BField)."""
+        import ltrace
+        return ltrace.default_bfield(b_r=float(self.b_r), b_phi=float(self.b_phi), b_z=float(self.b_z),
+                                     pol_frac=float(self.pol_frac))
+
+
+def _raise_index(M, a, r, s, c, k):
+    """Contravariant components of the covector k = (k_t, k_r, k_theta, k_phi) at (r, theta), s = sin theta, c = cos theta."""
+    s2 = s * s
+    sigma = r * r + a * a * c * c
+    delta = r * r - 2 * M * r + a * a
+    sd = sigma * delta
+    gtt = -((r * r + a * a) ** 2 - a * a * delta * s2) / sd
+    gtp = -2 * M * a * r / sd
+    gpp = (delta - a * a * s2) / (sd * s2)
+    return gtt * k[0] + gtp * k[3], delta / sigma * k[1], k[2] / sigma, gtp * k[0] + gpp * k[3]
+
+
+def walker_penrose(a, r, s, c, k, f):
+    """(Re, Im) of kappa = (A - i B)(r - i a cos theta) from the contravariant components of k and f at (r, theta)."""
+    A = (k[0] * f[1] - k[1] * f[0]) + a * s * s * (k[1] * f[3] - k[3] * f[1])
+    B = ((r * r + a * a) * (k[3] * f[2] - k[2] * f[3]) - a * (k[0] * f[2] - k[2] * f[0])) * s
+    return A * r - B * a * c, -(A * a * c + B * r)
+
+
+def emitter_frame(M, a, r):
+    """Of the circular equatorial geodesic in +phi at r: (sqrt(Delta) / r, e_(phi)^t, e_(phi)^phi) -- e_(r) = (0, sqrt(Delta)
+    / r, 0, 0), e_(z) = -d_theta / r, e_(phi) the unit vector of the t-phi plane orthogonal to u with positive phi part."""
+    delta = r * r - 2 * M * r + a * a
+    g_tt, g_tp, g_pp = -(1 - 2 * M / r), -2 * M * a / r, r * r + a * a + 2 * M * a * a / r
+    sM, sr = np.sqrt(M), np.sqrt(r)
+    r15 = r * sr
+    om = sM / (r15 + a * sM)
+    ut = (r15 + a * sM) / (np.sqrt(r15) * np.sqrt(r15 - 3 * M * sr + 2 * a * sM))
+    u_t, u_p = ut * (g_tt + g_tp * om), ut * (g_tp + g_pp * om)
+    n = np.sqrt(g_tt * u_p * u_p - 2 * g_tp * u_p * u_t + g_pp * u_t * u_t)
+    return np.sqrt(delta) / r, u_p / n, -u_t / n
+
+
+def emission_vector(M, a, L, hit_state, bfield, dtype=np.float64):
+    """At a hit (r, p_r, p_theta of the backward ray; theta = pi / 2): the received photon's contravariant k, the electric
+    vector f = (k^ x b^) / sin zeta lifted to coordinates, sin^2 zeta and mu = |k^ . e_(z)|."""
+    hs = np.asarray(hit_state, dtype=dtype)
+    L = np.asarray(L, dtype=dtype)
+    M, a = dtype(M), dtype(a)
+    r, pr, pth = hs[..., 0], hs[..., 1], hs[..., 2]
+    er, ept, epp = emitter_frame(M, a, r)
+    kr, kp, kz = -er * pr, epp * L - ept, pth / r      # k = (-1, -p_r, -p_theta, L) on e_(r), e_(phi), e_(z)
+    kn = np.sqrt(kr * kr + kp * kp + kz * kz)
+    kr, kp, kz = kr / kn, kp / kn, kz / kn
+    b = np.array([bfield.b_r, bfield.b_phi, bfield.b_z], dtype=dtype)
+    b = b / np.sqrt(b[0] * b[0] + b[1] * b[1] + b[2] * b[2])
+    cr, cp, cz = kp * b[2] - kz * b[1], kz * b[0] - kr * b[2], kr * b[1] - kp * b[0]
+    s2 = cr * cr + cp * cp + cz * cz
+    with np.errstate(invalid="ignore", divide="ignore"):
+        inv = 1 / np.sqrt(s2)
+    fr, fp, fz = cr * inv, cp * inv, cz * inv
+    one, zero = np.ones_like(r), np.zeros_like(r)
+    k = _raise_index(M, a, r, one, zero, (-one, -pr, -pth, L * one))
+    f = (fp * ept, fr * er, -fz / r, fp * epp)
+    return k, f, s2, np.abs(kz)
+
+
+def camera_screen(M, a, r_obs, theta_obs, L, cam_state, dtype=np.float64):
+    """At the static observer: the received photon's contravariant k and the screen vectors e_1, e_2 lifted to
+    coordinates (north e_2 ~ -e_theta + n^theta n, e_1 = e_2 x n in the right-handed (r, theta, phi) tetrad).  cam_state:
+    (p_r, p_theta) of the backward ray at the camera, the ray's own record."""
+    cs = np.asarray(cam_state, dtype=dtype)
+    L = np.asarray(L, dtype=dtype)
+    M, a = dtype(M), dtype(a)
+    r, th = np.asarray(r_obs, dtype=dtype), np.asarray(theta_obs, dtype=dtype)
+    pr, pth = cs[..., 0], cs[..., 1]
+    s, c = np.sin(th), np.cos(th)
+    sigma = r * r + a * a * c * c
+    delta = r * r - 2 * M * r + a * a
+    g_tt = -(1 - 2 * M * r / sigma)
+    g_tp = -2 * M * a * r * s * s / sigma
+    g_pp = (r * r + a * a + 2 * M * a * a * r * s * s / sigma) * s * s
+    w = -g_tp / g_tt
+    n_phi = np.sqrt(g_pp - g_tp * g_tp / g_tt)
+    e_r, e_th = np.sqrt(delta / sigma), 1 / np.sqrt(sigma)
+    n = [-e_r * pr, -e_th * pth, (L - w) / n_phi]
+    nn = np.sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2])
+    n = [x / nn for x in n]
+    e2 = [n[1] * n[0], n[1] * n[1] - 1, n[1] * n[2]]
+    en = np.sqrt(e2[0] * e2[0] + e2[1] * e2[1] + e2[2] * e2[2])
+    e2 = [x / en for x in e2]
+    e1 = [e2[1] * n[2] - e2[2] * n[1], e2[2] * n[0] - e2[0] * n[2], e2[0] * n[1] - e2[1] * n[0]]
+    lift = lambda e: (e[2] * w / n_phi, e[0] * e_r, e[1] * e_th, e[2] / n_phi)
+    one = np.ones_like(pr)
+    k = _raise_index(M, a, r * one, s * one, c * one, (-one, -pr, -pth, L * one))
+    return k, lift(e1), lift(e2), (r * one, s * one, c * one)
+
+
+def polarization(M, a, r_obs, theta_obs, L, hit_state, cam_state, bfield, dtype=np.float64):
+    """The polarization record of a hit (include/ltrace.h, "linear polarization") -> (..., 4): q = cos 2 chi, u = sin 2 chi
+    at the camera (chi from e_1 towards e_2), sin zeta and mu at the emitter.  hit_state (..., 3): r, p_r, p_theta of the
+    backward ray at the hit; cam_state (..., 2): its p_r, p_theta at the camera; L its p_phi.  The Walker-Penrose
+    constant of (k, f) at the hit is matched by x kappa(e_1) + y kappa(e_2) at the camera.  sin^2 zeta < 1e-24: q = u =
+    sin zeta = 0.  dtype np.longdouble evaluates the same statement in extended precision."""
+    M_, a_ = dtype(M), dtype(a)
+    k, f, s2, mu = emission_vector(M, a, L, hit_state, bfield, dtype)
+    r = np.asarray(hit_state, dtype=dtype)[..., 0]
+    kh = walker_penrose(a_, r, np.ones_like(r), np.zeros_like(r), k, f)
+    kc, f1, f2, (ro, so, co) = camera_screen(M, a, r_obs, theta_obs, L, cam_state, dtype)
+    k1, k2 = walker_penrose(a_, ro, so, co, kc, f1), walker_penrose(a_, ro, so, co, kc, f2)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        det = k1[0] * k2[1] - k2[0] * k1[1]
+        x = (kh[0] * k2[1] - k2[0] * kh[1]) / det
+        y = (k1[0] * kh[1] - kh[0] * k1[1]) / det
+        n2 = x * x + y * y
+        q, u = (x * x - y * y) / n2, 2 * x * y / n2
+    dark = s2 < 1e-24
+    out = np.stack(np.broadcast_arrays(np.where(dark, 0, q), np.where(dark, 0, u), np.where(dark, 0, np.sqrt(s2)), mu), axis=-1)
+    return out.astype(dtype)
+
+
+def _slot_means(M, a, hits, n_hits, disk, spot, t_obs, with_disk):
+    """(on, e): the stored slots (..., max_images) and per slot the mean of the three channels of its light, the disk's
+    (with_disk) plus the spot's, unclamped."""
+    hits = np.asarray(hits)
+    m = hits.shape[-2]
+    on = _stored(hits, n_hits)[..., None] > np.arange(m)
+    es = spot_emission(M, a, hits, spot, t_obs)
+    e = (es[..., 0] + es[..., 1] + es[..., 2]) / 3.0
+    if with_disk:
+        r = np.where(on, hits[..., 0].astype(np.float64), 1.0)
+        g = np.where(on, hits[..., 2].astype(np.float64), 0.0)
+        x = disk.inner_edge(M, a) / r
+        inten = disk.exposure * (g * g) ** 2 * x ** disk.q
+        s = g * x ** 0.75
+        ed = [inten * np.clip(2.0 * s - 0.5 * i, 0.0, 1.0) for i in range(3)]
+        e = (ed[0] + ed[1] + ed[2]) / 3.0 + e
+    return on, np.where(on, e, 0.0)
+
+
+def _stokes_weights(pol, on, bfield):
+    p = np.asarray(pol).astype(np.float64)
+    w = np.where(on, bfield.pol_frac * p[..., 2] * p[..., 2], 0.0)
+    return np.where(on, w * p[..., 0], 0.0), np.where(on, w * p[..., 1], 0.0)
+
+
+def stokes_frame(M, a, hits, n_hits, pol, disk, spot, t_obs, bfield):
+    """lt_shade_stokes restated: (..., 3) float32 (I, Q, U) at t_obs.  hits (..., max_images, 4) and n_hits as
+    shade_hotspot's, pol (..., max_images, 4) float32 (q, u, sin zeta, mu).  Per stored slot, e the mean of the three
+    channels of the slot's light (the disk's if spot.with_disk, plus the spot's): I += e, Q += Pi sin^2 zeta e q,
+    U += Pi sin^2 zeta e u, in float64, the slots in order; no clamp, no base."""
+    on, e = _slot_means(M, a, hits, n_hits, disk, spot, t_obs, spot.with_disk)
+    wq, wu = _stokes_weights(pol, on, bfield)
+    return np.stack([e.sum(axis=-1), (wq * e).sum(axis=-1), (wu * e).sum(axis=-1)], axis=-1).astype(np.float32)
+
+
+def stokes_lightcurve(M, a, hits, n_hits, pol, spot, times, bfield):
+    """lt_hotspot_lightcurve_stokes restated: (len(times), 3) float64, per time the sums of I, Q, U of the spot alone over
+    the pixels of hits (R, W, max_images, 4) and their stored slots.  Column 0 is lightcurve()'s column 0."""
+    hits = np.asarray(hits)
+    out = np.empty((len(times), 3))
+    for i, t in enumerate(times):
+        on, e = _slot_means(M, a, hits, n_hits, None, spot, float(t), False)
+        wq, wu = _stokes_weights(pol, on, bfield)
+        out[i] = e.sum(axis=-1).sum(), (wq * e).sum(axis=-1).sum(), (wu * e).sum(axis=-1).sum()
+    return out

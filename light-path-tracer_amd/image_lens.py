@@ -303,13 +303,16 @@ def render_frame(source_image, metric, r_obs, fov, psi=(0.0, 0.0), theta_obs=np.
 
 
 def render_sequence(source_image, metric, r_obs, fov, disk, hotspot, times, shape=None, psi=(0.0, 0.0), theta_obs=np.pi / 2,
-                    integrator=None, precision=None):
+                    integrator=None, precision=None, bfield=None):
     """A moving picture from ONE trace: an optically thin disk (disk.TransparentDisk) with a hot spot (disk.HotSpot) on a
     circular orbit, at the observer times `times`.  The rays are traced once with the light-travel time of every hit
     (lt_trace_disk_hits); each frame is a re-shade of the stored hits (lt_shade_hotspot) over `base`, the lensed
     source_image (None: black, then `shape` = (H, W) gives the size), and the light curve is a reduction over them
     (lt_hotspot_lightcurve, at times[0] + i (times[1] - times[0]): the times must be evenly spaced).
     -> dict(frames (n, H, W[, 3]) float32, rgba (n, H, W, 4) uint8, lightcurve (n, 3) float64, hits, n_hits, stats).
+    bfield (disk.BField): the trace also keeps every hit's linear polarization (lt_trace_disk_pol), and the result gains
+    pol (H, W, max_images, 4), stokes (n, H, W, 3) float32 (I, Q, U per frame; lt_shade_stokes) and stokes_lightcurve
+    (n, 3) float64 (lt_hotspot_lightcurve_stokes); everything else is what it is without a field.
     One GPU, every row traced, one ray per pixel (no supersampling)."""
     times = np.asarray(times, dtype=np.float64).ravel()
     if times.size == 0:
@@ -332,36 +335,56 @@ def render_sequence(source_image, metric, r_obs, fov, disk, hotspot, times, shap
         base = ltrace.render(cam, met, opts, background=source_image, want=("rgb",))["rgb"]
     d, spot = disk.to_lt(), hotspot.to_lt()
     m = int(getattr(disk, "max_images", 3))
-    traced = ltrace.trace_disk_hits(cam, met, opts, d, max_images=m, want=("hits", "n_hits"))
+    field = bfield.to_lt() if bfield is not None else None
+    if field is not None:
+        traced = ltrace.trace_disk_pol(cam, met, opts, d, field, max_images=m, want=("hits", "n_hits", "pol"))
+    else:
+        traced = ltrace.trace_disk_hits(cam, met, opts, d, max_images=m, want=("hits", "n_hits"))
     frames, rgba = [], []
     for t in times:
         f = ltrace.shade_hotspot(traced["hits"], traced["n_hits"], met, d, spot, float(t), base=base)
         frames.append(f["rgb"])
         rgba.append(f["rgba"])
     lc = ltrace.hotspot_lightcurve(traced["hits"], traced["n_hits"], met, d, spot, float(times[0]), dt, times.size)
-    return dict(frames=np.stack(frames), rgba=np.stack(rgba), lightcurve=lc, hits=traced["hits"], n_hits=traced["n_hits"],
-                stats=traced["stats"])
+    out = dict(frames=np.stack(frames), rgba=np.stack(rgba), lightcurve=lc, hits=traced["hits"], n_hits=traced["n_hits"],
+               stats=traced["stats"])
+    if field is not None:
+        rec = (traced["hits"], traced["n_hits"], traced["pol"], met, d, spot, field)
+        out.update(pol=traced["pol"], stokes=np.stack([ltrace.shade_stokes(*rec, float(t)) for t in times]),
+                   stokes_lightcurve=ltrace.hotspot_lightcurve_stokes(*rec, float(times[0]), dt, times.size))
+    return out
 
 
 def main_sequence(args, disk):
-    """--hotspot R PHI0 SIGMA --times T0 DT N: numbered PNGs next to --output and the light curve as .npy."""
-    from disk import HotSpot
+    """--hotspot R PHI0 SIGMA --times T0 DT N: numbered PNGs next to --output and the light curve as .npy.
+    --bfield BR BPHI BZ [--pol-frac P]: also the Stokes frames (I, Q, U) as numbered .npy and the Stokes light curve;
+    without --hotspot the spot is dark and the frames show the disk alone."""
+    from disk import BField, HotSpot
     if not args.synthetic:
-        raise ValueError("--hotspot renders over a black sky at the size given by --synthetic W H")
+        raise ValueError("--hotspot / --bfield render over a black sky at the size given by --synthetic W H")
     if disk is None or not hasattr(disk, "max_images"):
-        raise ValueError("--hotspot needs --disk-images N")
+        raise ValueError("--hotspot / --bfield need --disk-images N")
     width, height = int(args.synthetic[0]), int(args.synthetic[1])
     metric = Kerr(M=args.M, a=args.a, integrator=args.integrator, precision=args.precision)
     vfov = np.radians(args.fov_v)
     fov = (2 * np.arctan(np.tan(vfov / 2) * width / height), vfov)
     t0, dt, n = float(args.times[0]), float(args.times[1]), int(args.times[2])
-    spot = HotSpot(r_spot=args.hotspot[0], phi0=args.hotspot[1], sigma=args.hotspot[2], exposure=args.hotspot_exposure)
+    if args.hotspot is not None:
+        spot = HotSpot(r_spot=args.hotspot[0], phi0=args.hotspot[1], sigma=args.hotspot[2], exposure=args.hotspot_exposure)
+    else:
+        spot, n = HotSpot(exposure=0.0), 1
+    field = BField(*args.bfield, pol_frac=args.pol_frac) if args.bfield is not None else None
     out = render_sequence(None, metric, args.r_obs * metric.M, fov, disk, spot, t0 + dt * np.arange(n), shape=(height, width),
-                          psi=(np.radians(args.psi_y), np.radians(args.psi_x)), theta_obs=np.radians(args.theta_obs))
+                          psi=(np.radians(args.psi_y), np.radians(args.psi_x)), theta_obs=np.radians(args.theta_obs), bfield=field)
     stem = args.output[:-4] if args.output.lower().endswith(".png") else args.output
     for i in range(n):
         write_png_rgba8(f"{stem}_{i:04d}.png", out["rgba"][i])
     np.save(stem + "_lightcurve.npy", out["lightcurve"])
+    if field is not None:
+        for i in range(n):
+            np.save(f"{stem}_stokes_{i:04d}.npy", out["stokes"][i])
+        np.save(stem + "_stokes_lightcurve.npy", out["stokes_lightcurve"])
+        print(f"Polarization: Stokes frames -> {stem}_stokes_0000.npy ..., Stokes light curve -> {stem}_stokes_lightcurve.npy")
     print(f"Hot spot: one trace ({out['stats']['integrate_ms']:.2f} ms), {n} frames -> {stem}_0000.png ..., light curve -> "
           f"{stem}_lightcurve.npy")
     return out
@@ -628,6 +651,10 @@ def build_parser():
     ap.add_argument("--times", type=float, nargs=3, default=(0.0, 10.0, 8), metavar=("T0", "DT", "N"),
                     help="--hotspot: N observer times from T0 in steps of DT (in M)")
     ap.add_argument("--hotspot-exposure", type=float, default=1.0, help="--hotspot: brightness scale of the spot (default: 1)")
+    ap.add_argument("--bfield", type=float, nargs=3, default=None, metavar=("BR", "BPHI", "BZ"),
+                    help="with --disk-images: the magnetic field's direction in the disk material's frame; writes the Stokes "
+                         "frames (I, Q, U) as numbered .npy and the Stokes light curve, with --hotspot or without it")
+    ap.add_argument("--pol-frac", type=float, default=0.7, help="--bfield: polarization fraction in [0, 1] (default: 0.7)")
     return ap
 
 
@@ -641,7 +668,7 @@ if __name__ == "__main__":
     elif args.disk:
         from disk import ThinDisk
         disk = ThinDisk(r_in=args.disk_rin, r_out=args.disk_rout, q=args.disk_q, exposure=args.disk_exposure)
-    if args.hotspot is not None:
+    if args.hotspot is not None or args.bfield is not None:
         main_sequence(args, disk)
         sys.exit(0)
     main(M=args.M, a=args.a, r_obs_mult=args.r_obs, psi=(np.radians(args.psi_y), np.radians(args.psi_x)),

@@ -80,6 +80,11 @@ class HotSpot(C.Structure):
                 ("with_disk", C.c_int32), ("reserved", C.c_int32)]
 
 
+class BField(C.Structure):
+    """lt_bfield: the field's components in the emitter's frame and the polarization fraction."""
+    _fields_ = [("b_r", C.c_double), ("b_phi", C.c_double), ("b_z", C.c_double), ("pol_frac", C.c_double)]
+
+
 class AA(C.Structure):
     """lt_aa: supersampling (samples x samples rays per pixel; band_rows 0 = automatic)."""
     _fields_ = [("samples", C.c_int32), ("mode", C.c_int32), ("max_images", C.c_int32), ("band_rows", C.c_int32)]
@@ -196,6 +201,29 @@ SIGNATURES = {
     "lt_hotspot_lightcurve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Metric),
                                         C.POINTER(Disk), C.POINTER(HotSpot), C.c_double, C.c_double, C.c_int32,
                                         C.c_void_p]),
+    "lt_default_bfield": (None, [C.POINTER(BField)]),
+    "lt_trace_disk_pol_dev": (C.c_int, [C.POINTER(Camera), C.POINTER(Metric), C.POINTER(Opts), C.POINTER(Disk), C.POINTER(BField),
+                                        C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
+    "lt_trace_disk_pol": (C.c_int, [C.POINTER(Camera), C.POINTER(Metric), C.POINTER(Opts), C.POINTER(Disk), C.POINTER(BField),
+                                    C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.POINTER(Stats)]),
+    "lt_trace_batch_kerr_disk_pol": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_double,
+                                               C.c_double, C.c_void_p, C.c_int, C.c_int, C.POINTER(Disk), C.POINTER(BField),
+                                               C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lt_polarization_probe": (C.c_int, [C.POINTER(Metric), C.c_double, C.c_double, C.POINTER(BField), C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_int64, C.c_void_p]),
+    "lt_shade_stokes_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Metric),
+                                      C.POINTER(Disk), C.POINTER(HotSpot), C.POINTER(BField), C.c_double, C.c_void_p]),
+    "lt_shade_stokes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Metric),
+                                  C.POINTER(Disk), C.POINTER(HotSpot), C.POINTER(BField), C.c_double, C.c_void_p]),
+    "lt_hotspot_lightcurve_stokes_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                                   C.POINTER(Metric), C.POINTER(Disk), C.POINTER(HotSpot), C.POINTER(BField),
+                                                   C.c_double, C.c_double, C.c_int32, C.c_void_p]),
+    "lt_hotspot_lightcurve_stokes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                               C.POINTER(Metric), C.POINTER(Disk), C.POINTER(HotSpot), C.POINTER(BField),
+                                               C.c_double, C.c_double, C.c_int32, C.c_void_p]),
     "lt_default_aa": (None, [C.POINTER(AA)]),
     "lt_render_aa_dev": (C.c_int, [C.POINTER(Camera), C.POINTER(Metric), C.POINTER(Opts), C.POINTER(AA), C.POINTER(Disk),
                                    C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -918,6 +946,131 @@ def hotspot_lightcurve_dev(d_hits, d_n_hits, rows, width, max_images, metric, di
     """Device-pointer form of hotspot_lightcurve (lt_hotspot_lightcurve_dev); enqueues on the default stream."""
     _check(load().lt_hotspot_lightcurve_dev(_p(d_hits), _p(d_n_hits), rows, width, max_images, C.byref(metric),
                                             C.byref(disk), C.byref(spot), float(t_start), float(dt), int(n_times), _p(d_out)))
+
+
+# ---- linear polarization (lt_trace_disk_pol, lt_shade_stokes, lt_hotspot_lightcurve_stokes) ------------------------
+def default_bfield(**kw):
+    """lt_bfield with the library's defaults ((b_r, b_phi, b_z) = (0, 0, 1), pol_frac 0.7); keywords override."""
+    b = BField()
+    load().lt_default_bfield(C.byref(b))
+    for k, v in kw.items():
+        setattr(b, k, v)
+    return b
+
+
+def trace_disk_pol(cam, metric, opts, disk, field, max_images=3,
+                   want=("fa", "winding", "status", "steps", "hits", "n_hits", "pol")):
+    """Host-pointer polarized trace (lt_trace_disk_pol): trace_disk_hits() plus 'pol' (rows, W, max_images, 4) float32
+    (q, u, sin zeta, mu), NaN in unused slots."""
+    rows = _frame_rows(cam, opts)
+    out = _frame_outputs(rows, cam.width, 3, False, [k for k in want if k in ("fa", "winding", "status", "steps")])
+    for name in ("hits", "pol"):
+        if name in want:
+            out[name] = pinned_empty((rows, cam.width, int(max_images), 4), np.float32)
+    if "n_hits" in want:
+        out["n_hits"] = pinned_empty((rows, cam.width), np.uint8)
+    st = Stats()
+    _check(load().lt_trace_disk_pol(C.byref(cam), C.byref(metric), C.byref(opts), C.byref(disk), C.byref(field), int(max_images),
+                                    _np_ptr(out.get("fa")), _np_ptr(out.get("winding")), _np_ptr(out.get("status")),
+                                    _np_ptr(out.get("steps")), _np_ptr(out.get("hits")), _np_ptr(out.get("n_hits")),
+                                    _np_ptr(out.get("pol")), C.byref(st)))
+    out["stats"] = stats_dict(st.counters, st.prologue_ms, st.integrate_ms, st.epilogue_ms)
+    out["stats"]["disk"] = int(st.counters[STAT_DISK])
+    out["stats"]["disk_hits"] = int(st.counters[STAT_DISK_HITS])
+    return out
+
+
+def trace_disk_pol_dev(cam, metric, opts, disk, field, max_images=3, d_fa=0, d_w=0, d_status=0, d_steps=0, d_hits=0, d_n_hits=0,
+                       d_pol=0, d_stats=0):
+    """Device-pointer form of trace_disk_pol (lt_trace_disk_pol_dev); pointers are integers, 0 = NULL.  Asynchronous."""
+    _check(load().lt_trace_disk_pol_dev(C.byref(cam), C.byref(metric), C.byref(opts), C.byref(disk), C.byref(field), int(max_images),
+                                        _p(d_fa), _p(d_w), _p(d_status), _p(d_steps), _p(d_hits), _p(d_n_hits), _p(d_pol),
+                                        _p(d_stats)))
+
+
+def trace_batch_kerr_disk_pol(M, a, r_obs, alphas, thetas, theta_obs, lambda_max, disk, field, max_images=3,
+                              axis_refines=None, integrator=INTEGRATOR_RK4, precision=32):
+    """Batch twin of the polarized trace (lt_trace_batch_kerr_disk_pol): trace_batch_kerr_disk_hits() plus 'pol'
+    (n, max_images, 4) f64 (q, u, sin zeta, mu)."""
+    al = np.ascontiguousarray(alphas, dtype=np.float64)
+    th = np.ascontiguousarray(thetas, dtype=np.float64)
+    n = al.size
+    if th.size != n:
+        raise ValueError("alphas and thetas differ in length")
+    ar = None
+    if axis_refines is not None:
+        ar = np.ascontiguousarray(axis_refines).astype(np.uint8)
+        if ar.size != n:
+            raise ValueError("axis_refines has the wrong length")
+    if isinstance(integrator, str):
+        integrator = INTEGRATORS[integrator]
+    m = int(max_images)
+    out = dict(fa=np.empty(n), winding=np.empty(n, dtype=np.int64), status=np.empty(n, dtype=np.int8),
+               hits=np.empty((n, max(m, 0), 4)), n_hits=np.empty(n, dtype=np.int32), pol=np.empty((n, max(m, 0), 4)),
+               rhs_evals=np.empty(n, dtype=np.uint32))
+    _check(load().lt_trace_batch_kerr_disk_pol(M, a, r_obs, _np_ptr(al), _np_ptr(th), theta_obs, lambda_max, _np_ptr(ar),
+                                               integrator, precision, C.byref(disk), C.byref(field), m, n, _np_ptr(out["fa"]),
+                                               _np_ptr(out["winding"]), _np_ptr(out["status"]), _np_ptr(out["hits"]),
+                                               _np_ptr(out["n_hits"]), _np_ptr(out["pol"]), _np_ptr(out["rhs_evals"])))
+    return out
+
+
+def polarization_probe(metric, r_obs, theta_obs, p_phi, hit, cam, field):
+    """The device's own polarization rule (lt_polarization_probe) on n records: hit (n, 3) (r, p_r, p_theta at the hit),
+    cam (n, 2) (p_r, p_theta at the camera), p_phi scalar or (n,).  -> (n, 4) float64 (q, u, sin zeta, mu)."""
+    hit = np.ascontiguousarray(hit, dtype=np.float64).reshape(-1, 3)
+    cam = np.ascontiguousarray(cam, dtype=np.float64).reshape(-1, 2)
+    n = hit.shape[0]
+    if cam.shape[0] != n:
+        raise ValueError("hit and cam differ in length")
+    pp = np.ascontiguousarray(np.broadcast_to(np.asarray(p_phi, dtype=np.float64), (n,)))
+    out = np.empty((n, 4))
+    _check(load().lt_polarization_probe(C.byref(metric), float(r_obs), float(theta_obs), C.byref(field), _np_ptr(pp), _np_ptr(hit),
+                                        _np_ptr(cam), n, _np_ptr(out)))
+    return out
+
+
+def _pol_array(pol, hits):
+    pol = np.ascontiguousarray(pol, dtype=np.float32)
+    if pol.shape != hits.shape:
+        raise ValueError("pol must have the hits' shape (rows, W, max_images, 4)")
+    return pol
+
+
+def shade_stokes(hits, n_hits, pol, metric, disk, spot, field, t_obs):
+    """The Stokes frame at observer time t_obs from stored records (lt_shade_stokes) -> (rows, W, 3) float32 (I, Q, U)."""
+    hits, nh = _hit_arrays(hits, n_hits)
+    pol = _pol_array(pol, hits)
+    R, W, m = hits.shape[:3]
+    out = np.empty((R, W, 3), dtype=np.float32)
+    _check(load().lt_shade_stokes(_np_ptr(hits), _np_ptr(nh), _np_ptr(pol), R, W, m, C.byref(metric), C.byref(disk), C.byref(spot),
+                                  C.byref(field), float(t_obs), _np_ptr(out)))
+    return out
+
+
+def shade_stokes_dev(d_hits, d_n_hits, d_pol, rows, width, max_images, metric, disk, spot, field, t_obs, d_iqu):
+    """Device-pointer form of shade_stokes (lt_shade_stokes_dev); enqueues on the default stream."""
+    _check(load().lt_shade_stokes_dev(_p(d_hits), _p(d_n_hits), _p(d_pol), rows, width, max_images, C.byref(metric), C.byref(disk),
+                                      C.byref(spot), C.byref(field), float(t_obs), _p(d_iqu)))
+
+
+def hotspot_lightcurve_stokes(hits, n_hits, pol, metric, disk, spot, field, t_start, dt, n_times):
+    """The spot's Stokes light curve (lt_hotspot_lightcurve_stokes) -> (n_times, 3) float64: per time the sums of I, Q, U."""
+    hits, nh = _hit_arrays(hits, n_hits)
+    pol = _pol_array(pol, hits)
+    R, W, m = hits.shape[:3]
+    out = np.empty((int(n_times), 3))
+    _check(load().lt_hotspot_lightcurve_stokes(_np_ptr(hits), _np_ptr(nh), _np_ptr(pol), R, W, m, C.byref(metric), C.byref(disk),
+                                               C.byref(spot), C.byref(field), float(t_start), float(dt), int(n_times), _np_ptr(out)))
+    return out
+
+
+def hotspot_lightcurve_stokes_dev(d_hits, d_n_hits, d_pol, rows, width, max_images, metric, disk, spot, field, t_start, dt, n_times,
+                                  d_out):
+    """Device-pointer form of hotspot_lightcurve_stokes (lt_hotspot_lightcurve_stokes_dev); enqueues on the default stream."""
+    _check(load().lt_hotspot_lightcurve_stokes_dev(_p(d_hits), _p(d_n_hits), _p(d_pol), rows, width, max_images, C.byref(metric),
+                                                   C.byref(disk), C.byref(spot), C.byref(field), float(t_start), float(dt),
+                                                   int(n_times), _p(d_out)))
 
 
 # ---- supersampled frames (lt_render_aa) ---------------------------------------------------------------------------

@@ -304,6 +304,16 @@ class Kerr(Metric):
                                                  self._lambda_max(r_obs), d, max_images=m, axis_refines=axis_refines,
                                                  integrator=self.integrator, precision=self.precision)
 
+    def trace_rays_batch_disk_pol(self, r_obs, alphas, thetas, theta_obs, disk, bfield, max_images=None, axis_refines=None):
+        """trace_rays_batch_disk_hits with the linear polarization of every hit: 'pol' (n, max_images, 4) float64
+        (q, u, sin zeta, mu) for the field `bfield` (disk.BField or ltrace.BField; lt_trace_batch_kerr_disk_pol)."""
+        d = disk.to_lt() if hasattr(disk, "to_lt") else disk
+        b = bfield.to_lt() if hasattr(bfield, "to_lt") else bfield
+        m = max_images if max_images is not None else getattr(disk, "max_images", 3)
+        return ltrace.trace_batch_kerr_disk_pol(self.M, self.a, r_obs, alphas, thetas, theta_obs, self._lambda_max(r_obs), d, b,
+                                                max_images=m, axis_refines=axis_refines, integrator=self.integrator,
+                                                precision=self.precision)
+
     def trace_rays_batch_disk_images(self, r_obs, alphas, thetas, theta_obs, disk, max_images=None, axis_refines=None):
         """trace_rays_batch with the optically thin disk (disk.TransparentDisk, or ltrace.Disk with max_images),
         direct schedule -> dict(fa, winding, status (trace_rays_batch's), images (n, max_images, 3) float64
