@@ -454,7 +454,8 @@ int lt_trace_batch_kerr_disk_images(double M, double a, double r_obs, const doub
  * LT_STAT_DISK_HITS -- equals lt_render_disk_images' bit for bit; only LT_STAT_WAVE_ITERS and LT_STAT_EQ_ITERS       *
  * may differ.                                                                                                     *
  *                                                                                                               *
- * Out of scope: supersampled hot-spot frames, lt_render_multi and the multi-process path.                         */
+ * Supersampled hot-spot frames are lt_shade_hotspot_aa's ("supersampled hot-spot and Stokes frames" below).         *
+ * Out of scope: lt_render_multi and the multi-process path.                                                       */
 
 /* lt_render_disk_images_dev without the colour outputs and with
  *   d_hits (R, W, max_images, 4) float32 (r_hit, phi_hit in [0, 2 pi), g, elapsed time), NaN in unused slots
@@ -557,8 +558,8 @@ int lt_hotspot_lightcurve(const float *hits, const uint8_t *n_hits, int32_t R, i
  * Pi = pol_frac in [0, 1].  Nothing is clamped and there is no base.  disk.polarization / disk.stokes_frame /        *
  * disk.stokes_lightcurve (Python) state all of it in numpy; lt_polarization_probe runs the device's rule.           *
  *                                                                                                               *
- * Out of scope: supersampled polarized frames, lt_render_multi and the multi-process path, circular polarization   *
- * and Faraday effects.                                                                                            */
+ * Supersampled polarized frames are lt_shade_stokes_aa's ("supersampled hot-spot and Stokes frames" below).          *
+ * Out of scope: lt_render_multi and the multi-process path, circular polarization and Faraday effects.              */
 typedef struct lt_bfield {
     double b_r, b_phi, b_z; /* components in the emitter's frame; not all zero (LT_ERR_INVALID_ARG otherwise) */
     double pol_frac;        /* Pi, in [0, 1] */
@@ -604,6 +605,51 @@ int lt_hotspot_lightcurve_stokes_dev(const float *d_hits, const uint8_t *d_n_hit
 int lt_hotspot_lightcurve_stokes(const float *hits, const uint8_t *n_hits, const float *pol, int32_t R, int32_t W,
                                  int32_t max_images, const lt_metric *metric, const lt_disk *disk, const lt_hotspot *spot,
                                  const lt_bfield *field, double t_start, double dt, int32_t n_times, double *out);
+
+/* ---- supersampled hot-spot and Stokes frames, resolved on the GPU ------------------------------------------ *
+ * A hot spot's higher-order images are arcs a fraction of a pixel wide, so a one-ray-per-pixel sequence flickers.      *
+ * These entry points re-shade the records of the FINE camera (the same camera with width W S and height H S,          *
+ * "supersampled frames" below; S = samples, 1 <= S <= LT_AA_MAX_SAMPLES = 8) and resolve them in one kernel: only     *
+ * the (R, W) output is written and comes back.                                                                    *
+ *                                                                                                               *
+ * Fine records.  What lt_trace_disk_hits[_dev] / lt_trace_disk_pol[_dev] write for the fine camera:                    *
+ *   hits (R S, W S, max_images, 4) float32;  n_hits (R S, W S) uint8, or NULL with lt_shade_hotspot's meaning;          *
+ *   pol (R S, W S, max_images, 4) float32.                                                                         *
+ * R, W are OUTPUT rows and columns; fine pixel (y S + j, x S + i) is sub-sample (j, i) of output pixel (y, x).  For a    *
+ * partition the fine rows are the fine frame's partition with row blocks of row_block S, as in lt_render_aa, so local *
+ * fine row y S + j belongs to local output row y.                                                                  *
+ *                                                                                                               *
+ * Rule.  The value of a fine pixel is the float32 value lt_shade_hotspot (lt_shade_stokes) writes for that pixel of    *
+ * the fine buffers -- same arithmetic, same order, the clamp included for rgb; base, when given, is the fine-size      *
+ * (R S, W S, channels) buffer.  The output pixel is the resolve of lt_render_aa: the S^2 float32 values added in       *
+ * float64 in row-major order (j outer, i inner) from 0.0, divided by (double)(S S), rounded to float32; RGBA8 from     *
+ * that float32 as everywhere.  So rgb is, bit for bit, aa.resolve (Python) of the frame lt_shade_hotspot returns for   *
+ * the fine records, iqu the same of lt_shade_stokes', and with samples = 1 both are those entry points' outputs.        *
+ * No floating-point atomics; no result depends on the launch geometry.                                              *
+ *                                                                                                               *
+ * Refusals.  LT_ERR_NO_DEVICE without a GPU; then samples outside [1, LT_AA_MAX_SAMPLES]: LT_ERR_INVALID_ARG; then       *
+ * everything lt_shade_hotspot / lt_shade_stokes refuse, with their codes, in their order.                            *
+ *                                                                                                               *
+ * The light curve needs no entry point: lt_hotspot_lightcurve / lt_hotspot_lightcurve_stokes called with (R S, W S)   *
+ * and the fine records are the supersampled curves in FINE-pixel units -- the sums over S^2 sub-samples per pixel,      *
+ * the first moments in fine columns and rows.  In output-pixel units: column 0 / S^2 and the moments / S^3 for the      *
+ * first, all three columns / S^2 for the Stokes curve (image_lens.render_sequence does so).                           *
+ *                                                                                                               *
+ * Out of scope: lt_render_multi, the multi-process path, adaptive sampling of sequences.                             */
+int lt_shade_hotspot_aa_dev(const float *d_hits, const uint8_t *d_n_hits, int32_t R, int32_t W, int32_t samples,
+                            int32_t max_images, const lt_metric *metric, const lt_disk *disk, const lt_hotspot *spot,
+                            double t_obs, const float *d_base /* (R S, W S, channels) or NULL */, int32_t channels,
+                            float *d_rgb /* (R, W, channels) */, uint8_t *d_rgba /* (R, W, 4) */);
+/* The same with HOST pointers, staged like lt_shade_hotspot; only the resolved outputs come back. */
+int lt_shade_hotspot_aa(const float *hits, const uint8_t *n_hits, int32_t R, int32_t W, int32_t samples, int32_t max_images,
+                        const lt_metric *metric, const lt_disk *disk, const lt_hotspot *spot, double t_obs, const float *base,
+                        int32_t channels, float *out_rgb, uint8_t *out_rgba);
+int lt_shade_stokes_aa_dev(const float *d_hits, const uint8_t *d_n_hits, const float *d_pol, int32_t R, int32_t W,
+                           int32_t samples, int32_t max_images, const lt_metric *metric, const lt_disk *disk,
+                           const lt_hotspot *spot, const lt_bfield *field, double t_obs, float *d_iqu /* (R, W, 3) */);
+int lt_shade_stokes_aa(const float *hits, const uint8_t *n_hits, const float *pol, int32_t R, int32_t W, int32_t samples,
+                       int32_t max_images, const lt_metric *metric, const lt_disk *disk, const lt_hotspot *spot,
+                       const lt_bfield *field, double t_obs, float *out_iqu);
 
 /* ---- supersampled (anti-aliased) frames, resolved on the GPU ------------------------------------------- *
  * Every frame above is one ray per pixel, taken at the pixel's corner.  These entry points trace S x S rays per       *

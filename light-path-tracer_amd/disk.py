@@ -228,6 +228,13 @@ def shade_hotspot(M, a, hits, n_hits, disk, spot, t_obs, base=None, channels=3):
     return np.where(lit, np.clip(acc, 0.0, 1.0).astype(np.float32), base)
 
 
+def shade_hotspot_aa(M, a, hits, n_hits, disk, spot, t_obs, samples, base=None, channels=3):
+    """lt_shade_hotspot_aa restated: shade_hotspot of the FINE records (R S, W S, max_images, 4) (base at the fine size),
+    resolved by the rule of aa.resolve -> float32 (R, W, 3), or (R, W) for channels = 1."""
+    import aa
+    return aa.resolve(shade_hotspot(M, a, hits, n_hits, disk, spot, t_obs, base=base, channels=channels), samples)
+
+
 def lightcurve(M, a, hits, n_hits, spot, times):
     """lt_hotspot_lightcurve restated: (len(times), 3) float64, per time the sums of e, e ix, e iy over the pixels of
     hits (R, W, max_images, 4) and their stored slots, e the mean of E_spot's three channels."""
@@ -404,6 +411,12 @@ def stokes_frame(M, a, hits, n_hits, pol, disk, spot, t_obs, bfield):
     on, e = _slot_means(M, a, hits, n_hits, disk, spot, t_obs, spot.with_disk)
     wq, wu = _stokes_weights(pol, on, bfield)
     return np.stack([e.sum(axis=-1), (wq * e).sum(axis=-1), (wu * e).sum(axis=-1)], axis=-1).astype(np.float32)
+
+
+def stokes_frame_aa(M, a, hits, n_hits, pol, disk, spot, t_obs, bfield, samples):
+    """lt_shade_stokes_aa restated: stokes_frame of the FINE records, resolved by the rule of aa.resolve -> (R, W, 3)."""
+    import aa
+    return aa.resolve(stokes_frame(M, a, hits, n_hits, pol, disk, spot, t_obs, bfield), samples)
 
 
 def stokes_lightcurve(M, a, hits, n_hits, pol, spot, times, bfield):

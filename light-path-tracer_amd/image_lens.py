@@ -303,7 +303,7 @@ def render_frame(source_image, metric, r_obs, fov, psi=(0.0, 0.0), theta_obs=np.
 
 
 def render_sequence(source_image, metric, r_obs, fov, disk, hotspot, times, shape=None, psi=(0.0, 0.0), theta_obs=np.pi / 2,
-                    integrator=None, precision=None, bfield=None):
+                    integrator=None, precision=None, bfield=None, samples=None):
     """A moving picture from ONE trace: an optically thin disk (disk.TransparentDisk) with a hot spot (disk.HotSpot) on a
     circular orbit, at the observer times `times`.  The rays are traced once with the light-travel time of every hit
     (lt_trace_disk_hits); each frame is a re-shade of the stored hits (lt_shade_hotspot) over `base`, the lensed
@@ -313,7 +313,20 @@ def render_sequence(source_image, metric, r_obs, fov, disk, hotspot, times, shap
     bfield (disk.BField): the trace also keeps every hit's linear polarization (lt_trace_disk_pol), and the result gains
     pol (H, W, max_images, 4), stokes (n, H, W, 3) float32 (I, Q, U per frame; lt_shade_stokes) and stokes_lightcurve
     (n, 3) float64 (lt_hotspot_lightcurve_stokes); everything else is what it is without a field.
-    One GPU, every row traced, one ray per pixel (no supersampling)."""
+    samples: S (1 ... 8) -> an anti-aliased sequence: the rays of the FINE camera (H S, W S) are traced once, one ray per
+    fine pixel, and every frame is re-shaded and resolved S x S -> 1 on the GPU (lt_shade_hotspot_aa; stokes:
+    lt_shade_stokes_aa), so only (H, W) frames come back.  source_image, when given, is then the fine image
+    (H S, W S[, 3]) as in render_frame, and `shape` stays the output's (H, W).  frames (n, H, W[, 3]), rgba (n, H, W, 4)
+    and stokes (n, H, W, 3) have the output's size; hits, n_hits and pol are the FINE records; the result gains
+    `samples`.  lightcurve is the fine records' curve in output-pixel units (column 0 divided by S^2, the first moments
+    by S^3) and stokes_lightcurve the fine records' divided by S^2.  The fine records take 16 max_images S^2 H W bytes
+    (twice that with a field) and are held for the whole sequence.  samples=None: one ray per pixel, as without it.
+    One GPU, every row traced; sequences are not adaptively sampled."""
+    S = None
+    if samples is not None:
+        S = int(samples)
+        if not 1 <= S <= ltrace.AA_MAX_SAMPLES:
+            raise ValueError(f"samples={S}: a sequence takes 1 ... {ltrace.AA_MAX_SAMPLES} samples per axis")
     times = np.asarray(times, dtype=np.float64).ravel()
     if times.size == 0:
         raise ValueError("render_sequence needs at least one time")
@@ -330,7 +343,11 @@ def render_sequence(source_image, metric, r_obs, fov, disk, hotspot, times, shap
         if source_image.ndim == 3 and source_image.shape[2] == 4:
             source_image = source_image[..., :3]
         shape = source_image.shape[:2]
-    cam = _camera(shape, fov, psi, r_obs, theta_obs)
+        if S is not None and (shape[0] % S or shape[1] % S):
+            raise ValueError(f"samples={S}: the background must be the fine frame, (H * samples, W * samples); got {shape}")
+    elif S is not None:
+        shape = (int(shape[0]) * S, int(shape[1]) * S)
+    cam = _camera(shape, fov, psi, r_obs, theta_obs)      # (with samples: the fine camera)
     if source_image is not None:
         base = ltrace.render(cam, met, opts, background=source_image, want=("rgb",))["rgb"]
     d, spot = disk.to_lt(), hotspot.to_lt()
@@ -342,21 +359,34 @@ def render_sequence(source_image, metric, r_obs, fov, disk, hotspot, times, shap
         traced = ltrace.trace_disk_hits(cam, met, opts, d, max_images=m, want=("hits", "n_hits"))
     frames, rgba = [], []
     for t in times:
-        f = ltrace.shade_hotspot(traced["hits"], traced["n_hits"], met, d, spot, float(t), base=base)
+        if S is None:
+            f = ltrace.shade_hotspot(traced["hits"], traced["n_hits"], met, d, spot, float(t), base=base)
+        else:
+            f = ltrace.shade_hotspot_aa(traced["hits"], traced["n_hits"], S, met, d, spot, float(t), base=base)
         frames.append(f["rgb"])
         rgba.append(f["rgba"])
     lc = ltrace.hotspot_lightcurve(traced["hits"], traced["n_hits"], met, d, spot, float(times[0]), dt, times.size)
+    if S is not None:
+        lc = lc / np.array([S * S, S ** 3, S ** 3], dtype=np.float64)
     out = dict(frames=np.stack(frames), rgba=np.stack(rgba), lightcurve=lc, hits=traced["hits"], n_hits=traced["n_hits"],
                stats=traced["stats"])
     if field is not None:
         rec = (traced["hits"], traced["n_hits"], traced["pol"], met, d, spot, field)
-        out.update(pol=traced["pol"], stokes=np.stack([ltrace.shade_stokes(*rec, float(t)) for t in times]),
-                   stokes_lightcurve=ltrace.hotspot_lightcurve_stokes(*rec, float(times[0]), dt, times.size))
+        slc = ltrace.hotspot_lightcurve_stokes(*rec, float(times[0]), dt, times.size)
+        if S is None:
+            stokes = [ltrace.shade_stokes(*rec, float(t)) for t in times]
+        else:
+            stokes = [ltrace.shade_stokes_aa(*rec[:3], S, *rec[3:], float(t)) for t in times]
+            slc = slc / np.float64(S * S)
+        out.update(pol=traced["pol"], stokes=np.stack(stokes), stokes_lightcurve=slc)
+    if S is not None:
+        out["samples"] = S
     return out
 
 
 def main_sequence(args, disk):
     """--hotspot R PHI0 SIGMA --times T0 DT N: numbered PNGs next to --output and the light curve as .npy.
+    --samples S: the sequence supersampled, S x S rays per pixel traced once and every frame resolved on the GPU.
     --bfield BR BPHI BZ [--pol-frac P]: also the Stokes frames (I, Q, U) as numbered .npy and the Stokes light curve;
     without --hotspot the spot is dark and the frames show the disk alone."""
     from disk import BField, HotSpot
@@ -369,13 +399,16 @@ def main_sequence(args, disk):
     vfov = np.radians(args.fov_v)
     fov = (2 * np.arctan(np.tan(vfov / 2) * width / height), vfov)
     t0, dt, n = float(args.times[0]), float(args.times[1]), int(args.times[2])
+    if args.adaptive is not None:
+        raise ValueError("--adaptive: sequences (--hotspot / --bfield) are not adaptively sampled; use --samples S alone")
     if args.hotspot is not None:
         spot = HotSpot(r_spot=args.hotspot[0], phi0=args.hotspot[1], sigma=args.hotspot[2], exposure=args.hotspot_exposure)
     else:
         spot, n = HotSpot(exposure=0.0), 1
     field = BField(*args.bfield, pol_frac=args.pol_frac) if args.bfield is not None else None
     out = render_sequence(None, metric, args.r_obs * metric.M, fov, disk, spot, t0 + dt * np.arange(n), shape=(height, width),
-                          psi=(np.radians(args.psi_y), np.radians(args.psi_x)), theta_obs=np.radians(args.theta_obs), bfield=field)
+                          psi=(np.radians(args.psi_y), np.radians(args.psi_x)), theta_obs=np.radians(args.theta_obs), bfield=field,
+                          samples=args.samples)
     stem = args.output[:-4] if args.output.lower().endswith(".png") else args.output
     for i in range(n):
         write_png_rgba8(f"{stem}_{i:04d}.png", out["rgba"][i])
@@ -385,6 +418,8 @@ def main_sequence(args, disk):
             np.save(f"{stem}_stokes_{i:04d}.npy", out["stokes"][i])
         np.save(stem + "_stokes_lightcurve.npy", out["stokes_lightcurve"])
         print(f"Polarization: Stokes frames -> {stem}_stokes_0000.npy ..., Stokes light curve -> {stem}_stokes_lightcurve.npy")
+    if args.samples is not None:
+        print(f"Supersampling: {args.samples} x {args.samples} rays per pixel, every frame resolved on the GPU")
     print(f"Hot spot: one trace ({out['stats']['integrate_ms']:.2f} ms), {n} frames -> {stem}_0000.png ..., light curve -> "
           f"{stem}_lightcurve.npy")
     return out
@@ -638,7 +673,8 @@ def build_parser():
                          "the photon ring included (implies --disk)")
     ap.add_argument("--samples", type=int, default=None, metavar="S",
                     help="anti-aliasing: trace S x S rays per pixel (1 ... 8) and resolve them on the GPU; with --synthetic "
-                         "the background is generated at the fine size, a background file is repeated S times per axis")
+                         "the background is generated at the fine size, a background file is repeated S times per axis; with --hotspot / "
+                         "--bfield the sequence is traced once at the fine size and every frame resolved on the GPU")
     ap.add_argument("--adaptive", type=int, default=None, metavar="S_LO",
                     help="with --samples S_HI: trace S_LO x S_LO rays (1 ... 4) for every pixel and S_HI x S_HI only for the "
                          "pixels on an edge (of the shadow, the disk, the photon ring)")

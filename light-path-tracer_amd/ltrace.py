@@ -224,6 +224,18 @@ SIGNATURES = {
     "lt_hotspot_lightcurve_stokes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                                C.POINTER(Metric), C.POINTER(Disk), C.POINTER(HotSpot), C.POINTER(BField),
                                                C.c_double, C.c_double, C.c_int32, C.c_void_p]),
+    "lt_shade_hotspot_aa_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Metric),
+                                          C.POINTER(Disk), C.POINTER(HotSpot), C.c_double, C.c_void_p, C.c_int32, C.c_void_p,
+                                          C.c_void_p]),
+    "lt_shade_hotspot_aa": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Metric),
+                                      C.POINTER(Disk), C.POINTER(HotSpot), C.c_double, C.c_void_p, C.c_int32, C.c_void_p,
+                                      C.c_void_p]),
+    "lt_shade_stokes_aa_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                         C.POINTER(Metric), C.POINTER(Disk), C.POINTER(HotSpot), C.POINTER(BField), C.c_double,
+                                         C.c_void_p]),
+    "lt_shade_stokes_aa": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                     C.POINTER(Metric), C.POINTER(Disk), C.POINTER(HotSpot), C.POINTER(BField), C.c_double,
+                                     C.c_void_p]),
     "lt_default_aa": (None, [C.POINTER(AA)]),
     "lt_render_aa_dev": (C.c_int, [C.POINTER(Camera), C.POINTER(Metric), C.POINTER(Opts), C.POINTER(AA), C.POINTER(Disk),
                                    C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -1071,6 +1083,67 @@ def hotspot_lightcurve_stokes_dev(d_hits, d_n_hits, d_pol, rows, width, max_imag
     _check(load().lt_hotspot_lightcurve_stokes_dev(_p(d_hits), _p(d_n_hits), _p(d_pol), rows, width, max_images, C.byref(metric),
                                                    C.byref(disk), C.byref(spot), C.byref(field), float(t_start), float(dt),
                                                    int(n_times), _p(d_out)))
+
+
+# ---- supersampled hot-spot and Stokes frames (lt_shade_hotspot_aa, lt_shade_stokes_aa) -------------------------------
+def _fine_shape(hits, samples):
+    """(R, W, S) of the output frame of fine records (R S, W S, max_images, 4)."""
+    S = int(samples)
+    if S < 1 or hits.shape[0] % S or hits.shape[1] % S:
+        raise ValueError(f"fine records of {hits.shape[:2]} pixels are not {S} x {S} samples per pixel")
+    return hits.shape[0] // S, hits.shape[1] // S, S
+
+
+def shade_hotspot_aa(hits, n_hits, samples, metric, disk, spot, t_obs, base=None, channels=None, want=("rgb", "rgba")):
+    """The supersampled frame at observer time t_obs (lt_shade_hotspot_aa): shade_hotspot() of the FINE records hits
+    (rows S, W S, max_images, 4), n_hits (rows S, W S) or None and base (rows S, W S[, 3]) or None, resolved S x S -> 1 on
+    the GPU.  -> dict(rgb (rows, W[, 3]), rgba (rows, W, 4)); ValueError where the fine shape is no multiple of samples."""
+    hits, nh = _hit_arrays(hits, n_hits)
+    R, W, S = _fine_shape(hits, samples)
+    m = hits.shape[2]
+    b = None
+    nch = 3 if channels is None else int(channels)
+    if base is not None:
+        b = np.ascontiguousarray(base, dtype=np.float32)
+        if b.shape[:2] != hits.shape[:2]:
+            raise ValueError("base must have the fine records' rows and width")
+        nch = 1 if b.ndim == 2 else b.shape[2]
+    gray = nch == 1 and (b is None or b.ndim == 2)
+    out = {}
+    if "rgb" in want:
+        out["rgb"] = np.empty((R, W) if gray else (R, W, nch), dtype=np.float32)
+    if "rgba" in want:
+        out["rgba"] = np.empty((R, W, 4), dtype=np.uint8)
+    _check(load().lt_shade_hotspot_aa(_np_ptr(hits), _np_ptr(nh), R, W, S, m, C.byref(metric), C.byref(disk), C.byref(spot),
+                                      float(t_obs), _np_ptr(b), nch, _np_ptr(out.get("rgb")), _np_ptr(out.get("rgba"))))
+    return out
+
+
+def shade_hotspot_aa_dev(d_hits, d_n_hits, rows, width, samples, max_images, metric, disk, spot, t_obs, d_base=0, channels=3,
+                         d_rgb=0, d_rgba=0):
+    """Device-pointer form of shade_hotspot_aa (lt_shade_hotspot_aa_dev): rows, width of the OUTPUT; enqueues on the
+    default stream."""
+    _check(load().lt_shade_hotspot_aa_dev(_p(d_hits), _p(d_n_hits), rows, width, samples, max_images, C.byref(metric),
+                                          C.byref(disk), C.byref(spot), float(t_obs), _p(d_base), channels, _p(d_rgb), _p(d_rgba)))
+
+
+def shade_stokes_aa(hits, n_hits, pol, samples, metric, disk, spot, field, t_obs):
+    """The supersampled Stokes frame at t_obs (lt_shade_stokes_aa): shade_stokes() of the FINE records, resolved S x S -> 1
+    on the GPU -> (rows, W, 3) float32 (I, Q, U)."""
+    hits, nh = _hit_arrays(hits, n_hits)
+    pol = _pol_array(pol, hits)
+    R, W, S = _fine_shape(hits, samples)
+    out = np.empty((R, W, 3), dtype=np.float32)
+    _check(load().lt_shade_stokes_aa(_np_ptr(hits), _np_ptr(nh), _np_ptr(pol), R, W, S, hits.shape[2], C.byref(metric),
+                                     C.byref(disk), C.byref(spot), C.byref(field), float(t_obs), _np_ptr(out)))
+    return out
+
+
+def shade_stokes_aa_dev(d_hits, d_n_hits, d_pol, rows, width, samples, max_images, metric, disk, spot, field, t_obs, d_iqu):
+    """Device-pointer form of shade_stokes_aa (lt_shade_stokes_aa_dev): rows, width of the OUTPUT; enqueues on the default
+    stream."""
+    _check(load().lt_shade_stokes_aa_dev(_p(d_hits), _p(d_n_hits), _p(d_pol), rows, width, samples, max_images, C.byref(metric),
+                                         C.byref(disk), C.byref(spot), C.byref(field), float(t_obs), _p(d_iqu)))
 
 
 # ---- supersampled frames (lt_render_aa) ---------------------------------------------------------------------------
