@@ -651,6 +651,89 @@ int lt_shade_stokes_aa(const float *hits, const uint8_t *n_hits, const float *po
                        int32_t max_images, const lt_metric *metric, const lt_disk *disk, const lt_hotspot *spot,
                        const lt_bfield *field, double t_obs, float *out_iqu);
 
+/* ---- a rotating emissivity map on the disk, shaded from stored hits ------------------------------------------ *
+ * lt_shade_hotspot looks at one Gaussian spot on one orbit.  These entry points look an emissivity up in a table on   *
+ * the disk instead -- spiral arms, clumps, several spots, a snapshot of a simulation -- and turn the table since       *
+ * t = 0, each ring at the disk's own Keplerian rate (the pattern shears) or all of it at one pattern speed.  The       *
+ * records are lt_trace_disk_hits' (r, phi, g, dt), so the light-travel delay is taken per image order, as the hot      *
+ * spot takes it, and nothing is traced again: a frame, a supersampled frame and a light curve, at epilogue cost.       *
+ *                                                                                                               *
+ * The map.  texels (n_r, n_phi) float32, row-major with phi contiguous, plus lt_diskmap.  Texel (i, k) is the          *
+ * emissivity at t = 0 at radius r_min + (i + 1/2)(r_max - r_min)/n_r and azimuth (k + 1/2) 2 pi/n_phi.  Texels must be  *
+ * finite and are not checked.                                                                                    *
+ *                                                                                                               *
+ * Rule.  Per stored slot (hits and n_hits as lt_shade_hotspot takes them), in float64 from the float32 record, in      *
+ * this order:                                                                                                    *
+ *   1. t_em = t_obs - dt;  Omega = sqrt(M) / (r^1.5 + a sqrt(M)) of the hit's own r for LT_MAP_KEPLERIAN (the disk's    *
+ *      rate, the expression of the hot spot's orbit), Omega = omega_p for LT_MAP_RIGID;                               *
+ *   2. psi = wrap_2pi(phi - Omega t_em), the azimuth unwound to t = 0, in [0, 2 pi);                                   *
+ *   3. v = (r - r_min)/(r_max - r_min) n_r - 1/2, clamped to [0, n_r - 1];  i0 = min(floor(v), n_r - 1),               *
+ *      i1 = min(i0 + 1, n_r - 1),  f_r = v - i0: constant extrapolation over the outer half texels;                   *
+ *   4. u = psi (n_phi/2 pi) - 1/2;  k0 = floor(u) mod n_phi (-1 is n_phi - 1),  k1 = (k0 + 1) mod n_phi,                *
+ *      f_phi = u - floor(u): the seam is periodic;                                                                 *
+ *   5. m = (1 - f_r)[(1 - f_phi) T[i0,k0] + f_phi T[i0,k1]] + f_r[(1 - f_phi) T[i1,k0] + f_phi T[i1,k1]];              *
+ *      m = 0 where r < r_min, r > r_max or r is NaN, the float32 r compared exactly against the doubles;              *
+ *   6. E_map = exposure g^4 m ramp(g) -- the hot spot's law with w replaced by m -- and                               *
+ *      rgb = clamp(base + sum_j (with_disk E_j^disk + E_j^map), 0, 1),                                                *
+ *      base first, then the slots in order, each slot's disk term before its map term; a pixel without a stored hit   *
+ *      keeps base.  One channel: the mean of the three, as lt_shade_hotspot.                                          *
+ * base, channels, out_rgb, out_rgba, M and everything else as lt_shade_hotspot takes them.  An all-zero table with      *
+ * with_disk = 1 gives lt_shade_hotspot's frame of a spot with exposure 0.  disk.sample_map / disk.map_emission /        *
+ * disk.shade_diskmap / disk.diskmap_lightcurve (Python) state the rule in numpy.                                      *
+ *                                                                                                               *
+ * Supersampled frames.  lt_shade_diskmap_aa takes the FINE records and base of "supersampled hot-spot and Stokes        *
+ * frames" above; R, W are OUTPUT rows and columns and `samples` follows them.  The result is by definition, and bit    *
+ * for bit, aa.resolve (Python) of the frame lt_shade_diskmap returns for the fine records; samples = 1 is              *
+ * lt_shade_diskmap.  The light curve of fine records is lt_diskmap_lightcurve called with (R S, W S): column 0 / S^2   *
+ * and the moments / S^3 in output-pixel units (image_lens.render_sequence does so).                                  *
+ *                                                                                                               *
+ * Light curve.  out (n_times, 3) float64 at t_start + i dt, i < n_times (<= 65535): the sums of e, e ix and e iy over   *
+ * all pixels and stored slots, e the mean of E_map's channels.  No clamp, no base; lt_hotspot_lightcurve's two-stage    *
+ * reduction in its fixed order, without floating-point atomics: bitwise the same run to run.                          *
+ *                                                                                                               *
+ * Refusals, in this order.  No GPU: LT_ERR_NO_DEVICE (the _aa forms then refuse samples outside                        *
+ * [1, LT_AA_MAX_SAMPLES]: LT_ERR_INVALID_ARG); null hits / metric / disk / map / texels: LT_ERR_INVALID_ARG; a metric    *
+ * that is not LT_METRIC_KERR: LT_ERR_UNSUPPORTED; then LT_ERR_INVALID_ARG for a bad metric, an empty frame, max_images,  *
+ * the map's fields in the struct's order, the disk's q / exposure, channels, and t_obs or t_start / dt / n_times.       *
+ *                                                                                                               *
+ * Out of scope: polarized maps, a map plus a spot in one call, tables that change with time, lt_render_multi and the  *
+ * multi-process path, adaptive sampling of sequences.                                                             */
+#define LT_MAP_KEPLERIAN 0
+#define LT_MAP_RIGID 1
+
+typedef struct lt_diskmap {
+    double r_min, r_max; /* the annulus the table covers, 0 < r_min < r_max, finite */
+    double omega_p;      /* pattern speed for LT_MAP_RIGID (finite; ignored for LT_MAP_KEPLERIAN) */
+    double exposure;     /* brightness scale, finite, >= 0 */
+    int32_t n_r, n_phi;  /* >= 1 each, n_r n_phi <= 2^26 */
+    int32_t rotation;    /* LT_MAP_KEPLERIAN: every radius turns at the disk's own Omega(r); LT_MAP_RIGID: all at omega_p */
+    int32_t with_disk;   /* nonzero: the stationary disk's light is added as lt_shade_hotspot adds it */
+} lt_diskmap;
+void lt_default_diskmap(lt_diskmap *map); /* r_min 6, r_max 20, omega_p 0, exposure 1, 1 x 1 texels, Keplerian, with_disk 1 */
+
+/* The _dev forms take DEVICE pointers (d_texels too) and enqueue on the default stream. */
+int lt_shade_diskmap_dev(const float *d_hits, const uint8_t *d_n_hits, int32_t R, int32_t W, int32_t max_images,
+                         const lt_metric *metric, const lt_disk *disk, const lt_diskmap *map, const float *d_texels,
+                         double t_obs, const float *d_base, int32_t channels, float *d_rgb, uint8_t *d_rgba);
+/* The same with HOST pointers, staged like lt_shade_hotspot; the texels are one more input. */
+int lt_shade_diskmap(const float *hits, const uint8_t *n_hits, int32_t R, int32_t W, int32_t max_images,
+                     const lt_metric *metric, const lt_disk *disk, const lt_diskmap *map, const float *texels, double t_obs,
+                     const float *base, int32_t channels, float *out_rgb, uint8_t *out_rgba);
+int lt_shade_diskmap_aa_dev(const float *d_hits, const uint8_t *d_n_hits, int32_t R, int32_t W, int32_t samples,
+                            int32_t max_images, const lt_metric *metric, const lt_disk *disk, const lt_diskmap *map,
+                            const float *d_texels, double t_obs, const float *d_base /* (R S, W S, channels) or NULL */,
+                            int32_t channels, float *d_rgb /* (R, W, channels) */, uint8_t *d_rgba /* (R, W, 4) */);
+/* The same with HOST pointers; only the resolved outputs come back. */
+int lt_shade_diskmap_aa(const float *hits, const uint8_t *n_hits, int32_t R, int32_t W, int32_t samples, int32_t max_images,
+                        const lt_metric *metric, const lt_disk *disk, const lt_diskmap *map, const float *texels, double t_obs,
+                        const float *base, int32_t channels, float *out_rgb, uint8_t *out_rgba);
+int lt_diskmap_lightcurve_dev(const float *d_hits, const uint8_t *d_n_hits, int32_t R, int32_t W, int32_t max_images,
+                              const lt_metric *metric, const lt_disk *disk, const lt_diskmap *map, const float *d_texels,
+                              double t_start, double dt, int32_t n_times, double *d_out);
+int lt_diskmap_lightcurve(const float *hits, const uint8_t *n_hits, int32_t R, int32_t W, int32_t max_images,
+                          const lt_metric *metric, const lt_disk *disk, const lt_diskmap *map, const float *texels,
+                          double t_start, double dt, int32_t n_times, double *out);
+
 /* ---- supersampled (anti-aliased) frames, resolved on the GPU ------------------------------------------- *
  * Every frame above is one ray per pixel, taken at the pixel's corner.  These entry points trace S x S rays per       *
  * pixel and write only the resolved pixels: nothing of the S^2 times larger frame crosses PCIe or stays in memory.    *

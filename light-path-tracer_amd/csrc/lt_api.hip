@@ -13,6 +13,7 @@
 #include "lt_aa.hpp"
 #include "lt_aa_adaptive.hpp"
 #include "lt_hotspot_aa.hpp"
+#include "lt_diskmap.hpp"
 #ifdef LT_PROBES
 #include "lt_probe.hpp"
 #endif
@@ -1607,5 +1608,6 @@ extern "C" int lt_scatter_rows_indexed_dev(const void *d_rows, void *d_full, con
 #include "lt_api_hotspot.inc"
 #include "lt_api_polarization.inc"
 #include "lt_api_hotspot_aa.inc"
+#include "lt_api_diskmap.inc"
 #include "lt_api_aa.inc"
 #include "lt_api_aa_adaptive.inc"

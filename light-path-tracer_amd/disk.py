@@ -14,7 +14,8 @@ of the first max_images of them to the pixel: rgb = clamp(base + sum_j I_j ramp(
 
 lt_trace_disk_hits stores the light-travel time of every hit as well (step_time restates the rule it integrates with), so
 that a moving source -- HotSpot, a bright spot on a circular orbit -- can be re-shaded at any observer time from one
-trace (shade_hotspot) and reduced to a light curve (lightcurve).
+trace (shade_hotspot) and reduced to a light curve (lightcurve).  DiskMap is the general moving source: an emissivity
+table on the disk that turns with it (shade_diskmap, diskmap_lightcurve; spiral_map and spots_map make tables).
 """
 from dataclasses import dataclass
 from typing import Optional
@@ -248,6 +249,164 @@ def lightcurve(M, a, hits, n_hits, spot, times):
         e = np.where(on, (es[..., 0] + es[..., 1] + es[..., 2]) / 3.0, 0.0).sum(axis=-1)
         out[i] = e.sum(), (e * ix).sum(), (e * iy).sum()
     return out
+
+
+# ---- a rotating emissivity map on the disk (lt_shade_diskmap, lt_shade_diskmap_aa, lt_diskmap_lightcurve) ----------------
+TWO_PI = 6.283185307179586
+
+
+@dataclass
+class DiskMap:
+    """An emissivity table on the disk at coordinate time 0: texels (n_r, n_phi), texel (i, k) at radius
+    r_min + (i + 1/2)(r_max - r_min) / n_r and azimuth (k + 1/2) 2 pi / n_phi, looked up bilinearly (constant beyond the
+    first and last radial centres, periodic in azimuth, 0 outside [r_min, r_max]).  rotation "kepler": every radius turns
+    at the disk's own Omega(r), so the pattern shears; "rigid": all of it at the pattern speed omega_p.  with_disk: add
+    the stationary disk's light as the thin-disk renderer does."""
+    texels: np.ndarray
+    r_min: float = 6.0
+    r_max: float = 20.0
+    rotation: str = "kepler"
+    omega_p: float = 0.0
+    exposure: float = 1.0
+    with_disk: bool = True
+
+    def __post_init__(self):
+        self.texels = np.ascontiguousarray(self.texels, dtype=np.float32)
+        if self.texels.ndim != 2 or self.texels.size == 0:
+            raise ValueError("texels must be (n_r, n_phi)")
+        if self.rotation not in ("kepler", "rigid"):
+            raise ValueError('rotation must be "kepler" or "rigid"')
+
+    def to_lt(self):
+        """The lt_diskmap struct of this map (ltrace.DiskMap); the table itself is .texels."""
+        import ltrace
+        return ltrace.default_diskmap(r_min=float(self.r_min), r_max=float(self.r_max), omega_p=float(self.omega_p),
+                                      exposure=float(self.exposure), n_r=self.texels.shape[0], n_phi=self.texels.shape[1],
+                                      rotation=self.rotation, with_disk=int(bool(self.with_disk)))
+
+
+def wrap_2pi(ph):
+    """phi wrapped to [0, 2 pi), the device's statement."""
+    ph = np.asarray(ph, dtype=np.float64)
+    w = ph - TWO_PI * np.floor(ph * (1.0 / TWO_PI))
+    return np.where((w >= TWO_PI) | (w < 0.0), 0.0, w)
+
+
+def sample_map(dmap, r, psi):
+    """The table's value m at radius r and unwound azimuth psi in [0, 2 pi), float64 (include/ltrace.h, "a rotating
+    emissivity map", steps 3 to 5): bilinear, 0 where r < r_min, r > r_max or r is NaN."""
+    T = dmap.texels.astype(np.float64)
+    n_r, n_phi = T.shape
+    r, psi = np.broadcast_arrays(np.asarray(r, dtype=np.float64), np.asarray(psi, dtype=np.float64))
+    inside = (r >= dmap.r_min) & (r <= dmap.r_max)
+    rr = np.where(inside, r, dmap.r_min)
+    ps = np.where(inside & np.isfinite(psi), psi, 0.0)
+    v = np.clip((rr - dmap.r_min) / (dmap.r_max - dmap.r_min) * float(n_r) - 0.5, 0.0, float(n_r - 1))
+    i0 = np.minimum(np.floor(v).astype(np.int64), n_r - 1)
+    i1 = np.minimum(i0 + 1, n_r - 1)
+    f_r = v - i0
+    u = ps * (n_phi / TWO_PI) - 0.5
+    fl = np.floor(u)
+    k0 = np.mod(fl.astype(np.int64), n_phi)
+    k1 = np.mod(k0 + 1, n_phi)
+    f_p = u - fl
+    m = (1.0 - f_r) * ((1.0 - f_p) * T[i0, k0] + f_p * T[i0, k1]) + f_r * ((1.0 - f_p) * T[i1, k0] + f_p * T[i1, k1])
+    return np.where(inside, m, 0.0)
+
+
+def map_emission(M, a, hits, dmap, t_obs):
+    """E_map (..., max_images, 3) float64 of every slot of `hits` (..., max_images, 4) float32 (r, phi, g, dt), unclamped:
+    exposure g^4 m ramp(g), m the table at the hit's radius and at psi = wrap_2pi(phi - Omega (t_obs - dt)), Omega the
+    disk's own rate at the hit's r ("kepler") or omega_p ("rigid")."""
+    h = np.asarray(hits).astype(np.float64)
+    r, ph, g, dt = h[..., 0], h[..., 1], h[..., 2], h[..., 3]
+    with np.errstate(invalid="ignore"):
+        om = dmap.omega_p if dmap.rotation == "rigid" else omega(M, a, r)
+        m = sample_map(dmap, r, wrap_2pi(ph - om * (t_obs - dt)))
+    inten = dmap.exposure * (g * g) ** 2 * m
+    return np.stack([inten * np.clip(2.0 * g - 0.5 * i, 0.0, 1.0) for i in range(3)], axis=-1)
+
+
+def shade_diskmap(M, a, hits, n_hits, disk, dmap, t_obs, base=None, channels=3):
+    """lt_shade_diskmap restated: float32 (..., 3), or (...) for channels = 1.  shade_hotspot with the map's light in the
+    spot's place: rgb = clamp(base + sum_j (with_disk E_j^disk + E_j^map), 0, 1) in float64, base first, then the slots
+    in order, disk before map; a pixel without a stored hit keeps base."""
+    hits = np.asarray(hits)
+    m = hits.shape[-2]
+    ns = _stored(hits, n_hits)
+    r_in = disk.inner_edge(M, a)
+    shape = hits.shape[:-2] if channels == 1 else hits.shape[:-2] + (3,)
+    base = np.zeros(shape, dtype=np.float32) if base is None else np.asarray(base, dtype=np.float32)
+    acc = base.astype(np.float64)
+    es = map_emission(M, a, hits, dmap, t_obs)
+    for j in range(m):
+        on = ns > j
+        terms = []
+        if dmap.with_disk:
+            r = np.where(on, hits[..., j, 0].astype(np.float64), 1.0)
+            g = np.where(on, hits[..., j, 2].astype(np.float64), 0.0)
+            x = r_in / r
+            inten = disk.exposure * (g * g) ** 2 * x ** disk.q
+            s = g * x ** 0.75
+            terms.append(np.stack([inten * np.clip(2.0 * s - 0.5 * i, 0.0, 1.0) for i in range(3)], axis=-1))
+        terms.append(np.where(on[..., None], es[..., j, :], 0.0))
+        for e in terms:
+            if channels == 1:
+                acc = np.where(on, acc + (e[..., 0] + e[..., 1] + e[..., 2]) / 3.0, acc)
+            else:
+                acc = np.where(on[..., None], acc + e, acc)
+    lit = ns > 0 if channels == 1 else (ns > 0)[..., None]
+    return np.where(lit, np.clip(acc, 0.0, 1.0).astype(np.float32), base)
+
+
+def shade_diskmap_aa(M, a, hits, n_hits, disk, dmap, t_obs, samples, base=None, channels=3):
+    """lt_shade_diskmap_aa restated: shade_diskmap of the FINE records (R S, W S, max_images, 4) (base at the fine size),
+    resolved by the rule of aa.resolve -> float32 (R, W, 3), or (R, W) for channels = 1."""
+    import aa
+    return aa.resolve(shade_diskmap(M, a, hits, n_hits, disk, dmap, t_obs, base=base, channels=channels), samples)
+
+
+def diskmap_lightcurve(M, a, hits, n_hits, dmap, times):
+    """lt_diskmap_lightcurve restated: (len(times), 3) float64, per time the sums of e, e ix, e iy over the pixels of
+    hits (R, W, max_images, 4) and their stored slots, e the mean of E_map's three channels."""
+    hits = np.asarray(hits)
+    R, W, m = hits.shape[:3]
+    on = _stored(hits, n_hits)[..., None] > np.arange(m)
+    iy, ix = np.mgrid[0:R, 0:W].astype(np.float64)
+    out = np.empty((len(times), 3))
+    for i, t in enumerate(times):
+        es = map_emission(M, a, hits, dmap, float(t))
+        e = np.where(on, (es[..., 0] + es[..., 1] + es[..., 2]) / 3.0, 0.0).sum(axis=-1)
+        out[i] = e.sum(), (e * ix).sum(), (e * iy).sum()
+    return out
+
+
+def _texel_centres(n_r, n_phi, r_min, r_max):
+    r = r_min + (np.arange(n_r) + 0.5) * (r_max - r_min) / n_r
+    ph = (np.arange(n_phi) + 0.5) * TWO_PI / n_phi
+    return r[:, None], ph[None, :]
+
+
+def spiral_map(n_r, n_phi, arms=2, pitch=0.35, contrast=0.8, r_min=6.0, r_max=20.0):
+    """Texels (n_r, n_phi) float32 of `arms` logarithmic spiral arms of pitch angle `pitch` (rad) on [r_min, r_max]:
+    1 + contrast cos(arms (phi - ln(r / r_min) / tan(pitch))) at the texel centres, 0 <= contrast <= 1."""
+    if not 0.0 <= contrast <= 1.0:
+        raise ValueError("spiral_map: contrast must be in [0, 1]")
+    r, ph = _texel_centres(n_r, n_phi, r_min, r_max)
+    return (1.0 + contrast * np.cos(arms * (ph - np.log(r / r_min) / np.tan(pitch)))).astype(np.float32)
+
+
+def spots_map(n_r, n_phi, r_min, r_max, spots):
+    """Texels (n_r, n_phi) float32 of a sum of Gaussians on [r_min, r_max]: spots is a sequence of (r_s, phi_s, sigma) or
+    (r_s, phi_s, sigma, amplitude); each adds amplitude exp(-d^2 / 2 sigma^2), d the distance in the plane to the texel
+    centre -- the hot spot's profile at t = 0."""
+    r, ph = _texel_centres(n_r, n_phi, r_min, r_max)
+    out = np.zeros((n_r, n_phi))
+    for sp in spots:
+        r_s, phi_s, sigma = (float(x) for x in sp[:3])
+        amp = float(sp[3]) if len(sp) > 3 else 1.0
+        out += amp * np.exp(-(r * r + r_s * r_s - 2.0 * r * r_s * np.cos(ph - phi_s)) / (2.0 * sigma * sigma))
+    return out.astype(np.float32)
 
 
 # ---- linear polarization (lt_trace_disk_pol, lt_shade_stokes, lt_hotspot_lightcurve_stokes) ------------------------

@@ -303,7 +303,7 @@ def render_frame(source_image, metric, r_obs, fov, psi=(0.0, 0.0), theta_obs=np.
 
 
 def render_sequence(source_image, metric, r_obs, fov, disk, hotspot, times, shape=None, psi=(0.0, 0.0), theta_obs=np.pi / 2,
-                    integrator=None, precision=None, bfield=None, samples=None):
+                    integrator=None, precision=None, bfield=None, samples=None, diskmap=None):
     """A moving picture from ONE trace: an optically thin disk (disk.TransparentDisk) with a hot spot (disk.HotSpot) on a
     circular orbit, at the observer times `times`.  The rays are traced once with the light-travel time of every hit
     (lt_trace_disk_hits); each frame is a re-shade of the stored hits (lt_shade_hotspot) over `base`, the lensed
@@ -321,7 +321,15 @@ def render_sequence(source_image, metric, r_obs, fov, disk, hotspot, times, shap
     `samples`.  lightcurve is the fine records' curve in output-pixel units (column 0 divided by S^2, the first moments
     by S^3) and stokes_lightcurve the fine records' divided by S^2.  The fine records take 16 max_images S^2 H W bytes
     (twice that with a field) and are held for the whole sequence.  samples=None: one ray per pixel, as without it.
+    diskmap (disk.DiskMap): the moving source is an emissivity table on the disk that turns with it instead of a spot;
+    `hotspot` is then None.  Frames come from lt_shade_diskmap (samples: lt_shade_diskmap_aa) and the light curve from
+    lt_diskmap_lightcurve, scaled as above; everything else is as with a spot.  A map together with a spot or with a
+    field is refused: both are out of scope.
     One GPU, every row traced; sequences are not adaptively sampled."""
+    if diskmap is not None and hotspot is not None:
+        raise ValueError("render_sequence: a disk map together with a hot spot is out of scope; pass hotspot=None")
+    if diskmap is not None and bfield is not None:
+        raise ValueError("render_sequence: a disk map is not polarized; pass bfield=None")
     S = None
     if samples is not None:
         S = int(samples)
@@ -350,13 +358,15 @@ def render_sequence(source_image, metric, r_obs, fov, disk, hotspot, times, shap
     cam = _camera(shape, fov, psi, r_obs, theta_obs)      # (with samples: the fine camera)
     if source_image is not None:
         base = ltrace.render(cam, met, opts, background=source_image, want=("rgb",))["rgb"]
-    d, spot = disk.to_lt(), hotspot.to_lt()
+    d, spot = disk.to_lt(), hotspot.to_lt() if diskmap is None else None
     m = int(getattr(disk, "max_images", 3))
     field = bfield.to_lt() if bfield is not None else None
     if field is not None:
         traced = ltrace.trace_disk_pol(cam, met, opts, d, field, max_images=m, want=("hits", "n_hits", "pol"))
     else:
         traced = ltrace.trace_disk_hits(cam, met, opts, d, max_images=m, want=("hits", "n_hits"))
+    if diskmap is not None:
+        return _sequence_diskmap(traced, met, d, diskmap, times, dt, base, S)
     frames, rgba = [], []
     for t in times:
         if S is None:
@@ -384,31 +394,73 @@ def render_sequence(source_image, metric, r_obs, fov, disk, hotspot, times, shap
     return out
 
 
+def _sequence_diskmap(traced, met, d, diskmap, times, dt, base, S):
+    """render_sequence's frames and light curve for a disk map, from the traced records."""
+    dm, tex = diskmap.to_lt(), diskmap.texels
+    frames, rgba = [], []
+    for t in times:
+        if S is None:
+            f = ltrace.shade_diskmap(traced["hits"], traced["n_hits"], met, d, dm, tex, float(t), base=base)
+        else:
+            f = ltrace.shade_diskmap_aa(traced["hits"], traced["n_hits"], S, met, d, dm, tex, float(t), base=base)
+        frames.append(f["rgb"])
+        rgba.append(f["rgba"])
+    lc = ltrace.diskmap_lightcurve(traced["hits"], traced["n_hits"], met, d, dm, tex, float(times[0]), dt, times.size)
+    if S is not None:
+        lc = lc / np.array([S * S, S ** 3, S ** 3], dtype=np.float64)
+    out = dict(frames=np.stack(frames), rgba=np.stack(rgba), lightcurve=lc, hits=traced["hits"], n_hits=traced["n_hits"],
+               stats=traced["stats"])
+    if S is not None:
+        out["samples"] = S
+    return out
+
+
+def diskmap_from_args(args, disk, M, a):
+    """The disk.DiskMap of --disk-map PATH.npy|spiral and its --disk-map-* options; the range defaults to the disk's edges."""
+    from disk import DiskMap, spiral_map
+    r_min, r_max = args.disk_map_range if args.disk_map_range is not None else (disk.inner_edge(M, a), disk.r_out)
+    if args.disk_map == "spiral":
+        texels = spiral_map(256, 1024, r_min=r_min, r_max=r_max)
+    else:
+        texels = np.load(args.disk_map, allow_pickle=False)
+    return DiskMap(texels, r_min=float(r_min), r_max=float(r_max), rotation=args.disk_map_rotation, omega_p=args.disk_map_omega,
+                   exposure=args.disk_map_exposure)
+
+
 def main_sequence(args, disk):
     """--hotspot R PHI0 SIGMA --times T0 DT N: numbered PNGs next to --output and the light curve as .npy.
+    --disk-map PATH.npy|spiral (with --disk-map-range / -rotation / -omega / -exposure): the same for an emissivity table
+    that turns with the disk, in the spot's place.
     --samples S: the sequence supersampled, S x S rays per pixel traced once and every frame resolved on the GPU.
     --bfield BR BPHI BZ [--pol-frac P]: also the Stokes frames (I, Q, U) as numbered .npy and the Stokes light curve;
     without --hotspot the spot is dark and the frames show the disk alone."""
     from disk import BField, HotSpot
+    if args.disk_map is not None and args.hotspot is not None:
+        raise ValueError("--disk-map: a map together with --hotspot is out of scope; use one of them")
+    if args.disk_map is not None and args.bfield is not None:
+        raise ValueError("--disk-map: a map is not polarized; use it without --bfield")
     if not args.synthetic:
-        raise ValueError("--hotspot / --bfield render over a black sky at the size given by --synthetic W H")
+        raise ValueError("--hotspot / --bfield / --disk-map render over a black sky at the size given by --synthetic W H")
     if disk is None or not hasattr(disk, "max_images"):
-        raise ValueError("--hotspot / --bfield need --disk-images N")
+        raise ValueError("--hotspot / --bfield / --disk-map need --disk-images N")
     width, height = int(args.synthetic[0]), int(args.synthetic[1])
     metric = Kerr(M=args.M, a=args.a, integrator=args.integrator, precision=args.precision)
     vfov = np.radians(args.fov_v)
     fov = (2 * np.arctan(np.tan(vfov / 2) * width / height), vfov)
     t0, dt, n = float(args.times[0]), float(args.times[1]), int(args.times[2])
     if args.adaptive is not None:
-        raise ValueError("--adaptive: sequences (--hotspot / --bfield) are not adaptively sampled; use --samples S alone")
-    if args.hotspot is not None:
+        raise ValueError("--adaptive: sequences (--hotspot / --bfield / --disk-map) are not adaptively sampled; use --samples S alone")
+    dmap = None
+    if args.disk_map is not None:
+        spot, dmap = None, diskmap_from_args(args, disk, args.M, args.a)
+    elif args.hotspot is not None:
         spot = HotSpot(r_spot=args.hotspot[0], phi0=args.hotspot[1], sigma=args.hotspot[2], exposure=args.hotspot_exposure)
     else:
         spot, n = HotSpot(exposure=0.0), 1
     field = BField(*args.bfield, pol_frac=args.pol_frac) if args.bfield is not None else None
     out = render_sequence(None, metric, args.r_obs * metric.M, fov, disk, spot, t0 + dt * np.arange(n), shape=(height, width),
                           psi=(np.radians(args.psi_y), np.radians(args.psi_x)), theta_obs=np.radians(args.theta_obs), bfield=field,
-                          samples=args.samples)
+                          samples=args.samples, diskmap=dmap)
     stem = args.output[:-4] if args.output.lower().endswith(".png") else args.output
     for i in range(n):
         write_png_rgba8(f"{stem}_{i:04d}.png", out["rgba"][i])
@@ -420,7 +472,7 @@ def main_sequence(args, disk):
         print(f"Polarization: Stokes frames -> {stem}_stokes_0000.npy ..., Stokes light curve -> {stem}_stokes_lightcurve.npy")
     if args.samples is not None:
         print(f"Supersampling: {args.samples} x {args.samples} rays per pixel, every frame resolved on the GPU")
-    print(f"Hot spot: one trace ({out['stats']['integrate_ms']:.2f} ms), {n} frames -> {stem}_0000.png ..., light curve -> "
+    print(f"{'Hot spot' if dmap is None else 'Disk map'}: one trace ({out['stats']['integrate_ms']:.2f} ms), {n} frames -> {stem}_0000.png ..., light curve -> "
           f"{stem}_lightcurve.npy")
     return out
 
@@ -691,6 +743,15 @@ def build_parser():
                     help="with --disk-images: the magnetic field's direction in the disk material's frame; writes the Stokes "
                          "frames (I, Q, U) as numbered .npy and the Stokes light curve, with --hotspot or without it")
     ap.add_argument("--pol-frac", type=float, default=0.7, help="--bfield: polarization fraction in [0, 1] (default: 0.7)")
+    ap.add_argument("--disk-map", default=None, metavar="PATH.npy|spiral",
+                    help="with --disk-images: an emissivity table (n_r, n_phi) on the disk that turns with it, from a .npy file or "
+                         "the built-in two-armed spiral; re-shaded per --times from one trace like --hotspot, with --samples or without")
+    ap.add_argument("--disk-map-range", type=float, nargs=2, default=None, metavar=("RMIN", "RMAX"),
+                    help="--disk-map: the annulus the table covers, in M (default: the disk's edges)")
+    ap.add_argument("--disk-map-rotation", choices=["kepler", "rigid"], default="kepler",
+                    help="--disk-map: every radius turns at the disk's own rate (kepler, the pattern shears) or all at --disk-map-omega")
+    ap.add_argument("--disk-map-omega", type=float, default=0.0, metavar="W", help="--disk-map-rotation rigid: the pattern speed (1 / M)")
+    ap.add_argument("--disk-map-exposure", type=float, default=1.0, metavar="X", help="--disk-map: brightness scale of the map (default: 1)")
     return ap
 
 
@@ -704,7 +765,7 @@ if __name__ == "__main__":
     elif args.disk:
         from disk import ThinDisk
         disk = ThinDisk(r_in=args.disk_rin, r_out=args.disk_rout, q=args.disk_q, exposure=args.disk_exposure)
-    if args.hotspot is not None or args.bfield is not None:
+    if args.hotspot is not None or args.bfield is not None or args.disk_map is not None:
         main_sequence(args, disk)
         sys.exit(0)
     main(M=args.M, a=args.a, r_obs_mult=args.r_obs, psi=(np.radians(args.psi_y), np.radians(args.psi_x)),

@@ -80,6 +80,15 @@ class HotSpot(C.Structure):
                 ("with_disk", C.c_int32), ("reserved", C.c_int32)]
 
 
+class DiskMap(C.Structure):
+    """lt_diskmap: the annulus, rotation and brightness of an (n_r, n_phi) emissivity table on the disk."""
+    _fields_ = [("r_min", C.c_double), ("r_max", C.c_double), ("omega_p", C.c_double), ("exposure", C.c_double),
+                ("n_r", C.c_int32), ("n_phi", C.c_int32), ("rotation", C.c_int32), ("with_disk", C.c_int32)]
+
+
+MAP_KEPLERIAN, MAP_RIGID = 0, 1
+
+
 class BField(C.Structure):
     """lt_bfield: the field's components in the emitter's frame and the polarization fraction."""
     _fields_ = [("b_r", C.c_double), ("b_phi", C.c_double), ("b_z", C.c_double), ("pol_frac", C.c_double)]
@@ -236,6 +245,25 @@ SIGNATURES = {
     "lt_shade_stokes_aa": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      C.POINTER(Metric), C.POINTER(Disk), C.POINTER(HotSpot), C.POINTER(BField), C.c_double,
                                      C.c_void_p]),
+    "lt_default_diskmap": (None, [C.POINTER(DiskMap)]),
+    "lt_shade_diskmap_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Metric),
+                                       C.POINTER(Disk), C.POINTER(DiskMap), C.c_void_p, C.c_double, C.c_void_p, C.c_int32,
+                                       C.c_void_p, C.c_void_p]),
+    "lt_shade_diskmap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Metric),
+                                   C.POINTER(Disk), C.POINTER(DiskMap), C.c_void_p, C.c_double, C.c_void_p, C.c_int32,
+                                   C.c_void_p, C.c_void_p]),
+    "lt_shade_diskmap_aa_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Metric),
+                                          C.POINTER(Disk), C.POINTER(DiskMap), C.c_void_p, C.c_double, C.c_void_p, C.c_int32,
+                                          C.c_void_p, C.c_void_p]),
+    "lt_shade_diskmap_aa": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Metric),
+                                      C.POINTER(Disk), C.POINTER(DiskMap), C.c_void_p, C.c_double, C.c_void_p, C.c_int32,
+                                      C.c_void_p, C.c_void_p]),
+    "lt_diskmap_lightcurve_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Metric),
+                                            C.POINTER(Disk), C.POINTER(DiskMap), C.c_void_p, C.c_double, C.c_double, C.c_int32,
+                                            C.c_void_p]),
+    "lt_diskmap_lightcurve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Metric),
+                                        C.POINTER(Disk), C.POINTER(DiskMap), C.c_void_p, C.c_double, C.c_double, C.c_int32,
+                                        C.c_void_p]),
     "lt_default_aa": (None, [C.POINTER(AA)]),
     "lt_render_aa_dev": (C.c_int, [C.POINTER(Camera), C.POINTER(Metric), C.POINTER(Opts), C.POINTER(AA), C.POINTER(Disk),
                                    C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -1144,6 +1172,106 @@ def shade_stokes_aa_dev(d_hits, d_n_hits, d_pol, rows, width, samples, max_image
     stream."""
     _check(load().lt_shade_stokes_aa_dev(_p(d_hits), _p(d_n_hits), _p(d_pol), rows, width, samples, max_images, C.byref(metric),
                                          C.byref(disk), C.byref(spot), C.byref(field), float(t_obs), _p(d_iqu)))
+
+
+# ---- a rotating emissivity map on the disk (lt_shade_diskmap, lt_shade_diskmap_aa, lt_diskmap_lightcurve) ----------------
+MAP_ROTATIONS = {"kepler": MAP_KEPLERIAN, "rigid": MAP_RIGID}
+
+
+def default_diskmap(**kw):
+    """lt_diskmap with the library's defaults (r_min 6, r_max 20, omega_p 0, exposure 1, 1 x 1 texels, Keplerian,
+    with_disk 1); keywords override (rotation: "kepler" / "rigid" or the LT_MAP_* value)."""
+    m = DiskMap()
+    load().lt_default_diskmap(C.byref(m))
+    for k, v in kw.items():
+        if k == "rotation" and isinstance(v, str):
+            v = MAP_ROTATIONS[v]
+        setattr(m, k, v)
+    return m
+
+
+def _texel_array(dmap, texels):
+    """The table as the library reads it: C-contiguous float32 of exactly (dmap.n_r, dmap.n_phi) -- the kernels index it
+    with the struct's sizes, so any other shape is refused here."""
+    t = np.ascontiguousarray(texels, dtype=np.float32)
+    if t.shape != (int(dmap.n_r), int(dmap.n_phi)):
+        raise ValueError(f"texels must be (n_r, n_phi) = {(int(dmap.n_r), int(dmap.n_phi))}; got {t.shape}")
+    return t
+
+
+def _shade_frame(fn, hits, nh, R, W, mid, base, channels, want):
+    """The host-pointer call fn(hits, n_hits, R, W, *mid, base, channels, rgb, rgba) of a re-shade whose base has the
+    records' rows and width -> dict(rgb, rgba) of (R, W) pixels."""
+    b = None
+    nch = 3 if channels is None else int(channels)
+    if base is not None:
+        b = np.ascontiguousarray(base, dtype=np.float32)
+        if b.shape[:2] != hits.shape[:2]:
+            raise ValueError("base must have the records' rows and width")
+        nch = 1 if b.ndim == 2 else b.shape[2]
+    gray = nch == 1 and (b is None or b.ndim == 2)
+    out = {}
+    if "rgb" in want:
+        out["rgb"] = np.empty((R, W) if gray else (R, W, nch), dtype=np.float32)
+    if "rgba" in want:
+        out["rgba"] = np.empty((R, W, 4), dtype=np.uint8)
+    _check(fn(_np_ptr(hits), _np_ptr(nh), R, W, *mid, _np_ptr(b), nch, _np_ptr(out.get("rgb")), _np_ptr(out.get("rgba"))))
+    return out
+
+
+def shade_diskmap(hits, n_hits, metric, disk, dmap, texels, t_obs, base=None, channels=None, want=("rgb", "rgba")):
+    """The frame of a rotating emissivity map at observer time t_obs from stored hits (lt_shade_diskmap).  dmap: an
+    ltrace.DiskMap, texels (n_r, n_phi) float32; everything else as shade_hotspot.  -> dict(rgb, rgba)."""
+    hits, nh = _hit_arrays(hits, n_hits)
+    tex = _texel_array(dmap, texels)
+    R, W, m = hits.shape[:3]
+    return _shade_frame(load().lt_shade_diskmap, hits, nh, R, W,
+                        (m, C.byref(metric), C.byref(disk), C.byref(dmap), _np_ptr(tex), float(t_obs)), base, channels, want)
+
+
+def shade_diskmap_dev(d_hits, d_n_hits, rows, width, max_images, metric, disk, dmap, d_texels, t_obs, d_base=0, channels=3,
+                      d_rgb=0, d_rgba=0):
+    """Device-pointer form of shade_diskmap (lt_shade_diskmap_dev): d_texels holds dmap.n_r x dmap.n_phi float32; enqueues
+    on the default stream."""
+    _check(load().lt_shade_diskmap_dev(_p(d_hits), _p(d_n_hits), rows, width, max_images, C.byref(metric), C.byref(disk),
+                                       C.byref(dmap), _p(d_texels), float(t_obs), _p(d_base), channels, _p(d_rgb), _p(d_rgba)))
+
+
+def shade_diskmap_aa(hits, n_hits, samples, metric, disk, dmap, texels, t_obs, base=None, channels=None, want=("rgb", "rgba")):
+    """The supersampled frame of a rotating emissivity map (lt_shade_diskmap_aa): shade_diskmap() of the FINE records
+    (rows S, W S, max_images, 4) and base (rows S, W S[, 3]), resolved S x S -> 1 on the GPU.  -> dict(rgb (rows, W[, 3]),
+    rgba (rows, W, 4)); ValueError where the fine shape is no multiple of samples."""
+    hits, nh = _hit_arrays(hits, n_hits)
+    tex = _texel_array(dmap, texels)
+    R, W, S = _fine_shape(hits, samples)
+    return _shade_frame(load().lt_shade_diskmap_aa, hits, nh, R, W,
+                        (S, hits.shape[2], C.byref(metric), C.byref(disk), C.byref(dmap), _np_ptr(tex), float(t_obs)), base, channels, want)
+
+
+def shade_diskmap_aa_dev(d_hits, d_n_hits, rows, width, samples, max_images, metric, disk, dmap, d_texels, t_obs, d_base=0,
+                         channels=3, d_rgb=0, d_rgba=0):
+    """Device-pointer form of shade_diskmap_aa (lt_shade_diskmap_aa_dev): rows, width of the OUTPUT; enqueues on the
+    default stream."""
+    _check(load().lt_shade_diskmap_aa_dev(_p(d_hits), _p(d_n_hits), rows, width, samples, max_images, C.byref(metric),
+                                          C.byref(disk), C.byref(dmap), _p(d_texels), float(t_obs), _p(d_base), channels,
+                                          _p(d_rgb), _p(d_rgba)))
+
+
+def diskmap_lightcurve(hits, n_hits, metric, disk, dmap, texels, t_start, dt, n_times):
+    """The map's light curve (lt_diskmap_lightcurve) -> (n_times, 3) float64: per time the sums of e, e ix, e iy."""
+    hits, nh = _hit_arrays(hits, n_hits)
+    tex = _texel_array(dmap, texels)
+    R, W, m = hits.shape[:3]
+    out = np.empty((int(n_times), 3))
+    _check(load().lt_diskmap_lightcurve(_np_ptr(hits), _np_ptr(nh), R, W, m, C.byref(metric), C.byref(disk), C.byref(dmap),
+                                        _np_ptr(tex), float(t_start), float(dt), int(n_times), _np_ptr(out)))
+    return out
+
+
+def diskmap_lightcurve_dev(d_hits, d_n_hits, rows, width, max_images, metric, disk, dmap, d_texels, t_start, dt, n_times, d_out):
+    """Device-pointer form of diskmap_lightcurve (lt_diskmap_lightcurve_dev); enqueues on the default stream."""
+    _check(load().lt_diskmap_lightcurve_dev(_p(d_hits), _p(d_n_hits), rows, width, max_images, C.byref(metric), C.byref(disk),
+                                            C.byref(dmap), _p(d_texels), float(t_start), float(dt), int(n_times), _p(d_out)))
 
 
 # ---- supersampled frames (lt_render_aa) ---------------------------------------------------------------------------
