@@ -28,12 +28,11 @@ extern "C" int lt_shade_hotspot_aa_dev(const float *d_hits, const uint8_t *d_n_h
 {
     DiskShade ds;
     HotspotShade hs;
-    int rc = resolve_hotspot_aa(samples);
-    if (rc || (rc = resolve_hotspot(d_hits, R, W, max_images, metric, disk, spot, &ds, &hs))) return rc;
-    if (channels != 1 && channels != 3) return fail(LT_ERR_INVALID_ARG, "channels must be 1 or 3");
-    if (!std::isfinite(t_obs)) return fail(LT_ERR_INVALID_ARG, "t_obs must be finite");
     unsigned blocks;
-    if ((rc = hotspot_aa_grid(R, W, samples, &blocks))) return rc;
+    int rc = resolve_hotspot_aa(samples);
+    if (rc || (rc = resolve_hotspot(d_hits, R, W, max_images, metric, disk, spot, &ds, &hs)) || (rc = check_channels(channels)) ||
+        (rc = check_t_obs(t_obs)) || (rc = hotspot_aa_grid(R, W, samples, &blocks)))
+        return rc;
     k_shade_hotspot_aa<<<blocks, AA_BLOCK>>>(d_hits, d_n_hits, (int64_t)R * W, W, samples, max_images, ds, hs, t_obs, d_base, channels, d_rgb,
                                              d_rgba);
     HIP_TRY(hipGetLastError());
@@ -47,19 +46,13 @@ extern "C" int lt_shade_hotspot_aa(const float *hits, const uint8_t *n_hits, int
     DiskShade ds;
     HotspotShade hs;
     int rc = resolve_hotspot_aa(samples);
-    if (rc || (rc = resolve_hotspot(hits, R, W, max_images, metric, disk, spot, &ds, &hs))) return rc;
-    if (channels != 1 && channels != 3) return fail(LT_ERR_INVALID_ARG, "channels must be 1 or 3");
+    if (rc || (rc = resolve_hotspot(hits, R, W, max_images, metric, disk, spot, &ds, &hs)) || (rc = check_channels(channels))) return rc;
     const size_t n = (size_t)R * W, n_fine = n * (size_t)(samples * samples);
-    Staging st;
-    const int i_h = st.in(hits, n_fine, (size_t)max_images * 16), i_n = st.in(n_hits, n_fine, 1), i_b = st.in(base, n_fine, (size_t)channels * 4);
-    const int i_rgb = st.out(out_rgb, n, (size_t)channels * 4), i_rgba = st.out(out_rgba, n, 4);
-    if ((rc = st.commit(nullptr))) return rc;
-    if ((rc = lt_shade_hotspot_aa_dev(st.dev<const float>(i_h), st.dev<const uint8_t>(i_n), R, W, samples, max_images, metric, disk, spot,
-                                      t_obs, st.dev<const float>(i_b), channels, st.dev<float>(i_rgb), st.dev<uint8_t>(i_rgba))))
-        return rc;
-    if ((rc = st.fetch(i_rgba)) || (rc = st.fetch(i_rgb))) return rc;
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    return LT_OK;
+    return staged_call({{hits, n_fine, (size_t)max_images * 16}, {n_hits, n_fine, 1}, {base, n_fine, (size_t)channels * 4}},
+                       {{out_rgba, n, 4}, {out_rgb, n, (size_t)channels * 4}}, [&](void *const *in, void *const *out) {
+        return lt_shade_hotspot_aa_dev((const float *)in[0], (const uint8_t *)in[1], R, W, samples, max_images, metric, disk, spot, t_obs,
+                                       (const float *)in[2], channels, (float *)out[1], (uint8_t *)out[0]);
+    });
 }
 
 extern "C" int lt_shade_stokes_aa_dev(const float *d_hits, const uint8_t *d_n_hits, const float *d_pol, int32_t R, int32_t W,
@@ -69,8 +62,7 @@ extern "C" int lt_shade_stokes_aa_dev(const float *d_hits, const uint8_t *d_n_hi
     DiskShade ds;
     HotspotShade hs;
     int rc = resolve_hotspot_aa(samples);
-    if (rc || (rc = resolve_stokes(d_hits, d_pol, R, W, max_images, metric, disk, spot, field, &ds, &hs))) return rc;
-    if (!std::isfinite(t_obs)) return fail(LT_ERR_INVALID_ARG, "t_obs must be finite");
+    if (rc || (rc = resolve_stokes(d_hits, d_pol, R, W, max_images, metric, disk, spot, field, &ds, &hs)) || (rc = check_t_obs(t_obs))) return rc;
     if (!d_iqu) return fail(LT_ERR_INVALID_ARG, "null out");
     unsigned blocks;
     if ((rc = hotspot_aa_grid(R, W, samples, &blocks))) return rc;
@@ -88,16 +80,9 @@ extern "C" int lt_shade_stokes_aa(const float *hits, const uint8_t *n_hits, cons
     HotspotShade hs;
     int rc = resolve_hotspot_aa(samples);
     if (rc || (rc = resolve_stokes(hits, pol, R, W, max_images, metric, disk, spot, field, &ds, &hs))) return rc;
-    const size_t n = (size_t)R * W, n_fine = n * (size_t)(samples * samples);
-    Staging st;
-    const int i_h = st.in(hits, n_fine, (size_t)max_images * 16), i_n = st.in(n_hits, n_fine, 1),
-              i_p = st.in(pol, n_fine, (size_t)max_images * 16);
-    const int i_o = st.out(out_iqu, n, 12);
-    if ((rc = st.commit(nullptr))) return rc;
-    if ((rc = lt_shade_stokes_aa_dev(st.dev<const float>(i_h), st.dev<const uint8_t>(i_n), st.dev<const float>(i_p), R, W, samples, max_images,
-                                     metric, disk, spot, field, t_obs, st.dev<float>(i_o))))
-        return rc;
-    if ((rc = st.fetch(i_o))) return rc;
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    return LT_OK;
+    const size_t n = (size_t)R * W, n_fine = n * (size_t)(samples * samples), rec = (size_t)max_images * 16;
+    return staged_call({{hits, n_fine, rec}, {n_hits, n_fine, 1}, {pol, n_fine, rec}}, {{out_iqu, n, 12}}, [&](void *const *in, void *const *out) {
+        return lt_shade_stokes_aa_dev((const float *)in[0], (const uint8_t *)in[1], (const float *)in[2], R, W, samples, max_images, metric,
+                                      disk, spot, field, t_obs, (float *)out[0]);
+    });
 }

@@ -146,8 +146,7 @@ extern "C" int lt_shade_stokes_dev(const float *d_hits, const uint8_t *d_n_hits,
     DiskShade ds;
     HotspotShade hs;
     int rc = resolve_stokes(d_hits, d_pol, R, W, max_images, metric, disk, spot, field, &ds, &hs);
-    if (rc) return rc;
-    if (!std::isfinite(t_obs)) return fail(LT_ERR_INVALID_ARG, "t_obs must be finite");
+    if (rc || (rc = check_t_obs(t_obs))) return rc;
     if (!d_iqu) return fail(LT_ERR_INVALID_ARG, "null out");
     const int64_t n_px = (int64_t)R * W;
     k_shade_stokes<<<(unsigned)((n_px + 255) / 256), 256>>>(d_hits, d_n_hits, d_pol, n_px, max_images, ds, hs, field->pol_frac, t_obs, d_iqu);
@@ -163,17 +162,11 @@ extern "C" int lt_shade_stokes(const float *hits, const uint8_t *n_hits, const f
     HotspotShade hs;
     int rc = resolve_stokes(hits, pol, R, W, max_images, metric, disk, spot, field, &ds, &hs);
     if (rc) return rc;
-    const size_t n = (size_t)R * W;
-    Staging st;
-    const int i_h = st.in(hits, n, (size_t)max_images * 16), i_n = st.in(n_hits, n, 1), i_p = st.in(pol, n, (size_t)max_images * 16);
-    const int i_o = st.out(out_iqu, n, 12);
-    if ((rc = st.commit(nullptr))) return rc;
-    if ((rc = lt_shade_stokes_dev(st.dev<const float>(i_h), st.dev<const uint8_t>(i_n), st.dev<const float>(i_p), R, W, max_images, metric, disk,
-                                  spot, field, t_obs, st.dev<float>(i_o))))
-        return rc;
-    if ((rc = st.fetch(i_o))) return rc;
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    return LT_OK;
+    const size_t n = (size_t)R * W, rec = (size_t)max_images * 16;
+    return staged_call({{hits, n, rec}, {n_hits, n, 1}, {pol, n, rec}}, {{out_iqu, n, 12}}, [&](void *const *in, void *const *out) {
+        return lt_shade_stokes_dev((const float *)in[0], (const uint8_t *)in[1], (const float *)in[2], R, W, max_images, metric, disk, spot,
+                                   field, t_obs, (float *)out[0]);
+    });
 }
 
 extern "C" int lt_hotspot_lightcurve_stokes_dev(const float *d_hits, const uint8_t *d_n_hits, const float *d_pol, int32_t R, int32_t W,
@@ -184,17 +177,10 @@ extern "C" int lt_hotspot_lightcurve_stokes_dev(const float *d_hits, const uint8
     HotspotShade hs;
     int rc = resolve_stokes(d_hits, d_pol, R, W, max_images, metric, disk, spot, field, &ds, &hs);
     if (rc) return rc;
-    if (n_times < 0 || n_times > 65535) return fail(LT_ERR_INVALID_ARG, "n_times %d not in [0, 65535]", (int)n_times);
-    if (!std::isfinite(t_start) || !std::isfinite(dt)) return fail(LT_ERR_INVALID_ARG, "t_start / dt must be finite");
-    if (n_times == 0) return LT_OK;
-    if (!d_out) return fail(LT_ERR_INVALID_ARG, "null out");
-    StreamSlot *sl;
-    if ((rc = get_slot(nullptr, &sl)) || (rc = grow(sl->hotspot, (size_t)n_times * LC_BLOCKS * 3 * sizeof(double), nullptr))) return rc;
-    k_lightcurve_stokes_partial<<<dim3(LC_BLOCKS, (unsigned)n_times), 256>>>(d_hits, d_n_hits, d_pol, (int64_t)R * W, max_images, hs,
-                                                                             field->pol_frac, t_start, dt, (double *)sl->hotspot.p);
-    k_lightcurve_final<<<(unsigned)n_times, 256>>>((const double *)sl->hotspot.p, d_out);
-    HIP_TRY(hipGetLastError());
-    return LT_OK;
+    return launch_lightcurve(t_start, dt, n_times, d_out, [&](dim3 grid, double *partial) {
+        k_lightcurve_stokes_partial<<<grid, 256>>>(d_hits, d_n_hits, d_pol, (int64_t)R * W, max_images, hs, field->pol_frac, t_start, dt,
+                                                   partial);
+    });
 }
 
 extern "C" int lt_hotspot_lightcurve_stokes(const float *hits, const uint8_t *n_hits, const float *pol, int32_t R, int32_t W,
@@ -204,17 +190,10 @@ extern "C" int lt_hotspot_lightcurve_stokes(const float *hits, const uint8_t *n_
     DiskShade ds;
     HotspotShade hs;
     int rc = resolve_stokes(hits, pol, R, W, max_images, metric, disk, spot, field, &ds, &hs);
-    if (rc) return rc;
-    if (n_times < 0 || n_times > 65535) return fail(LT_ERR_INVALID_ARG, "n_times %d not in [0, 65535]", (int)n_times);
-    const size_t n = (size_t)R * W;
-    Staging st;
-    const int i_h = st.in(hits, n, (size_t)max_images * 16), i_n = st.in(n_hits, n, 1), i_p = st.in(pol, n, (size_t)max_images * 16);
-    const int i_o = st.out(out, (size_t)n_times, 24);
-    if ((rc = st.commit(nullptr))) return rc;
-    if ((rc = lt_hotspot_lightcurve_stokes_dev(st.dev<const float>(i_h), st.dev<const uint8_t>(i_n), st.dev<const float>(i_p), R, W, max_images,
-                                               metric, disk, spot, field, t_start, dt, n_times, st.dev<double>(i_o))))
-        return rc;
-    if ((rc = st.fetch(i_o))) return rc;
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    return LT_OK;
+    if (rc || (rc = check_n_times(n_times))) return rc;
+    const size_t n = (size_t)R * W, rec = (size_t)max_images * 16;
+    return staged_call({{hits, n, rec}, {n_hits, n, 1}, {pol, n, rec}}, {{out, (size_t)n_times, 24}}, [&](void *const *in, void *const *out_) {
+        return lt_hotspot_lightcurve_stokes_dev((const float *)in[0], (const uint8_t *)in[1], (const float *)in[2], R, W, max_images, metric,
+                                                disk, spot, field, t_start, dt, n_times, (double *)out_[0]);
+    });
 }

@@ -35,8 +35,45 @@ __device__ __forceinline__ int stored_slots(const float *rec, const uint8_t *n_h
     return ns;
 }
 
-// One pixel per work-item: rgb = clamp(base + sum_j (with_disk E_j^disk + E_j^spot), 0, 1), summed in float64, base first
-// (0 without one), then per slot the disk's light and the spot's.  A pixel without a stored hit keeps base.
+// One pixel of a re-shaded frame: rgb = clamp(base + sum_j (with_disk E_j^disk + E_j^emit), 0, 1), summed in float64, base
+// first (0 without one), then per slot the disk's light and the emitter's.  A pixel without a stored hit keeps base.
+// emit(rec, e): the emitter's unclamped light through one stored hit (hotspot_emission; diskmap_emission of lt_diskmap.hpp).
+// The body of every frame kernel of the family, one-sample and supersampled: they agree bit for bit because it is one.
+template <typename Emit>
+__device__ __forceinline__ void reshade_pixel(const float *hits, const uint8_t *n_hits, int64_t p, int max_images, const DiskShade &ds,
+                                              int with_disk, const float *base, int nch, Emit emit, float *rgb)
+{
+    const float *rec = hits + p * max_images * 4;
+    const int ns = stored_slots(rec, n_hits, p, max_images);
+    rgb[0] = rgb[1] = rgb[2] = 0.0f;
+    if (base) for (int ch = 0; ch < nch; ++ch) rgb[ch] = base[p * nch + ch];
+    double sum[3] = {(double)rgb[0], (double)rgb[1], (double)rgb[2]};
+    for (int j = 0; j < ns; ++j) {
+        double e[3];
+        if (with_disk) {
+            disk_emission(ds, rec[j * 4], rec[j * 4 + 2], e);
+            if (nch == 1) sum[0] += (e[0] + e[1] + e[2]) / 3.0;
+            else { sum[0] += e[0]; sum[1] += e[1]; sum[2] += e[2]; }
+        }
+        emit(rec + j * 4, e);
+        if (nch == 1) sum[0] += (e[0] + e[1] + e[2]) / 3.0;
+        else { sum[0] += e[0]; sum[1] += e[1]; sum[2] += e[2]; }
+    }
+    if (ns > 0) for (int ch = 0; ch < 3; ++ch) rgb[ch] = (float)fmin(fmax(sum[ch], 0.0), 1.0);
+}
+
+// The frame kernels' tail: pixel p of the float32 frame (nch channels) and of the RGBA8 frame, whichever is asked for.
+__device__ __forceinline__ void store_pixel(int64_t p, const float *rgb, int nch, float *out_rgb, uint8_t *out_rgba)
+{
+    if (out_rgb) for (int ch = 0; ch < nch; ++ch) out_rgb[p * nch + ch] = rgb[ch];
+    if (out_rgba) {
+        FrameOut o{};
+        o.rgba = out_rgba;
+        store_rgba(o, p, rgb, nch);
+    }
+}
+
+// One pixel per work-item.
 __global__ void __launch_bounds__(256) k_shade_hotspot(const float *__restrict__ hits, const uint8_t *__restrict__ n_hits, int64_t n_px,
                                                        int max_images, DiskShade ds, HotspotShade hs, double t_obs,
                                                        const float *__restrict__ base, int nch, float *__restrict__ out_rgb,
@@ -44,29 +81,10 @@ __global__ void __launch_bounds__(256) k_shade_hotspot(const float *__restrict__
 {
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (p >= n_px) return;
-    const float *rec = hits + p * max_images * 4;
-    const int ns = stored_slots(rec, n_hits, p, max_images);
-    float rgb[3] = {0.0f, 0.0f, 0.0f};
-    if (base) for (int ch = 0; ch < nch; ++ch) rgb[ch] = base[p * nch + ch];
-    double sum[3] = {(double)rgb[0], (double)rgb[1], (double)rgb[2]};
-    for (int j = 0; j < ns; ++j) {
-        double e[3];
-        if (hs.with_disk) {
-            disk_emission(ds, rec[j * 4], rec[j * 4 + 2], e);
-            if (nch == 1) sum[0] += (e[0] + e[1] + e[2]) / 3.0;
-            else { sum[0] += e[0]; sum[1] += e[1]; sum[2] += e[2]; }
-        }
-        hotspot_emission(hs, t_obs, rec + j * 4, e);
-        if (nch == 1) sum[0] += (e[0] + e[1] + e[2]) / 3.0;
-        else { sum[0] += e[0]; sum[1] += e[1]; sum[2] += e[2]; }
-    }
-    if (ns > 0) for (int ch = 0; ch < 3; ++ch) rgb[ch] = (float)fmin(fmax(sum[ch], 0.0), 1.0);
-    if (out_rgb) for (int ch = 0; ch < nch; ++ch) out_rgb[p * nch + ch] = rgb[ch];
-    if (out_rgba) {
-        FrameOut o{};
-        o.rgba = out_rgba;
-        store_rgba(o, p, rgb, nch);
-    }
+    float rgb[3];
+    reshade_pixel(hits, n_hits, p, max_images, ds, hs.with_disk, base, nch,
+                  [&](const float *rec, double *e) { hotspot_emission(hs, t_obs, rec, e); }, rgb);
+    store_pixel(p, rgb, nch, out_rgb, out_rgba);
 }
 
 // The light curve: per time, sum of e, e ix and e iy over all pixels and stored slots, e the mean of the spot's three
@@ -86,27 +104,42 @@ __device__ __forceinline__ void lc_tree(double (*sh)[3], double *v)
     }
 }
 
+// The first stage: the stride loop of work-item i of workgroup (b, t), the tree and the partial's store.  pixel(p, v) adds
+// pixel p's three columns to v.
+template <typename Pixel> __device__ __forceinline__ void lightcurve_partial(int64_t n_px, double *partial, Pixel pixel)
+{
+    __shared__ double sh[256][3];
+    double v[3] = {0.0, 0.0, 0.0};
+    for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < n_px; p += (int64_t)256 * LC_BLOCKS) pixel(p, v);
+    lc_tree(sh, v);
+    if (threadIdx.x == 0)
+        for (int c = 0; c < 3; ++c) partial[((int64_t)blockIdx.y * LC_BLOCKS + blockIdx.x) * 3 + c] = sh[0][c];
+}
+
+// The columns of an emitter's light curve (the spot's, the map's): (e, e ix, e iy) of pixel p, e the mean of the three
+// channels of emit(rec, e) summed over the pixel's stored slots.
+template <typename Emit>
+__device__ __forceinline__ void lc_add_centroid(const float *hits, const uint8_t *n_hits, int64_t p, int W, int max_images, Emit emit, double *v)
+{
+    const float *rec = hits + p * max_images * 4;
+    const int ns = stored_slots(rec, n_hits, p, max_images);
+    double e_px = 0.0;
+    for (int j = 0; j < ns; ++j) {
+        double e[3];
+        emit(rec + j * 4, e);
+        e_px += (e[0] + e[1] + e[2]) / 3.0;
+    }
+    v[0] += e_px; v[1] += e_px * (double)(p % W); v[2] += e_px * (double)(p / W);
+}
+
 __global__ void __launch_bounds__(256) k_lightcurve_partial(const float *__restrict__ hits, const uint8_t *__restrict__ n_hits, int64_t n_px,
                                                             int W, int max_images, HotspotShade hs, double t_start, double dt,
                                                             double *__restrict__ partial)
 {
-    __shared__ double sh[256][3];
     const double t_obs = t_start + dt * (double)blockIdx.y;
-    double v[3] = {0.0, 0.0, 0.0};
-    for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < n_px; p += (int64_t)256 * LC_BLOCKS) {
-        const float *rec = hits + p * max_images * 4;
-        const int ns = stored_slots(rec, n_hits, p, max_images);
-        double e_px = 0.0;
-        for (int j = 0; j < ns; ++j) {
-            double e[3];
-            hotspot_emission(hs, t_obs, rec + j * 4, e);
-            e_px += (e[0] + e[1] + e[2]) / 3.0;
-        }
-        v[0] += e_px; v[1] += e_px * (double)(p % W); v[2] += e_px * (double)(p / W);
-    }
-    lc_tree(sh, v);
-    if (threadIdx.x == 0)
-        for (int c = 0; c < 3; ++c) partial[((int64_t)blockIdx.y * LC_BLOCKS + blockIdx.x) * 3 + c] = sh[0][c];
+    lightcurve_partial(n_px, partial, [&](int64_t p, double *v) {
+        lc_add_centroid(hits, n_hits, p, W, max_images, [&](const float *rec, double *e) { hotspot_emission(hs, t_obs, rec, e); }, v);
+    });
 }
 
 __global__ void __launch_bounds__(256) k_lightcurve_final(const double *__restrict__ partial, double *__restrict__ out)

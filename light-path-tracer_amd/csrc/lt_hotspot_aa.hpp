@@ -10,11 +10,10 @@
 // t < P adds its slot's S^2 triples in order (j outer, i inner) in float64 from 0.0, divides by (double)(S S) and writes
 // the output pixel.
 //
-// The per-pixel bodies of k_shade_hotspot and k_shade_stokes are RESTATED here, statement for statement, through the
-// same device functions (stored_slots, disk_emission, hotspot_emission, stokes_weight), as DiskPolStep::advance
-// restates DiskTimedStep::advance: hoisting them into a function of their own is a change of those kernels' source, and
-// their code is held byte-identical (tools/kernel_diff.sh).  No floating-point atomics; nothing depends on the launch
-// geometry: a fine pixel's value is a function of its records, a sum's order is the definition's.
+// Phase 1 is the one-sample kernels' own pixel body (reshade_pixel of lt_hotspot.hpp, stokes_pixel of
+// lt_polarization.hpp) on the fine records, so S = 1 is the one-sample frame bit for bit.  No floating-point atomics;
+// nothing depends on the launch geometry: a fine pixel's value is a function of its records, a sum's order is the
+// definition's.
 #pragma once
 #include "lt_aa.hpp"
 #include "lt_polarization.hpp"
@@ -68,24 +67,9 @@ __global__ void __launch_bounds__(AA_BLOCK) k_shade_hotspot_aa(const float *__re
     const int t = (int)threadIdx.x;
     const int64_t p = sl.fine_pixel(t);
     if (p >= 0) {
-        // k_shade_hotspot's body for fine pixel p
-        const float *rec = hits + p * max_images * 4;
-        const int ns = stored_slots(rec, n_hits, p, max_images);
-        float rgb[3] = {0.0f, 0.0f, 0.0f};
-        if (base) for (int ch = 0; ch < nch; ++ch) rgb[ch] = base[p * nch + ch];
-        double sum[3] = {(double)rgb[0], (double)rgb[1], (double)rgb[2]};
-        for (int j = 0; j < ns; ++j) {
-            double e[3];
-            if (hs.with_disk) {
-                disk_emission(ds, rec[j * 4], rec[j * 4 + 2], e);
-                if (nch == 1) sum[0] += (e[0] + e[1] + e[2]) / 3.0;
-                else { sum[0] += e[0]; sum[1] += e[1]; sum[2] += e[2]; }
-            }
-            hotspot_emission(hs, t_obs, rec + j * 4, e);
-            if (nch == 1) sum[0] += (e[0] + e[1] + e[2]) / 3.0;
-            else { sum[0] += e[0]; sum[1] += e[1]; sum[2] += e[2]; }
-        }
-        if (ns > 0) for (int ch = 0; ch < 3; ++ch) rgb[ch] = (float)fmin(fmax(sum[ch], 0.0), 1.0);
+        float rgb[3];
+        reshade_pixel(hits, n_hits, p, max_images, ds, hs.with_disk, base, nch,
+                      [&](const float *rec, double *e) { hotspot_emission(hs, t_obs, rec, e); }, rgb);
         sh_rgb[t][0] = rgb[0]; sh_rgb[t][1] = rgb[1]; sh_rgb[t][2] = rgb[2];
     }
     __syncthreads();
@@ -93,12 +77,7 @@ __global__ void __launch_bounds__(AA_BLOCK) k_shade_hotspot_aa(const float *__re
     if (po >= 0) {
         float rgb[3];
         hotspot_aa_mean(sh_rgb, t, sl.S2, rgb);
-        if (out_rgb) for (int ch = 0; ch < nch; ++ch) out_rgb[po * nch + ch] = rgb[ch];
-        if (out_rgba) {
-            FrameOut o{};
-            o.rgba = out_rgba;
-            store_rgba(o, po, rgb, nch);
-        }
+        store_pixel(po, rgb, nch, out_rgb, out_rgba);
     }
 }
 
@@ -113,21 +92,8 @@ __global__ void __launch_bounds__(AA_BLOCK) k_shade_stokes_aa(const float *__res
     const int t = (int)threadIdx.x;
     const int64_t p = sl.fine_pixel(t);
     if (p >= 0) {
-        // k_shade_stokes' body for fine pixel p
-        const float *rec = hits + p * max_images * 4, *prec = pol + p * max_images * 4;
-        const int ns = stored_slots(rec, n_hits, p, max_images);
-        double sum[3] = {0.0, 0.0, 0.0};
-        for (int j = 0; j < ns; ++j) {
-            double e[3], m;
-            hotspot_emission(hs, t_obs, rec + j * 4, e);
-            m = (e[0] + e[1] + e[2]) / 3.0;
-            if (hs.with_disk) {
-                disk_emission(ds, rec[j * 4], rec[j * 4 + 2], e);
-                m = (e[0] + e[1] + e[2]) / 3.0 + m;
-            }
-            const double w = stokes_weight(pol_frac, prec + j * 4);
-            sum[0] += m; sum[1] += w * (double)prec[j * 4] * m; sum[2] += w * (double)prec[j * 4 + 1] * m;
-        }
+        double sum[3];
+        stokes_pixel(hits, n_hits, pol, p, max_images, ds, hs, pol_frac, t_obs, sum);
         for (int c = 0; c < 3; ++c) sh_iqu[t][c] = (float)sum[c];
     }
     __syncthreads();

@@ -282,16 +282,14 @@ __device__ __forceinline__ double stokes_weight(double pol_frac, const float *pr
     return pol_frac * (double)prec[2] * (double)prec[2];
 }
 
-// One pixel per work-item: out (R, W, 3) float32 = (I, Q, U) at t_obs; the light is the disk's (with_disk) plus the spot's.
-__global__ void __launch_bounds__(256) k_shade_stokes(const float *__restrict__ hits, const uint8_t *__restrict__ n_hits,
-                                                      const float *__restrict__ pol, int64_t n_px, int max_images, DiskShade ds,
-                                                      HotspotShade hs, double pol_frac, double t_obs, float *__restrict__ out)
+// (I, Q, U) of pixel p at t_obs, unrounded; the light is the disk's (with_disk) plus the spot's.  The body of k_shade_stokes
+// and of phase 1 of k_shade_stokes_aa (lt_hotspot_aa.hpp).
+__device__ __forceinline__ void stokes_pixel(const float *hits, const uint8_t *n_hits, const float *pol, int64_t p, int max_images,
+                                             const DiskShade &ds, const HotspotShade &hs, double pol_frac, double t_obs, double *sum)
 {
-    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (p >= n_px) return;
     const float *rec = hits + p * max_images * 4, *prec = pol + p * max_images * 4;
     const int ns = stored_slots(rec, n_hits, p, max_images);
-    double sum[3] = {0.0, 0.0, 0.0};
+    sum[0] = sum[1] = sum[2] = 0.0;
     for (int j = 0; j < ns; ++j) {
         double e[3], m;
         hotspot_emission(hs, t_obs, rec + j * 4, e);
@@ -303,20 +301,29 @@ __global__ void __launch_bounds__(256) k_shade_stokes(const float *__restrict__ 
         const double w = stokes_weight(pol_frac, prec + j * 4);
         sum[0] += m; sum[1] += w * (double)prec[j * 4] * m; sum[2] += w * (double)prec[j * 4 + 1] * m;
     }
+}
+
+// One pixel per work-item: out (R, W, 3) float32 = (I, Q, U) at t_obs.
+__global__ void __launch_bounds__(256) k_shade_stokes(const float *__restrict__ hits, const uint8_t *__restrict__ n_hits,
+                                                      const float *__restrict__ pol, int64_t n_px, int max_images, DiskShade ds,
+                                                      HotspotShade hs, double pol_frac, double t_obs, float *__restrict__ out)
+{
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= n_px) return;
+    double sum[3];
+    stokes_pixel(hits, n_hits, pol, p, max_images, ds, hs, pol_frac, t_obs, sum);
     for (int c = 0; c < 3; ++c) out[p * 3 + c] = (float)sum[c];
 }
 
-// The Stokes light curve of the spot: k_lightcurve_partial's grid, stride and tree (lc_tree) with (I, Q, U) in place of
+// The Stokes light curve of the spot: k_lightcurve_partial's first stage (lightcurve_partial) with (I, Q, U) in place of
 // (e, e ix, e iy); the I column is summed exactly as that kernel's column 0, so it has its bits.
 __global__ void __launch_bounds__(256) k_lightcurve_stokes_partial(const float *__restrict__ hits, const uint8_t *__restrict__ n_hits,
                                                                    const float *__restrict__ pol, int64_t n_px, int max_images,
                                                                    HotspotShade hs, double pol_frac, double t_start, double dt,
                                                                    double *__restrict__ partial)
 {
-    __shared__ double sh[256][3];
     const double t_obs = t_start + dt * (double)blockIdx.y;
-    double v[3] = {0.0, 0.0, 0.0};
-    for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < n_px; p += (int64_t)256 * LC_BLOCKS) {
+    lightcurve_partial(n_px, partial, [&](int64_t p, double *v) {
         const float *rec = hits + p * max_images * 4, *prec = pol + p * max_images * 4;
         const int ns = stored_slots(rec, n_hits, p, max_images);
         double e_px = 0.0, q_px = 0.0, u_px = 0.0;
@@ -328,10 +335,7 @@ __global__ void __launch_bounds__(256) k_lightcurve_stokes_partial(const float *
             e_px += m; q_px += w * (double)prec[j * 4] * m; u_px += w * (double)prec[j * 4 + 1] * m;
         }
         v[0] += e_px; v[1] += q_px; v[2] += u_px;
-    }
-    lc_tree(sh, v);
-    if (threadIdx.x == 0)
-        for (int c = 0; c < 3; ++c) partial[((int64_t)blockIdx.y * LC_BLOCKS + blockIdx.x) * 3 + c] = sh[0][c];
+    });
 }
 // (The second stage is k_lightcurve_final itself: it adds three columns of partials whatever they mean.)
 

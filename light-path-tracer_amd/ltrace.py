@@ -378,10 +378,8 @@ def trace_batch_schw(M, r_obs, alphas, out_fa, out_w, phi_max=50.0, h_max=0.05, 
                                       _np_ptr(out_rhs_evals)))
 
 
-def trace_batch_kerr(M, a, r_obs, alphas, thetas, theta_obs, lambda_max, axis_refines, out_fa, out_w,
-                     integrator=INTEGRATOR_RK4, precision=32, schedule=SCHED_DIRECT,
-                     out_status=None, out_rhs_evals=None):
-    """In-place twin of _trace_rays_batch_kerr (reference metrics.py:671-679)."""
+def _ray_inputs(alphas, thetas, axis_refines):
+    """The rays of a batch call as the library reads them -> (alphas f64, thetas f64, axis_refines u8 or None, n)."""
     al = np.ascontiguousarray(alphas, dtype=np.float64)
     th = np.ascontiguousarray(thetas, dtype=np.float64)
     n = al.size
@@ -392,14 +390,24 @@ def trace_batch_kerr(M, a, r_obs, alphas, thetas, theta_obs, lambda_max, axis_re
         ar = np.ascontiguousarray(axis_refines).astype(np.uint8)
         if ar.size != n:
             raise ValueError("axis_refines has the wrong length")
+    return al, th, ar, n
+
+
+def _named(table, v):
+    """An integrator / schedule given by name or by the library's value."""
+    return table[v] if isinstance(v, str) else v
+
+
+def trace_batch_kerr(M, a, r_obs, alphas, thetas, theta_obs, lambda_max, axis_refines, out_fa, out_w,
+                     integrator=INTEGRATOR_RK4, precision=32, schedule=SCHED_DIRECT,
+                     out_status=None, out_rhs_evals=None):
+    """In-place twin of _trace_rays_batch_kerr (reference metrics.py:671-679)."""
+    al, th, ar, n = _ray_inputs(alphas, thetas, axis_refines)
     _out(out_fa, np.float64, n, "out_fa")
     _out(out_w, np.int64, n, "out_w")
     _out(out_status, np.int8, n, "out_status")
     _out(out_rhs_evals, np.uint32, n, "out_rhs_evals")
-    if isinstance(integrator, str):
-        integrator = INTEGRATORS[integrator]
-    if isinstance(schedule, str):
-        schedule = SCHEDULES[schedule]
+    integrator, schedule = _named(INTEGRATORS, integrator), _named(SCHEDULES, schedule)
     _check(load().lt_trace_batch_kerr(M, a, r_obs, _np_ptr(al), _np_ptr(th), theta_obs, lambda_max, _np_ptr(ar),
                                       integrator, precision, schedule, n, _np_ptr(out_fa), _np_ptr(out_w),
                                       _np_ptr(out_status), _np_ptr(out_rhs_evals)))
@@ -512,6 +520,16 @@ def _frame_outputs(rows, W, nch, gray, want):
     return out
 
 
+def _frame_rows(cam, opts):
+    if opts.block_owner:
+        rows = len(owned_rows(cam.height, opts.row_block or 16, opts._owner_keep, opts.part))
+    else:
+        rows = local_rows(cam.height, opts.row_block or 16, opts.n_parts or 1, opts.part)
+    if rows < 0 or cam.width <= 0:
+        raise LtraceError(ERR_INVALID_ARG, f"bad frame {cam.width}x{cam.height} or partition {opts.part}/{opts.n_parts}")
+    return rows
+
+
 def _background(cam, background):
     if background is None:
         return None, 3, False
@@ -526,12 +544,7 @@ def _background(cam, background):
 
 def render(cam, metric, opts, background=None, want=("fa", "winding", "status", "steps", "rgb", "rgba")):
     """Host-pointer frame render (lt_render).  Returns dict of numpy arrays (pinned memory) + 'stats'."""
-    if opts.block_owner:
-        rows = len(owned_rows(cam.height, opts.row_block or 16, opts._owner_keep, opts.part))
-    else:
-        rows = local_rows(cam.height, opts.row_block or 16, opts.n_parts or 1, opts.part)
-    if rows < 0 or cam.width <= 0:
-        raise LtraceError(ERR_INVALID_ARG, f"bad frame {cam.width}x{cam.height} or partition {opts.part}/{opts.n_parts}")
+    rows = _frame_rows(cam, opts)
     bg, nch, gray = _background(cam, background)
     out = _frame_outputs(rows, cam.width, nch, gray, want)
     st = Stats()
@@ -655,6 +668,14 @@ def stats_dict(counters, prologue_ms=0.0, integrate_ms=0.0, epilogue_ms=0.0):
                 prologue_ms=prologue_ms, integrate_ms=integrate_ms, epilogue_ms=epilogue_ms)
 
 
+def _disk_stats(st):
+    """stats_dict of a call's Stats with the disk's counters: 'disk' (rays with a hit) and 'disk_hits' (all hits)."""
+    d = stats_dict(st.counters, st.prologue_ms, st.integrate_ms, st.epilogue_ms)
+    d["disk"] = int(st.counters[STAT_DISK])
+    d["disk_hits"] = int(st.counters[STAT_DISK_HITS])
+    return d
+
+
 def render_dev(cam, metric, opts, d_bg=0, bg_channels=3, d_fa=0, d_w=0, d_status=0, d_steps=0, d_rgb=0, d_rgba=0,
                d_stats=0):
     """Device-pointer frame render (lt_render_dev); pointers are integers (tensor.data_ptr()), 0 = NULL.
@@ -726,12 +747,7 @@ def render_disk(cam, metric, opts, disk, background=None,
                 want=("fa", "winding", "status", "steps", "rgb", "rgba", "disk")):
     """Host-pointer frame render with the accretion disk (lt_render_disk).  As render(), plus 'disk':
     (rows, W, 3) float32 (r_hit, phi_hit, g), NaN off the disk; stats gain 'disk' (rays that ended on it)."""
-    if opts.block_owner:
-        rows = len(owned_rows(cam.height, opts.row_block or 16, opts._owner_keep, opts.part))
-    else:
-        rows = local_rows(cam.height, opts.row_block or 16, opts.n_parts or 1, opts.part)
-    if rows < 0 or cam.width <= 0:
-        raise LtraceError(ERR_INVALID_ARG, f"bad frame {cam.width}x{cam.height} or partition {opts.part}/{opts.n_parts}")
+    rows = _frame_rows(cam, opts)
     bg, nch, gray = _background(cam, background)
     out = _frame_outputs(rows, cam.width, nch, gray, want)
     if "disk" in want:
@@ -757,18 +773,8 @@ def trace_batch_kerr_disk(M, a, r_obs, alphas, thetas, theta_obs, lambda_max, di
                           integrator=INTEGRATOR_RK4, precision=32):
     """Batch twin with the accretion disk (lt_trace_batch_kerr_disk) ->
     dict(fa (n,) f64, winding (n,) i64, status (n,) i8, disk (n, 3) f64 (r_hit, phi_hit, g), rhs_evals (n,) u32)."""
-    al = np.ascontiguousarray(alphas, dtype=np.float64)
-    th = np.ascontiguousarray(thetas, dtype=np.float64)
-    n = al.size
-    if th.size != n:
-        raise ValueError("alphas and thetas differ in length")
-    ar = None
-    if axis_refines is not None:
-        ar = np.ascontiguousarray(axis_refines).astype(np.uint8)
-        if ar.size != n:
-            raise ValueError("axis_refines has the wrong length")
-    if isinstance(integrator, str):
-        integrator = INTEGRATORS[integrator]
+    al, th, ar, n = _ray_inputs(alphas, thetas, axis_refines)
+    integrator = _named(INTEGRATORS, integrator)
     out = dict(fa=np.empty(n), winding=np.empty(n, dtype=np.int64), status=np.empty(n, dtype=np.int8),
                disk=np.empty((n, 3)), rhs_evals=np.empty(n, dtype=np.uint32))
     _check(load().lt_trace_batch_kerr_disk(M, a, r_obs, _np_ptr(al), _np_ptr(th), theta_obs, lambda_max, _np_ptr(ar),
@@ -779,16 +785,6 @@ def trace_batch_kerr_disk(M, a, r_obs, alphas, thetas, theta_obs, lambda_max, di
 
 
 # ---- optically thin disk: every image (lt_render_disk_images) ------------------------------------------------------
-def _frame_rows(cam, opts):
-    if opts.block_owner:
-        rows = len(owned_rows(cam.height, opts.row_block or 16, opts._owner_keep, opts.part))
-    else:
-        rows = local_rows(cam.height, opts.row_block or 16, opts.n_parts or 1, opts.part)
-    if rows < 0 or cam.width <= 0:
-        raise LtraceError(ERR_INVALID_ARG, f"bad frame {cam.width}x{cam.height} or partition {opts.part}/{opts.n_parts}")
-    return rows
-
-
 def render_disk_images(cam, metric, opts, disk, max_images=3, background=None,
                        want=("fa", "winding", "status", "steps", "rgb", "rgba", "images", "n_hits")):
     """Host-pointer frame render with the optically thin disk (lt_render_disk_images).  As render(), plus 'images':
@@ -808,9 +804,7 @@ def render_disk_images(cam, metric, opts, disk, max_images=3, background=None,
                                         _np_ptr(out.get("status")), _np_ptr(out.get("steps")), _np_ptr(out.get("images")),
                                         _np_ptr(out.get("n_hits")), _np_ptr(out.get("rgb")), _np_ptr(out.get("rgba")),
                                         C.byref(st)))
-    out["stats"] = stats_dict(st.counters, st.prologue_ms, st.integrate_ms, st.epilogue_ms)
-    out["stats"]["disk"] = int(st.counters[STAT_DISK])
-    out["stats"]["disk_hits"] = int(st.counters[STAT_DISK_HITS])
+    out["stats"] = _disk_stats(st)
     return out
 
 
@@ -828,18 +822,8 @@ def trace_batch_kerr_disk_images(M, a, r_obs, alphas, thetas, theta_obs, lambda_
     """Batch twin with the optically thin disk (lt_trace_batch_kerr_disk_images) -> dict(fa (n,) f64, winding (n,) i64,
     status (n,) i8 (trace_batch_kerr's), images (n, max_images, 3) f64 (r_hit, phi_hit, g), NaN in unused slots,
     n_hits (n,) i32, rhs_evals (n,) u32)."""
-    al = np.ascontiguousarray(alphas, dtype=np.float64)
-    th = np.ascontiguousarray(thetas, dtype=np.float64)
-    n = al.size
-    if th.size != n:
-        raise ValueError("alphas and thetas differ in length")
-    ar = None
-    if axis_refines is not None:
-        ar = np.ascontiguousarray(axis_refines).astype(np.uint8)
-        if ar.size != n:
-            raise ValueError("axis_refines has the wrong length")
-    if isinstance(integrator, str):
-        integrator = INTEGRATORS[integrator]
+    al, th, ar, n = _ray_inputs(alphas, thetas, axis_refines)
+    integrator = _named(INTEGRATORS, integrator)
     m = int(max_images)
     out = dict(fa=np.empty(n), winding=np.empty(n, dtype=np.int64), status=np.empty(n, dtype=np.int8),
                images=np.empty((n, max(m, 0), 3)), n_hits=np.empty(n, dtype=np.int32),
@@ -868,9 +852,7 @@ def trace_disk_hits(cam, metric, opts, disk, max_images=3, want=("fa", "winding"
                                      _np_ptr(out.get("fa")), _np_ptr(out.get("winding")), _np_ptr(out.get("status")),
                                      _np_ptr(out.get("steps")), _np_ptr(out.get("hits")), _np_ptr(out.get("n_hits")),
                                      C.byref(st)))
-    out["stats"] = stats_dict(st.counters, st.prologue_ms, st.integrate_ms, st.epilogue_ms)
-    out["stats"]["disk"] = int(st.counters[STAT_DISK])
-    out["stats"]["disk_hits"] = int(st.counters[STAT_DISK_HITS])
+    out["stats"] = _disk_stats(st)
     return out
 
 
@@ -885,18 +867,8 @@ def trace_batch_kerr_disk_hits(M, a, r_obs, alphas, thetas, theta_obs, lambda_ma
                                axis_refines=None, integrator=INTEGRATOR_RK4, precision=32):
     """Batch twin of the timed trace (lt_trace_batch_kerr_disk_hits): trace_batch_kerr_disk_images() with 'hits'
     (n, max_images, 4) f64 (r_hit, phi_hit, g, light-travel time) in place of 'images'."""
-    al = np.ascontiguousarray(alphas, dtype=np.float64)
-    th = np.ascontiguousarray(thetas, dtype=np.float64)
-    n = al.size
-    if th.size != n:
-        raise ValueError("alphas and thetas differ in length")
-    ar = None
-    if axis_refines is not None:
-        ar = np.ascontiguousarray(axis_refines).astype(np.uint8)
-        if ar.size != n:
-            raise ValueError("axis_refines has the wrong length")
-    if isinstance(integrator, str):
-        integrator = INTEGRATORS[integrator]
+    al, th, ar, n = _ray_inputs(alphas, thetas, axis_refines)
+    integrator = _named(INTEGRATORS, integrator)
     m = int(max_images)
     out = dict(fa=np.empty(n), winding=np.empty(n, dtype=np.int64), status=np.empty(n, dtype=np.int8),
                hits=np.empty((n, max(m, 0), 4)), n_hits=np.empty(n, dtype=np.int32),
@@ -942,17 +914,15 @@ def _hit_arrays(hits, n_hits):
     return hits, nh
 
 
-def shade_hotspot(hits, n_hits, metric, disk, spot, t_obs, base=None, channels=None, want=("rgb", "rgba")):
-    """The frame at observer time t_obs from stored hits (lt_shade_hotspot).  base: (rows, W) or (rows, W, 3) float32
-    or None (black; `channels` 1 or 3 then picks the output's shape, default 3).  -> dict(rgb, rgba)."""
-    hits, nh = _hit_arrays(hits, n_hits)
-    R, W, m = hits.shape[:3]
-    b, gray = None, False
+def _shade_frame(fn, hits, nh, R, W, mid, base, channels, want):
+    """The host-pointer call fn(hits, n_hits, R, W, *mid, base, channels, rgb, rgba) of a re-shade whose base has the
+    records' rows and width -> dict(rgb, rgba) of (R, W) pixels."""
+    b = None
     nch = 3 if channels is None else int(channels)
     if base is not None:
         b = np.ascontiguousarray(base, dtype=np.float32)
-        if b.shape[:2] != (R, W):
-            raise ValueError("base must have the hits' rows and width")
+        if b.shape[:2] != hits.shape[:2]:
+            raise ValueError("base must have the records' rows and width")
         nch = 1 if b.ndim == 2 else b.shape[2]
     gray = nch == 1 and (b is None or b.ndim == 2)
     out = {}
@@ -960,9 +930,17 @@ def shade_hotspot(hits, n_hits, metric, disk, spot, t_obs, base=None, channels=N
         out["rgb"] = np.empty((R, W) if gray else (R, W, nch), dtype=np.float32)
     if "rgba" in want:
         out["rgba"] = np.empty((R, W, 4), dtype=np.uint8)
-    _check(load().lt_shade_hotspot(_np_ptr(hits), _np_ptr(nh), R, W, m, C.byref(metric), C.byref(disk), C.byref(spot),
-                                   float(t_obs), _np_ptr(b), nch, _np_ptr(out.get("rgb")), _np_ptr(out.get("rgba"))))
+    _check(fn(_np_ptr(hits), _np_ptr(nh), R, W, *mid, _np_ptr(b), nch, _np_ptr(out.get("rgb")), _np_ptr(out.get("rgba"))))
     return out
+
+
+def shade_hotspot(hits, n_hits, metric, disk, spot, t_obs, base=None, channels=None, want=("rgb", "rgba")):
+    """The frame at observer time t_obs from stored hits (lt_shade_hotspot).  base: (rows, W) or (rows, W, 3) float32
+    or None (black; `channels` 1 or 3 then picks the output's shape, default 3).  -> dict(rgb, rgba)."""
+    hits, nh = _hit_arrays(hits, n_hits)
+    R, W, m = hits.shape[:3]
+    return _shade_frame(load().lt_shade_hotspot, hits, nh, R, W, (m, C.byref(metric), C.byref(disk), C.byref(spot), float(t_obs)),
+                        base, channels, want)
 
 
 def shade_hotspot_dev(d_hits, d_n_hits, rows, width, max_images, metric, disk, spot, t_obs, d_base=0, channels=3, d_rgb=0,
@@ -1014,9 +992,7 @@ def trace_disk_pol(cam, metric, opts, disk, field, max_images=3,
                                     _np_ptr(out.get("fa")), _np_ptr(out.get("winding")), _np_ptr(out.get("status")),
                                     _np_ptr(out.get("steps")), _np_ptr(out.get("hits")), _np_ptr(out.get("n_hits")),
                                     _np_ptr(out.get("pol")), C.byref(st)))
-    out["stats"] = stats_dict(st.counters, st.prologue_ms, st.integrate_ms, st.epilogue_ms)
-    out["stats"]["disk"] = int(st.counters[STAT_DISK])
-    out["stats"]["disk_hits"] = int(st.counters[STAT_DISK_HITS])
+    out["stats"] = _disk_stats(st)
     return out
 
 
@@ -1032,18 +1008,8 @@ def trace_batch_kerr_disk_pol(M, a, r_obs, alphas, thetas, theta_obs, lambda_max
                               axis_refines=None, integrator=INTEGRATOR_RK4, precision=32):
     """Batch twin of the polarized trace (lt_trace_batch_kerr_disk_pol): trace_batch_kerr_disk_hits() plus 'pol'
     (n, max_images, 4) f64 (q, u, sin zeta, mu)."""
-    al = np.ascontiguousarray(alphas, dtype=np.float64)
-    th = np.ascontiguousarray(thetas, dtype=np.float64)
-    n = al.size
-    if th.size != n:
-        raise ValueError("alphas and thetas differ in length")
-    ar = None
-    if axis_refines is not None:
-        ar = np.ascontiguousarray(axis_refines).astype(np.uint8)
-        if ar.size != n:
-            raise ValueError("axis_refines has the wrong length")
-    if isinstance(integrator, str):
-        integrator = INTEGRATORS[integrator]
+    al, th, ar, n = _ray_inputs(alphas, thetas, axis_refines)
+    integrator = _named(INTEGRATORS, integrator)
     m = int(max_images)
     out = dict(fa=np.empty(n), winding=np.empty(n, dtype=np.int64), status=np.empty(n, dtype=np.int8),
                hits=np.empty((n, max(m, 0), 4)), n_hits=np.empty(n, dtype=np.int32), pol=np.empty((n, max(m, 0), 4)),
@@ -1128,23 +1094,8 @@ def shade_hotspot_aa(hits, n_hits, samples, metric, disk, spot, t_obs, base=None
     the GPU.  -> dict(rgb (rows, W[, 3]), rgba (rows, W, 4)); ValueError where the fine shape is no multiple of samples."""
     hits, nh = _hit_arrays(hits, n_hits)
     R, W, S = _fine_shape(hits, samples)
-    m = hits.shape[2]
-    b = None
-    nch = 3 if channels is None else int(channels)
-    if base is not None:
-        b = np.ascontiguousarray(base, dtype=np.float32)
-        if b.shape[:2] != hits.shape[:2]:
-            raise ValueError("base must have the fine records' rows and width")
-        nch = 1 if b.ndim == 2 else b.shape[2]
-    gray = nch == 1 and (b is None or b.ndim == 2)
-    out = {}
-    if "rgb" in want:
-        out["rgb"] = np.empty((R, W) if gray else (R, W, nch), dtype=np.float32)
-    if "rgba" in want:
-        out["rgba"] = np.empty((R, W, 4), dtype=np.uint8)
-    _check(load().lt_shade_hotspot_aa(_np_ptr(hits), _np_ptr(nh), R, W, S, m, C.byref(metric), C.byref(disk), C.byref(spot),
-                                      float(t_obs), _np_ptr(b), nch, _np_ptr(out.get("rgb")), _np_ptr(out.get("rgba"))))
-    return out
+    return _shade_frame(load().lt_shade_hotspot_aa, hits, nh, R, W,
+                        (S, hits.shape[2], C.byref(metric), C.byref(disk), C.byref(spot), float(t_obs)), base, channels, want)
 
 
 def shade_hotspot_aa_dev(d_hits, d_n_hits, rows, width, samples, max_images, metric, disk, spot, t_obs, d_base=0, channels=3,
@@ -1197,26 +1148,6 @@ def _texel_array(dmap, texels):
     if t.shape != (int(dmap.n_r), int(dmap.n_phi)):
         raise ValueError(f"texels must be (n_r, n_phi) = {(int(dmap.n_r), int(dmap.n_phi))}; got {t.shape}")
     return t
-
-
-def _shade_frame(fn, hits, nh, R, W, mid, base, channels, want):
-    """The host-pointer call fn(hits, n_hits, R, W, *mid, base, channels, rgb, rgba) of a re-shade whose base has the
-    records' rows and width -> dict(rgb, rgba) of (R, W) pixels."""
-    b = None
-    nch = 3 if channels is None else int(channels)
-    if base is not None:
-        b = np.ascontiguousarray(base, dtype=np.float32)
-        if b.shape[:2] != hits.shape[:2]:
-            raise ValueError("base must have the records' rows and width")
-        nch = 1 if b.ndim == 2 else b.shape[2]
-    gray = nch == 1 and (b is None or b.ndim == 2)
-    out = {}
-    if "rgb" in want:
-        out["rgb"] = np.empty((R, W) if gray else (R, W, nch), dtype=np.float32)
-    if "rgba" in want:
-        out["rgba"] = np.empty((R, W, 4), dtype=np.uint8)
-    _check(fn(_np_ptr(hits), _np_ptr(nh), R, W, *mid, _np_ptr(b), nch, _np_ptr(out.get("rgb")), _np_ptr(out.get("rgba"))))
-    return out
 
 
 def shade_diskmap(hits, n_hits, metric, disk, dmap, texels, t_obs, base=None, channels=None, want=("rgb", "rgba")):
@@ -1318,9 +1249,7 @@ def _aa_render(fn, cam, metric, opts, aa, disk, rows, bgs, nch, gray, want, plan
     _check(fn(C.byref(cam), C.byref(metric), C.byref(opts), C.byref(aa), None if disk is None else C.byref(disk),
               *[_np_ptr(bg) for bg in bgs], nch, _np_ptr(out.get("rgb")), _np_ptr(out.get("rgba")),
               *[_np_ptr(out.get(name)) for name in planes], C.byref(st)))
-    out["stats"] = stats_dict(st.counters, st.prologue_ms, st.integrate_ms, st.epilogue_ms)
-    out["stats"]["disk"] = int(st.counters[STAT_DISK])
-    out["stats"]["disk_hits"] = int(st.counters[STAT_DISK_HITS])
+    out["stats"] = _disk_stats(st)
     return out, st
 
 
