@@ -734,6 +734,90 @@ int lt_diskmap_lightcurve(const float *hits, const uint8_t *n_hits, int32_t R, i
                           const lt_metric *metric, const lt_disk *disk, const lt_diskmap *map, const float *texels,
                           double t_start, double dt, int32_t n_times, double *out);
 
+/* ---- energy-resolved light: line profiles and dynamic spectra binned from the stored hits -------------------- *
+ * Every product above is bolometric: g^4 times an emissivity through the colour ramp.  These entry points bin the      *
+ * same unclamped intensities by the redshift factor g = E_obs / E_rest each record stores: for the stationary disk the  *
+ * relativistically broadened line (lt_disk_spectrum), for the moving emitters the dynamic spectrum, flux per energy bin *
+ * per observer time (lt_hotspot_spectrum, lt_diskmap_spectrum).  Every image order is binned at its own emission time   *
+ * t_obs - dt, so the photon ring draws the spot's trail in g again, delayed.  A fourth reduction over the records of     *
+ * lt_trace_disk_hits, next to the frame, the supersampled frame and the light curve; nothing is traced again.            *
+ *                                                                                                               *
+ * Grid.  lt_spectrum is a linear grid in g: 0 < g_min < g_max, both finite, n_bins in 1 ... LT_SPECTRUM_MAX_BINS.        *
+ *                                                                                                               *
+ * Bin of a hit, in float64 from the stored float32 g, in exactly this form (a subtraction followed by a                *
+ * multiplication: nothing an fma can contract, so every statement of the rule picks the same bin):                      *
+ *     inv_dg = n_bins / (g_max - g_min)          (computed once on the host)                                           *
+ *     x = (double)g                                                                                                  *
+ *     k = x < g_min ? 0 : x >= g_max ? n_bins + 1 : 1 + min((int)floor((x - g_min) * inv_dg), n_bins - 1)              *
+ * Column 0 is the underflow, column n_bins + 1 the overflow; bin k = 1 ... n_bins is half-open,                        *
+ * [g_min + (k - 1) dg, g_min + k dg).  A stored slot whose g is NaN is skipped; nothing else is filtered.              *
+ *                                                                                                               *
+ * Weight of a hit, float64: the unclamped intensity the emitter's frames and light curve multiply the ramp with,       *
+ *     the disk:  disk.exposure g^4 (r_in / r)^q                                                                        *
+ *     the spot:  spot.exposure g^4 exp(-d^2 / 2 sigma^2)      at t_obs - dt  ("hit times and an orbiting hot spot")     *
+ *     the map:   map.exposure g^4 m                           the table turned to t_obs - dt ("a rotating emissivity map") *
+ * (with_disk is not looked at: a spectrum is one emitter's).  The stored slots are the re-shades': the first            *
+ * min(n_hits, max_images), or the leading slots whose r is not NaN when n_hits is NULL.                              *
+ *                                                                                                               *
+ * Times.  Row i is at t_i = t_start + i dt, the product rounded and then the sum (no fma), i < n_times <= 65535.        *
+ *                                                                                                               *
+ * Output.  float64 (n_times, planes, n_bins + 2), lt_disk_spectrum one row (1, planes, n_bins + 2).  planes is 1, or    *
+ * max_images with split_orders: plane j then holds the hits stored in slot j, image order j.  An empty bin is exactly   *
+ * 0.0.  A row summed over all columns and planes is the emitter's bolometric light at that time.                     *
+ *                                                                                                               *
+ * Order of every sum (it depends on R, W, max_images and the grid alone, never on scheduling; no floating-point        *
+ * atomics anywhere, so a result is the same bits run after run and whatever batch of times a row is computed in).      *
+ * Key = plane (n_bins + 2) + k.  Workgroup b of LT_SPECTRUM_BLOCKS walks the chunks of 256 pixels                      *
+ * p = 256 (b + c LT_SPECTRUM_BLOCKS) + i, c ascending (the light curve's stride order).  Within a chunk, wavefront      *
+ * w = i div 64 adds, for every slot j, the weights of a key over its 64 lanes l = i mod 64 with the butterfly           *
+ * l ^ 32, l ^ 16, ... l ^ 1 (lanes without that key add +0.0, which changes no bit; so do entries of weight exactly 0).  *
+ * The owner of a key adds these sums to the workgroup's accumulator ordered by w, then j; the final stage adds a         *
+ * time's LT_SPECTRUM_BLOCKS partials per key, b ascending.                                                          *
+ * The partials live in a grow-only workspace of at most LT_SPECTRUM_WORKSPACE_BYTES: the times are launched in batches  *
+ * of max(1, LT_SPECTRUM_WORKSPACE_BYTES / (LT_SPECTRUM_BLOCKS planes (n_bins + 2) 8)).                                 *
+ *                                                                                                               *
+ * Supersampled records.  Called with the fine records (R S, W S) the result divided by S^2 is in output-pixel units,    *
+ * as the light curve's first column (image_lens.render_sequence does so).                                            *
+ *                                                                                                               *
+ * Refusals, in this order: those of the emitter's frame up to and including the disk's q / exposure (lt_shade_hotspot,  *
+ * lt_shade_diskmap; lt_disk_spectrum: null hits / metric / disk, the metric, the frame, max_images, q / exposure);       *
+ * then LT_ERR_INVALID_ARG for a null spec, the g range, n_bins, n_times, t_start / dt, and a null out.  n_times = 0 is   *
+ * LT_OK and writes nothing.  The outputs of a refused call are untouched.                                           *
+ * disk.Spectrum / disk.spectrum_bin / disk.disk_spectrum / disk.hotspot_spectrum / disk.diskmap_spectrum (Python)       *
+ * state the rule in numpy.                                                                                       *
+ *                                                                                                               *
+ * Out of scope: the thermal continuum and any rest-frame shape other than a line, polarized spectra, logarithmic        *
+ * grids, per-pixel spectra, lt_render_multi and the multi-process path, adaptive sampling.                          */
+#define LT_SPECTRUM_MAX_BINS 512
+#define LT_SPECTRUM_BLOCKS 256
+#define LT_SPECTRUM_WORKSPACE_BYTES (64 << 20)
+
+typedef struct lt_spectrum {
+    double g_min, g_max;  /* the grid's ends in g = E_obs / E_rest, 0 < g_min < g_max, finite */
+    int32_t n_bins;       /* 1 ... LT_SPECTRUM_MAX_BINS */
+    int32_t split_orders; /* nonzero: one plane per stored slot (image order) */
+} lt_spectrum;
+void lt_default_spectrum(lt_spectrum *spec); /* 0.0625 ... 1.5625, 96 bins, not split */
+
+/* The _dev forms take DEVICE pointers and enqueue on the default stream; the others HOST pointers, staged like the light
+ * curves.  out: (n_times, planes, n_bins + 2) float64. */
+int lt_disk_spectrum_dev(const float *d_hits, const uint8_t *d_n_hits, int32_t R, int32_t W, int32_t max_images,
+                         const lt_metric *metric, const lt_disk *disk, const lt_spectrum *spec, double *d_out);
+int lt_disk_spectrum(const float *hits, const uint8_t *n_hits, int32_t R, int32_t W, int32_t max_images,
+                     const lt_metric *metric, const lt_disk *disk, const lt_spectrum *spec, double *out);
+int lt_hotspot_spectrum_dev(const float *d_hits, const uint8_t *d_n_hits, int32_t R, int32_t W, int32_t max_images,
+                            const lt_metric *metric, const lt_disk *disk, const lt_hotspot *spot, const lt_spectrum *spec,
+                            double t_start, double dt, int32_t n_times, double *d_out);
+int lt_hotspot_spectrum(const float *hits, const uint8_t *n_hits, int32_t R, int32_t W, int32_t max_images,
+                        const lt_metric *metric, const lt_disk *disk, const lt_hotspot *spot, const lt_spectrum *spec,
+                        double t_start, double dt, int32_t n_times, double *out);
+int lt_diskmap_spectrum_dev(const float *d_hits, const uint8_t *d_n_hits, int32_t R, int32_t W, int32_t max_images,
+                            const lt_metric *metric, const lt_disk *disk, const lt_diskmap *map, const float *d_texels,
+                            const lt_spectrum *spec, double t_start, double dt, int32_t n_times, double *d_out);
+int lt_diskmap_spectrum(const float *hits, const uint8_t *n_hits, int32_t R, int32_t W, int32_t max_images,
+                        const lt_metric *metric, const lt_disk *disk, const lt_diskmap *map, const float *texels,
+                        const lt_spectrum *spec, double t_start, double dt, int32_t n_times, double *out);
+
 /* ---- supersampled (anti-aliased) frames, resolved on the GPU ------------------------------------------- *
  * Every frame above is one ray per pixel, taken at the pixel's corner.  These entry points trace S x S rays per       *
  * pixel and write only the resolved pixels: nothing of the S^2 times larger frame crosses PCIe or stays in memory.    *

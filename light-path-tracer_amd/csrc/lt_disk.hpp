@@ -219,11 +219,18 @@ __device__ __forceinline__ double disk_redshift(double M_, double a, double r, d
 // Light of one point of the disk, unclamped: E = I ramp(s) with I = exposure g^4 (r_in / r)^q, s = g (r_in / r)^(3/4),
 // ramp(s) = (clamp(2s, 0, 1), clamp(2s - 0.5, 0, 1), clamp(2s - 1, 0, 1)).  Evaluated in float64 from the float32 (r, g)
 // the caller gets in d_disk / d_images, so that the colour is a function of what is stored.
+// I of it alone, x = r_in / r: what a spectrum bins (lt_spectrum.hpp).
+__device__ __forceinline__ double disk_intensity(const DiskShade &ds, double x, double g)
+{
+    const double g2 = g * g;
+    return ds.exposure * (g2 * g2) * pow(x, ds.q);
+}
+
 __device__ __forceinline__ void disk_emission(const DiskShade &ds, float r32, float g32, double *e)
 {
     const double r = (double)r32, g = (double)g32;
-    const double x = ds.r_in / r, g2 = g * g;
-    const double I = ds.exposure * (g2 * g2) * pow(x, ds.q);
+    const double x = ds.r_in / r;
+    const double I = disk_intensity(ds, x, g);
     const double s = g * pow(x, 0.75);
     for (int i = 0; i < 3; ++i) e[i] = I * fmin(fmax(2.0 * s - 0.5 * i, 0.0), 1.0);
 }

@@ -28,8 +28,7 @@ struct DiskMapShade {
 // the hit's radius and at its azimuth unwound to t = 0, psi = wrap_2pi(phi - Omega (t_obs - dt)); constant extrapolation
 // over the outer half texels in r, periodic in psi; m = 0 outside [r_min, r_max] and for a NaN r (the comparisons are
 // false).  Every index is clamped before it is used, whatever the record holds.
-__device__ __forceinline__ void diskmap_emission(const DiskMapShade &dm, const float *__restrict__ texels, double t_obs, const float *rec,
-                                                 double *e)
+__device__ __forceinline__ double diskmap_intensity(const DiskMapShade &dm, const float *__restrict__ texels, double t_obs, const float *rec)
 {
     const double r = (double)rec[0], ph = (double)rec[1], g = (double)rec[2], dt = (double)rec[3];
     double m = 0.0;
@@ -53,7 +52,14 @@ __device__ __forceinline__ void diskmap_emission(const DiskMapShade &dm, const f
         m = (1.0 - f_r) * ((1.0 - f_p) * t00 + f_p * t01) + f_r * ((1.0 - f_p) * t10 + f_p * t11);
     }
     const double g2 = g * g;
-    const double I = dm.exposure * (g2 * g2) * m;
+    return dm.exposure * (g2 * g2) * m;
+}
+
+__device__ __forceinline__ void diskmap_emission(const DiskMapShade &dm, const float *__restrict__ texels, double t_obs, const float *rec,
+                                                 double *e)
+{
+    const double g = (double)rec[2];
+    const double I = diskmap_intensity(dm, texels, t_obs, rec); // exposure g^4 m, what a spectrum bins (lt_spectrum.hpp)
     for (int i = 0; i < 3; ++i) e[i] = I * fmin(fmax(2.0 * g - 0.5 * i, 0.0), 1.0);
 }
 

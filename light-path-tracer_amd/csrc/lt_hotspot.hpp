@@ -16,13 +16,19 @@ struct HotspotShade {
 
 // Light of the spot seen through one stored hit, unclamped: E = exposure g^4 w ramp(g), w = exp(-d^2 / 2 sigma^2) with d the
 // distance in the disk's plane between the hit and the spot at the time the light left, t_obs - dt.
-__device__ __forceinline__ void hotspot_emission(const HotspotShade &hs, double t_obs, const float *rec, double *e)
+__device__ __forceinline__ double hotspot_intensity(const HotspotShade &hs, double t_obs, const float *rec)
 {
     const double r = (double)rec[0], ph = (double)rec[1], g = (double)rec[2], dt = (double)rec[3];
     const double phi_s = hs.phi0 + hs.omega * (t_obs - dt);
     const double d2 = r * r + hs.r_spot * hs.r_spot - 2.0 * r * hs.r_spot * cos(ph - phi_s);
     const double g2 = g * g;
-    const double I = hs.exposure * (g2 * g2) * exp(-d2 * hs.inv_2s2);
+    return hs.exposure * (g2 * g2) * exp(-d2 * hs.inv_2s2);
+}
+
+__device__ __forceinline__ void hotspot_emission(const HotspotShade &hs, double t_obs, const float *rec, double *e)
+{
+    const double g = (double)rec[2];
+    const double I = hotspot_intensity(hs, t_obs, rec); // exposure g^4 w, what a spectrum bins (lt_spectrum.hpp)
     for (int i = 0; i < 3; ++i) e[i] = I * fmin(fmax(2.0 * g - 0.5 * i, 0.0), 1.0);
 }
 

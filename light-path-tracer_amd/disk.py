@@ -16,6 +16,9 @@ lt_trace_disk_hits stores the light-travel time of every hit as well (step_time 
 that a moving source -- HotSpot, a bright spot on a circular orbit -- can be re-shaded at any observer time from one
 trace (shade_hotspot) and reduced to a light curve (lightcurve).  DiskMap is the general moving source: an emissivity
 table on the disk that turns with it (shade_diskmap, diskmap_lightcurve; spiral_map and spots_map make tables).
+
+The same records binned by g give the energy-resolved light: Spectrum is the grid, spectrum_bin the bin rule, and
+disk_spectrum / hotspot_spectrum / diskmap_spectrum the broadened line and the dynamic spectra (lt_*_spectrum).
 """
 from dataclasses import dataclass
 from typing import Optional
@@ -188,11 +191,8 @@ def _stored(hits, n_hits):
 def spot_emission(M, a, hits, spot, t_obs):
     """E_spot (..., max_images, 3) float64 of every slot of `hits` (..., max_images, 4) float32 (r, phi, g, dt), unclamped:
     exposure g^4 exp(-d^2 / 2 sigma^2) ramp(g), d the distance in the plane to the spot at t_obs - dt."""
-    h = np.asarray(hits).astype(np.float64)
-    r, ph, g, dt = h[..., 0], h[..., 1], h[..., 2], h[..., 3]
-    phi_s = spot.phi0 + omega(M, a, spot.r_spot) * (t_obs - dt)
-    d2 = r * r + spot.r_spot * spot.r_spot - 2.0 * r * spot.r_spot * np.cos(ph - phi_s)
-    inten = spot.exposure * (g * g) ** 2 * np.exp(-d2 * (1.0 / (2.0 * spot.sigma * spot.sigma)))
+    g = np.asarray(hits).astype(np.float64)[..., 2]
+    inten = spot_intensity(M, a, hits, spot, t_obs)
     return np.stack([inten * np.clip(2.0 * g - 0.5 * i, 0.0, 1.0) for i in range(3)], axis=-1)
 
 
@@ -318,12 +318,8 @@ def map_emission(M, a, hits, dmap, t_obs):
     """E_map (..., max_images, 3) float64 of every slot of `hits` (..., max_images, 4) float32 (r, phi, g, dt), unclamped:
     exposure g^4 m ramp(g), m the table at the hit's radius and at psi = wrap_2pi(phi - Omega (t_obs - dt)), Omega the
     disk's own rate at the hit's r ("kepler") or omega_p ("rigid")."""
-    h = np.asarray(hits).astype(np.float64)
-    r, ph, g, dt = h[..., 0], h[..., 1], h[..., 2], h[..., 3]
-    with np.errstate(invalid="ignore"):
-        om = dmap.omega_p if dmap.rotation == "rigid" else omega(M, a, r)
-        m = sample_map(dmap, r, wrap_2pi(ph - om * (t_obs - dt)))
-    inten = dmap.exposure * (g * g) ** 2 * m
+    g = np.asarray(hits).astype(np.float64)[..., 2]
+    inten = map_intensity(M, a, hits, dmap, t_obs)
     return np.stack([inten * np.clip(2.0 * g - 0.5 * i, 0.0, 1.0) for i in range(3)], axis=-1)
 
 
@@ -407,6 +403,113 @@ def spots_map(n_r, n_phi, r_min, r_max, spots):
         amp = float(sp[3]) if len(sp) > 3 else 1.0
         out += amp * np.exp(-(r * r + r_s * r_s - 2.0 * r * r_s * np.cos(ph - phi_s)) / (2.0 * sigma * sigma))
     return out.astype(np.float32)
+
+
+# ---- energy-resolved light (lt_disk_spectrum, lt_hotspot_spectrum, lt_diskmap_spectrum) -----------------------------------
+SPECTRUM_MAX_BINS = 512
+
+
+@dataclass
+class Spectrum:
+    """A linear grid in g = E_obs / E_rest (include/ltrace.h, "energy-resolved light"): n_bins half-open bins on
+    [g_min, g_max), an underflow column before them and an overflow column after.  split_orders: one plane per stored
+    slot (image order) instead of one for all."""
+    g_min: float = 0.0625
+    g_max: float = 1.5625
+    n_bins: int = 96
+    split_orders: bool = False
+
+    def __post_init__(self):
+        if not (0.0 < self.g_min < self.g_max and np.isfinite(self.g_max)):
+            raise ValueError("Spectrum needs 0 < g_min < g_max, both finite")
+        if int(self.n_bins) != self.n_bins or not 1 <= self.n_bins <= SPECTRUM_MAX_BINS:
+            raise ValueError(f"Spectrum n_bins must be 1 ... {SPECTRUM_MAX_BINS}")
+        self.g_min, self.g_max, self.n_bins, self.split_orders = float(self.g_min), float(self.g_max), int(self.n_bins), bool(self.split_orders)
+
+    def to_lt(self):
+        """The lt_spectrum struct of this grid (ltrace.Spectrum)."""
+        import ltrace
+        return ltrace.default_spectrum(g_min=self.g_min, g_max=self.g_max, n_bins=self.n_bins, split_orders=int(self.split_orders))
+
+    def planes(self, max_images):
+        return int(max_images) if self.split_orders else 1
+
+    def edges(self):
+        """The n_bins + 1 edges of the bins proper, g_min ... g_max (columns 1 ... n_bins of a spectrum)."""
+        e = self.g_min + (self.g_max - self.g_min) * np.arange(self.n_bins + 1) / self.n_bins
+        e[-1] = self.g_max
+        return e
+
+    def energies(self, E_rest):
+        """The bins' central photon energies for a line at E_rest, (n_bins,)."""
+        e = self.edges()
+        return 0.5 * (e[:-1] + e[1:]) * float(E_rest)
+
+
+def spectrum_bin(g, spec):
+    """The header's bin rule, vectorised: the column (int64) of every g, float32 as stored, evaluated in float64;
+    0 the underflow, n_bins + 1 the overflow, -1 for a NaN (skipped)."""
+    x = np.asarray(g, dtype=np.float32).astype(np.float64)
+    inv_dg = spec.n_bins / (spec.g_max - spec.g_min)
+    nan = np.isnan(x)
+    with np.errstate(invalid="ignore", over="ignore"):
+        inner = np.floor((np.where(nan | np.isinf(x), spec.g_min, x) - spec.g_min) * inv_dg)
+    k = 1 + np.minimum(np.clip(inner, 0, spec.n_bins).astype(np.int64), spec.n_bins - 1)
+    k = np.where(x < spec.g_min, 0, np.where(x >= spec.g_max, spec.n_bins + 1, k))
+    return np.where(nan, -1, k)
+
+
+def _bin_weights(hits, n_hits, spec, weights):
+    """One row (planes, n_bins + 2) float64: weights (R, W, max_images) of the stored slots of hits binned by their g."""
+    hits = np.asarray(hits)
+    m = hits.shape[-2]
+    k = spectrum_bin(hits[..., 2], spec)
+    on = (_stored(hits, n_hits)[..., None] > np.arange(m)) & (k >= 0)
+    cols = spec.n_bins + 2
+    plane = np.broadcast_to(np.arange(m), k.shape) if spec.split_orders else np.zeros(k.shape, dtype=np.int64)
+    key = (plane * cols + k)[on]
+    return np.bincount(key, weights=np.asarray(weights, dtype=np.float64)[on], minlength=spec.planes(m) * cols).reshape(spec.planes(m), cols)
+
+
+def spot_intensity(M, a, hits, spot, t_obs):
+    """exposure g^4 exp(-d^2 / 2 sigma^2) of every slot, (..., max_images) float64: spot_emission without the ramp."""
+    h = np.asarray(hits).astype(np.float64)
+    r, ph, g, dt = h[..., 0], h[..., 1], h[..., 2], h[..., 3]
+    phi_s = spot.phi0 + omega(M, a, spot.r_spot) * (t_obs - dt)
+    d2 = r * r + spot.r_spot * spot.r_spot - 2.0 * r * spot.r_spot * np.cos(ph - phi_s)
+    return spot.exposure * (g * g) ** 2 * np.exp(-d2 * (1.0 / (2.0 * spot.sigma * spot.sigma)))
+
+
+def map_intensity(M, a, hits, dmap, t_obs):
+    """exposure g^4 m of every slot, (..., max_images) float64: map_emission without the ramp."""
+    h = np.asarray(hits).astype(np.float64)
+    r, ph, g, dt = h[..., 0], h[..., 1], h[..., 2], h[..., 3]
+    with np.errstate(invalid="ignore"):
+        om = dmap.omega_p if dmap.rotation == "rigid" else omega(M, a, r)
+        m = sample_map(dmap, r, wrap_2pi(ph - om * (t_obs - dt)))
+    return dmap.exposure * (g * g) ** 2 * m
+
+
+def disk_spectrum(M, a, hits, n_hits, disk, spec):
+    """lt_disk_spectrum restated: the stationary disk's line profile, (planes, n_bins + 2) float64 -- per stored slot
+    disk.exposure g^4 (r_in / r)^q added to the column of its g (spectrum_bin); column 0 the underflow, the last the
+    overflow; plane j the image order j with spec.split_orders."""
+    h = np.asarray(hits).astype(np.float64)
+    with np.errstate(invalid="ignore"):
+        w = disk.exposure * (h[..., 2] * h[..., 2]) ** 2 * (disk.inner_edge(M, a) / h[..., 0]) ** disk.q
+    return _bin_weights(hits, n_hits, spec, w)
+
+
+def hotspot_spectrum(M, a, hits, n_hits, spot, spec, times):
+    """lt_hotspot_spectrum restated: the spot's dynamic spectrum, (len(times), planes, n_bins + 2) float64; every image
+    order is binned at its own emission time t - dt."""
+    with np.errstate(invalid="ignore"):
+        return np.stack([_bin_weights(hits, n_hits, spec, spot_intensity(M, a, hits, spot, float(t))) for t in times])
+
+
+def diskmap_spectrum(M, a, hits, n_hits, dmap, spec, times):
+    """lt_diskmap_spectrum restated: the map's dynamic spectrum, (len(times), planes, n_bins + 2) float64."""
+    return np.stack([_bin_weights(hits, n_hits, spec, map_intensity(M, a, hits, dmap, float(t))) for t in times])
 
 
 # ---- linear polarization (lt_trace_disk_pol, lt_shade_stokes, lt_hotspot_lightcurve_stokes) ------------------------

@@ -303,7 +303,7 @@ def render_frame(source_image, metric, r_obs, fov, psi=(0.0, 0.0), theta_obs=np.
 
 
 def render_sequence(source_image, metric, r_obs, fov, disk, hotspot, times, shape=None, psi=(0.0, 0.0), theta_obs=np.pi / 2,
-                    integrator=None, precision=None, bfield=None, samples=None, diskmap=None):
+                    integrator=None, precision=None, bfield=None, samples=None, diskmap=None, spectrum=None):
     """A moving picture from ONE trace: an optically thin disk (disk.TransparentDisk) with a hot spot (disk.HotSpot) on a
     circular orbit, at the observer times `times`.  The rays are traced once with the light-travel time of every hit
     (lt_trace_disk_hits); each frame is a re-shade of the stored hits (lt_shade_hotspot) over `base`, the lensed
@@ -325,6 +325,10 @@ def render_sequence(source_image, metric, r_obs, fov, disk, hotspot, times, shap
     `hotspot` is then None.  Frames come from lt_shade_diskmap (samples: lt_shade_diskmap_aa) and the light curve from
     lt_diskmap_lightcurve, scaled as above; everything else is as with a spot.  A map together with a spot or with a
     field is refused: both are out of scope.
+    spectrum (disk.Spectrum): the result gains `spectrum` (n, planes, n_bins + 2) float64, the moving emitter's dynamic
+    spectrum over the grid in g (lt_hotspot_spectrum, or lt_diskmap_spectrum with a map), and `disk_spectrum`
+    (planes, n_bins + 2), the stationary disk's line profile (lt_disk_spectrum); planes is 1, or max_images with
+    spectrum.split_orders.  With `samples` both are the fine records' divided by S^2, as the light curve's first column.
     One GPU, every row traced; sequences are not adaptively sampled."""
     if diskmap is not None and hotspot is not None:
         raise ValueError("render_sequence: a disk map together with a hot spot is out of scope; pass hotspot=None")
@@ -366,7 +370,7 @@ def render_sequence(source_image, metric, r_obs, fov, disk, hotspot, times, shap
     else:
         traced = ltrace.trace_disk_hits(cam, met, opts, d, max_images=m, want=("hits", "n_hits"))
     if diskmap is not None:
-        return _sequence_diskmap(traced, met, d, diskmap, times, dt, base, S)
+        return _sequence_diskmap(traced, met, d, diskmap, times, dt, base, S, spectrum)
     frames, rgba = [], []
     for t in times:
         if S is None:
@@ -389,12 +393,23 @@ def render_sequence(source_image, metric, r_obs, fov, disk, hotspot, times, shap
             stokes = [ltrace.shade_stokes_aa(*rec[:3], S, *rec[3:], float(t)) for t in times]
             slc = slc / np.float64(S * S)
         out.update(pol=traced["pol"], stokes=np.stack(stokes), stokes_lightcurve=slc)
+    if spectrum is not None:
+        sp = spectrum.to_lt()
+        dyn = ltrace.hotspot_spectrum(traced["hits"], traced["n_hits"], met, d, spot, sp, float(times[0]), dt, times.size)
+        _sequence_spectra(out, traced, met, d, sp, dyn, S)
     if S is not None:
         out["samples"] = S
     return out
 
 
-def _sequence_diskmap(traced, met, d, diskmap, times, dt, base, S):
+def _sequence_spectra(out, traced, met, d, sp, dyn, S):
+    """render_sequence's `spectrum` (the moving emitter's, dyn) and `disk_spectrum`, in output-pixel units."""
+    line = ltrace.disk_spectrum(traced["hits"], traced["n_hits"], met, d, sp)
+    scale = np.float64(1 if S is None else S * S)
+    out.update(spectrum=dyn / scale, disk_spectrum=line / scale)
+
+
+def _sequence_diskmap(traced, met, d, diskmap, times, dt, base, S, spectrum=None):
     """render_sequence's frames and light curve for a disk map, from the traced records."""
     dm, tex = diskmap.to_lt(), diskmap.texels
     frames, rgba = [], []
@@ -410,9 +425,27 @@ def _sequence_diskmap(traced, met, d, diskmap, times, dt, base, S):
         lc = lc / np.array([S * S, S ** 3, S ** 3], dtype=np.float64)
     out = dict(frames=np.stack(frames), rgba=np.stack(rgba), lightcurve=lc, hits=traced["hits"], n_hits=traced["n_hits"],
                stats=traced["stats"])
+    if spectrum is not None:
+        sp = spectrum.to_lt()
+        dyn = ltrace.diskmap_spectrum(traced["hits"], traced["n_hits"], met, d, dm, tex, sp, float(times[0]), dt, times.size)
+        _sequence_spectra(out, traced, met, d, sp, dyn, S)
     if S is not None:
         out["samples"] = S
     return out
+
+
+def spectrum_from_args(args):
+    """The disk.Spectrum of --spectrum G_MIN G_MAX N_BINS [--spectrum-orders], or None; refused without a sequence."""
+    from disk import Spectrum
+    if args.spectrum is None:
+        if args.spectrum_orders:
+            raise ValueError("--spectrum-orders needs --spectrum G_MIN G_MAX N_BINS")
+        return None
+    if args.hotspot is None and args.bfield is None and args.disk_map is None:
+        raise ValueError("--spectrum bins the stored hits of a sequence; use it with --hotspot or --disk-map (and --disk-images N)")
+    if args.spectrum[2] != int(args.spectrum[2]):
+        raise ValueError("--spectrum: N_BINS must be a whole number")
+    return Spectrum(args.spectrum[0], args.spectrum[1], int(args.spectrum[2]), split_orders=args.spectrum_orders)
 
 
 def diskmap_from_args(args, disk, M, a):
@@ -433,8 +466,11 @@ def main_sequence(args, disk):
     that turns with the disk, in the spot's place.
     --samples S: the sequence supersampled, S x S rays per pixel traced once and every frame resolved on the GPU.
     --bfield BR BPHI BZ [--pol-frac P]: also the Stokes frames (I, Q, U) as numbered .npy and the Stokes light curve;
-    without --hotspot the spot is dark and the frames show the disk alone."""
+    without --hotspot the spot is dark and the frames show the disk alone.
+    --spectrum G_MIN G_MAX N_BINS [--spectrum-orders]: also the moving emitter's dynamic spectrum, the disk's line profile
+    and the grid's edges as .npy."""
     from disk import BField, HotSpot
+    spec = spectrum_from_args(args)
     if args.disk_map is not None and args.hotspot is not None:
         raise ValueError("--disk-map: a map together with --hotspot is out of scope; use one of them")
     if args.disk_map is not None and args.bfield is not None:
@@ -460,7 +496,7 @@ def main_sequence(args, disk):
     field = BField(*args.bfield, pol_frac=args.pol_frac) if args.bfield is not None else None
     out = render_sequence(None, metric, args.r_obs * metric.M, fov, disk, spot, t0 + dt * np.arange(n), shape=(height, width),
                           psi=(np.radians(args.psi_y), np.radians(args.psi_x)), theta_obs=np.radians(args.theta_obs), bfield=field,
-                          samples=args.samples, diskmap=dmap)
+                          samples=args.samples, diskmap=dmap, spectrum=spec)
     stem = args.output[:-4] if args.output.lower().endswith(".png") else args.output
     for i in range(n):
         write_png_rgba8(f"{stem}_{i:04d}.png", out["rgba"][i])
@@ -470,6 +506,12 @@ def main_sequence(args, disk):
             np.save(f"{stem}_stokes_{i:04d}.npy", out["stokes"][i])
         np.save(stem + "_stokes_lightcurve.npy", out["stokes_lightcurve"])
         print(f"Polarization: Stokes frames -> {stem}_stokes_0000.npy ..., Stokes light curve -> {stem}_stokes_lightcurve.npy")
+    if spec is not None:
+        np.save(stem + "_spectrum.npy", out["spectrum"])
+        np.save(stem + "_line.npy", out["disk_spectrum"])
+        np.save(stem + "_spectrum_edges.npy", spec.edges())
+        print(f"Spectrum: {spec.n_bins} bins of g in [{spec.g_min:g}, {spec.g_max:g}) -> {stem}_spectrum.npy (dynamic), {stem}_line.npy (the disk's "
+              f"line), {stem}_spectrum_edges.npy")
     if args.samples is not None:
         print(f"Supersampling: {args.samples} x {args.samples} rays per pixel, every frame resolved on the GPU")
     print(f"{'Hot spot' if dmap is None else 'Disk map'}: one trace ({out['stats']['integrate_ms']:.2f} ms), {n} frames -> {stem}_0000.png ..., light curve -> "
@@ -752,6 +794,10 @@ def build_parser():
                     help="--disk-map: every radius turns at the disk's own rate (kepler, the pattern shears) or all at --disk-map-omega")
     ap.add_argument("--disk-map-omega", type=float, default=0.0, metavar="W", help="--disk-map-rotation rigid: the pattern speed (1 / M)")
     ap.add_argument("--disk-map-exposure", type=float, default=1.0, metavar="X", help="--disk-map: brightness scale of the map (default: 1)")
+    ap.add_argument("--spectrum", type=float, nargs=3, default=None, metavar=("G_MIN", "G_MAX", "N_BINS"),
+                    help="with --hotspot / --disk-map: bin the stored hits by g = E_obs / E_rest on a linear grid of N_BINS (1 ... 512) bins; "
+                         "writes the dynamic spectrum, the disk's line profile and the bin edges as .npy")
+    ap.add_argument("--spectrum-orders", action="store_true", help="--spectrum: one plane per image order instead of one for all")
     return ap
 
 
@@ -765,6 +811,7 @@ if __name__ == "__main__":
     elif args.disk:
         from disk import ThinDisk
         disk = ThinDisk(r_in=args.disk_rin, r_out=args.disk_rout, q=args.disk_q, exposure=args.disk_exposure)
+    spectrum_from_args(args)                                  # (refuses --spectrum without a sequence)
     if args.hotspot is not None or args.bfield is not None or args.disk_map is not None:
         main_sequence(args, disk)
         sys.exit(0)

@@ -89,6 +89,14 @@ class DiskMap(C.Structure):
 MAP_KEPLERIAN, MAP_RIGID = 0, 1
 
 
+class Spectrum(C.Structure):
+    """lt_spectrum: a linear grid in g = E_obs / E_rest (n_bins bins, an underflow and an overflow column)."""
+    _fields_ = [("g_min", C.c_double), ("g_max", C.c_double), ("n_bins", C.c_int32), ("split_orders", C.c_int32)]
+
+
+SPECTRUM_MAX_BINS, SPECTRUM_BLOCKS, SPECTRUM_WORKSPACE_BYTES = 512, 256, 64 << 20
+
+
 class BField(C.Structure):
     """lt_bfield: the field's components in the emitter's frame and the polarization fraction."""
     _fields_ = [("b_r", C.c_double), ("b_phi", C.c_double), ("b_z", C.c_double), ("pol_frac", C.c_double)]
@@ -246,6 +254,21 @@ SIGNATURES = {
                                      C.POINTER(Metric), C.POINTER(Disk), C.POINTER(HotSpot), C.POINTER(BField), C.c_double,
                                      C.c_void_p]),
     "lt_default_diskmap": (None, [C.POINTER(DiskMap)]),
+    "lt_default_spectrum": (None, [C.POINTER(Spectrum)]),
+    "lt_disk_spectrum_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Metric), C.POINTER(Disk),
+                                    C.POINTER(Spectrum), C.c_void_p]),
+    "lt_hotspot_spectrum_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Metric), C.POINTER(Disk),
+                                       C.POINTER(HotSpot), C.POINTER(Spectrum), C.c_double, C.c_double, C.c_int32, C.c_void_p]),
+    "lt_diskmap_spectrum_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Metric), C.POINTER(Disk),
+                                       C.POINTER(DiskMap), C.c_void_p, C.POINTER(Spectrum), C.c_double, C.c_double, C.c_int32,
+                                       C.c_void_p]),
+    "lt_disk_spectrum": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Metric), C.POINTER(Disk),
+                                    C.POINTER(Spectrum), C.c_void_p]),
+    "lt_hotspot_spectrum": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Metric), C.POINTER(Disk),
+                                       C.POINTER(HotSpot), C.POINTER(Spectrum), C.c_double, C.c_double, C.c_int32, C.c_void_p]),
+    "lt_diskmap_spectrum": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Metric), C.POINTER(Disk),
+                                       C.POINTER(DiskMap), C.c_void_p, C.POINTER(Spectrum), C.c_double, C.c_double, C.c_int32,
+                                       C.c_void_p]),
     "lt_shade_diskmap_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Metric),
                                        C.POINTER(Disk), C.POINTER(DiskMap), C.c_void_p, C.c_double, C.c_void_p, C.c_int32,
                                        C.c_void_p, C.c_void_p]),
@@ -1203,6 +1226,83 @@ def diskmap_lightcurve_dev(d_hits, d_n_hits, rows, width, max_images, metric, di
     """Device-pointer form of diskmap_lightcurve (lt_diskmap_lightcurve_dev); enqueues on the default stream."""
     _check(load().lt_diskmap_lightcurve_dev(_p(d_hits), _p(d_n_hits), rows, width, max_images, C.byref(metric), C.byref(disk),
                                             C.byref(dmap), _p(d_texels), float(t_start), float(dt), int(n_times), _p(d_out)))
+
+
+# ---- energy-resolved light (lt_disk_spectrum, lt_hotspot_spectrum, lt_diskmap_spectrum) ---------------------------------
+def default_spectrum(**kw):
+    """lt_spectrum with the library's defaults (g 0.0625 ... 1.5625, 96 bins, not split); keywords override."""
+    s = Spectrum()
+    load().lt_default_spectrum(C.byref(s))
+    for k, v in kw.items():
+        setattr(s, k, v)
+    return s
+
+
+def spectrum_planes(spec, max_images):
+    """Planes of a spectrum's output: 1, or max_images with split_orders."""
+    return int(max_images) if spec.split_orders else 1
+
+
+def spectrum_batch_times(spec, max_images):
+    """Times one launch of a spectrum's first stage holds: its partials, SPECTRUM_BLOCKS histograms of float64 per time,
+    stay within SPECTRUM_WORKSPACE_BYTES (at least one time); longer sequences run in batches of this many."""
+    return max(1, SPECTRUM_WORKSPACE_BYTES // (SPECTRUM_BLOCKS * spectrum_planes(spec, max_images) * (int(spec.n_bins) + 2) * 8))
+
+
+def _spectrum_out(spec, max_images, n_times):
+    """The output of a spectrum call; sized by the header's limits so that a grid the library will refuse allocates little."""
+    bins = min(max(int(spec.n_bins), 0), SPECTRUM_MAX_BINS)
+    return np.empty((max(int(n_times), 0), spectrum_planes(spec, min(max(int(max_images), 0), 8)), bins + 2))
+
+
+def disk_spectrum(hits, n_hits, metric, disk, spec):
+    """The stationary disk's line profile from stored hits (lt_disk_spectrum) -> (planes, n_bins + 2) float64: column 0
+    the underflow, the last the overflow; plane j the image order j with spec.split_orders."""
+    hits, nh = _hit_arrays(hits, n_hits)
+    R, W, m = hits.shape[:3]
+    out = _spectrum_out(spec, m, 1)
+    _check(load().lt_disk_spectrum(_np_ptr(hits), _np_ptr(nh), R, W, m, C.byref(metric), C.byref(disk), C.byref(spec), _np_ptr(out)))
+    return out[0]
+
+
+def disk_spectrum_dev(d_hits, d_n_hits, rows, width, max_images, metric, disk, spec, d_out):
+    """Device-pointer form of disk_spectrum (lt_disk_spectrum_dev); enqueues on the default stream."""
+    _check(load().lt_disk_spectrum_dev(_p(d_hits), _p(d_n_hits), rows, width, max_images, C.byref(metric), C.byref(disk),
+                                       C.byref(spec), _p(d_out)))
+
+
+def hotspot_spectrum(hits, n_hits, metric, disk, spot, spec, t_start, dt, n_times):
+    """The spot's dynamic spectrum (lt_hotspot_spectrum) -> (n_times, planes, n_bins + 2) float64 at t_start + i dt."""
+    hits, nh = _hit_arrays(hits, n_hits)
+    R, W, m = hits.shape[:3]
+    out = _spectrum_out(spec, m, n_times)
+    _check(load().lt_hotspot_spectrum(_np_ptr(hits), _np_ptr(nh), R, W, m, C.byref(metric), C.byref(disk), C.byref(spot),
+                                      C.byref(spec), float(t_start), float(dt), int(n_times), _np_ptr(out)))
+    return out
+
+
+def hotspot_spectrum_dev(d_hits, d_n_hits, rows, width, max_images, metric, disk, spot, spec, t_start, dt, n_times, d_out):
+    """Device-pointer form of hotspot_spectrum (lt_hotspot_spectrum_dev); enqueues on the default stream."""
+    _check(load().lt_hotspot_spectrum_dev(_p(d_hits), _p(d_n_hits), rows, width, max_images, C.byref(metric), C.byref(disk),
+                                          C.byref(spot), C.byref(spec), float(t_start), float(dt), int(n_times), _p(d_out)))
+
+
+def diskmap_spectrum(hits, n_hits, metric, disk, dmap, texels, spec, t_start, dt, n_times):
+    """The map's dynamic spectrum (lt_diskmap_spectrum) -> (n_times, planes, n_bins + 2) float64 at t_start + i dt."""
+    hits, nh = _hit_arrays(hits, n_hits)
+    tex = _texel_array(dmap, texels)
+    R, W, m = hits.shape[:3]
+    out = _spectrum_out(spec, m, n_times)
+    _check(load().lt_diskmap_spectrum(_np_ptr(hits), _np_ptr(nh), R, W, m, C.byref(metric), C.byref(disk), C.byref(dmap),
+                                      _np_ptr(tex), C.byref(spec), float(t_start), float(dt), int(n_times), _np_ptr(out)))
+    return out
+
+
+def diskmap_spectrum_dev(d_hits, d_n_hits, rows, width, max_images, metric, disk, dmap, d_texels, spec, t_start, dt, n_times, d_out):
+    """Device-pointer form of diskmap_spectrum (lt_diskmap_spectrum_dev); enqueues on the default stream."""
+    _check(load().lt_diskmap_spectrum_dev(_p(d_hits), _p(d_n_hits), rows, width, max_images, C.byref(metric), C.byref(disk),
+                                          C.byref(dmap), _p(d_texels), C.byref(spec), float(t_start), float(dt), int(n_times),
+                                          _p(d_out)))
 
 
 # ---- supersampled frames (lt_render_aa) ---------------------------------------------------------------------------
