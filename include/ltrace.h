@@ -818,6 +818,89 @@ int lt_diskmap_spectrum(const float *hits, const uint8_t *n_hits, int32_t R, int
                         const lt_metric *metric, const lt_disk *disk, const lt_diskmap *map, const float *texels,
                         const lt_spectrum *spec, double t_start, double dt, int32_t n_times, double *out);
 
+/* ---- visibilities: what an interferometer measures, from the stored hits ------------------------------------ *
+ * Every product above lives in the image plane or is a total flux.  An interferometer samples the image's Fourier     *
+ * transform on a set of baselines; the photon ring's thin arcs carry almost no flux and dominate the long ones.       *
+ * These entry points give the complex visibility of one emitter's light per observer time, image order and baseline:  *
+ * a fifth reduction over the records of lt_trace_disk_hits; nothing is traced again.                               *
+ *                                                                                                               *
+ * The rule.  For a record buffer of R x W pixels (pixel p has ix = p % W, iy = p / W), a baseline b = (u_b, v_b) in     *
+ * CYCLES PER PIXEL OF THAT BUFFER and an observer time t,                                                          *
+ *     V[t, plane, b] = sum over pixels p and stored slots j of the plane:  w(rec_pj, t) exp(-2 pi i (u_b ix + v_b iy))  *
+ * Weight.  w is exactly what a spectrum bins ("energy-resolved light": the disk's, the spot's or the map's unclamped   *
+ * exposure g^4 emitter, no colour ramp; with_disk is not looked at).  The stored slots are the re-shades'; a stored    *
+ * slot whose g is NaN is skipped.                                                                                  *
+ * Planes.  1, or max_images with split_orders != 0: plane j then holds the hits stored in slot j, image order j.       *
+ * Without split_orders a pixel's slots are added first, in their order, and the sum takes the pixel's phase.           *
+ * Phase, in float64 and in exactly this form:                                                                      *
+ *     x = u ix + v iy        both products rounded, then the sum (no fma)                                             *
+ *     f = x - rint(x)        exact; |f| <= 1/2                                                                        *
+ *     (s, c) = sincospi(2 f)                                                                                        *
+ * and the term is (w c, -w s), each component added to its sum with one fused multiply-add.  The reduced argument      *
+ * makes the phases at quarter cycles exact (c, s in {0, 1, -1}) and keeps the phase's error, 2 pi (W + H) 2^-53 from   *
+ * the roundings of x plus sincospi's own, independent of anything else.  The origin of the phase is pixel (0, 0).     *
+ * Limits.  |u|, |v| <= 0.5, the Nyquist limit of the buffer, both finite; 1 <= n_baselines <=                          *
+ * LT_VISIBILITY_MAX_BASELINES.  Times as the spectrum's: row i at t_start + i dt (product rounded, then the sum),      *
+ * i < n_times <= 65535.                                                                                            *
+ *                                                                                                               *
+ * Output.  float64 (n_times, planes, n_baselines, 2) holding (re, im); lt_disk_visibility one row (1, planes,         *
+ * n_baselines, 2) and no time.  A plane without light is exactly 0 + 0i.  V at (0, 0) is the plane's total flux.       *
+ *                                                                                                               *
+ * Order of every sum (it depends on R, W, max_images and the records alone; no floating-point atomics anywhere, so a   *
+ * result is the same bits run after run, whatever batch of times it is computed in and whatever other baselines are    *
+ * asked for with it).  Workgroup k of LT_VISIBILITY_BLOCKS walks the chunks of 256 pixels p = 256 (k + c               *
+ * LT_VISIBILITY_BLOCKS) + i, c ascending (the light curve's stride order), and adds to its sum, which starts at 0,    *
+ * the terms of the chunk's pixels in ascending i; a pixel whose weights are exactly 0 at every time and plane of its   *
+ * batch is left out, which changes no bit.  The final stage adds the LT_VISIBILITY_BLOCKS partial sums, k ascending.    *
+ * A workgroup keeps the sums of a batch of times in registers: max(1, LT_VISIBILITY_BATCH_TERMS / planes) times        *
+ * (lt_visibility_batch_times).  The partials live in a grow-only workspace of at most LT_VISIBILITY_WORKSPACE_BYTES     *
+ * (plus the baselines' 16 KiB): a call's batches go in as few launches as that allows.                                *
+ *                                                                                                               *
+ * Supersampled records.  Called with the fine records (R S, W S) and the baselines (u / S, v / S), u, v in cycles per  *
+ * output pixel, the result divided by S^2 is in output-pixel units; image_lens.render_sequence does so and moves the    *
+ * phase's origin to the centre of the output frame (disk.Baselines.recentre).                                        *
+ *                                                                                                               *
+ * Refusals, in this order: those of the emitter's frame up to and including the disk's q / exposure, as the spectrum's; *
+ * then LT_ERR_INVALID_ARG for a null uv, n_baselines, a baseline out of range or not finite, n_times, t_start / dt,     *
+ * and a null out.  n_times = 0 is LT_OK and writes nothing, even with a null out.  The outputs of a refused call are   *
+ * untouched.  disk.Baselines / disk.visibility_phase / disk.disk_visibility / disk.hotspot_visibility /              *
+ * disk.diskmap_visibility (Python) state the rule in numpy.                                                        *
+ *                                                                                                               *
+ * Out of scope: polarized visibilities, closure quantities (products of these numbers), baselines beyond Nyquist,      *
+ * noise and the (u, v) tracks of real arrays, lt_render_multi and the multi-process path, adaptive sampling.          */
+#define LT_VISIBILITY_MAX_BASELINES 1024
+#define LT_VISIBILITY_BLOCKS 256
+#define LT_VISIBILITY_BATCH_TERMS 16 /* times x planes a workgroup accumulates at once, per owned baseline */
+#define LT_VISIBILITY_WORKSPACE_BYTES (64 << 20)
+
+/* Times of one batch: max(1, LT_VISIBILITY_BATCH_TERMS / planes).  Needs no device. */
+int32_t lt_visibility_batch_times(int32_t max_images, int32_t split_orders);
+
+/* The _dev forms take DEVICE pointers for the records, the texels and the output and enqueue on the default stream; the
+ * others HOST pointers, staged like the spectra.  uv is a HOST pointer in both: n_baselines pairs (u, v) of float64,
+ * checked on the host and uploaded with the call.  out: (n_times, planes, n_baselines, 2) float64. */
+int lt_disk_visibility_dev(const float *d_hits, const uint8_t *d_n_hits, int32_t R, int32_t W, int32_t max_images,
+                           const lt_metric *metric, const lt_disk *disk, const double *uv, int32_t n_baselines,
+                           int32_t split_orders, double *d_out);
+int lt_disk_visibility(const float *hits, const uint8_t *n_hits, int32_t R, int32_t W, int32_t max_images,
+                       const lt_metric *metric, const lt_disk *disk, const double *uv, int32_t n_baselines,
+                       int32_t split_orders, double *out);
+int lt_hotspot_visibility_dev(const float *d_hits, const uint8_t *d_n_hits, int32_t R, int32_t W, int32_t max_images,
+                              const lt_metric *metric, const lt_disk *disk, const lt_hotspot *spot, const double *uv,
+                              int32_t n_baselines, int32_t split_orders, double t_start, double dt, int32_t n_times,
+                              double *d_out);
+int lt_hotspot_visibility(const float *hits, const uint8_t *n_hits, int32_t R, int32_t W, int32_t max_images,
+                          const lt_metric *metric, const lt_disk *disk, const lt_hotspot *spot, const double *uv,
+                          int32_t n_baselines, int32_t split_orders, double t_start, double dt, int32_t n_times, double *out);
+int lt_diskmap_visibility_dev(const float *d_hits, const uint8_t *d_n_hits, int32_t R, int32_t W, int32_t max_images,
+                              const lt_metric *metric, const lt_disk *disk, const lt_diskmap *map, const float *d_texels,
+                              const double *uv, int32_t n_baselines, int32_t split_orders, double t_start, double dt,
+                              int32_t n_times, double *d_out);
+int lt_diskmap_visibility(const float *hits, const uint8_t *n_hits, int32_t R, int32_t W, int32_t max_images,
+                          const lt_metric *metric, const lt_disk *disk, const lt_diskmap *map, const float *texels,
+                          const double *uv, int32_t n_baselines, int32_t split_orders, double t_start, double dt,
+                          int32_t n_times, double *out);
+
 /* ---- supersampled (anti-aliased) frames, resolved on the GPU ------------------------------------------- *
  * Every frame above is one ray per pixel, taken at the pixel's corner.  These entry points trace S x S rays per       *
  * pixel and write only the resolved pixels: nothing of the S^2 times larger frame crosses PCIe or stays in memory.    *

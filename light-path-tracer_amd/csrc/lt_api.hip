@@ -15,6 +15,7 @@
 #include "lt_hotspot_aa.hpp"
 #include "lt_diskmap.hpp"
 #include "lt_spectrum.hpp"
+#include "lt_visibility.hpp"
 #ifdef LT_PROBES
 #include "lt_probe.hpp"
 #endif
@@ -146,6 +147,7 @@ struct StreamSlot {
     Grow disk_mom;  // lt_trace_disk_pol / its batch twin: the integrate kernel's hit momenta
     Grow hotspot;   // lt_hotspot_lightcurve: the first stage's partial sums
     Grow spectrum;  // lt_*_spectrum: the first stage's partial histograms of one batch of times (<= LT_SPECTRUM_WORKSPACE_BYTES)
+    Grow visibility; // lt_*_visibility: the baselines, then the first stage's partials of one launch (<= LT_VISIBILITY_WORKSPACE_BYTES)
     std::vector<int32_t> blocks_host; // what `blocks` holds (skip the upload when unchanged)
     EventQuad own{}; // lt_render's private timing events (created on first use)
     bool own_ok = false;
@@ -232,7 +234,7 @@ static void release(Grow &g)
 // Everything a slot owns, and the slot.  The caller has drained the slot's stream and taken the slot off its list.
 static void destroy_slot(StreamSlot *sl)
 {
-    for (Grow *g : {&sl->ws, &sl->dev, &sl->dense, &sl->blocks, &sl->disk_img, &sl->disk_time, &sl->disk_mom, &sl->hotspot, &sl->spectrum, &sl->aa_list, &sl->aa_scratch}) release(*g);
+    for (Grow *g : {&sl->ws, &sl->dev, &sl->dense, &sl->blocks, &sl->disk_img, &sl->disk_time, &sl->disk_mom, &sl->hotspot, &sl->spectrum, &sl->visibility, &sl->aa_list, &sl->aa_scratch}) release(*g);
     if (sl->own_ok) for (auto &e : sl->own.e) (void)hipEventDestroy(e);
     for (auto &q : sl->aa_events) for (auto &e : q.e) (void)hipEventDestroy(e);
     delete sl;
@@ -1614,3 +1616,4 @@ extern "C" int lt_scatter_rows_indexed_dev(const void *d_rows, void *d_full, con
 #include "lt_api_aa.inc"
 #include "lt_api_aa_adaptive.inc"
 #include "lt_api_spectrum.inc"
+#include "lt_api_visibility.inc"

@@ -19,6 +19,9 @@ table on the disk that turns with it (shade_diskmap, diskmap_lightcurve; spiral_
 
 The same records binned by g give the energy-resolved light: Spectrum is the grid, spectrum_bin the bin rule, and
 disk_spectrum / hotspot_spectrum / diskmap_spectrum the broadened line and the dynamic spectra (lt_*_spectrum).
+The same weights taken with a phase per pixel give what an interferometer measures: Baselines holds the (u, v) points,
+visibility_phase is the phase rule, and disk_visibility / hotspot_visibility / diskmap_visibility the complex
+visibilities per image order (lt_*_visibility).
 """
 from dataclasses import dataclass
 from typing import Optional
@@ -510,6 +513,128 @@ def hotspot_spectrum(M, a, hits, n_hits, spot, spec, times):
 def diskmap_spectrum(M, a, hits, n_hits, dmap, spec, times):
     """lt_diskmap_spectrum restated: the map's dynamic spectrum, (len(times), planes, n_bins + 2) float64."""
     return np.stack([_bin_weights(hits, n_hits, spec, map_intensity(M, a, hits, dmap, float(t))) for t in times])
+
+
+# ---- visibilities (lt_disk_visibility, lt_hotspot_visibility, lt_diskmap_visibility) -----------------------------------------
+VISIBILITY_MAX_BASELINES = 1024
+
+
+def sincospi_reduced(x):
+    """(sin 2 pi x, cos 2 pi x) by the header's rule, float64: f = x - rint(x) (exact), then sincospi(2 f) -- the argument
+    split into the nearest quarter turn k / 2 and a rest |r| <= 1/4 (exact), sin and cos of pi r, and the quarter turns
+    applied by swapping and negating.  So whole and quarter cycles give exactly 0, 1 and -1."""
+    x = np.asarray(x, dtype=np.float64)
+    y = 2.0 * (x - np.rint(x))
+    k = np.rint(2.0 * y)
+    r = y - 0.5 * k
+    s0, c0 = np.sin(np.pi * r), np.cos(np.pi * r)
+    q = np.mod(k.astype(np.int64), 4)
+    s = np.choose(q, [s0, c0, -s0, -c0])
+    c = np.choose(q, [c0, -s0, -c0, s0])
+    return s, c
+
+
+def visibility_phase(uv, ix, iy):
+    """exp(-2 pi i (u ix + v iy)) by the header's rule -> complex128 (n_baselines,) + ix.shape: x = u ix + v iy with both
+    products rounded and then the sum, reduced by sincospi_reduced; the term of a weight w is w times this."""
+    uv = np.asarray(uv, dtype=np.float64).reshape(-1, 2)
+    ix, iy = np.broadcast_arrays(np.asarray(ix, dtype=np.float64), np.asarray(iy, dtype=np.float64))
+    shape = (-1,) + (1,) * ix.ndim
+    s, c = sincospi_reduced(uv[:, 0].reshape(shape) * ix + uv[:, 1].reshape(shape) * iy)
+    return c - 1j * s
+
+
+@dataclass
+class Baselines:
+    """The (u, v) points of an interferometer (include/ltrace.h, "visibilities"): uv (n, 2) float64 in cycles per pixel,
+    |u|, |v| <= 0.5 (the Nyquist limit), 1 <= n <= 1024.  split_orders: one plane per stored slot (image order) instead of
+    one for all.  The entry points take them per pixel of the record buffer; image_lens.render_sequence takes them per
+    output pixel and refers the phase to the frame's centre (recentre)."""
+    uv: np.ndarray
+    split_orders: bool = False
+
+    def __post_init__(self):
+        uv = np.array(self.uv, dtype=np.float64)
+        if uv.ndim != 2 or uv.shape[1] != 2:
+            raise ValueError("Baselines: uv must be (n, 2)")
+        if not 1 <= uv.shape[0] <= VISIBILITY_MAX_BASELINES:
+            raise ValueError(f"Baselines: 1 ... {VISIBILITY_MAX_BASELINES} baselines")
+        if not np.all(np.isfinite(uv)) or not np.all(np.abs(uv) <= 0.5):
+            raise ValueError("Baselines: |u|, |v| <= 0.5 cycles per pixel, both finite")
+        self.uv, self.split_orders = np.ascontiguousarray(uv), bool(self.split_orders)
+
+    @classmethod
+    def radial(cls, n, u_max, angle_deg, split_orders=False):
+        """n baselines of lengths 0 ... u_max along the direction angle_deg (from +u towards +v)."""
+        rho = float(u_max) * (np.arange(int(n)) / max(int(n) - 1, 1))
+        th = np.radians(float(angle_deg))
+        return cls(np.stack([rho * np.cos(th), rho * np.sin(th)], axis=-1), split_orders)
+
+    @classmethod
+    def grid(cls, n_u, n_v, u_max, split_orders=False):
+        """n_u x n_v baselines on a regular grid over [-u_max, u_max]^2, v outer and u inner."""
+        u, v = np.linspace(-float(u_max), float(u_max), int(n_u)), np.linspace(-float(u_max), float(u_max), int(n_v))
+        vv, uu = np.meshgrid(v, u, indexing="ij")
+        return cls(np.stack([uu.ravel(), vv.ravel()], axis=-1), split_orders)
+
+    def __len__(self):
+        return self.uv.shape[0]
+
+    def planes(self, max_images):
+        return int(max_images) if self.split_orders else 1
+
+    def fine(self, samples=1):
+        """The baselines in cycles per pixel of the fine records of `samples`: (u / S, v / S)."""
+        return self.uv / np.float64(samples)
+
+    def recentre(self, V, shape, samples=1):
+        """V (..., n) as an entry point gives it for the fine records of an (H, W) = shape frame at fine(samples) -> the
+        same in output-pixel units, referred to the centre of the output frame: multiplied by
+        exp(2 pi i [u (x_c + 1/2 - 1/(2 S)) + v (y_c + 1/2 - 1/(2 S))]), x_c = (W - 1) / 2, y_c = (H - 1) / 2, u and v in
+        cycles per output pixel (the factor by sincospi_reduced), and divided by S^2."""
+        H, W = shape
+        S = np.float64(samples)
+        off = 0.5 - 0.5 / S
+        s, c = sincospi_reduced(self.uv[:, 0] * ((W - 1) / 2.0 + off) + self.uv[:, 1] * ((H - 1) / 2.0 + off))
+        return np.asarray(V) * (c + 1j * s) / (S * S)
+
+
+def _visibility(hits, n_hits, uv, split_orders, weights):
+    """(planes, n_baselines) complex128: weights (R, W, max_images) of the stored slots of hits whose g is not NaN, each
+    plane's added over the pixels with visibility_phase."""
+    hits = np.asarray(hits)
+    R, W, m = hits.shape[:3]
+    on = (_stored(hits, n_hits)[..., None] > np.arange(m)) & ~np.isnan(hits[..., 2])
+    w = np.where(on, np.asarray(weights, dtype=np.float64), 0.0)
+    w = w if split_orders else w.sum(axis=-1, keepdims=True)
+    lit = np.nonzero(np.any(w != 0.0, axis=-1).ravel())[0]                # (a pixel without light adds exactly nothing)
+    w = w.reshape(R * W, -1)[lit]
+    uv = np.asarray(uv, dtype=np.float64).reshape(-1, 2)
+    out = np.zeros((w.shape[1], uv.shape[0]), dtype=np.complex128)
+    for b in range(0, uv.shape[0], 64):
+        out[:, b:b + 64] = (w.T[:, None, :] * visibility_phase(uv[b:b + 64], lit % W, lit // W)[None]).sum(axis=-1)
+    return out
+
+
+def disk_visibility(M, a, hits, n_hits, disk, uv, split_orders=False):
+    """lt_disk_visibility restated: (planes, n_baselines) complex128, per stored slot disk.exposure g^4 (r_in / r)^q times
+    exp(-2 pi i (u ix + v iy)); uv in cycles per pixel of hits."""
+    h = np.asarray(hits).astype(np.float64)
+    with np.errstate(invalid="ignore"):
+        w = disk.exposure * (h[..., 2] * h[..., 2]) ** 2 * (disk.inner_edge(M, a) / h[..., 0]) ** disk.q
+    return _visibility(hits, n_hits, uv, split_orders, w)
+
+
+def hotspot_visibility(M, a, hits, n_hits, spot, uv, split_orders, times):
+    """lt_hotspot_visibility restated: (len(times), planes, n_baselines) complex128; every image order at its own
+    emission time t - dt."""
+    with np.errstate(invalid="ignore"):
+        return np.stack([_visibility(hits, n_hits, uv, split_orders, spot_intensity(M, a, hits, spot, float(t))) for t in times])
+
+
+def diskmap_visibility(M, a, hits, n_hits, dmap, uv, split_orders, times):
+    """lt_diskmap_visibility restated: (len(times), planes, n_baselines) complex128."""
+    return np.stack([_visibility(hits, n_hits, uv, split_orders, map_intensity(M, a, hits, dmap, float(t))) for t in times])
 
 
 # ---- linear polarization (lt_trace_disk_pol, lt_shade_stokes, lt_hotspot_lightcurve_stokes) ------------------------

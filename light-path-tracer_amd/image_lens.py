@@ -303,7 +303,7 @@ def render_frame(source_image, metric, r_obs, fov, psi=(0.0, 0.0), theta_obs=np.
 
 
 def render_sequence(source_image, metric, r_obs, fov, disk, hotspot, times, shape=None, psi=(0.0, 0.0), theta_obs=np.pi / 2,
-                    integrator=None, precision=None, bfield=None, samples=None, diskmap=None, spectrum=None):
+                    integrator=None, precision=None, bfield=None, samples=None, diskmap=None, spectrum=None, baselines=None):
     """A moving picture from ONE trace: an optically thin disk (disk.TransparentDisk) with a hot spot (disk.HotSpot) on a
     circular orbit, at the observer times `times`.  The rays are traced once with the light-travel time of every hit
     (lt_trace_disk_hits); each frame is a re-shade of the stored hits (lt_shade_hotspot) over `base`, the lensed
@@ -329,6 +329,11 @@ def render_sequence(source_image, metric, r_obs, fov, disk, hotspot, times, shap
     spectrum over the grid in g (lt_hotspot_spectrum, or lt_diskmap_spectrum with a map), and `disk_spectrum`
     (planes, n_bins + 2), the stationary disk's line profile (lt_disk_spectrum); planes is 1, or max_images with
     spectrum.split_orders.  With `samples` both are the fine records' divided by S^2, as the light curve's first column.
+    baselines (disk.Baselines, (u, v) in cycles per OUTPUT pixel): the result gains `visibility` (n, planes, n_baselines)
+    complex128, the moving emitter's complex visibilities (lt_hotspot_visibility, or lt_diskmap_visibility with a map),
+    and `disk_visibility` (planes, n_baselines), the stationary disk's (lt_disk_visibility); planes is 1, or max_images
+    with baselines.split_orders.  Both are in output-pixel units with the phase referred to the frame's centre
+    (Baselines.recentre); with `samples` they are computed on the fine records at (u / S, v / S).
     One GPU, every row traced; sequences are not adaptively sampled."""
     if diskmap is not None and hotspot is not None:
         raise ValueError("render_sequence: a disk map together with a hot spot is out of scope; pass hotspot=None")
@@ -370,7 +375,7 @@ def render_sequence(source_image, metric, r_obs, fov, disk, hotspot, times, shap
     else:
         traced = ltrace.trace_disk_hits(cam, met, opts, d, max_images=m, want=("hits", "n_hits"))
     if diskmap is not None:
-        return _sequence_diskmap(traced, met, d, diskmap, times, dt, base, S, spectrum)
+        return _sequence_diskmap(traced, met, d, diskmap, times, dt, base, S, spectrum, baselines)
     frames, rgba = [], []
     for t in times:
         if S is None:
@@ -397,9 +402,22 @@ def render_sequence(source_image, metric, r_obs, fov, disk, hotspot, times, shap
         sp = spectrum.to_lt()
         dyn = ltrace.hotspot_spectrum(traced["hits"], traced["n_hits"], met, d, spot, sp, float(times[0]), dt, times.size)
         _sequence_spectra(out, traced, met, d, sp, dyn, S)
+    if baselines is not None:
+        uv = baselines.fine(1 if S is None else S)
+        dyn = ltrace.hotspot_visibility(traced["hits"], traced["n_hits"], met, d, spot, uv, baselines.split_orders, float(times[0]), dt,
+                                        times.size)
+        _sequence_visibilities(out, traced, met, d, baselines, uv, dyn, S)
     if S is not None:
         out["samples"] = S
     return out
+
+
+def _sequence_visibilities(out, traced, met, d, baselines, uv, dyn, S):
+    """render_sequence's `visibility` (the moving emitter's, dyn) and `disk_visibility`: per output pixel, about the centre."""
+    still = ltrace.disk_visibility(traced["hits"], traced["n_hits"], met, d, uv, baselines.split_orders)
+    k = 1 if S is None else S
+    shape = (traced["hits"].shape[0] // k, traced["hits"].shape[1] // k)
+    out.update(visibility=baselines.recentre(dyn, shape, k), disk_visibility=baselines.recentre(still, shape, k))
 
 
 def _sequence_spectra(out, traced, met, d, sp, dyn, S):
@@ -409,7 +427,7 @@ def _sequence_spectra(out, traced, met, d, sp, dyn, S):
     out.update(spectrum=dyn / scale, disk_spectrum=line / scale)
 
 
-def _sequence_diskmap(traced, met, d, diskmap, times, dt, base, S, spectrum=None):
+def _sequence_diskmap(traced, met, d, diskmap, times, dt, base, S, spectrum=None, baselines=None):
     """render_sequence's frames and light curve for a disk map, from the traced records."""
     dm, tex = diskmap.to_lt(), diskmap.texels
     frames, rgba = [], []
@@ -429,6 +447,11 @@ def _sequence_diskmap(traced, met, d, diskmap, times, dt, base, S, spectrum=None
         sp = spectrum.to_lt()
         dyn = ltrace.diskmap_spectrum(traced["hits"], traced["n_hits"], met, d, dm, tex, sp, float(times[0]), dt, times.size)
         _sequence_spectra(out, traced, met, d, sp, dyn, S)
+    if baselines is not None:
+        uv = baselines.fine(1 if S is None else S)
+        dyn = ltrace.diskmap_visibility(traced["hits"], traced["n_hits"], met, d, dm, tex, uv, baselines.split_orders, float(times[0]), dt,
+                                        times.size)
+        _sequence_visibilities(out, traced, met, d, baselines, uv, dyn, S)
     if S is not None:
         out["samples"] = S
     return out
@@ -446,6 +469,20 @@ def spectrum_from_args(args):
     if args.spectrum[2] != int(args.spectrum[2]):
         raise ValueError("--spectrum: N_BINS must be a whole number")
     return Spectrum(args.spectrum[0], args.spectrum[1], int(args.spectrum[2]), split_orders=args.spectrum_orders)
+
+
+def baselines_from_args(args):
+    """The disk.Baselines of --visibility N U_MAX ANGLE_DEG [--visibility-orders], or None; refused without a sequence."""
+    from disk import Baselines
+    if args.visibility is None:
+        if args.visibility_orders:
+            raise ValueError("--visibility-orders needs --visibility N U_MAX ANGLE_DEG")
+        return None
+    if args.hotspot is None and args.bfield is None and args.disk_map is None:
+        raise ValueError("--visibility transforms the stored hits of a sequence; use it with --hotspot or --disk-map (and --disk-images N)")
+    if args.visibility[0] != int(args.visibility[0]):
+        raise ValueError("--visibility: N must be a whole number")
+    return Baselines.radial(int(args.visibility[0]), args.visibility[1], args.visibility[2], split_orders=args.visibility_orders)
 
 
 def diskmap_from_args(args, disk, M, a):
@@ -468,9 +505,12 @@ def main_sequence(args, disk):
     --bfield BR BPHI BZ [--pol-frac P]: also the Stokes frames (I, Q, U) as numbered .npy and the Stokes light curve;
     without --hotspot the spot is dark and the frames show the disk alone.
     --spectrum G_MIN G_MAX N_BINS [--spectrum-orders]: also the moving emitter's dynamic spectrum, the disk's line profile
-    and the grid's edges as .npy."""
+    and the grid's edges as .npy.
+    --visibility N U_MAX ANGLE_DEG [--visibility-orders]: also the complex visibilities of the moving emitter and of the disk
+    on N baselines of 0 ... U_MAX cycles per pixel along ANGLE_DEG, and the baselines, as .npy."""
     from disk import BField, HotSpot
     spec = spectrum_from_args(args)
+    base_lines = baselines_from_args(args)
     if args.disk_map is not None and args.hotspot is not None:
         raise ValueError("--disk-map: a map together with --hotspot is out of scope; use one of them")
     if args.disk_map is not None and args.bfield is not None:
@@ -496,7 +536,7 @@ def main_sequence(args, disk):
     field = BField(*args.bfield, pol_frac=args.pol_frac) if args.bfield is not None else None
     out = render_sequence(None, metric, args.r_obs * metric.M, fov, disk, spot, t0 + dt * np.arange(n), shape=(height, width),
                           psi=(np.radians(args.psi_y), np.radians(args.psi_x)), theta_obs=np.radians(args.theta_obs), bfield=field,
-                          samples=args.samples, diskmap=dmap, spectrum=spec)
+                          samples=args.samples, diskmap=dmap, spectrum=spec, baselines=base_lines)
     stem = args.output[:-4] if args.output.lower().endswith(".png") else args.output
     for i in range(n):
         write_png_rgba8(f"{stem}_{i:04d}.png", out["rgba"][i])
@@ -512,6 +552,12 @@ def main_sequence(args, disk):
         np.save(stem + "_spectrum_edges.npy", spec.edges())
         print(f"Spectrum: {spec.n_bins} bins of g in [{spec.g_min:g}, {spec.g_max:g}) -> {stem}_spectrum.npy (dynamic), {stem}_line.npy (the disk's "
               f"line), {stem}_spectrum_edges.npy")
+    if base_lines is not None:
+        np.save(stem + "_visibility.npy", out["visibility"])
+        np.save(stem + "_disk_visibility.npy", out["disk_visibility"])
+        np.save(stem + "_baselines.npy", base_lines.uv)
+        print(f"Visibilities: {len(base_lines)} baselines up to {args.visibility[1]:g} cycles per pixel at {args.visibility[2]:g} deg -> "
+              f"{stem}_visibility.npy (per time), {stem}_disk_visibility.npy (the disk's), {stem}_baselines.npy")
     if args.samples is not None:
         print(f"Supersampling: {args.samples} x {args.samples} rays per pixel, every frame resolved on the GPU")
     print(f"{'Hot spot' if dmap is None else 'Disk map'}: one trace ({out['stats']['integrate_ms']:.2f} ms), {n} frames -> {stem}_0000.png ..., light curve -> "
@@ -798,6 +844,11 @@ def build_parser():
                     help="with --hotspot / --disk-map: bin the stored hits by g = E_obs / E_rest on a linear grid of N_BINS (1 ... 512) bins; "
                          "writes the dynamic spectrum, the disk's line profile and the bin edges as .npy")
     ap.add_argument("--spectrum-orders", action="store_true", help="--spectrum: one plane per image order instead of one for all")
+    ap.add_argument("--visibility", type=float, nargs=3, default=None, metavar=("N", "U_MAX", "ANGLE_DEG"),
+                    help="with --hotspot / --disk-map: the complex visibilities of the stored hits on N (1 ... 1024) baselines of "
+                         "0 ... U_MAX (<= 0.5) cycles per pixel along ANGLE_DEG, about the frame's centre; writes them per time, the "
+                         "disk's own and the baselines as .npy")
+    ap.add_argument("--visibility-orders", action="store_true", help="--visibility: one plane per image order instead of one for all")
     return ap
 
 
@@ -812,6 +863,7 @@ if __name__ == "__main__":
         from disk import ThinDisk
         disk = ThinDisk(r_in=args.disk_rin, r_out=args.disk_rout, q=args.disk_q, exposure=args.disk_exposure)
     spectrum_from_args(args)                                  # (refuses --spectrum without a sequence)
+    baselines_from_args(args)                                 # (and --visibility)
     if args.hotspot is not None or args.bfield is not None or args.disk_map is not None:
         main_sequence(args, disk)
         sys.exit(0)

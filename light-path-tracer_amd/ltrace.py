@@ -95,6 +95,7 @@ class Spectrum(C.Structure):
 
 
 SPECTRUM_MAX_BINS, SPECTRUM_BLOCKS, SPECTRUM_WORKSPACE_BYTES = 512, 256, 64 << 20
+VISIBILITY_MAX_BASELINES, VISIBILITY_BLOCKS, VISIBILITY_BATCH_TERMS, VISIBILITY_WORKSPACE_BYTES = 1024, 256, 16, 64 << 20
 
 
 class BField(C.Structure):
@@ -269,6 +270,21 @@ SIGNATURES = {
     "lt_diskmap_spectrum": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Metric), C.POINTER(Disk),
                                        C.POINTER(DiskMap), C.c_void_p, C.POINTER(Spectrum), C.c_double, C.c_double, C.c_int32,
                                        C.c_void_p]),
+    "lt_visibility_batch_times": (C.c_int32, [C.c_int32, C.c_int32]),
+    "lt_disk_visibility_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Metric), C.POINTER(Disk),
+                                   C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "lt_hotspot_visibility_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Metric), C.POINTER(Disk),
+                                      C.POINTER(HotSpot), C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_void_p]),
+    "lt_diskmap_visibility_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Metric), C.POINTER(Disk),
+                                      C.POINTER(DiskMap), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32,
+                                      C.c_void_p]),
+    "lt_disk_visibility": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Metric), C.POINTER(Disk),
+                                   C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "lt_hotspot_visibility": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Metric), C.POINTER(Disk),
+                                      C.POINTER(HotSpot), C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_void_p]),
+    "lt_diskmap_visibility": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Metric), C.POINTER(Disk),
+                                      C.POINTER(DiskMap), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32,
+                                      C.c_void_p]),
     "lt_shade_diskmap_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Metric),
                                        C.POINTER(Disk), C.POINTER(DiskMap), C.c_void_p, C.c_double, C.c_void_p, C.c_int32,
                                        C.c_void_p, C.c_void_p]),
@@ -1303,6 +1319,100 @@ def diskmap_spectrum_dev(d_hits, d_n_hits, rows, width, max_images, metric, disk
     _check(load().lt_diskmap_spectrum_dev(_p(d_hits), _p(d_n_hits), rows, width, max_images, C.byref(metric), C.byref(disk),
                                           C.byref(dmap), _p(d_texels), C.byref(spec), float(t_start), float(dt), int(n_times),
                                           _p(d_out)))
+
+
+# ---- visibilities (lt_disk_visibility, lt_hotspot_visibility, lt_diskmap_visibility) ---------------------------------------
+def visibility_planes(split_orders, max_images):
+    """Planes of a visibility's output: 1, or max_images with split_orders."""
+    return int(max_images) if split_orders else 1
+
+
+def visibility_batch_times(split_orders, max_images):
+    """Times a workgroup of the visibilities' first stage accumulates at once (lt_visibility_batch_times):
+    max(1, VISIBILITY_BATCH_TERMS // planes); longer sequences run in batches of this many.  Needs no GPU."""
+    return int(load().lt_visibility_batch_times(int(max_images), int(bool(split_orders))))
+
+
+def _uv_array(uv):
+    """The baselines as the library reads them: C-contiguous float64 (n, 2), cycles per pixel of the record buffer."""
+    uv = np.ascontiguousarray(uv, dtype=np.float64)
+    if uv.ndim != 2 or uv.shape[1] != 2:
+        raise ValueError(f"uv must be (n_baselines, 2); got {uv.shape}")
+    return uv
+
+
+def _visibility_out(uv, split_orders, max_images, n_times):
+    """The float64 (n_times, planes, n_baselines, 2) output of a visibility call; sized by the header's limits so that a
+    call the library will refuse allocates little."""
+    n_b = min(uv.shape[0], VISIBILITY_MAX_BASELINES)
+    return np.empty((max(int(n_times), 0), visibility_planes(split_orders, min(max(int(max_images), 0), 8)), n_b, 2))
+
+
+def _complex(out):
+    """(..., 2) float64 (re, im) as complex128 (...)."""
+    return np.ascontiguousarray(out).view(np.complex128)[..., 0]
+
+
+def disk_visibility(hits, n_hits, metric, disk, uv, split_orders=False):
+    """The stationary disk's visibilities from stored hits (lt_disk_visibility) -> (planes, n_baselines) complex128.  uv
+    (n_baselines, 2) float64 in cycles per pixel of the records, |u|, |v| <= 0.5; plane j the image order j with
+    split_orders.  The phase's origin is pixel (0, 0)."""
+    hits, nh = _hit_arrays(hits, n_hits)
+    uv = _uv_array(uv)
+    R, W, m = hits.shape[:3]
+    out = _visibility_out(uv, split_orders, m, 1)
+    _check(load().lt_disk_visibility(_np_ptr(hits), _np_ptr(nh), R, W, m, C.byref(metric), C.byref(disk), _np_ptr(uv), uv.shape[0],
+                                     int(bool(split_orders)), _np_ptr(out)))
+    return _complex(out)[0]
+
+
+def disk_visibility_dev(d_hits, d_n_hits, rows, width, max_images, metric, disk, uv, split_orders, d_out):
+    """Device-pointer form of disk_visibility (lt_disk_visibility_dev): uv stays a host array, d_out holds
+    (1, planes, n_baselines, 2) float64; enqueues on the default stream."""
+    uv = _uv_array(uv)
+    _check(load().lt_disk_visibility_dev(_p(d_hits), _p(d_n_hits), rows, width, max_images, C.byref(metric), C.byref(disk), _np_ptr(uv),
+                                         uv.shape[0], int(bool(split_orders)), _p(d_out)))
+
+
+def hotspot_visibility(hits, n_hits, metric, disk, spot, uv, split_orders, t_start, dt, n_times):
+    """The spot's visibilities (lt_hotspot_visibility) -> (n_times, planes, n_baselines) complex128 at t_start + i dt."""
+    hits, nh = _hit_arrays(hits, n_hits)
+    uv = _uv_array(uv)
+    R, W, m = hits.shape[:3]
+    out = _visibility_out(uv, split_orders, m, n_times)
+    _check(load().lt_hotspot_visibility(_np_ptr(hits), _np_ptr(nh), R, W, m, C.byref(metric), C.byref(disk), C.byref(spot), _np_ptr(uv),
+                                        uv.shape[0], int(bool(split_orders)), float(t_start), float(dt), int(n_times), _np_ptr(out)))
+    return _complex(out)
+
+
+def hotspot_visibility_dev(d_hits, d_n_hits, rows, width, max_images, metric, disk, spot, uv, split_orders, t_start, dt, n_times, d_out):
+    """Device-pointer form of hotspot_visibility (lt_hotspot_visibility_dev); uv stays a host array."""
+    uv = _uv_array(uv)
+    _check(load().lt_hotspot_visibility_dev(_p(d_hits), _p(d_n_hits), rows, width, max_images, C.byref(metric), C.byref(disk),
+                                            C.byref(spot), _np_ptr(uv), uv.shape[0], int(bool(split_orders)), float(t_start), float(dt),
+                                            int(n_times), _p(d_out)))
+
+
+def diskmap_visibility(hits, n_hits, metric, disk, dmap, texels, uv, split_orders, t_start, dt, n_times):
+    """The map's visibilities (lt_diskmap_visibility) -> (n_times, planes, n_baselines) complex128 at t_start + i dt."""
+    hits, nh = _hit_arrays(hits, n_hits)
+    tex = _texel_array(dmap, texels)
+    uv = _uv_array(uv)
+    R, W, m = hits.shape[:3]
+    out = _visibility_out(uv, split_orders, m, n_times)
+    _check(load().lt_diskmap_visibility(_np_ptr(hits), _np_ptr(nh), R, W, m, C.byref(metric), C.byref(disk), C.byref(dmap), _np_ptr(tex),
+                                        _np_ptr(uv), uv.shape[0], int(bool(split_orders)), float(t_start), float(dt), int(n_times),
+                                        _np_ptr(out)))
+    return _complex(out)
+
+
+def diskmap_visibility_dev(d_hits, d_n_hits, rows, width, max_images, metric, disk, dmap, d_texels, uv, split_orders, t_start, dt, n_times,
+                           d_out):
+    """Device-pointer form of diskmap_visibility (lt_diskmap_visibility_dev); uv stays a host array."""
+    uv = _uv_array(uv)
+    _check(load().lt_diskmap_visibility_dev(_p(d_hits), _p(d_n_hits), rows, width, max_images, C.byref(metric), C.byref(disk),
+                                            C.byref(dmap), _p(d_texels), _np_ptr(uv), uv.shape[0], int(bool(split_orders)), float(t_start),
+                                            float(dt), int(n_times), _p(d_out)))
 
 
 # ---- supersampled frames (lt_render_aa) ---------------------------------------------------------------------------
