@@ -866,8 +866,9 @@ int lt_diskmap_spectrum(const float *hits, const uint8_t *n_hits, int32_t R, int
  * untouched.  disk.Baselines / disk.visibility_phase / disk.disk_visibility / disk.hotspot_visibility /              *
  * disk.diskmap_visibility (Python) state the rule in numpy.                                                        *
  *                                                                                                               *
- * Out of scope: polarized visibilities, closure quantities (products of these numbers), baselines beyond Nyquist,      *
- * noise and the (u, v) tracks of real arrays, lt_render_multi and the multi-process path, adaptive sampling.          */
+ * Out of scope: closure quantities (products of these numbers), baselines beyond Nyquist, noise and the (u, v) tracks  *
+ * of real arrays, lt_render_multi and the multi-process path, adaptive sampling.  Polarized visibilities are the next   *
+ * section's.                                                                                                       */
 #define LT_VISIBILITY_MAX_BASELINES 1024
 #define LT_VISIBILITY_BLOCKS 256
 #define LT_VISIBILITY_BATCH_TERMS 16 /* times x planes a workgroup accumulates at once, per owned baseline */
@@ -900,6 +901,69 @@ int lt_diskmap_visibility(const float *hits, const uint8_t *n_hits, int32_t R, i
                           const lt_metric *metric, const lt_disk *disk, const lt_diskmap *map, const float *texels,
                           const double *uv, int32_t n_baselines, int32_t split_orders, double t_start, double dt,
                           int32_t n_times, double *out);
+
+/* ---- polarized visibilities: Stokes I, Q, U of the stored hits on every baseline ------------------------------ *
+ * What polarimetric interferometry measures: the Fourier transforms Q~(u, v) and U~(u, v) of the linearly polarized  *
+ * image next to I~(u, v), and from them the fractional polarization m = (Q~ + i U~) / I~ on a baseline.  These entry  *
+ * points are lt_disk_visibility / lt_hotspot_visibility ("visibilities") with the polarization records of           *
+ * lt_trace_disk_pol ("linear polarization"): pol (R, W, max_images, 4) float32 = (q, u, sin zeta, mu) per stored     *
+ * slot, and the field, of which only pol_frac (Pi) enters.  The rule, the phase, the limits, the times, the stored    *
+ * slots and the order of every sum are those of "visibilities"; what is new is the Stokes axis.                     *
+ *                                                                                                               *
+ * Weights.  Per stored slot whose g is not NaN, in float64 from the float32 records and in exactly this order, every   *
+ * product rounded:                                                                                               *
+ *     w_I                                 the weight of lt_disk_visibility / lt_hotspot_visibility, unchanged          *
+ *     w_Q = ((Pi sz sz) q) w_I            sz = sin zeta; Pi sz sz evaluated as (Pi sz) sz                            *
+ *     w_U = ((Pi sz sz) u) w_I                                                                                      *
+ * A slot whose g is NaN is skipped in all three.  A NaN in the slot's pol record propagates into Q~ and U~: it is the  *
+ * record's answer.  Without split_orders a pixel's slots are added in slot order before the phase is applied, once     *
+ * per Stokes parameter.                                                                                           *
+ *                                                                                                               *
+ * Output.  float64 (n_times, planes, 3, n_baselines, 2) holding (re, im), the Stokes axis (I, Q, U);                  *
+ * lt_disk_visibility_stokes one row (1, planes, 3, n_baselines, 2) and no time.  planes as lt_*_visibility: 1, or      *
+ * max_images with split_orders.  A plane without light is exactly 0 + 0i in all three.                              *
+ *                                                                                                               *
+ * Batches.  (time, plane) is flattened into a pair index k = time planes + plane over the whole call; a workgroup      *
+ * keeps the sums of LT_VISIBILITY_STOKES_BATCH_PAIRS consecutive pairs in registers (three terms each, within         *
+ * LT_VISIBILITY_BATCH_TERMS), so a batch may begin and end in the middle of a time.  Workspace, blocks, chunk order     *
+ * and final stage are those of "visibilities".                                                                    *
+ *                                                                                                               *
+ * Guarantees.  The I plane has the bits of lt_disk_visibility / lt_hotspot_visibility for the same arguments.  The     *
+ * same bits come out run after run; a row depends neither on its batch nor on its launch; a baseline's result does     *
+ * not depend on what other baselines are asked for with it; V(-u, -v) is the bitwise conjugate of V(u, v) in all      *
+ * three planes.  No floating-point atomics are used.                                                              *
+ *                                                                                                               *
+ * Refusals, in this order: everything the unpolarized entry point refuses, with its codes and in its order, through    *
+ * the baselines; then LT_ERR_INVALID_ARG for a null pol, a null field and the field's own faults (direction not finite  *
+ * or zero, pol_frac outside [0, 1]), as lt_shade_stokes words them; then the times; then a null out.  n_times = 0 is    *
+ * LT_OK and writes nothing, even with a null out.  The outputs of a refused call are untouched.  Without a device      *
+ * LT_ERR_NO_DEVICE, as everywhere.  disk.disk_visibility_stokes / disk.hotspot_visibility_stokes /                  *
+ * disk.fractional_polarization (Python) state the rule in numpy.                                                   *
+ *                                                                                                               *
+ * Out of scope: the emissivity map (it is not polarized: image_lens.render_sequence refuses a map with a field),      *
+ * circular polarization (Stokes V), Faraday rotation and conversion, closure quantities, lt_render_multi.            */
+#define LT_VISIBILITY_STOKES_BATCH_PAIRS 5 /* (time, plane) pairs a workgroup accumulates at once: 15 of the 16 terms */
+
+/* LT_VISIBILITY_STOKES_BATCH_PAIRS.  Needs no device. */
+int32_t lt_visibility_stokes_batch_pairs(void);
+
+/* Pointers as lt_*_visibility's: the _dev forms take DEVICE pointers for the records (hits, n_hits, pol) and the output
+ * and enqueue on the default stream, the others HOST pointers; uv is a HOST pointer in both.
+ * out: (n_times, planes, 3, n_baselines, 2) float64. */
+int lt_disk_visibility_stokes_dev(const float *d_hits, const uint8_t *d_n_hits, const float *d_pol, int32_t R, int32_t W,
+                                  int32_t max_images, const lt_metric *metric, const lt_disk *disk, const lt_bfield *field,
+                                  const double *uv, int32_t n_baselines, int32_t split_orders, double *d_out);
+int lt_disk_visibility_stokes(const float *hits, const uint8_t *n_hits, const float *pol, int32_t R, int32_t W,
+                              int32_t max_images, const lt_metric *metric, const lt_disk *disk, const lt_bfield *field,
+                              const double *uv, int32_t n_baselines, int32_t split_orders, double *out);
+int lt_hotspot_visibility_stokes_dev(const float *d_hits, const uint8_t *d_n_hits, const float *d_pol, int32_t R, int32_t W,
+                                     int32_t max_images, const lt_metric *metric, const lt_disk *disk, const lt_hotspot *spot,
+                                     const lt_bfield *field, const double *uv, int32_t n_baselines, int32_t split_orders,
+                                     double t_start, double dt, int32_t n_times, double *d_out);
+int lt_hotspot_visibility_stokes(const float *hits, const uint8_t *n_hits, const float *pol, int32_t R, int32_t W,
+                                 int32_t max_images, const lt_metric *metric, const lt_disk *disk, const lt_hotspot *spot,
+                                 const lt_bfield *field, const double *uv, int32_t n_baselines, int32_t split_orders,
+                                 double t_start, double dt, int32_t n_times, double *out);
 
 /* ---- supersampled (anti-aliased) frames, resolved on the GPU ------------------------------------------- *
  * Every frame above is one ray per pixel, taken at the pixel's corner.  These entry points trace S x S rays per       *

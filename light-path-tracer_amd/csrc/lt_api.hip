@@ -16,6 +16,7 @@
 #include "lt_diskmap.hpp"
 #include "lt_spectrum.hpp"
 #include "lt_visibility.hpp"
+#include "lt_visibility_stokes.hpp"
 #ifdef LT_PROBES
 #include "lt_probe.hpp"
 #endif
@@ -1617,3 +1618,4 @@ extern "C" int lt_scatter_rows_indexed_dev(const void *d_rows, void *d_full, con
 #include "lt_api_aa_adaptive.inc"
 #include "lt_api_spectrum.inc"
 #include "lt_api_visibility.inc"
+#include "lt_api_visibility_stokes.inc"

@@ -21,7 +21,8 @@ The same records binned by g give the energy-resolved light: Spectrum is the gri
 disk_spectrum / hotspot_spectrum / diskmap_spectrum the broadened line and the dynamic spectra (lt_*_spectrum).
 The same weights taken with a phase per pixel give what an interferometer measures: Baselines holds the (u, v) points,
 visibility_phase is the phase rule, and disk_visibility / hotspot_visibility / diskmap_visibility the complex
-visibilities per image order (lt_*_visibility).
+visibilities per image order (lt_*_visibility).  disk_visibility_stokes / hotspot_visibility_stokes carry the polarization
+records through the same sums (I, Q, U per baseline; lt_*_visibility_stokes), and fractional_polarization divides them.
 """
 from dataclasses import dataclass
 from typing import Optional
@@ -816,3 +817,40 @@ def stokes_lightcurve(M, a, hits, n_hits, pol, spot, times, bfield):
         wq, wu = _stokes_weights(pol, on, bfield)
         out[i] = e.sum(axis=-1).sum(), (wq * e).sum(axis=-1).sum(), (wu * e).sum(axis=-1).sum()
     return out
+
+
+# ---- polarized visibilities (lt_disk_visibility_stokes, lt_hotspot_visibility_stokes) ---------------------------------------
+def _visibility_stokes(hits, n_hits, pol, uv, split_orders, w_i, bfield):
+    """(planes, 3, n_baselines) complex128: _visibility of w_I, ((Pi sz sz) q) w_I and ((Pi sz sz) u) w_I, the products in
+    _stokes_weights' order, over the stored slots whose g is not NaN."""
+    hits = np.asarray(hits)
+    on = (_stored(hits, n_hits)[..., None] > np.arange(hits.shape[-2])) & ~np.isnan(hits[..., 2])
+    wq, wu = _stokes_weights(pol, on, bfield)
+    w_i = np.where(on, np.asarray(w_i, dtype=np.float64), 0.0)
+    return np.stack([_visibility(hits, n_hits, uv, split_orders, w) for w in (w_i, wq * w_i, wu * w_i)], axis=1)
+
+
+def disk_visibility_stokes(M, a, hits, n_hits, pol, disk, uv, bfield, split_orders=False):
+    """lt_disk_visibility_stokes restated: (planes, 3, n_baselines) complex128, the Stokes axis (I, Q, U); plane I is
+    disk_visibility's.  pol (R, W, max_images, 4) float32 (q, u, sin zeta, mu)."""
+    h = np.asarray(hits).astype(np.float64)
+    with np.errstate(invalid="ignore"):
+        w = disk.exposure * (h[..., 2] * h[..., 2]) ** 2 * (disk.inner_edge(M, a) / h[..., 0]) ** disk.q
+    return _visibility_stokes(hits, n_hits, pol, uv, split_orders, w, bfield)
+
+
+def hotspot_visibility_stokes(M, a, hits, n_hits, pol, spot, uv, bfield, split_orders, times):
+    """lt_hotspot_visibility_stokes restated: (len(times), planes, 3, n_baselines) complex128; plane I is
+    hotspot_visibility's."""
+    with np.errstate(invalid="ignore"):
+        return np.stack([_visibility_stokes(hits, n_hits, pol, uv, split_orders, spot_intensity(M, a, hits, spot, float(t)), bfield)
+                         for t in times])
+
+
+def fractional_polarization(V):
+    """m = (Q~ + i U~) / I~ of polarized visibilities V (..., 3, n_baselines) -> (..., n_baselines) complex128, NaN where
+    I~ is 0.  |m| at (0, 0) is the image's net polarization fraction; on a long baseline it may exceed 1."""
+    V = np.asarray(V, dtype=np.complex128)
+    i, q, u = V[..., 0, :], V[..., 1, :], V[..., 2, :]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(i == 0, np.nan + 0j, (q + 1j * u) / np.where(i == 0, 1.0, i))

@@ -334,6 +334,10 @@ def render_sequence(source_image, metric, r_obs, fov, disk, hotspot, times, shap
     and `disk_visibility` (planes, n_baselines), the stationary disk's (lt_disk_visibility); planes is 1, or max_images
     with baselines.split_orders.  Both are in output-pixel units with the phase referred to the frame's centre
     (Baselines.recentre); with `samples` they are computed on the fine records at (u / S, v / S).
+    bfield and baselines together: the result also gains `visibility_stokes` (n, planes, 3, n_baselines) complex128, the
+    spot's polarized visibilities (I, Q, U; lt_hotspot_visibility_stokes), and `disk_visibility_stokes` (planes, 3,
+    n_baselines), the stationary disk's (lt_disk_visibility_stokes), recentred and scaled like `visibility`; their I plane
+    is `visibility` / `disk_visibility`, and disk.fractional_polarization gives (Q~ + i U~) / I~.
     One GPU, every row traced; sequences are not adaptively sampled."""
     if diskmap is not None and hotspot is not None:
         raise ValueError("render_sequence: a disk map together with a hot spot is out of scope; pass hotspot=None")
@@ -407,6 +411,13 @@ def render_sequence(source_image, metric, r_obs, fov, disk, hotspot, times, shap
         dyn = ltrace.hotspot_visibility(traced["hits"], traced["n_hits"], met, d, spot, uv, baselines.split_orders, float(times[0]), dt,
                                         times.size)
         _sequence_visibilities(out, traced, met, d, baselines, uv, dyn, S)
+        if field is not None:
+            rec = (traced["hits"], traced["n_hits"], traced["pol"], met, d)
+            still = ltrace.disk_visibility_stokes(*rec, field, uv, baselines.split_orders)
+            dyn = ltrace.hotspot_visibility_stokes(*rec, spot, field, uv, baselines.split_orders, float(times[0]), dt, times.size)
+            k = 1 if S is None else S
+            shape = (traced["hits"].shape[0] // k, traced["hits"].shape[1] // k)
+            out.update(visibility_stokes=baselines.recentre(dyn, shape, k), disk_visibility_stokes=baselines.recentre(still, shape, k))
     if S is not None:
         out["samples"] = S
     return out
@@ -507,7 +518,8 @@ def main_sequence(args, disk):
     --spectrum G_MIN G_MAX N_BINS [--spectrum-orders]: also the moving emitter's dynamic spectrum, the disk's line profile
     and the grid's edges as .npy.
     --visibility N U_MAX ANGLE_DEG [--visibility-orders]: also the complex visibilities of the moving emitter and of the disk
-    on N baselines of 0 ... U_MAX cycles per pixel along ANGLE_DEG, and the baselines, as .npy."""
+    on N baselines of 0 ... U_MAX cycles per pixel along ANGLE_DEG, and the baselines, as .npy; together with --bfield also
+    the polarized visibilities (I, Q, U per baseline) of the spot and of the disk."""
     from disk import BField, HotSpot
     spec = spectrum_from_args(args)
     base_lines = baselines_from_args(args)
@@ -556,8 +568,13 @@ def main_sequence(args, disk):
         np.save(stem + "_visibility.npy", out["visibility"])
         np.save(stem + "_disk_visibility.npy", out["disk_visibility"])
         np.save(stem + "_baselines.npy", base_lines.uv)
+        if field is not None:
+            np.save(stem + "_visibility_stokes.npy", out["visibility_stokes"])
+            np.save(stem + "_disk_visibility_stokes.npy", out["disk_visibility_stokes"])
         print(f"Visibilities: {len(base_lines)} baselines up to {args.visibility[1]:g} cycles per pixel at {args.visibility[2]:g} deg -> "
               f"{stem}_visibility.npy (per time), {stem}_disk_visibility.npy (the disk's), {stem}_baselines.npy")
+        if field is not None:
+            print(f"Polarized visibilities (I, Q, U) -> {stem}_visibility_stokes.npy (per time), {stem}_disk_visibility_stokes.npy (the disk's)")
     if args.samples is not None:
         print(f"Supersampling: {args.samples} x {args.samples} rays per pixel, every frame resolved on the GPU")
     print(f"{'Hot spot' if dmap is None else 'Disk map'}: one trace ({out['stats']['integrate_ms']:.2f} ms), {n} frames -> {stem}_0000.png ..., light curve -> "
@@ -847,7 +864,7 @@ def build_parser():
     ap.add_argument("--visibility", type=float, nargs=3, default=None, metavar=("N", "U_MAX", "ANGLE_DEG"),
                     help="with --hotspot / --disk-map: the complex visibilities of the stored hits on N (1 ... 1024) baselines of "
                          "0 ... U_MAX (<= 0.5) cycles per pixel along ANGLE_DEG, about the frame's centre; writes them per time, the "
-                         "disk's own and the baselines as .npy")
+                         "disk's own and the baselines as .npy; with --bfield also the polarized ones (I, Q, U per baseline)")
     ap.add_argument("--visibility-orders", action="store_true", help="--visibility: one plane per image order instead of one for all")
     return ap
 

@@ -96,6 +96,7 @@ class Spectrum(C.Structure):
 
 SPECTRUM_MAX_BINS, SPECTRUM_BLOCKS, SPECTRUM_WORKSPACE_BYTES = 512, 256, 64 << 20
 VISIBILITY_MAX_BASELINES, VISIBILITY_BLOCKS, VISIBILITY_BATCH_TERMS, VISIBILITY_WORKSPACE_BYTES = 1024, 256, 16, 64 << 20
+VISIBILITY_STOKES_BATCH_PAIRS = 5
 
 
 class BField(C.Structure):
@@ -285,6 +286,17 @@ SIGNATURES = {
     "lt_diskmap_visibility": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Metric), C.POINTER(Disk),
                                       C.POINTER(DiskMap), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32,
                                       C.c_void_p]),
+    "lt_visibility_stokes_batch_pairs": (C.c_int32, []),
+    "lt_disk_visibility_stokes_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Metric),
+                                          C.POINTER(Disk), C.POINTER(BField), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "lt_hotspot_visibility_stokes_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Metric),
+                                             C.POINTER(Disk), C.POINTER(HotSpot), C.POINTER(BField), C.c_void_p, C.c_int32, C.c_int32,
+                                             C.c_double, C.c_double, C.c_int32, C.c_void_p]),
+    "lt_disk_visibility_stokes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Metric),
+                                          C.POINTER(Disk), C.POINTER(BField), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "lt_hotspot_visibility_stokes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Metric),
+                                             C.POINTER(Disk), C.POINTER(HotSpot), C.POINTER(BField), C.c_void_p, C.c_int32, C.c_int32,
+                                             C.c_double, C.c_double, C.c_int32, C.c_void_p]),
     "lt_shade_diskmap_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Metric),
                                        C.POINTER(Disk), C.POINTER(DiskMap), C.c_void_p, C.c_double, C.c_void_p, C.c_int32,
                                        C.c_void_p, C.c_void_p]),
@@ -1413,6 +1425,65 @@ def diskmap_visibility_dev(d_hits, d_n_hits, rows, width, max_images, metric, di
     _check(load().lt_diskmap_visibility_dev(_p(d_hits), _p(d_n_hits), rows, width, max_images, C.byref(metric), C.byref(disk),
                                             C.byref(dmap), _p(d_texels), _np_ptr(uv), uv.shape[0], int(bool(split_orders)), float(t_start),
                                             float(dt), int(n_times), _p(d_out)))
+
+
+# ---- polarized visibilities (lt_disk_visibility_stokes, lt_hotspot_visibility_stokes) -------------------------------------
+def visibility_stokes_batch_pairs():
+    """(time, plane) pairs a workgroup of the polarized visibilities' first stage accumulates at once
+    (lt_visibility_stokes_batch_pairs): VISIBILITY_STOKES_BATCH_PAIRS, three terms each.  Needs no GPU."""
+    return int(load().lt_visibility_stokes_batch_pairs())
+
+
+def _visibility_stokes_out(uv, split_orders, max_images, n_times):
+    """The float64 (n_times, planes, 3, n_baselines, 2) output of a polarized visibility call, sized as _visibility_out."""
+    shape = _visibility_out(uv, split_orders, max_images, 0).shape
+    return np.empty((max(int(n_times), 0), shape[1], 3, shape[2], 2))
+
+
+def disk_visibility_stokes(hits, n_hits, pol, metric, disk, field, uv, split_orders=False):
+    """The stationary disk's polarized visibilities (lt_disk_visibility_stokes) -> (planes, 3, n_baselines) complex128, the
+    Stokes axis (I, Q, U); pol the (rows, W, max_images, 4) records of trace_disk_pol, the rest as disk_visibility.  The I
+    plane has disk_visibility's bits."""
+    hits, nh = _hit_arrays(hits, n_hits)
+    pol = _pol_array(pol, hits)
+    uv = _uv_array(uv)
+    R, W, m = hits.shape[:3]
+    out = _visibility_stokes_out(uv, split_orders, m, 1)
+    _check(load().lt_disk_visibility_stokes(_np_ptr(hits), _np_ptr(nh), _np_ptr(pol), R, W, m, C.byref(metric), C.byref(disk),
+                                            C.byref(field), _np_ptr(uv), uv.shape[0], int(bool(split_orders)), _np_ptr(out)))
+    return _complex(out)[0]
+
+
+def disk_visibility_stokes_dev(d_hits, d_n_hits, d_pol, rows, width, max_images, metric, disk, field, uv, split_orders, d_out):
+    """Device-pointer form of disk_visibility_stokes (lt_disk_visibility_stokes_dev): uv stays a host array, d_out holds
+    (1, planes, 3, n_baselines, 2) float64; enqueues on the default stream."""
+    uv = _uv_array(uv)
+    _check(load().lt_disk_visibility_stokes_dev(_p(d_hits), _p(d_n_hits), _p(d_pol), rows, width, max_images, C.byref(metric),
+                                                C.byref(disk), C.byref(field), _np_ptr(uv), uv.shape[0], int(bool(split_orders)),
+                                                _p(d_out)))
+
+
+def hotspot_visibility_stokes(hits, n_hits, pol, metric, disk, spot, field, uv, split_orders, t_start, dt, n_times):
+    """The spot's polarized visibilities (lt_hotspot_visibility_stokes) -> (n_times, planes, 3, n_baselines) complex128 at
+    t_start + i dt, the Stokes axis (I, Q, U).  The I plane has hotspot_visibility's bits."""
+    hits, nh = _hit_arrays(hits, n_hits)
+    pol = _pol_array(pol, hits)
+    uv = _uv_array(uv)
+    R, W, m = hits.shape[:3]
+    out = _visibility_stokes_out(uv, split_orders, m, n_times)
+    _check(load().lt_hotspot_visibility_stokes(_np_ptr(hits), _np_ptr(nh), _np_ptr(pol), R, W, m, C.byref(metric), C.byref(disk),
+                                               C.byref(spot), C.byref(field), _np_ptr(uv), uv.shape[0], int(bool(split_orders)),
+                                               float(t_start), float(dt), int(n_times), _np_ptr(out)))
+    return _complex(out)
+
+
+def hotspot_visibility_stokes_dev(d_hits, d_n_hits, d_pol, rows, width, max_images, metric, disk, spot, field, uv, split_orders, t_start, dt,
+                                  n_times, d_out):
+    """Device-pointer form of hotspot_visibility_stokes (lt_hotspot_visibility_stokes_dev); uv stays a host array."""
+    uv = _uv_array(uv)
+    _check(load().lt_hotspot_visibility_stokes_dev(_p(d_hits), _p(d_n_hits), _p(d_pol), rows, width, max_images, C.byref(metric),
+                                                   C.byref(disk), C.byref(spot), C.byref(field), _np_ptr(uv), uv.shape[0],
+                                                   int(bool(split_orders)), float(t_start), float(dt), int(n_times), _p(d_out)))
 
 
 # ---- supersampled frames (lt_render_aa) ---------------------------------------------------------------------------
