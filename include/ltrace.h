@@ -173,6 +173,14 @@ int lt_trace_batch_kerr(double M, double a, double r_obs, const double *alphas, 
                         int integrator, int precision, int schedule, int64_t n, double *out_fa,
                         int64_t *out_w, int8_t *out_status, uint32_t *out_rhs_evals);
 
+/* Device probe for the tests: lt_trace_batch_kerr with the fixed-step RK4 integrator, every ray traced by the general
+ * iteration alone (the far-field streak is never entered, no ghost lanes).  The streak takes the same steps by the same
+ * arithmetic, so lt_trace_batch_kerr must agree with this bit for bit, in the evaluation counts too. */
+int lt_trace_batch_kerr_general_probe(double M, double a, double r_obs, const double *alphas, const double *thetas,
+                                      double theta_obs, double lambda_max, const uint8_t *axis_refines, int precision,
+                                      int64_t n, double *out_fa, int64_t *out_w, int8_t *out_status,
+                                      uint32_t *out_rhs_evals);
+
 /* The float32 far-field streak's fixed-quadrant loop: on != 0 enables it, 0 disables it, for every Kerr
  * launch enqueued afterwards (the default: on, or LT_EQ_STREAK=0/1 in the environment when the library is loaded).  It
  * changes no output and no counter but LT_STAT_EQ_ITERS.  Returns the previous setting. */

@@ -1406,7 +1406,8 @@ extern "C" int lt_render_multi(const lt_camera *cam, const lt_metric *metric, co
 static int trace_batch(const MetricConsts &mc, lt_opts &o, double lambda_max, const double *alphas, const double *thetas,
                        const uint8_t *refines, int64_t n, double *out_fa, int64_t *out_w, int8_t *out_status,
                        uint32_t *out_evals, const DiskParams *disk = nullptr, double *out_disk = nullptr,
-                       double *out_images = nullptr, int32_t *out_n_hits = nullptr, double *out_pol = nullptr)
+                       double *out_images = nullptr, int32_t *out_n_hits = nullptr, double *out_pol = nullptr,
+                       bool general_only = false)
 {
     int rc;
     if (n < 0) return fail(LT_ERR_INVALID_ARG, "negative ray count");
@@ -1438,7 +1439,13 @@ static int trace_batch(const MetricConsts &mc, lt_opts &o, double lambda_max, co
                                                                           st.dev<const uint8_t>(i_ref), n, w.ic<T>(), n_q);
     });
     HIP_TRY(hipGetLastError());
-    if ((rc = launch_integrate_any(mc, o, lambda_max, w, n_q, s, nullptr, disk, recs))) return rc;
+    if (general_only) {
+        with_precision(o.precision, [&](auto t) {
+            using T = decltype(t);
+            k_kerr_general_only<T><<<(unsigned)(n_q / 64), 64, 0, s>>>(make_kerr<T>(mc, lambda_max, o.h_max), w.ic<T>(), w.fin0<T>(), w.fin1<T>(), n_q);
+        });
+        HIP_TRY(hipGetLastError());
+    } else if ((rc = launch_integrate_any(mc, o, lambda_max, w, n_q, s, nullptr, disk, recs))) return rc;
     DiskParams dp_batch{};
     if (disk) { dp_batch = *disk; dp_batch.d_pol = st.dev<double>(i_pol); disk = &dp_batch; }
     if (disk && disk->max_images) {
@@ -1504,6 +1511,22 @@ extern "C" int lt_trace_batch_kerr(double M, double a, double r_obs, const doubl
     MetricConsts mc;
     if ((rc = kerr_batch_setup(&m, r_obs, theta_obs, integrator, precision, schedule, &o, &mc))) return rc;
     return trace_batch(mc, o, lambda_max, alphas, thetas, axis_refines, n, out_fa, out_w, out_status, out_rhs_evals);
+}
+
+// lt_trace_batch_kerr (fixed-step RK4) by the general iteration alone: no streak, no ghost lanes.
+extern "C" int lt_trace_batch_kerr_general_probe(double M, double a, double r_obs, const double *alphas, const double *thetas,
+                                                 double theta_obs, double lambda_max, const uint8_t *axis_refines, int precision,
+                                                 int64_t n, double *out_fa, int64_t *out_w, int8_t *out_status,
+                                                 uint32_t *out_rhs_evals)
+{
+    int rc = require_device();
+    if (rc) return rc;
+    lt_metric m{LT_METRIC_KERR, 0, M, a};
+    lt_opts o;
+    MetricConsts mc;
+    if ((rc = kerr_batch_setup(&m, r_obs, theta_obs, LT_INTEGRATOR_RK4, precision, LT_SCHED_DIRECT, &o, &mc))) return rc;
+    return trace_batch(mc, o, lambda_max, alphas, thetas, axis_refines, n, out_fa, out_w, out_status, out_rhs_evals, nullptr, nullptr,
+                       nullptr, nullptr, nullptr, true);
 }
 
 extern "C" int lt_kerr_rhs_probe(double M, double a, const double *states, const double *p_phi, int64_t n, int precision,

@@ -30,6 +30,12 @@ __device__ __forceinline__ bool wave_any(bool p) { return __builtin_amdgcn_ballo
 // also used for per-lane selects the compiler keeps its lane mask, and negating it first costs a 0/1 materialisation
 // and a compare -- two VALU instructions per test.)
 __device__ __forceinline__ bool wave_all(bool p) { return __builtin_amdgcn_ballot_w64(p) == __builtin_amdgcn_ballot_w64(true); }
+// A predicate as the wave's lane mask, and a wave-uniform lane mask as each lane's predicate again.  Several tests
+// that only ever meet in one wave-uniform branch are cheapest as one mask each, combined on the scalar unit: ANDed as
+// bools they are turned into a 0/1 VGPR and compared again to feed the ballot.  lane_pred costs no instruction: the
+// mask IS the condition register of the selects that use it.
+__device__ __forceinline__ uint64_t lane_mask(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+__device__ __forceinline__ bool lane_pred(uint64_t mask) { return __builtin_amdgcn_inverse_ballot_w64(mask); }
 
 
 // ---------------------------------------------------------------------------------------
@@ -125,6 +131,7 @@ template <> struct M<float> {
     }
     // true unless x is NaN or +-inf
     static __device__ __forceinline__ bool finite(float x) { return __builtin_fabsf(x) < __builtin_inff(); }
+    static constexpr float LARGEST = __FLT_MAX__;
 };
 
 // sin and cos of a float64 angle of modest size without libm's generic range reduction: Cody-Waite
@@ -202,6 +209,7 @@ template <> struct M<double> {
         c = __builtin_fma(pc, z, 1.0);
     }
     static __device__ __forceinline__ bool finite(double x) { return __builtin_fabs(x) < __builtin_inf(); }
+    static constexpr double LARGEST = __DBL_MAX__;
 };
 
 // ---------------------------------------------------------------------------------------
@@ -693,57 +701,84 @@ template <typename T> __device__ __forceinline__ void ray_start(const KerrConsts
 
 // The loop itself.  EQ: the fixed-quadrant form.  `done` counts attempts.  True if the loop left before max_steps
 // attempts although every lane's last attempt was ordinary (EQ: some lane left the band; never without EQ).
+//
+// The per-step test is lane masks, not a per-lane bool: each compare of `good` goes into a ballot of its own, the masks
+// are ANDed and compared with the active lanes' on the scalar unit, and only the code after the loop turns the mask back
+// into a lane predicate for the keep/discard selects (lane_pred: no instruction).
+// Finiteness is tested on the components that no range test of the same mask covers.  The old test was
+//     F5 = finite(|r| + |th| + |ph| + |p_r| + |p_th|)   (summed left to right).
+// A lane whose mask bit is set has rc4 <= r < r_escape, so r is finite, and -- a few hundred against 3.4e38 -- cannot
+// move an overflow of the sum: it changes a partial sum only below 2^31, and through three more roundings, each of
+// which can widen a one-ulp difference by 2^24 at most, that stays below 2^103, half an ulp of the largest float
+// (float64: the same with its exponents).  So the general loop sums |th| + |ph| + |p_r| + |p_th|.  In the EQ loop the
+// continue condition also holds the new angle inside the band, |th| < 2.4, and the same argument drops it from the
+// sum: (mask & band) is (good & band) of the old test for every input.  `good` ALONE, which the selects and the
+// return value use, is not: an angle outside the band may be huge or not a number.  On leaving the EQ loop -- once per
+// call -- the old F5 itself is therefore ANDed into the lane's predicate (F5 implies the shorter sum finite: rounding
+// is monotonic and every term is >= 0).  tests/test_streak_predicate_host.py holds both forms to the old predicate on
+// a grid of edge values.
 template <typename T, bool LONE, bool EQ>
 __device__ __forceinline__ bool kerr_rk4_streak_loop(const KerrConsts<T> &k, const RayConsts<T> &rc, RayState<T> &s,
                                                      uint32_t max_steps, uint32_t &done)
 {
-    // One attempt: from state `from` at affine parameter lam into `to`; true if it was an ordinary far-field step.
-    // (predicates are combined with & and |, not && and ||: short-circuit evaluation would turn them into branches)
+    // One attempt: from state `from` at affine parameter lam into `to`; the mask of the lanes for which it was an
+    // ordinary far-field step (EQ: up to F5, see above).
     // The streak only takes FULL base steps: h = h_base needs remaining >= h_base, i.e. lam <= lambda_max - h_base
     // (the tracer's h = min(h_base, remaining) is then h_base exactly).  A ray within one base step of the range end
     // fails the test and takes its last, shorter step in the general iteration.  With h invariant the step's h / 2 and
     // h / 6, the subtraction and the min leave the loop.
     // in_band: with EQ, the other half of the continue condition -- the new angle is inside the band.
     const T lam_limit = k.lambda_max - rc.hb;
-    auto attempt = [&](const State5<T> &from, const StepCarry<T, LONE> &cfrom, T lam, State5<T> &to, StepCarry<T, LONE> &cto, T &h) -> bool {
+    const uint64_t all = lane_mask(true);
+    auto attempt = [&](const State5<T> &from, const StepCarry<T, LONE> &cfrom, T lam, State5<T> &to, StepCarry<T, LONE> &cto, T &h) -> uint64_t {
         h = rc.hb;
         T min_r, max_d;
         to = kerr_rk4_step_fast_for<T, LONE, EQ>(k, rc, from, cfrom, h, min_r, max_d, cto);
-        T mag = M<T>::abs(to.r) + M<T>::abs(to.th) + M<T>::abs(to.ph) + M<T>::abs(to.pr) + M<T>::abs(to.pth);
+        T mag = (M<T>::abs(to.ph) + M<T>::abs(to.pr)) + M<T>::abs(to.pth);
+        if constexpr (!EQ) mag = ((M<T>::abs(to.th) + M<T>::abs(to.ph)) + M<T>::abs(to.pr)) + M<T>::abs(to.pth);
         ++done;
-        return (lam <= lam_limit) & M<T>::finite(mag) & (to.r >= k.rc4) & (to.r < k.r_escape) & (min_r > k.r_cut) &
-               !(max_d > T(0.25));
+        // (mag >= 0 or NaN: an ordered compare with the largest finite number is the finiteness test)
+        return lane_mask(lam <= lam_limit) & lane_mask(mag <= M<T>::LARGEST) & lane_mask(to.r >= k.rc4) &
+               lane_mask(to.r < k.r_escape) & lane_mask(min_r > k.r_cut) & lane_mask(!(max_d > T(0.25)));
     };
-    auto in_band = [&](T th) -> bool { return !EQ | ((th > k.eq_lo) & (th < k.eq_hi)); };
+    auto in_band = [&](T th) -> uint64_t { return EQ ? lane_mask(th > k.eq_lo) & lane_mask(th < k.eq_hi) : all; };
     // The state ping-pongs between two register sets (A = s.y, B) so that accepting an attempt costs no copies:
     // the loop body is two attempts, A -> B and B -> A, each followed by the one wave-uniform test.  On leaving,
-    // a lane keeps the attempted state if its own predicate held, its previous state otherwise.
+    // a lane keeps the attempted state if its own predicate held, its previous state otherwise.  The loop has ONE
+    // exit, taken from either half, and `second` says which: the selects are stated once, on (good == second), and
+    // lie outside the loop.
+    // `steps` is settled on leaving: every lane in the loop took every attempt but the last (the loop goes on only
+    // while all of them are good), and the lanes in the loop are the same from entry to exit.
     State5<T> b;
     StepCarry<T, LONE> ca, cb;
     ca.init(s.y.th);
     T h;
+    const uint32_t before = done;
+    uint64_t mask, second; // second: all ones if the loop leaves after its second attempt (B -> A), else zero
     for (;;) {
-        bool good = attempt(s.y, ca, s.lam, b, cb, h);
-        if (!wave_all(good & in_band(b.th)) | (done >= max_steps)) {
-            s.y.r = good ? b.r : s.y.r; s.y.th = good ? b.th : s.y.th; s.y.ph = good ? b.ph : s.y.ph;
-            s.y.pr = good ? b.pr : s.y.pr; s.y.pth = good ? b.pth : s.y.pth;
-            s.lam = good ? s.lam + h : s.lam;
-            s.steps += good ? 1u : 0u;
-            return EQ && wave_all(good) & (done < max_steps);
-        }
+        mask = attempt(s.y, ca, s.lam, b, cb, h);
+        second = 0ull;
+        if (((mask & in_band(b.th)) != all) | (done >= max_steps)) break;
         s.lam += h;
-        ++s.steps;
-        good = attempt(b, cb, s.lam, s.y, ca, h);
-        if (!wave_all(good & in_band(s.y.th)) | (done >= max_steps)) {
-            s.y.r = good ? s.y.r : b.r; s.y.th = good ? s.y.th : b.th; s.y.ph = good ? s.y.ph : b.ph;
-            s.y.pr = good ? s.y.pr : b.pr; s.y.pth = good ? s.y.pth : b.pth;
-            s.lam = good ? s.lam + h : s.lam;
-            s.steps += good ? 1u : 0u;
-            return EQ && wave_all(good) & (done < max_steps);
-        }
+        mask = attempt(b, cb, s.lam, s.y, ca, h);
+        second = ~0ull;
+        if (((mask & in_band(s.y.th)) != all) | (done >= max_steps)) break;
         s.lam += h;
-        ++s.steps;
     }
+    if constexpr (EQ) { // the lane's own `good`: the mask and F5 of the attempted state
+        const bool sec = lane_pred(second);
+        State5<T> to;
+        to.r = sec ? s.y.r : b.r; to.th = sec ? s.y.th : b.th; to.ph = sec ? s.y.ph : b.ph;
+        to.pr = sec ? s.y.pr : b.pr; to.pth = sec ? s.y.pth : b.pth;
+        mask &= lane_mask(M<T>::finite(M<T>::abs(to.r) + M<T>::abs(to.th) + M<T>::abs(to.ph) + M<T>::abs(to.pr) + M<T>::abs(to.pth)));
+    }
+    const bool good = lane_pred(mask);
+    const bool keep_a = lane_pred(~(mask ^ second)); // the lane's state is in A: good after B -> A, or not good after A -> B
+    s.y.r = keep_a ? s.y.r : b.r; s.y.th = keep_a ? s.y.th : b.th; s.y.ph = keep_a ? s.y.ph : b.ph;
+    s.y.pr = keep_a ? s.y.pr : b.pr; s.y.pth = keep_a ? s.y.pth : b.pth;
+    s.lam = good ? s.lam + h : s.lam;
+    s.steps += (done - before - 1u) + (good ? 1u : 0u);
+    return EQ && (mask == all) & (done < max_steps);
 }
 
 template <typename T, bool LONE = false>
@@ -754,7 +789,7 @@ __device__ __forceinline__ uint32_t kerr_rk4_streak(const KerrConsts<T> &k, cons
     uint32_t done = 0, eq = 0;
     bool more = true;
     if constexpr (!LONE && sizeof(T) == 4) {
-        if (wave_all((s.y.th > k.eq_lo) & (s.y.th < k.eq_hi))) {
+        if ((lane_mask(s.y.th > k.eq_lo) & lane_mask(s.y.th < k.eq_hi)) == lane_mask(true)) {
             more = kerr_rk4_streak_loop<T, LONE, true>(k, rc, s, max_steps, done);
             eq = done;
         }

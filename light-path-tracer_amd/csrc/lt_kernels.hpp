@@ -1106,6 +1106,30 @@ __global__ void k_kerr_rhs_probe(KerrConsts<T> k, const double *__restrict__ sta
     out[i * 5 + 0] = dr; out[i * 5 + 1] = dth; out[i * 5 + 2] = dph; out[i * 5 + 3] = dpr; out[i * 5 + 4] = dpth;
 }
 
+// The yardstick of the far-field streak (lt_trace_batch_kerr_general_probe): every ray of a batch by the general
+// iteration alone, one lane per ray, one wavefront per workgroup; no streak, no ghost lanes.  A lane leaves the loop when
+// its own ray ends.  Records in and out as in k_kerr_direct (n_q is a multiple of 64, the grid n_q / 64 workgroups).
+template <typename T>
+__global__ void __launch_bounds__(64) k_kerr_general_only(KerrConsts<T> k, const typename Vec4<T>::type *__restrict__ ic,
+                                                          typename Vec4<T>::type *__restrict__ fin0,
+                                                          typename Vec4<T>::type *__restrict__ fin1, int64_t n_q)
+{
+    const int64_t q = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (q >= n_q) return;
+    typename Vec4<T>::type rec = ic[q];
+    const int flags = (int)rec.w;
+    RayState<T> st;
+    st.y.r = k.r_obs; st.y.th = k.theta_obs; st.y.ph = T(0); st.y.pr = rec.x; st.y.pth = rec.y;
+    st.steps = 0;
+    int ev = (flags & FLAG_PAD) ? EV_PAD : EV_INVALID;
+    const RayConsts<T> rc = make_ray_consts(k, rec.z, (flags & FLAG_REFINE) != 0);
+    if (flags & FLAG_OK) {
+        ray_start(k, st, rec.x, rec.y);
+        do ev = kerr_rk4_advance(k, rc, st); while (ev == EV_RUNNING);
+    }
+    store_fin<T>(fin0, fin1, q, st.y.r, st.y.th, st.y.ph, st.y.pr, st.y.pth, rec.z, ev, st.steps);
+}
+
 #ifdef LT_PROBES
 // Issue-efficiency probe: the RK4 step alone -- no events, no divergence, no refill -- iterated on
 // every lane.  Comparing its cycles per step with the integrate kernel's separates what the

@@ -151,6 +151,9 @@ SIGNATURES = {
     "lt_trace_batch_kerr": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_double,
                                       C.c_double, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lt_trace_batch_kerr_general_probe": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_double,
+                                                    C.c_double, C.c_void_p, C.c_int, C.c_int64,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lt_kerr_rhs_probe": (C.c_int, [C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "lt_set_eq_streak": (C.c_int, [C.c_int]),
     "lt_sincos_q1_probe": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
@@ -462,6 +465,20 @@ def trace_batch_kerr(M, a, r_obs, alphas, thetas, theta_obs, lambda_max, axis_re
     _check(load().lt_trace_batch_kerr(M, a, r_obs, _np_ptr(al), _np_ptr(th), theta_obs, lambda_max, _np_ptr(ar),
                                       integrator, precision, schedule, n, _np_ptr(out_fa), _np_ptr(out_w),
                                       _np_ptr(out_status), _np_ptr(out_rhs_evals)))
+
+
+def trace_batch_kerr_general_probe(M, a, r_obs, alphas, thetas, theta_obs, lambda_max, axis_refines, out_fa, out_w,
+                                   precision=32, out_status=None, out_rhs_evals=None):
+    """trace_batch_kerr (RK4) by the general iteration alone, without the far-field streak: the streak's yardstick
+    (lt_trace_batch_kerr_general_probe)."""
+    al, th, ar, n = _ray_inputs(alphas, thetas, axis_refines)
+    _out(out_fa, np.float64, n, "out_fa")
+    _out(out_w, np.int64, n, "out_w")
+    _out(out_status, np.int8, n, "out_status")
+    _out(out_rhs_evals, np.uint32, n, "out_rhs_evals")
+    _check(load().lt_trace_batch_kerr_general_probe(M, a, r_obs, _np_ptr(al), _np_ptr(th), theta_obs, lambda_max, _np_ptr(ar),
+                                                    precision, n, _np_ptr(out_fa), _np_ptr(out_w), _np_ptr(out_status),
+                                                    _np_ptr(out_rhs_evals)))
 
 
 def kerr_rhs_probe(M, a, states, p_phi, precision=32):
