@@ -198,6 +198,43 @@ int lt_sincos_q1_probe(uint32_t bits_lo, uint32_t bits_hi, uint64_t out[4], floa
 int lt_kerr_rhs_probe(double M, double a, const double *states, const double *p_phi, int64_t n,
                       int precision, double *out);
 
+/* The same right-hand side in each form the RK4 steps evaluate it in.  form 0: checked (lt_kerr_rhs_probe), 1: without
+ * the r <= r_cut handling, 2: the packed lone-wave form, 3: the packed form in the shape of a step's last stage, its
+ * three velocities rebuilt from the factors it hands out (2, 3: float32 only).  All four agree bit for bit for r > r_cut. */
+int lt_kerr_rhs_form_probe(double M, double a, const double *states, const double *p_phi, int64_t n, int precision,
+                           int form, double *out);
+
+/* Device probe of one RK4 step (metrics.py:306-323) per state: states (n,5), p_phi (n), refine (n) (axis-refine flag of
+ * the ray), h (n) the step sizes; out_states (n,5).  form 0: the checked step, 1: the branch-free step, 2: its
+ * fixed-quadrant form (valid for a polar angle inside the streak's band, lt_sincos_q1_probe), 3: the packed lone-wave step
+ * (2, 3: float32 only).  out_min_r / out_max_d (n): the smallest stage radius and largest stage angle offset that forms
+ * 1..3 report (the step is valid iff min_r > 1.001 r_plus and max_d <= 0.25; NaN for form 0).  out_cs (n,2), may be NULL:
+ * the [cos, sin] of the new polar angle that form 3 hands to the next step (NaN otherwise). */
+int lt_kerr_step_probe(double M, double a, const double *states, const double *p_phi, const uint8_t *refine,
+                       const double *h, int64_t n, int precision, int form, double *out_states, double *out_min_r,
+                       double *out_max_d, double *out_cs);
+
+/* Accuracy sweep of a float32 math primitive of the integrators: every float32 with bit pattern in [bits_lo, bits_hi]
+ * (at most 2^30 of them) goes through the primitive and through a float64 yardstick, compared on the device.
+ *   which 0: sincos(x)        1: the small-angle sincos(d), |d| <= 0.25       (yardstick: the float64 sincos)
+ *         2: the reciprocal of a positive normal x                             (yardstick: 1.0 / x)
+ *         3: sin and cos of th0 + d rotated from the float32 (sin, cos)(th0), in the scalar and in the packed form, d
+ *            swept, for each of the n_bases (1..16) angles th0 in `bases`; the yardstick is the float64 rotation of those
+ *            float32 (sin, cos)(th0), so that the base's own rounding is not counted again.
+ * out[13]: out[0] = values compared (which 3: per base), then five pairs (largest value as the bits of a double, the
+ * argument that reached it, the lowest if several; which 3: base index << 32 | bits of d):
+ *   out[1], out[2]: absolute error of the sine;  out[3], out[4]: of the cosine (which 2: unused);
+ *   out[5], out[6]: error of the sine (which 2: of the reciprocal) in ulps of the true value;  out[7], out[8]: cosine;
+ *   out[9], out[10] (which 3): the NUMBER of (base, d) for which scalar and packed form differ in a bit, and the first;
+ *   out[11], out[12] (which 3): absolute error of either value against the float64 sincos of (double)th0 + d. */
+int lt_math32_probe(int which, uint32_t bits_lo, uint32_t bits_hi, const float *bases, int n_bases, uint64_t *out);
+
+/* The float64 primitives the yardsticks above and the float64 integrators are made of, values in and values out:
+ * x (n), out (n,2).  which 0: sincos -> [sin, cos]; 1: small-angle sincos (|x| <= 0.25) -> [sin, cos]; 2: reciprocal of a
+ * positive normal x -> [1/x, 0]; 3: x^(-1/5) of the step controllers, clamped outside [1e-6, 1e4] -> [value, 0];
+ * 4: the FLOAT32 sincos of (float)x -> [sin, cos], for tests that need its values and not its error. */
+int lt_math64_probe(int which, const double *x, int64_t n, double *out);
+
 /* ---- fused frame path ---------------------------------------------------------------- *
  * Replaces, in one call, build_alpha_lookup (image_lens.py:133-152),                     *
  * precompute_final_alpha_lookup / _2d (image_lens.py:155-178 / :185-280) and             *

@@ -1586,6 +1586,125 @@ extern "C" int lt_sincos_q1_probe(uint32_t bits_lo, uint32_t bits_hi, uint64_t o
     return LT_OK;
 }
 
+extern "C" int lt_kerr_rhs_form_probe(double M, double a, const double *states, const double *p_phi, int64_t n, int precision,
+                                      int form, double *out)
+{
+    int rc = require_device();
+    if (rc) return rc;
+    if (form < 0 || form > 3 || (form >= 2 && precision != 32)) return fail(LT_ERR_INVALID_ARG, "right-hand side form %d (float%d)", form, precision);
+    if (n <= 0) return LT_OK;
+    lt_metric m{LT_METRIC_KERR, 0, M, a};
+    MetricConsts mc;
+    if ((rc = make_metric(&m, 50.0, M_PI / 2, 0.0, &mc))) return rc;
+    DevBuf ds, dp, dout;
+    if ((rc = ds.alloc(n * 40)) || (rc = dp.alloc(n * 8)) || (rc = dout.alloc(n * 40))) return rc;
+    HIP_TRY(hipMemcpy(ds.p, states, n * 40, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dp.p, p_phi, n * 8, hipMemcpyHostToDevice));
+    with_precision(precision, [&](auto t) {
+        using T = decltype(t);
+        k_kerr_rhs_form_probe<T><<<(unsigned)((n + 63) / 64), 64>>>(make_kerr<T>(mc, 5000.0, 1.0), (const double *)ds.p, (const double *)dp.p,
+                                                                    n, form, (double *)dout.p);
+    });
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(out, dout.p, n * 40, hipMemcpyDeviceToHost));
+    return LT_OK;
+}
+
+extern "C" int lt_kerr_step_probe(double M, double a, const double *states, const double *p_phi, const uint8_t *refine,
+                                  const double *h, int64_t n, int precision, int form, double *out_states, double *out_min_r,
+                                  double *out_max_d, double *out_cs)
+{
+    int rc = require_device();
+    if (rc) return rc;
+    if (form < 0 || form > 3 || (form >= 2 && precision != 32)) return fail(LT_ERR_INVALID_ARG, "step form %d (float%d)", form, precision);
+    if (n <= 0) return LT_OK;
+    if (!states || !p_phi || !refine || !h || !out_states || !out_min_r || !out_max_d) return fail(LT_ERR_INVALID_ARG, "null pointer");
+    lt_metric m{LT_METRIC_KERR, 0, M, a};
+    MetricConsts mc;
+    if ((rc = make_metric(&m, 50.0, M_PI / 2, 0.0, &mc))) return rc;
+    DevBuf ds, dp, dr, dh, dos, dmr, dmd, dcs;
+    if ((rc = ds.alloc(n * 40)) || (rc = dp.alloc(n * 8)) || (rc = dr.alloc(n)) || (rc = dh.alloc(n * 8)) || (rc = dos.alloc(n * 40)) ||
+        (rc = dmr.alloc(n * 8)) || (rc = dmd.alloc(n * 8)) || (rc = dcs.alloc(n * 16))) return rc;
+    HIP_TRY(hipMemcpy(ds.p, states, n * 40, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dp.p, p_phi, n * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dr.p, refine, n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dh.p, h, n * 8, hipMemcpyHostToDevice));
+    with_precision(precision, [&](auto t) {
+        using T = decltype(t);
+        k_kerr_step_probe<T><<<(unsigned)((n + 63) / 64), 64>>>(make_kerr<T>(mc, 5000.0, 1.0), (const double *)ds.p, (const double *)dp.p,
+                                                                (const uint8_t *)dr.p, (const double *)dh.p, n, form, (double *)dos.p,
+                                                                (double *)dmr.p, (double *)dmd.p, (double *)dcs.p);
+    });
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(out_states, dos.p, n * 40, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_min_r, dmr.p, n * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_max_d, dmd.p, n * 8, hipMemcpyDeviceToHost));
+    if (out_cs) HIP_TRY(hipMemcpy(out_cs, dcs.p, n * 16, hipMemcpyDeviceToHost));
+    return LT_OK;
+}
+
+extern "C" int lt_math32_probe(int which, uint32_t bits_lo, uint32_t bits_hi, const float *bases, int n_bases, uint64_t *out)
+{
+    int rc = require_device();
+    if (rc) return rc;
+    if (!out || which < 0 || which > 3 || bits_hi < bits_lo || bits_hi - bits_lo >= (1u << 30))
+        return fail(LT_ERR_INVALID_ARG, "bad math probe arguments");
+    if (which == 3 && (!bases || n_bases < 1 || n_bases > 16)) return fail(LT_ERR_INVALID_ARG, "the shift probe takes 1 to 16 base angles");
+    const uint32_t n = bits_hi - bits_lo + 1;
+    DevBuf d, db;
+    if ((rc = d.alloc(MATH32_OUT * sizeof(uint64_t))) || (rc = db.alloc(16 * sizeof(float)))) return rc;
+    uint64_t init[MATH32_OUT] = {0};
+    for (int m = 0; m < MATH32_MEASURES; ++m) init[2 + 2 * m] = ~0ull;
+    HIP_TRY(hipMemcpy(d.p, init, sizeof(init), hipMemcpyHostToDevice));
+    if (which == 3) HIP_TRY(hipMemcpy(db.p, bases, n_bases * sizeof(float), hipMemcpyHostToDevice));
+    const unsigned grid = (unsigned)(((uint64_t)n + 256u * MATH32_ITEMS - 1) / (256u * MATH32_ITEMS));
+    for (int pass = 0; pass < 2; ++pass) {
+        unsigned long long *o = (unsigned long long *)d.p;
+        const float *b = (const float *)db.p;
+        if (which == 0) k_math32_probe<0><<<grid, 256>>>(bits_lo, n, b, 0, pass, o);
+        else if (which == 1) k_math32_probe<1><<<grid, 256>>>(bits_lo, n, b, 0, pass, o);
+        else if (which == 2) k_math32_probe<2><<<grid, 256>>>(bits_lo, n, b, 0, pass, o);
+        else k_math32_probe<3><<<grid, 256>>>(bits_lo, n, b, n_bases, pass, o);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpy(out, d.p, sizeof(init), hipMemcpyDeviceToHost));
+    return LT_OK;
+}
+
+// The float64 primitives, values in and values out; out as in lt_math64_probe.
+__global__ void k_math64_probe(int which, const double *__restrict__ x, int64_t n, double *__restrict__ out)
+{
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double u = 0.0, v = 0.0;
+    if (which == 0) sincos_f64(x[i], u, v);
+    else if (which == 1) M<double>::sincos_small(x[i], u, v);
+    else if (which == 2) u = M<double>::rcp_pos(x[i]);
+    else if (which == 3) u = pow_m02(x[i]);
+    else {
+        float s, c;
+        M<float>::sincos((float)x[i], s, c);
+        u = s; v = c;
+    }
+    out[i * 2 + 0] = u; out[i * 2 + 1] = v;
+}
+
+extern "C" int lt_math64_probe(int which, const double *x, int64_t n, double *out)
+{
+    int rc = require_device();
+    if (rc) return rc;
+    if (which < 0 || which > 4) return fail(LT_ERR_INVALID_ARG, "bad math probe arguments");
+    if (n <= 0) return LT_OK;
+    if (!x || !out) return fail(LT_ERR_INVALID_ARG, "null pointer");
+    DevBuf dx, dout;
+    if ((rc = dx.alloc(n * 8)) || (rc = dout.alloc(n * 16))) return rc;
+    HIP_TRY(hipMemcpy(dx.p, x, n * 8, hipMemcpyHostToDevice));
+    k_math64_probe<<<(unsigned)((n + 255) / 256), 256>>>(which, (const double *)dx.p, n, (double *)dout.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(out, dout.p, n * 16, hipMemcpyDeviceToHost));
+    return LT_OK;
+}
+
 extern "C" int lt_scatter_rows_dev(const void *d_part, void *d_full, int32_t height, int32_t width, int32_t elem_bytes,
                                    int32_t row_block, int32_t n_parts, int32_t part, void *stream)
 {

@@ -55,7 +55,8 @@ template <> struct M<float> {
     // one v_rcp_f32 inside this kernel's FMA-dense stream costs ~70 SIMD cycles, whatever the
     // occupancy and whether or not anything depends on it, against ~13 for six FMA-class instructions.
     // Bit trick seed (relative error <= 5.1 %), one cubic and one quadratic Newton step: error 1.7e-8
-    // before rounding, i.e. correctly rounded to within 1 ulp like rcp + Newton.
+    // before rounding, i.e. within 1 ulp like rcp + Newton (every float32 in [2^-100, 2^100] against float64: 0.775 ulp,
+    // tests/test_gpu_step_blocks.py).
     static __device__ __forceinline__ float rcp_pos(float x)
     {
         float y = __uint_as_float(0x7EF311C0u - __float_as_uint(x));
@@ -69,7 +70,9 @@ template <> struct M<float> {
     static __device__ __forceinline__ float max(float a, float b) { return __builtin_fmaxf(a, b); }
     static __device__ __forceinline__ float min(float a, float b) { return __builtin_fminf(a, b); }
     // sin^2 floored at 1e-15 (metrics.py:236-237): below float resolution unless sin^2 < 1e-8, so an
-    // add does the job of the max without leaving the FMA pipe.
+    // add does the job of the max without leaving the FMA pipe.  (Within 1e-4 rad of the axis the two differ: at the
+    // float32 next to pi, sin^2 = 7.6e-15 becomes 8.6e-15.  Only the L / sin^2 terms see it, and a ray that close to the
+    // axis has |L| < 1e-4 r sin theta.)
     static __device__ __forceinline__ float sin2_floor(float s) { return __builtin_fmaf(s, s, 1e-15f); }
     // pi/2 split for the Cody-Waite reduction: 8 + 11 + 24 significant bits
     static constexpr float PIO2_1 = 1.5703125f, PIO2_2 = 4.837512969970703125e-4f, PIO2_3 = 7.54978995489188e-8f;
@@ -86,7 +89,10 @@ template <> struct M<float> {
     }
     // sin and cos of an angle of modest size (|x| < ~1e4; the polar angle of a ray stays within a
     // few pi).  Cody-Waite reduction by pi/2 in three pieces, the polynomials above, quadrant fix-up
-    // with integer ops: ~25 VALU ops for both values, ~1 ulp.
+    // with integer ops: ~25 VALU ops for both values.  ABSOLUTE error <= 1.56 u (u = 2^-24, half an ulp of 1) over every
+    // float32 |x| <= 1e4 (tests/test_gpu_step_blocks.py) -- about an ulp of a result near 1, not a relative figure: next
+    // to a zero of the function the reduced angle carries the argument's rounding of pi/2's third piece, 5.8 ulp of the
+    // result at |x| = 3 pi/2, 3 pi.
     static LT_HD void sincos(float x, float &s, float &c)
     {
         const float TWO_OVER_PI = 0.636619772367581343f;
@@ -119,7 +125,9 @@ template <> struct M<float> {
         s = cy;
         c = -sy;
     }
-    // sin and cos of a SMALL angle (|d| <= 0.25): Taylor, 7 FMA-class instructions, error < 1.3e-8
+    // sin and cos of a SMALL angle (|d| <= 0.25): Taylor, 7 FMA-class instructions; truncation error < 1.3e-8, and with
+    // the rounding of the operations, over every float32 of the range: cosine within 0.53 u absolute, sine within 1.32 ulp
+    // of the result (0.33 u)
     static __device__ __forceinline__ void sincos_small(float d, float &s, float &c)
     {
         float z = d * d;
@@ -136,8 +144,10 @@ template <> struct M<float> {
 
 // sin and cos of a float64 angle of modest size without libm's generic range reduction: Cody-Waite
 // by pi/2 (fdlibm's pio2_1 + pio2_1t split, a double-double remainder y0 + y1 good to |x| ~ 1e5) and
-// the fdlibm kernel polynomials on [-pi/4, pi/4] (< 1 ulp).  ~40 float64 FMA-class instructions, no
-// branches, no scratch -- OCML's sincos carries a Payne-Hanek path and costs registers and time.
+// the fdlibm kernel polynomials on [-pi/4, pi/4].  Error < 1 ulp of the result plus the reduction's: pi/2 is carried to
+// 86 bits, so the reduced angle of x = k pi/2 + y is off by up to 1.4e-26 |k| -- next to a multiple of pi/2, where one of
+// the two results is tiny, that is many ulps OF THAT RESULT and nothing beside the argument's own rounding.  ~45 float64
+// FMA-class instructions, no branches, no scratch -- OCML's sincos carries a Payne-Hanek path and costs registers and time.
 __device__ __forceinline__ void sincos_f64(double x, double &s, double &c)
 {
     const double TWO_OVER_PI = 6.36619772367581382433e-01;
@@ -156,7 +166,6 @@ __device__ __forceinline__ void sincos_f64(double x, double &s, double &c)
     ps = __builtin_fma(z, ps, S3);
     ps = __builtin_fma(z, ps, S2);
     ps = __builtin_fma(z, ps, S1);
-    double sy = __builtin_fma(z * y0, ps, y0);
     const double C1 = 4.16666666666666019037e-02, C2 = -1.38888888888741095749e-03, C3 = 2.48015872894767294178e-05,
                  C4 = -2.75573143513906633035e-07, C5 = 2.08757232129817482790e-09, C6 = -1.13596475577881948265e-11;
     double pc = __builtin_fma(z, C6, C5);
@@ -164,8 +173,15 @@ __device__ __forceinline__ void sincos_f64(double x, double &s, double &c)
     pc = __builtin_fma(z, pc, C3);
     pc = __builtin_fma(z, pc, C2);
     pc = __builtin_fma(z, pc, C1);
-    double cy = __builtin_fma(z * z, pc, __builtin_fma(-0.5, z, 1.0));
-    double sr = __builtin_fma(y1, cy, sy), cr = __builtin_fma(-y1, sy, cy); // first-order in the low word
+    // Each value is (large part) + (everything small), summed last, so that it carries ONE rounding of its own size:
+    // sin = y0 + (y0 z ps + y1 cos), cos = w + ((1 - w) - z/2 + z^2 pc - y1 y0) with w = 1 - z/2 rounded and (1 - w) - z/2
+    // its rounding error, exact (z/2 <= 0.31: 1 - w is exact, fdlibm's __kernel_cos).  The low word y1 enters to first
+    // order.  Measured against mpmath over |x| <= 1e5: 0.78 ulp (tests/test_gpu_step_blocks.py); with the polynomial, the
+    // 1 - z/2 and the y1 term rounded one after the other, as this function did at first, 1.52.
+    const double hz = 0.5 * z;
+    const double w1 = 1.0 - hz;
+    const double cl = __builtin_fma(z * z, pc, (1.0 - w1) - hz);
+    double sr = y0 + __builtin_fma(z * y0, ps, y1 * w1), cr = w1 + __builtin_fma(-y1, y0, cl);
     bool swap = k & 1;
     double ss = swap ? cr : sr, cc = swap ? sr : cr;
     s = (k & 2) ? -ss : ss;
@@ -192,7 +208,7 @@ template <> struct M<double> {
     static __device__ __forceinline__ void sincos(double x, double &s, double &c) { sincos_f64(x, s, c); }
     // (float64 has no fixed-quadrant form: its streak never asks for one)
     static __device__ __forceinline__ void sincos_q1(double x, double &s, double &c) { sincos_f64(x, s, c); }
-    // |d| <= 0.25: Taylor to d^11 / d^12, error < 3e-18
+    // |d| <= 0.25: Taylor to d^11 / d^12, truncation error < 3e-18; with the rounding of the operations 0.58 ulp
     static __device__ __forceinline__ void sincos_small(double d, double &s, double &c)
     {
         double z = d * d;
@@ -307,6 +323,12 @@ __device__ __forceinline__ KerrRhsParts<T> kerr_rhs_parts(const KerrConsts<T> &k
     T ra = M<T>::fma(r, r, k.a2);
     T Sigma = M<T>::fma(-k.a2, s2, ra);          // r^2 + a^2 cos^2 as r^2 + a^2 - a^2 sin^2 (the 1e-15 floor is far below an ulp)
     T Delta = M<T>::fma(-k.two_M, r, ra);
+    // float64: r (r - 2M) + a^2 instead.  Delta above carries the rounding of ra, u (r^2 + a^2), which just outside the horizon
+    // of a fast hole is (r^2 + a^2 + 2 M r) / Delta = 30 ... 1000 ulps of Delta itself, and every quotient P / Delta inherits
+    // it; r - 2M is exact for M <= r <= 4M, so this form rounds Delta once.  One step from r = 1.3 ... 4 r_plus at
+    // a = 0.998 went from 12.9 to under 8 units of tests/step_blocks.py.  The float32 forms keep the two-fma chain (one
+    // instruction fewer in the issue-bound kernel, and their step stays inside the same bound: 2.9).
+    if constexpr (sizeof(T) == 8) Delta = M<T>::fma(r, r - k.two_M, k.a2);
     T SD = Sigma * Delta;
     T t = M<T>::rcp_pos(SD * s2); // > 0: r >= r_cut > r_plus so Delta > 0, Sigma > 0, s2 >= 1e-15
     T iS = (Delta * s2) * t;

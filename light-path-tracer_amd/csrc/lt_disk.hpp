@@ -207,13 +207,18 @@ struct DiskShade {
 
 // g = nu_obs / nu_em = 1 / (u^t (1 - Omega xi)) for the circular equatorial geodesic at r orbiting in +phi:
 // Omega = sqrt(M) / (r^1.5 + a sqrt(M)), u^t = (r^1.5 + a sqrt(M)) / (r^0.75 sqrt(r^1.5 - 3 M r^0.5 + 2 a sqrt(M))).
+// Every multiply-add is written as the fma it is to be: under -ffp-contract=fast the compiler otherwise decides per kernel
+// which of them to fuse, and the kernels that evaluate this on the same hit (opaque disk, images, timed hits, supersampled
+// frames) differed by up to 5 ulp -- 1 - Omega xi cancels -- where tests/test_gpu_disk_images.py allows 4.  Now they agree
+// in every bit.
 __device__ __forceinline__ double disk_redshift(double M_, double a, double r, double xi)
 {
     const double sM = sqrt(M_), sr = sqrt(r), r15 = r * sr;
-    const double num = r15 + a * sM;
+    const double asM = a * sM;
+    const double num = __builtin_fma(a, sM, r15);
     const double omega = sM / num;
-    const double ut = num / (sqrt(r15) * sqrt(r15 - 3.0 * M_ * sr + 2.0 * a * sM));
-    return 1.0 / (ut * (1.0 - omega * xi));
+    const double ut = num / (sqrt(r15) * sqrt(__builtin_fma(2.0, asM, __builtin_fma(-3.0 * M_, sr, r15))));
+    return 1.0 / (ut * __builtin_fma(-omega, xi, 1.0));
 }
 
 // Light of one point of the disk, unclamped: E = I ramp(s) with I = exposure g^4 (r_in / r)^q, s = g (r_in / r)^(3/4),

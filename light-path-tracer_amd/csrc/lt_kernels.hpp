@@ -1106,6 +1106,173 @@ __global__ void k_kerr_rhs_probe(KerrConsts<T> k, const double *__restrict__ sta
     out[i * 5 + 0] = dr; out[i * 5 + 1] = dth; out[i * 5 + 2] = dph; out[i * 5 + 3] = dpr; out[i * 5 + 4] = dpth;
 }
 
+// The right-hand side in each form the steps use (lt_kerr_rhs_form_probe): 0 checked, 1 unchecked, 2 packed, 3 packed in
+// its LAST shape, the velocities rebuilt from the factors (the step fuses those products into its sums instead).
+template <typename T>
+__global__ void __launch_bounds__(64) k_kerr_rhs_form_probe(KerrConsts<T> k_in, const double *__restrict__ states,
+                                                            const double *__restrict__ p_phi, int64_t n, int form,
+                                                            double *__restrict__ out)
+{
+    int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    KerrConsts<T> k = k_in;
+    pin_consts(k);
+    const RayConsts<T> rc = make_ray_consts(k, (T)p_phi[i], false);
+    const T r = (T)states[i * 5 + 0], th = (T)states[i * 5 + 1], pr = (T)states[i * 5 + 3], pth = (T)states[i * 5 + 4];
+    T dr, dth, dph, dpr, dpth;
+    if (form == 0) kerr_rhs<T>(k, rc, r, th, pr, pth, dr, dth, dph, dpr, dpth);
+    else {
+        T s, c;
+        M<T>::sincos(th, s, c);
+        if constexpr (sizeof(T) == 4) {
+            if (form == 1) kerr_rhs_sc<T, false>(k, rc, r, s, c, pr, pth, dr, dth, dph, dpr, dpth);
+            else if (form == 2) {
+                const PkStage g = kerr_rhs_pk<false>(k, rc, r, (f32x2){s, c}, (f32x2){pr, pth});
+                dr = g.dr; dth = g.dth; dph = g.dph; dpr = g.dp.x; dpth = g.dp.y;
+            } else {
+                const PkStage g = kerr_rhs_pk<true>(k, rc, r, (f32x2){s, c}, (f32x2){pr, pth});
+                dr = g.Delta * g.iSpr; dth = pth * g.iS; dph = g.iS * g.u; dpr = g.dp.x; dpth = g.dp.y;
+            }
+        } else kerr_rhs_sc<T, false>(k, rc, r, s, c, pr, pth, dr, dth, dph, dpr, dpth);
+    }
+    out[i * 5 + 0] = dr; out[i * 5 + 1] = dth; out[i * 5 + 2] = dph; out[i * 5 + 3] = dpr; out[i * 5 + 4] = dpth;
+}
+
+// One RK4 step per state in the form asked for (lt_kerr_step_probe): 0 kerr_rk4_step, 1 kerr_rk4_step_fast, 2 its
+// fixed-quadrant form, 3 kerr_rk4_step_fast_pk (2, 3: float32).  One lane per state; lanes beyond n leave before any
+// wave-wide test of the checked step.  Form 0 reports NaN for min_r and max_d, forms 0..2 NaN for the outgoing [cos, sin].
+template <typename T>
+__global__ void __launch_bounds__(64) k_kerr_step_probe(KerrConsts<T> k_in, const double *__restrict__ states,
+                                                        const double *__restrict__ p_phi, const uint8_t *__restrict__ refine,
+                                                        const double *__restrict__ hs, int64_t n, int form,
+                                                        double *__restrict__ out_states, double *__restrict__ out_min_r,
+                                                        double *__restrict__ out_max_d, double *__restrict__ out_cs)
+{
+    int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    KerrConsts<T> k = k_in;
+    pin_consts(k);
+    const RayConsts<T> rc = make_ray_consts(k, (T)p_phi[i], refine[i] != 0);
+    State5<T> y;
+    y.r = (T)states[i * 5 + 0]; y.th = (T)states[i * 5 + 1]; y.ph = (T)states[i * 5 + 2];
+    y.pr = (T)states[i * 5 + 3]; y.pth = (T)states[i * 5 + 4];
+    const T h = (T)hs[i];
+    T min_r = __builtin_nanf(""), max_d = __builtin_nanf("");
+    double cs0 = __builtin_nan(""), cs1 = __builtin_nan("");
+    State5<T> o;
+    if (form == 0) o = kerr_rk4_step(k, rc, y, h);
+    else if (form == 1) o = kerr_rk4_step_fast<T, false>(k, rc, y, h, min_r, max_d);
+    else if constexpr (sizeof(T) == 4) {
+        if (form == 2) o = kerr_rk4_step_fast<T, true>(k, rc, y, h, min_r, max_d);
+        else {
+            StepCarry<float, true> cin, cout;
+            cin.init(y.th);
+            o = kerr_rk4_step_fast_pk(k, rc, y, cin.cs, h, min_r, max_d, cout.cs);
+            cs0 = cout.cs.x; cs1 = cout.cs.y;
+        }
+    } else o = y; // (refused by the host)
+    out_states[i * 5 + 0] = o.r; out_states[i * 5 + 1] = o.th; out_states[i * 5 + 2] = o.ph;
+    out_states[i * 5 + 3] = o.pr; out_states[i * 5 + 4] = o.pth;
+    out_min_r[i] = min_r; out_max_d[i] = max_d;
+    if (out_cs) { out_cs[i * 2 + 0] = cs0; out_cs[i * 2 + 1] = cs1; }
+}
+
+// ---- accuracy sweeps of the float32 math primitives (lt_math32_probe) ---------------------------------------------------
+// Every float32 with bit pattern bits_lo + i, i < n, through one primitive and through a float64 yardstick, compared on the
+// device.  A thread takes MATH32_ITEMS values and keeps the largest of each error measure with the argument that gave it.
+// Pass 0 raises out[1 + 2 m] to the largest value of measure m (the bit pattern of a non-negative double orders like the
+// double: an integer atomicMax); pass 1, the same sweep again, lowers out[2 + 2 m] to the smallest argument that reaches it.
+// Measure MATH32_DIFF is a count instead (pass 0), with the smallest argument counted.
+constexpr int MATH32_ITEMS = 256, MATH32_MEASURES = 6, MATH32_DIFF = 4, MATH32_OUT = 1 + 2 * MATH32_MEASURES;
+
+// |got - want| in absolute terms and in ulps of `want` as a float32 (an ulp of the smallest normal below it)
+__device__ __forceinline__ void math32_err(float got, double want, double &abs_err, double &ulp_err)
+{
+    double e = __builtin_fabs((double)got - want);
+    e = e >= 0.0 ? e : __builtin_inf(); // a NaN must not hide
+    int ex = (int)((__double_as_longlong(want) >> 52) & 0x7ff) - 1023;
+    ex = ex < -126 ? -126 : ex;
+    abs_err = e;
+    ulp_err = e * __longlong_as_double((long long)(1023 + 23 - ex) << 52);
+}
+
+template <int WHICH>
+__global__ void __launch_bounds__(256) k_math32_probe(uint32_t bits_lo, uint32_t n, const float *__restrict__ bases, int n_bases,
+                                                      int pass, unsigned long long *__restrict__ out)
+{
+    double best[MATH32_MEASURES];
+    unsigned long long arg[MATH32_MEASURES];
+#pragma unroll
+    for (int m = 0; m < MATH32_MEASURES; ++m) { best[m] = 0.0; arg[m] = ~0ull; }
+    unsigned long long count = 0, differing = 0;
+    auto take = [&](int m, double v, unsigned long long a) {
+        if (v > best[m]) { best[m] = v; arg[m] = a; }
+    };
+    const uint64_t first = (uint64_t)blockIdx.x * (256u * MATH32_ITEMS) + threadIdx.x;
+    for (int j = 0; j < MATH32_ITEMS; ++j) {
+        const uint64_t idx = first + (uint64_t)j * 256u;
+        if (idx >= n) break;
+        const uint32_t bits = bits_lo + (uint32_t)idx;
+        const float x = __uint_as_float(bits);
+        double ea, eu;
+        if constexpr (WHICH == 0 || WHICH == 1) {
+            float s, c;
+            if constexpr (WHICH == 0) M<float>::sincos(x, s, c);
+            else M<float>::sincos_small(x, s, c);
+            double sd, cd;
+            sincos_f64((double)x, sd, cd);
+            math32_err(s, sd, ea, eu); take(0, ea, bits); take(2, eu, bits);
+            math32_err(c, cd, ea, eu); take(1, ea, bits); take(3, eu, bits);
+            ++count;
+        } else if constexpr (WHICH == 2) {
+            math32_err(M<float>::rcp_pos(x), 1.0 / (double)x, ea, eu);
+            take(0, ea, bits); take(2, eu, bits);
+            ++count;
+        } else {
+            double sdd, cdd;
+            sincos_f64((double)x, sdd, cdd);
+            for (int b = 0; b < n_bases; ++b) {
+                const float th0 = bases[b];
+                const unsigned long long a = ((unsigned long long)b << 32) | bits;
+                float s0, c0, s, c;
+                M<float>::sincos(th0, s0, c0);
+                sincos_shift<float, false>(th0, s0, c0, x, s, c);
+                const f32x2 pk = sincos_shift_pk((f32x2){c0, s0}, x);
+                if ((__float_as_uint(s) != __float_as_uint(pk.x)) | (__float_as_uint(c) != __float_as_uint(pk.y))) {
+                    ++differing;
+                    arg[MATH32_DIFF] = arg[MATH32_DIFF] < a ? arg[MATH32_DIFF] : a;
+                }
+                // the truth of the float32 inputs (s0, c0, d): the base's own rounding is not counted again
+                const double st = __builtin_fma((double)s0, cdd, (double)c0 * sdd), ct = __builtin_fma((double)c0, cdd, -((double)s0 * sdd));
+                math32_err(s, st, ea, eu); take(0, ea, a); take(2, eu, a);
+                math32_err(c, ct, ea, eu); take(1, ea, a); take(3, eu, a);
+                // and against the angle itself
+                double sa, ca;
+                sincos_f64((double)th0 + (double)x, sa, ca);
+                math32_err(s, sa, ea, eu); take(5, ea, a);
+                math32_err(c, ca, ea, eu); take(5, ea, a);
+                ++count;
+            }
+        }
+    }
+    if (pass == 0) {
+        if (count) atomicAdd(&out[0], count);
+        if (differing) atomicAdd(&out[1 + 2 * MATH32_DIFF], differing);
+    }
+#pragma unroll
+    for (int m = 0; m < MATH32_MEASURES; ++m) {
+        if (WHICH == 3 && m == MATH32_DIFF) {
+            if (pass == 0 && differing) atomicMin(&out[2 + 2 * m], arg[m]);
+            continue;
+        }
+        const unsigned long long v = (unsigned long long)__double_as_longlong(best[m]);
+        if (pass == 0) {
+            // (the plain read only spares atomics: the slot never decreases)
+            if (v > __atomic_load_n(&out[1 + 2 * m], __ATOMIC_RELAXED)) atomicMax(&out[1 + 2 * m], v);
+        } else if (v != 0 && v == out[1 + 2 * m]) atomicMin(&out[2 + 2 * m], arg[m]);
+    }
+}
+
 // The yardstick of the far-field streak (lt_trace_batch_kerr_general_probe): every ray of a batch by the general
 // iteration alone, one lane per ray, one wavefront per workgroup; no streak, no ghost lanes.  A lane leaves the loop when
 // its own ray ends.  Records in and out as in k_kerr_direct (n_q is a multiple of 64, the grid n_q / 64 workgroups).

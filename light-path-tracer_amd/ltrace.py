@@ -155,6 +155,11 @@ SIGNATURES = {
                                                     C.c_double, C.c_void_p, C.c_int, C.c_int64,
                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lt_kerr_rhs_probe": (C.c_int, [C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
+    "lt_kerr_rhs_form_probe": (C.c_int, [C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
+    "lt_kerr_step_probe": (C.c_int, [C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
+                                     C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lt_math32_probe": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p]),
+    "lt_math64_probe": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
     "lt_set_eq_streak": (C.c_int, [C.c_int]),
     "lt_sincos_q1_probe": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "lt_local_rows": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
@@ -486,6 +491,61 @@ def kerr_rhs_probe(M, a, states, p_phi, precision=32):
     pp = np.ascontiguousarray(p_phi, dtype=np.float64).ravel()
     out = np.empty_like(st)
     _check(load().lt_kerr_rhs_probe(M, a, _np_ptr(st), _np_ptr(pp), st.shape[0], precision, _np_ptr(out)))
+    return out
+
+
+RHS_FORMS = {"checked": 0, "unchecked": 1, "packed": 2, "packed_last": 3}
+STEP_FORMS = {"checked": 0, "fast": 1, "fast_q1": 2, "packed": 3}
+
+
+def kerr_rhs_form_probe(M, a, states, p_phi, precision=32, form="checked"):
+    """The right-hand side in one of the forms the steps use (RHS_FORMS; lt_kerr_rhs_form_probe) -> (n,5) float64."""
+    st = np.ascontiguousarray(states, dtype=np.float64).reshape(-1, 5)
+    pp = np.ascontiguousarray(p_phi, dtype=np.float64).ravel()
+    out = np.empty_like(st)
+    _check(load().lt_kerr_rhs_form_probe(M, a, _np_ptr(st), _np_ptr(pp), st.shape[0], precision, RHS_FORMS[form], _np_ptr(out)))
+    return out
+
+
+def kerr_step_probe(M, a, states, p_phi, h, refine=None, precision=32, form="checked"):
+    """One RK4 step from each of n states in one of the step's forms (STEP_FORMS; lt_kerr_step_probe).
+    -> dict(states (n,5), min_r (n,), max_d (n,), cs (n,2)): float64 holding the values of the precision computed in."""
+    st = np.ascontiguousarray(states, dtype=np.float64).reshape(-1, 5)
+    n = st.shape[0]
+    pp = np.ascontiguousarray(p_phi, dtype=np.float64).ravel()
+    hh = np.ascontiguousarray(np.broadcast_to(np.asarray(h, dtype=np.float64), (n,)))
+    rf = np.zeros(n, dtype=np.uint8) if refine is None else np.ascontiguousarray(np.broadcast_to(np.asarray(refine), (n,))).astype(np.uint8)
+    out, mr, md, cs = np.empty_like(st), np.empty(n), np.empty(n), np.empty((n, 2))
+    _check(load().lt_kerr_step_probe(M, a, _np_ptr(st), _np_ptr(pp), _np_ptr(rf), _np_ptr(hh), n, precision, STEP_FORMS[form],
+                                     _np_ptr(out), _np_ptr(mr), _np_ptr(md), _np_ptr(cs)))
+    return dict(states=out, min_r=mr, max_d=md, cs=cs)
+
+
+MATH32_WHICH = {"sincos": 0, "sincos_small": 1, "rcp_pos": 2, "sincos_shift": 3}
+MATH64_WHICH = {"sincos": 0, "sincos_small": 1, "rcp_pos": 2, "pow_m02": 3, "sincos_f32": 4}
+
+
+def math32_probe(which, bits_lo, bits_hi, bases=None):
+    """Accuracy sweep of one float32 primitive over every float32 with bit pattern in [bits_lo, bits_hi], compared with
+    float64 on the device (lt_math32_probe).  -> dict(compared, and per measure (value, argument bits or None):
+    abs_sin, abs_cos, ulp_sin, ulp_cos, abs_angle; differing, first_differing)."""
+    out = np.zeros(13, dtype=np.uint64)
+    b = None if bases is None else np.ascontiguousarray(bases, dtype=np.float32).ravel()
+    _check(load().lt_math32_probe(MATH32_WHICH[which], int(bits_lo), int(bits_hi), _np_ptr(b), 0 if b is None else b.size,
+                                  _np_ptr(out)))
+    val = out.view(np.float64)
+    none = np.uint64(0xFFFFFFFFFFFFFFFF)
+    res = dict(compared=int(out[0]), differing=int(out[9]), first_differing=None if out[10] == none else int(out[10]))
+    for m, name in ((0, "abs_sin"), (1, "abs_cos"), (2, "ulp_sin"), (3, "ulp_cos"), (5, "abs_angle")):
+        res[name] = (float(val[1 + 2 * m]), None if out[2 + 2 * m] == none else int(out[2 + 2 * m]))
+    return res
+
+
+def math64_probe(which, x):
+    """A float64 primitive on the device, values in, values out (lt_math64_probe) -> (n,2)."""
+    xx = np.ascontiguousarray(x, dtype=np.float64).ravel()
+    out = np.empty((xx.size, 2))
+    _check(load().lt_math64_probe(MATH64_WHICH[which], _np_ptr(xx), xx.size, _np_ptr(out)))
     return out
 
 

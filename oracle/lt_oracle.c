@@ -713,6 +713,30 @@ void LTO_NAME(lto_kerr_rhs)(const real *state5, real p_t, real p_phi, real M, re
     kerr_rhs(state5, p_t, p_phi, M, a, r_plus, out5);
 }
 
+/* One classic RK4 step (metrics.py:306-323) of each of n states (n,5), with its own p_phi and h; p_t = -1.  stage_r
+ * (n,4), may be NULL: the radius each of the four right-hand sides was evaluated at. */
+void LTO_NAME(lto_rk4_step_kerr)(const real *states, const real *p_phi, const real *h, int64_t n, real M, real a,
+                                 real r_plus, real *out_states, real *stage_r)
+{
+    for (int64_t i = 0; i < n; ++i) {
+        const real *y = states + 5 * i;
+        real k1[5], k2[5], k3[5], k4[5], tmp[5];
+        rk4_step_kerr(y, h[i], R(-1.0), p_phi[i], M, a, r_plus, k1, k2, k3, k4, tmp, out_states + 5 * i);
+        if (stage_r) {
+            stage_r[4 * i + 0] = y[0];
+            stage_r[4 * i + 1] = y[0] + R(0.5) * h[i] * k1[0];
+            stage_r[4 * i + 2] = y[0] + R(0.5) * h[i] * k2[0];
+            stage_r[4 * i + 3] = tmp[0];
+        }
+    }
+}
+
+/* lto_kerr_rhs of n states (n,5), each with its own p_phi; p_t = -1. */
+void LTO_NAME(lto_kerr_rhs_n)(const real *states, const real *p_phi, int64_t n, real M, real a, real r_plus, real *out)
+{
+    for (int64_t i = 0; i < n; ++i) kerr_rhs(states + 5 * i, R(-1.0), p_phi[i], M, a, r_plus, out + 5 * i);
+}
+
 int LTO_NAME(lto_kerr_ic)(real M, real a, real r_obs, real alpha, real theta, real theta_obs,
                           real *state5, real *p_t, real *p_phi)
 {

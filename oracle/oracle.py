@@ -142,6 +142,42 @@ def kerr_rhs(state5, p_t, p_phi, M, a, r_plus):
     return out
 
 
+def _real(f32):
+    return (np.float32, _fp, C.c_float) if f32 else (np.float64, _dp, C.c_double)
+
+
+def kerr_rhs_n(states, p_phi, M, a, f32=False):
+    """The reference's right-hand side (p_t = -1) of n states (n,5), in float64 or entirely in float32 (lto_kerr_rhs_f32:
+    the same statements with every operation rounded to float32).  -> (n,5) of that type."""
+    dt, pt, ct = _real(f32)
+    st = np.ascontiguousarray(states, dtype=dt).reshape(-1, 5)
+    pp = np.ascontiguousarray(p_phi, dtype=dt).ravel()
+    out = np.empty_like(st)
+    L = lib32() if f32 else lib()
+    fn = L.lto_kerr_rhs_n_f32 if f32 else L.lto_kerr_rhs_n
+    fn.argtypes = [pt, pt, C.c_int64, ct, ct, ct, pt]
+    fn.restype = None
+    fn(_ptr(st, pt), _ptr(pp, pt), st.shape[0], M, a, M + np.sqrt(M * M - a * a), _ptr(out, pt))
+    return out
+
+
+def rk4_step_kerr(states, p_phi, h, M, a, f32=False):
+    """One RK4 step of the reference (metrics.py:306-323, p_t = -1) from each of n states (n,5), step sizes h (n,) or a
+    scalar.  -> (new states (n,5), stage radii (n,4)), float64 or float32 throughout."""
+    dt, pt, ct = _real(f32)
+    st = np.ascontiguousarray(states, dtype=dt).reshape(-1, 5)
+    pp = np.ascontiguousarray(p_phi, dtype=dt).ravel()
+    hh = np.ascontiguousarray(np.broadcast_to(np.asarray(h, dtype=dt), pp.shape))
+    out = np.empty_like(st)
+    sr = np.empty((st.shape[0], 4), dtype=dt)
+    L = lib32() if f32 else lib()
+    fn = L.lto_rk4_step_kerr_f32 if f32 else L.lto_rk4_step_kerr
+    fn.argtypes = [pt, pt, pt, C.c_int64, ct, ct, ct, pt, pt]
+    fn.restype = None
+    fn(_ptr(st, pt), _ptr(pp, pt), _ptr(hh, pt), st.shape[0], M, a, M + np.sqrt(M * M - a * a), _ptr(out, pt), _ptr(sr, pt))
+    return out, sr
+
+
 def kerr_ic(M, a, r_obs, alpha, theta, theta_obs):
     st = np.zeros(5)
     pt = C.c_double()
