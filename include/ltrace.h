@@ -214,6 +214,35 @@ int lt_kerr_step_probe(double M, double a, const double *states, const double *p
                        const double *h, int64_t n, int precision, int form, double *out_states, double *out_min_r,
                        double *out_max_d, double *out_cs);
 
+/* ---- the float64 DP45 integrator block by block (parity probes; they call the functions the integrate kernels call) ---- *
+ * Common inputs: the metric (M, a), the observer radius (r_escape = 2 r_obs) and lambda_max; per row: states (n,5), p_phi (n),
+ * refine (n) the ray's axis-refine flag (tolerances 1e-10 / 1e-8 in place of 1e-8 / 1e-6), k1 (n,5) the carried derivative
+ * and sc0 (n,2) the carried [sin, cos] of the polar angle -- either may be NULL: computed from the state as at a ray's start --
+ * and h (n) the step size.  exact != 0: the controller of LT_INTEGRATOR_DP45_EXACT. */
+
+/* One step attempt per row, checked != 0 in the form with the in-line r <= r_cut and |dtheta| > 0.25 handling, else in the
+ * branch-free form.  out_next, out_k7 (n,5): the candidate state and its derivative; out_sc (n,2): [sin, cos] of its polar
+ * angle; out_err_sq (n): the squared error norm (err_norm = sqrt(err_sq / 5)); out_min_r, out_max_d (n): the smallest stage
+ * radius and the largest stage angle offset the branch-free form reports (stages only, the candidate's own turn not counted; it is valid iff min_r > 1.001 r_plus and
+ * max_d <= 0.25; NaN for the checked form). */
+int lt_dp45_attempt_probe(double M, double a, double r_obs, double lambda_max, const double *states, const double *p_phi,
+                          const uint8_t *refine, const double *k1, const double *sc0, const double *h, int64_t n, int exact,
+                          int checked, double *out_next, double *out_k7, double *out_sc, double *out_err_sq,
+                          double *out_min_r, double *out_max_d);
+
+/* Up to n_attempts iterations of the loop body metrics.py:454-564 per row, ending at the first that ends the ray.  lam (n)
+ * and steps (n) (attempts made so far), NULL: zeros.  Rows 64 b ... 64 b + 63 share a wavefront.  out_states, out_k1 (n,5);
+ * out_misc (n,4): sin, cos of the polar angle as carried, lam, h; out_int (n,3): the event (4 still running, 2 out of range
+ * or attempts, 0 invalid, -1 captured, 1 escaped), steps, attempts made by this call. */
+int lt_dp45_advance_probe(double M, double a, double r_obs, double lambda_max, const double *states, const double *p_phi,
+                          const uint8_t *refine, const double *k1, const double *sc0, const double *h, const double *lam,
+                          const uint32_t *steps, int64_t n, int exact, int n_attempts, double *out_states, double *out_k1,
+                          double *out_misc, int32_t *out_int);
+
+/* The step-size controller alone (the function advance() calls) on any (err_sq, h): out_reject (n) 1 where the attempt is
+ * rejected, out_h (n) the step size the loop goes on with (metrics.py:514-522, :560-564). */
+int lt_dp45_controller_probe(int exact, const double *err_sq, const double *h, int64_t n, uint8_t *out_reject, double *out_h);
+
 /* Accuracy sweep of a float32 math primitive of the integrators: every float32 with bit pattern in [bits_lo, bits_hi]
  * (at most 2^30 of them) goes through the primitive and through a float64 yardstick, compared on the device.
  *   which 0: sincos(x)        1: the small-angle sincos(d), |d| <= 0.25       (yardstick: the float64 sincos)
@@ -226,13 +255,17 @@ int lt_kerr_step_probe(double M, double a, const double *states, const double *p
  *   out[1], out[2]: absolute error of the sine;  out[3], out[4]: of the cosine (which 2: unused);
  *   out[5], out[6]: error of the sine (which 2: of the reciprocal) in ulps of the true value;  out[7], out[8]: cosine;
  *   out[9], out[10] (which 3): the NUMBER of (base, d) for which scalar and packed form differ in a bit, and the first;
- *   out[11], out[12] (which 3): absolute error of either value against the float64 sincos of (double)th0 + d. */
+ *   out[11], out[12] (which 3): absolute error of either value against the float64 sincos of (double)th0 + d.
+ *   which 4: z^(-1/10) of the float32 DP45 step controller (yardstick: the float64 pow(z, -0.1)).  out[1], out[2]: the
+ *            largest relative error among the results that are positive and finite, and its argument; out[9], out[10]: the
+ *            NUMBER of arguments whose result is not a positive finite number, and the first. */
 int lt_math32_probe(int which, uint32_t bits_lo, uint32_t bits_hi, const float *bases, int n_bases, uint64_t *out);
 
 /* The float64 primitives the yardsticks above and the float64 integrators are made of, values in and values out:
  * x (n), out (n,2).  which 0: sincos -> [sin, cos]; 1: small-angle sincos (|x| <= 0.25) -> [sin, cos]; 2: reciprocal of a
  * positive normal x -> [1/x, 0]; 3: x^(-1/5) of the step controllers, clamped outside [1e-6, 1e4] -> [value, 0];
- * 4: the FLOAT32 sincos of (float)x -> [sin, cos], for tests that need its values and not its error. */
+ * 4: the FLOAT32 sincos of (float)x -> [sin, cos], for tests that need its values and not its error;
+ * 5: the float32 controller's (float)x^(-1/10) -> [value, 0], whatever x is. */
 int lt_math64_probe(int which, const double *x, int64_t n, double *out);
 
 /* ---- fused frame path ---------------------------------------------------------------- *

@@ -1643,11 +1643,115 @@ extern "C" int lt_kerr_step_probe(double M, double a, const double *states, cons
     return LT_OK;
 }
 
+// ---- the DP45 integrator block by block ----------------------------------------------------------------------------------
+// Device copy of a host array (src may be NULL: nothing allocated), and an output buffer with its way back.
+static int probe_upload(DevBuf &d, const void *src, size_t bytes)
+{
+    if (!src) return LT_OK;
+    int rc = d.alloc(bytes);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
+    return LT_OK;
+}
+static int probe_download(void *dst, const DevBuf &d, size_t bytes)
+{
+    if (dst) HIP_TRY(hipMemcpy(dst, d.p, bytes, hipMemcpyDeviceToHost));
+    return LT_OK;
+}
+
+static int dp45_probe_consts(double M, double a, double r_obs, double lambda_max, KerrConsts<double> *k)
+{
+    lt_metric m{LT_METRIC_KERR, 0, M, a};
+    MetricConsts mc;
+    int rc = make_metric(&m, r_obs, M_PI / 2, 0.0, &mc);
+    if (rc) return rc;
+    *k = make_kerr<double>(mc, lambda_max, 1.0);
+    return LT_OK;
+}
+
+extern "C" int lt_dp45_attempt_probe(double M, double a, double r_obs, double lambda_max, const double *states,
+                                     const double *p_phi, const uint8_t *refine, const double *k1, const double *sc0,
+                                     const double *h, int64_t n, int exact, int checked, double *out_next, double *out_k7,
+                                     double *out_sc, double *out_err_sq, double *out_min_r, double *out_max_d)
+{
+    int rc = require_device();
+    if (rc) return rc;
+    if (n <= 0) return LT_OK;
+    if (!states || !p_phi || !refine || !h || !out_next || !out_k7 || !out_sc || !out_err_sq || !out_min_r || !out_max_d)
+        return fail(LT_ERR_INVALID_ARG, "null pointer");
+    KerrConsts<double> k;
+    if ((rc = dp45_probe_consts(M, a, r_obs, lambda_max, &k))) return rc;
+    DevBuf ds, dp, dr, dk, dc, dh, on, ok7, osc, oe, omr, omd;
+    if ((rc = probe_upload(ds, states, n * 40)) || (rc = probe_upload(dp, p_phi, n * 8)) || (rc = probe_upload(dr, refine, n)) ||
+        (rc = probe_upload(dk, k1, n * 40)) || (rc = probe_upload(dc, sc0, n * 16)) || (rc = probe_upload(dh, h, n * 8)) ||
+        (rc = on.alloc(n * 40)) || (rc = ok7.alloc(n * 40)) || (rc = osc.alloc(n * 16)) || (rc = oe.alloc(n * 8)) ||
+        (rc = omr.alloc(n * 8)) || (rc = omd.alloc(n * 8))) return rc;
+    auto launch = [&](auto ex, auto ch) {
+        k_dp45_attempt_probe<decltype(ex)::value, decltype(ch)::value><<<(unsigned)((n + 63) / 64), 64>>>(
+            k, (const double *)ds.p, (const double *)dp.p, (const uint8_t *)dr.p, (const double *)dk.p, (const double *)dc.p,
+            (const double *)dh.p, n, (double *)on.p, (double *)ok7.p, (double *)osc.p, (double *)oe.p, (double *)omr.p, (double *)omd.p);
+    };
+    if (exact) { if (checked) launch(std::true_type{}, std::true_type{}); else launch(std::true_type{}, std::false_type{}); }
+    else { if (checked) launch(std::false_type{}, std::true_type{}); else launch(std::false_type{}, std::false_type{}); }
+    HIP_TRY(hipGetLastError());
+    if ((rc = probe_download(out_next, on, n * 40)) || (rc = probe_download(out_k7, ok7, n * 40)) || (rc = probe_download(out_sc, osc, n * 16)) ||
+        (rc = probe_download(out_err_sq, oe, n * 8)) || (rc = probe_download(out_min_r, omr, n * 8)) || (rc = probe_download(out_max_d, omd, n * 8)))
+        return rc;
+    return LT_OK;
+}
+
+extern "C" int lt_dp45_advance_probe(double M, double a, double r_obs, double lambda_max, const double *states,
+                                     const double *p_phi, const uint8_t *refine, const double *k1, const double *sc0,
+                                     const double *h, const double *lam, const uint32_t *steps, int64_t n, int exact,
+                                     int n_attempts, double *out_states, double *out_k1, double *out_misc, int32_t *out_int)
+{
+    int rc = require_device();
+    if (rc) return rc;
+    if (n <= 0) return LT_OK;
+    if (n_attempts < 1) return fail(LT_ERR_INVALID_ARG, "n_attempts must be at least 1");
+    if (!states || !p_phi || !refine || !h || !out_states || !out_k1 || !out_misc || !out_int) return fail(LT_ERR_INVALID_ARG, "null pointer");
+    KerrConsts<double> k;
+    if ((rc = dp45_probe_consts(M, a, r_obs, lambda_max, &k))) return rc;
+    DevBuf ds, dp, dr, dk, dc, dh, dl, dst, os, ok1, om, oi;
+    if ((rc = probe_upload(ds, states, n * 40)) || (rc = probe_upload(dp, p_phi, n * 8)) || (rc = probe_upload(dr, refine, n)) ||
+        (rc = probe_upload(dk, k1, n * 40)) || (rc = probe_upload(dc, sc0, n * 16)) || (rc = probe_upload(dh, h, n * 8)) ||
+        (rc = probe_upload(dl, lam, n * 8)) || (rc = probe_upload(dst, steps, n * 4)) || (rc = os.alloc(n * 40)) ||
+        (rc = ok1.alloc(n * 40)) || (rc = om.alloc(n * 32)) || (rc = oi.alloc(n * 12))) return rc;
+    auto launch = [&](auto ex) {
+        k_dp45_advance_probe<decltype(ex)::value><<<(unsigned)((n + 63) / 64), 64>>>(
+            k, (const double *)ds.p, (const double *)dp.p, (const uint8_t *)dr.p, (const double *)dk.p, (const double *)dc.p,
+            (const double *)dh.p, (const double *)dl.p, (const uint32_t *)dst.p, n, n_attempts, (double *)os.p, (double *)ok1.p,
+            (double *)om.p, (int32_t *)oi.p);
+    };
+    if (exact) launch(std::true_type{}); else launch(std::false_type{});
+    HIP_TRY(hipGetLastError());
+    if ((rc = probe_download(out_states, os, n * 40)) || (rc = probe_download(out_k1, ok1, n * 40)) ||
+        (rc = probe_download(out_misc, om, n * 32)) || (rc = probe_download(out_int, oi, n * 12))) return rc;
+    return LT_OK;
+}
+
+extern "C" int lt_dp45_controller_probe(int exact, const double *err_sq, const double *h, int64_t n, uint8_t *out_reject,
+                                        double *out_h)
+{
+    int rc = require_device();
+    if (rc) return rc;
+    if (n <= 0) return LT_OK;
+    if (!err_sq || !h || !out_reject || !out_h) return fail(LT_ERR_INVALID_ARG, "null pointer");
+    DevBuf de, dh, orj, oh;
+    if ((rc = probe_upload(de, err_sq, n * 8)) || (rc = probe_upload(dh, h, n * 8)) || (rc = orj.alloc(n)) || (rc = oh.alloc(n * 8))) return rc;
+    const unsigned grid = (unsigned)((n + 255) / 256);
+    if (exact) k_dp45_controller_probe<true><<<grid, 256>>>((const double *)de.p, (const double *)dh.p, n, (uint8_t *)orj.p, (double *)oh.p);
+    else k_dp45_controller_probe<false><<<grid, 256>>>((const double *)de.p, (const double *)dh.p, n, (uint8_t *)orj.p, (double *)oh.p);
+    HIP_TRY(hipGetLastError());
+    if ((rc = probe_download(out_reject, orj, n)) || (rc = probe_download(out_h, oh, n * 8))) return rc;
+    return LT_OK;
+}
+
 extern "C" int lt_math32_probe(int which, uint32_t bits_lo, uint32_t bits_hi, const float *bases, int n_bases, uint64_t *out)
 {
     int rc = require_device();
     if (rc) return rc;
-    if (!out || which < 0 || which > 3 || bits_hi < bits_lo || bits_hi - bits_lo >= (1u << 30))
+    if (!out || which < 0 || which > 4 || bits_hi < bits_lo || bits_hi - bits_lo >= (1u << 30))
         return fail(LT_ERR_INVALID_ARG, "bad math probe arguments");
     if (which == 3 && (!bases || n_bases < 1 || n_bases > 16)) return fail(LT_ERR_INVALID_ARG, "the shift probe takes 1 to 16 base angles");
     const uint32_t n = bits_hi - bits_lo + 1;
@@ -1664,7 +1768,8 @@ extern "C" int lt_math32_probe(int which, uint32_t bits_lo, uint32_t bits_hi, co
         if (which == 0) k_math32_probe<0><<<grid, 256>>>(bits_lo, n, b, 0, pass, o);
         else if (which == 1) k_math32_probe<1><<<grid, 256>>>(bits_lo, n, b, 0, pass, o);
         else if (which == 2) k_math32_probe<2><<<grid, 256>>>(bits_lo, n, b, 0, pass, o);
-        else k_math32_probe<3><<<grid, 256>>>(bits_lo, n, b, n_bases, pass, o);
+        else if (which == 3) k_math32_probe<3><<<grid, 256>>>(bits_lo, n, b, n_bases, pass, o);
+        else k_math32_probe<4><<<grid, 256>>>(bits_lo, n, b, 0, pass, o);
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipMemcpy(out, d.p, sizeof(init), hipMemcpyDeviceToHost));
@@ -1681,6 +1786,7 @@ __global__ void k_math64_probe(int which, const double *__restrict__ x, int64_t 
     else if (which == 1) M<double>::sincos_small(x[i], u, v);
     else if (which == 2) u = M<double>::rcp_pos(x[i]);
     else if (which == 3) u = pow_m02(x[i]);
+    else if (which == 5) u = pow_minus_tenth((float)x[i]);
     else {
         float s, c;
         M<float>::sincos((float)x[i], s, c);
@@ -1693,7 +1799,7 @@ extern "C" int lt_math64_probe(int which, const double *x, int64_t n, double *ou
 {
     int rc = require_device();
     if (rc) return rc;
-    if (which < 0 || which > 4) return fail(LT_ERR_INVALID_ARG, "bad math probe arguments");
+    if (which < 0 || which > 5) return fail(LT_ERR_INVALID_ARG, "bad math probe arguments");
     if (n <= 0) return LT_OK;
     if (!x || !out) return fail(LT_ERR_INVALID_ARG, "null pointer");
     DevBuf dx, dout;

@@ -45,7 +45,8 @@ template <typename T> struct Rk4 {
 // ---------------------------------------------------------------------------------------------
 // z^(-1/10) for 1e-30 < z < 1e30 in float, without the transcendental unit (one v_exp / v_log costs
 // tens of issue slots in an FMA-dense stream): exponent bit trick (3 % off) + three
-// Newton steps y <- y (1 + (1 - z y^10) / 10), relative error ~2e-7.  It only scales the next step
+// Newton steps y <- y (1 + (1 - z y^10) / 10), relative error 2.09e-7 over every float32 of that range (measured,
+// tests/test_gpu_dp45_blocks.py; bound 2.5e-7); NaN at 0, at a denormal, at +inf.  It only scales the next step
 // size h, where 1e-7 is far below what the integration can notice.
 __device__ __forceinline__ float pow_minus_tenth(float z)
 {
@@ -61,7 +62,7 @@ __device__ __forceinline__ float pow_minus_tenth(float z)
 template <typename T> struct Dp45State {
     State5<T> y;
     T k1[5];       // FSAL: derivative at y
-    T s0, c0;      // sin / cos of y.th, carried like k1 (the stages rotate it: sincos_shift)
+    T s0, c0;      // sin / cos of y.th, carried like k1: the accepted candidate's own sincos (the stages rotate it: sincos_shift)
     T lam, h;
     uint32_t steps; // step attempts (accepted + rejected), metrics.py:454
 };
@@ -120,53 +121,90 @@ template <typename T, bool EXACT_CTRL = false> struct Dp45 {
         const T E1 = T(71.0 / 57600.0), E3 = T(-71.0 / 16695.0), E4 = T(71.0 / 1920.0), E5 = T(-17253.0 / 339200.0),
                 E6 = T(22.0 / 525.0), E7 = T(-1.0 / 40.0);
         const T y[5] = {s.y.r, s.y.th, s.y.ph, s.y.pr, s.y.pth};
+        // Every multiply-add of the stage sums, the candidate and the error norm is an explicit fma, in this order: left to
+        // the compiler's contraction, which product of a sum is fused depended on what else the kernel inlined -- advance()
+        // and a kernel that inlines attempt() alone differed in the last digits (tests/test_gpu_dp45_blocks.py).
+        const auto F = [](T a, T b, T c) { return M<T>::fma(a, b, c); };
         T k2[5], k3[5], k4[5], k5[5], k6[5], tmp[5];
         const T *k1 = s.k1;
         T ss, cc;
         const T th0 = y[1], s0 = s.s0, c0 = s.c0;
-        T d2, d3, d4, d5, d6, d7, r2, r3, r4, r5, r6;
+        T d2, d3, d4, d5, d6, r2, r3, r4, r5, r6;
 #pragma unroll
-        for (int i = 0; i < 5; ++i) tmp[i] = y[i] + h * A21 * k1[i];
+        for (int i = 0; i < 5; ++i) tmp[i] = F(h * A21, k1[i], y[i]);
         d2 = tmp[1] - th0; r2 = tmp[0];
         rhs5<CHECKED>(k, rc, tmp, th0, s0, c0, d2, k2, ss, cc);
 #pragma unroll
-        for (int i = 0; i < 5; ++i) tmp[i] = y[i] + h * (A31 * k1[i] + A32 * k2[i]);
+        for (int i = 0; i < 5; ++i) tmp[i] = F(h, F(A32, k2[i], A31 * k1[i]), y[i]);
         d3 = tmp[1] - th0; r3 = tmp[0];
         rhs5<CHECKED>(k, rc, tmp, th0, s0, c0, d3, k3, ss, cc);
 #pragma unroll
-        for (int i = 0; i < 5; ++i) tmp[i] = y[i] + h * (A41 * k1[i] + A42 * k2[i] + A43 * k3[i]);
+        for (int i = 0; i < 5; ++i) tmp[i] = F(h, F(A43, k3[i], F(A42, k2[i], A41 * k1[i])), y[i]);
         d4 = tmp[1] - th0; r4 = tmp[0];
         rhs5<CHECKED>(k, rc, tmp, th0, s0, c0, d4, k4, ss, cc);
 #pragma unroll
-        for (int i = 0; i < 5; ++i) tmp[i] = y[i] + h * (A51 * k1[i] + A52 * k2[i] + A53 * k3[i] + A54 * k4[i]);
+        for (int i = 0; i < 5; ++i) tmp[i] = F(h, F(A54, k4[i], F(A53, k3[i], F(A52, k2[i], A51 * k1[i]))), y[i]);
         d5 = tmp[1] - th0; r5 = tmp[0];
         rhs5<CHECKED>(k, rc, tmp, th0, s0, c0, d5, k5, ss, cc);
 #pragma unroll
         for (int i = 0; i < 5; ++i)
-            tmp[i] = y[i] + h * (A61 * k1[i] + A62 * k2[i] + A63 * k3[i] + A64 * k4[i] + A65 * k5[i]);
+            tmp[i] = F(h, F(A65, k5[i], F(A64, k4[i], F(A63, k3[i], F(A62, k2[i], A61 * k1[i])))), y[i]);
         d6 = tmp[1] - th0; r6 = tmp[0];
         rhs5<CHECKED>(k, rc, tmp, th0, s0, c0, d6, k6, ss, cc);
 #pragma unroll
-        for (int i = 0; i < 5; ++i) nxt[i] = y[i] + h * (B1 * k1[i] + B3 * k3[i] + B4 * k4[i] + B5 * k5[i] + B6 * k6[i]);
-        d7 = nxt[1] - th0;
-        rhs5<CHECKED>(k, rc, nxt, th0, s0, c0, d7, k7, sn, cn);
+        for (int i = 0; i < 5; ++i) nxt[i] = F(h, F(B6, k6[i], F(B5, k5[i], F(B4, k4[i], F(B3, k3[i], B1 * k1[i])))), y[i]);
+        // The candidate's own (sn, cn) is taken from its angle, not rotated from the base: it becomes the next step's base
+        // and k7 its k1.  Rotated, the pair carried an absolute error that grew from step to step (8 ... 13 u after 30 ... 380
+        // accepted steps), and where sin or cos is small -- a ray crossing the equator or passing the axis -- that put the
+        // carried k1 up to 26 000 units of 2^-53 S from the right-hand side at the carried state
+        // (tests/test_gpu_dp45_blocks.py).  The six stages still rotate from the base; the candidate's own turn no longer
+        // counts towards max_d, since nothing is rotated by it.
+        M<T>::sincos(nxt[1], sn, cn);
+        kerr_rhs_sc<T, CHECKED>(k, rc, nxt[0], sn, cn, nxt[3], nxt[4], k7[0], k7[1], k7[2], k7[3], k7[4]);
         if (!CHECKED) { // (min / max ignore a NaN stage value; it makes nxt non-finite in either variant)
             min_r = M<T>::min(M<T>::min(M<T>::min(r2, r3), M<T>::min(r4, r5)), M<T>::min(r6, nxt[0]));
             max_d = M<T>::max(M<T>::max(M<T>::max(M<T>::abs(d2), M<T>::abs(d3)), M<T>::max(M<T>::abs(d4), M<T>::abs(d5))),
-                              M<T>::max(M<T>::abs(d6), M<T>::abs(d7)));
+                              M<T>::abs(d6));
         }
         const T atol = rc.refine ? T(1e-10) : T(1e-8), rtol = rc.refine ? T(1e-8) : T(1e-6); // metrics.py:431-432
         err_sq = T(0);
 #pragma unroll
         for (int i = 0; i < 5; ++i) {
-            T ei = h * (E1 * k1[i] + E3 * k3[i] + E4 * k4[i] + E5 * k5[i] + E6 * k6[i] + E7 * k7[i]);
-            T sc = atol + rtol * M<T>::max(M<T>::abs(y[i]), M<T>::abs(nxt[i]));
+            T ei = h * F(E7, k7[i], F(E6, k6[i], F(E5, k5[i], F(E4, k4[i], F(E3, k3[i], E1 * k1[i])))));
+            T sc = F(rtol, M<T>::max(M<T>::abs(y[i]), M<T>::abs(nxt[i])), atol);
             // ei / sc with a float reciprocal (relative error 1e-7): the error norm only gates accept / reject
             // and scales h; a float64 division is ~12 instructions, five of them per attempt.  The exact controller
             // takes the float64 reciprocal (seed + two Newton steps, within an ulp).
             T q = EXACT_CTRL ? ei * (T)M<double>::rcp_pos((double)sc) : ei * (T)M<float>::rcp_pos((float)sc);
-            err_sq += q * q;
+            err_sq = F(q, q, err_sq);
         }
+    }
+
+    // The step-size controller of one attempt whose candidate is usable (metrics.py:514-522, :560-564): from the squared
+    // error norm and the step size tried, whether the attempt is rejected and the step size the loop goes on with
+    // (lt_dp45_controller_probe calls it on any err_sq).
+    static __device__ __forceinline__ void control(T err_sq, T h, bool &reject, T &h_next)
+    {
+        // err_norm = sqrt(err_sq / 5); err_norm^(-0.2) = (err_sq / 5)^(-0.1).
+        // What keeps a value that is not a positive finite number out of h, whatever err_sq is: `tiny` takes err_sq = 0 and
+        // everything whose float32 image would be a denormal (pow_minus_tenth is NaN there); max / min below return their
+        // other argument for a NaN `grow` (an infinite err_sq makes pow_minus_tenth NaN, a NaN err_sq makes either power
+        // NaN) -- as the reference's max(0.2, nan) = 0.2 and min(5.0, nan) = 5.0 do; and a NaN err_sq compares false with
+        // the reject threshold: accepted, h * 5, as in the reference (tests/test_gpu_dp45_blocks.py).
+        T grow;
+        bool tiny;
+        if (EXACT_CTRL) {
+            const double err_norm = __builtin_sqrt((double)err_sq * 0.2);          // metrics.py:514 (err_sq / 5 to an ulp)
+            grow = (T)(0.9 * pow_m02(err_norm));                                    // metrics.py:518, :564 (err_norm ** -0.2)
+            reject = err_norm > 1.0;
+            tiny = err_norm < 1e-10;
+        } else {
+            grow = T(0.9) * (T)pow_minus_tenth((float)(err_sq * T(0.2)));
+            reject = err_sq > T(5);
+            tiny = err_sq < T(5e-20);
+        }
+        if (reject) h_next = h * M<T>::max(T(0.2), grow);                           // metrics.py:516-522
+        else h_next = tiny ? h * T(5) : h * M<T>::min(T(5), grow);                  // err_norm < 1e-10, metrics.py:561-564
     }
 
     // One attempt of the loop body metrics.py:454-564.
@@ -199,21 +237,11 @@ template <typename T, bool EXACT_CTRL = false> struct Dp45 {
             s.h *= T(0.25);
             return s.h < h_min ? EV_INVALID : EV_RUNNING;
         }
-        // err_norm = sqrt(err_sq / 5); err_norm^(-0.2) = (err_sq / 5)^(-0.1)
-        T grow;
-        bool reject, tiny;
-        if (EXACT_CTRL) {
-            const double err_norm = __builtin_sqrt((double)err_sq * 0.2);          // metrics.py:514 (err_sq / 5 to an ulp)
-            grow = (T)(0.9 * pow_m02(err_norm));                                    // metrics.py:518, :564 (err_norm ** -0.2)
-            reject = err_norm > 1.0;
-            tiny = err_norm < 1e-10;
-        } else {
-            grow = T(0.9) * (T)pow_minus_tenth((float)(err_sq * T(0.2)));
-            reject = err_sq > T(5);
-            tiny = err_sq < T(5e-20);
-        }
+        bool reject;
+        T h_next;
+        control(err_sq, h, reject, h_next);
         if (reject) { // err_norm > 1: reject, metrics.py:516-522
-            s.h *= M<T>::max(T(0.2), grow);
+            s.h = h_next;
             return s.h < h_min ? EV_INVALID : EV_RUNNING;
         }
         // accept
@@ -236,7 +264,7 @@ template <typename T, bool EXACT_CTRL = false> struct Dp45 {
         for (int i = 0; i < 5; ++i) s.k1[i] = k7[i];
         s.s0 = sn; s.c0 = cn; // FSAL for the trigonometry too
         s.lam += h;
-        s.h = tiny ? h * T(5) : h * M<T>::min(T(5), grow); // err_norm < 1e-10, metrics.py:561-564
+        s.h = h_next;
         return EV_RUNNING;
     }
 };

@@ -1177,6 +1177,99 @@ __global__ void __launch_bounds__(64) k_kerr_step_probe(KerrConsts<T> k_in, cons
     if (out_cs) { out_cs[i * 2 + 0] = cs0; out_cs[i * 2 + 1] = cs1; }
 }
 
+// ---- the DP45 integrator block by block (lt_dp45_attempt_probe, lt_dp45_advance_probe, lt_dp45_controller_probe) ---------
+// A Dp45State from a row: the state, and the carried derivative and [sin, cos] -- computed as Dp45::start computes them
+// where the caller hands none.
+__device__ __forceinline__ Dp45State<double> dp45_probe_state(const KerrConsts<double> &k, const RayConsts<double> &rc,
+                                                              const double *__restrict__ states, const double *__restrict__ k1,
+                                                              const double *__restrict__ sc0, int64_t i)
+{
+    Dp45State<double> s;
+    s.y.r = states[i * 5 + 0]; s.y.th = states[i * 5 + 1]; s.y.ph = states[i * 5 + 2];
+    s.y.pr = states[i * 5 + 3]; s.y.pth = states[i * 5 + 4];
+    if (sc0) { s.s0 = sc0[i * 2 + 0]; s.c0 = sc0[i * 2 + 1]; }
+    else M<double>::sincos(s.y.th, s.s0, s.c0);
+    if (k1) {
+#pragma unroll
+        for (int j = 0; j < 5; ++j) s.k1[j] = k1[i * 5 + j];
+    } else kerr_rhs_sc(k, rc, s.y.r, s.s0, s.c0, s.y.pr, s.y.pth, s.k1[0], s.k1[1], s.k1[2], s.k1[3], s.k1[4]);
+    s.lam = 0.0; s.h = 0.0; s.steps = 0;
+    return s;
+}
+
+// Dp45<double, EXACT>::attempt<CHECKED> once per row.  One lane per row; lanes beyond n leave before any wave-wide test of
+// the checked form.
+template <bool EXACT, bool CHECKED>
+__global__ void __launch_bounds__(64) k_dp45_attempt_probe(KerrConsts<double> k_in, const double *__restrict__ states,
+                                                           const double *__restrict__ p_phi, const uint8_t *__restrict__ refine,
+                                                           const double *__restrict__ k1, const double *__restrict__ sc0,
+                                                           const double *__restrict__ hs, int64_t n, double *__restrict__ out_nxt,
+                                                           double *__restrict__ out_k7, double *__restrict__ out_sc,
+                                                           double *__restrict__ out_err_sq, double *__restrict__ out_min_r,
+                                                           double *__restrict__ out_max_d)
+{
+    const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    KerrConsts<double> k = k_in;
+    pin_consts(k);
+    const RayConsts<double> rc = make_ray_consts(k, p_phi[i], refine[i] != 0);
+    const Dp45State<double> s = dp45_probe_state(k, rc, states, k1, sc0, i);
+    double nxt[5], k7[5], sn, cn, err_sq, min_r = __builtin_nan(""), max_d = __builtin_nan("");
+    Dp45<double, EXACT>::template attempt<CHECKED>(k, rc, s, hs[i], nxt, k7, sn, cn, err_sq, min_r, max_d);
+#pragma unroll
+    for (int j = 0; j < 5; ++j) { out_nxt[i * 5 + j] = nxt[j]; out_k7[i * 5 + j] = k7[j]; }
+    out_sc[i * 2 + 0] = sn; out_sc[i * 2 + 1] = cn;
+    out_err_sq[i] = err_sq; out_min_r[i] = min_r; out_max_d[i] = max_d;
+}
+
+// Dp45<double, EXACT>::advance up to n_attempts times per row, until it returns something other than EV_RUNNING.  Blocks
+// of 64: rows 64 b ... 64 b + 63 share a wavefront.  out_misc (n,4): s0, c0, lam, h; out_int (n,3): event, steps, attempts.
+template <bool EXACT>
+__global__ void __launch_bounds__(64) k_dp45_advance_probe(KerrConsts<double> k_in, const double *__restrict__ states,
+                                                           const double *__restrict__ p_phi, const uint8_t *__restrict__ refine,
+                                                           const double *__restrict__ k1, const double *__restrict__ sc0,
+                                                           const double *__restrict__ hs, const double *__restrict__ lams,
+                                                           const uint32_t *__restrict__ steps, int64_t n, int n_attempts,
+                                                           double *__restrict__ out_states, double *__restrict__ out_k1,
+                                                           double *__restrict__ out_misc, int32_t *__restrict__ out_int)
+{
+    const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    KerrConsts<double> k = k_in;
+    pin_consts(k);
+    const RayConsts<double> rc = make_ray_consts(k, p_phi[i], refine[i] != 0);
+    Dp45State<double> s = dp45_probe_state(k, rc, states, k1, sc0, i);
+    s.h = hs[i];
+    s.lam = lams ? lams[i] : 0.0;
+    s.steps = steps ? steps[i] : 0u;
+    int ev = EV_RUNNING, made = 0;
+    while (made < n_attempts) {
+        ev = Dp45<double, EXACT>::advance(k, rc, s);
+        ++made;
+        if (ev != EV_RUNNING) break;
+    }
+    out_states[i * 5 + 0] = s.y.r; out_states[i * 5 + 1] = s.y.th; out_states[i * 5 + 2] = s.y.ph;
+    out_states[i * 5 + 3] = s.y.pr; out_states[i * 5 + 4] = s.y.pth;
+#pragma unroll
+    for (int j = 0; j < 5; ++j) out_k1[i * 5 + j] = s.k1[j];
+    out_misc[i * 4 + 0] = s.s0; out_misc[i * 4 + 1] = s.c0; out_misc[i * 4 + 2] = s.lam; out_misc[i * 4 + 3] = s.h;
+    out_int[i * 3 + 0] = ev; out_int[i * 3 + 1] = (int32_t)s.steps; out_int[i * 3 + 2] = made;
+}
+
+// Dp45<double, EXACT>::control on any (err_sq, h) (lt_dp45_controller_probe).
+template <bool EXACT>
+__global__ void k_dp45_controller_probe(const double *__restrict__ err_sq, const double *__restrict__ h, int64_t n,
+                                        uint8_t *__restrict__ out_reject, double *__restrict__ out_h)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    bool reject;
+    double h_next;
+    Dp45<double, EXACT>::control(err_sq[i], h[i], reject, h_next);
+    out_reject[i] = reject ? 1 : 0;
+    out_h[i] = h_next;
+}
+
 // ---- accuracy sweeps of the float32 math primitives (lt_math32_probe) ---------------------------------------------------
 // Every float32 with bit pattern bits_lo + i, i < n, through one primitive and through a float64 yardstick, compared on the
 // device.  A thread takes MATH32_ITEMS values and keeps the largest of each error measure with the argument that gave it.
@@ -1228,6 +1321,20 @@ __global__ void __launch_bounds__(256) k_math32_probe(uint32_t bits_lo, uint32_t
             math32_err(M<float>::rcp_pos(x), 1.0 / (double)x, ea, eu);
             take(0, ea, bits); take(2, eu, bits);
             ++count;
+        } else if constexpr (WHICH == 4) {
+            // pow_minus_tenth against the float64 pow: the relative error (measure 0); a result that is not a positive
+            // finite number is counted instead (MATH32_DIFF) and takes no part in the maximum
+            const float y = pow_minus_tenth(x);
+            if (!(y > 0.0f && y < __builtin_inff())) {
+                ++differing;
+                arg[MATH32_DIFF] = arg[MATH32_DIFF] < bits ? arg[MATH32_DIFF] : bits;
+            } else {
+                const double want = pow((double)x, -0.1);
+                double e = __builtin_fabs((double)y - want) / want;
+                e = e >= 0.0 ? e : __builtin_inf(); // a NaN must not hide
+                take(0, e, bits);
+            }
+            ++count;
         } else {
             double sdd, cdd;
             sincos_f64((double)x, sdd, cdd);
@@ -1261,7 +1368,7 @@ __global__ void __launch_bounds__(256) k_math32_probe(uint32_t bits_lo, uint32_t
     }
 #pragma unroll
     for (int m = 0; m < MATH32_MEASURES; ++m) {
-        if (WHICH == 3 && m == MATH32_DIFF) {
+        if ((WHICH == 3 || WHICH == 4) && m == MATH32_DIFF) {
             if (pass == 0 && differing) atomicMin(&out[2 + 2 * m], arg[m]);
             continue;
         }

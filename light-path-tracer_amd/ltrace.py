@@ -158,6 +158,9 @@ SIGNATURES = {
     "lt_kerr_rhs_form_probe": (C.c_int, [C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
     "lt_kerr_step_probe": (C.c_int, [C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
                                      C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lt_dp45_attempt_probe": (C.c_int, [C.c_double] * 4 + [C.c_void_p] * 6 + [C.c_int64, C.c_int, C.c_int] + [C.c_void_p] * 6),
+    "lt_dp45_advance_probe": (C.c_int, [C.c_double] * 4 + [C.c_void_p] * 8 + [C.c_int64, C.c_int, C.c_int] + [C.c_void_p] * 4),
+    "lt_dp45_controller_probe": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "lt_math32_probe": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p]),
     "lt_math64_probe": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
     "lt_set_eq_streak": (C.c_int, [C.c_int]),
@@ -521,8 +524,56 @@ def kerr_step_probe(M, a, states, p_phi, h, refine=None, precision=32, form="che
     return dict(states=out, min_r=mr, max_d=md, cs=cs)
 
 
-MATH32_WHICH = {"sincos": 0, "sincos_small": 1, "rcp_pos": 2, "sincos_shift": 3}
-MATH64_WHICH = {"sincos": 0, "sincos_small": 1, "rcp_pos": 2, "pow_m02": 3, "sincos_f32": 4}
+def _dp45_rows(states, p_phi, h, refine, k1, sc0):
+    st = np.ascontiguousarray(states, dtype=np.float64).reshape(-1, 5)
+    n = st.shape[0]
+    pp = np.ascontiguousarray(np.broadcast_to(np.asarray(p_phi, dtype=np.float64), (n,)))
+    hh = np.ascontiguousarray(np.broadcast_to(np.asarray(h, dtype=np.float64), (n,)))
+    rf = np.zeros(n, dtype=np.uint8) if refine is None else np.ascontiguousarray(np.broadcast_to(np.asarray(refine), (n,))).astype(np.uint8)
+    kk = None if k1 is None else np.ascontiguousarray(k1, dtype=np.float64).reshape(n, 5)
+    sc = None if sc0 is None else np.ascontiguousarray(sc0, dtype=np.float64).reshape(n, 2)
+    return st, n, pp, hh, rf, kk, sc
+
+
+def dp45_attempt_probe(M, a, states, p_phi, h, refine=None, k1=None, sc0=None, exact=True, checked=False, r_obs=50.0,
+                       lambda_max=5000.0):
+    """One DP45 step attempt per state in the checked or the branch-free form (lt_dp45_attempt_probe), float64.
+    -> dict(next (n,5), k7 (n,5), sc (n,2) [sin, cos] of the candidate's polar angle, err_sq, min_r, max_d (n,))."""
+    st, n, pp, hh, rf, kk, sc = _dp45_rows(states, p_phi, h, refine, k1, sc0)
+    nxt, k7, osc = np.empty_like(st), np.empty_like(st), np.empty((n, 2))
+    err, mr, md = np.empty(n), np.empty(n), np.empty(n)
+    _check(load().lt_dp45_attempt_probe(M, a, r_obs, lambda_max, _np_ptr(st), _np_ptr(pp), _np_ptr(rf), _np_ptr(kk), _np_ptr(sc),
+                                        _np_ptr(hh), n, int(bool(exact)), int(bool(checked)), _np_ptr(nxt), _np_ptr(k7), _np_ptr(osc),
+                                        _np_ptr(err), _np_ptr(mr), _np_ptr(md)))
+    return dict(next=nxt, k7=k7, sc=osc, err_sq=err, min_r=mr, max_d=md)
+
+
+def dp45_advance_probe(M, a, states, p_phi, h, refine=None, k1=None, sc0=None, lam=None, steps=None, exact=True, n_attempts=1,
+                       r_obs=50.0, lambda_max=5000.0):
+    """Up to n_attempts iterations of the DP45 loop body per state (lt_dp45_advance_probe); rows 64 b ... 64 b + 63 share a
+    wavefront.  -> dict(event, steps, attempts (n,) int32, state (n,5), k1 (n,5), sc (n,2), lam, h (n,))."""
+    st, n, pp, hh, rf, kk, sc = _dp45_rows(states, p_phi, h, refine, k1, sc0)
+    ll = None if lam is None else np.ascontiguousarray(np.broadcast_to(np.asarray(lam, dtype=np.float64), (n,)))
+    ss = None if steps is None else np.ascontiguousarray(np.broadcast_to(np.asarray(steps), (n,))).astype(np.uint32)
+    out, ok1, misc, oi = np.empty_like(st), np.empty_like(st), np.empty((n, 4)), np.empty((n, 3), dtype=np.int32)
+    _check(load().lt_dp45_advance_probe(M, a, r_obs, lambda_max, _np_ptr(st), _np_ptr(pp), _np_ptr(rf), _np_ptr(kk), _np_ptr(sc),
+                                        _np_ptr(hh), _np_ptr(ll), _np_ptr(ss), n, int(bool(exact)), int(n_attempts), _np_ptr(out),
+                                        _np_ptr(ok1), _np_ptr(misc), _np_ptr(oi)))
+    return dict(event=oi[:, 0].copy(), steps=oi[:, 1].copy(), attempts=oi[:, 2].copy(), state=out, k1=ok1, sc=misc[:, :2].copy(),
+                lam=misc[:, 2].copy(), h=misc[:, 3].copy())
+
+
+def dp45_controller_probe(err_sq, h, exact=True):
+    """The DP45 step-size controller on any (err_sq, h) (lt_dp45_controller_probe) -> (reject (n,) bool, h_next (n,))."""
+    e = np.ascontiguousarray(err_sq, dtype=np.float64).ravel()
+    hh = np.ascontiguousarray(np.broadcast_to(np.asarray(h, dtype=np.float64), e.shape))
+    rj, out = np.empty(e.size, dtype=np.uint8), np.empty(e.size)
+    _check(load().lt_dp45_controller_probe(int(bool(exact)), _np_ptr(e), _np_ptr(hh), e.size, _np_ptr(rj), _np_ptr(out)))
+    return rj.astype(bool), out
+
+
+MATH32_WHICH = {"sincos": 0, "sincos_small": 1, "rcp_pos": 2, "sincos_shift": 3, "pow_minus_tenth": 4}
+MATH64_WHICH = {"sincos": 0, "sincos_small": 1, "rcp_pos": 2, "pow_m02": 3, "sincos_f32": 4, "pow_minus_tenth_f32": 5}
 
 
 def math32_probe(which, bits_lo, bits_hi, bases=None):

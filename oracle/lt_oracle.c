@@ -527,6 +527,79 @@ static int disk_end(const disk_hook *d, real *fa_out, int64_t *nh_out)
     return 2;
 }
 
+/* What the reference's pure-Python min / max return where the step controller hands them 0.9 err_norm^-0.2 as their
+ * SECOND argument (metrics.py:518, :564): the first argument unless the second compares beyond it -- so a NaN second
+ * argument gives the first (max(0.2, nan) = 0.2, min(5.0, nan) = 5.0).  rmax / rmin above return the NaN. */
+static real py_max(real a, real b) { return b > a ? b : a; }
+static real py_min(real a, real b) { return b < a ? b : a; }
+
+enum { DP_BAD = 0, DP_REJECT = 1, DP_ACCEPT = 2 };
+
+/* The decision of one attempt whose candidate is usable (metrics.py:516-522, :560-564): DP_REJECT or DP_ACCEPT from the
+ * error norm, and the step size the loop goes on with. */
+static int dp45_decide(real err_norm, real h, real *h_next)
+{
+    if (err_norm > R(1.0)) {
+        real factor = py_max(R(0.2), R(0.9) * M_POW(err_norm, R(-0.2)));
+        *h_next = h * factor;
+        return DP_REJECT;
+    }
+    if (err_norm < R(1e-10)) *h_next = h * R(5.0);
+    else *h_next = h * py_min(R(5.0), R(0.9) * M_POW(err_norm, R(-0.2)));
+    return DP_ACCEPT;
+}
+
+/* One attempt of the DP45 loop (metrics.py:464-522, :560-564): the six stages from (state, k1) with step h, the candidate
+ * next_state with its derivative k7, the finiteness test, the error norm and the decision.  Returns DP_BAD (candidate
+ * non-finite or r <= 0: *err_norm untouched), DP_REJECT or DP_ACCEPT; *h_next is the step size the loop goes on with.
+ * stage_r, may be NULL: the radii the right-hand sides k2..k7 were evaluated at. */
+static int dp45_attempt(const real *state, const real *k1, real p_t, real p_phi, real M, real a, real r_plus, real h,
+                        real atol, real rtol, real *next_state, real *k7, real *err_norm_out, real *h_next, real *stage_r)
+{
+    real k2[5], k3[5], k4[5], k5[5], k6[5], tmp[5];
+    for (int i = 0; i < 5; ++i) tmp[i] = state[i] + h * DP_A21 * k1[i];
+    if (stage_r) stage_r[0] = tmp[0];
+    kerr_rhs(tmp, p_t, p_phi, M, a, r_plus, k2);
+    for (int i = 0; i < 5; ++i) tmp[i] = state[i] + h * (DP_A31 * k1[i] + DP_A32 * k2[i]);
+    if (stage_r) stage_r[1] = tmp[0];
+    kerr_rhs(tmp, p_t, p_phi, M, a, r_plus, k3);
+    for (int i = 0; i < 5; ++i)
+        tmp[i] = state[i] + h * (DP_A41 * k1[i] + DP_A42 * k2[i] + DP_A43 * k3[i]);
+    if (stage_r) stage_r[2] = tmp[0];
+    kerr_rhs(tmp, p_t, p_phi, M, a, r_plus, k4);
+    for (int i = 0; i < 5; ++i)
+        tmp[i] = state[i] + h * (DP_A51 * k1[i] + DP_A52 * k2[i]
+                                 + DP_A53 * k3[i] + DP_A54 * k4[i]);
+    if (stage_r) stage_r[3] = tmp[0];
+    kerr_rhs(tmp, p_t, p_phi, M, a, r_plus, k5);
+    for (int i = 0; i < 5; ++i)
+        tmp[i] = state[i] + h * (DP_A61 * k1[i] + DP_A62 * k2[i] + DP_A63 * k3[i]
+                                 + DP_A64 * k4[i] + DP_A65 * k5[i]);
+    if (stage_r) stage_r[4] = tmp[0];
+    kerr_rhs(tmp, p_t, p_phi, M, a, r_plus, k6);
+    for (int i = 0; i < 5; ++i)
+        next_state[i] = state[i] + h * (DP_B1 * k1[i] + DP_B3 * k3[i] + DP_B4 * k4[i]
+                                        + DP_B5 * k5[i] + DP_B6 * k6[i]);
+    if (stage_r) stage_r[5] = next_state[0];
+    kerr_rhs(next_state, p_t, p_phi, M, a, r_plus, k7);
+    if (!all_finite5(next_state) || next_state[0] <= R(0.0)) {
+        *h_next = h * R(0.25);
+        return DP_BAD;
+    }
+    real err_sq = R(0.0);
+    for (int idx = 0; idx < 5; ++idx) {
+        real ei = h * (DP_E1 * k1[idx] + DP_E3 * k3[idx]
+                       + DP_E4 * k4[idx] + DP_E5 * k5[idx]
+                       + DP_E6 * k6[idx] + DP_E7 * k7[idx]);
+        real sc = atol + rtol * rmax(M_FABS(state[idx]), M_FABS(next_state[idx]));
+        real q = ei / sc;
+        err_sq += q * q;
+    }
+    real err_norm = M_SQRT(err_sq / R(5.0));
+    *err_norm_out = err_norm;
+    return dp45_decide(err_norm, h, h_next);
+}
+
 /* metrics.py:419-567, production integrator (DP45, FSAL) */
 static int kerr_trace_dp45_h(real M, real a, real r_plus, real r_obs, real alpha, real theta,
                              real theta_obs, real lambda_max, real h_max, int axis_refine,
@@ -541,7 +614,7 @@ static int kerr_trace_dp45_h(real M, real a, real r_plus, real r_obs, real alpha
     real r_escape = r_obs * R(2.0);
     real atol = axis_refine ? R(1e-10) : R(1e-8);
     real rtol = axis_refine ? R(1e-8) : R(1e-6);
-    real k1[5], k2[5], k3[5], k4[5], k5[5], k6[5], k7[5], tmp[5], next_state[5];
+    real k1[5], k7[5], next_state[5];
     kerr_rhs(state, p_t, p_phi, M, a, r_plus, k1);
     real lam = R(0.0);
     real h = rmax(R(1.0), R(0.01) * r_obs);
@@ -553,43 +626,10 @@ static int kerr_trace_dp45_h(real M, real a, real r_plus, real r_obs, real alpha
         real remaining = lambda_max - lam;
         if (h > remaining) h = remaining;
         if (h <= R(0.0)) break;
-        for (int i = 0; i < 5; ++i) tmp[i] = state[i] + h * DP_A21 * k1[i];
-        kerr_rhs(tmp, p_t, p_phi, M, a, r_plus, k2);
-        for (int i = 0; i < 5; ++i) tmp[i] = state[i] + h * (DP_A31 * k1[i] + DP_A32 * k2[i]);
-        kerr_rhs(tmp, p_t, p_phi, M, a, r_plus, k3);
-        for (int i = 0; i < 5; ++i)
-            tmp[i] = state[i] + h * (DP_A41 * k1[i] + DP_A42 * k2[i] + DP_A43 * k3[i]);
-        kerr_rhs(tmp, p_t, p_phi, M, a, r_plus, k4);
-        for (int i = 0; i < 5; ++i)
-            tmp[i] = state[i] + h * (DP_A51 * k1[i] + DP_A52 * k2[i]
-                                     + DP_A53 * k3[i] + DP_A54 * k4[i]);
-        kerr_rhs(tmp, p_t, p_phi, M, a, r_plus, k5);
-        for (int i = 0; i < 5; ++i)
-            tmp[i] = state[i] + h * (DP_A61 * k1[i] + DP_A62 * k2[i] + DP_A63 * k3[i]
-                                     + DP_A64 * k4[i] + DP_A65 * k5[i]);
-        kerr_rhs(tmp, p_t, p_phi, M, a, r_plus, k6);
-        for (int i = 0; i < 5; ++i)
-            next_state[i] = state[i] + h * (DP_B1 * k1[i] + DP_B3 * k3[i] + DP_B4 * k4[i]
-                                            + DP_B5 * k5[i] + DP_B6 * k6[i]);
-        kerr_rhs(next_state, p_t, p_phi, M, a, r_plus, k7);
-        if (!all_finite5(next_state) || next_state[0] <= R(0.0)) {
-            h *= R(0.25);
-            if (h < h_min) return 0;
-            continue;
-        }
-        real err_sq = R(0.0);
-        for (int idx = 0; idx < 5; ++idx) {
-            real ei = h * (DP_E1 * k1[idx] + DP_E3 * k3[idx]
-                           + DP_E4 * k4[idx] + DP_E5 * k5[idx]
-                           + DP_E6 * k6[idx] + DP_E7 * k7[idx]);
-            real sc = atol + rtol * rmax(M_FABS(state[idx]), M_FABS(next_state[idx]));
-            real q = ei / sc;
-            err_sq += q * q;
-        }
-        real err_norm = M_SQRT(err_sq / R(5.0));
-        if (err_norm > R(1.0)) {
-            real factor = rmax(R(0.2), R(0.9) * M_POW(err_norm, R(-0.2)));
-            h *= factor;
+        real err_norm, h_next;
+        if (dp45_attempt(state, k1, p_t, p_phi, M, a, r_plus, h, atol, rtol, next_state, k7, &err_norm, &h_next, NULL)
+            != DP_ACCEPT) { /* candidate unusable, or rejected */
+            h = h_next;
             if (h < h_min) return 0;
             continue;
         }
@@ -619,8 +659,7 @@ static int kerr_trace_dp45_h(real M, real a, real r_plus, real r_obs, real alpha
         for (int i = 0; i < 5; ++i) k1[i] = k7[i];
         lam += h;
         if (!all_finite5(state)) return 0;
-        if (err_norm < R(1e-10)) h *= R(5.0);
-        else h *= rmin(R(5.0), R(0.9) * M_POW(err_norm, R(-0.2)));
+        h = h_next;
     }
     return kerr_extract_angle(state, p_t, p_phi, M, a, r_capture, event_status, fa_out, nh_out);
 }
@@ -729,6 +768,78 @@ void LTO_NAME(lto_rk4_step_kerr)(const real *states, const real *p_phi, const re
             stage_r[4 * i + 3] = tmp[0];
         }
     }
+}
+
+/* One attempt of the DP45 loop (metrics.py:454-564) from each of n rows, by the function the tracer itself runs
+ * (dp45_attempt): states (n,5); k1 (n,5) the carried derivative, NULL: the right-hand side at the state; p_phi, h (n);
+ * lam (n), NULL: 0; axis_refine (n), NULL: 0; p_t = -1.
+ *   next_state, k7 (n,5): the candidate and its derivative;  err_norm (n): NaN where the candidate was unusable;
+ *   stage_r (n,6): the radii k2..k7 were evaluated at;  h_next (n): the step size the loop goes on with (the clamped h
+ *   where the row ended);  state_out (n,5): the state the row is left in (the interpolated one at a capture / escape);
+ *   outcome (n,2): [0] the row's event in the kernels' codes (4 goes on, 2 lam >= lambda_max or no step left, 0 step size
+ *   under 1e-12, -1 captured, 1 escaped), [1] -1 no attempt made, else DP_BAD 0 / DP_REJECT 1 / DP_ACCEPT 2.
+ * Every output but outcome may be NULL. */
+void LTO_NAME(lto_dp45_attempt)(const real *states, const real *k1_in, const real *p_phi, const real *hs, int64_t n, real M,
+                                real a, real r_plus, real r_obs, real lambda_max, const real *lams,
+                                const uint8_t *axis_refine, real *next_out, real *k7_out, real *err_out, int32_t *outcome,
+                                real *h_next_out, real *state_out, real *stage_r)
+{
+    const real r_capture = r_plus * R(1.01), r_escape = r_obs * R(2.0), h_min = R(1e-12);
+    for (int64_t i = 0; i < n; ++i) {
+        const real *state = states + 5 * i;
+        const int refine = axis_refine && axis_refine[i];
+        const real atol = refine ? R(1e-10) : R(1e-8), rtol = refine ? R(1e-8) : R(1e-6);
+        real k1[5], k7[5], nxt[5], out[5], sr[6], err_norm = LTO_NAN, h = hs[i], h_next;
+        const real lam = lams ? lams[i] : R(0.0);
+        int event = 4, decision = -1;
+        for (int j = 0; j < 5; ++j) { out[j] = state[j]; nxt[j] = k7[j] = LTO_NAN; }
+        for (int j = 0; j < 6; ++j) sr[j] = LTO_NAN;
+        if (k1_in) for (int j = 0; j < 5; ++j) k1[j] = k1_in[5 * i + j];
+        else kerr_rhs(state, R(-1.0), p_phi[i], M, a, r_plus, k1);
+        if (lam >= lambda_max) event = 2;
+        else {
+            real remaining = lambda_max - lam;
+            if (h > remaining) h = remaining;
+            if (h <= R(0.0)) event = 2;
+        }
+        h_next = h;
+        if (event == 4) {
+            decision = dp45_attempt(state, k1, R(-1.0), p_phi[i], M, a, r_plus, h, atol, rtol, nxt, k7, &err_norm, &h_next, sr);
+            if (decision != DP_ACCEPT) {
+                if (h_next < h_min) event = 0;
+            } else {
+                real r_prev = state[0], r_next = nxt[0];
+                int cap = r_prev > r_capture && r_next <= r_capture;
+                int esc = !cap && r_prev < r_escape && r_next >= r_escape;
+                if (cap || esc) {
+                    real target = cap ? r_capture : r_escape, denom = r_next - r_prev;
+                    real frac = (denom == R(0.0)) ? R(1.0) : (target - r_prev) / denom;
+                    frac = clip_scalar(frac, R(0.0), R(1.0));
+                    for (int j = 0; j < 5; ++j) out[j] = state[j] + frac * (nxt[j] - state[j]);
+                    event = cap ? -1 : 1;
+                    h_next = h;
+                } else {
+                    for (int j = 0; j < 5; ++j) out[j] = nxt[j];
+                    if (!all_finite5(out)) event = 0;
+                }
+            }
+        }
+        for (int j = 0; j < 5; ++j) {
+            if (next_out) next_out[5 * i + j] = nxt[j];
+            if (k7_out) k7_out[5 * i + j] = k7[j];
+            if (state_out) state_out[5 * i + j] = out[j];
+        }
+        if (stage_r) for (int j = 0; j < 6; ++j) stage_r[6 * i + j] = sr[j];
+        if (err_out) err_out[i] = err_norm;
+        if (h_next_out) h_next_out[i] = h_next;
+        outcome[2 * i] = event; outcome[2 * i + 1] = decision;
+    }
+}
+
+/* The decision alone, on any error norm (a NaN included): decision (n) DP_REJECT 1 / DP_ACCEPT 2, h_next (n). */
+void LTO_NAME(lto_dp45_decide)(const real *err_norm, const real *h, int64_t n, int32_t *decision, real *h_next)
+{
+    for (int64_t i = 0; i < n; ++i) decision[i] = dp45_decide(err_norm[i], h[i], h_next + i);
 }
 
 /* lto_kerr_rhs of n states (n,5), each with its own p_phi; p_t = -1. */

@@ -178,6 +178,51 @@ def rk4_step_kerr(states, p_phi, h, M, a, f32=False):
     return out, sr
 
 
+DP45_DECISIONS = {-1: "none", 0: "bad", 1: "reject", 2: "accept"}
+
+
+def dp45_attempt(states, p_phi, h, M, a, r_obs=50.0, lambda_max=5000.0, k1=None, lam=None, axis_refine=None, f32=False):
+    """One attempt of the DP45 loop (metrics.py:454-564, p_t = -1) from each of n rows, by the function the oracle's tracer
+    itself runs (lto_dp45_attempt).  k1 (n,5): the carried derivative (None: the right-hand side at the state); lam (n).
+    -> dict(next (n,5), k7 (n,5), err_norm (n,) NaN where the candidate was unusable, event (n,) in the kernels' codes
+    (4 goes on, 2 out of range, 0 invalid, -1 captured, 1 escaped), decision (n,) (-1 none, 0 bad, 1 reject, 2 accept),
+    h_next (n,), state (n,5), stage_r (n,6)), float64 or float32 throughout."""
+    dt, pt, ct = _real(f32)
+    st = np.ascontiguousarray(states, dtype=dt).reshape(-1, 5)
+    n = st.shape[0]
+    pp = np.ascontiguousarray(np.broadcast_to(np.asarray(p_phi, dtype=dt), (n,)))
+    hh = np.ascontiguousarray(np.broadcast_to(np.asarray(h, dtype=dt), (n,)))
+    kk = None if k1 is None else np.ascontiguousarray(k1, dtype=dt).reshape(n, 5)
+    ll = None if lam is None else np.ascontiguousarray(np.broadcast_to(np.asarray(lam, dtype=dt), (n,)))
+    rf = None if axis_refine is None else np.ascontiguousarray(np.broadcast_to(np.asarray(axis_refine), (n,))).astype(np.uint8)
+    nxt, k7, so = np.empty_like(st), np.empty_like(st), np.empty_like(st)
+    err, hn, sr = np.empty(n, dtype=dt), np.empty(n, dtype=dt), np.empty((n, 6), dtype=dt)
+    oc = np.empty((n, 2), dtype=np.int32)
+    L = lib32() if f32 else lib()
+    fn = L.lto_dp45_attempt_f32 if f32 else L.lto_dp45_attempt
+    fn.argtypes = [pt, pt, pt, pt, C.c_int64, ct, ct, ct, ct, ct, pt, C.POINTER(C.c_uint8), pt, pt, pt, C.POINTER(C.c_int32), pt, pt, pt]
+    fn.restype = None
+    fn(_ptr(st, pt), _ptr(kk, pt), _ptr(pp, pt), _ptr(hh, pt), n, M, a, M + np.sqrt(M * M - a * a), r_obs, lambda_max,
+       _ptr(ll, pt), _ptr(rf, C.POINTER(C.c_uint8)), _ptr(nxt, pt), _ptr(k7, pt), _ptr(err, pt), _ptr(oc, C.POINTER(C.c_int32)),
+       _ptr(hn, pt), _ptr(so, pt), _ptr(sr, pt))
+    return dict(next=nxt, k7=k7, err_norm=err, event=oc[:, 0].copy(), decision=oc[:, 1].copy(), h_next=hn, state=so, stage_r=sr)
+
+
+def dp45_decide(err_norm, h, f32=False):
+    """The accept / reject decision and the next step size of the oracle's DP45 loop on any error norm (lto_dp45_decide)
+    -> (decision (n,) 1 reject / 2 accept, h_next (n,))."""
+    dt, pt, _ = _real(f32)
+    e = np.ascontiguousarray(err_norm, dtype=dt).ravel()
+    hh = np.ascontiguousarray(np.broadcast_to(np.asarray(h, dtype=dt), e.shape))
+    dec, out = np.empty(e.size, dtype=np.int32), np.empty(e.size, dtype=dt)
+    L = lib32() if f32 else lib()
+    fn = L.lto_dp45_decide_f32 if f32 else L.lto_dp45_decide
+    fn.argtypes = [pt, pt, C.c_int64, C.POINTER(C.c_int32), pt]
+    fn.restype = None
+    fn(_ptr(e, pt), _ptr(hh, pt), e.size, _ptr(dec, C.POINTER(C.c_int32)), _ptr(out, pt))
+    return dec, out
+
+
 def kerr_ic(M, a, r_obs, alpha, theta, theta_obs):
     st = np.zeros(5)
     pt = C.c_double()

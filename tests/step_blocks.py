@@ -203,9 +203,10 @@ def inside_cut_class(a, n, seed=0):
 STEP_CLASSES = ("far", "mid", "band", "near", "pole_approach")
 
 
-def step_class(name, a, n, seed=0):
+def step_class(name, a, n, seed=0, rounded=True):
     """-> (states (n,5), L (n,), h, refine) with h as the tracer's step-size rule gives it (metrics.py:597-611); None if
-    the class does not exist at this spin.  Momenta of the size a ray from a camera at r ~ 50 has."""
+    the class does not exist at this spin.  Momenta of the size a ray from a camera at r ~ 50 has.  rounded=False: the
+    values as drawn, at float64 precision (tests/dp45_blocks.py), not rounded to float32."""
     rng = np.random.default_rng([seed, 200 + (STEP_CLASSES + ("eq_band",)).index(name), int(round(a * 1000))])
     rp = r_plus(a)
     th = (0.35, np.pi - 0.35)
@@ -226,7 +227,7 @@ def step_class(name, a, n, seed=0):
         (st, L), h, refine = _states(rng, n, 8.2 * rp, 600.0, 0.81, 2.33), 1.0, 0
     else:
         raise KeyError(name)
-    return f32(st), f32(L), h, refine
+    return (f32(st), f32(L), h, refine) if rounded else (st, L, h, refine)
 
 
 def step_unit(a, states, L, h, ref_step, u=U32):
@@ -250,7 +251,7 @@ def _step_parts(a, states, L, h, ref_step, u):
     return y1, A + u * hS, stage_r, stiff
 
 
-def fallback_class(a, n, seed=0):
+def fallback_class(a, n, seed=0, rounded=True):
     """States whose step fails the branch-free step's validity test.  First half: just outside r_cut and falling, so that
     later stages are evaluated at or inside it (h = 0.05); second half: a polar momentum that turns the stage angles by
     more than 0.25 rad (h = 0.5).  -> (states, L, h (n,))"""
@@ -262,7 +263,7 @@ def fallback_class(a, n, seed=0):
     st[m:, 1] = rng.uniform(0.5, np.pi - 0.5, n - m)
     st[m:, 4] = rng.choice([-1.0, 1.0], n - m) * rng.uniform(20.0, 60.0, n - m)
     h = np.where(np.arange(n) < m, 0.05, 0.5)
-    return f32(st), f32(L), h
+    return (f32(st), f32(L), h) if rounded else (st, L, h)
 
 
 def fallback_unit(a, states, L, h, ref_step, u=U32):
