@@ -243,6 +243,44 @@ int lt_dp45_advance_probe(double M, double a, double r_obs, double lambda_max, c
  * rejected, out_h (n) the step size the loop goes on with (metrics.py:514-522, :560-564). */
 int lt_dp45_controller_probe(int exact, const double *err_sq, const double *h, int64_t n, uint8_t *out_reject, double *out_h);
 
+/* ---- a ray's two ends and the RK4 loop body (parity probes; they run the kernels and functions the product runs) ---- */
+
+/* The ray records of k_prologue_arrays as stored, for kind LT_METRIC_KERR (alphas, thetas (n)) or LT_METRIC_SCHWARZSCHILD
+ * (alphas; thetas may be NULL), refines (n) or NULL.  out_records (n_q,4) float64, n_q = n rounded up to a multiple of 64:
+ * the record of precision 32 / 64 widened -- p_r, p_theta, p_phi, flags (Kerr) or w0, 0, 0, flags (Schwarzschild); flags
+ * 1 the ray is valid, 2 axis-refine, 4 a padding row (every row from n on). */
+int lt_ic_probe(int kind, double M, double a, double r_obs, double theta_obs, const double *alphas, const double *thetas,
+                const uint8_t *refines, int64_t n, int precision, double *out_records);
+
+/* Up to n_iters iterations of the fixed-step RK4 loop body (metrics.py:596-655, kerr_rk4_advance) per row, ending at the
+ * first that ends the ray.  states (n,5), p_phi (n), refine (n); lam (n), h_retry (n) (> 0: the halved step size a failed
+ * attempt left for the next iteration) and steps (n), NULL: zeros; h_max the base step.  One iteration is one step ATTEMPT:
+ * a reference iteration whose step is halved k times takes k + 1 of them, and the row stands at a reference iteration
+ * boundary where out h_retry == 0.  Rows 64 b ... 64 b + 63 share a wavefront.  out_states (n,5); out_misc (n,2): lam,
+ * h_retry; out_int (n,3): the event (4 still running, 2 out of range, 0 invalid, -1 captured, 1 escaped), steps (attempts
+ * so far), iterations made by this call. */
+int lt_rk4_advance_probe(double M, double a, double r_obs, double lambda_max, double h_max, const double *states,
+                         const double *p_phi, const uint8_t *refine, const double *lam, const double *h_retry,
+                         const uint32_t *steps, int64_t n, int precision, int n_iters, double *out_states, double *out_misc,
+                         int32_t *out_int);
+
+/* The Schwarzschild integrator (metrics.py:66-117, schw_trace) from a supplied start (u0, w0) (n) instead of the observer's;
+ * M, r_obs, phi_max and h_max become the kernel's constants exactly as for lt_trace_batch_schw (one step: phi_max = h_max).
+ * out (n,3): u, w, phi_last (the part of the last, shorter or interrupted, step used); out_int (n,3): the event (-1, 1, or
+ * 2 at the range end), steps taken (the ending one included: rhs_evals = 4 steps), full steps (phi_f = full steps * h_max +
+ * phi_last).  out_n_full, out_h_last (may be NULL): the host's step plan for the call -- n_full steps of h_max, then one of
+ * h_last if h_last > 0; they are set for n = 0 too, for which no device is needed. */
+int lt_schw_trace_probe(double M, double r_obs, double phi_max, double h_max, const double *u0, const double *w0, int64_t n,
+                        int precision, double *out, int32_t *out_int, uint32_t *out_n_full, double *out_h_last);
+
+/* k_epilogue_arrays on final records in the integrate kernels' own layout, fin0, fin1 (n,4) float64, rounded to float32 on
+ * the host first for precision 32:  Kerr fin0 = (r, theta, phi, p_r), fin1 = (p_theta, p_phi, event, steps);  Schwarzschild
+ * fin0 = (u, w, phi_last, full steps), fin1 = (0, 0, event, steps), h_schw the step size the full steps are multiplied by.
+ * event: -1 captured, 1 escaped, 2 range end, 0 invalid, 3 padding.  integrator sets the evaluation count per step
+ * (LT_INTEGRATOR_*).  out_fa (n) NaN unless escaped, out_w (n), out_status (n), out_evals (n). */
+int lt_extract_probe(int kind, double M, double a, double h_schw, int integrator, const double *fin0, const double *fin1,
+                     int64_t n, int precision, double *out_fa, int64_t *out_w, int8_t *out_status, uint32_t *out_evals);
+
 /* Accuracy sweep of a float32 math primitive of the integrators: every float32 with bit pattern in [bits_lo, bits_hi]
  * (at most 2^30 of them) goes through the primitive and through a float64 yardstick, compared on the device.
  *   which 0: sincos(x)        1: the small-angle sincos(d), |d| <= 0.25       (yardstick: the float64 sincos)
@@ -265,7 +303,8 @@ int lt_math32_probe(int which, uint32_t bits_lo, uint32_t bits_hi, const float *
  * x (n), out (n,2).  which 0: sincos -> [sin, cos]; 1: small-angle sincos (|x| <= 0.25) -> [sin, cos]; 2: reciprocal of a
  * positive normal x -> [1/x, 0]; 3: x^(-1/5) of the step controllers, clamped outside [1e-6, 1e4] -> [value, 0];
  * 4: the FLOAT32 sincos of (float)x -> [sin, cos], for tests that need its values and not its error;
- * 5: the float32 controller's (float)x^(-1/10) -> [value, 0], whatever x is. */
+ * 5: the float32 controller's (float)x^(-1/10) -> [value, 0], whatever x is;
+ * 6: the correctly rounded sincos of the prologue (angles of a few radians) -> [sin, cos]. */
 int lt_math64_probe(int which, const double *x, int64_t n, double *out);
 
 /* ---- fused frame path ---------------------------------------------------------------- *

@@ -544,18 +544,42 @@ template <typename T> static KerrConsts<T> make_kerr(const MetricConsts &mc, dou
     return k;
 }
 
+// The steps of the reference's loop (metrics.py:68-73): while phi < phi_max, h = min(h_max, phi_max - phi), phi += h, with
+// phi ACCUMULATED in float64.  The sum of n_full steps seldom lands on phi_max exactly, so a range that is a whole multiple
+// of h_max on paper (50 / 0.05) still ends in a step of the rounding's size (7e-13), four evaluations that a closed form
+// floor(phi_max / h_max) leaves out.  The loop is run here once per launch, in float64 whatever the kernel's precision
+// (the fixtures are the float64 reference's): n_full full steps, then h_last > 0 if a shorter one follows.  The shorter
+// step ends the range: remaining < h_max <= phi puts phi within a factor two of phi_max, where phi_max - phi and
+// phi + (phi_max - phi) are both exact.
+// (check_opts refuses a range of more than SCHW_MAX_STEPS steps: the loop below is bounded by it, and phi += h_max always
+// moves phi -- h_max >= phi_max / 2^24 is far above an ulp of any phi <= phi_max.)
+constexpr uint32_t SCHW_MAX_STEPS = 1u << 24;
+static void schw_step_plan(double phi_max, double h_max, uint32_t *n_full, double *h_last)
+{
+    double phi = 0.0;
+    uint32_t nf = 0;
+    *h_last = 0.0;
+    while (phi < phi_max && nf <= SCHW_MAX_STEPS) {
+        double h = h_max, remaining = phi_max - phi;
+        if (remaining < h) h = remaining;
+        if (h <= 0.0) break;
+        if (h < h_max) { *h_last = h; break; }
+        phi += h;
+        ++nf;
+    }
+    *n_full = nf;
+}
+
 template <typename T> static SchwConsts<T> make_schw(const MetricConsts &mc, double phi_max, double h_max)
 {
     SchwConsts<T> k;
+    double rest;
     k.M = (T)mc.M; k.three_M = (T)(3.0 * mc.M);
     k.u0 = (T)(1.0 / mc.r_obs);
     k.u_capture = (T)(1.0 / (mc.R_S * 1.01)); // metrics.py:66
     k.u_escape = (T)(1.0 / (2.0 * mc.r_obs)); // metrics.py:67
     k.h_max = (T)h_max; k.phi_max = (T)phi_max;
-    double nf = floor(phi_max / h_max + 1e-9);
-    double rest = phi_max - nf * h_max;
-    if (rest < 1e-9 * h_max) rest = 0.0;
-    k.n_full = (uint32_t)nf;
+    schw_step_plan(phi_max, h_max, &k.n_full, &rest);
     k.h_last = (T)rest;
     return k;
 }
@@ -797,6 +821,8 @@ static int check_opts(const lt_metric *metric, lt_opts *o)
         return fail(LT_ERR_INVALID_ARG, "unknown bg_sampling %d", o->bg_sampling);
     if (o->h_max <= 0.0) o->h_max = metric->kind == LT_METRIC_KERR ? 1.0 : 0.05;
     if (o->phi_max <= 0.0) o->phi_max = 50.0;
+    if (metric->kind == LT_METRIC_SCHWARZSCHILD && !(o->phi_max / o->h_max <= (double)SCHW_MAX_STEPS))
+        return fail(LT_ERR_INVALID_ARG, "phi_max / h_max = %g: more than %u steps per ray", o->phi_max / o->h_max, SCHW_MAX_STEPS);
     if (o->row_block <= 0) o->row_block = 16;
     if (o->n_parts <= 0) o->n_parts = 1;
     if (o->part < 0 || o->part >= o->n_parts) return fail(LT_ERR_INVALID_ARG, "part %d not in [0, %d)", o->part, o->n_parts);
@@ -1747,6 +1773,135 @@ extern "C" int lt_dp45_controller_probe(int exact, const double *err_sq, const d
     return LT_OK;
 }
 
+// ---- a ray's two ends and the RK4 loop body ------------------------------------------------------------------------------
+// (n,4) records of precision T on the device <-> (n,4) float64 on the host.
+template <typename T> static int probe_upload_recs(DevBuf &d, const double *src, int64_t n)
+{
+    std::vector<T> h((size_t)n * 4);
+    for (size_t j = 0; j < h.size(); ++j) h[j] = (T)src[j];
+    return probe_upload(d, h.data(), h.size() * sizeof(T));
+}
+template <typename T> static int probe_download_recs(double *dst, const DevBuf &d, int64_t n)
+{
+    std::vector<T> h((size_t)n * 4);
+    int rc = probe_download(h.data(), d, h.size() * sizeof(T));
+    for (size_t j = 0; j < h.size(); ++j) dst[j] = (double)h[j];
+    return rc;
+}
+
+extern "C" int lt_ic_probe(int kind, double M, double a, double r_obs, double theta_obs, const double *alphas,
+                           const double *thetas, const uint8_t *refines, int64_t n, int precision, double *out_records)
+{
+    int rc = require_device();
+    if (rc) return rc;
+    if (precision != 32 && precision != 64) return fail(LT_ERR_INVALID_ARG, "precision must be 32 or 64");
+    if (n <= 0) return LT_OK;
+    if (!alphas || !out_records || (kind == LT_METRIC_KERR && !thetas)) return fail(LT_ERR_INVALID_ARG, "null pointer");
+    lt_metric m{kind, 0, M, a};
+    MetricConsts mc;
+    if ((rc = make_metric(&m, r_obs, theta_obs, 0.0, &mc))) return rc;
+    const int64_t n_q = (n + 63) / 64 * 64;
+    DevBuf da, dt, dr, dic;
+    if ((rc = probe_upload(da, alphas, n * 8)) || (rc = probe_upload(dt, thetas, n * 8)) || (rc = probe_upload(dr, refines, n)) ||
+        (rc = dic.alloc((size_t)n_q * 4 * elem_size(precision)))) return rc;
+    with_precision(precision, [&](auto t) {
+        using T = decltype(t);
+        k_prologue_arrays<T><<<(unsigned)((n_q + 255) / 256), 256>>>(mc, (const double *)da.p, (const double *)dt.p, (const uint8_t *)dr.p, n,
+                                                                     (typename Vec4<T>::type *)dic.p, n_q);
+    });
+    HIP_TRY(hipGetLastError());
+    return with_precision(precision, [&](auto t) { return probe_download_recs<decltype(t)>(out_records, dic, n_q); });
+}
+
+extern "C" int lt_rk4_advance_probe(double M, double a, double r_obs, double lambda_max, double h_max, const double *states,
+                                    const double *p_phi, const uint8_t *refine, const double *lam, const double *h_retry,
+                                    const uint32_t *steps, int64_t n, int precision, int n_iters, double *out_states,
+                                    double *out_misc, int32_t *out_int)
+{
+    int rc = require_device();
+    if (rc) return rc;
+    if (precision != 32 && precision != 64) return fail(LT_ERR_INVALID_ARG, "precision must be 32 or 64");
+    if (n <= 0) return LT_OK;
+    if (n_iters < 1) return fail(LT_ERR_INVALID_ARG, "n_iters must be at least 1");
+    if (!(h_max > 0.0)) return fail(LT_ERR_INVALID_ARG, "h_max must be positive");
+    if (!states || !p_phi || !refine || !out_states || !out_misc || !out_int) return fail(LT_ERR_INVALID_ARG, "null pointer");
+    lt_metric m{LT_METRIC_KERR, 0, M, a};
+    MetricConsts mc;
+    if ((rc = make_metric(&m, r_obs, M_PI / 2, 0.0, &mc))) return rc;
+    DevBuf ds, dp, dr, dl, dh, dst, os, om, oi;
+    if ((rc = probe_upload(ds, states, n * 40)) || (rc = probe_upload(dp, p_phi, n * 8)) || (rc = probe_upload(dr, refine, n)) ||
+        (rc = probe_upload(dl, lam, n * 8)) || (rc = probe_upload(dh, h_retry, n * 8)) || (rc = probe_upload(dst, steps, n * 4)) ||
+        (rc = os.alloc(n * 40)) || (rc = om.alloc(n * 16)) || (rc = oi.alloc(n * 12))) return rc;
+    with_precision(precision, [&](auto t) {
+        using T = decltype(t);
+        k_rk4_advance_probe<T><<<(unsigned)((n + 63) / 64), 64>>>(make_kerr<T>(mc, lambda_max, h_max), (const double *)ds.p, (const double *)dp.p,
+                                                                  (const uint8_t *)dr.p, (const double *)dl.p, (const double *)dh.p,
+                                                                  (const uint32_t *)dst.p, n, n_iters, (double *)os.p, (double *)om.p,
+                                                                  (int32_t *)oi.p);
+    });
+    HIP_TRY(hipGetLastError());
+    if ((rc = probe_download(out_states, os, n * 40)) || (rc = probe_download(out_misc, om, n * 16)) ||
+        (rc = probe_download(out_int, oi, n * 12))) return rc;
+    return LT_OK;
+}
+
+extern "C" int lt_schw_trace_probe(double M, double r_obs, double phi_max, double h_max, const double *u0, const double *w0,
+                                   int64_t n, int precision, double *out, int32_t *out_int, uint32_t *out_n_full, double *out_h_last)
+{
+    int rc;
+    if (precision != 32 && precision != 64) return fail(LT_ERR_INVALID_ARG, "precision must be 32 or 64");
+    if (!(phi_max > 0.0) || !(h_max > 0.0) || !(phi_max / h_max <= (double)SCHW_MAX_STEPS))
+        return fail(LT_ERR_INVALID_ARG, "phi_max and h_max must be positive, phi_max / h_max at most %u", SCHW_MAX_STEPS);
+    lt_metric m{LT_METRIC_SCHWARZSCHILD, 0, M, 0.0};
+    MetricConsts mc;
+    if ((rc = make_metric(&m, r_obs, M_PI / 2, h_max, &mc))) return rc;
+    const SchwConsts<double> plan = make_schw<double>(mc, phi_max, h_max);
+    if (out_n_full) *out_n_full = plan.n_full;
+    if (out_h_last) *out_h_last = plan.h_last;
+    if (n <= 0) return LT_OK; // (the plan is the host's: no device is needed for it)
+    if ((rc = require_device())) return rc;
+    if (!u0 || !w0 || !out || !out_int) return fail(LT_ERR_INVALID_ARG, "null pointer");
+    DevBuf du, dw, dout, di;
+    if ((rc = probe_upload(du, u0, n * 8)) || (rc = probe_upload(dw, w0, n * 8)) || (rc = dout.alloc(n * 24)) || (rc = di.alloc(n * 12)))
+        return rc;
+    with_precision(precision, [&](auto t) {
+        using T = decltype(t);
+        k_schw_trace_probe<T><<<(unsigned)((n + 255) / 256), 256>>>(make_schw<T>(mc, phi_max, h_max), (const double *)du.p, (const double *)dw.p,
+                                                                    n, (double *)dout.p, (int32_t *)di.p);
+    });
+    HIP_TRY(hipGetLastError());
+    if ((rc = probe_download(out, dout, n * 24)) || (rc = probe_download(out_int, di, n * 12))) return rc;
+    return LT_OK;
+}
+
+extern "C" int lt_extract_probe(int kind, double M, double a, double h_schw, int integrator, const double *fin0, const double *fin1,
+                                int64_t n, int precision, double *out_fa, int64_t *out_w, int8_t *out_status, uint32_t *out_evals)
+{
+    int rc = require_device();
+    if (rc) return rc;
+    if (precision != 32 && precision != 64) return fail(LT_ERR_INVALID_ARG, "precision must be 32 or 64");
+    if (n <= 0) return LT_OK;
+    if (!fin0 || !fin1 || !out_fa || !out_w || !out_status || !out_evals) return fail(LT_ERR_INVALID_ARG, "null pointer");
+    lt_metric m{kind, 0, M, a};
+    MetricConsts mc;
+    if ((rc = make_metric(&m, 50.0, M_PI / 2, h_schw, &mc))) return rc;
+    count_evals(integrator, &mc);
+    DevBuf d0, d1, dfa, dw, dst, dev;
+    if ((rc = with_precision(precision, [&](auto t) { return probe_upload_recs<decltype(t)>(d0, fin0, n); })) ||
+        (rc = with_precision(precision, [&](auto t) { return probe_upload_recs<decltype(t)>(d1, fin1, n); })) ||
+        (rc = dfa.alloc(n * 8)) || (rc = dw.alloc(n * 8)) || (rc = dst.alloc(n)) || (rc = dev.alloc(n * 4))) return rc;
+    with_precision(precision, [&](auto t) {
+        using T = decltype(t);
+        using V = typename Vec4<T>::type;
+        k_epilogue_arrays<T><<<(unsigned)((n + 255) / 256), 256>>>(mc, (const V *)d0.p, (const V *)d1.p, n, (double *)dfa.p, (int64_t *)dw.p,
+                                                                   (int8_t *)dst.p, (uint32_t *)dev.p);
+    });
+    HIP_TRY(hipGetLastError());
+    if ((rc = probe_download(out_fa, dfa, n * 8)) || (rc = probe_download(out_w, dw, n * 8)) || (rc = probe_download(out_status, dst, n)) ||
+        (rc = probe_download(out_evals, dev, n * 4))) return rc;
+    return LT_OK;
+}
+
 extern "C" int lt_math32_probe(int which, uint32_t bits_lo, uint32_t bits_hi, const float *bases, int n_bases, uint64_t *out)
 {
     int rc = require_device();
@@ -1787,6 +1942,7 @@ __global__ void k_math64_probe(int which, const double *__restrict__ x, int64_t 
     else if (which == 2) u = M<double>::rcp_pos(x[i]);
     else if (which == 3) u = pow_m02(x[i]);
     else if (which == 5) u = pow_minus_tenth((float)x[i]);
+    else if (which == 6) sincos_f64_exact(x[i], u, v);
     else {
         float s, c;
         M<float>::sincos((float)x[i], s, c);
@@ -1799,7 +1955,7 @@ extern "C" int lt_math64_probe(int which, const double *x, int64_t n, double *ou
 {
     int rc = require_device();
     if (rc) return rc;
-    if (which < 0 || which > 5) return fail(LT_ERR_INVALID_ARG, "bad math probe arguments");
+    if (which < 0 || which > 6) return fail(LT_ERR_INVALID_ARG, "bad math probe arguments");
     if (n <= 0) return LT_OK;
     if (!x || !out) return fail(LT_ERR_INVALID_ARG, "null pointer");
     DevBuf dx, dout;

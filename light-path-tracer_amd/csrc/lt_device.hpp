@@ -188,6 +188,68 @@ __device__ __forceinline__ void sincos_f64(double x, double &s, double &c)
     c = ((k + 1) & 2) ? -cc : cc;
 }
 
+// x, hidden from the optimiser.  A product passed through it is rounded on its own: it cannot be fused into the sum it feeds
+// (-ffp-contract=fast fuses whatever it can, a function's `fp contract(off)` notwithstanding, and which product of a sum of
+// products it picks differs from one kernel to the next).
+__device__ __forceinline__ double unfused(double x)
+{
+    asm volatile("" : "+v"(x));
+    return x;
+}
+
+// sin and cos of a float64 angle of a few radians, correctly rounded (against mpmath: every one of 40 000 arguments; glibc's
+// own differ from them on 1 in 1000): for what runs once per ray and has to give the reference's bits -- the prologue, whose
+// Theta and p_r^2 cancel completely on some rays, where the reference's value is the rounding of its own sin(alpha) and
+// only the same sine gives it.  pi/2 is carried to 141 bits (P1 + P1T + P1TT, the product kf P1T exactly), the reduced
+// angle is a double-double, the first four terms of either Taylor series are summed in double-double arithmetic and the
+// rest (below 2^-21 of the result) in float64.  ~400 float64 operations: not for the integrators, which keep sincos_f64.
+struct DD { double hi, lo; };
+__device__ __forceinline__ DD dd_two_sum(double a, double b) { double s = a + b, bb = s - a; return {s, (a - (s - bb)) + (b - bb)}; }
+__device__ __forceinline__ DD dd_quick_two_sum(double a, double b) { double s = a + b; return {s, b - (s - a)}; }
+// (the product is hidden from the compiler: fused into the sum it later feeds, that sum would no longer be the rounded sum of
+// its two float64 operands that dd_two_sum's error term is the error of)
+__device__ __forceinline__ DD dd_two_prod(double a, double b) { double p = unfused(a * b); return {p, __builtin_fma(a, b, -p)}; }
+__device__ __forceinline__ DD dd_add(DD a, DD b)
+{
+    DD s = dd_two_sum(a.hi, b.hi);
+    return dd_quick_two_sum(s.hi, s.lo + (a.lo + b.lo));
+}
+__device__ __forceinline__ DD dd_mul(DD a, DD b)
+{
+    DD p = dd_two_prod(a.hi, b.hi);
+    return dd_quick_two_sum(p.hi, p.lo + __builtin_fma(a.hi, b.lo, a.lo * b.hi));
+}
+__device__ __forceinline__ void sincos_f64_exact(double x, double &s, double &c)
+{
+    // (-1)^k / (2k+1)! and (-1)^k / (2k)!, k = 1 ... 13, as unevaluated sums of two float64
+    constexpr double DD_S[13][2] = {{-0.16666666666666666, -9.25185853854297e-18}, {0.008333333333333333, 1.1564823173178714e-19}, {-0.0001984126984126984, -1.7209558293420705e-22}, {2.7557319223985893e-06, -1.858393274046472e-22}, {-2.505210838544172e-08, 1.448814070935912e-24}, {1.6059043836821613e-10, 1.2585294588752098e-26}, {-7.647163731819816e-13, -7.03872877733453e-30}, {2.8114572543455206e-15, 1.6508842730861433e-31}, {-8.22063524662433e-18, -2.2141894119604265e-34}, {1.9572941063391263e-20, -1.3643503830087908e-36}, {-3.868170170630684e-23, 8.843177655482344e-40}, {6.446950284384474e-26, -1.9330404233703465e-42}, {-9.183689863795546e-29, -1.4303150396787322e-45}};
+    constexpr double DD_C[13][2] = {{-0.5, 0.0}, {0.041666666666666664, 2.3129646346357427e-18}, {-0.001388888888888889, 5.300543954373577e-20}, {2.48015873015873e-05, 2.1511947866775882e-23}, {-2.755731922398589e-07, -2.3767714622250297e-23}, {2.08767569878681e-09, -1.20734505911326e-25}, {-1.1470745597729725e-11, -2.0655512752830745e-28}, {4.779477332387385e-14, 4.399205485834081e-31}, {-1.5619206968586225e-16, -1.1910679660273754e-32}, {4.110317623312165e-19, 1.4412973378659527e-36}, {-8.896791392450574e-22, 7.911402614872376e-38}, {1.6117375710961184e-24, -3.6846573564509766e-41}, {-2.4795962632247976e-27, 1.2953730964765229e-43}};
+    const double TWO_OVER_PI = 6.36619772367581382433e-01;
+    const double P1 = 1.57079632673412561417e+00, P1T = 6.07710050650619224932e-11, P1TT = 3.5215598651832003884e-27;
+    const double kf = __builtin_rint(x * TWO_OVER_PI);
+    const double r = __builtin_fma(-kf, P1, x); // exact
+    const DD w = dd_two_prod(kf, P1T);
+    DD y = dd_two_sum(r, -w.hi);
+    y = dd_quick_two_sum(y.hi, y.lo + __builtin_fma(-kf, P1TT, -w.lo));
+    const DD z = dd_mul(y, y);
+    double qs = DD_S[12][0], qc = DD_C[12][0];
+#pragma unroll
+    for (int i = 11; i >= 4; --i) { qs = __builtin_fma(qs, z.hi, DD_S[i][0]); qc = __builtin_fma(qc, z.hi, DD_C[i][0]); }
+    DD ps = {qs, 0.0}, pc = {qc, 0.0};
+#pragma unroll
+    for (int i = 3; i >= 0; --i) {
+        ps = dd_add(dd_mul(ps, z), DD{DD_S[i][0], DD_S[i][1]});
+        pc = dd_add(dd_mul(pc, z), DD{DD_C[i][0], DD_C[i][1]});
+    }
+    const DD sn = dd_add(y, dd_mul(dd_mul(ps, z), y)), cn = dd_add(DD{1.0, 0.0}, dd_mul(pc, z));
+    const double sr = sn.hi + sn.lo, cr = cn.hi + cn.lo;
+    const int k = (int)kf;
+    const bool swap = k & 1;
+    const double ss = swap ? cr : sr, cc = swap ? sr : cr;
+    s = (k & 2) ? -ss : ss;
+    c = ((k + 1) & 2) ? -cc : cc;
+}
+
 template <> struct M<double> {
     static __device__ __forceinline__ double rcp(double x) { return 1.0 / x; }
     // 1/x for positive normal x: the hardware seed and two Newton steps -- the core of the compiler's IEEE division
@@ -905,12 +967,12 @@ template <typename T> struct SchwConsts {
     T u_capture;  // 1 / (1.01 R_S)
     T u_escape;   // 1 / (2 r_obs)
     T h_max, phi_max;
-    uint32_t n_full; // number of full h_max steps that fit below phi_max
-    T h_last;        // remaining partial step (0 if none)
+    uint32_t n_full; // full h_max steps of the reference's loop, counted by the host as the reference accumulates phi
+    T h_last;        // the shorter step that ends the range (0 if none)
 };
 
-// Returns the event code; u, w are the final values, phi_last the part of the last step used
-// (phi_f = steps_before * h + phi_last is rebuilt in float64 by the epilogue).
+// Returns the event code; u, w are the final values, phi_last the part of the last, shorter or interrupted, step used
+// (phi_f = schw_full_steps * h_max + phi_last is rebuilt in float64 by the epilogue).
 template <typename T>
 __device__ __forceinline__ int schw_trace(const SchwConsts<T> &k, T &u, T &w, uint32_t &steps, T &phi_last)
 {
@@ -947,7 +1009,14 @@ __device__ __forceinline__ int schw_trace(const SchwConsts<T> &k, T &u, T &w, ui
         u = un; w = wn;
         ++steps;
     }
+    if (ev == EV_MAXRANGE && k.h_last > T(0)) phi_last = k.h_last; // the range ended with the shorter step
     return ev;
+}
+
+// Of the `steps` completed steps, the ones of length h_max (the last may be the shorter one).
+template <typename T> __device__ __forceinline__ uint32_t schw_full_steps(const SchwConsts<T> &k, uint32_t steps)
+{
+    return steps < k.n_full ? steps : k.n_full;
 }
 
 } // namespace lt

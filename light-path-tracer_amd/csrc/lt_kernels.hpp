@@ -193,27 +193,30 @@ __device__ __forceinline__ void pixel_angles(const CamConsts &c, int ix, int gro
     theta = atan2(vx * c.ex[0] + vy * c.ex[1] + vz * c.ex[2], vx * c.ey[0] + vy * c.ey[1] + vz * c.ey[2]);
 }
 
-// Kerr initial momenta, metrics.py:148-218, float64, operation order as written there.
+// Kerr initial momenta, metrics.py:148-218, float64: the reference's operations one by one, in its order, on the reference's
+// values.  Theta and p_r^2 cancel completely on some rays (any screen angle seen from off the equator at small alpha,
+// alpha = pi / 2), where the reference's value is the rounding of its own operations; so the sines and cosines are the
+// correctly rounded ones (sincos_f64_exact) and no product is fused into the sum it feeds (unfused).
 __device__ __forceinline__ bool kerr_initial_momenta(const MetricConsts &m, double alpha, double theta,
                                                      double &p_r, double &p_theta, double &p_phi)
 {
     double r = m.r_obs, a = m.a;
     p_r = p_theta = p_phi = 0.0;
     if (!m.obs_ok) return false;
-    // (sincos_f64: branch-free reduction + the fdlibm kernels, < 1 ulp, for angles of a few radians; OCML's carry a
-    // large-argument path)
     double sin_alpha, cos_alpha_unused, sin_screen, cos_screen;
-    sincos_f64(alpha, sin_alpha, cos_alpha_unused);
-    sincos_f64(theta, sin_screen, cos_screen);
+    sincos_f64_exact(alpha, sin_alpha, cos_alpha_unused);
+    sincos_f64_exact(theta, sin_screen, cos_screen);
     double rho = r * sin_alpha * m.obs_sqrt_Sigma / m.obs_sqrt_Delta;
     double alpha_screen = -rho * sin_screen, beta_screen = -rho * cos_screen;
     double xi = -alpha_screen * m.obs_sin_th;
-    double eta = beta_screen * beta_screen + m.obs_cos2 * (alpha_screen * alpha_screen - a * a);
+    const double a_sq = unfused(a * a);
+    double eta = unfused(beta_screen * beta_screen) + unfused(m.obs_cos2 * (unfused(alpha_screen * alpha_screen) - a_sq));
     double L = xi, Q = eta;
-    double Theta = Q - m.obs_cos2 * (L * L / m.obs_sin2 - a * a);
+    double Theta = Q - unfused(m.obs_cos2 * (L * L / m.obs_sin2 - a_sq));
     if (Theta < 0.0) Theta = 0.0;
     p_theta = (cos_screen > 0.0 ? -1.0 : 1.0) * sqrt(Theta);
-    double other = m.obs_g_tt + 2.0 * m.obs_g_tphi * (-1.0) * L + m.obs_g_thth * p_theta * p_theta + m.obs_g_phiphi * L * L;
+    double other = m.obs_g_tt + unfused(2.0 * m.obs_g_tphi * (-1.0) * L) + unfused(m.obs_g_thth * p_theta * p_theta) +
+                   unfused(m.obs_g_phiphi * L * L);
     double p_r_sq = -other / m.obs_g_rr;
     if (p_r_sq < 0.0) p_r_sq = 0.0;
     p_r = -sqrt(p_r_sq);
@@ -671,7 +674,7 @@ __global__ void __launch_bounds__(256) k_schw_rk4_direct(SchwConsts<T> k, const 
     uint32_t steps = 0;
     if (flags & FLAG_OK) ev = schw_trace(k, u, w, steps, phi_last);
     uint32_t total = steps + ((ev == EV_CAPTURED || ev == EV_ESCAPED) ? 1u : 0u);
-    store_fin<T>(fin0, fin1, q, u, w, phi_last, (T)steps, T(0), T(0), ev, total);
+    store_fin<T>(fin0, fin1, q, u, w, phi_last, (T)schw_full_steps(k, steps), T(0), T(0), ev, total);
 }
 
 // ---- K3: epilogue -----------------------------------------------------------------------------
@@ -691,6 +694,10 @@ __device__ __forceinline__ long long half_orbits(double phi)
     q = r < 0.0 ? q - 1.0 : (r >= PI ? q + 1.0 : q);
     return (long long)q;
 }
+
+// clip_scalar(x, -1, 1) of the reference (metrics.py:35-41): compares, so a NaN stays a NaN (fmin / fmax would turn it into
+// a bound, and a ray whose state is NaN into one that escaped at final_alpha = pi).
+__device__ __forceinline__ double clip_unit(double x) { return x < -1.0 ? -1.0 : (x > 1.0 ? 1.0 : x); }
 
 struct RayResult {
     int status;       // LT_STATUS_*
@@ -721,8 +728,11 @@ __device__ __forceinline__ void kerr_extract(const MetricConsts &m, double r_f, 
     sincos_f64(phi_f, sin_phi, cos_phi);
     double sin_th_sq = sin_th * sin_th;
     if (sin_th_sq < 1e-15) sin_th_sq = 1e-15;
-    double Sigma_f = r_f * r_f + a * a * cos_th * cos_th;
-    double Delta_f = r_f * r_f - 2.0 * M_ * r_f + a * a;
+    // (unfused: every product of a sum is rounded on its own, so that the angle of a record does not depend on which of
+    // them the compiler fuses in the kernel at hand -- the float32 and the float64 epilogues gave different bits)
+    const double rr = unfused(r_f * r_f), aa = unfused(a * a);
+    double Sigma_f = rr + unfused(aa * cos_th * cos_th);
+    double Delta_f = rr - unfused(2.0 * M_ * r_f) + aa;
     if (Sigma_f <= 1e-15 || fabs(Delta_f) <= 1e-15) { o.status = 0; return; }
     // r_f > 1.1 r_capture > r_plus: Delta > 0, Sigma > 0, sin^2 >= 1e-15 -- the common denominator is a positive normal number
     const double SD = Sigma_f * Delta_f;
@@ -730,15 +740,15 @@ __device__ __forceinline__ void kerr_extract(const MetricConsts &m, double r_f, 
     const double iS = (Delta_f * sin_th_sq) * t, iSD = sin_th_sq * t, iSDs = t; // 1/Sigma, 1/(Sigma Delta), 1/(Sigma Delta sin^2)
     double dr_dl = (Delta_f * iS) * p_r_f;
     double dth_dl = p_th_f * iS;
-    double dphi_dl = (-2.0 * M_ * a * r_f * iSD * p_t + (Delta_f - a * a * sin_th_sq) * iSDs * p_phi);
-    double vx = sin_th * cos_phi * dr_dl + r_f * cos_th * cos_phi * dth_dl - r_f * sin_th * sin_phi * dphi_dl;
-    double vy = sin_th * sin_phi * dr_dl + r_f * cos_th * sin_phi * dth_dl + r_f * sin_th * cos_phi * dphi_dl;
-    double vz = cos_th * dr_dl - r_f * sin_th * dth_dl;
+    double dphi_dl = unfused(-2.0 * M_ * a * r_f * iSD * p_t) + unfused((Delta_f - unfused(aa * sin_th_sq)) * iSDs * p_phi);
+    double vx = unfused(sin_th * cos_phi * dr_dl) + unfused(r_f * cos_th * cos_phi * dth_dl) - unfused(r_f * sin_th * sin_phi * dphi_dl);
+    double vy = unfused(sin_th * sin_phi * dr_dl) + unfused(r_f * cos_th * sin_phi * dth_dl) + unfused(r_f * sin_th * cos_phi * dphi_dl);
+    double vz = unfused(cos_th * dr_dl) - unfused(r_f * sin_th * dth_dl);
     if (!isfinite(vx) || !isfinite(vy) || !isfinite(vz)) { o.status = 0; return; }
-    double v_mag = __builtin_sqrt(vx * vx + vy * vy + vz * vz);
+    double v_mag = __builtin_sqrt(unfused(vx * vx) + unfused(vy * vy) + unfused(vz * vz));
     o.status = 1;
     if (v_mag < 1e-30) return;
-    o.fa = acos(fmin(fmax(-vx * M<double>::rcp_pos(v_mag), -1.0), 1.0));
+    o.fa = acos(clip_unit(-vx * M<double>::rcp_pos(v_mag)));
 }
 
 // _schwarzschild_trace_ray_numba tail, metrics.py:129-145.
@@ -754,9 +764,9 @@ __device__ __forceinline__ void schw_extract(const MetricConsts &m, double u_f, 
     double dr_dphi = -w_f / (u_f * u_f);
     double sin_phi, cos_phi;
     sincos(phi_f, &sin_phi, &cos_phi);
-    double heading = atan2(dr_dphi * sin_phi + r_f * cos_phi, dr_dphi * cos_phi - r_f * sin_phi);
+    double heading = atan2(unfused(dr_dphi * sin_phi) + unfused(r_f * cos_phi), unfused(dr_dphi * cos_phi) - unfused(r_f * sin_phi));
     o.status = 1;
-    o.fa = acos(fmin(fmax(-cos(heading), -1.0), 1.0));
+    o.fa = acos(clip_unit(-cos(heading)));
 }
 
 template <typename T>
@@ -767,7 +777,7 @@ __device__ __forceinline__ void load_result(const MetricConsts &m, const typenam
     int ev = (int)v1.z;
     o.steps = (uint32_t)v1.w;
     if (m.kind == 0) {
-        double phi_f = (double)v0.w * m.phi_h + (double)v0.z;
+        double phi_f = __builtin_fma((double)v0.w, m.phi_h, (double)v0.z);
         schw_extract(m, (double)v0.x, (double)v0.y, phi_f, ev, o);
     } else {
         kerr_extract(m, (double)v0.x, (double)v0.y, (double)v0.z, (double)v0.w, (double)v1.x, (double)v1.y, ev, o);
@@ -1254,6 +1264,60 @@ __global__ void __launch_bounds__(64) k_dp45_advance_probe(KerrConsts<double> k_
     for (int j = 0; j < 5; ++j) out_k1[i * 5 + j] = s.k1[j];
     out_misc[i * 4 + 0] = s.s0; out_misc[i * 4 + 1] = s.c0; out_misc[i * 4 + 2] = s.lam; out_misc[i * 4 + 3] = s.h;
     out_int[i * 3 + 0] = ev; out_int[i * 3 + 1] = (int32_t)s.steps; out_int[i * 3 + 2] = made;
+}
+
+// ---- a ray's two ends and the RK4 loop body (lt_rk4_advance_probe, lt_schw_trace_probe; lt_ic_probe and lt_extract_probe
+// run k_prologue_arrays / k_epilogue_arrays themselves) ----------------------------------------------------------------------
+// kerr_rk4_advance up to n_iters times per row, until it returns something other than EV_RUNNING.  Blocks of 64: rows
+// 64 b ... 64 b + 63 share a wavefront; a lane whose ray has ended (or a row beyond n) leaves the loop, as in
+// k_kerr_general_only.  out_misc (n,2): lam, h_retry; out_int (n,3): event, steps, iterations made.
+template <typename T>
+__global__ void __launch_bounds__(64) k_rk4_advance_probe(KerrConsts<T> k_in, const double *__restrict__ states,
+                                                          const double *__restrict__ p_phi, const uint8_t *__restrict__ refine,
+                                                          const double *__restrict__ lams, const double *__restrict__ h_retry,
+                                                          const uint32_t *__restrict__ steps, int64_t n, int n_iters,
+                                                          double *__restrict__ out_states, double *__restrict__ out_misc,
+                                                          int32_t *__restrict__ out_int)
+{
+    const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    KerrConsts<T> k = k_in;
+    pin_consts(k);
+    const RayConsts<T> rc = make_ray_consts(k, (T)p_phi[i], refine[i] != 0);
+    RayState<T> s;
+    s.y.r = (T)states[i * 5 + 0]; s.y.th = (T)states[i * 5 + 1]; s.y.ph = (T)states[i * 5 + 2];
+    s.y.pr = (T)states[i * 5 + 3]; s.y.pth = (T)states[i * 5 + 4];
+    s.lam = lams ? (T)lams[i] : T(0);
+    s.h_retry = h_retry ? (T)h_retry[i] : T(0);
+    s.steps = steps ? steps[i] : 0u;
+    int ev = EV_RUNNING, made = 0;
+    while (made < n_iters) {
+        ev = kerr_rk4_advance(k, rc, s);
+        ++made;
+        if (ev != EV_RUNNING) break;
+    }
+    out_states[i * 5 + 0] = s.y.r; out_states[i * 5 + 1] = s.y.th; out_states[i * 5 + 2] = s.y.ph;
+    out_states[i * 5 + 3] = s.y.pr; out_states[i * 5 + 4] = s.y.pth;
+    out_misc[i * 2 + 0] = s.lam; out_misc[i * 2 + 1] = s.h_retry;
+    out_int[i * 3 + 0] = ev; out_int[i * 3 + 1] = (int32_t)s.steps; out_int[i * 3 + 2] = made;
+}
+
+// schw_trace from a supplied start (u, w) per row, stored as k_schw_rk4_direct stores it.  out (n,3): u, w, phi_last;
+// out_int (n,3): event, steps (the ending one included), full steps (what the epilogue multiplies by h_max).
+template <typename T>
+__global__ void __launch_bounds__(256) k_schw_trace_probe(SchwConsts<T> k, const double *__restrict__ u0,
+                                                          const double *__restrict__ w0, int64_t n, double *__restrict__ out,
+                                                          int32_t *__restrict__ out_int)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    T u = (T)u0[i], w = (T)w0[i], phi_last = T(0);
+    uint32_t steps = 0;
+    const int ev = schw_trace(k, u, w, steps, phi_last);
+    out[i * 3 + 0] = u; out[i * 3 + 1] = w; out[i * 3 + 2] = phi_last;
+    out_int[i * 3 + 0] = ev;
+    out_int[i * 3 + 1] = (int32_t)(steps + ((ev == EV_CAPTURED || ev == EV_ESCAPED) ? 1u : 0u));
+    out_int[i * 3 + 2] = (int32_t)schw_full_steps(k, steps);
 }
 
 // Dp45<double, EXACT>::control on any (err_sq, h) (lt_dp45_controller_probe).

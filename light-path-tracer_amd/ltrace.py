@@ -161,6 +161,11 @@ SIGNATURES = {
     "lt_dp45_attempt_probe": (C.c_int, [C.c_double] * 4 + [C.c_void_p] * 6 + [C.c_int64, C.c_int, C.c_int] + [C.c_void_p] * 6),
     "lt_dp45_advance_probe": (C.c_int, [C.c_double] * 4 + [C.c_void_p] * 8 + [C.c_int64, C.c_int, C.c_int] + [C.c_void_p] * 4),
     "lt_dp45_controller_probe": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "lt_ic_probe": (C.c_int, [C.c_int] + [C.c_double] * 4 + [C.c_void_p] * 3 + [C.c_int64, C.c_int, C.c_void_p]),
+    "lt_rk4_advance_probe": (C.c_int, [C.c_double] * 5 + [C.c_void_p] * 6 + [C.c_int64, C.c_int, C.c_int] + [C.c_void_p] * 3),
+    "lt_schw_trace_probe": (C.c_int, [C.c_double] * 4 + [C.c_void_p] * 2 + [C.c_int64, C.c_int] + [C.c_void_p] * 4),
+    "lt_extract_probe": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int]
+                         + [C.c_void_p] * 4),
     "lt_math32_probe": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p]),
     "lt_math64_probe": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
     "lt_set_eq_streak": (C.c_int, [C.c_int]),
@@ -572,8 +577,70 @@ def dp45_controller_probe(err_sq, h, exact=True):
     return rj.astype(bool), out
 
 
+FLAG_OK, FLAG_REFINE, FLAG_PAD = 1, 2, 4                                # flags of a ray record (lt_ic_probe)
+EV_CAPTURED, EV_INVALID, EV_ESCAPED, EV_MAXRANGE, EV_PAD, EV_RUNNING = -1, 0, 1, 2, 3, 4   # events of a final record
+
+
+def ic_probe(kind, M, a, r_obs, theta_obs, alphas, thetas=None, refines=None, precision=64):
+    """The ray records the array prologue stores (lt_ic_probe) -> (n_q,4) float64, n_q = n rounded up to a multiple of 64:
+    p_r, p_theta, p_phi, flags (Kerr) or w0, 0, 0, flags (Schwarzschild); the rows from n on are padding (FLAG_PAD)."""
+    al = np.ascontiguousarray(alphas, dtype=np.float64).ravel()
+    n = al.size
+    th = None if thetas is None else np.ascontiguousarray(np.broadcast_to(np.asarray(thetas, dtype=np.float64), (n,)))
+    rf = None if refines is None else np.ascontiguousarray(np.broadcast_to(np.asarray(refines), (n,))).astype(np.uint8)
+    out = np.empty(((n + 63) // 64 * 64, 4))
+    _check(load().lt_ic_probe(int(kind), M, a, r_obs, theta_obs, _np_ptr(al), _np_ptr(th), _np_ptr(rf), n, precision, _np_ptr(out)))
+    return out
+
+
+def rk4_advance_probe(M, a, states, p_phi, refine=None, lam=None, h_retry=None, steps=None, precision=64, n_iters=1, r_obs=50.0,
+                      lambda_max=5000.0, h_max=1.0):
+    """Up to n_iters iterations (step attempts) of the fixed-step RK4 loop body per state (lt_rk4_advance_probe); rows
+    64 b ... 64 b + 63 share a wavefront.  -> dict(event, steps, iters (n,) int32, state (n,5), lam, h_retry (n,))."""
+    st = np.ascontiguousarray(states, dtype=np.float64).reshape(-1, 5)
+    n = st.shape[0]
+    pp = np.ascontiguousarray(np.broadcast_to(np.asarray(p_phi, dtype=np.float64), (n,)))
+    rf = np.zeros(n, dtype=np.uint8) if refine is None else np.ascontiguousarray(np.broadcast_to(np.asarray(refine), (n,))).astype(np.uint8)
+    ll = None if lam is None else np.ascontiguousarray(np.broadcast_to(np.asarray(lam, dtype=np.float64), (n,)))
+    hr = None if h_retry is None else np.ascontiguousarray(np.broadcast_to(np.asarray(h_retry, dtype=np.float64), (n,)))
+    ss = None if steps is None else np.ascontiguousarray(np.broadcast_to(np.asarray(steps), (n,))).astype(np.uint32)
+    out, misc, oi = np.empty_like(st), np.empty((n, 2)), np.empty((n, 3), dtype=np.int32)
+    _check(load().lt_rk4_advance_probe(M, a, r_obs, lambda_max, h_max, _np_ptr(st), _np_ptr(pp), _np_ptr(rf), _np_ptr(ll), _np_ptr(hr),
+                                       _np_ptr(ss), n, precision, int(n_iters), _np_ptr(out), _np_ptr(misc), _np_ptr(oi)))
+    return dict(event=oi[:, 0].copy(), steps=oi[:, 1].copy(), iters=oi[:, 2].copy(), state=out, lam=misc[:, 0].copy(),
+                h_retry=misc[:, 1].copy())
+
+
+def schw_trace_probe(M, r_obs, u0, w0, phi_max=50.0, h_max=0.05, precision=64):
+    """The Schwarzschild integrator from supplied starts (lt_schw_trace_probe).
+    -> dict(u, w, phi_last (n,), event, steps, full_steps (n,) int32, n_full, h_last: the host's step plan for the call)."""
+    uu = np.ascontiguousarray(u0, dtype=np.float64).ravel()
+    n = uu.size
+    ww = np.ascontiguousarray(np.broadcast_to(np.asarray(w0, dtype=np.float64), (n,)))
+    out, oi = np.empty((n, 3)), np.empty((n, 3), dtype=np.int32)
+    nf, hl = C.c_uint32(0), C.c_double(0.0)
+    _check(load().lt_schw_trace_probe(M, r_obs, phi_max, h_max, _np_ptr(uu), _np_ptr(ww), n, precision, _np_ptr(out), _np_ptr(oi),
+                                      C.cast(C.byref(nf), C.c_void_p), C.cast(C.byref(hl), C.c_void_p)))
+    return dict(u=out[:, 0].copy(), w=out[:, 1].copy(), phi_last=out[:, 2].copy(), event=oi[:, 0].copy(), steps=oi[:, 1].copy(),
+                full_steps=oi[:, 2].copy(), n_full=int(nf.value), h_last=float(hl.value))
+
+
+def extract_probe(kind, M, a, fin0, fin1, precision=64, integrator=INTEGRATOR_RK4, h_schw=0.05):
+    """The array epilogue on final records in the integrate kernels' layout (lt_extract_probe): fin0, fin1 (n,4).
+    -> dict(fa (n,) NaN unless escaped, winding (n,) i64, status (n,) i8, evals (n,) u32)."""
+    f0 = np.ascontiguousarray(fin0, dtype=np.float64).reshape(-1, 4)
+    f1 = np.ascontiguousarray(fin1, dtype=np.float64).reshape(-1, 4)
+    n = f0.shape[0]
+    if f1.shape[0] != n:
+        raise ValueError("fin0 and fin1 differ in length")
+    fa, w, st, ev = np.empty(n), np.empty(n, dtype=np.int64), np.empty(n, dtype=np.int8), np.empty(n, dtype=np.uint32)
+    _check(load().lt_extract_probe(int(kind), M, a, h_schw, _named(INTEGRATORS, integrator), _np_ptr(f0), _np_ptr(f1), n, precision,
+                                   _np_ptr(fa), _np_ptr(w), _np_ptr(st), _np_ptr(ev)))
+    return dict(fa=fa, winding=w, status=st, evals=ev)
+
+
 MATH32_WHICH = {"sincos": 0, "sincos_small": 1, "rcp_pos": 2, "sincos_shift": 3, "pow_minus_tenth": 4}
-MATH64_WHICH = {"sincos": 0, "sincos_small": 1, "rcp_pos": 2, "pow_m02": 3, "sincos_f32": 4, "pow_minus_tenth_f32": 5}
+MATH64_WHICH = {"sincos": 0, "sincos_small": 1, "rcp_pos": 2, "pow_m02": 3, "sincos_f32": 4, "pow_minus_tenth_f32": 5, "sincos_exact": 6}
 
 
 def math32_probe(which, bits_lo, bits_hi, bases=None):

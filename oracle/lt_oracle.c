@@ -111,11 +111,10 @@ static void schw_rhs(real u, real w, real M, real *du, real *dw)
     *dw = -u + R(3.0) * M * u * u;
 }
 
-/* metrics.py:49-117; status 1 escaped, -1 captured, 0 invalid, 2 max-range */
-static int schw_trace_orbit(real M, real R_S, real r_obs, real alpha, real phi_max, real h_max,
-                            real *phi_out, real *u_out, real *w_out)
+/* metrics.py:57-65: the ray's start (u = 1 / r_obs, w0); returns 0 where the reference returns "invalid" */
+static int schw_ic(real M, real R_S, real r_obs, real alpha, real *w0)
 {
-    *phi_out = LTO_NAN; *u_out = R(0.0); *w_out = R(0.0);
+    *w0 = R(0.0);
     real f0 = R(1.0) - R_S / r_obs;
     if (f0 <= R(0.0)) return 0;
     real b = r_obs * M_SIN(alpha) / M_SQRT(f0);
@@ -123,8 +122,14 @@ static int schw_trace_orbit(real M, real R_S, real r_obs, real alpha, real phi_m
     real u = R(1.0) / r_obs;
     real w0_sq = R(1.0) / (b * b) - u * u + R(2.0) * M * u * u * u;
     if (w0_sq < R(0.0)) return 0;
-    real w = M_SQRT(w0_sq);
-    real phi = R(0.0);
+    *w0 = M_SQRT(w0_sq);
+    return 1;
+}
+
+/* metrics.py:66-117, the loop, from any (phi, u, w); status 1 escaped, -1 captured, 2 max-range */
+static int schw_orbit_loop(real M, real R_S, real r_obs, real phi_max, real h_max, real *phi_io, real *u_io, real *w_io)
+{
+    real phi = *phi_io, u = *u_io, w = *w_io;
     real u_capture = R(1.0) / (R_S * R(1.01));
     real u_escape = R(1.0) / (R(2.0) * r_obs);
     int status = 2;
@@ -164,16 +169,24 @@ static int schw_trace_orbit(real M, real R_S, real r_obs, real alpha, real phi_m
         }
         phi = phi_next;
     }
-    *phi_out = phi; *u_out = u; *w_out = w;
+    *phi_io = phi; *u_io = u; *w_io = w;
     return status;
 }
 
-/* metrics.py:120-145 -> (status, final_alpha, n_half) */
-static int schw_trace_ray(real M, real R_S, real r_obs, real alpha, real phi_max, real h_max,
-                          real *fa_out, int64_t *nh_out)
+/* metrics.py:49-117; status 1 escaped, -1 captured, 0 invalid, 2 max-range */
+static int schw_trace_orbit(real M, real R_S, real r_obs, real alpha, real phi_max, real h_max,
+                            real *phi_out, real *u_out, real *w_out)
 {
-    real phi_f, u_f, w_f;
-    int status = schw_trace_orbit(M, R_S, r_obs, alpha, phi_max, h_max, &phi_f, &u_f, &w_f);
+    real w;
+    *phi_out = LTO_NAN; *u_out = R(0.0); *w_out = R(0.0);
+    if (!schw_ic(M, R_S, r_obs, alpha, &w)) return 0;
+    *phi_out = R(0.0); *u_out = R(1.0) / r_obs; *w_out = w;
+    return schw_orbit_loop(M, R_S, r_obs, phi_max, h_max, phi_out, u_out, w_out);
+}
+
+/* metrics.py:129-145, the tail of the ray tracer: (orbit status, phi_f, u_f, w_f) -> (status, final_alpha, n_half) */
+static int schw_extract_angle(real R_S, int status, real phi_f, real u_f, real w_f, real *fa_out, int64_t *nh_out)
+{
     *fa_out = LTO_NAN; *nh_out = 0;
     if (status == 0) return 0;
     real r_f = R(1.0) / u_f;
@@ -186,6 +199,15 @@ static int schw_trace_ray(real M, real R_S, real r_obs, real alpha, real phi_max
                            dr_dphi * cos_phi - r_f * sin_phi);
     *fa_out = M_ACOS(clip_scalar(-M_COS(heading), R(-1.0), R(1.0)));
     return 1;
+}
+
+/* metrics.py:120-145 -> (status, final_alpha, n_half) */
+static int schw_trace_ray(real M, real R_S, real r_obs, real alpha, real phi_max, real h_max,
+                          real *fa_out, int64_t *nh_out)
+{
+    real phi_f, u_f, w_f;
+    int status = schw_trace_orbit(M, R_S, r_obs, alpha, phi_max, h_max, &phi_f, &u_f, &w_f);
+    return schw_extract_angle(R_S, status, phi_f, u_f, w_f, fa_out, nh_out);
 }
 
 /* ------------------------------------------------------------------------ */
@@ -664,6 +686,62 @@ static int kerr_trace_dp45_h(real M, real a, real r_plus, real r_obs, real alpha
     return kerr_extract_angle(state, p_t, p_phi, M, a, r_capture, event_status, fa_out, nh_out);
 }
 
+/* One iteration of the loop of metrics.py:596-655 (its inner halve-and-retry loop included) on (state, lam).  Returns
+ * RK4_GO, RK4_DISK (the disk twin ended the ray), or the event that ends it: -1 captured, 1 escaped, 2 no step left,
+ * 0 invalid.  h_used: the step size of the last attempt; attempts: RK4 steps taken. */
+#define RK4_GO 4
+#define RK4_DISK 5
+static int rk4_iteration(real *state, real *lam_io, real p_t, real p_phi, real M, real a, real r_plus, real r_capture,
+                         real r_escape, real lambda_max, real h_base, real h_floor, int axis_refine, disk_hook *hk,
+                         real *h_used, int *attempts)
+{
+    real k1[5], k2[5], k3[5], k4[5], tmp[5], next_state[5];
+    real lam = *lam_io;
+    real h = h_base;
+    real remaining = lambda_max - lam;
+    *attempts = 0;
+    if (remaining < h) h = remaining;
+    *h_used = h;
+    if (h <= R(0.0)) return 2;
+    real r_curr = state[0];
+    if (r_curr < r_capture * R(4.0)) h = rmin(h, axis_refine ? R(0.20) : R(0.25));
+    if (r_curr < r_capture * R(2.0)) h = rmin(h, axis_refine ? R(0.08) : R(0.10));
+    if (r_curr < r_capture * R(1.2)) h = rmin(h, axis_refine ? R(0.03) : R(0.05));
+    real r_prev = state[0];
+    for (;;) {
+        *h_used = h;
+        ++*attempts;
+        rk4_step_kerr(state, h, p_t, p_phi, M, a, r_plus, k1, k2, k3, k4, tmp, next_state);
+        if (all_finite5(next_state) && next_state[0] > R(0.0)) break;
+        if (h <= h_floor) return 0;
+        h *= R(0.5);
+    }
+    real r_next = next_state[0];
+    if (r_prev > r_capture && r_next <= r_capture) {
+        real denom = r_next - r_prev;
+        real frac = (denom == R(0.0)) ? R(1.0) : (r_capture - r_prev) / denom;
+        frac = clip_scalar(frac, R(0.0), R(1.0));
+        if (hk && disk_step(hk, state, next_state, h, -1, frac)) return RK4_DISK;
+        for (int i = 0; i < 5; ++i) state[i] = state[i] + frac * (next_state[i] - state[i]);
+        *lam_io = lam + frac * h;
+        return -1;
+    }
+    if (r_prev < r_escape && r_next >= r_escape) {
+        real denom = r_next - r_prev;
+        real frac = (denom == R(0.0)) ? R(1.0) : (r_escape - r_prev) / denom;
+        frac = clip_scalar(frac, R(0.0), R(1.0));
+        if (hk && disk_step(hk, state, next_state, h, 1, frac)) return RK4_DISK;
+        for (int i = 0; i < 5; ++i) state[i] = state[i] + frac * (next_state[i] - state[i]);
+        *lam_io = lam + frac * h;
+        return 1;
+    }
+    if (hk && disk_step(hk, state, next_state, h, 0, R(1.0))) return RK4_DISK;
+    for (int i = 0; i < 5; ++i) state[i] = next_state[i];
+    *lam_io = lam + h;
+    if (!all_finite5(state)) return 0;
+    return RK4_GO;
+}
+
 /* metrics.py:570-658, fixed-step (radius-banded) RK4 -- the GPU fp32 kernel's spec */
 static int kerr_trace_rk4_h(real M, real a, real r_plus, real r_obs, real alpha, real theta,
                             real theta_obs, real lambda_max, real h_max, int axis_refine,
@@ -675,53 +753,21 @@ static int kerr_trace_rk4_h(real M, real a, real r_plus, real r_obs, real alpha,
     if (hk) { hk->p_t = p_t; hk->p_phi = p_phi; }
     real r_capture = r_plus * R(1.01);
     real r_escape = r_obs * R(2.0);
-    real k1[5], k2[5], k3[5], k4[5], tmp[5], next_state[5];
     real lam = R(0.0);
     int event_status = 2;
     real h_base = h_max;
     if (axis_refine) h_base = rmin(h_base, R(0.5));
     real h_floor = rmin(axis_refine ? R(0.01) : R(0.02), h_base);
     while (lam < lambda_max) {
-        real h = h_base;
-        real remaining = lambda_max - lam;
-        if (remaining < h) h = remaining;
-        if (h <= R(0.0)) break;
-        real r_curr = state[0];
-        if (r_curr < r_capture * R(4.0)) h = rmin(h, axis_refine ? R(0.20) : R(0.25));
-        if (r_curr < r_capture * R(2.0)) h = rmin(h, axis_refine ? R(0.08) : R(0.10));
-        if (r_curr < r_capture * R(1.2)) h = rmin(h, axis_refine ? R(0.03) : R(0.05));
-        real r_prev = state[0];
-        for (;;) {
-            rk4_step_kerr(state, h, p_t, p_phi, M, a, r_plus, k1, k2, k3, k4, tmp, next_state);
-            if (all_finite5(next_state) && next_state[0] > R(0.0)) break;
-            if (h <= h_floor) return 0;
-            h *= R(0.5);
-        }
-        real r_next = next_state[0];
-        if (r_prev > r_capture && r_next <= r_capture) {
-            real denom = r_next - r_prev;
-            real frac = (denom == R(0.0)) ? R(1.0) : (r_capture - r_prev) / denom;
-            frac = clip_scalar(frac, R(0.0), R(1.0));
-            if (hk && disk_step(hk, state, next_state, h, -1, frac)) return disk_end(hk, fa_out, nh_out);
-            for (int i = 0; i < 5; ++i) state[i] = state[i] + frac * (next_state[i] - state[i]);
-            lam += frac * h;
-            event_status = -1;
-            break;
-        }
-        if (r_prev < r_escape && r_next >= r_escape) {
-            real denom = r_next - r_prev;
-            real frac = (denom == R(0.0)) ? R(1.0) : (r_escape - r_prev) / denom;
-            frac = clip_scalar(frac, R(0.0), R(1.0));
-            if (hk && disk_step(hk, state, next_state, h, 1, frac)) return disk_end(hk, fa_out, nh_out);
-            for (int i = 0; i < 5; ++i) state[i] = state[i] + frac * (next_state[i] - state[i]);
-            lam += frac * h;
-            event_status = 1;
-            break;
-        }
-        if (hk && disk_step(hk, state, next_state, h, 0, R(1.0))) return disk_end(hk, fa_out, nh_out);
-        for (int i = 0; i < 5; ++i) state[i] = next_state[i];
-        lam += h;
-        if (!all_finite5(state)) return 0;
+        real h;
+        int attempts;
+        int ev = rk4_iteration(state, &lam, p_t, p_phi, M, a, r_plus, r_capture, r_escape, lambda_max, h_base, h_floor,
+                               axis_refine, hk, &h, &attempts);
+        if (ev == RK4_GO) continue;
+        if (ev == RK4_DISK) return disk_end(hk, fa_out, nh_out);
+        if (ev == 0) return 0;
+        if (ev != 2) event_status = ev;
+        break;
     }
     return kerr_extract_angle(state, p_t, p_phi, M, a, r_capture, event_status, fa_out, nh_out);
 }
@@ -846,6 +892,68 @@ void LTO_NAME(lto_dp45_decide)(const real *err_norm, const real *h, int64_t n, i
 void LTO_NAME(lto_kerr_rhs_n)(const real *states, const real *p_phi, int64_t n, real M, real a, real r_plus, real *out)
 {
     for (int64_t i = 0; i < n; ++i) kerr_rhs(states + 5 * i, R(-1.0), p_phi[i], M, a, r_plus, out + 5 * i);
+}
+
+/* One iteration of the fixed-step RK4 loop (metrics.py:596-655) from each of n rows, by the function the tracer itself
+ * runs (rk4_iteration): states (n,5), p_phi, lam (n), axis_refine (n) (NULL: 0), h_max the tracer's base step; p_t = -1.
+ *   state_out (n,5), lam_out (n): where the row is left (the interpolated point at a capture / escape);  h_out (n): the
+ *   step size of the last attempt;  outcome (n,2): [0] 4 goes on, 2 lam >= lambda_max or no step left, 0 invalid,
+ *   -1 captured, 1 escaped;  [1] the RK4 steps taken (1 + the halvings of the inner retry loop). */
+void LTO_NAME(lto_rk4_iteration)(const real *states, const real *p_phi, const real *lams, const uint8_t *axis_refine,
+                                 int64_t n, real M, real a, real r_plus, real r_obs, real lambda_max, real h_max,
+                                 real *state_out, real *lam_out, real *h_out, int32_t *outcome)
+{
+    const real r_capture = r_plus * R(1.01), r_escape = r_obs * R(2.0);
+    for (int64_t i = 0; i < n; ++i) {
+        const int refine = axis_refine && axis_refine[i];
+        real h_base = h_max;
+        if (refine) h_base = rmin(h_base, R(0.5));
+        const real h_floor = rmin(refine ? R(0.01) : R(0.02), h_base);
+        real st[5], lam = lams[i], h = R(0.0);
+        int attempts = 0, ev = 2;
+        for (int j = 0; j < 5; ++j) st[j] = states[5 * i + j];
+        if (lam < lambda_max)
+            ev = rk4_iteration(st, &lam, R(-1.0), p_phi[i], M, a, r_plus, r_capture, r_escape, lambda_max, h_base, h_floor,
+                               refine, NULL, &h, &attempts);
+        for (int j = 0; j < 5; ++j) state_out[5 * i + j] = st[j];
+        lam_out[i] = lam; h_out[i] = h;
+        outcome[2 * i] = ev; outcome[2 * i + 1] = attempts;
+    }
+}
+
+/* kerr_extract_angle (metrics.py:363-416) on n final records: states (n,5), p_phi (n), event (n) the tracer's
+ * event_status (-1, 1, or 2 at the range end); p_t = -1.  -> fa (n) (NaN unless set), nh (n), status (n). */
+void LTO_NAME(lto_kerr_extract)(const real *states, const real *p_phi, const int32_t *event, int64_t n, real M, real a,
+                                real r_plus, real *fa, int64_t *nh, int8_t *status)
+{
+    for (int64_t i = 0; i < n; ++i)
+        status[i] = (int8_t)kerr_extract_angle(states + 5 * i, R(-1.0), p_phi[i], M, a, r_plus * R(1.01), event[i], fa + i, nh + i);
+}
+
+/* The initial w0 of the Schwarzschild tracer (metrics.py:57-65) for n impact angles; ok (n) 0 where the ray is invalid. */
+void LTO_NAME(lto_schw_ic)(real M, real r_obs, const real *alphas, int64_t n, real *w0, uint8_t *ok)
+{
+    for (int64_t i = 0; i < n; ++i) ok[i] = (uint8_t)schw_ic(M, R(2.0) * M, r_obs, alphas[i], w0 + i);
+}
+
+/* The loop of the Schwarzschild tracer (metrics.py:66-117) from n supplied starts (phi, u, w), in place; status (n)
+ * 1 escaped, -1 captured, 2 range end; evals (n) the right-hand sides evaluated (4 per step, the ending one included). */
+void LTO_NAME(lto_schw_orbit)(real M, real r_obs, real phi_max, real h_max, int64_t n, real *phi, real *u, real *w,
+                              int8_t *status, uint32_t *evals)
+{
+    for (int64_t i = 0; i < n; ++i) {
+        lto_evals = 0;
+        status[i] = (int8_t)schw_orbit_loop(M, R(2.0) * M, r_obs, phi_max, h_max, phi + i, u + i, w + i);
+        evals[i] = lto_evals;
+    }
+}
+
+/* The tail of the Schwarzschild ray tracer (metrics.py:129-145) on n orbit results. */
+void LTO_NAME(lto_schw_extract)(real M, const int8_t *orbit_status, const real *phi, const real *u, const real *w, int64_t n,
+                                real *fa, int64_t *nh, int8_t *status)
+{
+    for (int64_t i = 0; i < n; ++i)
+        status[i] = (int8_t)schw_extract_angle(R(2.0) * M, orbit_status[i], phi[i], u[i], w[i], fa + i, nh + i);
 }
 
 int LTO_NAME(lto_kerr_ic)(real M, real a, real r_obs, real alpha, real theta, real theta_obs,

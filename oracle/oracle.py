@@ -223,6 +223,90 @@ def dp45_decide(err_norm, h, f32=False):
     return dec, out
 
 
+def _fn(name, f32, argtypes):
+    L = lib32() if f32 else lib()
+    fn = getattr(L, name + ("_f32" if f32 else ""))
+    fn.argtypes = argtypes
+    fn.restype = None
+    return fn
+
+
+_u8p, _i8p, _i32p, _i64p, _u32p = (C.POINTER(t) for t in (C.c_uint8, C.c_int8, C.c_int32, C.c_int64, C.c_uint32))
+
+
+def rk4_iteration(states, p_phi, lam, M, a, r_obs=50.0, lambda_max=5000.0, h_max=1.0, axis_refine=None, f32=False):
+    """One iteration of the fixed-step RK4 loop (metrics.py:596-655, its inner halve-and-retry loop included, p_t = -1) from
+    each of n rows, by the function the oracle's tracer itself runs (lto_rk4_iteration).
+    -> dict(state (n,5), lam (n,), h (n,) the step size of the last attempt, event (n,) in the kernels' codes (4 goes on,
+    2 out of range, 0 invalid, -1 captured, 1 escaped), attempts (n,) RK4 steps taken), float64 or float32 throughout."""
+    dt, pt, ct = _real(f32)
+    st = np.ascontiguousarray(states, dtype=dt).reshape(-1, 5)
+    n = st.shape[0]
+    pp = np.ascontiguousarray(np.broadcast_to(np.asarray(p_phi, dtype=dt), (n,)))
+    ll = np.ascontiguousarray(np.broadcast_to(np.asarray(lam, dtype=dt), (n,)))
+    rf = None if axis_refine is None else np.ascontiguousarray(np.broadcast_to(np.asarray(axis_refine), (n,))).astype(np.uint8)
+    so, lo, ho, oc = np.empty_like(st), np.empty(n, dtype=dt), np.empty(n, dtype=dt), np.empty((n, 2), dtype=np.int32)
+    fn = _fn("lto_rk4_iteration", f32, [pt, pt, pt, _u8p, C.c_int64, ct, ct, ct, ct, ct, ct, pt, pt, pt, _i32p])
+    fn(_ptr(st, pt), _ptr(pp, pt), _ptr(ll, pt), _ptr(rf, _u8p), n, M, a, M + np.sqrt(M * M - a * a), r_obs, lambda_max, h_max,
+       _ptr(so, pt), _ptr(lo, pt), _ptr(ho, pt), _ptr(oc, _i32p))
+    return dict(state=so, lam=lo, h=ho, event=oc[:, 0].copy(), attempts=oc[:, 1].copy())
+
+
+def kerr_extract(states, p_phi, event, M, a, f32=False):
+    """_kerr_extract_angle (metrics.py:363-416, p_t = -1) on n final records: states (n,5), p_phi (n,), event (n,) the
+    tracer's event_status (-1 captured, 1 escaped, 2 range end).  -> (final_alpha (n,) NaN unless set, n_half (n,) i64,
+    status (n,) i8)."""
+    dt, pt, ct = _real(f32)
+    st = np.ascontiguousarray(states, dtype=dt).reshape(-1, 5)
+    n = st.shape[0]
+    pp = np.ascontiguousarray(np.broadcast_to(np.asarray(p_phi, dtype=dt), (n,)))
+    ev = np.ascontiguousarray(np.broadcast_to(np.asarray(event), (n,))).astype(np.int32)
+    fa, nh, status = np.empty(n, dtype=dt), np.empty(n, dtype=np.int64), np.empty(n, dtype=np.int8)
+    fn = _fn("lto_kerr_extract", f32, [pt, pt, _i32p, C.c_int64, ct, ct, ct, pt, _i64p, _i8p])
+    fn(_ptr(st, pt), _ptr(pp, pt), _ptr(ev, _i32p), n, M, a, M + np.sqrt(M * M - a * a), _ptr(fa, pt), _ptr(nh, _i64p),
+       _ptr(status, _i8p))
+    return fa, nh, status
+
+
+def schw_ic(M, r_obs, alphas, f32=False):
+    """The Schwarzschild tracer's initial w0 (metrics.py:57-65) -> (w0 (n,), ok (n,) bool)."""
+    dt, pt, ct = _real(f32)
+    al = np.ascontiguousarray(alphas, dtype=dt).ravel()
+    w0, ok = np.empty(al.size, dtype=dt), np.empty(al.size, dtype=np.uint8)
+    _fn("lto_schw_ic", f32, [ct, ct, pt, C.c_int64, pt, _u8p])(M, r_obs, _ptr(al, pt), al.size, _ptr(w0, pt), _ptr(ok, _u8p))
+    return w0, ok.astype(bool)
+
+
+def schw_orbit(M, r_obs, u, w, phi=0.0, phi_max=50.0, h_max=0.05, f32=False):
+    """The loop of the Schwarzschild tracer (metrics.py:66-117) from n supplied starts (u, w, phi).
+    -> dict(u, w, phi (n,), status (n,) i8 (1 escaped, -1 captured, 2 range end), evals (n,) u32: four per step taken, the
+    step that ends the ray included)."""
+    dt, pt, ct = _real(f32)
+    uu = np.array(u, dtype=dt).ravel()
+    n = uu.size
+    ww = np.array(np.broadcast_to(np.asarray(w, dtype=dt), (n,)))
+    ph = np.array(np.broadcast_to(np.asarray(phi, dtype=dt), (n,)))
+    status, evals = np.empty(n, dtype=np.int8), np.empty(n, dtype=np.uint32)
+    fn = _fn("lto_schw_orbit", f32, [ct, ct, ct, ct, C.c_int64, pt, pt, pt, _i8p, _u32p])
+    fn(M, r_obs, phi_max, h_max, n, _ptr(ph, pt), _ptr(uu, pt), _ptr(ww, pt), _ptr(status, _i8p), _ptr(evals, _u32p))
+    return dict(u=uu, w=ww, phi=ph, status=status, evals=evals)
+
+
+def schw_extract(M, orbit_status, phi, u, w, f32=False):
+    """The tail of the Schwarzschild ray tracer (metrics.py:129-145) on n orbit results (status 0 invalid, -1, 1, 2).
+    -> (final_alpha (n,) NaN unless set, n_half (n,) i64, status (n,) i8)."""
+    dt, pt, ct = _real(f32)
+    ph = np.ascontiguousarray(phi, dtype=dt).ravel()
+    n = ph.size
+    uu = np.ascontiguousarray(np.broadcast_to(np.asarray(u, dtype=dt), (n,)))
+    ww = np.ascontiguousarray(np.broadcast_to(np.asarray(w, dtype=dt), (n,)))
+    os_ = np.ascontiguousarray(np.broadcast_to(np.asarray(orbit_status), (n,))).astype(np.int8)
+    fa, nh, status = np.empty(n, dtype=dt), np.empty(n, dtype=np.int64), np.empty(n, dtype=np.int8)
+    fn = _fn("lto_schw_extract", f32, [ct, _i8p, pt, pt, pt, C.c_int64, pt, _i64p, _i8p])
+    fn(M, _ptr(os_, _i8p), _ptr(ph, pt), _ptr(uu, pt), _ptr(ww, pt), n, _ptr(fa, pt), _ptr(nh, _i64p), _ptr(status, _i8p))
+    return fa, nh, status
+
+
 def kerr_ic(M, a, r_obs, alpha, theta, theta_obs):
     st = np.zeros(5)
     pt = C.c_double()
