@@ -35,17 +35,35 @@ static int check_spectrum_times(double t_start, double dt, int32_t n_times)
     return LT_OK;
 }
 
+// What a two-stage reduction of the stored hits (a spectrum, a visibility) refuses behind its resolves, in this order: the
+// times, then a null out unless there is no time, which is no error and no work.
+static int check_times_and_out(double t_start, double dt, int32_t n_times, const void *d_out)
+{
+    const int rc = check_spectrum_times(t_start, dt, n_times);
+    if (rc || n_times == 0) return rc;
+    return d_out ? LT_OK : fail(LT_ERR_INVALID_ARG, "null out");
+}
+
+// A host-pointer reduction through its _dev form (staged_call): the records, their counts and one more input -- the
+// polarization records, the map's texels, or {} for none (a null array stays null and takes no room) -- staged as in[0],
+// in[1], in[2], and the rows of `out` fetched.
+template <typename Dev>
+static int staged_hits_call(const float *hits, const uint8_t *n_hits, int32_t R, int32_t W, int32_t max_images, const HostArray &more,
+                            const HostArray &out, Dev dev)
+{
+    const size_t n = (size_t)R * W;
+    return staged_call({{hits, n, (size_t)max_images * 16}, {n_hits, n, 1}, more}, {out}, dev);
+}
+
 // A _dev spectrum behind its resolves: the refusals of the times and of a null out, then the times in batches whose
 // partials fit the slot's bounded workspace -- first_stage(grid, lds, first, partial) launches the emitter's kernel for the
-// times first ... first + grid.y - 1 -- each followed by k_spectrum_final into its rows.  A row does not depend on its batch.
+// times first ... first + grid.y - 1 -- each followed by k_sum_blocks into its rows.  A row does not depend on its batch.
 template <typename FirstStage>
 static int launch_spectrum(const SpectrumGrid &sg, int32_t max_images, double t_start, double dt, int32_t n_times, double *d_out,
                            FirstStage first_stage)
 {
-    int rc = check_spectrum_times(t_start, dt, n_times);
-    if (rc) return rc;
-    if (n_times == 0) return LT_OK;
-    if (!d_out) return fail(LT_ERR_INVALID_ARG, "null out");
+    int rc = check_times_and_out(t_start, dt, n_times, d_out);
+    if (rc || n_times == 0) return rc;
     const int n_keys = (sg.n_bins + 2) * sg.planes;
     const size_t per_time = (size_t)SP_BLOCKS * n_keys * sizeof(double);
     const int32_t batch = (int32_t)std::min<size_t>((size_t)n_times, std::max<size_t>(1, (size_t)LT_SPECTRUM_WORKSPACE_BYTES / per_time));
@@ -55,7 +73,7 @@ static int launch_spectrum(const SpectrumGrid &sg, int32_t max_images, double t_
     for (int32_t first = 0; first < n_times; first += batch) {
         const unsigned n = (unsigned)std::min(batch, n_times - first);
         first_stage(dim3(SP_BLOCKS, n), spectrum_lds_bytes(n_keys, max_images), (int)first, partial);
-        k_spectrum_final<<<dim3((unsigned)((n_keys + 255) / 256), n), 256>>>(partial, n_keys, d_out + (int64_t)first * n_keys);
+        k_sum_blocks<<<dim3((unsigned)((n_keys + 255) / 256), n), 256>>>(partial, n_keys, (int64_t)n * n_keys, d_out + (int64_t)first * n_keys);
     }
     HIP_TRY(hipGetLastError());
     return LT_OK;
@@ -89,8 +107,7 @@ extern "C" int lt_disk_spectrum(const float *hits, const uint8_t *n_hits, int32_
     SpectrumGrid sg;
     int rc = resolve_disk_spectrum(hits, R, W, max_images, metric, disk, &ds);
     if (rc || (rc = resolve_spectrum(spec, max_images, &sg))) return rc;
-    const size_t n = (size_t)R * W;
-    return staged_call({{hits, n, (size_t)max_images * 16}, {n_hits, n, 1}}, {{out, 1, spectrum_row_bytes(sg)}}, [&](void *const *in, void *const *out_) {
+    return staged_hits_call(hits, n_hits, R, W, max_images, {}, {out, 1, spectrum_row_bytes(sg)}, [&](void *const *in, void *const *out_) {
         return lt_disk_spectrum_dev((const float *)in[0], (const uint8_t *)in[1], R, W, max_images, metric, disk, spec, (double *)out_[0]);
     });
 }
@@ -118,9 +135,8 @@ extern "C" int lt_hotspot_spectrum(const float *hits, const uint8_t *n_hits, int
     SpectrumGrid sg;
     int rc = resolve_hotspot(hits, R, W, max_images, metric, disk, spot, &ds, &hs);
     if (rc || (rc = resolve_spectrum(spec, max_images, &sg)) || (rc = check_spectrum_times(t_start, dt, n_times))) return rc;
-    const size_t n = (size_t)R * W;
-    return staged_call({{hits, n, (size_t)max_images * 16}, {n_hits, n, 1}}, {{out, (size_t)n_times, spectrum_row_bytes(sg)}},
-                       [&](void *const *in, void *const *out_) {
+    return staged_hits_call(hits, n_hits, R, W, max_images, {}, {out, (size_t)n_times, spectrum_row_bytes(sg)},
+                            [&](void *const *in, void *const *out_) {
         return lt_hotspot_spectrum_dev((const float *)in[0], (const uint8_t *)in[1], R, W, max_images, metric, disk, spot, spec, t_start, dt,
                                        n_times, (double *)out_[0]);
     });
@@ -149,9 +165,8 @@ extern "C" int lt_diskmap_spectrum(const float *hits, const uint8_t *n_hits, int
     SpectrumGrid sg;
     int rc = resolve_diskmap(hits, R, W, max_images, metric, disk, map, texels, &ds, &dm);
     if (rc || (rc = resolve_spectrum(spec, max_images, &sg)) || (rc = check_spectrum_times(t_start, dt, n_times))) return rc;
-    const size_t n = (size_t)R * W;
-    return staged_call({{hits, n, (size_t)max_images * 16}, {n_hits, n, 1}, {texels, (size_t)map->n_r * map->n_phi, 4}},
-                       {{out, (size_t)n_times, spectrum_row_bytes(sg)}}, [&](void *const *in, void *const *out_) {
+    return staged_hits_call(hits, n_hits, R, W, max_images, {texels, (size_t)map->n_r * map->n_phi, 4},
+                            {out, (size_t)n_times, spectrum_row_bytes(sg)}, [&](void *const *in, void *const *out_) {
         return lt_diskmap_spectrum_dev((const float *)in[0], (const uint8_t *)in[1], R, W, max_images, metric, disk, map, (const float *)in[2],
                                        spec, t_start, dt, n_times, (double *)out_[0]);
     });

@@ -9,6 +9,13 @@ static_assert(VIS_BLOCKS == LT_VISIBILITY_BLOCKS && VIS_MAX_BASELINES == LT_VISI
 static_assert((size_t)LT_VISIBILITY_BLOCKS * LT_VISIBILITY_BATCH_TERMS * LT_VISIBILITY_MAX_BASELINES * 16 <= (size_t)LT_VISIBILITY_WORKSPACE_BYTES,
               "the partials of one batch at the most baselines fit the workspace");
 
+// The disk's refusals, shared with its polarized form: resolve_reshade's with no emitter.
+static int resolve_disk_visibility(const void *hits, int32_t R, int32_t W, int32_t max_images, const lt_metric *metric, const lt_disk *disk,
+                                   DiskShade *ds)
+{
+    return resolve_reshade("disk visibility", "records", hits != nullptr, R, W, max_images, metric, disk, ds, []() { return LT_OK; });
+}
+
 // The baselines' refusals (behind the emitter's resolve).
 static int resolve_baselines(const double *uv, int32_t n_baselines)
 {
@@ -37,43 +44,53 @@ template <typename F> static void with_visibility_terms(int terms, F f)
     else f(std::integral_constant<int, 16>{});
 }
 
-// A _dev visibility behind its resolves: the refusals of the times and of a null out, the baselines' upload to the head of
-// the slot's workspace, then the times in launches whose partials fit it -- first_stage(NT, grid, lds, vg, d_uv, partial)
-// launches the emitter's kernel for the batches of vg.times times from vg.first on -- each followed by k_visibility_final
-// into its rows.  A row depends neither on its batch nor on its launch.
-template <typename FirstStage>
-static int launch_visibility(int32_t W, int32_t max_images, const double *uv, int32_t n_baselines, int32_t split_orders, double t_start, double dt,
-                             int32_t n_times, double *d_out, FirstStage first_stage)
+// A _dev visibility of either family behind its resolves: the refusals of the times and of a null out, the baselines' upload
+// to the head of the slot's workspace, then the call's units -- a unit is a time here and a (time, plane) pair in
+// lt_api_visibility_stokes.inc: units_per_time of them per time, at most batch_units in a batch, unit_doubles doubles of
+// output each -- in launches whose partials fit the workspace.  with_terms(units, f) calls f(N) with the compile-time
+// constant for a batch of `units`; first_stage(N, grid, vg, d_uv, partial) launches the emitter's kernel for the batches of
+// vg.units units from vg.first on.  Each launch is followed by k_sum_blocks into its rows.  A row depends neither on its
+// batch nor on its launch.
+template <typename WithTerms, typename FirstStage>
+static int launch_visibility(int32_t W, int planes, const double *uv, int32_t n_baselines, double t_start, double dt, int32_t n_times,
+                             int units_per_time, int batch_units, int unit_doubles, double *d_out, WithTerms with_terms, FirstStage first_stage)
 {
-    int rc = check_spectrum_times(t_start, dt, n_times);
-    if (rc) return rc;
-    if (n_times == 0) return LT_OK;
-    if (!d_out) return fail(LT_ERR_INVALID_ARG, "null out");
-    const int planes = split_orders ? max_images : 1;
-    const int times = std::min<int>(n_times, lt_visibility_batch_times(max_images, split_orders));
-    const int row = times * planes * n_baselines * 2;                     // doubles of a full batch's output
+    int rc = check_times_and_out(t_start, dt, n_times, d_out);
+    if (rc || n_times == 0) return rc;
+    const int n_units = n_times * units_per_time;                         // <= 65535 x 8
+    const int units = std::min(n_units, batch_units);
+    const int row = units * unit_doubles;                                 // doubles of a full batch's output
     const size_t per_batch = (size_t)VIS_BLOCKS * row * sizeof(double);
-    const int n_batches = (n_times + times - 1) / times;
+    const int n_batches = (n_units + units - 1) / units;
     const int per_launch = (int)std::min<size_t>((size_t)n_batches, std::max<size_t>(1, (size_t)LT_VISIBILITY_WORKSPACE_BYTES / per_batch));
     const size_t uv_bytes = (size_t)LT_VISIBILITY_MAX_BASELINES * 16;
     StreamSlot *sl;
     if ((rc = get_slot(nullptr, &sl)) || (rc = grow(sl->visibility, uv_bytes + (size_t)per_launch * per_batch, nullptr))) return rc;
     double *d_uv = (double *)sl->visibility.p, *partial = (double *)((char *)sl->visibility.p + uv_bytes);
     HIP_TRY(hipMemcpyAsync(d_uv, uv, (size_t)n_baselines * 16, hipMemcpyHostToDevice, nullptr));
-    const int64_t out_row = (int64_t)planes * n_baselines * 2;            // doubles of one time
-    with_visibility_terms(times * planes, [&](auto nt) {
-        for (int first = 0; first < n_times; first += per_launch * times) {
-            const int left = n_times - first;
-            const unsigned n = (unsigned)std::min(per_launch, (left + times - 1) / times);
-            const VisibilityGrid vg{n_baselines, planes, times, n_times, first, W};
-            first_stage(nt, dim3(VIS_BLOCKS, n, (unsigned)((n_baselines + 255) / 256)), visibility_lds_bytes(decltype(nt)::value), vg, (const double *)d_uv,
-                        partial);
-            k_visibility_final<<<dim3((unsigned)((row + 255) / 256), n), 256>>>(partial, row, (int64_t)std::min<int>(left, (int)n * times) * out_row,
-                                                                             d_out + (int64_t)first * out_row);
+    with_terms(units, [&](auto nt) {
+        for (int first = 0; first < n_units; first += per_launch * units) {
+            const int left = n_units - first;
+            const unsigned n = (unsigned)std::min(per_launch, (left + units - 1) / units);
+            const VisibilityGrid vg{n_baselines, planes, units, n_units, first, W};
+            first_stage(nt, dim3(VIS_BLOCKS, n, (unsigned)((n_baselines + 255) / 256)), vg, (const double *)d_uv, partial);
+            k_sum_blocks<<<dim3((unsigned)((row + 255) / 256), n), 256>>>(partial, row, (int64_t)std::min<int>(left, (int)n * units) * unit_doubles,
+                                                                       d_out + (int64_t)first * unit_doubles);
         }
     });
     HIP_TRY(hipGetLastError());
     return LT_OK;
+}
+
+// The unpolarized family's units: a time is a unit of planes x n_baselines x 2 doubles, lt_visibility_batch_times of them in a
+// batch, NT from the batch's terms.
+template <typename FirstStage>
+static int launch_visibility_times(int32_t W, int32_t max_images, const double *uv, int32_t n_baselines, int32_t split_orders, double t_start,
+                                   double dt, int32_t n_times, double *d_out, FirstStage first_stage)
+{
+    const int planes = split_orders ? max_images : 1;
+    return launch_visibility(W, planes, uv, n_baselines, t_start, dt, n_times, 1, lt_visibility_batch_times(max_images, split_orders),
+                             planes * n_baselines * 2, d_out, [&](int times, auto f) { with_visibility_terms(times * planes, f); }, first_stage);
 }
 
 static size_t visibility_row_bytes(int32_t max_images, int32_t n_baselines, int32_t split_orders)
@@ -86,11 +103,12 @@ extern "C" int lt_disk_visibility_dev(const float *d_hits, const uint8_t *d_n_hi
                                       double *d_out)
 {
     DiskShade ds;
-    int rc = resolve_reshade("disk visibility", "records", d_hits != nullptr, R, W, max_images, metric, disk, &ds, []() { return LT_OK; });
+    int rc = resolve_disk_visibility(d_hits, R, W, max_images, metric, disk, &ds);
     if (rc || (rc = resolve_baselines(uv, n_baselines))) return rc;
-    return launch_visibility(W, max_images, uv, n_baselines, split_orders, 0.0, 0.0, 1, d_out,
-                             [&](auto nt, dim3 grid, size_t lds, const VisibilityGrid &vg, const double *d_uv, double *partial) {
-        k_disk_visibility_partial<decltype(nt)::value><<<grid, 256, lds>>>(d_hits, d_n_hits, (int64_t)R * W, max_images, ds, vg, d_uv, partial);
+    return launch_visibility_times(W, max_images, uv, n_baselines, split_orders, 0.0, 0.0, 1, d_out,
+                                   [&](auto nt, dim3 grid, const VisibilityGrid &vg, const double *d_uv, double *partial) {
+        constexpr int NT = decltype(nt)::value;
+        k_disk_visibility_partial<NT><<<grid, 256, visibility_lds_bytes(NT)>>>(d_hits, d_n_hits, (int64_t)R * W, max_images, ds, vg, d_uv, partial);
     });
 }
 
@@ -98,11 +116,10 @@ extern "C" int lt_disk_visibility(const float *hits, const uint8_t *n_hits, int3
                                   const lt_disk *disk, const double *uv, int32_t n_baselines, int32_t split_orders, double *out)
 {
     DiskShade ds;
-    int rc = resolve_reshade("disk visibility", "records", hits != nullptr, R, W, max_images, metric, disk, &ds, []() { return LT_OK; });
+    int rc = resolve_disk_visibility(hits, R, W, max_images, metric, disk, &ds);
     if (rc || (rc = resolve_baselines(uv, n_baselines))) return rc;
-    const size_t n = (size_t)R * W;
-    return staged_call({{hits, n, (size_t)max_images * 16}, {n_hits, n, 1}}, {{out, 1, visibility_row_bytes(max_images, n_baselines, split_orders)}},
-                       [&](void *const *in, void *const *out_) {
+    return staged_hits_call(hits, n_hits, R, W, max_images, {}, {out, 1, visibility_row_bytes(max_images, n_baselines, split_orders)},
+                            [&](void *const *in, void *const *out_) {
         return lt_disk_visibility_dev((const float *)in[0], (const uint8_t *)in[1], R, W, max_images, metric, disk, uv, n_baselines, split_orders,
                                       (double *)out_[0]);
     });
@@ -116,10 +133,11 @@ extern "C" int lt_hotspot_visibility_dev(const float *d_hits, const uint8_t *d_n
     HotspotShade hs;
     int rc = resolve_hotspot(d_hits, R, W, max_images, metric, disk, spot, &ds, &hs);
     if (rc || (rc = resolve_baselines(uv, n_baselines))) return rc;
-    return launch_visibility(W, max_images, uv, n_baselines, split_orders, t_start, dt, n_times, d_out,
-                             [&](auto nt, dim3 grid, size_t lds, const VisibilityGrid &vg, const double *d_uv, double *partial) {
-        k_hotspot_visibility_partial<decltype(nt)::value><<<grid, 256, lds>>>(d_hits, d_n_hits, (int64_t)R * W, max_images, hs, vg, t_start, dt, d_uv,
-                                                                             partial);
+    return launch_visibility_times(W, max_images, uv, n_baselines, split_orders, t_start, dt, n_times, d_out,
+                                   [&](auto nt, dim3 grid, const VisibilityGrid &vg, const double *d_uv, double *partial) {
+        constexpr int NT = decltype(nt)::value;
+        k_hotspot_visibility_partial<NT><<<grid, 256, visibility_lds_bytes(NT)>>>(d_hits, d_n_hits, (int64_t)R * W, max_images, hs, vg, t_start, dt,
+                                                                                 d_uv, partial);
     });
 }
 
@@ -131,9 +149,8 @@ extern "C" int lt_hotspot_visibility(const float *hits, const uint8_t *n_hits, i
     HotspotShade hs;
     int rc = resolve_hotspot(hits, R, W, max_images, metric, disk, spot, &ds, &hs);
     if (rc || (rc = resolve_baselines(uv, n_baselines)) || (rc = check_spectrum_times(t_start, dt, n_times))) return rc;
-    const size_t n = (size_t)R * W;
-    return staged_call({{hits, n, (size_t)max_images * 16}, {n_hits, n, 1}},
-                       {{out, (size_t)n_times, visibility_row_bytes(max_images, n_baselines, split_orders)}}, [&](void *const *in, void *const *out_) {
+    return staged_hits_call(hits, n_hits, R, W, max_images, {}, {out, (size_t)n_times, visibility_row_bytes(max_images, n_baselines, split_orders)},
+                            [&](void *const *in, void *const *out_) {
         return lt_hotspot_visibility_dev((const float *)in[0], (const uint8_t *)in[1], R, W, max_images, metric, disk, spot, uv, n_baselines,
                                          split_orders, t_start, dt, n_times, (double *)out_[0]);
     });
@@ -148,10 +165,11 @@ extern "C" int lt_diskmap_visibility_dev(const float *d_hits, const uint8_t *d_n
     DiskMapShade dm;
     int rc = resolve_diskmap(d_hits, R, W, max_images, metric, disk, map, d_texels, &ds, &dm);
     if (rc || (rc = resolve_baselines(uv, n_baselines))) return rc;
-    return launch_visibility(W, max_images, uv, n_baselines, split_orders, t_start, dt, n_times, d_out,
-                             [&](auto nt, dim3 grid, size_t lds, const VisibilityGrid &vg, const double *d_uv, double *partial) {
-        k_diskmap_visibility_partial<decltype(nt)::value><<<grid, 256, lds>>>(d_hits, d_n_hits, (int64_t)R * W, max_images, dm, d_texels, vg, t_start,
-                                                                             dt, d_uv, partial);
+    return launch_visibility_times(W, max_images, uv, n_baselines, split_orders, t_start, dt, n_times, d_out,
+                                   [&](auto nt, dim3 grid, const VisibilityGrid &vg, const double *d_uv, double *partial) {
+        constexpr int NT = decltype(nt)::value;
+        k_diskmap_visibility_partial<NT><<<grid, 256, visibility_lds_bytes(NT)>>>(d_hits, d_n_hits, (int64_t)R * W, max_images, dm, d_texels, vg,
+                                                                                 t_start, dt, d_uv, partial);
     });
 }
 
@@ -163,9 +181,8 @@ extern "C" int lt_diskmap_visibility(const float *hits, const uint8_t *n_hits, i
     DiskMapShade dm;
     int rc = resolve_diskmap(hits, R, W, max_images, metric, disk, map, texels, &ds, &dm);
     if (rc || (rc = resolve_baselines(uv, n_baselines)) || (rc = check_spectrum_times(t_start, dt, n_times))) return rc;
-    const size_t n = (size_t)R * W;
-    return staged_call({{hits, n, (size_t)max_images * 16}, {n_hits, n, 1}, {texels, (size_t)map->n_r * map->n_phi, 4}},
-                       {{out, (size_t)n_times, visibility_row_bytes(max_images, n_baselines, split_orders)}}, [&](void *const *in, void *const *out_) {
+    return staged_hits_call(hits, n_hits, R, W, max_images, {texels, (size_t)map->n_r * map->n_phi, 4},
+                            {out, (size_t)n_times, visibility_row_bytes(max_images, n_baselines, split_orders)}, [&](void *const *in, void *const *out_) {
         return lt_diskmap_visibility_dev((const float *)in[0], (const uint8_t *)in[1], R, W, max_images, metric, disk, map, (const float *)in[2], uv,
                                          n_baselines, split_orders, t_start, dt, n_times, (double *)out_[0]);
     });

@@ -13,7 +13,7 @@
 // alone owns the keys = i (mod 256); every work-item scans the four segments in order -- all lanes read the same entry,
 // a broadcast -- and adds the entries it owns, an unshared read-modify-write.  After the last chunk the workgroup
 // writes its accumulators as one partial.
-// Final stage (k_spectrum_final): one work-item per key adds a time's SP_BLOCKS partials in ascending block order.
+// Final stage (k_sum_blocks): one work-item per key adds a time's SP_BLOCKS partials in ascending block order.
 //
 // LDS is sized by the launch (spectrum_lds_bytes): at most 4112 x 8 (accumulators) + 2048 x (8 + 4) (entries) + 16 =
 // 57 488 B per workgroup, so two workgroups share a CU's 160 KiB even then; the default grid with three images takes
@@ -160,15 +160,19 @@ __global__ void __launch_bounds__(256) k_diskmap_spectrum_partial(const float *_
     spectrum_partial(hits, n_hits, n_px, max_images, sg, partial, [&](const float *rec) { return diskmap_intensity(dm, texels, t_obs, rec); });
 }
 
-// grid (ceil(n_keys / 256), times of this batch); out: the first row of this batch.
-__global__ void __launch_bounds__(256) k_spectrum_final(const double *__restrict__ partial, int n_keys, double *__restrict__ out)
+// The final stage of the two-stage reductions whose partials are (batch, block, row): the spectra's (a batch is a time, row
+// = n_keys) and the visibilities' (lt_visibility.hpp; VIS_BLOCKS == SP_BLOCKS is asserted there).  grid (ceil(row / 256),
+// batches of this launch); n_rows: the doubles this launch writes in all (its last batch may hold less than a row).  out: the
+// first row of this launch.  One work-item per double adds its SP_BLOCKS partials in ascending block order.
+__global__ void __launch_bounds__(256) k_sum_blocks(const double *__restrict__ partial, int row, int64_t n_rows, double *__restrict__ out)
 {
     const int k = (int)blockIdx.x * 256 + (int)threadIdx.x;
-    if (k >= n_keys) return;
-    const double *p = partial + (int64_t)blockIdx.y * SP_BLOCKS * n_keys + k;
+    const int64_t at = (int64_t)blockIdx.y * row + k;
+    if (k >= row || at >= n_rows) return;
+    const double *p = partial + (int64_t)blockIdx.y * SP_BLOCKS * row + k;
     double sum = 0.0;
-    for (int b = 0; b < SP_BLOCKS; ++b) sum += p[(int64_t)b * n_keys];
-    out[(int64_t)blockIdx.y * n_keys + k] = sum;
+    for (int b = 0; b < SP_BLOCKS; ++b) sum += p[(int64_t)b * row];
+    out[at] = sum;
 }
 
 } // namespace lt

@@ -1,14 +1,14 @@
 // lt_visibility_stokes.hpp -- polarized visibilities of the stored hits (include/ltrace.h, "polarized visibilities"): per
 // observer time, plane, Stokes parameter (I, Q, U) and baseline the sum of w exp(-2 pi i (u ix + v iy)) over the stored
 // slots, w_I the weight lt_*_visibility adds and w_Q, w_U = ((Pi sz sz) q) w_I, ((Pi sz sz) u) w_I from the records of
-// lt_trace_disk_pol.  The sibling of visibility_partial (lt_visibility.hpp), whose phase two, LDS layout, lists, chunk
-// order, block count and final stage (k_visibility_final) it keeps: the phases depend on (pixel, baseline) alone, so I, Q
-// and U of a hit are three terms of one batch and share the one sincospi.
+// lt_trace_disk_pol.  A second phase one for visibility_walk (lt_visibility.hpp), whose phase two, LDS layout, lists, chunk
+// order, block count and final stage (k_sum_blocks) it calls: the phases depend on (pixel, baseline) alone, so I, Q and U
+// of a hit are three terms of one batch and share the one sincospi.
 //
 // Batches.  (time, plane) is flattened into a pair index k = time x planes + plane over the whole call; a batch is a run of
 // up to VIS_STOKES_BATCH_PAIRS = 5 consecutive pairs, term = pair of the batch x 3 + stokes: 15 of VIS_BATCH_TERMS.  A
 // batch may begin and end in the middle of a time.  With the Stokes index innermost a batch's output rows are contiguous
-// in (n_times, planes, 3, n_baselines, 2), which is what k_visibility_final writes.  NP, the pairs a work-item keeps
+// in (n_times, planes, 3, n_baselines, 2), which is what k_sum_blocks writes.  NP, the pairs a work-item keeps
 // accumulators for (1, 2, 3 or 5; 6 NP doubles), is the call's pair count where that is below 5.
 //
 // Phase one evaluates w_I once per (pair's time, slot) with the unpolarized kernel's lambda and derives w_Q and w_U from it
@@ -16,7 +16,8 @@
 // a pixel that is kept here and not there (or the other way round) has weights of exactly 0 in the I terms, and
 // fma(0, c, re) = re.
 //
-// A sibling and not a parameter of visibility_partial: its three kernels keep their code.
+// Shared, not restated: everything but phase one is visibility_walk, the one text both families compile, so the guarantees
+// above hold by construction (profiles/visibility_fold_check.txt has the fold's check against the restated sibling).
 #pragma once
 #include "lt_polarization.hpp"
 #include "lt_visibility.hpp"
@@ -25,13 +26,6 @@ namespace lt {
 
 constexpr int VIS_STOKES_BATCH_PAIRS = 5; // LT_VISIBILITY_STOKES_BATCH_PAIRS
 static_assert(VIS_STOKES_BATCH_PAIRS * 3 <= VIS_BATCH_TERMS, "a batch of pairs lives within the unpolarized batch's terms");
-
-struct VisibilityStokesGrid {
-    int n_baselines, planes; // planes: 1, or max_images with split_orders
-    int pairs;               // (time, plane) pairs of a batch: <= VIS_STOKES_BATCH_PAIRS
-    int n_pairs, first;      // the call's pairs, n_times x planes, and the index of this launch's first one
-    int W;                   // the record buffer's width: pixel p is (p % W, p / W)
-};
 
 // (w_I, w_Q, w_U) of one slot that is not skipped, in stokes_weight's order: ((Pi sz) sz) q) w_I, every product rounded.
 // The empty asm keeps the products from being fused into the sum over a pixel's slots (-ffp-contract=fast, see
@@ -46,38 +40,20 @@ __device__ __forceinline__ void visibility_stokes_weights(double pol_frac, const
 }
 
 // The first stage.  weight(rec, t_obs): the emitter's unclamped intensity through one stored hit, as visibility_partial's.
-// partial: this launch's (batch, block, term, baseline) complex sums, term = pair of the batch x 3 + stokes.
+// A unit of the grid is a (time, plane) pair, term = pair of the batch x 3 + stokes.
 template <int NP, typename Weight>
 __device__ __forceinline__ void visibility_stokes_partial(const float *__restrict__ hits, const uint8_t *__restrict__ n_hits,
                                                           const float *__restrict__ pol, int64_t n_px, int max_images,
-                                                          const VisibilityStokesGrid &vg, double pol_frac, double t_start, double dt,
+                                                          const VisibilityGrid &vg, double pol_frac, double t_start, double dt,
                                                           const double *__restrict__ uv, double *__restrict__ partial, Weight weight)
 {
-    constexpr int NT = 3 * NP;
-    const int t = (int)threadIdx.x, wave = t >> 6, lane = t & 63;
-    double *sh_w = (double *)vis_lds, *sh_x = sh_w + NT * 256, *sh_y = sh_x + 256;
-    uint16_t *sh_list = (uint16_t *)(sh_y + 256);
-    int *sh_cnt = (int *)(sh_list + 256);
-    const int first = vg.first + (int)blockIdx.y * vg.pairs;             // this batch's first pair
-    const int pairs = min(min(vg.pairs, NP), vg.n_pairs - first);        // (the call's last batch may hold fewer)
-    const int terms = pairs * 3;                                         // <= NT
-    const int b = (int)blockIdx.z * 256 + t;
-    const bool owner = b < vg.n_baselines;
-    const bool wave_owns = (int)blockIdx.z * 256 + wave * 64 < vg.n_baselines;
-    const double u = owner ? uv[2 * b] : 0.0, v = owner ? uv[2 * b + 1] : 0.0;
-    double re[NT], im[NT];
-#pragma unroll
-    for (int i = 0; i < NT; ++i) {
-        re[i] = im[i] = 0.0;
-        sh_w[i * 256 + t] = 0.0; // (the terms beyond `terms` stay 0)
-    }
-    for (int64_t base = (int64_t)blockIdx.x * 256; base < n_px; base += (int64_t)256 * VIS_BLOCKS) {
-        // phase one: this pixel's weights, term-major, and the list of the pixels that hold light
-        const int64_t p = base + t;
+    const int first = vg.first + (int)blockIdx.y * vg.units;             // this batch's first pair
+    const int pairs = min(min(vg.units, NP), vg.n_units - first);        // (the call's last batch may hold fewer)
+    visibility_walk<3 * NP>(n_px, vg.W, vg.n_baselines, uv, partial, vg.units * 3, pairs * 3, [=](int64_t p, double *sh_w, int t) {
         const float *rec = hits + (p < n_px ? p : 0) * max_images * 4, *prec = pol + (p < n_px ? p : 0) * max_images * 4;
         const int ns = p < n_px ? stored_slots(rec, n_hits, p, max_images) : 0;
         bool has = false;
-        for (int i = 0; i < pairs; ++i) {
+        for (int i = 0; i < min(pairs, NP); ++i) { // (pairs <= NP already: the bound restated where the compiler sees it, 2 % at NP = 1)
             const int k = first + i, tt = k / vg.planes, plane = k - tt * vg.planes;
             const double t_obs = spectrum_time(t_start, dt, tt);
             double sum[3] = {0.0, 0.0, 0.0};
@@ -97,46 +73,15 @@ __device__ __forceinline__ void visibility_stokes_partial(const float *__restric
                 has |= !(sum[c] == 0.0); // (a NaN weight is kept: it is the emitter's, or the record's, answer)
             }
         }
-        sh_x[t] = (double)(p % vg.W);
-        sh_y[t] = (double)(p / vg.W);
-        const uint64_t kept = __ballot(has);
-        if (has) sh_list[wave * 64 + __popcll(kept & (((uint64_t)1 << lane) - 1))] = (uint16_t)t;
-        if (lane == 0) sh_cnt[wave] = __popcll(kept);
-        __syncthreads();
-        // phase two: one sincospi per kept pixel and owned baseline, the batch's terms from LDS
-        if (wave_owns) {
-            for (int s = 0; s < 4; ++s) {
-                const int n = sh_cnt[s];
-                for (int e = 0; e < n; ++e) {
-                    const int q = sh_list[s * 64 + e];
-                    double sn, cs;
-                    visibility_phase(u, v, sh_x[q], sh_y[q], &sn, &cs);
-#pragma unroll
-                    for (int i = 0; i < NT; ++i) {
-                        const double w = sh_w[i * 256 + q];
-                        re[i] = fma(w, cs, re[i]);
-                        im[i] = fma(-w, sn, im[i]);
-                    }
-                }
-            }
-        }
-        __syncthreads();
-    }
-    if (!owner) return;
-    double *mine = partial + (((int64_t)blockIdx.y * VIS_BLOCKS + blockIdx.x) * (vg.pairs * 3) * vg.n_baselines + b) * 2;
-#pragma unroll
-    for (int i = 0; i < NT; ++i)
-        if (i < terms) {
-            mine[(int64_t)i * vg.n_baselines * 2] = re[i];
-            mine[(int64_t)i * vg.n_baselines * 2 + 1] = im[i];
-        }
+        return has;
+    });
 }
 
 // The two emitters (the disk has one row and no time).
 template <int NP>
 __global__ void __launch_bounds__(256) k_disk_visibility_stokes_partial(const float *__restrict__ hits, const uint8_t *__restrict__ n_hits,
                                                                         const float *__restrict__ pol, int64_t n_px, int max_images,
-                                                                        DiskShade ds, double pol_frac, VisibilityStokesGrid vg,
+                                                                        DiskShade ds, double pol_frac, VisibilityGrid vg,
                                                                         const double *__restrict__ uv, double *__restrict__ partial)
 {
     visibility_stokes_partial<NP>(hits, n_hits, pol, n_px, max_images, vg, pol_frac, 0.0, 0.0, uv, partial,
@@ -146,7 +91,7 @@ __global__ void __launch_bounds__(256) k_disk_visibility_stokes_partial(const fl
 template <int NP>
 __global__ void __launch_bounds__(256) k_hotspot_visibility_stokes_partial(const float *__restrict__ hits, const uint8_t *__restrict__ n_hits,
                                                                            const float *__restrict__ pol, int64_t n_px, int max_images,
-                                                                           HotspotShade hs, double pol_frac, VisibilityStokesGrid vg,
+                                                                           HotspotShade hs, double pol_frac, VisibilityGrid vg,
                                                                            double t_start, double dt, const double *__restrict__ uv,
                                                                            double *__restrict__ partial)
 {

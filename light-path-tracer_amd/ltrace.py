@@ -1478,14 +1478,25 @@ def _spectrum_out(spec, max_images, n_times):
     return np.empty((max(int(n_times), 0), spectrum_planes(spec, min(max(int(max_images), 0), 8)), bins + 2))
 
 
+def _times(t_start, dt, n_times):
+    """The argument tail of a call over observer times t_start + i dt."""
+    return float(t_start), float(dt), int(n_times)
+
+
+def _spectrum(fn, records, emitter, spec, times):
+    """The host-pointer call fn(hits, n_hits, R, W, max_images, *emitter, spec, *times, out) of a spectrum -> its
+    (n_times, planes, n_bins + 2) output.  records: _hit_arrays' pair; emitter: metric, disk and the emitter's own
+    arguments as ctypes passes them; times: _times' tail, or () for the disk's one row."""
+    R, W, m = records[0].shape[:3]
+    out = _spectrum_out(spec, m, times[2] if times else 1)
+    _check(fn(*map(_np_ptr, records), R, W, m, *emitter, C.byref(spec), *times, _np_ptr(out)))
+    return out
+
+
 def disk_spectrum(hits, n_hits, metric, disk, spec):
     """The stationary disk's line profile from stored hits (lt_disk_spectrum) -> (planes, n_bins + 2) float64: column 0
     the underflow, the last the overflow; plane j the image order j with spec.split_orders."""
-    hits, nh = _hit_arrays(hits, n_hits)
-    R, W, m = hits.shape[:3]
-    out = _spectrum_out(spec, m, 1)
-    _check(load().lt_disk_spectrum(_np_ptr(hits), _np_ptr(nh), R, W, m, C.byref(metric), C.byref(disk), C.byref(spec), _np_ptr(out)))
-    return out[0]
+    return _spectrum(load().lt_disk_spectrum, _hit_arrays(hits, n_hits), (C.byref(metric), C.byref(disk)), spec, ())[0]
 
 
 def disk_spectrum_dev(d_hits, d_n_hits, rows, width, max_images, metric, disk, spec, d_out):
@@ -1496,36 +1507,28 @@ def disk_spectrum_dev(d_hits, d_n_hits, rows, width, max_images, metric, disk, s
 
 def hotspot_spectrum(hits, n_hits, metric, disk, spot, spec, t_start, dt, n_times):
     """The spot's dynamic spectrum (lt_hotspot_spectrum) -> (n_times, planes, n_bins + 2) float64 at t_start + i dt."""
-    hits, nh = _hit_arrays(hits, n_hits)
-    R, W, m = hits.shape[:3]
-    out = _spectrum_out(spec, m, n_times)
-    _check(load().lt_hotspot_spectrum(_np_ptr(hits), _np_ptr(nh), R, W, m, C.byref(metric), C.byref(disk), C.byref(spot),
-                                      C.byref(spec), float(t_start), float(dt), int(n_times), _np_ptr(out)))
-    return out
+    return _spectrum(load().lt_hotspot_spectrum, _hit_arrays(hits, n_hits), (C.byref(metric), C.byref(disk), C.byref(spot)), spec,
+                     _times(t_start, dt, n_times))
 
 
 def hotspot_spectrum_dev(d_hits, d_n_hits, rows, width, max_images, metric, disk, spot, spec, t_start, dt, n_times, d_out):
     """Device-pointer form of hotspot_spectrum (lt_hotspot_spectrum_dev); enqueues on the default stream."""
     _check(load().lt_hotspot_spectrum_dev(_p(d_hits), _p(d_n_hits), rows, width, max_images, C.byref(metric), C.byref(disk),
-                                          C.byref(spot), C.byref(spec), float(t_start), float(dt), int(n_times), _p(d_out)))
+                                          C.byref(spot), C.byref(spec), *_times(t_start, dt, n_times), _p(d_out)))
 
 
 def diskmap_spectrum(hits, n_hits, metric, disk, dmap, texels, spec, t_start, dt, n_times):
     """The map's dynamic spectrum (lt_diskmap_spectrum) -> (n_times, planes, n_bins + 2) float64 at t_start + i dt."""
-    hits, nh = _hit_arrays(hits, n_hits)
+    records = _hit_arrays(hits, n_hits)
     tex = _texel_array(dmap, texels)
-    R, W, m = hits.shape[:3]
-    out = _spectrum_out(spec, m, n_times)
-    _check(load().lt_diskmap_spectrum(_np_ptr(hits), _np_ptr(nh), R, W, m, C.byref(metric), C.byref(disk), C.byref(dmap),
-                                      _np_ptr(tex), C.byref(spec), float(t_start), float(dt), int(n_times), _np_ptr(out)))
-    return out
+    return _spectrum(load().lt_diskmap_spectrum, records, (C.byref(metric), C.byref(disk), C.byref(dmap), _np_ptr(tex)), spec,
+                     _times(t_start, dt, n_times))
 
 
 def diskmap_spectrum_dev(d_hits, d_n_hits, rows, width, max_images, metric, disk, dmap, d_texels, spec, t_start, dt, n_times, d_out):
     """Device-pointer form of diskmap_spectrum (lt_diskmap_spectrum_dev); enqueues on the default stream."""
     _check(load().lt_diskmap_spectrum_dev(_p(d_hits), _p(d_n_hits), rows, width, max_images, C.byref(metric), C.byref(disk),
-                                          C.byref(dmap), _p(d_texels), C.byref(spec), float(t_start), float(dt), int(n_times),
-                                          _p(d_out)))
+                                          C.byref(dmap), _p(d_texels), C.byref(spec), *_times(t_start, dt, n_times), _p(d_out)))
 
 
 # ---- visibilities (lt_disk_visibility, lt_hotspot_visibility, lt_diskmap_visibility) ---------------------------------------
@@ -1560,66 +1563,64 @@ def _complex(out):
     return np.ascontiguousarray(out).view(np.complex128)[..., 0]
 
 
+def _visibility(fn, records, emitter, uv, split_orders, times, out_of=_visibility_out):
+    """The host-pointer call fn(*records, R, W, max_images, *emitter, uv, n_baselines, split_orders, *times, out) of a
+    visibility -> complex128 of out_of's shape.  records: _hit_arrays' pair, with the polarization records behind it
+    where the call takes them; emitter: metric, disk and the emitter's own arguments as ctypes passes them; times:
+    _times' tail, or () for the disk's one row."""
+    uv = _uv_array(uv)
+    R, W, m = records[0].shape[:3]
+    out = out_of(uv, split_orders, m, times[2] if times else 1)
+    _check(fn(*map(_np_ptr, records), R, W, m, *emitter, _np_ptr(uv), uv.shape[0], int(bool(split_orders)), *times, _np_ptr(out)))
+    return _complex(out)
+
+
+def _visibility_dev(fn, d_records, shape, emitter, uv, split_orders, times, d_out):
+    """The device-pointer call of a visibility: d_records, shape = (rows, width, max_images), then as _visibility; uv stays
+    a host array."""
+    uv = _uv_array(uv)
+    _check(fn(*map(_p, d_records), *shape, *emitter, _np_ptr(uv), uv.shape[0], int(bool(split_orders)), *times, _p(d_out)))
+
+
 def disk_visibility(hits, n_hits, metric, disk, uv, split_orders=False):
     """The stationary disk's visibilities from stored hits (lt_disk_visibility) -> (planes, n_baselines) complex128.  uv
     (n_baselines, 2) float64 in cycles per pixel of the records, |u|, |v| <= 0.5; plane j the image order j with
     split_orders.  The phase's origin is pixel (0, 0)."""
-    hits, nh = _hit_arrays(hits, n_hits)
-    uv = _uv_array(uv)
-    R, W, m = hits.shape[:3]
-    out = _visibility_out(uv, split_orders, m, 1)
-    _check(load().lt_disk_visibility(_np_ptr(hits), _np_ptr(nh), R, W, m, C.byref(metric), C.byref(disk), _np_ptr(uv), uv.shape[0],
-                                     int(bool(split_orders)), _np_ptr(out)))
-    return _complex(out)[0]
+    return _visibility(load().lt_disk_visibility, _hit_arrays(hits, n_hits), (C.byref(metric), C.byref(disk)), uv, split_orders, ())[0]
 
 
 def disk_visibility_dev(d_hits, d_n_hits, rows, width, max_images, metric, disk, uv, split_orders, d_out):
     """Device-pointer form of disk_visibility (lt_disk_visibility_dev): uv stays a host array, d_out holds
     (1, planes, n_baselines, 2) float64; enqueues on the default stream."""
-    uv = _uv_array(uv)
-    _check(load().lt_disk_visibility_dev(_p(d_hits), _p(d_n_hits), rows, width, max_images, C.byref(metric), C.byref(disk), _np_ptr(uv),
-                                         uv.shape[0], int(bool(split_orders)), _p(d_out)))
+    _visibility_dev(load().lt_disk_visibility_dev, (d_hits, d_n_hits), (rows, width, max_images), (C.byref(metric), C.byref(disk)), uv,
+                    split_orders, (), d_out)
 
 
 def hotspot_visibility(hits, n_hits, metric, disk, spot, uv, split_orders, t_start, dt, n_times):
     """The spot's visibilities (lt_hotspot_visibility) -> (n_times, planes, n_baselines) complex128 at t_start + i dt."""
-    hits, nh = _hit_arrays(hits, n_hits)
-    uv = _uv_array(uv)
-    R, W, m = hits.shape[:3]
-    out = _visibility_out(uv, split_orders, m, n_times)
-    _check(load().lt_hotspot_visibility(_np_ptr(hits), _np_ptr(nh), R, W, m, C.byref(metric), C.byref(disk), C.byref(spot), _np_ptr(uv),
-                                        uv.shape[0], int(bool(split_orders)), float(t_start), float(dt), int(n_times), _np_ptr(out)))
-    return _complex(out)
+    return _visibility(load().lt_hotspot_visibility, _hit_arrays(hits, n_hits), (C.byref(metric), C.byref(disk), C.byref(spot)), uv,
+                       split_orders, _times(t_start, dt, n_times))
 
 
 def hotspot_visibility_dev(d_hits, d_n_hits, rows, width, max_images, metric, disk, spot, uv, split_orders, t_start, dt, n_times, d_out):
     """Device-pointer form of hotspot_visibility (lt_hotspot_visibility_dev); uv stays a host array."""
-    uv = _uv_array(uv)
-    _check(load().lt_hotspot_visibility_dev(_p(d_hits), _p(d_n_hits), rows, width, max_images, C.byref(metric), C.byref(disk),
-                                            C.byref(spot), _np_ptr(uv), uv.shape[0], int(bool(split_orders)), float(t_start), float(dt),
-                                            int(n_times), _p(d_out)))
+    _visibility_dev(load().lt_hotspot_visibility_dev, (d_hits, d_n_hits), (rows, width, max_images),
+                    (C.byref(metric), C.byref(disk), C.byref(spot)), uv, split_orders, _times(t_start, dt, n_times), d_out)
 
 
 def diskmap_visibility(hits, n_hits, metric, disk, dmap, texels, uv, split_orders, t_start, dt, n_times):
     """The map's visibilities (lt_diskmap_visibility) -> (n_times, planes, n_baselines) complex128 at t_start + i dt."""
-    hits, nh = _hit_arrays(hits, n_hits)
+    records = _hit_arrays(hits, n_hits)
     tex = _texel_array(dmap, texels)
-    uv = _uv_array(uv)
-    R, W, m = hits.shape[:3]
-    out = _visibility_out(uv, split_orders, m, n_times)
-    _check(load().lt_diskmap_visibility(_np_ptr(hits), _np_ptr(nh), R, W, m, C.byref(metric), C.byref(disk), C.byref(dmap), _np_ptr(tex),
-                                        _np_ptr(uv), uv.shape[0], int(bool(split_orders)), float(t_start), float(dt), int(n_times),
-                                        _np_ptr(out)))
-    return _complex(out)
+    return _visibility(load().lt_diskmap_visibility, records, (C.byref(metric), C.byref(disk), C.byref(dmap), _np_ptr(tex)), uv,
+                       split_orders, _times(t_start, dt, n_times))
 
 
 def diskmap_visibility_dev(d_hits, d_n_hits, rows, width, max_images, metric, disk, dmap, d_texels, uv, split_orders, t_start, dt, n_times,
                            d_out):
     """Device-pointer form of diskmap_visibility (lt_diskmap_visibility_dev); uv stays a host array."""
-    uv = _uv_array(uv)
-    _check(load().lt_diskmap_visibility_dev(_p(d_hits), _p(d_n_hits), rows, width, max_images, C.byref(metric), C.byref(disk),
-                                            C.byref(dmap), _p(d_texels), _np_ptr(uv), uv.shape[0], int(bool(split_orders)), float(t_start),
-                                            float(dt), int(n_times), _p(d_out)))
+    _visibility_dev(load().lt_diskmap_visibility_dev, (d_hits, d_n_hits), (rows, width, max_images),
+                    (C.byref(metric), C.byref(disk), C.byref(dmap), _p(d_texels)), uv, split_orders, _times(t_start, dt, n_times), d_out)
 
 
 # ---- polarized visibilities (lt_disk_visibility_stokes, lt_hotspot_visibility_stokes) -------------------------------------
@@ -1635,50 +1636,40 @@ def _visibility_stokes_out(uv, split_orders, max_images, n_times):
     return np.empty((max(int(n_times), 0), shape[1], 3, shape[2], 2))
 
 
+def _pol_records(hits, n_hits, pol):
+    """_hit_arrays' pair with the checked polarization records behind it."""
+    records = _hit_arrays(hits, n_hits)
+    return records + (_pol_array(pol, records[0]),)
+
+
 def disk_visibility_stokes(hits, n_hits, pol, metric, disk, field, uv, split_orders=False):
     """The stationary disk's polarized visibilities (lt_disk_visibility_stokes) -> (planes, 3, n_baselines) complex128, the
     Stokes axis (I, Q, U); pol the (rows, W, max_images, 4) records of trace_disk_pol, the rest as disk_visibility.  The I
     plane has disk_visibility's bits."""
-    hits, nh = _hit_arrays(hits, n_hits)
-    pol = _pol_array(pol, hits)
-    uv = _uv_array(uv)
-    R, W, m = hits.shape[:3]
-    out = _visibility_stokes_out(uv, split_orders, m, 1)
-    _check(load().lt_disk_visibility_stokes(_np_ptr(hits), _np_ptr(nh), _np_ptr(pol), R, W, m, C.byref(metric), C.byref(disk),
-                                            C.byref(field), _np_ptr(uv), uv.shape[0], int(bool(split_orders)), _np_ptr(out)))
-    return _complex(out)[0]
+    return _visibility(load().lt_disk_visibility_stokes, _pol_records(hits, n_hits, pol), (C.byref(metric), C.byref(disk), C.byref(field)),
+                       uv, split_orders, (), _visibility_stokes_out)[0]
 
 
 def disk_visibility_stokes_dev(d_hits, d_n_hits, d_pol, rows, width, max_images, metric, disk, field, uv, split_orders, d_out):
     """Device-pointer form of disk_visibility_stokes (lt_disk_visibility_stokes_dev): uv stays a host array, d_out holds
     (1, planes, 3, n_baselines, 2) float64; enqueues on the default stream."""
-    uv = _uv_array(uv)
-    _check(load().lt_disk_visibility_stokes_dev(_p(d_hits), _p(d_n_hits), _p(d_pol), rows, width, max_images, C.byref(metric),
-                                                C.byref(disk), C.byref(field), _np_ptr(uv), uv.shape[0], int(bool(split_orders)),
-                                                _p(d_out)))
+    _visibility_dev(load().lt_disk_visibility_stokes_dev, (d_hits, d_n_hits, d_pol), (rows, width, max_images),
+                    (C.byref(metric), C.byref(disk), C.byref(field)), uv, split_orders, (), d_out)
 
 
 def hotspot_visibility_stokes(hits, n_hits, pol, metric, disk, spot, field, uv, split_orders, t_start, dt, n_times):
     """The spot's polarized visibilities (lt_hotspot_visibility_stokes) -> (n_times, planes, 3, n_baselines) complex128 at
     t_start + i dt, the Stokes axis (I, Q, U).  The I plane has hotspot_visibility's bits."""
-    hits, nh = _hit_arrays(hits, n_hits)
-    pol = _pol_array(pol, hits)
-    uv = _uv_array(uv)
-    R, W, m = hits.shape[:3]
-    out = _visibility_stokes_out(uv, split_orders, m, n_times)
-    _check(load().lt_hotspot_visibility_stokes(_np_ptr(hits), _np_ptr(nh), _np_ptr(pol), R, W, m, C.byref(metric), C.byref(disk),
-                                               C.byref(spot), C.byref(field), _np_ptr(uv), uv.shape[0], int(bool(split_orders)),
-                                               float(t_start), float(dt), int(n_times), _np_ptr(out)))
-    return _complex(out)
+    return _visibility(load().lt_hotspot_visibility_stokes, _pol_records(hits, n_hits, pol),
+                       (C.byref(metric), C.byref(disk), C.byref(spot), C.byref(field)), uv, split_orders, _times(t_start, dt, n_times),
+                       _visibility_stokes_out)
 
 
 def hotspot_visibility_stokes_dev(d_hits, d_n_hits, d_pol, rows, width, max_images, metric, disk, spot, field, uv, split_orders, t_start, dt,
                                   n_times, d_out):
     """Device-pointer form of hotspot_visibility_stokes (lt_hotspot_visibility_stokes_dev); uv stays a host array."""
-    uv = _uv_array(uv)
-    _check(load().lt_hotspot_visibility_stokes_dev(_p(d_hits), _p(d_n_hits), _p(d_pol), rows, width, max_images, C.byref(metric),
-                                                   C.byref(disk), C.byref(spot), C.byref(field), _np_ptr(uv), uv.shape[0],
-                                                   int(bool(split_orders)), float(t_start), float(dt), int(n_times), _p(d_out)))
+    _visibility_dev(load().lt_hotspot_visibility_stokes_dev, (d_hits, d_n_hits, d_pol), (rows, width, max_images),
+                    (C.byref(metric), C.byref(disk), C.byref(spot), C.byref(field)), uv, split_orders, _times(t_start, dt, n_times), d_out)
 
 
 # ---- supersampled frames (lt_render_aa) ---------------------------------------------------------------------------

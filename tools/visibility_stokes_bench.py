@@ -46,7 +46,7 @@ def plain_batches(n_times, planes):
 
 
 def stokes_batches(n_times, planes):
-    """Accumulators of every batch of lt_hotspot_visibility_stokes, as launch_visibility_stokes forms them."""
+    """Accumulators of every batch of lt_hotspot_visibility_stokes, as launch_visibility forms them from pairs."""
     pairs = n_times * planes
     per = min(pairs, STOKES_PAIRS)
     np_ = next(k for k in (1, 2, 3, 5) if k >= per)
