@@ -186,6 +186,12 @@ int lt_trace_batch_kerr_general_probe(double M, double a, double r_obs, const do
  * changes no output and no counter but LT_STAT_EQ_ITERS.  Returns the previous setting. */
 int lt_set_eq_streak(int on);
 
+/* The unit-step form of that loop, taken by a wavefront whose rays all step by exactly 1 and are far from
+ * the end of the affine range: on != 0 enables it, 0 disables it, for every Kerr launch enqueued afterwards (the default:
+ * on, or LT_UNIT_STREAK=0/1 in the environment when the library is loaded).  It changes no output and no counter.
+ * Returns the previous setting. */
+int lt_set_unit_streak(int on);
+
 /* Device probe of the float32 sincos for the tests: every float32 x with bit pattern in [bits_lo, bits_hi] goes through
  * the general form and through the fixed-quadrant form.  out[0] = values compared, out[1] = values for which either
  * result differs in any bit, out[2] = values that do not reduce to the quadrant k = 1, out[3] = bit pattern of the

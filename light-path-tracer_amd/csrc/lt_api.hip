@@ -325,6 +325,26 @@ extern "C" int lt_set_eq_streak(int on)
     return before;
 }
 
+// LT_UNIT_STREAK=0 / lt_set_unit_streak(0): the fixed-quadrant loop never takes its unit-step form (A/B measurements,
+// bisecting, tests/test_gpu_unit_streak.py).  Read by make_kerr for every launch.
+static std::atomic<int> g_unit_streak{-1}; // -1: not yet read from the environment
+static bool unit_streak_enabled()
+{
+    int v = g_unit_streak.load(std::memory_order_relaxed);
+    if (v < 0) {
+        v = env_int("LT_UNIT_STREAK", 1) != 0;
+        int unset = -1;
+        if (!g_unit_streak.compare_exchange_strong(unset, v)) v = unset;
+    }
+    return v != 0;
+}
+extern "C" int lt_set_unit_streak(int on)
+{
+    const int before = unit_streak_enabled();
+    g_unit_streak.store(on != 0);
+    return before;
+}
+
 // Frames that reused the ray records of their slot / that ran k_prologue_camera, since the library was loaded.
 static uint64_t g_ic_hits = 0, g_ic_misses = 0; // (under g_mu)
 extern "C" void lt_ic_reuse_counts(uint64_t *hits, uint64_t *misses)
@@ -541,6 +561,10 @@ template <typename T> static KerrConsts<T> make_kerr(const MetricConsts &mc, dou
     const bool eq = sizeof(T) == 4 && eq_streak_enabled();
     k.eq_lo = eq ? (T)M<float>::EQ_BAND_LO : (T)1;
     k.eq_hi = eq ? (T)M<float>::EQ_BAND_HI : (T)0;
+    // the unit-step form of that loop: the loop's own range limit lambda_max - h_base at h_base = 1, in the kernel's
+    // arithmetic; never taken with the switch off or beyond the range its margin is proved for (kerr_rk4_streak)
+    const bool unit = eq && unit_streak_enabled() && k.lambda_max <= (T)8192;
+    k.unit_lam = unit ? (T)(k.lambda_max - (T)1) : -(T)INFINITY;
     return k;
 }
 

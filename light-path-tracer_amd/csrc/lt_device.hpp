@@ -196,6 +196,11 @@ __device__ __forceinline__ double unfused(double x)
     asm volatile("" : "+v"(x));
     return x;
 }
+__device__ __forceinline__ float unfused(float x)
+{
+    asm("" : "+v"(x));
+    return x;
+}
 
 // sin and cos of a float64 angle of a few radians, correctly rounded (against mpmath: every one of 40 000 arguments; glibc's
 // own differ from them on 1 in 1000): for what runs once per ray and has to give the reference's bits -- the prologue, whose
@@ -305,6 +310,7 @@ template <typename T> struct KerrConsts {
     T h_max;       // 1.0 (metrics.py:677)
     T rc4, rc2, rc12; // r_capture * 4, * 2, * 1.2 (metrics.py:606-611)
     T eq_lo, eq_hi;   // polar-angle band of the float32 streak's fixed-quadrant loop (kerr_rk4_streak); lo >= hi: never taken
+    T unit_lam;       // lambda_max - 1, the range limit of that loop's unit-step form (kerr_rk4_streak); -inf: never taken
 };
 
 // A VALU instruction with an SGPR source runs on the half-rate pipe on gfx950 (v_fma_f32 with an
@@ -498,10 +504,20 @@ template <typename T> struct State5 {
 // the checked one) -- one test per step instead of seven, for the same results.
 //
 // Q1 = true: the caller knows that y.th reduces to the quadrant k = 1 (M<T>::sincos_q1); same bits, fewer instructions.
-template <typename T, bool CHECKED, bool Q1 = false>
+//
+// UNIT = true: the caller knows that h == 1 in every lane (the `h` passed is not read).  h / 2 and h / 6 are then
+// literals of the instructions instead of per-lane registers -- T(0.5) * T(1) is 0.5 and T(1) * T(1.0 / 6.0) is
+// T(1.0 / 6.0), both exactly, so they are the multipliers of the general form at h = 1 -- and stage 4 needs no multiply at all: fma(1, k, y) is
+// k + y rounded once, and d4 = 1 * k_th is k_th.  Same bits, one instruction fewer, and fourteen three-register fmas
+// become the literal form.  The one trap is stage 4's radius: k_r is the ROUNDED product Delta * iSpr there (it also
+// feeds the running sum), and under -ffp-contract=fast a plain k_r + y.r is compiled as fma(Delta, iSpr, y.r); the
+// product goes through `unfused` first.  (k_pr and k_pth end in a product as well -- -iS * (...) -- same treatment.)
+template <typename T, bool CHECKED, bool Q1 = false, bool UNIT = false>
 __device__ __forceinline__ State5<T> kerr_rk4_step_impl(const KerrConsts<T> &k, const RayConsts<T> &rc,
-                                                        const State5<T> &y, T h, T &min_r, T &max_d)
+                                                        const State5<T> &y, T h_in, T &min_r, T &max_d)
 {
+    static_assert(!UNIT || sizeof(T) == 4, "the unit-step form is float32 only");
+    const T h = UNIT ? T(1) : h_in;
     T k_r, k_th, k_ph, k_pr, k_pth;
     T a_r, a_th, a_ph, a_pr, a_pth; // running k1 + 2 k2 + 2 k3 + k4
     T s0, c0, s, c;
@@ -523,10 +539,17 @@ __device__ __forceinline__ State5<T> kerr_rk4_step_impl(const KerrConsts<T> &k, 
     T r3 = t_r;
     sincos_shift<T, CHECKED>(y.th, s0, c0, d3, s, c);
     kerr_rhs_sc<T, CHECKED>(k, rc, t_r, s, c, t_pr, t_pth, k_r, k_th, k_ph, k_pr, k_pth);
+    if constexpr (UNIT) { k_r = unfused(k_r); k_pr = unfused(k_pr); k_pth = unfused(k_pth); } // (before their first use: no copy)
     a_r = M<T>::fma(T(2), k_r, a_r); a_th = M<T>::fma(T(2), k_th, a_th); a_ph = M<T>::fma(T(2), k_ph, a_ph);
     a_pr = M<T>::fma(T(2), k_pr, a_pr); a_pth = M<T>::fma(T(2), k_pth, a_pth);
-    t_r = M<T>::fma(h, k_r, y.r); t_pr = M<T>::fma(h, k_pr, y.pr); t_pth = M<T>::fma(h, k_pth, y.pth);
-    T d4 = h * k_th;
+    T d4;
+    if constexpr (UNIT) {
+        t_r = k_r + y.r; t_pr = k_pr + y.pr; t_pth = k_pth + y.pth;
+        d4 = k_th;
+    } else {
+        t_r = M<T>::fma(h, k_r, y.r); t_pr = M<T>::fma(h, k_pr, y.pr); t_pth = M<T>::fma(h, k_pth, y.pth);
+        d4 = h * k_th;
+    }
     sincos_shift<T, CHECKED>(y.th, s0, c0, d4, s, c);
     const KerrRhsParts<T> k4 = kerr_rhs_parts<T, CHECKED>(k, rc, t_r, s, c, t_pr, t_pth);
     if (!CHECKED) {
@@ -554,11 +577,11 @@ __device__ __forceinline__ State5<T> kerr_rk4_step(const KerrConsts<T> &k, const
 }
 
 // The branch-free variant; valid for a lane iff min_r > k.r_cut and max_d <= 0.25 (kerr_rk4_step_ok).
-template <typename T, bool Q1 = false>
+template <typename T, bool Q1 = false, bool UNIT = false>
 __device__ __forceinline__ State5<T> kerr_rk4_step_fast(const KerrConsts<T> &k, const RayConsts<T> &rc,
                                                         const State5<T> &y, T h, T &min_r, T &max_d)
 {
-    return kerr_rk4_step_impl<T, false, Q1>(k, rc, y, h, min_r, max_d);
+    return kerr_rk4_step_impl<T, false, Q1, UNIT>(k, rc, y, h, min_r, max_d);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -712,14 +735,15 @@ template <> struct StepCarry<float, true> {
     }
 };
 
-// LONE = true: the packed form where there is one (float32); the scalar step otherwise (Q1: its fixed-quadrant form)
-template <typename T, bool LONE, bool Q1 = false>
+// LONE = true: the packed form where there is one (float32); the scalar step otherwise (Q1: its fixed-quadrant form,
+// UNIT: its unit-step form)
+template <typename T, bool LONE, bool Q1 = false, bool UNIT = false>
 __device__ __forceinline__ State5<T> kerr_rk4_step_fast_for(const KerrConsts<T> &k, const RayConsts<T> &rc, const State5<T> &y,
                                                             const StepCarry<T, LONE> &cin, T h, T &min_r, T &max_d,
                                                             StepCarry<T, LONE> &cout)
 {
     if constexpr (LONE && sizeof(T) == 4) return kerr_rk4_step_fast_pk(k, rc, y, cin.cs, h, min_r, max_d, cout.cs);
-    else return kerr_rk4_step_fast<T, Q1>(k, rc, y, h, min_r, max_d);
+    else return kerr_rk4_step_fast<T, Q1, UNIT>(k, rc, y, h, min_r, max_d);
 }
 
 // Step-size rule of the reference's fixed-step RK4 tracer (metrics.py:597-611): h_base, capped in
@@ -801,7 +825,12 @@ template <typename T> __device__ __forceinline__ void ray_start(const KerrConsts
 // call -- the old F5 itself is therefore ANDed into the lane's predicate (F5 implies the shorter sum finite: rounding
 // is monotonic and every term is >= 0).  tests/test_streak_predicate_host.py holds both forms to the old predicate on
 // a grid of edge values.
-template <typename T, bool LONE, bool EQ>
+//
+// UNIT (with EQ only): the form for a call in which every active lane steps by exactly 1 and none can come within a
+// step of the range end -- kerr_rk4_streak decides both once per call and says why they hold for all of it.  The step
+// takes its unit form (kerr_rk4_step_impl), lam advances by the literal, and `lam <= lam_limit` leaves the test: it
+// is true on every attempt of such a call.  Nothing else differs, so neither an output nor a counter can tell.
+template <typename T, bool LONE, bool EQ, bool UNIT = false>
 __device__ __forceinline__ bool kerr_rk4_streak_loop(const KerrConsts<T> &k, const RayConsts<T> &rc, RayState<T> &s,
                                                      uint32_t max_steps, uint32_t &done)
 {
@@ -812,25 +841,37 @@ __device__ __forceinline__ bool kerr_rk4_streak_loop(const KerrConsts<T> &k, con
     // fails the test and takes its last, shorter step in the general iteration.  With h invariant the step's h / 2 and
     // h / 6, the subtraction and the min leave the loop.
     // in_band: with EQ, the other half of the continue condition -- the new angle is inside the band.
+    static_assert(!UNIT || (EQ && !LONE && sizeof(T) == 4), "the unit-step form belongs to the float32 fixed-quadrant loop");
     const T lam_limit = k.lambda_max - rc.hb;
     const uint64_t all = lane_mask(true);
     auto attempt = [&](const State5<T> &from, const StepCarry<T, LONE> &cfrom, T lam, State5<T> &to, StepCarry<T, LONE> &cto, T &h) -> uint64_t {
-        h = rc.hb;
+        h = UNIT ? T(1) : rc.hb;
         T min_r, max_d;
-        to = kerr_rk4_step_fast_for<T, LONE, EQ>(k, rc, from, cfrom, h, min_r, max_d, cto);
+        to = kerr_rk4_step_fast_for<T, LONE, EQ, UNIT>(k, rc, from, cfrom, h, min_r, max_d, cto);
         T mag = (M<T>::abs(to.ph) + M<T>::abs(to.pr)) + M<T>::abs(to.pth);
         if constexpr (!EQ) mag = ((M<T>::abs(to.th) + M<T>::abs(to.ph)) + M<T>::abs(to.pr)) + M<T>::abs(to.pth);
         ++done;
         // (mag >= 0 or NaN: an ordered compare with the largest finite number is the finiteness test)
-        return lane_mask(lam <= lam_limit) & lane_mask(mag <= M<T>::LARGEST) & lane_mask(to.r >= k.rc4) &
+        return (UNIT ? all : lane_mask(lam <= lam_limit)) & lane_mask(mag <= M<T>::LARGEST) & lane_mask(to.r >= k.rc4) &
                lane_mask(to.r < k.r_escape) & lane_mask(min_r > k.r_cut) & lane_mask(!(max_d > T(0.25)));
     };
     auto in_band = [&](T th) -> uint64_t { return EQ ? lane_mask(th > k.eq_lo) & lane_mask(th < k.eq_hi) : all; };
+    // The continue test as one scalar word, zero iff the loop goes on: every lane's bit is set and attempts are left
+    // (done < max_steps < 2^31: the sign of the difference).
+    auto stop_bits = [&](uint64_t ok) -> uint64_t { return (ok ^ all) | (uint64_t)(((done - max_steps) >> 31) ^ 1u); };
     // The state ping-pongs between two register sets (A = s.y, B) so that accepting an attempt costs no copies:
     // the loop body is two attempts, A -> B and B -> A, each followed by the one wave-uniform test.  On leaving,
     // a lane keeps the attempted state if its own predicate held, its previous state otherwise.  The loop has ONE
-    // exit, taken from either half, and `second` says which: the selects are stated once, on (good == second), and
+    // exit, and `second` says after which half it was taken: the selects are stated once, on (good == second), and
     // lie outside the loop.
+    // One exit in the machine code too, which is what keeps the ping-pong free of copies.  Written with a `break` after
+    // either attempt -- and equally when the compiler finds out that a failed first test decides the second -- the loop
+    // has two exits; the backend then gives it one again by routing the first through a block where the second half's
+    // results are formally defined (as undefined), and the register allocator, seeing set A live across that
+    // definition, puts the results of B -> A into a third set and copies them to A on the way back: five v_mov per two
+    // steps in every form of the loop.  So a failed first test only skips the second attempt, the exit is the one test
+    // below it, and the word that carries the first test's outcome there passes through an empty asm, so that nothing
+    // can tell the optimiser what it holds.  The hints keep both attempts on the fall-through path.
     // `steps` is settled on leaving: every lane in the loop took every attempt but the last (the loop goes on only
     // while all of them are good), and the lanes in the loop are the same from entry to exit.
     State5<T> b;
@@ -842,11 +883,16 @@ __device__ __forceinline__ bool kerr_rk4_streak_loop(const KerrConsts<T> &k, con
     for (;;) {
         mask = attempt(s.y, ca, s.lam, b, cb, h);
         second = 0ull;
-        if (((mask & in_band(b.th)) != all) | (done >= max_steps)) break;
-        s.lam += h;
-        mask = attempt(b, cb, s.lam, s.y, ca, h);
-        second = ~0ull;
-        if (((mask & in_band(s.y.th)) != all) | (done >= max_steps)) break;
+        uint64_t stop = stop_bits(mask & in_band(b.th));
+        asm volatile("" : "+s"(stop));
+        if (__builtin_expect(stop == 0, 1)) {
+            s.lam += h;
+            mask = attempt(b, cb, s.lam, s.y, ca, h);
+            second = ~0ull;
+            stop = stop_bits(mask & in_band(s.y.th));
+            asm volatile("" : "+s"(stop));
+        }
+        if (__builtin_expect(stop != 0, 0)) break;
         s.lam += h;
     }
     if constexpr (EQ) { // the lane's own `good`: the mask and F5 of the attempted state
@@ -874,7 +920,22 @@ __device__ __forceinline__ uint32_t kerr_rk4_streak(const KerrConsts<T> &k, cons
     bool more = true;
     if constexpr (!LONE && sizeof(T) == 4) {
         if ((lane_mask(s.y.th > k.eq_lo) & lane_mask(s.y.th < k.eq_hi)) == lane_mask(true)) {
-            more = kerr_rk4_streak_loop<T, LONE, true>(k, rc, s, max_steps, done);
+            // The unit-step form of that loop, chosen here once per call like the band: every active lane's base step
+            // is exactly 1 (every ray outside the axis-refine columns at the default h_max), and every lane starts the
+            // call at least max_steps + 1 below the loop's range limit lambda_max - 1 (k.unit_lam; -inf: the switch
+            // lt_set_unit_streak is off, or lambda_max > 2^13).  Then `lam <= lam_limit` holds on every attempt of the
+            // call and the loop need not test it: attempt i <= max_steps - 1 sees lam after i additions of 1, each
+            // rounded by at most half an ulp of a number below 2^13, 2^-12, so lam_i <= lam_0 + i (1 + 2^-12); the sum
+            // tested below is rounded by 2^-12 at most as well, and lam_0 + max_steps + 1 <= lam_limit + 2^-12 gives
+            // lam_i <= lam_limit - 2 + max_steps 2^-12 <= lam_limit - 1 for every max_steps <= 2^12
+            // (tests/test_unit_streak_host.py replays the recurrence in float32 on both sides of the threshold).
+            // (The margin is added to lam, a literal of that instruction; subtracted from the limit, which is wave-uniform,
+            // it would be a register that lives through the whole kernel.)
+            const T lam_far = s.lam + T(max_steps + 1u);
+            if ((max_steps <= 4096u) & ((lane_mask(rc.hb == T(1)) & lane_mask(lam_far <= k.unit_lam)) == lane_mask(true)))
+                more = kerr_rk4_streak_loop<T, LONE, true, true>(k, rc, s, max_steps, done);
+            else
+                more = kerr_rk4_streak_loop<T, LONE, true>(k, rc, s, max_steps, done);
             eq = done;
         }
     }

@@ -169,6 +169,7 @@ SIGNATURES = {
     "lt_math32_probe": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p]),
     "lt_math64_probe": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
     "lt_set_eq_streak": (C.c_int, [C.c_int]),
+    "lt_set_unit_streak": (C.c_int, [C.c_int]),
     "lt_sincos_q1_probe": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "lt_local_rows": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "lt_global_row": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
@@ -670,6 +671,11 @@ def math64_probe(which, x):
 def set_eq_streak(on):
     """Enable / disable the float32 streak's fixed-quadrant loop for the launches that follow; returns the previous setting."""
     return bool(load().lt_set_eq_streak(int(bool(on))))
+
+
+def set_unit_streak(on):
+    """Enable / disable the unit-step form of the fixed-quadrant loop for the launches that follow; returns the previous setting."""
+    return bool(load().lt_set_unit_streak(int(bool(on))))
 
 
 def sincos_q1_probe(bits_lo, bits_hi):
