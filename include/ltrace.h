@@ -313,6 +313,39 @@ int lt_math32_probe(int which, uint32_t bits_lo, uint32_t bits_hi, const float *
  * 6: the correctly rounded sincos of the prologue (angles of a few radians) -> [sin, cos]. */
 int lt_math64_probe(int which, const double *x, int64_t n, double *out);
 
+/* ---- the disk test block by block (parity probes; they call the functions the disk kernels call; the disk itself is     *
+ * described under "thin Keplerian accretion disk" below).  r_in, r_out: the annulus, resolved and refused as a disk call   *
+ * does it (r_in <= 0: the ISCO), then rounded to the precision computed in, as the integrate kernels get them. ---- */
+
+/* The crossing of the plane on one step per row (disk_crossing): y0, y1 (n,5) the step's ends [r, theta, phi, p_r, p_theta],
+ * p_phi (n), h (n) its length, t_end (n) the fraction of the step that is searched (1, or less where the step was cut at a
+ * capture / escape radius).  out_found (n): 1 where the Hermite cubic of theta crosses pi/2 on [0, t_end] and the crossing
+ * point lies in the annulus; out_hit (n,5): the crossing state (theta exactly pi/2 in the precision computed in) and out_tau
+ * (n) the root, wherever the cubic crosses -- in the annulus or not -- and NaN elsewhere.  Float64 I/O. */
+int lt_disk_crossing_probe(const lt_metric *metric, double r_in, double r_out, const double *y0, const double *y1,
+                           const double *p_phi, const double *h, const double *t_end, int64_t n, int precision,
+                           uint8_t *out_found, double *out_hit, double *out_tau);
+
+/* One iteration of an integrator with the disk test behind it (disk_advance) per row: LT_INTEGRATOR_RK4 (precision 32, 64)
+ * or LT_INTEGRATOR_DP45_EXACT (64).  states (n,5), p_phi (n), refine (n), steps (n) as for lt_rk4_advance_probe /
+ * lt_dp45_advance_probe; aux (n,2): lam and h_retry (RK4), lam and h (DP45; its carried derivative and sincos are computed
+ * from the state); act (n): 0 where the lane's hit is to be ignored.  Rows 64 b ... 64 b + 63 share a wavefront.
+ * out_state (n,5), out_aux (n,2): the integrator's state after the iteration (a hit does not replace it here);
+ * out_int (n,3): the event (5 where the row hit the disk, else the integrator's), steps, 1 if the row hit;
+ * out_hit (n,5): the hit state; out_on (n,7): the step the hit lies on -- its end state (5), its length, the root.  NaN where
+ * nothing was written (the root is written wherever the crossing was searched and the cubic crossed). */
+int lt_disk_advance_probe(const lt_metric *metric, double r_obs, double lambda_max, double h_max, double r_in, double r_out,
+                          int integrator, int precision, const double *states, const double *p_phi, const uint8_t *refine,
+                          const double *aux, const uint32_t *steps, const uint8_t *act, int64_t n, double *out_state,
+                          double *out_aux, int32_t *out_int, double *out_hit, double *out_on);
+
+/* The closed forms a hit goes through on its way to a pixel, as the disk epilogues state them.  in (n,4): r, phi (unwrapped),
+ * xi, g_given.  out_f64 (n,5): g(r, xi), phi wrapped to [0, 2 pi), then the unclamped emission E (3) from the float32-rounded
+ * (r, g) -- of g_given instead of g where g_given is not NaN; out_half (n): the half orbits of phi; out_f32 (n,4): the disk
+ * colour of that float32 (r, g) with one channel, then with three.  r_in <= 0: the ISCO; q, exposure as lt_disk. */
+int lt_disk_shade_probe(const lt_metric *metric, double r_in, double q, double exposure, const double *in, int64_t n,
+                        double *out_f64, int64_t *out_half, float *out_f32);
+
 /* ---- fused frame path ---------------------------------------------------------------- *
  * Replaces, in one call, build_alpha_lookup (image_lens.py:133-152),                     *
  * precompute_final_alpha_lookup / _2d (image_lens.py:155-178 / :185-280) and             *

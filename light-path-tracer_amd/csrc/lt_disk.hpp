@@ -343,4 +343,119 @@ __global__ void __launch_bounds__(256) k_epilogue_arrays_disk(MetricConsts m, Di
     if (out_evals) out_evals[q] = res.evals;
 }
 
+// ---- the disk test block by block (lt_disk_crossing_probe, lt_disk_advance_probe, lt_disk_shade_probe) -------------------
+// disk_crossing<T> once per row, on the step y0 -> y1 of length h searched up to t_end.  out_hit (n,5), out_tau (n): what
+// the call left in `hit` and `tau` (NaN where it returned before setting them); out_found (n).
+template <typename T>
+__global__ void __launch_bounds__(64) k_disk_crossing_probe(KerrConsts<T> k_in, DiskConsts<T> d, const double *__restrict__ y0,
+                                                            const double *__restrict__ y1, const double *__restrict__ p_phi,
+                                                            const double *__restrict__ h, const double *__restrict__ t_end,
+                                                            int64_t n, uint8_t *__restrict__ out_found,
+                                                            double *__restrict__ out_hit, double *__restrict__ out_tau)
+{
+    const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    KerrConsts<T> k = k_in;
+    pin_consts(k);
+    const RayConsts<T> rc = make_ray_consts(k, (T)p_phi[i], false);
+    State5<T> a, b, hit;
+    a.r = (T)y0[i * 5 + 0]; a.th = (T)y0[i * 5 + 1]; a.ph = (T)y0[i * 5 + 2]; a.pr = (T)y0[i * 5 + 3]; a.pth = (T)y0[i * 5 + 4];
+    b.r = (T)y1[i * 5 + 0]; b.th = (T)y1[i * 5 + 1]; b.ph = (T)y1[i * 5 + 2]; b.pr = (T)y1[i * 5 + 3]; b.pth = (T)y1[i * 5 + 4];
+    const T nan = (T)__builtin_nan("");
+    hit.r = hit.th = hit.ph = hit.pr = hit.pth = nan;
+    T tau = nan;
+    const bool found = disk_crossing(k, d, rc, a, b, (T)h[i], (T)t_end[i], hit, &tau);
+    out_found[i] = found ? 1 : 0;
+    out_hit[i * 5 + 0] = (double)hit.r; out_hit[i * 5 + 1] = (double)hit.th; out_hit[i * 5 + 2] = (double)hit.ph;
+    out_hit[i * 5 + 3] = (double)hit.pr; out_hit[i * 5 + 4] = (double)hit.pth;
+    out_tau[i] = (double)tau;
+}
+
+// A row's integrator state, in the layouts of k_rk4_advance_probe and k_dp45_advance_probe (lt_kernels.hpp).
+// aux (n,2): RK4 lam, h_retry; DP45 lam, h (the carried derivative and sincos are computed from the state, as at a start).
+template <typename T>
+__device__ __forceinline__ void disk_probe_state(const KerrConsts<T> &, const RayConsts<T> &, const double *__restrict__ states,
+                                                 const double *__restrict__ aux, const uint32_t *__restrict__ steps, int64_t i,
+                                                 RayState<T> &s)
+{
+    s.y.r = (T)states[i * 5 + 0]; s.y.th = (T)states[i * 5 + 1]; s.y.ph = (T)states[i * 5 + 2];
+    s.y.pr = (T)states[i * 5 + 3]; s.y.pth = (T)states[i * 5 + 4];
+    s.lam = (T)aux[i * 2 + 0]; s.h_retry = (T)aux[i * 2 + 1];
+    s.steps = steps[i];
+}
+__device__ __forceinline__ void disk_probe_state(const KerrConsts<double> &k, const RayConsts<double> &rc,
+                                                 const double *__restrict__ states, const double *__restrict__ aux,
+                                                 const uint32_t *__restrict__ steps, int64_t i, Dp45State<double> &s)
+{
+    s = dp45_probe_state(k, rc, states, nullptr, nullptr, i);
+    s.lam = aux[i * 2 + 0]; s.h = aux[i * 2 + 1];
+    s.steps = steps[i];
+}
+template <typename T> __device__ __forceinline__ T disk_probe_aux1(const RayState<T> &s) { return s.h_retry; }
+template <typename T> __device__ __forceinline__ T disk_probe_aux1(const Dp45State<T> &s) { return s.h; }
+
+// disk_advance<T, Integ> once per row, with an on_hit that records the hit and returns EV_DISK (the state is left as
+// Integ::advance left it) and with `on` given.  Blocks of 64: rows 64 b ... 64 b + 63 share a wavefront.  act (n): the
+// lane's `act`.  out_state (n,5), out_aux (n,2) as aux, out_int (n,3): the event, steps, 1 if on_hit ran; out_hit (n,5) and
+// out_on (n,7): on.y1 (5), on.h, on.tau -- NaN where nothing wrote them.
+template <typename T, typename Integ>
+__global__ void __launch_bounds__(64) k_disk_advance_probe(KerrConsts<T> k_in, DiskConsts<T> d, const double *__restrict__ states,
+                                                           const double *__restrict__ p_phi, const uint8_t *__restrict__ refine,
+                                                           const double *__restrict__ aux, const uint32_t *__restrict__ steps,
+                                                           const uint8_t *__restrict__ act, int64_t n,
+                                                           double *__restrict__ out_state, double *__restrict__ out_aux,
+                                                           int32_t *__restrict__ out_int, double *__restrict__ out_hit,
+                                                           double *__restrict__ out_on)
+{
+    const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    KerrConsts<T> k = k_in;
+    pin_consts(k);
+    const RayConsts<T> rc = make_ray_consts(k, (T)p_phi[i], refine[i] != 0);
+    typename Integ::State s;
+    disk_probe_state(k, rc, states, aux, steps, i, s);
+    const T nan = (T)__builtin_nan("");
+    State5<T> rec;
+    rec.r = rec.th = rec.ph = rec.pr = rec.pth = nan;
+    DiskHitStep<T> on;
+    on.y1 = rec; on.h = nan; on.tau = nan;
+    int was_hit = 0;
+    const T vmax2 = T(2) * disk_vmax(k, d, rc);
+    const int ev = disk_advance<T, Integ>(k, d, rc, vmax2, s, act[i] != 0, [&](typename Integ::State &, const State5<T> &hit, int) {
+        rec = hit;
+        was_hit = 1;
+        return (int)EV_DISK;
+    }, &on);
+    out_state[i * 5 + 0] = (double)s.y.r; out_state[i * 5 + 1] = (double)s.y.th; out_state[i * 5 + 2] = (double)s.y.ph;
+    out_state[i * 5 + 3] = (double)s.y.pr; out_state[i * 5 + 4] = (double)s.y.pth;
+    out_aux[i * 2 + 0] = (double)s.lam; out_aux[i * 2 + 1] = (double)disk_probe_aux1(s);
+    out_int[i * 3 + 0] = ev; out_int[i * 3 + 1] = (int32_t)s.steps; out_int[i * 3 + 2] = was_hit;
+    out_hit[i * 5 + 0] = (double)rec.r; out_hit[i * 5 + 1] = (double)rec.th; out_hit[i * 5 + 2] = (double)rec.ph;
+    out_hit[i * 5 + 3] = (double)rec.pr; out_hit[i * 5 + 4] = (double)rec.pth;
+    out_on[i * 7 + 0] = (double)on.y1.r; out_on[i * 7 + 1] = (double)on.y1.th; out_on[i * 7 + 2] = (double)on.y1.ph;
+    out_on[i * 7 + 3] = (double)on.y1.pr; out_on[i * 7 + 4] = (double)on.y1.pth;
+    out_on[i * 7 + 5] = (double)on.h; out_on[i * 7 + 6] = (double)on.tau;
+}
+
+// The closed forms a hit goes through (k_epilogue_disk's statements): in (n,4) r, phi (unwrapped), xi, g_given.  out_f64
+// (n,5): g = disk_redshift(r, xi), wrap_2pi(phi), then disk_emission (3) from the float32-rounded (r, g) -- of g_given where
+// that is not NaN, so that a test can place s on the ramp's knees; out_half (n): half_orbits(phi); out_f32 (n,4): disk_shade
+// of the same float32 (r, g) with 1 channel, then with 3.
+__global__ void __launch_bounds__(64) k_disk_shade_probe(DiskShade ds, const double *__restrict__ in, int64_t n,
+                                                         double *__restrict__ out_f64, int64_t *__restrict__ out_half,
+                                                         float *__restrict__ out_f32)
+{
+    const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const double r = in[i * 4 + 0], ph = in[i * 4 + 1], xi = in[i * 4 + 2], g_given = in[i * 4 + 3];
+    const double g = disk_redshift(ds.M, ds.a, r, xi);
+    const float r32 = (float)r, g32 = (float)(g_given == g_given ? g_given : g);
+    out_f64[i * 5 + 0] = g;
+    out_f64[i * 5 + 1] = wrap_2pi(ph);
+    disk_emission(ds, r32, g32, out_f64 + i * 5 + 2);
+    out_half[i] = (int64_t)half_orbits(ph);
+    disk_shade(ds, r32, g32, 1, out_f32 + i * 4);
+    disk_shade(ds, r32, g32, 3, out_f32 + i * 4 + 1);
+}
+
 } // namespace lt

@@ -168,6 +168,11 @@ SIGNATURES = {
                          + [C.c_void_p] * 4),
     "lt_math32_probe": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p]),
     "lt_math64_probe": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    "lt_disk_crossing_probe": (C.c_int, [C.POINTER(Metric), C.c_double, C.c_double] + [C.c_void_p] * 5 + [C.c_int64, C.c_int]
+                               + [C.c_void_p] * 3),
+    "lt_disk_advance_probe": (C.c_int, [C.POINTER(Metric)] + [C.c_double] * 5 + [C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_int64]
+                              + [C.c_void_p] * 5),
+    "lt_disk_shade_probe": (C.c_int, [C.POINTER(Metric), C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_int64] + [C.c_void_p] * 3),
     "lt_set_eq_streak": (C.c_int, [C.c_int]),
     "lt_set_unit_streak": (C.c_int, [C.c_int]),
     "lt_sincos_q1_probe": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
@@ -1143,6 +1148,55 @@ def step_time_probe(metric, p_phi, y0, y1, h, tau=1.0, precision=64):
     _check(load().lt_step_time_probe(C.byref(metric), _np_ptr(pp), _np_ptr(y0), _np_ptr(y1), _np_ptr(hh), _np_ptr(tt), n,
                                      int(precision), _np_ptr(out)))
     return out
+
+
+EV_DISK = 5                                                              # the event of a row that hit the disk
+
+
+def disk_crossing_probe(metric, y0, y1, p_phi, h, t_end=1.0, r_in=0.0, r_out=20.0, precision=64):
+    """The device's crossing search (lt_disk_crossing_probe) on n steps: y0, y1 (n,5); p_phi, h, t_end scalars or (n,).
+    -> dict(found (n,) bool, hit (n,5), tau (n,)): float64 holding the values of the precision computed in."""
+    y0 = np.ascontiguousarray(y0, dtype=np.float64).reshape(-1, 5)
+    y1 = np.ascontiguousarray(y1, dtype=np.float64).reshape(-1, 5)
+    n = y0.shape[0]
+    pp, hh, tt = (np.ascontiguousarray(np.broadcast_to(np.asarray(x, dtype=np.float64), (n,))) for x in (p_phi, h, t_end))
+    found, hit, tau = np.empty(n, dtype=np.uint8), np.empty((n, 5)), np.empty(n)
+    _check(load().lt_disk_crossing_probe(C.byref(metric), r_in, r_out, _np_ptr(y0), _np_ptr(y1), _np_ptr(pp), _np_ptr(hh), _np_ptr(tt),
+                                         n, int(precision), _np_ptr(found), _np_ptr(hit), _np_ptr(tau)))
+    return dict(found=found.astype(bool), hit=hit, tau=tau)
+
+
+def disk_advance_probe(metric, states, p_phi, integrator=INTEGRATOR_RK4, precision=64, lam=0.0, h=0.0, refine=None, steps=None,
+                       act=True, r_in=0.0, r_out=20.0, r_obs=50.0, lambda_max=5000.0, h_max=1.0):
+    """One iteration of an integrator with the disk test behind it per state (lt_disk_advance_probe); rows 64 b ... 64 b + 63
+    share a wavefront.  h: RK4's h_retry, DP45's step size.  -> dict(event, steps (n,) int32, is_hit (n,) bool, state (n,5),
+    lam, h (n,), hit (n,5), on_y1 (n,5), on_h, on_tau (n,))."""
+    st = np.ascontiguousarray(states, dtype=np.float64).reshape(-1, 5)
+    n = st.shape[0]
+    pp = np.ascontiguousarray(np.broadcast_to(np.asarray(p_phi, dtype=np.float64), (n,)))
+    rf = np.zeros(n, dtype=np.uint8) if refine is None else np.ascontiguousarray(np.broadcast_to(np.asarray(refine), (n,))).astype(np.uint8)
+    ss = np.zeros(n, dtype=np.uint32) if steps is None else np.ascontiguousarray(np.broadcast_to(np.asarray(steps), (n,))).astype(np.uint32)
+    ac = np.ascontiguousarray(np.broadcast_to(np.asarray(act), (n,))).astype(np.uint8)
+    aux = np.ascontiguousarray(np.stack([np.broadcast_to(np.asarray(x, dtype=np.float64), (n,)) for x in (lam, h)], axis=1))
+    out, oa, oi, oh, oo = np.empty_like(st), np.empty((n, 2)), np.empty((n, 3), dtype=np.int32), np.empty((n, 5)), np.empty((n, 7))
+    _check(load().lt_disk_advance_probe(C.byref(metric), r_obs, lambda_max, h_max, r_in, r_out, int(integrator), int(precision),
+                                        _np_ptr(st), _np_ptr(pp), _np_ptr(rf), _np_ptr(aux), _np_ptr(ss), _np_ptr(ac), n, _np_ptr(out),
+                                        _np_ptr(oa), _np_ptr(oi), _np_ptr(oh), _np_ptr(oo)))
+    return dict(event=oi[:, 0].copy(), steps=oi[:, 1].copy(), is_hit=oi[:, 2] != 0, state=out, lam=oa[:, 0].copy(), h=oa[:, 1].copy(),
+                hit=oh, on_y1=oo[:, :5].copy(), on_h=oo[:, 5].copy(), on_tau=oo[:, 6].copy())
+
+
+def disk_shade_probe(metric, r, phi=0.0, xi=0.0, g=np.nan, r_in=0.0, q=3.0, exposure=1.0):
+    """The closed forms of a disk hit on the device (lt_disk_shade_probe): r (n,), phi, xi, g scalars or (n,) (g NaN: the
+    emission and the colour take the device's own g).  -> dict(g, phi (n,), emission (n,3) float64, half_orbits (n,) int64,
+    shade1 (n,), shade3 (n,3) float32)."""
+    r = np.asarray(r, dtype=np.float64).ravel()
+    n = r.size
+    inp = np.ascontiguousarray(np.stack([np.broadcast_to(np.asarray(x, dtype=np.float64), (n,)) for x in (r, phi, xi, g)], axis=1))
+    o64, oh, o32 = np.empty((n, 5)), np.empty(n, dtype=np.int64), np.empty((n, 4), dtype=np.float32)
+    _check(load().lt_disk_shade_probe(C.byref(metric), r_in, q, exposure, _np_ptr(inp), n, _np_ptr(o64), _np_ptr(oh), _np_ptr(o32)))
+    return dict(g=o64[:, 0].copy(), phi=o64[:, 1].copy(), emission=o64[:, 2:].copy(), half_orbits=oh, shade1=o32[:, 0].copy(),
+                shade3=o32[:, 1:].copy())
 
 
 def default_hotspot(**kw):

@@ -441,7 +441,9 @@ typedef struct disk_hook {
     real graze, gscale;  /* min over turning points of |theta - pi/2| e^(-pi k); e^(-pi k) */
     real hit[5];         /* opaque: the state the ray ended in */
     uint32_t evals_hit;  /* opaque: the integrator's evaluations up to and including the hit's step */
+    real *one;           /* lto_disk_step: what this step decided, LTO_DISK_NS reals (NULL in a trace) */
 } disk_hook;
+#define LTO_DISK_NS 15 /* cross, t, c[5], on_path, is_hit, frac used, y1 used[5] */
 
 static real herm(real y0, real hd0, real y1, real hd1, real t)
 {
@@ -471,6 +473,7 @@ static int disk_step(disk_hook *d, const real *y0, const real *y1_in, real h, in
     int cross = (z0 < R(0.0) && z1 >= R(0.0)) || (z0 > R(0.0) && z1 <= R(0.0));
     int turn = (y0[4] < R(0.0) && y1[4] >= R(0.0)) || (y0[4] > R(0.0) && y1[4] <= R(0.0));
     int ended = 0;
+    if (d->one) d->one[0] = (real)cross;
     if (cross || turn) {
         real f0[5], f1[5];
         if (terminal && d->is_dp45 && cross) { /* the header: the full step is retaken as one RK4 step of the same length */
@@ -515,6 +518,11 @@ static int disk_step(disk_hook *d, const real *y0, const real *y1_in, real h, in
             kerr_rhs(c, d->p_t, d->p_phi, d->M, d->a, d->r_plus, fc);
             int on_path = !terminal || t <= frac;
             int is_hit = on_path && c[0] >= d->r_in && c[0] <= d->r_out;
+            if (d->one) {
+                real *o = d->one;
+                o[1] = t; o[7] = (real)on_path; o[8] = (real)is_hit; o[9] = frac;
+                for (int i = 0; i < 5; ++i) { o[2 + i] = c[i]; o[10 + i] = y1[i]; }
+            }
             if (d->cross && d->n_cross < d->max_cross) {
                 real *o = d->cross + (size_t)d->n_cross * LTO_DISK_NC;
                 o[0] = (real)step; o[1] = t; o[2] = h; o[3] = y0[0]; o[4] = y1[0]; o[5] = c[0]; o[6] = c[2];
@@ -918,6 +926,27 @@ void LTO_NAME(lto_rk4_iteration)(const real *states, const real *p_phi, const re
         for (int j = 0; j < 5; ++j) state_out[5 * i + j] = st[j];
         lam_out[i] = lam; h_out[i] = h;
         outcome[2 * i] = ev; outcome[2 * i + 1] = attempts;
+    }
+}
+
+/* disk_step on one step per row, as the disk tracers call it: y0, y1 (n,5), p_phi, h (n), terminal (n) 0 / -1 / 1, frac (n).
+ * out (n, LTO_DISK_NS): cross; then, where cross, the root t, the crossing state (5), on_path, is_hit, the fraction and the
+ * end state (5) the root was searched with (the retaken RK4 step's on a terminal DP45 step) -- NaN where no crossing. */
+void LTO_NAME(lto_disk_step)(const real *y0, const real *y1, const real *p_phi, const real *h, const int32_t *terminal,
+                             const real *frac, int64_t n, real M, real a, real r_plus, real r_obs, real r_in, real r_out,
+                             int is_dp45, real *out)
+{
+    for (int64_t i = 0; i < n; ++i) {
+        disk_hook hk;
+        memset(&hk, 0, sizeof hk);
+        hk.M = M; hk.a = a; hk.r_plus = r_plus; hk.r_in = r_in; hk.r_out = r_out;
+        hk.r_capture = r_plus * R(1.01); hk.r_escape = r_obs * R(2.0);
+        hk.is_dp45 = is_dp45;
+        hk.p_t = R(-1.0); hk.p_phi = p_phi[i];
+        hk.graze = (real)INFINITY; hk.gscale = R(1.0);
+        hk.one = out + i * LTO_DISK_NS;
+        for (int j = 0; j < LTO_DISK_NS; ++j) hk.one[j] = LTO_NAN;
+        disk_step(&hk, y0 + i * 5, y1 + i * 5, h[i], terminal[i], frac[i]);
     }
 }
 

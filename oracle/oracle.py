@@ -252,6 +252,26 @@ def rk4_iteration(states, p_phi, lam, M, a, r_obs=50.0, lambda_max=5000.0, h_max
     return dict(state=so, lam=lo, h=ho, event=oc[:, 0].copy(), attempts=oc[:, 1].copy())
 
 
+def disk_step(y0, y1, p_phi, h, M, a, r_in, r_out, terminal=0, frac=1.0, is_dp45=False, r_obs=50.0, f32=False):
+    """The disk twin's test of one accepted step y0 -> y1 (n,5) of length h per row, by the function the disk tracers
+    themselves call (lto_disk_step).  terminal (n) 0 / -1 / 1: the step also ended the ray by capture / escape at the
+    fraction frac of its chord.  -> dict(cross (n,) bool; where cross: t (n,), state (n,5), on_path, is_hit (n,) bool,
+    frac (n,) and y1 (n,5) the root was searched with; NaN / False elsewhere), float64 or float32 throughout."""
+    dt, pt, ct = _real(f32)
+    a0 = np.ascontiguousarray(y0, dtype=dt).reshape(-1, 5)
+    a1 = np.ascontiguousarray(y1, dtype=dt).reshape(-1, 5)
+    n = a0.shape[0]
+    pp, hh, ff = (np.ascontiguousarray(np.broadcast_to(np.asarray(x, dtype=dt), (n,))) for x in (p_phi, h, frac))
+    tm = np.ascontiguousarray(np.broadcast_to(np.asarray(terminal), (n,))).astype(np.int32)
+    out = np.empty((n, 15), dtype=dt)
+    fn = _fn("lto_disk_step", f32, [pt, pt, pt, pt, _i32p, pt, C.c_int64, ct, ct, ct, ct, ct, ct, C.c_int, pt])
+    fn(_ptr(a0, pt), _ptr(a1, pt), _ptr(pp, pt), _ptr(hh, pt), _ptr(tm, _i32p), _ptr(ff, pt), n, M, a,
+       M + np.sqrt(M * M - a * a), r_obs, r_in, r_out, int(bool(is_dp45)), _ptr(out, pt))
+    cross = out[:, 0] == 1
+    return dict(cross=cross, t=out[:, 1].copy(), state=out[:, 2:7].copy(), on_path=out[:, 7] == 1, is_hit=out[:, 8] == 1,
+                frac=out[:, 9].copy(), y1=out[:, 10:15].copy())
+
+
 def kerr_extract(states, p_phi, event, M, a, f32=False):
     """_kerr_extract_angle (metrics.py:363-416, p_t = -1) on n final records: states (n,5), p_phi (n,), event (n,) the
     tracer's event_status (-1 captured, 1 escaped, 2 range end).  -> (final_alpha (n,) NaN unless set, n_half (n,) i64,

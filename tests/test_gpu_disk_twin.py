@@ -35,6 +35,7 @@ import numpy as np
 import pytest
 
 import disk as diskmod
+import disk_blocks as dk
 import ltrace
 from oracle import oracle  # noqa: F401
 from test_oracle_disk import (BUDGET64, CASES, CASE_IDS, E_PI, FRAME_H, FRAME_W, M, crossing_k, excluded, fans,  # noqa: F401
@@ -115,11 +116,15 @@ def check_slots(ci, a, images, tw, rays, n_slots, budget, xi):
 
 
 def check_g_closed_form(a, images, xi):
-    """g is disk.redshift of the r the call returns, to 1e-12 relative."""
+    """g is disk.redshift of the r the call returns, within the unit of tests/disk_blocks.py: 2 K_G units for the device's g and
+    K_G for numpy's -- a few 1e-15 relative; 2e-13 at the ISCO of a = 0.998, where the radicand r^1.5 - 3 M sqrt r + 2 a sqrt M
+    cancels by a factor of a hundred."""
     r, g = images[..., 0], images[..., 2]
     on = ~np.isnan(r)
-    ref = diskmod.redshift(M, a, r[on], np.broadcast_to(xi.reshape((-1,) + (1,) * (r.ndim - 1)), r.shape)[on])
-    assert np.all(np.abs(g[on] - ref) <= 1e-12 * np.abs(ref)), float(np.max(np.abs(g[on] - ref) / np.abs(ref)))
+    xi_on = np.broadcast_to(xi.reshape((-1,) + (1,) * (r.ndim - 1)), r.shape)[on]
+    ref = diskmod.redshift(M, a, r[on], xi_on)
+    bound = 3 * dk.K_G * dk.g_unit(M, a, r[on], xi_on)
+    assert np.all(np.abs(g[on] - ref) <= bound), float(np.max(np.abs(g[on] - ref) / bound))
 
 
 def check_fa(fa_gpu, fa_tw, rays):
