@@ -192,6 +192,30 @@ int lt_set_eq_streak(int on);
  * Returns the previous setting. */
 int lt_set_unit_streak(int on);
 
+/* The tail split of the frame path: a Kerr frame of the direct schedule integrates the last tile rows of
+ * its tile queue with a launch of its own on a side stream of the library's, which takes the wave slots the main launch
+ * leaves free while it runs dry; the rows above are shaded while that second launch ends.  tile_rows: -1 an automatic
+ * size (about one fill of the device's wave slots; frames too short for it are not split), 0 off, n > 0 that many tile
+ * rows (8 pixel rows each), at most what lies below the frame's hot rectangle.  For every frame enqueued afterwards; the
+ * default is -1, or LT_TAIL_SPLIT in the environment when the library is loaded.  Frames with a disk, supersampling,
+ * tb_symmetry, the queue schedule, the Schwarzschild metric or LT_BG_LDS_TILES with a background, and frames on a stream
+ * that is being captured, are never split.  It changes no output and no counter; with opts->timing the integrate time of
+ * a split frame includes the shading that overlaps it.  Everything is joined back into opts->stream before the call
+ * returns.  Returns the previous setting. */
+int lt_set_tail_split(int tile_rows);
+
+/* *split = frames that were split that way, *whole = frames of lt_render_dev and its relatives that were not, both since
+ * the library was loaded, over all devices and streams; either may be NULL.  Needs no device. */
+void lt_tail_split_counts(uint64_t *split, uint64_t *whole);
+
+/* Where the tail split cuts a frame of tiles_x x tiles_y tiles (8 x 8 pixels) whose tile queue begins with the strip of
+ * tile columns [strip_x0, strip_x1) and a hot rectangle that ends above tile row hot_y1 (0: none), on a device of `slots`
+ * wave slots, for the setting `request` (lt_set_tail_split): *ty_split = the first tile row and *pos_split = the first
+ * queue position of the second part (tiles_y and tiles_x * tiles_y where the frame is not split).  Returns 1 if the frame
+ * is split, 0 if not, -1 on arguments that describe no frame.  Host arithmetic only (test probe). */
+int lt_tail_split_plan(int32_t tiles_x, int32_t tiles_y, int32_t strip_x0, int32_t strip_x1, int32_t hot_y1, int32_t slots,
+                       int32_t request, int32_t *ty_split, int64_t *pos_split);
+
 /* Device probe of the float32 sincos for the tests: every float32 x with bit pattern in [bits_lo, bits_hi] goes through
  * the general form and through the fixed-quadrant form.  out[0] = values compared, out[1] = values for which either
  * result differs in any bit, out[2] = values that do not reduce to the quadrant k = 1, out[3] = bit pattern of the

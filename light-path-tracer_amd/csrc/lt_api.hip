@@ -45,7 +45,8 @@ using namespace lt;
 namespace lt {
 extern template __global__ void k_kerr_direct<float, Rk4<float>>(KerrConsts<float>, const typename Vec4<float>::type *__restrict__,
                                                                  typename Vec4<float>::type *__restrict__, typename Vec4<float>::type *__restrict__,
-                                                                 int64_t, uint32_t, uint4 *__restrict__, uint64_t *__restrict__, unsigned long long *__restrict__);
+                                                                 int64_t, uint32_t, uint4 *__restrict__, uint64_t *__restrict__, unsigned long long *__restrict__,
+                                                                 int64_t);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -155,6 +156,10 @@ struct StreamSlot {
     std::vector<EventQuad> aa_events; // lt_render_aa's: one quad per band, grown to the most bands a call had
     Grow aa_list;    // lt_render_aa_adaptive: the count (first 256 bytes) and the list of refined pixels
     Grow aa_scratch; // ... and the base pass's cover / rgb when the caller did not ask for them
+    // The tail split of the plain frame path (render_dev_impl): the stream the queue's tail is integrated on and the two
+    // events that fork it off `stream` and join it back, all three or none (slot_side, created on first use).
+    hipStream_t side = nullptr;
+    hipEvent_t fork = nullptr, join = nullptr;
 };
 
 struct Ctx {
@@ -177,6 +182,29 @@ static int slot_events(StreamSlot *sl)
         return fail(LT_ERR_HIP, "hipEventCreate failed");
     }
     sl->own_ok = true;
+    return LT_OK;
+}
+
+// The side stream of a slot and its fork / join events, all three or none.  Non-blocking (it is ordered against `stream`
+// by the two events alone, also when `stream` is the legacy default stream) and of the lowest priority the device has:
+// the work put there is meant to take the wave slots the user's stream leaves free, not to compete for them.
+static int slot_side(StreamSlot *sl)
+{
+    if (sl->side) return LT_OK;
+    int least = 0, greatest = 0;
+    HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
+    hipStream_t side = nullptr;
+    hipEvent_t fork = nullptr, join = nullptr;
+    hipError_t e = hipStreamCreateWithPriority(&side, hipStreamNonBlocking, least);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&fork, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&join, hipEventDisableTiming);
+    if (e != hipSuccess) {
+        if (join) (void)hipEventDestroy(join);
+        if (fork) (void)hipEventDestroy(fork);
+        if (side) (void)hipStreamDestroy(side);
+        return fail(LT_ERR_HIP, "creating the side stream of a slot failed: %s", hipGetErrorString(e));
+    }
+    sl->side = side; sl->fork = fork; sl->join = join;
     return LT_OK;
 }
 
@@ -209,7 +237,10 @@ static int get_slot(hipStream_t s, StreamSlot **out)
     return LT_OK;
 }
 
-// Only `stream` ever touches the buffer, so draining that stream is enough before it is replaced.
+// Draining `stream` is enough before the buffer is replaced.  Every launch that touches it is on `stream`, with one
+// exception: the tail split of render_dev_impl integrates the end of the tile queue on the slot's side stream.  That
+// call makes `stream` wait for the side stream's join event before it returns (SideJoin, on its error returns too), so
+// whatever the side stream was given completes before anything enqueued on `stream` afterwards -- this drain included.
 static int grow(Grow &g, size_t need, hipStream_t stream)
 {
     if (need <= g.bytes) return LT_OK;
@@ -238,15 +269,21 @@ static void destroy_slot(StreamSlot *sl)
     for (Grow *g : {&sl->ws, &sl->dev, &sl->dense, &sl->blocks, &sl->disk_img, &sl->disk_time, &sl->disk_mom, &sl->hotspot, &sl->spectrum, &sl->visibility, &sl->aa_list, &sl->aa_scratch}) release(*g);
     if (sl->own_ok) for (auto &e : sl->own.e) (void)hipEventDestroy(e);
     for (auto &q : sl->aa_events) for (auto &e : q.e) (void)hipEventDestroy(e);
+    if (sl->side) { // (joined into the slot's stream by every call that used it; drained here all the same)
+        (void)hipStreamSynchronize(sl->side);
+        (void)hipEventDestroy(sl->fork);
+        (void)hipEventDestroy(sl->join);
+        (void)hipStreamDestroy(sl->side);
+    }
     delete sl;
 }
 
-// Workspace layout: 256 B of control words (queue head) | STAT_SLOTS x 8 partial counters of the epilogue | ic[n_q] |
+// Workspace layout: 256 B of control words (queue head; at byte 128 the head of the tail split's second part) | STAT_SLOTS x 8 partial counters of the epilogue | ic[n_q] |
 // fin0[n_q] | fin1[n_q], each a 4-vector of T.  The partial counters are zero between frames (zeroed when the buffer
 // is allocated, and again by k_stats_reduce after it has read them).
 constexpr size_t WS_CTRL_BYTES = 256 + (size_t)STAT_SLOTS * 8 * sizeof(unsigned long long);
 struct Workspace {
-    unsigned long long *head, *partials;
+    unsigned long long *head, *head_b, *partials;
     char *records; // ic, fin0, fin1: n_q records each, of the precision the workspace was asked for
     size_t n_q;
     template <typename T> typename Vec4<T>::type *ic() const { return (typename Vec4<T>::type *)records; }
@@ -280,6 +317,7 @@ static int get_workspace(hipStream_t stream, size_t n_q, size_t elem, Workspace 
     if (sl->ws.p != before) HIP_TRY(hipMemsetAsync(sl->ws.p, 0, WS_CTRL_BYTES, stream)); // a new buffer: control words and partial counters start at zero
     char *base = (char *)sl->ws.p;
     w->head = (unsigned long long *)base;
+    w->head_b = (unsigned long long *)(base + 128);
     w->partials = (unsigned long long *)(base + 256);
     w->records = base + WS_CTRL_BYTES;
     w->n_q = n_q;
@@ -343,6 +381,86 @@ extern "C" int lt_set_unit_streak(int on)
     const int before = unit_streak_enabled();
     g_unit_streak.store(on != 0);
     return before;
+}
+
+// The tail split of the plain frame path (render_dev_impl): the last tile rows of the queue are integrated
+// by a launch of their own on the slot's side stream.  LT_TAIL_SPLIT / lt_set_tail_split(n): -1 the automatic size,
+// 0 off, n > 0 that many tile rows, clamped to what the frame allows.  Read by render_dev_impl for every frame.
+constexpr int TAIL_SPLIT_DEFAULT = -1; // (automatic: profiles/tail_split_ab.txt)
+static std::atomic<int> g_tail_split{INT32_MIN}; // INT32_MIN: not yet read from the environment
+static int tail_split_request()
+{
+    int v = g_tail_split.load(std::memory_order_relaxed);
+    if (v == INT32_MIN) {
+        v = env_int("LT_TAIL_SPLIT", TAIL_SPLIT_DEFAULT);
+        if (v < -1) v = -1;
+        int unset = INT32_MIN;
+        if (!g_tail_split.compare_exchange_strong(unset, v)) v = unset;
+    }
+    return v;
+}
+extern "C" int lt_set_tail_split(int tile_rows)
+{
+    const int before = tail_split_request();
+    g_tail_split.store(tile_rows < -1 ? -1 : tile_rows);
+    return before;
+}
+
+// Where the tail split cuts a frame's tile queue (queue_pos_to_tile, lt_kernels.hpp): host arithmetic only.  The queue
+// ends with the whole tile rows below the hot rectangle, ty >= hot_y1, row-major over the cw = tiles_x - strip width
+// columns beside the strip (without a rectangle hot_y1 is 0 and that is every row).  Part B is the last `rows_b` of them,
+// queue positions [pos_split, n_tiles) with pos_split = n_tiles - rows_b * cw; part A is everything before, which holds
+// every tile with ty < ty_split = tiles_y - rows_b and every tile of the strip.
+//   request > 0:  rows_b = request, at most the rows below the rectangle, and part A keeps at least one tile
+//   request == -1: rows_b = ceil(TAIL_SPLIT_FILLS * slots / cw), one fill of the chip's `slots` wave slots (measured at
+//                  4096^2: half a fill gains a third less, two fills the same -- profiles/tail_split_ab.txt); declines
+//                  where that is more than the rows below the rectangle, or where part A would be left with less than
+//                  TAIL_SPLIT_MIN_FILLS_A fills (a frame that short is bound by its longest ray, not by the ramp-down)
+// Returns false where the frame is not split (then ty_split = tiles_y, pos_split = n_tiles).
+constexpr int TAIL_SPLIT_FILLS_NUM = 1, TAIL_SPLIT_FILLS_DEN = 1, TAIL_SPLIT_MIN_FILLS_A = 1;
+static bool tail_split_plan(int tiles_x, int tiles_y, int strip_w, int hot_y1, int slots, int request, int *ty_split,
+                            int64_t *pos_split)
+{
+    const int64_t n_tiles = (int64_t)tiles_x * tiles_y;
+    *ty_split = tiles_y;
+    *pos_split = n_tiles;
+    const int64_t cw = (int64_t)tiles_x - strip_w;
+    int64_t avail = (int64_t)tiles_y - hot_y1; // tile rows below the rectangle
+    if (request == 0 || cw <= 0 || avail <= 0) return false;
+    int64_t rows_b;
+    if (request > 0) {
+        if (avail * cw >= n_tiles) --avail; // (no strip and no rectangle: the first tile row stays in part A)
+        rows_b = request < avail ? request : avail;
+    } else {
+        if (slots <= 0) return false;
+        rows_b = ((int64_t)TAIL_SPLIT_FILLS_NUM * slots + TAIL_SPLIT_FILLS_DEN * cw - 1) / (TAIL_SPLIT_FILLS_DEN * cw);
+        if (rows_b > avail || n_tiles - rows_b * cw < (int64_t)TAIL_SPLIT_MIN_FILLS_A * slots) return false;
+    }
+    if (rows_b <= 0) return false;
+    *ty_split = (int)(tiles_y - rows_b);
+    *pos_split = n_tiles - rows_b * cw;
+    return true;
+}
+// (for tests/test_tail_split_host.py: needs no device)
+extern "C" int lt_tail_split_plan(int32_t tiles_x, int32_t tiles_y, int32_t strip_x0, int32_t strip_x1, int32_t hot_y1, int32_t slots,
+                                  int32_t request, int32_t *ty_split, int64_t *pos_split)
+{
+    int ty = 0;
+    int64_t pos = 0;
+    if (tiles_x <= 0 || tiles_y <= 0 || strip_x0 < 0 || strip_x1 < strip_x0 || strip_x1 > tiles_x || hot_y1 < 0 || hot_y1 > tiles_y) return -1;
+    const bool on = tail_split_plan(tiles_x, tiles_y, strip_x1 - strip_x0, hot_y1, slots, request, &ty, &pos);
+    if (ty_split) *ty_split = ty;
+    if (pos_split) *pos_split = pos;
+    return on ? 1 : 0;
+}
+
+// Frames of render_dev_impl that were split / that ran as one integrate launch, since the library was loaded.
+static uint64_t g_split_frames = 0, g_whole_frames = 0; // (under g_mu)
+extern "C" void lt_tail_split_counts(uint64_t *split, uint64_t *whole)
+{
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (split) *split = g_split_frames;
+    if (whole) *whole = g_whole_frames;
 }
 
 // Frames that reused the ray records of their slot / that ran k_prologue_camera, since the library was loaded.
@@ -762,29 +880,65 @@ template <typename T, typename Go> static int with_integrator(const lt_opts &o, 
     return go(IntegTag<Rk4<T>>{}, long_rk4);
 }
 
-// One launch of the direct schedule (direct_tiles, lt_kernels.hpp): picks the integrator's kernel of the family `Kernels`,
-// sizes the grid, zeroes the queue head and calls launch(kernel, grid, long_iters, head), which adds the family's own
-// arguments.  `block`: work-items per workgroup (64 everywhere but under LT_K2_BLOCK on the plain frame path).
+// A run of queue positions of the direct schedule and the head word its launch hands them out from: the whole queue, or
+// one of the two parts the tail split cuts it into (render_dev_impl).
+struct QueuePart {
+    int64_t tile0, n_tiles;
+    unsigned long long *head;
+    int64_t q_end() const { return (tile0 + n_tiles) * 64; } // what the kernel's end test compares with
+};
+
+// One launch of the direct schedule (direct_tiles, lt_kernels.hpp) over the queue part `part`: picks the integrator's
+// kernel of the family `Kernels`, sizes the grid to the part -- one wavefront per resident slot and the part's head word,
+// or one workgroup per tile and no head when the part fits the chip --, zeroes the head and calls
+// launch(kernel, grid, long_iters, head), which adds the family's own arguments.  `block`: work-items per workgroup (64
+// everywhere but under LT_K2_BLOCK on the plain frame path).
 template <typename T, typename Kernels, typename Launch>
-static int launch_direct(const lt_opts &o, const Workspace &w, int64_t n_q, hipStream_t s, int block, Launch launch)
+static int launch_direct(const lt_opts &o, const QueuePart &part, hipStream_t s, int block, Launch launch)
 {
     const DirectTuning &tune = direct_tuning();
     return with_integrator<T>(o, tune.long_iters, [&](auto integ, int long_it) -> int {
         constexpr auto kernel = Kernels::template kernel<typename decltype(integ)::type>;
-        unsigned grid = (unsigned)((n_q + block - 1) / block);
+        unsigned grid = (unsigned)((part.n_tiles * 64 + block - 1) / block);
         unsigned long long *head = nullptr;
         const int slots = tune.persist && block == 64 ? resident_slots<kernel>() : 0;
-        if (slots > 0 && (unsigned)slots < grid) { grid = (unsigned)slots; head = w.head; } // (a launch that fits the chip needs no queue)
+        if (slots > 0 && (unsigned)slots < grid) { grid = (unsigned)slots; head = part.head; } // (a launch that fits the chip needs no queue)
         if (head) HIP_TRY(hipMemsetAsync(head, 0, sizeof(unsigned long long), s));
         launch(kernel, grid, (uint32_t)long_it, head);
         HIP_TRY(hipGetLastError());
         return LT_OK;
     });
 }
+// ... over the whole queue (the disks)
+template <typename T, typename Kernels, typename Launch>
+static int launch_direct(const lt_opts &o, const Workspace &w, int64_t n_q, hipStream_t s, int block, Launch launch)
+{
+    return launch_direct<T, Kernels>(o, QueuePart{0, n_q / 64, w.head}, s, block, launch);
+}
+
+// Work-items per workgroup of the plain frame path's direct kernel (LT_K2_BLOCK: 64, 128 or 256).
+static int k2_block()
+{
+    static const int b = [] { int v = env_int("LT_K2_BLOCK", 64); return (v == 64 || v == 128 || v == 256) ? v : 64; }();
+    return b;
+}
+
+// Wavefront slots the plain frame path's direct kernel of these options fills the chip with (0: it does not run as a
+// persistent grid -- LT_D_PERSIST=0, wider workgroups, or the occupancy query failed).
+template <typename T> static int direct_slots(const lt_opts &o)
+{
+    int slots = 0;
+    if (!direct_tuning().persist || k2_block() != 64) return 0;
+    (void)with_integrator<T>(o, 0, [&](auto integ, int) -> int {
+        slots = resident_slots<PlainKernels<T>::template kernel<typename decltype(integ)::type>>();
+        return LT_OK;
+    });
+    return slots;
+}
 
 template <typename T>
 static int launch_integrate(const MetricConsts &mc, const lt_opts &o, double lambda_max, const Workspace &w,
-                            int64_t n_q, hipStream_t s, uint64_t *kstats)
+                            int64_t n_q, hipStream_t s, uint64_t *kstats, const QueuePart *part = nullptr)
 {
     int rc;
     unsigned grid = (unsigned)((n_q + 255) / 256);
@@ -796,11 +950,11 @@ static int launch_integrate(const MetricConsts &mc, const lt_opts &o, double lam
         StampDump sd;
         if (o.schedule == LT_SCHED_DIRECT) {
             // wider workgroups and the per-wave stamps (StampDump) exist on this path only, not for the disks
-            static const int k2_block = [] { int b = env_int("LT_K2_BLOCK", 64);
-                                             return (b == 64 || b == 128 || b == 256) ? b : 64; }();
+            // `part`: the queue positions of this launch (the tail split); NULL: the whole queue
+            const QueuePart qp = part ? *part : QueuePart{0, n_q / 64, w.head};
             if ((rc = sd.begin((size_t)(n_q / 64)))) return rc;
-            rc = launch_direct<T, PlainKernels<T>>(o, w, n_q, s, k2_block, [&](auto kernel, unsigned kgrid, uint32_t long_iters, unsigned long long *head) {
-                kernel<<<kgrid, k2_block, 0, s>>>(k, w.ic<T>(), w.fin0<T>(), w.fin1<T>(), n_q, long_iters, sd.dev, kstats, head);
+            rc = launch_direct<T, PlainKernels<T>>(o, qp, s, k2_block(), [&](auto kernel, unsigned kgrid, uint32_t long_iters, unsigned long long *head) {
+                kernel<<<kgrid, k2_block(), 0, s>>>(k, w.ic<T>(), w.fin0<T>(), w.fin1<T>(), qp.q_end(), long_iters, sd.dev, kstats, head, qp.tile0);
             });
             if (rc) return rc;
         } else {
@@ -947,22 +1101,48 @@ template <typename Launch> static void launch_epilogue_rows(const CamConsts &c, 
     });
 }
 
+// The same for the local rows [row0, row1), in slices of at most 65535 rows (grid.y carries the row within a slice):
+// launch(T{}, std::bool_constant<HAS_BG>{}, grid, first row of the slice).
+template <typename Launch>
+static void launch_epilogue_rows(const CamConsts &c, const lt_opts &o, const FrameOut &fo, int row0, int row1, Launch launch)
+{
+    const bool has_bg = fo.bg != nullptr && (fo.rgb || fo.rgba);
+    with_precision(o.precision, [&](auto t) {
+        for (int r = row0; r < row1; r += std::min(row1 - r, 65535)) {
+            const dim3 ge((unsigned)((c.W + EPILOGUE_BLOCK - 1) / EPILOGUE_BLOCK), (unsigned)std::min(row1 - r, 65535));
+            if (has_bg) launch(t, std::true_type{}, ge, r);
+            else launch(t, std::false_type{}, ge, r);
+        }
+    });
+}
+
+// Whether a frame's epilogue is the one that stages background tiles in LDS (opts->bg_sampling, a background is lensed)
+static bool epilogue_is_lds(const lt_opts &o, const FrameOut &fo) { return o.bg_sampling == LT_BG_LDS_TILES && fo.bg && (fo.rgb || fo.rgba); }
+
+// k_epilogue_frame over the local rows [row0, row1); the counters stay in the workspace's partial sets
+static int launch_epilogue_frame_rows(const CamConsts &c, const MetricConsts &mc, const lt_opts &o, const Workspace &w,
+                                      const FrameOut &fo, hipStream_t s, int row0, int row1)
+{
+    launch_epilogue_rows(c, o, fo, row0, row1, [&](auto t, auto bg, dim3 ge, int r0) {
+        using T = decltype(t);
+        k_epilogue_frame<T, decltype(bg)::value><<<ge, EPILOGUE_BLOCK, 0, s>>>(c, mc, w.fin0<T>(), w.fin1<T>(), fo, r0);
+    });
+    HIP_TRY(hipGetLastError());
+    return LT_OK;
+}
+
 static int launch_epilogue_frame(const CamConsts &c, const MetricConsts &mc, const lt_opts &o, const Workspace &w,
-                                 const FrameOut &fo, uint64_t *d_stats, hipStream_t s)
+                                 const FrameOut &fo, uint64_t *d_stats, hipStream_t s, int row0 = 0)
 {
     // background tiles staged in LDS when a background is lensed (opts->bg_sampling)
-    if (o.bg_sampling == LT_BG_LDS_TILES && fo.bg && (fo.rgb || fo.rgba)) {
+    if (epilogue_is_lds(o, fo)) {
         const unsigned gp = (unsigned)((int64_t)((c.W + 15) / 16) * ((c.rows_local + 15) / 16)); // one 16x16 tile per workgroup
         with_precision(o.precision, [&](auto t) {
             using T = decltype(t);
             k_epilogue_frame_lds<T><<<gp, 256, 0, s>>>(c, mc, w.fin0<T>(), w.fin1<T>(), fo);
         });
-    } else {
-        launch_epilogue_rows(c, o, fo, [&](auto t, auto bg, dim3 ge) {
-            using T = decltype(t);
-            k_epilogue_frame<T, decltype(bg)::value><<<ge, EPILOGUE_BLOCK, 0, s>>>(c, mc, w.fin0<T>(), w.fin1<T>(), fo);
-        });
-    }
+    } else if (int rc = launch_epilogue_frame_rows(c, mc, o, w, fo, s, row0, c.rows_local)) // (row0 > 0: the rows before were shaded already, the tail split)
+        return rc;
     if (d_stats) k_stats_reduce<<<1, STAT_SLOTS, 0, s>>>(w.partials, (unsigned long long *)d_stats, LT_STAT_BG_TILES_LDS, LT_STAT_BG_TILES_GLOBAL);
     HIP_TRY(hipGetLastError());
     return LT_OK;
@@ -1008,7 +1188,10 @@ static int make_camera(const lt_camera *cam, int kind, const lt_opts &o, const M
     c.trace_rows = c.use_tb ? (c.H + 1) / 2 : c.rows_local;
     c.tiles_x = (c.W + 7) / 8;
     if (c.rows_local <= 0) return LT_OK;
-    if (c.rows_local > 65535) // (the epilogue's launch grid carries the row in its y dimension; checked before anything is launched)
+    // (the disks' epilogues carry the whole partition's rows in their launch grid's y dimension; the frame path's epilogue is
+    // launched in slices of that many rows, launch_epilogue_rows; a supersampled frame's bands are cut to fit.  Checked
+    // before anything is launched)
+    if (disk && c.rows_local > 65535)
         return fail(LT_ERR_UNSUPPORTED, "a partition of %d rows exceeds the epilogue's launch grid (65535 rows): split it (n_parts)", c.rows_local);
     const int tiles_y = (c.trace_rows + 7) / 8;
     c.tiles_y = tiles_y;
@@ -1101,6 +1284,23 @@ struct KeyGuard {
     ~KeyGuard() { if (ok) return; std::lock_guard<std::mutex> lk(g_mu); sl->ic_key.valid = false; }
 };
 
+// The tail split's join: once the fork event is recorded, the slot's stream waits for whatever the side stream was given
+// before the call returns, on every path (grow() and lt_release_stream rely on it).  record() after the side stream's
+// last launch, wait() where the user's stream needs its results; a return before either does both here.
+struct SideJoin {
+    StreamSlot *sl;
+    hipStream_t s;
+    bool recorded = false, waited = false;
+    int record() { HIP_TRY(hipEventRecord(sl->join, sl->side)); recorded = true; return LT_OK; }
+    int wait() { HIP_TRY(hipStreamWaitEvent(s, sl->join, 0)); waited = true; return LT_OK; }
+    ~SideJoin()
+    {
+        if (waited) return; // (an error return: g_err keeps the message of what failed)
+        if ((!recorded && hipEventRecord(sl->join, sl->side) != hipSuccess) || hipStreamWaitEvent(s, sl->join, 0) != hipSuccess)
+            (void)hipStreamSynchronize(sl->side);
+    }
+};
+
 // disk == NULL: the frame path.  Else the disk frame (lt_render_disk_dev): every row traced, the disk kernels.
 // aa != NULL: a band of a supersampled frame, resolved by k_epilogue_aa instead of the mode's epilogue.
 static int render_dev_impl(const lt_camera *cam, const lt_metric *metric, const lt_opts *opts, const float *d_bg,
@@ -1157,6 +1357,27 @@ static int render_dev_impl(const lt_camera *cam, const lt_metric *metric, const 
     // small launch behind it folds them into the caller's counters
     FrameOut fo{d_bg, bg_channels, d_fa, d_w, d_status, d_steps, d_rgb, d_rgba, d_stats ? (uint64_t *)w.partials : nullptr};
 
+    // The tail split, decided once per call: the plain Kerr frame of the direct schedule whose epilogue is
+    // k_epilogue_frame over every row (no disk, no supersampling band, no top/bottom mirror, no LDS-tiled background), on a
+    // stream that is not being captured -- a capture would draw the side stream into the caller's graph --, and without the
+    // diagnostic wave stamps, which are dumped per launch.  tail_split_plan decides whether the frame has the rows for it.
+    int ty_split = c.tiles_y;
+    int64_t pos_split = n_q / 64;
+    bool split = false;
+    const int split_request = tail_split_request();
+    if (split_request != 0 && !disk && !aa && mc.kind == LT_METRIC_KERR && o.schedule == LT_SCHED_DIRECT && !c.use_tb &&
+        !epilogue_is_lds(o, fo) && !getenv("LT_STAMPS_FILE")) {
+        hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(s, &capturing) != hipSuccess) {
+            (void)hipGetLastError(); // (the legacy stream while another stream captures: no split, and the launches below report what there is to report)
+            capturing = hipStreamCaptureStatusActive;
+        }
+        if (capturing == hipStreamCaptureStatusNone) {
+            const int slots = with_precision(o.precision, [&](auto t) { return direct_slots<decltype(t)>(o); });
+            split = tail_split_plan(c.tiles_x, c.tiles_y, c.strip_x1 - c.strip_x0, c.hot_y1, slots, split_request, &ty_split, &pos_split);
+        }
+    }
+
     if ((rc = tm.mark(0, s))) return rc;
     // (marks 0 and 1 are recorded either way: a reused prologue reports a time near zero, not a stale one)
     if (!reuse && (rc = launch_prologue_camera(c, mc, o, w, n_q, s))) return rc;
@@ -1164,8 +1385,40 @@ static int render_dev_impl(const lt_camera *cam, const lt_metric *metric, const 
         std::lock_guard<std::mutex> lk(g_mu);
         slot->ic_key = std::move(key);
         ++(reuse ? g_ic_hits : g_ic_misses);
+        ++(split ? g_split_frames : g_whole_frames);
     }
     if ((rc = tm.mark(1, s))) return rc;
+    if (split) {
+        // user's stream:  record fork . K2a (part A) ......... K3a (rows of part A) . wait join . K3b (the other rows) . reduce
+        // side stream:    wait fork . zero head_b . K2b (part B) . record join
+        // K2a's grid fills the chip; K2b's workgroups get the wave slots K2a's wavefronts leave as the queue runs dry, K3a
+        // starts when K2a has ended and runs beside what is left of K2b.  No wave waits for another and every output is
+        // written on the user's stream, K3b's after the join: what the caller may assume on return is what it was.
+        // Timing marks: 2 is recorded after the join, so integrate_ms spans K2a and K2b AND the K3a that overlaps them, and
+        // epilogue_ms is K3b and the reduce alone.  The three times still tile the frame (their sum is the span from mark 0
+        // to mark 3), so a rate derived from integrate_ms can only read lower than the kernel's own, never higher.
+        const int64_t n_tiles = n_q / 64;
+        const QueuePart part_a{0, pos_split, w.head}, part_b{pos_split, n_tiles - pos_split, w.head_b};
+        const int rows_a = std::min(ty_split * 8, c.rows_local);
+        if ((rc = slot_side(slot))) return rc;
+        HIP_TRY(hipEventRecord(slot->fork, s));
+        SideJoin sj{slot, s}; // from here on every return joins the side stream back into `s`
+        auto integrate = [&](const QueuePart &part, hipStream_t on) {
+            return with_precision(o.precision, [&](auto t) { return launch_integrate<decltype(t)>(mc, o, lambda_max, w, n_q, on, d_stats, &part); });
+        };
+        if ((rc = integrate(part_a, s))) return rc;
+        HIP_TRY(hipStreamWaitEvent(slot->side, slot->fork, 0));
+        if ((rc = integrate(part_b, slot->side))) return rc;
+        if ((rc = sj.record())) return rc;
+        if (rows_a > 0 && (rc = launch_epilogue_frame_rows(c, mc, o, w, fo, s, 0, rows_a))) return rc;
+        if ((rc = sj.wait())) return rc;
+        if ((rc = tm.mark(2, s))) return rc;
+        if ((rc = launch_epilogue_frame(c, mc, o, w, fo, d_stats, s, rows_a))) return rc;
+        if ((rc = tm.mark(3, s))) return rc;
+        tm.finish();
+        guard.ok = true;
+        return LT_OK;
+    }
     if ((rc = launch_integrate_any(mc, o, lambda_max, w, n_q, s, d_stats, disk, recs))) return rc;
     if ((rc = tm.mark(2, s))) return rc;
     if (aa) rc = launch_epilogue_aa(c, mc, o, w, fo, d_stats, s, disk, recs, *aa);

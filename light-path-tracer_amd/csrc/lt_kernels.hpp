@@ -413,6 +413,11 @@ template <typename S> __device__ __forceinline__ void take_from_lane(S &s, uint3
 // (4.7 of 5 slots occupied).  A wave that takes the next tile itself does neither.  `head` == nullptr: one tile per
 // workgroup, tile = workgroup index (the batch twins' short launches, LT_D_PERSIST=0).
 //
+// A launch covers the queue positions [tile0, n_q / 64): the whole queue (tile0 = 0, what the disks' kernels pass), or one
+// of the two parts the plain frame path cuts it into (the tail split, lt_api.hip).  The head word counts from 0 and the
+// workgroup index starts at 0 in either case, tile0 is added to both; `tile` -- what the records, the stamps and WaveMeter's
+// sampling are indexed with -- is the position in the whole queue.
+//
 // The loop is shared by the kernels of the direct schedule (k_kerr_direct here, k_kerr_disk, k_kerr_disk_images); what
 // they do differently is in `step`, a policy object passed by value (the kernel's own arguments), and in its Step::Lane,
 // what it keeps per ray next to `st` and `rc` (declared where they are: the order of the locals decides the compiler's
@@ -440,18 +445,18 @@ __device__ __forceinline__ void direct_tiles(const KerrConsts<T> &k_in, Step ste
                                              typename Vec4<T>::type *__restrict__ fin0,
                                              typename Vec4<T>::type *__restrict__ fin1, int64_t n_q, uint32_t long_iters,
                                              uint4 *__restrict__ stamps, uint64_t *__restrict__ kstats,
-                                             unsigned long long *__restrict__ head)
+                                             unsigned long long *__restrict__ head, int64_t tile0 = 0)
 {
     KerrConsts<T> k = k_in;
     pin_consts(k);
     const int lane = (int)(threadIdx.x & 63u);
-    int64_t tile = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    int64_t tile = tile0 + (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     for (;;) {
     if (head) {
         unsigned long long w = 0;
         if (lane == 0) w = atomicAdd(head, 1ull);
-        tile = (int64_t)(((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(w >> 32)) << 32) |
-                         (uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)w));
+        tile = tile0 + (int64_t)(((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(w >> 32)) << 32) |
+                                 (uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)w));
     }
     const int64_t q = tile * 64 + lane;
     if (q >= n_q) return; // n_q is a multiple of 64: the whole wave leaves (queue empty, or a workgroup past the end)
@@ -544,9 +549,10 @@ __global__ void __launch_bounds__(256, Integ::MIN_WAVES_PER_SIMD) k_kerr_direct(
                                                          typename Vec4<T>::type *__restrict__ fin0,
                                                          typename Vec4<T>::type *__restrict__ fin1, int64_t n_q,
                                                          uint32_t long_iters, uint4 *__restrict__ stamps,
-                                                         uint64_t *__restrict__ kstats, unsigned long long *__restrict__ head)
+                                                         uint64_t *__restrict__ kstats, unsigned long long *__restrict__ head,
+                                                         int64_t tile0)
 {
-    direct_tiles<T, Integ>(k_in, PlainStep<T, Integ>{}, ic, fin0, fin1, n_q, long_iters, stamps, kstats, head);
+    direct_tiles<T, Integ>(k_in, PlainStep<T, Integ>{}, ic, fin0, fin1, n_q, long_iters, stamps, kstats, head, tile0);
 }
 
 // Queue schedule: persistent wavefronts.  The grid is sized to fill the chip once (blocks = CUs x
@@ -959,10 +965,12 @@ constexpr int EPILOGUE_BLOCK = 512;
 template <typename T, bool HAS_BG>
 __global__ void __launch_bounds__(EPILOGUE_BLOCK) k_epilogue_frame(CamConsts c, MetricConsts m,
                                                                    const typename Vec4<T>::type *__restrict__ fin0,
-                                                                   const typename Vec4<T>::type *__restrict__ fin1, FrameOut o)
+                                                                   const typename Vec4<T>::type *__restrict__ fin1, FrameOut o,
+                                                                   int row0)
 {
     // grid = (row segments of EPILOGUE_BLOCK pixels, rows): no 64-bit division to find the row of a pixel
-    const int lrow = (int)blockIdx.y, ix = (int)(blockIdx.x * EPILOGUE_BLOCK + threadIdx.x);
+    // (row0: the first local row of this launch -- a launch is a slice of at most 65535 rows of the partition)
+    const int lrow = row0 + (int)blockIdx.y, ix = (int)(blockIdx.x * EPILOGUE_BLOCK + threadIdx.x);
     const int64_t p = (int64_t)lrow * c.W + ix;
     StatAcc acc;
     if (ix < c.W) {

@@ -175,6 +175,9 @@ SIGNATURES = {
     "lt_disk_shade_probe": (C.c_int, [C.POINTER(Metric), C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_int64] + [C.c_void_p] * 3),
     "lt_set_eq_streak": (C.c_int, [C.c_int]),
     "lt_set_unit_streak": (C.c_int, [C.c_int]),
+    "lt_set_tail_split": (C.c_int, [C.c_int]),
+    "lt_tail_split_counts": (None, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "lt_tail_split_plan": (C.c_int, [C.c_int32] * 7 + [C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "lt_sincos_q1_probe": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "lt_local_rows": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "lt_global_row": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
@@ -681,6 +684,28 @@ def set_eq_streak(on):
 def set_unit_streak(on):
     """Enable / disable the unit-step form of the fixed-quadrant loop for the launches that follow; returns the previous setting."""
     return bool(load().lt_set_unit_streak(int(bool(on))))
+
+
+def set_tail_split(tile_rows):
+    """The tail split of the frame path for the frames that follow: -1 automatic, 0 off, n > 0 that many tile rows; returns
+    the previous setting."""
+    return int(load().lt_set_tail_split(int(tile_rows)))
+
+
+def tail_split_counts():
+    """(split, whole): frames whose integrate launch was split in two / that ran as one launch."""
+    a, b = C.c_uint64(), C.c_uint64()
+    load().lt_tail_split_counts(C.byref(a), C.byref(b))
+    return int(a.value), int(b.value)
+
+
+def tail_split_plan(tiles_x, tiles_y, strip_x0, strip_x1, hot_y1, slots, request):
+    """(split, ty_split, pos_split) of lt_tail_split_plan; needs no device."""
+    ty, pos = C.c_int32(), C.c_int64()
+    r = load().lt_tail_split_plan(tiles_x, tiles_y, strip_x0, strip_x1, hot_y1, slots, request, C.byref(ty), C.byref(pos))
+    if r < 0:
+        raise LtraceError(ERR_INVALID_ARG, "lt_tail_split_plan: the arguments describe no frame")
+    return bool(r), int(ty.value), int(pos.value)
 
 
 def sincos_q1_probe(bits_lo, bits_hi):

@@ -43,7 +43,9 @@ def profiled(tag, pmc, args):
     os.makedirs(d, exist_ok=True)
     cmd = ["rocprofv3", "--kernel-trace", "--pmc"] + pmc + ["--output-format", "csv", "-d", d, "--",
                                                            "python3", BENCH] + COMMON + args
-    env = dict(os.environ, TMPDIR="/tmp")
+    # LT_TAIL_SPLIT=0: the figures are per LAUNCH of the integrate kernel and bench.py scales them by the loop iterations of
+    # a whole frame, so a frame must be one launch here; the split launches execute the same instructions in two parts
+    env = dict(os.environ, TMPDIR="/tmp", LT_TAIL_SPLIT="0")
     r = subprocess.run(cmd, cwd="/tmp", env=env, capture_output=True, text=True)
     line = [l for l in r.stdout.splitlines() if l.startswith("{")]
     if r.returncode != 0 or not line:
