@@ -363,6 +363,28 @@ int lt_disk_advance_probe(const lt_metric *metric, double r_obs, double lambda_m
                           const double *aux, const uint32_t *steps, const uint8_t *act, int64_t n, double *out_state,
                           double *out_aux, int32_t *out_int, double *out_hit, double *out_on);
 
+/* Up to `iters` iterations of the timed trace's lane (pol = 0: DiskTimedStep::advance of lt_trace_disk_hits; pol = 1:
+ * DiskPolStep::advance of lt_trace_disk_pol) per row, by the calls the tile loop makes (begin_tile, bind, advance):
+ * LT_INTEGRATOR_RK4 (32, 64), LT_INTEGRATOR_DP45 and LT_INTEGRATOR_DP45_EXACT (64).  A row leaves the loop at its first
+ * event other than 4 (running).  Inputs as lt_disk_advance_probe, plus what a lane carries between iterations, so that N
+ * calls of one iteration resume exactly: k1 (n,5) and sc0 (n,2), DP45's carried derivative and [sin, cos] (NULL: computed
+ * from the state, as at a start; ignored by RK4); lane (n,5): t_hi, t_lo and the rates t', r', theta' at the state; lane_int
+ * (n,2): 1 if the rates are set, the hits counted so far.
+ * out_state (n,5), out_aux (n,2), out_k1 (n,5), out_sc (n,2) (NaN for RK4), out_lane (n,5), out_lane_int (n,2): the same after
+ * the last iteration; out_int (n,3): the last event, steps, iterations run.  The records, slot-major as the kernels keep them
+ * and NaN where nothing was stored: out_img (max_images, n, 2) (r, phi), out_tim (max_images, n), out_mom (max_images, n, 2)
+ * (p_r, p_theta; NaN with pol = 0).  out_trace (iters, n, 7), may be NULL: after each iteration r, theta, p_r, p_theta, the
+ * h counted (0 where the attempt added no time) and the dt added -- evaluated by the probe itself from the step's ends and the
+ * lane's rates by the lane's own statements, and tied to the lane through out_lane's (t_hi, t_lo) -- and the hits counted so far; NaN for iterations a row did not run.  Every value
+ * is the T computed, widened to float64. */
+int lt_disk_timed_advance_probe(const lt_metric *metric, double r_obs, double lambda_max, double h_max, double r_in, double r_out,
+                                int integrator, int precision, int pol, const double *states, const double *p_phi,
+                                const uint8_t *refine, const double *aux, const uint32_t *steps, const uint8_t *act,
+                                const double *k1, const double *sc0, const double *lane, const int32_t *lane_int, int64_t n,
+                                int32_t max_images, int32_t iters, double *out_state, double *out_aux, double *out_k1,
+                                double *out_sc, int32_t *out_int, double *out_lane, int32_t *out_lane_int, double *out_img,
+                                double *out_tim, double *out_mom, double *out_trace);
+
 /* The closed forms a hit goes through on its way to a pixel, as the disk epilogues state them.  in (n,4): r, phi (unwrapped),
  * xi, g_given.  out_f64 (n,5): g(r, xi), phi wrapped to [0, 2 pi), then the unclamped emission E (3) from the float32-rounded
  * (r, g) -- of g_given instead of g where g_given is not NaN; out_half (n): the half orbits of phi; out_f32 (n,4): the disk
@@ -658,6 +680,8 @@ int lt_trace_batch_kerr_disk_hits(double M, double a, double r_obs, const double
  * p_theta), h (n), tau (n), out (n), all float64 HOST arrays; the arithmetic runs in `precision` (32 or 64). */
 int lt_step_time_probe(const lt_metric *metric, const double *p_phi, const double *y0, const double *y1, const double *h,
                        const double *tau, int64_t n, int precision, double *out);
+/* The rates a lane carries from one step to the next: out (n, 3) = t', r', theta' at y (n, 4: r, theta, p_r, p_theta). */
+int lt_time_rates_probe(const lt_metric *metric, const double *p_phi, const double *y, int64_t n, int precision, double *out);
 
 /* A spot of Gaussian profile on the circular equatorial orbit of the disk's direction at r_spot, at azimuth phi0 at
  * coordinate time 0: phi_s(t) = phi0 + Omega(r_spot) t, Omega = sqrt(M) / (r^1.5 + a sqrt(M)). */

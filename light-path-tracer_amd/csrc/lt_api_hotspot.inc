@@ -94,6 +94,31 @@ extern "C" int lt_step_time_probe(const lt_metric *metric, const double *p_phi, 
     return LT_OK;
 }
 
+extern "C" int lt_time_rates_probe(const lt_metric *metric, const double *p_phi, const double *y, int64_t n, int precision, double *out)
+{
+    int rc = require_device();
+    if (rc) return rc;
+    if (!metric || metric->kind != LT_METRIC_KERR) return fail(LT_ERR_UNSUPPORTED, "the time-rates probe needs LT_METRIC_KERR");
+    if (precision != 32 && precision != 64) return fail(LT_ERR_INVALID_ARG, "precision must be 32 or 64");
+    if (n <= 0) return LT_OK;
+    if (!p_phi || !y || !out) return fail(LT_ERR_INVALID_ARG, "null array");
+    MetricConsts mc;
+    if ((rc = make_metric(metric, 50.0, M_PI / 2, 0.0, &mc))) return rc;
+    Staging st;
+    const int i_l = st.in(p_phi, n, 8), i_y = st.in(y, n, 32);
+    const int i_o = st.out(out, n, 24);
+    if ((rc = st.commit(nullptr))) return rc;
+    with_precision(precision, [&](auto t) {
+        using T = decltype(t);
+        k_time_rates_probe<T><<<(unsigned)((n + 63) / 64), 64>>>(make_kerr<T>(mc, 5000.0, 1.0), st.dev<const double>(i_l), st.dev<const double>(i_y),
+                                                                 n, st.dev<double>(i_o));
+    });
+    HIP_TRY(hipGetLastError());
+    if ((rc = st.fetch(i_o))) return rc;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return LT_OK;
+}
+
 extern "C" void lt_default_hotspot(lt_hotspot *h)
 {
     memset(h, 0, sizeof(*h));

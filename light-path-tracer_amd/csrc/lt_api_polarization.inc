@@ -127,6 +127,69 @@ extern "C" int lt_polarization_probe(const lt_metric *metric, double r_obs, doub
     return LT_OK;
 }
 
+extern "C" int lt_disk_timed_advance_probe(const lt_metric *metric, double r_obs, double lambda_max, double h_max, double r_in, double r_out,
+                                           int integrator, int precision, int pol, const double *states, const double *p_phi,
+                                           const uint8_t *refine, const double *aux, const uint32_t *steps, const uint8_t *act,
+                                           const double *k1, const double *sc0, const double *lane, const int32_t *lane_int, int64_t n,
+                                           int32_t max_images, int32_t iters, double *out_state, double *out_aux, double *out_k1,
+                                           double *out_sc, int32_t *out_int, double *out_lane, int32_t *out_lane_int, double *out_img,
+                                           double *out_tim, double *out_mom, double *out_trace)
+{
+    MetricConsts mc;
+    DiskParams dp;
+    int rc = disk_probe_setup(metric, r_obs, r_in, r_out, &mc, &dp);
+    if (rc) return rc;
+    if (precision != 32 && precision != 64) return fail(LT_ERR_INVALID_ARG, "precision must be 32 or 64");
+    const bool is_dp45 = integrator == LT_INTEGRATOR_DP45 || integrator == LT_INTEGRATOR_DP45_EXACT;
+    if (!(integrator == LT_INTEGRATOR_RK4 || (is_dp45 && precision == 64)))
+        return fail(LT_ERR_UNSUPPORTED, "the timed advance probe runs RK4 (float32, float64), DP45 and DP45-exact (float64)");
+    if (!(h_max > 0.0)) return fail(LT_ERR_INVALID_ARG, "h_max must be positive");
+    if (max_images < 1 || max_images > DISK_MAX_IMAGES) return fail(LT_ERR_INVALID_ARG, "max_images %d not in [1, %d]", max_images, DISK_MAX_IMAGES);
+    if (iters < 1 || iters > (1 << 20)) return fail(LT_ERR_INVALID_ARG, "iters %d not in [1, 2^20]", iters);
+    if (n <= 0) return LT_OK;
+    if (out_trace && (double)n * iters * 7 > (double)(1 << 28)) return fail(LT_ERR_INVALID_ARG, "trace of %lld x %d rows too large", (long long)n, iters);
+    if (!states || !p_phi || !refine || !aux || !steps || !act || !lane || !lane_int || !out_state || !out_aux || !out_k1 || !out_sc ||
+        !out_int || !out_lane || !out_lane_int || !out_img || !out_tim || !out_mom)
+        return fail(LT_ERR_INVALID_ARG, "null pointer");
+    const size_t el = elem_size(precision), slots = (size_t)max_images * (size_t)n, tr = out_trace ? (size_t)n * iters * 56 : 0;
+    DevBuf ds, dl, dr, da, dst, dac, dk, dsc, dla, dli, wi, wt, wm, os, oa, ok, osc, oi, ol, oli, og, ot, om, otr;
+    if ((rc = probe_upload(ds, states, n * 40)) || (rc = probe_upload(dl, p_phi, n * 8)) || (rc = probe_upload(dr, refine, n)) ||
+        (rc = probe_upload(da, aux, n * 16)) || (rc = probe_upload(dst, steps, n * 4)) || (rc = probe_upload(dac, act, n)) ||
+        (rc = probe_upload(dk, k1, n * 40)) || (rc = probe_upload(dsc, sc0, n * 16)) || (rc = probe_upload(dla, lane, n * 40)) ||
+        (rc = probe_upload(dli, lane_int, n * 8)) || (rc = wi.alloc(slots * 2 * el)) || (rc = wt.alloc(slots * el)) ||
+        (rc = wm.alloc(slots * 2 * el)) || (rc = os.alloc(n * 40)) || (rc = oa.alloc(n * 16)) || (rc = ok.alloc(n * 40)) ||
+        (rc = osc.alloc(n * 16)) || (rc = oi.alloc(n * 12)) || (rc = ol.alloc(n * 40)) || (rc = oli.alloc(n * 8)) ||
+        (rc = og.alloc(slots * 16)) || (rc = ot.alloc(slots * 8)) || (rc = om.alloc(slots * 16)) || (tr && (rc = otr.alloc(tr))))
+        return rc;
+    if (tr) HIP_TRY(hipMemset(otr.p, 0xff, tr)); // NaN in the rows of iterations a lane did not run
+    TimedProbeIo io{};
+    io.states = (const double *)ds.p; io.p_phi = (const double *)dl.p; io.aux = (const double *)da.p; io.k1 = (const double *)dk.p;
+    io.sc0 = (const double *)dsc.p; io.lane = (const double *)dla.p; io.refine = (const uint8_t *)dr.p; io.act = (const uint8_t *)dac.p;
+    io.steps = (const uint32_t *)dst.p; io.lane_int = (const int32_t *)dli.p; io.n = n; io.max_images = max_images; io.iters = iters;
+    io.w_img = wi.p; io.w_tim = wt.p; io.w_mom = wm.p;
+    io.out_state = (double *)os.p; io.out_aux = (double *)oa.p; io.out_k1 = (double *)ok.p; io.out_sc = (double *)osc.p;
+    io.out_lane = (double *)ol.p; io.out_img = (double *)og.p; io.out_tim = (double *)ot.p; io.out_mom = (double *)om.p;
+    io.trace = tr ? (double *)otr.p : nullptr; io.out_int = (int32_t *)oi.p; io.out_lane_int = (int32_t *)oli.p;
+    auto launch = [&](auto t, auto integ) {
+        using T = decltype(t);
+        using Integ = decltype(integ);
+        const unsigned g = (unsigned)((n + 63) / 64);
+        if (pol) k_disk_timed_advance_probe<T, Integ, true><<<g, 64>>>(make_kerr<T>(mc, lambda_max, h_max), make_disk_consts<T>(mc, dp), io);
+        else k_disk_timed_advance_probe<T, Integ, false><<<g, 64>>>(make_kerr<T>(mc, lambda_max, h_max), make_disk_consts<T>(mc, dp), io);
+    };
+    if (integrator == LT_INTEGRATOR_DP45_EXACT) launch(double{}, Dp45<double, true>{});
+    else if (integrator == LT_INTEGRATOR_DP45) launch(double{}, Dp45<double, false>{});
+    else if (precision == 32) launch(float{}, Rk4<float>{});
+    else launch(double{}, Rk4<double>{});
+    HIP_TRY(hipGetLastError());
+    if ((rc = probe_download(out_state, os, n * 40)) || (rc = probe_download(out_aux, oa, n * 16)) || (rc = probe_download(out_k1, ok, n * 40)) ||
+        (rc = probe_download(out_sc, osc, n * 16)) || (rc = probe_download(out_int, oi, n * 12)) || (rc = probe_download(out_lane, ol, n * 40)) ||
+        (rc = probe_download(out_lane_int, oli, n * 8)) || (rc = probe_download(out_img, og, slots * 16)) ||
+        (rc = probe_download(out_tim, ot, slots * 8)) || (rc = probe_download(out_mom, om, slots * 16)) ||
+        (tr && (rc = probe_download(out_trace, otr, tr)))) return rc;
+    return LT_OK;
+}
+
 // The hot spot's refusals (resolve_hotspot) plus the field's and the polarization records'.
 static int resolve_stokes(const void *hits, const void *pol, int32_t R, int32_t W, int32_t max_images, const lt_metric *metric,
                           const lt_disk *disk, const lt_hotspot *spot, const lt_bfield *field, DiskShade *ds, HotspotShade *hs)

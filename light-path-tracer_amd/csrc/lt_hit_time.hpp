@@ -15,10 +15,14 @@
 
 namespace lt {
 
-// dt/dlambda, dr/dlambda and dtheta/dlambda at one state (outside the horizon: Sigma, Delta > 0).
-template <typename T> struct TimeRates { T t, r, th; };
+// dt/dlambda, dr/dlambda and dtheta/dlambda at one state (outside the horizon: Sigma, Delta > 0).  t = tx * ts: the two
+// factors travel with it for the one place that adds t' to a sum (step_time), which writes that multiply-add as the fma it is
+// to be.  Left to -ffp-contract=fast, the compiler fused the product into the sum in one kernel and not in another: the step
+// rule of k_step_time_probe and that of the timed kernels differed in the last bit on 2 % of whole steps
+// (tests/test_gpu_hit_blocks.py).  A lane carries t, r, th alone: the factors are dead once the step that made them is added.
+template <typename T> struct TimeRates { T t, r, th, tx, ts; };
 
-template <typename T> __device__ __forceinline__ T time_rate(const KerrConsts<T> &k, const RayConsts<T> &rc, T r, T th, T &iS, T &Delta)
+template <typename T> __device__ __forceinline__ void time_rate_parts(const KerrConsts<T> &k, const RayConsts<T> &rc, T r, T th, T &tx, T &iS, T &Delta)
 {
     T s, c;
     M<T>::sincos(th, s, c);
@@ -29,15 +33,16 @@ template <typename T> __device__ __forceinline__ T time_rate(const KerrConsts<T>
     const T inv = M<T>::rcp_pos(Sigma * Delta);
     iS = Delta * inv;
     const T P = M<T>::fma(r, r, rc.c_P);
-    return M<T>::fma(ra * P, Sigma * inv, k.a * M<T>::fma(-k.a, s2, rc.L)) * iS;
+    tx = M<T>::fma(ra * P, Sigma * inv, k.a * M<T>::fma(-k.a, s2, rc.L));
 }
 template <typename T> __device__ __forceinline__ TimeRates<T> time_rates(const KerrConsts<T> &k, const RayConsts<T> &rc, const State5<T> &y)
 {
-    T iS, Delta;
+    T Delta;
     TimeRates<T> o;
-    o.t = time_rate(k, rc, y.r, y.th, iS, Delta);
-    o.r = Delta * y.pr * iS;
-    o.th = y.pth * iS;
+    time_rate_parts(k, rc, y.r, y.th, o.tx, o.ts, Delta);
+    o.t = o.tx * o.ts;
+    o.r = Delta * y.pr * o.ts;
+    o.th = y.pth * o.ts;
     return o;
 }
 
@@ -47,12 +52,14 @@ __device__ __forceinline__ T step_time(const KerrConsts<T> &k, const RayConsts<T
                                        const State5<T> &y1, const TimeRates<T> &d1, T h, T tau)
 {
     const T hr0 = h * d0.r, hr1 = h * d1.r, hth0 = h * d0.th, hth1 = h * d1.th;
-    T iS, Delta;
+    T Delta, xm, sm, xe = d1.tx, se = d1.ts;
     const T tm = T(0.5) * tau;
-    const T t_mid = time_rate(k, rc, hermite(y0.r, hr0, y1.r, hr1, tm), hermite(y0.th, hth0, y1.th, hth1, tm), iS, Delta);
-    T t_end = d1.t;
-    if (tau != T(1)) t_end = time_rate(k, rc, hermite(y0.r, hr0, y1.r, hr1, tau), hermite(y0.th, hth0, y1.th, hth1, tau), iS, Delta);
-    return (tau * h) * T(1.0 / 6.0) * (d0.t + T(4) * t_mid + t_end);
+    time_rate_parts(k, rc, hermite(y0.r, hr0, y1.r, hr1, tm), hermite(y0.th, hth0, y1.th, hth1, tm), xm, sm, Delta);
+    if (tau != T(1)) time_rate_parts(k, rc, hermite(y0.r, hr0, y1.r, hr1, tau), hermite(y0.th, hth0, y1.th, hth1, tau), xe, se, Delta);
+    // d0.t + 4 t'(mid) + t'(end), the start's rate as the lane carries it (rounded), the other two fused into the sum.  The
+    // result is rounded HERE (fma with +0: the product, and no bare product for the caller's next add to absorb -- the stored
+    // time t_hi + (t_lo + part) took `part` unrounded into its inner add, one stored time in ~250 a last bit off that sequence)
+    return M<T>::fma((tau * h) * T(1.0 / 6.0), M<T>::fma(xe, se, M<T>::fma(T(4) * xm, sm, d0.t)), T(0));
 }
 
 // The thin disk's hooks (DiskImagesStep) plus the elapsed coordinate time of the lane's ray: a compensated (two-term)
@@ -212,6 +219,20 @@ __global__ void k_step_time_probe(KerrConsts<T> k, const double *__restrict__ p_
     a.r = (T)y0[i * 4]; a.th = (T)y0[i * 4 + 1]; a.ph = T(0); a.pr = (T)y0[i * 4 + 2]; a.pth = (T)y0[i * 4 + 3];
     b.r = (T)y1[i * 4]; b.th = (T)y1[i * 4 + 1]; b.ph = T(0); b.pr = (T)y1[i * 4 + 2]; b.pth = (T)y1[i * 4 + 3];
     out[i] = (double)step_time(k, rc, a, time_rates(k, rc, a), b, time_rates(k, rc, b), (T)h[i], (T)tau[i]);
+}
+
+// lt_time_rates_probe: time_rates on n states (r, theta, p_r, p_theta) -- what a lane carries from one step to the next.
+template <typename T>
+__global__ void k_time_rates_probe(KerrConsts<T> k, const double *__restrict__ p_phi, const double *__restrict__ y, int64_t n,
+                                   double *__restrict__ out)
+{
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    RayConsts<T> rc = make_ray_consts(k, (T)p_phi[i], false);
+    State5<T> a;
+    a.r = (T)y[i * 4]; a.th = (T)y[i * 4 + 1]; a.ph = T(0); a.pr = (T)y[i * 4 + 2]; a.pth = (T)y[i * 4 + 3];
+    const TimeRates<T> d = time_rates(k, rc, a);
+    out[i * 3] = (double)d.t; out[i * 3 + 1] = (double)d.r; out[i * 3 + 2] = (double)d.th;
 }
 
 } // namespace lt

@@ -70,8 +70,12 @@ __global__ void __launch_bounds__(256, Integ::MIN_WAVES_PER_SIMD) k_kerr_disk_po
 }
 
 // ---- the rule, float64 ----------------------------------------------------------------------------------------------------
-// Written operation by operation as disk.polarization (Python) states it; the compiler contracts multiply-adds, so the two
-// differ by rounding (tests/test_gpu_polarization.py bounds it by float64's own error on the same records).
+// disk.polarization (Python) states it.  Every multiply-add is written as the fma it is to be, and no product is left beside
+// an add: under -ffp-contract=fast the compiler otherwise decides per kernel which of them to fuse, and the epilogues and the
+// probe, which evaluate this on the same record, differed in the last bits of (q, u) on most records
+// (tests/test_gpu_hit_blocks.py; disk_redshift, lt_disk.hpp, had the same).  Now they agree in every bit; against numpy the
+// rule differs by rounding (tests/test_gpu_polarization.py bounds it by float64's own error on the same records).
+#define LT_FMA __builtin_fma
 struct PolConsts {
     double M, a;
     double r_obs, s_obs, c_obs; // the static observer: r, sin theta, cos theta
@@ -82,27 +86,27 @@ struct PolConsts {
 __device__ __forceinline__ void pol_raise(double M_, double a, double r, double s, double c, const double *k, double *out)
 {
     const double s2 = s * s;
-    const double sigma = r * r + a * a * c * c;
-    const double delta = r * r - 2.0 * M_ * r + a * a;
+    const double sigma = LT_FMA(r, r, a * a * c * c);
+    const double delta = LT_FMA(a, a, LT_FMA(-(2.0 * M_), r, r * r));
     const double sd = sigma * delta;
-    const double x = r * r + a * a;
-    const double gtt = -(x * x - a * a * delta * s2) / sd;
+    const double x = LT_FMA(r, r, a * a);
+    const double gtt = -LT_FMA(-(a * a * delta), s2, x * x) / sd;
     const double gtp = -2.0 * M_ * a * r / sd;
-    const double gpp = (delta - a * a * s2) / (sd * s2);
-    out[0] = gtt * k[0] + gtp * k[3];
+    const double gpp = LT_FMA(-(a * a), s2, delta) / (sd * s2);
+    out[0] = LT_FMA(gtt, k[0], gtp * k[3]);
     out[1] = delta / sigma * k[1];
     out[2] = k[2] / sigma;
-    out[3] = gtp * k[0] + gpp * k[3];
+    out[3] = LT_FMA(gtp, k[0], gpp * k[3]);
 }
 
 // kappa = (A - i B)(r - i a cos theta) of contravariant k, f: one function for both ends, so that a sign or conjugation
 // convention cancels.
 __device__ __forceinline__ void walker_penrose(double a, double r, double s, double c, const double *k, const double *f, double &re, double &im)
 {
-    const double A = (k[0] * f[1] - k[1] * f[0]) + a * s * s * (k[1] * f[3] - k[3] * f[1]);
-    const double B = ((r * r + a * a) * (k[3] * f[2] - k[2] * f[3]) - a * (k[0] * f[2] - k[2] * f[0])) * s;
-    re = A * r - B * a * c;
-    im = -(A * a * c + B * r);
+    const double A = LT_FMA(a * s * s, LT_FMA(k[1], f[3], -(k[3] * f[1])), LT_FMA(k[0], f[1], -(k[1] * f[0])));
+    const double B = LT_FMA(LT_FMA(r, r, a * a), LT_FMA(k[3], f[2], -(k[2] * f[3])), -(a * LT_FMA(k[0], f[2], -(k[2] * f[0])))) * s;
+    re = LT_FMA(A, r, -(B * a * c));
+    im = -LT_FMA(A * a, c, B * r);
 }
 
 // The camera end of one ray: kappa of the two screen vectors.  North e_2 ~ -e_theta + n^theta n, e_1 = e_2 x n in the
@@ -111,21 +115,21 @@ struct PolCamera { double k1re, k1im, k2re, k2im; };
 __device__ __forceinline__ PolCamera pol_camera(const PolConsts &pc, double L, double pr, double pth)
 {
     const double M_ = pc.M, a = pc.a, r = pc.r_obs, s = pc.s_obs, c = pc.c_obs;
-    const double sigma = r * r + a * a * c * c;
-    const double delta = r * r - 2.0 * M_ * r + a * a;
+    const double sigma = LT_FMA(r, r, a * a * c * c);
+    const double delta = LT_FMA(a, a, LT_FMA(-(2.0 * M_), r, r * r));
     const double g_tt = -(1.0 - 2.0 * M_ * r / sigma);
     const double g_tp = -2.0 * M_ * a * r * s * s / sigma;
-    const double g_pp = (r * r + a * a + 2.0 * M_ * a * a * r * s * s / sigma) * s * s;
+    const double g_pp = (LT_FMA(r, r, a * a) + 2.0 * M_ * a * a * r * s * s / sigma) * s * s;
     const double w = -g_tp / g_tt;
     const double n_phi = sqrt(g_pp - g_tp * g_tp / g_tt);
     const double e_r = sqrt(delta / sigma), e_th = 1.0 / sqrt(sigma);
     double n[3] = {-e_r * pr, -e_th * pth, (L - w) / n_phi};
-    const double nn = sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+    const double nn = sqrt(LT_FMA(n[2], n[2], LT_FMA(n[1], n[1], n[0] * n[0])));
     for (int i = 0; i < 3; ++i) n[i] = n[i] / nn;
-    double e2[3] = {n[1] * n[0], n[1] * n[1] - 1.0, n[1] * n[2]};
-    const double en = sqrt(e2[0] * e2[0] + e2[1] * e2[1] + e2[2] * e2[2]);
+    double e2[3] = {n[1] * n[0], LT_FMA(n[1], n[1], -1.0), n[1] * n[2]};
+    const double en = sqrt(LT_FMA(e2[2], e2[2], LT_FMA(e2[1], e2[1], e2[0] * e2[0])));
     for (int i = 0; i < 3; ++i) e2[i] = e2[i] / en;
-    const double e1[3] = {e2[1] * n[2] - e2[2] * n[1], e2[2] * n[0] - e2[0] * n[2], e2[0] * n[1] - e2[1] * n[0]};
+    const double e1[3] = {LT_FMA(e2[1], n[2], -(e2[2] * n[1])), LT_FMA(e2[2], n[0], -(e2[0] * n[2])), LT_FMA(e2[0], n[1], -(e2[1] * n[0]))};
     const double f1[4] = {e1[2] * w / n_phi, e1[0] * e_r, e1[1] * e_th, e1[2] / n_phi};
     const double f2[4] = {e2[2] * w / n_phi, e2[0] * e_r, e2[1] * e_th, e2[2] / n_phi};
     const double kc[4] = {-1.0, -pr, -pth, L};
@@ -142,21 +146,22 @@ __device__ __forceinline__ void pol_record(const PolConsts &pc, const PolCamera 
 {
     const double M_ = pc.M, a = pc.a;
     // the emitter's frame: e_(r) = (0, sqrt(Delta) / r, 0, 0), e_(z) = -d_theta / r, e_(phi) = (ept, 0, 0, epp)
-    const double delta = r * r - 2.0 * M_ * r + a * a;
-    const double g_tt = -(1.0 - 2.0 * M_ / r), g_tp = -2.0 * M_ * a / r, g_pp = r * r + a * a + 2.0 * M_ * a * a / r;
+    const double delta = LT_FMA(a, a, LT_FMA(-(2.0 * M_), r, r * r));
+    const double g_tt = -(1.0 - 2.0 * M_ / r), g_tp = -2.0 * M_ * a / r, g_pp = LT_FMA(r, r, a * a) + 2.0 * M_ * a * a / r;
     const double sM = sqrt(M_), sr = sqrt(r);
     const double r15 = r * sr;
-    const double om = sM / (r15 + a * sM);
-    const double ut = (r15 + a * sM) / (sqrt(r15) * sqrt(r15 - 3.0 * M_ * sr + 2.0 * a * sM));
-    const double u_t = ut * (g_tt + g_tp * om), u_p = ut * (g_tp + g_pp * om);
-    const double nrm = sqrt(g_tt * u_p * u_p - 2.0 * g_tp * u_p * u_t + g_pp * u_t * u_t);
+    const double den = LT_FMA(a, sM, r15);
+    const double om = sM / den;
+    const double ut = den / (sqrt(r15) * sqrt(LT_FMA(2.0 * a, sM, LT_FMA(-(3.0 * M_), sr, r15))));
+    const double u_t = ut * LT_FMA(g_tp, om, g_tt), u_p = ut * LT_FMA(g_pp, om, g_tp);
+    const double nrm = sqrt(LT_FMA(g_pp * u_t, u_t, LT_FMA(-(2.0 * g_tp * u_p), u_t, g_tt * u_p * u_p)));
     const double er = sqrt(delta) / r, ept = u_p / nrm, epp = -u_t / nrm;
     // the received photon k = (-1, -p_r, -p_theta, L) on the triad, and f = (k^ x b^) / sin zeta
-    double kr = -er * pr, kp = epp * L - ept, kz = pth / r;
-    const double kn = sqrt(kr * kr + kp * kp + kz * kz);
+    double kr = -er * pr, kp = LT_FMA(epp, L, -ept), kz = pth / r;
+    const double kn = sqrt(LT_FMA(kz, kz, LT_FMA(kp, kp, kr * kr)));
     kr = kr / kn; kp = kp / kn; kz = kz / kn;
-    const double cr = kp * pc.b[2] - kz * pc.b[1], cp = kz * pc.b[0] - kr * pc.b[2], cz = kr * pc.b[1] - kp * pc.b[0];
-    const double s2 = cr * cr + cp * cp + cz * cz;
+    const double cr = LT_FMA(kp, pc.b[2], -(kz * pc.b[1])), cp = LT_FMA(kz, pc.b[0], -(kr * pc.b[2])), cz = LT_FMA(kr, pc.b[1], -(kp * pc.b[0]));
+    const double s2 = LT_FMA(cz, cz, LT_FMA(cp, cp, cr * cr));
     out[3] = fabs(kz);
     if (s2 < 1e-24) { out[0] = out[1] = out[2] = 0.0; return; }
     const double inv = 1.0 / sqrt(s2);
@@ -168,14 +173,16 @@ __device__ __forceinline__ void pol_record(const PolConsts &pc, const PolCamera 
     double hre, him;
     walker_penrose(a, r, 1.0, 0.0, k, f, hre, him);
     // real (x, y) with x kappa(e_1) + y kappa(e_2) = kappa_hit
-    const double det = cam.k1re * cam.k2im - cam.k2re * cam.k1im;
-    const double x = (hre * cam.k2im - cam.k2re * him) / det;
-    const double y = (cam.k1re * him - hre * cam.k1im) / det;
-    const double n2 = x * x + y * y;
-    out[0] = (x * x - y * y) / n2;
+    const double det = LT_FMA(cam.k1re, cam.k2im, -(cam.k2re * cam.k1im));
+    const double x = LT_FMA(hre, cam.k2im, -(cam.k2re * him)) / det;
+    const double y = LT_FMA(cam.k1re, him, -(hre * cam.k1im)) / det;
+    const double n2 = LT_FMA(y, y, x * x);
+    out[0] = LT_FMA(x, x, -(y * y)) / n2;
     out[1] = 2.0 * x * y / n2;
     out[2] = sqrt(s2);
 }
+
+#undef LT_FMA
 
 // ---- K3 ---------------------------------------------------------------------------------------------------------------
 // The polarization records of one ray: slot j -> (q, u, sin zeta, mu), NaN in an unused slot.  Out: float or double.
@@ -272,6 +279,130 @@ __global__ void k_polarization_probe(PolConsts pc, const double *__restrict__ L,
     double v4[4];
     pol_record(pc, pcam, L[i], hit[i * 3], hit[i * 3 + 1], hit[i * 3 + 2], v4);
     for (int c = 0; c < 4; ++c) out[i * 4 + c] = v4[c];
+}
+
+// ---- the timed lane block by block (lt_disk_timed_advance_probe) -------------------------------------------------------------
+// Step::advance of the timed (POL = false) or the polarized (POL = true) trace up to `iters` times per row, by the calls
+// direct_tiles makes: begin_tile, bind, advance.  Blocks of 64: rows 64 b ... 64 b + 63 share a wavefront; a lane leaves the
+// loop at its first event other than EV_RUNNING.  What a lane carries goes in and comes out, so that N launches of one
+// iteration resume exactly: the integrator's state (states, aux, steps as k_disk_advance_probe; DP45's k1 and [sin, cos],
+// computed from the state where null), the elapsed time and the rates (lane (n,5): t_hi, t_lo, rate.t, rate.r, rate.th;
+// lane_int (n,2): have, n).  The records are the policy's own buffers of T (w_img, w_tim, w_mom: slot-major, n_q = n), filled
+// with NaN by the lane that owns them and handed out as float64.  trace (iters, n, 7), where given: after each iteration
+// r, theta, p_r, p_theta, the h counted (0 where the attempt added nothing), the dt added and the hits counted so far.  h and dt
+// are the probe's OWN evaluation of advance()'s two statements on the values advance() used (the step's ends, the rates the lane
+// carried in and carries out), not a read-out of advance(): they are tied to the lane by the carried (t_hi, t_lo), which is the
+// TwoSum of these terms in every bit or the test that replays it fails.
+struct TimedProbeIo {
+    const double *states, *p_phi, *aux, *k1, *sc0, *lane;
+    const uint8_t *refine, *act;
+    const uint32_t *steps;
+    const int32_t *lane_int;
+    int64_t n;
+    int max_images, iters;
+    void *w_img, *w_tim, *w_mom;
+    double *out_state, *out_aux, *out_k1, *out_sc, *out_lane, *out_img, *out_tim, *out_mom, *trace;
+    int32_t *out_int, *out_lane_int;
+};
+
+template <typename T, typename Integ, bool POL> struct TimedProbeStep {
+    using type = DiskTimedStep<T, Integ>;
+    static __device__ __forceinline__ void set_mom(type &, void *) {}
+};
+template <typename T, typename Integ> struct TimedProbeStep<T, Integ, true> {
+    using type = DiskPolStep<T, Integ>;
+    static __device__ __forceinline__ void set_mom(type &s, void *p) { s.mom = (typename Vec2<T>::type *)p; }
+};
+
+template <typename T>
+__device__ __forceinline__ void timed_probe_state(const KerrConsts<T> &k, const RayConsts<T> &rc, const TimedProbeIo &io, int64_t i, RayState<T> &s)
+{
+    disk_probe_state(k, rc, io.states, io.aux, io.steps, i, s);
+}
+__device__ __forceinline__ void timed_probe_state(const KerrConsts<double> &k, const RayConsts<double> &rc, const TimedProbeIo &io, int64_t i,
+                                                  Dp45State<double> &s)
+{
+    s = dp45_probe_state(k, rc, io.states, io.k1, io.sc0, i);
+    s.lam = io.aux[i * 2 + 0]; s.h = io.aux[i * 2 + 1];
+    s.steps = io.steps[i];
+}
+template <typename T> __device__ __forceinline__ void timed_probe_carry(const RayState<T> &, double *k1, double *sc)
+{
+    for (int j = 0; j < 5; ++j) k1[j] = __builtin_nan("");
+    sc[0] = sc[1] = __builtin_nan("");
+}
+template <typename T> __device__ __forceinline__ void timed_probe_carry(const Dp45State<T> &s, double *k1, double *sc)
+{
+    for (int j = 0; j < 5; ++j) k1[j] = (double)s.k1[j];
+    sc[0] = (double)s.s0; sc[1] = (double)s.c0;
+}
+
+template <typename T, typename Integ, bool POL>
+__global__ void __launch_bounds__(64) k_disk_timed_advance_probe(KerrConsts<T> k_in, DiskConsts<T> d, TimedProbeIo io)
+{
+    const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= io.n) return;
+    using Sel = TimedProbeStep<T, Integ, POL>;
+    using V2 = typename Vec2<T>::type;
+    KerrConsts<T> k = k_in;
+    pin_consts(k);
+    const RayConsts<T> rc = make_ray_consts(k, (T)io.p_phi[i], io.refine[i] != 0);
+    typename Integ::State s;
+    timed_probe_state(k, rc, io, i, s);
+    const T nan = (T)__builtin_nan("");
+    V2 *w_img = (V2 *)io.w_img, *w_mom = (V2 *)io.w_mom;
+    T *w_tim = (T *)io.w_tim;
+    for (int j = 0; j < io.max_images; ++j) {
+        V2 v;
+        v.x = v.y = nan;
+        w_img[(int64_t)j * io.n + i] = v;
+        w_mom[(int64_t)j * io.n + i] = v;
+        w_tim[(int64_t)j * io.n + i] = nan;
+    }
+    typename Sel::type step;
+    step.d = d;
+    step.img = w_img; step.hits = nullptr; step.n_q = io.n; step.max_images = io.max_images; step.tim = w_tim;
+    Sel::set_mom(step, io.w_mom);
+    typename Sel::type::Lane l;
+    step.begin_tile(l, k);
+    step.bind(l, k, rc);
+    l.t_hi = (T)io.lane[i * 5 + 0]; l.t_lo = (T)io.lane[i * 5 + 1];
+    l.rate.t = (T)io.lane[i * 5 + 2]; l.rate.r = (T)io.lane[i * 5 + 3]; l.rate.th = (T)io.lane[i * 5 + 4];
+    l.rate.tx = l.rate.ts = nan; // (the factors of a carried rate are dead: step_time reads them of the step's END alone)
+    l.have = io.lane_int[i * 2 + 0] != 0;
+    l.n = (uint32_t)io.lane_int[i * 2 + 1];
+    const bool act = io.act[i] != 0;
+    int ev = EV_RUNNING, made = 0;
+    while (made < io.iters) {
+        const State5<T> y0 = s.y;
+        const T lam0 = s.lam;
+        const T h_try = DiskStepLen<Integ>::h(k, rc, s);
+        const TimeRates<T> d0 = l.have ? l.rate : time_rates(k, rc, y0);
+        ev = step.advance(l, k, rc, s, i, act);
+        if (io.trace) {
+            const T h = s.lam != lam0 ? h_try : T(0);
+            const T dt = h != T(0) ? step_time(k, rc, y0, d0, s.y, l.rate, h, T(1)) : T(0);
+            double *tr = io.trace + ((int64_t)made * io.n + i) * 7;
+            tr[0] = (double)s.y.r; tr[1] = (double)s.y.th; tr[2] = (double)s.y.pr; tr[3] = (double)s.y.pth;
+            tr[4] = (double)h; tr[5] = (double)dt; tr[6] = (double)l.n;
+        }
+        ++made;
+        if (ev != EV_RUNNING) break;
+    }
+    io.out_state[i * 5 + 0] = (double)s.y.r; io.out_state[i * 5 + 1] = (double)s.y.th; io.out_state[i * 5 + 2] = (double)s.y.ph;
+    io.out_state[i * 5 + 3] = (double)s.y.pr; io.out_state[i * 5 + 4] = (double)s.y.pth;
+    io.out_aux[i * 2 + 0] = (double)s.lam; io.out_aux[i * 2 + 1] = (double)disk_probe_aux1(s);
+    timed_probe_carry(s, io.out_k1 + i * 5, io.out_sc + i * 2);
+    io.out_int[i * 3 + 0] = ev; io.out_int[i * 3 + 1] = (int32_t)s.steps; io.out_int[i * 3 + 2] = made;
+    io.out_lane[i * 5 + 0] = (double)l.t_hi; io.out_lane[i * 5 + 1] = (double)l.t_lo;
+    io.out_lane[i * 5 + 2] = (double)l.rate.t; io.out_lane[i * 5 + 3] = (double)l.rate.r; io.out_lane[i * 5 + 4] = (double)l.rate.th;
+    io.out_lane_int[i * 2 + 0] = l.have ? 1 : 0; io.out_lane_int[i * 2 + 1] = (int32_t)l.n;
+    for (int j = 0; j < io.max_images; ++j) {
+        const int64_t slot = (int64_t)j * io.n + i;
+        io.out_img[slot * 2 + 0] = (double)w_img[slot].x; io.out_img[slot * 2 + 1] = (double)w_img[slot].y;
+        io.out_mom[slot * 2 + 0] = (double)w_mom[slot].x; io.out_mom[slot * 2 + 1] = (double)w_mom[slot].y;
+        io.out_tim[slot] = (double)w_tim[slot];
+    }
 }
 
 // ---- Stokes siblings of the hot spot's kernels ---------------------------------------------------------------------------

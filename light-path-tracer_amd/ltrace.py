@@ -173,6 +173,8 @@ SIGNATURES = {
     "lt_disk_advance_probe": (C.c_int, [C.POINTER(Metric)] + [C.c_double] * 5 + [C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_int64]
                               + [C.c_void_p] * 5),
     "lt_disk_shade_probe": (C.c_int, [C.POINTER(Metric), C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_int64] + [C.c_void_p] * 3),
+    "lt_disk_timed_advance_probe": (C.c_int, [C.POINTER(Metric)] + [C.c_double] * 5 + [C.c_int] * 3 + [C.c_void_p] * 10
+                                    + [C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 11),
     "lt_set_eq_streak": (C.c_int, [C.c_int]),
     "lt_set_unit_streak": (C.c_int, [C.c_int]),
     "lt_set_tail_split": (C.c_int, [C.c_int]),
@@ -232,6 +234,7 @@ SIGNATURES = {
                                                 C.c_void_p, C.c_void_p]),
     "lt_step_time_probe": (C.c_int, [C.POINTER(Metric), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_int64, C.c_int, C.c_void_p]),
+    "lt_time_rates_probe": (C.c_int, [C.POINTER(Metric), C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "lt_default_hotspot": (None, [C.POINTER(HotSpot)]),
     "lt_shade_hotspot_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Metric),
                                        C.POINTER(Disk), C.POINTER(HotSpot), C.c_double, C.c_void_p, C.c_int32, C.c_void_p,
@@ -1175,6 +1178,17 @@ def step_time_probe(metric, p_phi, y0, y1, h, tau=1.0, precision=64):
     return out
 
 
+def time_rates_probe(metric, p_phi, y, precision=64):
+    """The rates a lane carries (lt_time_rates_probe) at n states y (n, 4) (r, theta, p_r, p_theta) -> (n, 3) float64
+    (t', r', theta') holding the values of the precision computed in."""
+    y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1, 4)
+    n = y.shape[0]
+    pp = np.ascontiguousarray(np.broadcast_to(np.asarray(p_phi, dtype=np.float64), (n,)))
+    out = np.empty((n, 3))
+    _check(load().lt_time_rates_probe(C.byref(metric), _np_ptr(pp), _np_ptr(y), n, int(precision), _np_ptr(out)))
+    return out
+
+
 EV_DISK = 5                                                              # the event of a row that hit the disk
 
 
@@ -1209,6 +1223,47 @@ def disk_advance_probe(metric, states, p_phi, integrator=INTEGRATOR_RK4, precisi
                                         _np_ptr(oa), _np_ptr(oi), _np_ptr(oh), _np_ptr(oo)))
     return dict(event=oi[:, 0].copy(), steps=oi[:, 1].copy(), is_hit=oi[:, 2] != 0, state=out, lam=oa[:, 0].copy(), h=oa[:, 1].copy(),
                 hit=oh, on_y1=oo[:, :5].copy(), on_h=oo[:, 5].copy(), on_tau=oo[:, 6].copy())
+
+
+TIMED_CARRY = ("state", "lam", "h", "steps", "k1", "sc", "t_hi", "t_lo", "rate", "have", "n")  # what a lane hands to its next iteration
+
+
+def disk_timed_advance_probe(metric, states, p_phi, integrator=INTEGRATOR_RK4, precision=64, pol=False, lam=0.0, h=0.0, refine=None,
+                             steps=None, act=True, k1=None, sc=None, t_hi=0.0, t_lo=0.0, rate=None, have=False, n=0, max_images=2,
+                             iters=1, trace=False, r_in=0.0, r_out=20.0, r_obs=50.0, lambda_max=5000.0, h_max=1.0):
+    """Up to `iters` iterations of the timed (pol: the polarized) trace's lane per state (lt_disk_timed_advance_probe); rows
+    64 b ... 64 b + 63 share a wavefront.  h: RK4's h_retry, DP45's step size; k1, sc: DP45's carried derivative and [sin, cos]
+    (None: from the state); t_hi, t_lo, rate (rows,3), have, n: the lane's carried time, rates and hit count.  A result's
+    TIMED_CARRY entries, passed back as keywords, resume the lane exactly.
+    -> dict(event, steps, iters (rows,) int32, state (rows,5), lam, h (rows,), k1 (rows,5), sc (rows,2), t_hi, t_lo (rows,), rate
+    (rows,3), have (rows,) bool, n (rows,) int32, img (max_images, rows, 2), tim (max_images, rows), mom (max_images, rows, 2),
+    trace (iters, rows, 7) or None: r, theta, p_r, p_theta, h counted, dt added, hits counted after each iteration)."""
+    st = np.ascontiguousarray(states, dtype=np.float64).reshape(-1, 5)
+    m = st.shape[0]
+    col = lambda x, dt=np.float64: np.ascontiguousarray(np.broadcast_to(np.asarray(x), (m,))).astype(dt)
+    pp = col(p_phi)
+    rf = np.zeros(m, dtype=np.uint8) if refine is None else col(refine, np.uint8)
+    ss = np.zeros(m, dtype=np.uint32) if steps is None else col(steps, np.uint32)
+    ac = col(act, np.uint8)
+    aux = np.ascontiguousarray(np.stack([col(lam), col(h)], axis=1))
+    kk = None if k1 is None else np.ascontiguousarray(k1, dtype=np.float64).reshape(m, 5)
+    sc0 = None if sc is None else np.ascontiguousarray(sc, dtype=np.float64).reshape(m, 2)
+    rt = np.zeros((m, 3)) if rate is None else np.asarray(rate, dtype=np.float64).reshape(m, 3)
+    lane = np.ascontiguousarray(np.concatenate([np.stack([col(t_hi), col(t_lo)], axis=1), rt], axis=1))
+    lane_int = np.ascontiguousarray(np.stack([col(have, np.int32), col(n, np.int32)], axis=1))
+    mi, it = int(max_images), int(iters)
+    out, oa, ok, osc = np.empty_like(st), np.empty((m, 2)), np.empty((m, 5)), np.empty((m, 2))
+    oi, ol, oli = np.empty((m, 3), dtype=np.int32), np.empty((m, 5)), np.empty((m, 2), dtype=np.int32)
+    img, tim, mom = np.empty((max(mi, 0), m, 2)), np.empty((max(mi, 0), m)), np.empty((max(mi, 0), m, 2))
+    tr = np.empty((max(it, 0), m, 7)) if trace else None
+    _check(load().lt_disk_timed_advance_probe(C.byref(metric), r_obs, lambda_max, h_max, r_in, r_out, int(integrator), int(precision),
+                                              int(bool(pol)), _np_ptr(st), _np_ptr(pp), _np_ptr(rf), _np_ptr(aux), _np_ptr(ss), _np_ptr(ac),
+                                              _np_ptr(kk), _np_ptr(sc0), _np_ptr(lane), _np_ptr(lane_int), m, mi, it, _np_ptr(out),
+                                              _np_ptr(oa), _np_ptr(ok), _np_ptr(osc), _np_ptr(oi), _np_ptr(ol), _np_ptr(oli), _np_ptr(img),
+                                              _np_ptr(tim), _np_ptr(mom), _np_ptr(tr)))
+    return dict(event=oi[:, 0].copy(), steps=oi[:, 1].copy(), iters=oi[:, 2].copy(), state=out, lam=oa[:, 0].copy(), h=oa[:, 1].copy(),
+                k1=ok, sc=osc, t_hi=ol[:, 0].copy(), t_lo=ol[:, 1].copy(), rate=ol[:, 2:].copy(), have=oli[:, 0] != 0, n=oli[:, 1].copy(),
+                img=img, tim=tim, mom=mom, trace=tr)
 
 
 def disk_shade_probe(metric, r, phi=0.0, xi=0.0, g=np.nan, r_in=0.0, q=3.0, exposure=1.0):
