@@ -313,18 +313,26 @@ template <typename T> struct KerrConsts {
     T unit_lam;       // lambda_max - 1, the range limit of that loop's unit-step form (kerr_rk4_streak); -inf: never taken
 };
 
-// A VALU instruction with an SGPR source runs on the half-rate pipe on gfx950 (v_fma_f32 with an
-// SGPR operand: 4.1 issue cycles against 2.2; tools/issue_probe.py).  The constants the right-hand
-// side multiplies with are therefore copied into VGPRs once per kernel; the empty asm makes the
-// compiler forget that they are wave-uniform.
-#ifndef LT_PIN_CONSTS
-#define LT_PIN_CONSTS 1
-#endif
-template <typename T> __device__ __forceinline__ void pin_consts(KerrConsts<T> &k)
+// A stream of nothing but VALU instructions with an SGPR source runs on the half-rate pipe on gfx950 (v_fma_f32 with
+// an SGPR operand: 4.1 issue cycles against 2.2; tools/issue_probe.py), which is why the constants the right-hand
+// side multiplies with are copied into VGPRs once per kernel; the empty asm makes the compiler forget that they are
+// wave-uniform.  Interleaved one by one among plain FMAs the same instructions issue at full rate, and the SIMD holds
+// a higher clock than on three-register FMAs alone: measured in k_kerr_direct<float, Rk4<float>> (48 v_fma_f32 and
+// 16 v_fmac_f32 of its 521-instruction loop read a, a^2 or 2M), leaving all three in SGPRs is 1.2 % faster than
+// copying them, a^2 alone 0.9 %, a 0.2 % and 2M 0.3 % (profiles/const_operands_ab.txt).
+// Which of the three a kernel copies is therefore its own choice, one bit per constant: pin_consts<PIN_A | PIN_2M>
+// leaves a^2 in its SGPR.  Every kernel pins all three (the default) unless it says otherwise where it calls this;
+// the one that does is the plain float32 RK4 frame kernel (DirectPin, lt_kernels.hpp), the one that was measured.
+enum : unsigned { PIN_NONE = 0u, PIN_A = 1u, PIN_A2 = 2u, PIN_2M = 4u, PIN_ALL = 7u };
+template <unsigned PIN = PIN_ALL, typename T> __device__ __forceinline__ void pin_consts(KerrConsts<T> &k)
 {
-#if LT_PIN_CONSTS
-    asm volatile("" : "+v"(k.a), "+v"(k.a2), "+v"(k.two_M));
-#endif
+    // (all three in ONE statement, as before the mask existed: it keeps every all-pinning kernel's code byte for byte)
+    if constexpr (PIN == PIN_ALL) asm volatile("" : "+v"(k.a), "+v"(k.a2), "+v"(k.two_M));
+    else {
+        if constexpr ((PIN & PIN_A) != 0) asm volatile("" : "+v"(k.a));
+        if constexpr ((PIN & PIN_A2) != 0) asm volatile("" : "+v"(k.a2));
+        if constexpr ((PIN & PIN_2M) != 0) asm volatile("" : "+v"(k.two_M));
+    }
 }
 
 // Per-ray constants: the conserved p_phi = L (p_t = -1 throughout, metrics.py:187), what follows

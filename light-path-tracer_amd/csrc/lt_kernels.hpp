@@ -440,7 +440,7 @@ template <typename T, typename Integ> struct PlainStep {
     __device__ __forceinline__ void stored(Lane &, int64_t) {}
 };
 
-template <typename T, typename Integ, typename Step>
+template <typename T, typename Integ, typename Step, unsigned PIN = PIN_ALL>
 __device__ __forceinline__ void direct_tiles(const KerrConsts<T> &k_in, Step step, const typename Vec4<T>::type *__restrict__ ic,
                                              typename Vec4<T>::type *__restrict__ fin0,
                                              typename Vec4<T>::type *__restrict__ fin1, int64_t n_q, uint32_t long_iters,
@@ -448,7 +448,7 @@ __device__ __forceinline__ void direct_tiles(const KerrConsts<T> &k_in, Step ste
                                              unsigned long long *__restrict__ head, int64_t tile0 = 0)
 {
     KerrConsts<T> k = k_in;
-    pin_consts(k);
+    pin_consts<PIN>(k);
     const int lane = (int)(threadIdx.x & 63u);
     int64_t tile = tile0 + (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     for (;;) {
@@ -544,6 +544,17 @@ __device__ __forceinline__ void direct_tiles(const KerrConsts<T> &k_in, Step ste
     }
 }
 
+// Which of a, a^2 and 2M k_kerr_direct<T, Integ> copies into VGPRs (pin_consts, lt_device.hpp).  The choice belongs to this
+// kernel alone: the disks' kernels, the queue schedule, the batch twins and the probes call pin_consts with its default.
+// LT_K2_F32_PIN is the mask of the plain float32 RK4 frame kernel, a macro so that tools/const_operands_ab.sh can build
+// the other subsets; DESIGN.md 4.1 and profiles/const_operands_ab.txt hold what each measured.  It copies none: same
+// operations, same bits (tests/test_gpu_const_operands.py), 92 VGPRs against 96, and 1.2 % less time per frame.
+#ifndef LT_K2_F32_PIN
+#define LT_K2_F32_PIN PIN_NONE
+#endif
+template <typename T, typename Integ> struct DirectPin { static constexpr unsigned value = PIN_ALL; };
+template <> struct DirectPin<float, Rk4<float>> { static constexpr unsigned value = (LT_K2_F32_PIN); };
+
 template <typename T, typename Integ>
 __global__ void __launch_bounds__(256, Integ::MIN_WAVES_PER_SIMD) k_kerr_direct(KerrConsts<T> k_in, const typename Vec4<T>::type *__restrict__ ic,
                                                          typename Vec4<T>::type *__restrict__ fin0,
@@ -552,7 +563,8 @@ __global__ void __launch_bounds__(256, Integ::MIN_WAVES_PER_SIMD) k_kerr_direct(
                                                          uint64_t *__restrict__ kstats, unsigned long long *__restrict__ head,
                                                          int64_t tile0)
 {
-    direct_tiles<T, Integ>(k_in, PlainStep<T, Integ>{}, ic, fin0, fin1, n_q, long_iters, stamps, kstats, head, tile0);
+    direct_tiles<T, Integ, PlainStep<T, Integ>, DirectPin<T, Integ>::value>(k_in, PlainStep<T, Integ>{}, ic, fin0, fin1, n_q, long_iters, stamps,
+                                                                          kstats, head, tile0);
 }
 
 // Queue schedule: persistent wavefronts.  The grid is sized to fill the chip once (blocks = CUs x
