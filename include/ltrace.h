@@ -900,8 +900,8 @@ int lt_shade_stokes_aa(const float *hits, const uint8_t *n_hits, const float *po
  * that is not LT_METRIC_KERR: LT_ERR_UNSUPPORTED; then LT_ERR_INVALID_ARG for a bad metric, an empty frame, max_images,  *
  * the map's fields in the struct's order, the disk's q / exposure, channels, and t_obs or t_start / dt / n_times.       *
  *                                                                                                               *
- * Out of scope: polarized maps, a map plus a spot in one call, tables that change with time, lt_render_multi and the  *
- * multi-process path, adaptive sampling of sequences.                                                             */
+ * Out of scope: polarized maps, a map plus a spot in one call, lt_render_multi and the multi-process path, adaptive   *
+ * sampling of sequences.  Tables that change with time are "a disk movie" below.                                   */
 #define LT_MAP_KEPLERIAN 0
 #define LT_MAP_RIGID 1
 
@@ -1105,6 +1105,111 @@ int lt_diskmap_visibility(const float *hits, const uint8_t *n_hits, int32_t R, i
                           const lt_metric *metric, const lt_disk *disk, const lt_diskmap *map, const float *texels,
                           const double *uv, int32_t n_baselines, int32_t split_orders, double t_start, double dt,
                           int32_t n_times, double *out);
+
+/* ---- a disk movie: emissivity tables that change with time, shaded from stored hits --------------------------- *
+ * A map ("a rotating emissivity map") is one snapshot that can only turn.  A movie is a sequence of snapshots at      *
+ * evenly spaced coordinate times -- a flare that brightens and fades, a clump that forms and shears apart, the        *
+ * frames of a simulation -- looked up at each stored slot's own emission time t_obs - dt, so every image order sees   *
+ * the movie at its own moment and the photon ring shows a flare again, later.  All five products of the stored hits:  *
+ * the frame, the supersampled frame, the light curve, the dynamic spectrum and the visibilities.  Nothing is traced    *
+ * again.                                                                                                         *
+ *                                                                                                               *
+ * The movie.  texels (n_frames, n_r, n_phi) float32, frame-major with phi contiguous, plus lt_diskmap, whose fields    *
+ * keep their meaning for every frame, plus lt_diskmovie.  Frame q is the emissivity at coordinate time                *
+ * T_q = t0 + q dt_frame.  Texels must be finite and are not checked.                                               *
+ *                                                                                                               *
+ * Rule.  Per stored slot, in float64 from the float32 record (r, phi, g, dt), in this order:                         *
+ *   1. t_em = t_obs - dt;  s = (t_em - t0) / dt_frame;                                                             *
+ *   2. LT_MOVIE_HOLD:  q0 = clamp(floor(s), 0, n_frames - 1),  q1 = min(q0 + 1, n_frames - 1),                       *
+ *      f_t = clamp(s - q0, 0, 1);  the table indices are k0 = q0, k1 = q1.  Where q1 == q0 -- at or after the last   *
+ *      frame, n_frames = 1 -- ONE look-up is made and m = m_q0 exactly; before frame 0 f_t = 0 and m = m_0 exactly    *
+ *      as well (finite texels).  A NaN s gives q0 = 0, f_t = 0;                                                     *
+ *   3. LT_MOVIE_LOOP:  q0 = floor(s),  q1 = q0 + 1,  f_t = s - q0;  k = q - n_frames floor(q / n_frames), clamped     *
+ *      into [0, n_frames - 1]: the last frame blends into frame 0.  Always two look-ups.  A NaN s takes frame 0 with   *
+ *      f_t = 0.  Every index is clamped before it is used, whatever the record holds;                               *
+ *   4. each frame of the pair is unwound from its OWN epoch by the map's rotation:  T_q = t0 + q dt_frame,            *
+ *      psi_q = wrap_2pi(phi - Omega (t_em - T_q)), Omega as in the map's step 1 (the hit's own r for LT_MAP_KEPLERIAN,  *
+ *      omega_p for LT_MAP_RIGID);  m_q = the map's steps 3 to 5 (bilinear in r and psi, periodic seam, 0 outside       *
+ *      [r_min, r_max]) on frame k_q at psi_q.  So between two snapshots the pattern is carried along by the disk's     *
+ *      rotation instead of cross-fading in place; inside the movie the phase Omega (t_em - T_q) is at most            *
+ *      Omega dt_frame, however large t_obs is; outside a held movie the end frame keeps turning as a rotating map      *
+ *      would.  LT_MAP_RIGID with omega_p = 0 is plain interpolation of lab-frame snapshots;                         *
+ *   5. m = (1 - f_t) m_q0 + f_t m_q1;  E = exposure g^4 m ramp(g);  the frame's composition, with_disk, base,        *
+ *      channels and the clamp are exactly the map's step 6.                                                        *
+ * The rule is continuous in t_em across every floor and clamp: at a whole s the pair (q0 - 1, q0) at f_t -> 1 and the  *
+ * pair (q0, q0 + 1) at f_t = 0 both give m_q0 at psi = phi; before frame 0 of a held movie f_t = 0 and past its last    *
+ * frame the single look-up is the limit of f_t -> 1; a loop's index wraps where the pair's weights do not change.  A    *
+ * rounding of s therefore moves m by the rounding times the slope, never by a jump.  One held frame with t0 = 0 is the  *
+ * map, bit for bit.  disk.DiskMovie / disk.sample_movie / disk.movie_emission / disk.shade_diskmovie /               *
+ * disk.diskmovie_lightcurve / disk.diskmovie_spectrum / disk.diskmovie_visibility (Python) state the rule in numpy.    *
+ *                                                                                                               *
+ * Products.  Each is the map's with the movie as the emitter: lt_shade_diskmovie the frame, lt_shade_diskmovie_aa     *
+ * the supersampled frame (bit for bit aa.resolve of the fine frame; samples = 1 is lt_shade_diskmovie),              *
+ * lt_diskmovie_lightcurve the light curve (n_times, 3), lt_diskmovie_spectrum the dynamic spectrum                  *
+ * ("energy-resolved light": the weight is exposure g^4 m) and lt_diskmovie_visibility the visibilities              *
+ * ("visibilities", the same weight).  Outputs, limits, batches, the fixed order of every sum and the guarantees are   *
+ * the map's; no floating-point atomics are used.                                                                  *
+ *                                                                                                               *
+ * Refusals, in the map's order.  No GPU: LT_ERR_NO_DEVICE (the _aa forms then refuse samples); null hits / metric /    *
+ * disk / map / movie / texels: LT_ERR_INVALID_ARG; a metric that is not LT_METRIC_KERR: LT_ERR_UNSUPPORTED; then        *
+ * LT_ERR_INVALID_ARG for a bad metric, an empty frame, max_images, the map's fields in the struct's order, the         *
+ * movie's fields in the struct's order (t0, dt_frame, n_frames with the size limit, boundary), the disk's            *
+ * q / exposure, and then what the map's entry point of the same product refuses behind them.  The size limit is        *
+ * refused before the table is read.  A refused call writes nothing.                                               *
+ *                                                                                                               *
+ * Out of scope: non-uniform frame times, polarized movies, a movie plus a spot in one call, lt_render_multi and the    *
+ * multi-process path, adaptive sampling of sequences, streaming a movie larger than the limit.                     */
+#define LT_MOVIE_HOLD 0
+#define LT_MOVIE_LOOP 1
+
+typedef struct lt_diskmovie {
+    double t0;        /* coordinate time of frame 0, finite */
+    double dt_frame;  /* spacing of the frames, finite, > 0 */
+    int32_t n_frames; /* >= 1; n_frames n_r n_phi <= 2^28 (and n_r n_phi <= 2^26 as before) */
+    int32_t boundary; /* LT_MOVIE_HOLD: the end frames are held; LT_MOVIE_LOOP: the last frame blends into frame 0 */
+} lt_diskmovie;
+void lt_default_diskmovie(lt_diskmovie *mv); /* t0 0, dt_frame 1, 1 frame, hold */
+
+/* Pointers as the map's: the _dev forms take DEVICE pointers (d_texels too) and enqueue on the default stream, the
+ * others HOST pointers; uv is a HOST pointer in both.  texels: (n_frames, n_r, n_phi) float32. */
+int lt_shade_diskmovie_dev(const float *d_hits, const uint8_t *d_n_hits, int32_t R, int32_t W, int32_t max_images,
+                           const lt_metric *metric, const lt_disk *disk, const lt_diskmap *map, const lt_diskmovie *movie,
+                           const float *d_texels, double t_obs, const float *d_base, int32_t channels, float *d_rgb,
+                           uint8_t *d_rgba);
+int lt_shade_diskmovie(const float *hits, const uint8_t *n_hits, int32_t R, int32_t W, int32_t max_images,
+                       const lt_metric *metric, const lt_disk *disk, const lt_diskmap *map, const lt_diskmovie *movie,
+                       const float *texels, double t_obs, const float *base, int32_t channels, float *out_rgb,
+                       uint8_t *out_rgba);
+int lt_shade_diskmovie_aa_dev(const float *d_hits, const uint8_t *d_n_hits, int32_t R, int32_t W, int32_t samples,
+                              int32_t max_images, const lt_metric *metric, const lt_disk *disk, const lt_diskmap *map,
+                              const lt_diskmovie *movie, const float *d_texels, double t_obs,
+                              const float *d_base /* (R S, W S, channels) or NULL */, int32_t channels,
+                              float *d_rgb /* (R, W, channels) */, uint8_t *d_rgba /* (R, W, 4) */);
+int lt_shade_diskmovie_aa(const float *hits, const uint8_t *n_hits, int32_t R, int32_t W, int32_t samples,
+                          int32_t max_images, const lt_metric *metric, const lt_disk *disk, const lt_diskmap *map,
+                          const lt_diskmovie *movie, const float *texels, double t_obs, const float *base, int32_t channels,
+                          float *out_rgb, uint8_t *out_rgba);
+int lt_diskmovie_lightcurve_dev(const float *d_hits, const uint8_t *d_n_hits, int32_t R, int32_t W, int32_t max_images,
+                                const lt_metric *metric, const lt_disk *disk, const lt_diskmap *map, const lt_diskmovie *movie,
+                                const float *d_texels, double t_start, double dt, int32_t n_times, double *d_out);
+int lt_diskmovie_lightcurve(const float *hits, const uint8_t *n_hits, int32_t R, int32_t W, int32_t max_images,
+                            const lt_metric *metric, const lt_disk *disk, const lt_diskmap *map, const lt_diskmovie *movie,
+                            const float *texels, double t_start, double dt, int32_t n_times, double *out);
+int lt_diskmovie_spectrum_dev(const float *d_hits, const uint8_t *d_n_hits, int32_t R, int32_t W, int32_t max_images,
+                              const lt_metric *metric, const lt_disk *disk, const lt_diskmap *map, const lt_diskmovie *movie,
+                              const float *d_texels, const lt_spectrum *spec, double t_start, double dt, int32_t n_times,
+                              double *d_out);
+int lt_diskmovie_spectrum(const float *hits, const uint8_t *n_hits, int32_t R, int32_t W, int32_t max_images,
+                          const lt_metric *metric, const lt_disk *disk, const lt_diskmap *map, const lt_diskmovie *movie,
+                          const float *texels, const lt_spectrum *spec, double t_start, double dt, int32_t n_times, double *out);
+int lt_diskmovie_visibility_dev(const float *d_hits, const uint8_t *d_n_hits, int32_t R, int32_t W, int32_t max_images,
+                                const lt_metric *metric, const lt_disk *disk, const lt_diskmap *map, const lt_diskmovie *movie,
+                                const float *d_texels, const double *uv, int32_t n_baselines, int32_t split_orders,
+                                double t_start, double dt, int32_t n_times, double *d_out);
+int lt_diskmovie_visibility(const float *hits, const uint8_t *n_hits, int32_t R, int32_t W, int32_t max_images,
+                            const lt_metric *metric, const lt_disk *disk, const lt_diskmap *map, const lt_diskmovie *movie,
+                            const float *texels, const double *uv, int32_t n_baselines, int32_t split_orders, double t_start,
+                            double dt, int32_t n_times, double *out);
 
 /* ---- polarized visibilities: Stokes I, Q, U of the stored hits on every baseline ------------------------------ *
  * What polarimetric interferometry measures: the Fourier transforms Q~(u, v) and U~(u, v) of the linearly polarized  *

@@ -17,6 +17,7 @@
 #include "lt_spectrum.hpp"
 #include "lt_visibility.hpp"
 #include "lt_visibility_stokes.hpp"
+#include "lt_diskmovie.hpp"
 #ifdef LT_PROBES
 #include "lt_probe.hpp"
 #endif
@@ -2300,3 +2301,4 @@ extern "C" int lt_scatter_rows_indexed_dev(const void *d_rows, void *d_full, con
 #include "lt_api_spectrum.inc"
 #include "lt_api_visibility.inc"
 #include "lt_api_visibility_stokes.inc"
+#include "lt_api_diskmovie.inc"

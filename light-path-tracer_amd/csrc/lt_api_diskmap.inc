@@ -16,24 +16,30 @@ extern "C" void lt_default_diskmap(lt_diskmap *m)
     m->with_disk = 1;
 }
 
+// The refusals of the map's fields, in the struct's order, and its shading constants; the movie's resolve
+// (lt_api_diskmovie.inc) goes through them too.
+static int resolve_diskmap_fields(const lt_metric *metric, const lt_diskmap *map, DiskMapShade *dm)
+{
+    if (!(map->r_min > 0.0) || !(map->r_max > map->r_min) || !std::isfinite(map->r_max))
+        return fail(LT_ERR_INVALID_ARG, "disk map needs 0 < r_min < r_max, both finite");
+    if (map->rotation != LT_MAP_KEPLERIAN && !std::isfinite(map->omega_p)) return fail(LT_ERR_INVALID_ARG, "disk map omega_p must be finite");
+    if (!(map->exposure >= 0.0) || !std::isfinite(map->exposure)) return fail(LT_ERR_INVALID_ARG, "disk map exposure must be finite, >= 0");
+    if (map->n_r < 1 || map->n_phi < 1 || (int64_t)map->n_r * map->n_phi > ((int64_t)1 << 26))
+        return fail(LT_ERR_INVALID_ARG, "disk map of %d x %d texels: n_r, n_phi >= 1 and n_r n_phi <= 2^26", (int)map->n_r, (int)map->n_phi);
+    if (map->rotation != LT_MAP_KEPLERIAN && map->rotation != LT_MAP_RIGID)
+        return fail(LT_ERR_INVALID_ARG, "disk map rotation %d is neither LT_MAP_KEPLERIAN nor LT_MAP_RIGID", (int)map->rotation);
+    const double sM = sqrt(metric->M);
+    *dm = DiskMapShade{map->r_min, map->r_max, map->omega_p, sM, metric->a * sM, (double)map->n_phi / 6.283185307179586, map->exposure,
+                       map->n_r, map->n_phi, map->rotation == LT_MAP_RIGID, map->with_disk != 0};
+    return LT_OK;
+}
+
 // Refusals, the disk's shading constants and the map's.
 static int resolve_diskmap(const void *hits, int32_t R, int32_t W, int32_t max_images, const lt_metric *metric, const lt_disk *disk,
                            const lt_diskmap *map, const float *texels, DiskShade *ds, DiskMapShade *dm)
 {
-    return resolve_reshade("disk map", "map / texels", hits && map && texels, R, W, max_images, metric, disk, ds, [&]() {
-        if (!(map->r_min > 0.0) || !(map->r_max > map->r_min) || !std::isfinite(map->r_max))
-            return fail(LT_ERR_INVALID_ARG, "disk map needs 0 < r_min < r_max, both finite");
-        if (map->rotation != LT_MAP_KEPLERIAN && !std::isfinite(map->omega_p)) return fail(LT_ERR_INVALID_ARG, "disk map omega_p must be finite");
-        if (!(map->exposure >= 0.0) || !std::isfinite(map->exposure)) return fail(LT_ERR_INVALID_ARG, "disk map exposure must be finite, >= 0");
-        if (map->n_r < 1 || map->n_phi < 1 || (int64_t)map->n_r * map->n_phi > ((int64_t)1 << 26))
-            return fail(LT_ERR_INVALID_ARG, "disk map of %d x %d texels: n_r, n_phi >= 1 and n_r n_phi <= 2^26", (int)map->n_r, (int)map->n_phi);
-        if (map->rotation != LT_MAP_KEPLERIAN && map->rotation != LT_MAP_RIGID)
-            return fail(LT_ERR_INVALID_ARG, "disk map rotation %d is neither LT_MAP_KEPLERIAN nor LT_MAP_RIGID", (int)map->rotation);
-        const double sM = sqrt(metric->M);
-        *dm = DiskMapShade{map->r_min, map->r_max, map->omega_p, sM, metric->a * sM, (double)map->n_phi / 6.283185307179586, map->exposure,
-                           map->n_r, map->n_phi, map->rotation == LT_MAP_RIGID, map->with_disk != 0};
-        return LT_OK;
-    });
+    return resolve_reshade("disk map", "map / texels", hits && map && texels, R, W, max_images, metric, disk, ds,
+                           [&]() { return resolve_diskmap_fields(metric, map, dm); });
 }
 
 extern "C" int lt_shade_diskmap_dev(const float *d_hits, const uint8_t *d_n_hits, int32_t R, int32_t W, int32_t max_images,

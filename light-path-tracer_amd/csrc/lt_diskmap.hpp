@@ -24,32 +24,44 @@ struct DiskMapShade {
     int rigid, with_disk;
 };
 
+// The table's bilinear value at radius r in [r_min, r_max] and unwound azimuth psi (the header's steps 3 to 5), stated once
+// for the map and for the frames of a movie (lt_diskmovie.hpp): constant extrapolation over the outer half texels in r,
+// periodic in psi.  Every index is clamped before it is used, whatever r and psi hold.
+__device__ __forceinline__ double diskmap_bilinear(const DiskMapShade &dm, const float *__restrict__ texels, double r, double psi)
+{
+    const int top = dm.n_r - 1;
+    const double v = fmin(fmax((r - dm.r_min) / (dm.r_max - dm.r_min) * (double)dm.n_r - 0.5, 0.0), (double)top);
+    const int i0 = min((int)floor(v), top), i1 = min(i0 + 1, top);
+    const double f_r = v - (double)i0;
+    const double u = psi * dm.phi_scale - 0.5;
+    const double fl = floor(u);
+    int k0 = (int)fmin(fmax(fl, -1.0), (double)dm.n_phi); // psi in [0, 2 pi): floor(u) in [-1, n_phi]; a NaN gives -1
+    if (k0 < 0) k0 += dm.n_phi;
+    if (k0 >= dm.n_phi) k0 -= dm.n_phi;
+    const int k1 = k0 + 1 < dm.n_phi ? k0 + 1 : 0;
+    const double f_p = u - fl;
+    const float *row0 = texels + (int64_t)i0 * dm.n_phi, *row1 = texels + (int64_t)i1 * dm.n_phi;
+    const double t00 = (double)row0[k0], t01 = (double)row0[k1], t10 = (double)row1[k0], t11 = (double)row1[k1];
+    return (1.0 - f_r) * ((1.0 - f_p) * t00 + f_p * t01) + f_r * ((1.0 - f_p) * t10 + f_p * t11);
+}
+
+// The disk's rate at a hit: the hit's own Keplerian Omega(r), or the pattern speed (the header's step 1).
+__device__ __forceinline__ double diskmap_omega(const DiskMapShade &dm, double r)
+{
+    return dm.rigid ? dm.omega_p : dm.sM / (r * sqrt(r) + dm.a_sM);
+}
+
 // Light of the map seen through one stored hit, unclamped: E = exposure g^4 m ramp(g), m the table's bilinear value at
-// the hit's radius and at its azimuth unwound to t = 0, psi = wrap_2pi(phi - Omega (t_obs - dt)); constant extrapolation
-// over the outer half texels in r, periodic in psi; m = 0 outside [r_min, r_max] and for a NaN r (the comparisons are
-// false).  Every index is clamped before it is used, whatever the record holds.
+// the hit's radius and at its azimuth unwound to t = 0, psi = wrap_2pi(phi - Omega (t_obs - dt)); m = 0 outside
+// [r_min, r_max] and for a NaN r (the comparisons are false).
 __device__ __forceinline__ double diskmap_intensity(const DiskMapShade &dm, const float *__restrict__ texels, double t_obs, const float *rec)
 {
     const double r = (double)rec[0], ph = (double)rec[1], g = (double)rec[2], dt = (double)rec[3];
     double m = 0.0;
     if (r >= dm.r_min && r <= dm.r_max) {
         const double t_em = t_obs - dt;
-        const double om = dm.rigid ? dm.omega_p : dm.sM / (r * sqrt(r) + dm.a_sM);
-        const double psi = wrap_2pi(ph - om * t_em);
-        const int top = dm.n_r - 1;
-        const double v = fmin(fmax((r - dm.r_min) / (dm.r_max - dm.r_min) * (double)dm.n_r - 0.5, 0.0), (double)top);
-        const int i0 = min((int)floor(v), top), i1 = min(i0 + 1, top);
-        const double f_r = v - (double)i0;
-        const double u = psi * dm.phi_scale - 0.5;
-        const double fl = floor(u);
-        int k0 = (int)fmin(fmax(fl, -1.0), (double)dm.n_phi); // psi in [0, 2 pi): floor(u) in [-1, n_phi]; a NaN gives -1
-        if (k0 < 0) k0 += dm.n_phi;
-        if (k0 >= dm.n_phi) k0 -= dm.n_phi;
-        const int k1 = k0 + 1 < dm.n_phi ? k0 + 1 : 0;
-        const double f_p = u - fl;
-        const float *row0 = texels + (int64_t)i0 * dm.n_phi, *row1 = texels + (int64_t)i1 * dm.n_phi;
-        const double t00 = (double)row0[k0], t01 = (double)row0[k1], t10 = (double)row1[k0], t11 = (double)row1[k1];
-        m = (1.0 - f_r) * ((1.0 - f_p) * t00 + f_p * t01) + f_r * ((1.0 - f_p) * t10 + f_p * t11);
+        const double om = diskmap_omega(dm, r);
+        m = diskmap_bilinear(dm, texels, r, wrap_2pi(ph - om * t_em));
     }
     const double g2 = g * g;
     return dm.exposure * (g2 * g2) * m;

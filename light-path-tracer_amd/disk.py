@@ -15,7 +15,9 @@ of the first max_images of them to the pixel: rgb = clamp(base + sum_j I_j ramp(
 lt_trace_disk_hits stores the light-travel time of every hit as well (step_time restates the rule it integrates with), so
 that a moving source -- HotSpot, a bright spot on a circular orbit -- can be re-shaded at any observer time from one
 trace (shade_hotspot) and reduced to a light curve (lightcurve).  DiskMap is the general moving source: an emissivity
-table on the disk that turns with it (shade_diskmap, diskmap_lightcurve; spiral_map and spots_map make tables).
+table on the disk that turns with it (shade_diskmap, diskmap_lightcurve; spiral_map and spots_map make tables), and
+DiskMovie a sequence of such tables that change with time (shade_diskmovie, diskmovie_lightcurve, diskmovie_spectrum,
+diskmovie_visibility; flare_movie makes one).
 
 The same records binned by g give the energy-resolved light: Spectrum is the grid, spectrum_bin the bin rule, and
 disk_spectrum / hotspot_spectrum / diskmap_spectrum the broadened line and the dynamic spectra (lt_*_spectrum).
@@ -327,10 +329,10 @@ def map_emission(M, a, hits, dmap, t_obs):
     return np.stack([inten * np.clip(2.0 * g - 0.5 * i, 0.0, 1.0) for i in range(3)], axis=-1)
 
 
-def shade_diskmap(M, a, hits, n_hits, disk, dmap, t_obs, base=None, channels=3):
-    """lt_shade_diskmap restated: float32 (..., 3), or (...) for channels = 1.  shade_hotspot with the map's light in the
-    spot's place: rgb = clamp(base + sum_j (with_disk E_j^disk + E_j^map), 0, 1) in float64, base first, then the slots
-    in order, disk before map; a pixel without a stored hit keeps base."""
+def _shade_table(M, a, hits, n_hits, disk, with_disk, es, base, channels):
+    """The frame of a table's light es (..., max_images, 3) (map_emission, movie_emission): rgb = clamp(base + sum_j
+    (with_disk E_j^disk + es_j), 0, 1) in float64, base first, then the slots in order, disk before table; a pixel
+    without a stored hit keeps base."""
     hits = np.asarray(hits)
     m = hits.shape[-2]
     ns = _stored(hits, n_hits)
@@ -338,11 +340,10 @@ def shade_diskmap(M, a, hits, n_hits, disk, dmap, t_obs, base=None, channels=3):
     shape = hits.shape[:-2] if channels == 1 else hits.shape[:-2] + (3,)
     base = np.zeros(shape, dtype=np.float32) if base is None else np.asarray(base, dtype=np.float32)
     acc = base.astype(np.float64)
-    es = map_emission(M, a, hits, dmap, t_obs)
     for j in range(m):
         on = ns > j
         terms = []
-        if dmap.with_disk:
+        if with_disk:
             r = np.where(on, hits[..., j, 0].astype(np.float64), 1.0)
             g = np.where(on, hits[..., j, 2].astype(np.float64), 0.0)
             x = r_in / r
@@ -357,6 +358,13 @@ def shade_diskmap(M, a, hits, n_hits, disk, dmap, t_obs, base=None, channels=3):
                 acc = np.where(on[..., None], acc + e, acc)
     lit = ns > 0 if channels == 1 else (ns > 0)[..., None]
     return np.where(lit, np.clip(acc, 0.0, 1.0).astype(np.float32), base)
+
+
+def shade_diskmap(M, a, hits, n_hits, disk, dmap, t_obs, base=None, channels=3):
+    """lt_shade_diskmap restated: float32 (..., 3), or (...) for channels = 1.  shade_hotspot with the map's light in the
+    spot's place: rgb = clamp(base + sum_j (with_disk E_j^disk + E_j^map), 0, 1) in float64, base first, then the slots
+    in order, disk before map; a pixel without a stored hit keeps base."""
+    return _shade_table(M, a, hits, n_hits, disk, dmap.with_disk, map_emission(M, a, hits, dmap, t_obs), base, channels)
 
 
 def shade_diskmap_aa(M, a, hits, n_hits, disk, dmap, t_obs, samples, base=None, channels=3):
@@ -636,6 +644,166 @@ def hotspot_visibility(M, a, hits, n_hits, spot, uv, split_orders, times):
 def diskmap_visibility(M, a, hits, n_hits, dmap, uv, split_orders, times):
     """lt_diskmap_visibility restated: (len(times), planes, n_baselines) complex128."""
     return np.stack([_visibility(hits, n_hits, uv, split_orders, map_intensity(M, a, hits, dmap, float(t))) for t in times])
+
+
+# ---- a disk movie: tables that change with time (lt_shade_diskmovie, lt_shade_diskmovie_aa, lt_diskmovie_*) ---------------
+@dataclass
+class DiskMovie:
+    """Emissivity tables on the disk at evenly spaced coordinate times (include/ltrace.h, "a disk movie"): texels
+    (n_frames, n_r, n_phi), frame q at t0 + q dt_frame, every frame laid out and looked up as a DiskMap's table.  Between
+    two frames each is unwound from its own epoch by the rotation ("kepler" / "rigid" with omega_p, as DiskMap) and the two
+    are blended linearly in time.  boundary "hold": the first and the last frame are held (and keep turning); "loop": the
+    last frame blends into frame 0.  with_disk: add the stationary disk's light."""
+    texels: np.ndarray
+    t0: float = 0.0
+    dt_frame: float = 1.0
+    boundary: str = "hold"
+    r_min: float = 6.0
+    r_max: float = 20.0
+    rotation: str = "kepler"
+    omega_p: float = 0.0
+    exposure: float = 1.0
+    with_disk: bool = True
+
+    def __post_init__(self):
+        self.texels = np.ascontiguousarray(self.texels, dtype=np.float32)
+        if self.texels.ndim != 3 or self.texels.size == 0:
+            raise ValueError("texels must be (n_frames, n_r, n_phi)")
+        if self.rotation not in ("kepler", "rigid"):
+            raise ValueError('rotation must be "kepler" or "rigid"')
+        if self.boundary not in ("hold", "loop"):
+            raise ValueError('boundary must be "hold" or "loop"')
+        if not (np.isfinite(self.t0) and np.isfinite(self.dt_frame) and self.dt_frame > 0.0):
+            raise ValueError("t0 and dt_frame must be finite, dt_frame > 0")
+
+    @property
+    def n_frames(self):
+        return self.texels.shape[0]
+
+    def frame(self, k):
+        """Frame k as a DiskMap (the same annulus, rotation and brightness)."""
+        return DiskMap(self.texels[k], r_min=self.r_min, r_max=self.r_max, rotation=self.rotation, omega_p=self.omega_p,
+                       exposure=self.exposure, with_disk=self.with_disk)
+
+    def to_lt(self):
+        """(lt_diskmap, lt_diskmovie) of this movie (ltrace.DiskMap, ltrace.DiskMovie); the tables are .texels."""
+        import ltrace
+        return self.frame(0).to_lt(), ltrace.default_diskmovie(t0=float(self.t0), dt_frame=float(self.dt_frame), n_frames=self.n_frames,
+                                                               boundary=self.boundary)
+
+
+def movie_pair(movie, t_em):
+    """The header's steps 1 to 3: (q0, q1, f_t, k0, k1) of every emission time -- the frame pair as float64 epochs'
+    indices, the blend weight, and the table indices (int64, clamped into the movie)."""
+    t_em = np.asarray(t_em, dtype=np.float64)
+    n = movie.n_frames
+    with np.errstate(invalid="ignore"):
+        s = (t_em - movie.t0) / movie.dt_frame
+        nan = np.isnan(s)
+        fl = np.floor(np.where(nan, 0.0, s))
+        if movie.boundary == "hold":
+            q0 = np.clip(fl, 0.0, float(n - 1))
+            q1 = np.minimum(q0 + 1.0, float(n - 1))
+            f_t = np.where(nan, 0.0, np.clip(s - q0, 0.0, 1.0))
+            k0, k1 = q0, q1
+        else:
+            q0, q1 = fl, fl + 1.0
+            f_t = np.where(nan, 0.0, s - q0)
+            k0, k1 = (np.nan_to_num(np.clip(q - n * np.floor(q / n), 0.0, float(n - 1)), nan=0.0) for q in (q0, q1))
+    return q0, q1, f_t, k0.astype(np.int64), k1.astype(np.int64)
+
+
+def sample_movie(movie, r, phi, om, t_em):
+    """The movie's value m at radius r and azimuth phi of material turning at rate om, at emission time t_em, float64
+    (the header's steps 1 to 5 up to the blend): each frame of the pair looked up by sample_map at the azimuth unwound to
+    its own epoch."""
+    r, phi, om, t_em = np.broadcast_arrays(*(np.asarray(x, dtype=np.float64) for x in (r, phi, om, t_em)))
+    q0, q1, f_t, k0, k1 = movie_pair(movie, t_em)
+
+    def look(q, k):
+        with np.errstate(invalid="ignore"):
+            psi = wrap_2pi(phi - om * (t_em - (movie.t0 + q * movie.dt_frame)))
+        out = np.zeros(r.shape)
+        for f in np.unique(k):
+            out = np.where(k == f, sample_map(movie.frame(int(f)), r, psi), out)
+        return out
+
+    m0, m1 = look(q0, k0), look(q1, k1)
+    with np.errstate(invalid="ignore"):
+        blend = (1.0 - f_t) * m0 + f_t * m1
+    return np.where(q1 == q0, m0, blend) if movie.boundary == "hold" else blend
+
+
+def movie_intensity(M, a, hits, movie, t_obs):
+    """exposure g^4 m of every slot, (..., max_images) float64: movie_emission without the ramp."""
+    h = np.asarray(hits).astype(np.float64)
+    r, ph, g, dt = h[..., 0], h[..., 1], h[..., 2], h[..., 3]
+    with np.errstate(invalid="ignore"):
+        om = np.full(r.shape, movie.omega_p) if movie.rotation == "rigid" else omega(M, a, r)
+        m = sample_movie(movie, r, ph, om, t_obs - dt)
+    return movie.exposure * (g * g) ** 2 * m
+
+
+def movie_emission(M, a, hits, movie, t_obs):
+    """E (..., max_images, 3) float64 of every slot of `hits`, unclamped: exposure g^4 m ramp(g), m the movie at the slot's
+    own emission time t_obs - dt."""
+    g = np.asarray(hits).astype(np.float64)[..., 2]
+    inten = movie_intensity(M, a, hits, movie, t_obs)
+    return np.stack([inten * np.clip(2.0 * g - 0.5 * i, 0.0, 1.0) for i in range(3)], axis=-1)
+
+
+def shade_diskmovie(M, a, hits, n_hits, disk, movie, t_obs, base=None, channels=3):
+    """lt_shade_diskmovie restated: shade_diskmap with the movie's light in the map's place."""
+    return _shade_table(M, a, hits, n_hits, disk, movie.with_disk, movie_emission(M, a, hits, movie, t_obs), base, channels)
+
+
+def shade_diskmovie_aa(M, a, hits, n_hits, disk, movie, t_obs, samples, base=None, channels=3):
+    """lt_shade_diskmovie_aa restated: shade_diskmovie of the FINE records, resolved by the rule of aa.resolve."""
+    import aa
+    return aa.resolve(shade_diskmovie(M, a, hits, n_hits, disk, movie, t_obs, base=base, channels=channels), samples)
+
+
+def diskmovie_lightcurve(M, a, hits, n_hits, movie, times):
+    """lt_diskmovie_lightcurve restated: (len(times), 3) float64, per time the sums of e, e ix, e iy over the pixels of
+    hits (R, W, max_images, 4) and their stored slots, e the mean of the movie's three channels."""
+    hits = np.asarray(hits)
+    R, W, m = hits.shape[:3]
+    on = _stored(hits, n_hits)[..., None] > np.arange(m)
+    iy, ix = np.mgrid[0:R, 0:W].astype(np.float64)
+    out = np.empty((len(times), 3))
+    for i, t in enumerate(times):
+        es = movie_emission(M, a, hits, movie, float(t))
+        e = np.where(on, (es[..., 0] + es[..., 1] + es[..., 2]) / 3.0, 0.0).sum(axis=-1)
+        out[i] = e.sum(), (e * ix).sum(), (e * iy).sum()
+    return out
+
+
+def diskmovie_spectrum(M, a, hits, n_hits, movie, spec, times):
+    """lt_diskmovie_spectrum restated: the movie's dynamic spectrum, (len(times), planes, n_bins + 2) float64."""
+    return np.stack([_bin_weights(hits, n_hits, spec, movie_intensity(M, a, hits, movie, float(t))) for t in times])
+
+
+def diskmovie_visibility(M, a, hits, n_hits, movie, uv, split_orders, times):
+    """lt_diskmovie_visibility restated: (len(times), planes, n_baselines) complex128."""
+    return np.stack([_visibility(hits, n_hits, uv, split_orders, movie_intensity(M, a, hits, movie, float(t))) for t in times])
+
+
+def flare_movie(n_frames, n_r, n_phi, r_min, r_max, r_s, phi_s, sigma, t_peak, t_width, dt_frame, t0=0.0, floor=0.1, amplitude=1.0,
+                rotation="kepler", omega_p=0.0, M=1.0, a=0.0, **kw):
+    """A DiskMovie of a flare, something a turning table cannot show: on a quiescent floor a Gaussian clump of width
+    sigma whose amplitude rises and falls as a Gaussian in time, amplitude exp(-(T - t_peak)^2 / 2 t_width^2).  The clump is
+    stated in the co-rotating sense: the material of radius r that carries it stands at azimuth phi_s + Omega (T - t_peak)
+    in the frame of epoch T -- Omega the disk's own rate at r ("kepler": round at (r_s, phi_s) at t_peak, sheared before
+    and after) or omega_p ("rigid") -- so the advected interpolation between two frames carries it instead of
+    cross-fading two copies.  Frame q is at T = t0 + q dt_frame; further keywords (boundary, exposure, with_disk) go to
+    DiskMovie."""
+    r, ph = _texel_centres(n_r, n_phi, r_min, r_max)
+    om = np.full(r.shape, float(omega_p)) if rotation == "rigid" else omega(M, a, r)
+    T = float(t0) + float(dt_frame) * np.arange(int(n_frames))[:, None, None]
+    d2 = r * r + r_s * r_s - 2.0 * r * r_s * np.cos(ph - (phi_s + om * (T - t_peak)))
+    texels = floor + amplitude * np.exp(-(T - t_peak) ** 2 / (2.0 * t_width * t_width)) * np.exp(-d2 / (2.0 * sigma * sigma))
+    return DiskMovie(texels.astype(np.float32), t0=float(t0), dt_frame=float(dt_frame), r_min=float(r_min), r_max=float(r_max),
+                     rotation=rotation, omega_p=float(omega_p), **kw)
 
 
 # ---- linear polarization (lt_trace_disk_pol, lt_shade_stokes, lt_hotspot_lightcurve_stokes) ------------------------

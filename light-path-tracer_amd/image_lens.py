@@ -324,7 +324,8 @@ def render_sequence(source_image, metric, r_obs, fov, disk, hotspot, times, shap
     diskmap (disk.DiskMap): the moving source is an emissivity table on the disk that turns with it instead of a spot;
     `hotspot` is then None.  Frames come from lt_shade_diskmap (samples: lt_shade_diskmap_aa) and the light curve from
     lt_diskmap_lightcurve, scaled as above; everything else is as with a spot.  A map together with a spot or with a
-    field is refused: both are out of scope.
+    field is refused: both are out of scope.  diskmap may also be a disk.DiskMovie, tables that change with time: the same
+    keys come back from the lt_*diskmovie* entry points, every image order looking the movie up at its own emission time.
     spectrum (disk.Spectrum): the result gains `spectrum` (n, planes, n_bins + 2) float64, the moving emitter's dynamic
     spectrum over the grid in g (lt_hotspot_spectrum, or lt_diskmap_spectrum with a map), and `disk_spectrum`
     (planes, n_bins + 2), the stationary disk's line profile (lt_disk_spectrum); planes is 1, or max_images with
@@ -438,30 +439,41 @@ def _sequence_spectra(out, traced, met, d, sp, dyn, S):
     out.update(spectrum=dyn / scale, disk_spectrum=line / scale)
 
 
+def _table_emitter(diskmap):
+    """(the emitter's arguments, the entry points frame / supersampled frame / light curve / spectrum / visibility) of a
+    disk.DiskMap, or of a disk.DiskMovie: the map's with the movie's clock behind the map's struct."""
+    from disk import DiskMovie
+    if isinstance(diskmap, DiskMovie):
+        dm, mv = diskmap.to_lt()
+        return (dm, mv, diskmap.texels), (ltrace.shade_diskmovie, ltrace.shade_diskmovie_aa, ltrace.diskmovie_lightcurve,
+                                          ltrace.diskmovie_spectrum, ltrace.diskmovie_visibility)
+    return (diskmap.to_lt(), diskmap.texels), (ltrace.shade_diskmap, ltrace.shade_diskmap_aa, ltrace.diskmap_lightcurve,
+                                               ltrace.diskmap_spectrum, ltrace.diskmap_visibility)
+
+
 def _sequence_diskmap(traced, met, d, diskmap, times, dt, base, S, spectrum=None, baselines=None):
-    """render_sequence's frames and light curve for a disk map, from the traced records."""
-    dm, tex = diskmap.to_lt(), diskmap.texels
+    """render_sequence's frames and light curve for a disk map or a disk movie, from the traced records."""
+    table, (shade, shade_aa, lightcurve, dyn_spectrum, dyn_visibility) = _table_emitter(diskmap)
     frames, rgba = [], []
     for t in times:
         if S is None:
-            f = ltrace.shade_diskmap(traced["hits"], traced["n_hits"], met, d, dm, tex, float(t), base=base)
+            f = shade(traced["hits"], traced["n_hits"], met, d, *table, float(t), base=base)
         else:
-            f = ltrace.shade_diskmap_aa(traced["hits"], traced["n_hits"], S, met, d, dm, tex, float(t), base=base)
+            f = shade_aa(traced["hits"], traced["n_hits"], S, met, d, *table, float(t), base=base)
         frames.append(f["rgb"])
         rgba.append(f["rgba"])
-    lc = ltrace.diskmap_lightcurve(traced["hits"], traced["n_hits"], met, d, dm, tex, float(times[0]), dt, times.size)
+    lc = lightcurve(traced["hits"], traced["n_hits"], met, d, *table, float(times[0]), dt, times.size)
     if S is not None:
         lc = lc / np.array([S * S, S ** 3, S ** 3], dtype=np.float64)
     out = dict(frames=np.stack(frames), rgba=np.stack(rgba), lightcurve=lc, hits=traced["hits"], n_hits=traced["n_hits"],
                stats=traced["stats"])
     if spectrum is not None:
         sp = spectrum.to_lt()
-        dyn = ltrace.diskmap_spectrum(traced["hits"], traced["n_hits"], met, d, dm, tex, sp, float(times[0]), dt, times.size)
+        dyn = dyn_spectrum(traced["hits"], traced["n_hits"], met, d, *table, sp, float(times[0]), dt, times.size)
         _sequence_spectra(out, traced, met, d, sp, dyn, S)
     if baselines is not None:
         uv = baselines.fine(1 if S is None else S)
-        dyn = ltrace.diskmap_visibility(traced["hits"], traced["n_hits"], met, d, dm, tex, uv, baselines.split_orders, float(times[0]), dt,
-                                        times.size)
+        dyn = dyn_visibility(traced["hits"], traced["n_hits"], met, d, *table, uv, baselines.split_orders, float(times[0]), dt, times.size)
         _sequence_visibilities(out, traced, met, d, baselines, uv, dyn, S)
     if S is not None:
         out["samples"] = S
@@ -497,21 +509,55 @@ def baselines_from_args(args):
 
 
 def diskmap_from_args(args, disk, M, a):
-    """The disk.DiskMap of --disk-map PATH.npy|spiral and its --disk-map-* options; the range defaults to the disk's edges."""
-    from disk import DiskMap, spiral_map
+    """The disk.DiskMap of --disk-map PATH.npy|spiral and its --disk-map-* options; the range defaults to the disk's edges.
+    A 3-D array, or --disk-map flare, is a disk.DiskMovie on the clock of --disk-map-frames T0 DT [hold|loop]."""
+    from disk import DiskMap, DiskMovie, flare_movie, spiral_map
     r_min, r_max = args.disk_map_range if args.disk_map_range is not None else (disk.inner_edge(M, a), disk.r_out)
+    common = dict(r_min=float(r_min), r_max=float(r_max), rotation=args.disk_map_rotation, omega_p=args.disk_map_omega,
+                  exposure=args.disk_map_exposure)
+    clock = movie_clock_from_args(args)
     if args.disk_map == "spiral":
         texels = spiral_map(256, 1024, r_min=r_min, r_max=r_max)
+    elif args.disk_map == "flare":
+        if clock is None:
+            raise ValueError("--disk-map flare is a movie and needs its clock: --disk-map-frames T0 DT [hold|loop]")
+        t0, dt, boundary = clock
+        # 32 frames: a clump at 0.4 of the way out that outshines the quiescent disk threefold at frame 12 and lasts some five frames
+        return flare_movie(32, 256, 1024, r_s=r_min + 0.4 * (r_max - r_min), phi_s=0.0, sigma=0.08 * (r_max - r_min), t_peak=t0 + 12 * dt,
+                           t_width=2 * dt, dt_frame=dt, t0=t0, floor=0.05, amplitude=10.0, boundary=boundary, M=M, a=a, **common)
     else:
         texels = np.load(args.disk_map, allow_pickle=False)
-    return DiskMap(texels, r_min=float(r_min), r_max=float(r_max), rotation=args.disk_map_rotation, omega_p=args.disk_map_omega,
-                   exposure=args.disk_map_exposure)
+    if texels.ndim == 3:
+        if clock is None:
+            raise ValueError(f"--disk-map: {texels.shape} is a movie of {texels.shape[0]} frames and needs its clock: "
+                             "--disk-map-frames T0 DT [hold|loop]")
+        return DiskMovie(texels, t0=clock[0], dt_frame=clock[1], boundary=clock[2], **common)
+    if clock is not None:
+        raise ValueError("--disk-map-frames is the clock of a movie: a 3-D array (n_frames, n_r, n_phi), or --disk-map flare")
+    return DiskMap(texels, **common)
+
+
+def movie_clock_from_args(args):
+    """(t0, dt_frame, boundary) of --disk-map-frames T0 DT [hold|loop], or None."""
+    f = args.disk_map_frames
+    if f is None:
+        return None
+    if len(f) not in (2, 3) or (len(f) == 3 and f[2] not in ("hold", "loop")):
+        raise ValueError("--disk-map-frames takes T0 DT [hold|loop]")
+    try:
+        t0, dt = float(f[0]), float(f[1])
+    except ValueError:
+        raise ValueError("--disk-map-frames takes T0 DT [hold|loop]: T0 and DT are numbers") from None
+    if not (np.isfinite(t0) and np.isfinite(dt) and dt > 0.0):
+        raise ValueError("--disk-map-frames: T0 and DT must be finite, DT > 0")
+    return t0, dt, f[2] if len(f) == 3 else "hold"
 
 
 def main_sequence(args, disk):
     """--hotspot R PHI0 SIGMA --times T0 DT N: numbered PNGs next to --output and the light curve as .npy.
     --disk-map PATH.npy|spiral (with --disk-map-range / -rotation / -omega / -exposure): the same for an emissivity table
-    that turns with the disk, in the spot's place.
+    that turns with the disk, in the spot's place.  A 3-D array (n_frames, n_r, n_phi) or --disk-map flare, with
+    --disk-map-frames T0 DT [hold|loop]: the same for a movie, tables that change with time.
     --samples S: the sequence supersampled, S x S rays per pixel traced once and every frame resolved on the GPU.
     --bfield BR BPHI BZ [--pol-frac P]: also the Stokes frames (I, Q, U) as numbered .npy and the Stokes light curve;
     without --hotspot the spot is dark and the frames show the disk alone.
@@ -577,7 +623,7 @@ def main_sequence(args, disk):
             print(f"Polarized visibilities (I, Q, U) -> {stem}_visibility_stokes.npy (per time), {stem}_disk_visibility_stokes.npy (the disk's)")
     if args.samples is not None:
         print(f"Supersampling: {args.samples} x {args.samples} rays per pixel, every frame resolved on the GPU")
-    print(f"{'Hot spot' if dmap is None else 'Disk map'}: one trace ({out['stats']['integrate_ms']:.2f} ms), {n} frames -> {stem}_0000.png ..., light curve -> "
+    print(f"{'Hot spot' if dmap is None else 'Disk map' if dmap.texels.ndim == 2 else 'Disk movie'}: one trace ({out['stats']['integrate_ms']:.2f} ms), {n} frames -> {stem}_0000.png ..., light curve -> "
           f"{stem}_lightcurve.npy")
     return out
 
@@ -848,9 +894,13 @@ def build_parser():
                     help="with --disk-images: the magnetic field's direction in the disk material's frame; writes the Stokes "
                          "frames (I, Q, U) as numbered .npy and the Stokes light curve, with --hotspot or without it")
     ap.add_argument("--pol-frac", type=float, default=0.7, help="--bfield: polarization fraction in [0, 1] (default: 0.7)")
-    ap.add_argument("--disk-map", default=None, metavar="PATH.npy|spiral",
+    ap.add_argument("--disk-map", default=None, metavar="PATH.npy|spiral|flare",
                     help="with --disk-images: an emissivity table (n_r, n_phi) on the disk that turns with it, from a .npy file or "
-                         "the built-in two-armed spiral; re-shaded per --times from one trace like --hotspot, with --samples or without")
+                         "the built-in two-armed spiral; re-shaded per --times from one trace like --hotspot, with --samples or without.  "
+                         "A 3-D array (n_frames, n_r, n_phi), or the built-in flare, is a movie and needs --disk-map-frames")
+    ap.add_argument("--disk-map-frames", nargs="+", default=None, metavar="T0 DT [hold|loop]",
+                    help="--disk-map with a movie: frame q is at coordinate time T0 + q DT; beyond the movie its end frames are held "
+                         "(default) or it loops")
     ap.add_argument("--disk-map-range", type=float, nargs=2, default=None, metavar=("RMIN", "RMAX"),
                     help="--disk-map: the annulus the table covers, in M (default: the disk's edges)")
     ap.add_argument("--disk-map-rotation", choices=["kepler", "rigid"], default="kepler",

@@ -89,6 +89,15 @@ class DiskMap(C.Structure):
 MAP_KEPLERIAN, MAP_RIGID = 0, 1
 
 
+class DiskMovie(C.Structure):
+    """lt_diskmovie: the clock of (n_frames, n_r, n_phi) emissivity tables -- frame q at t0 + q dt_frame -- and what
+    happens beyond them (MOVIE_HOLD / MOVIE_LOOP)."""
+    _fields_ = [("t0", C.c_double), ("dt_frame", C.c_double), ("n_frames", C.c_int32), ("boundary", C.c_int32)]
+
+
+MOVIE_HOLD, MOVIE_LOOP = 0, 1
+
+
 class Spectrum(C.Structure):
     """lt_spectrum: a linear grid in g = E_obs / E_rest (n_bins bins, an underflow and an overflow column)."""
     _fields_ = [("g_min", C.c_double), ("g_max", C.c_double), ("n_bins", C.c_int32), ("split_orders", C.c_int32)]
@@ -343,6 +352,7 @@ SIGNATURES = {
     "lt_diskmap_lightcurve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Metric),
                                         C.POINTER(Disk), C.POINTER(DiskMap), C.c_void_p, C.c_double, C.c_double, C.c_int32,
                                         C.c_void_p]),
+    "lt_default_diskmovie": (None, [C.POINTER(DiskMovie)]),
     "lt_default_aa": (None, [C.POINTER(AA)]),
     "lt_render_aa_dev": (C.c_int, [C.POINTER(Camera), C.POINTER(Metric), C.POINTER(Opts), C.POINTER(AA), C.POINTER(Disk),
                                    C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -360,6 +370,19 @@ SIGNATURES = {
     "lt_aa_adaptive_plan": (C.c_int, [C.POINTER(Camera), C.POINTER(Metric), C.POINTER(Opts), C.POINTER(AAAdaptive),
                                       C.POINTER(Disk), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
 }
+
+
+def _movie_signature(name):
+    """The map's signature with `const lt_diskmovie *movie` after `map`."""
+    res, args = SIGNATURES[name]
+    at = args.index(C.POINTER(DiskMap)) + 1
+    return res, args[:at] + [C.POINTER(DiskMovie)] + args[at:]
+
+
+# the movie's ten entry points: lt_shade_diskmovie[_aa][_dev], lt_diskmovie_{lightcurve,spectrum,visibility}[_dev]
+for _name in ("lt_shade_diskmap", "lt_shade_diskmap_aa", "lt_diskmap_lightcurve", "lt_diskmap_spectrum", "lt_diskmap_visibility"):
+    for _suffix in ("", "_dev"):
+        SIGNATURES[_name.replace("diskmap", "diskmovie") + _suffix] = _movie_signature(_name + _suffix)
 
 
 def load():
@@ -1761,6 +1784,123 @@ def diskmap_visibility_dev(d_hits, d_n_hits, rows, width, max_images, metric, di
     """Device-pointer form of diskmap_visibility (lt_diskmap_visibility_dev); uv stays a host array."""
     _visibility_dev(load().lt_diskmap_visibility_dev, (d_hits, d_n_hits), (rows, width, max_images),
                     (C.byref(metric), C.byref(disk), C.byref(dmap), _p(d_texels)), uv, split_orders, _times(t_start, dt, n_times), d_out)
+
+
+# ---- a disk movie: tables that change with time (lt_shade_diskmovie, lt_shade_diskmovie_aa, lt_diskmovie_*) ---------------
+MOVIE_BOUNDARIES = {"hold": MOVIE_HOLD, "loop": MOVIE_LOOP}
+
+
+def default_diskmovie(**kw):
+    """lt_diskmovie with the library's defaults (t0 0, dt_frame 1, 1 frame, hold); keywords override (boundary: "hold" /
+    "loop" or the LT_MOVIE_* value)."""
+    mv = DiskMovie()
+    load().lt_default_diskmovie(C.byref(mv))
+    for k, v in kw.items():
+        if k == "boundary" and isinstance(v, str):
+            v = MOVIE_BOUNDARIES[v]
+        setattr(mv, k, v)
+    return mv
+
+
+def _movie_array(dmap, movie, texels):
+    """The movie's tables as the library reads them: C-contiguous float32 of exactly (movie.n_frames, dmap.n_r, dmap.n_phi)
+    -- the kernels index them with the structs' sizes, so any other shape is refused here."""
+    t = np.ascontiguousarray(texels, dtype=np.float32)
+    want = (int(movie.n_frames), int(dmap.n_r), int(dmap.n_phi))
+    if t.shape != want:
+        raise ValueError(f"texels must be (n_frames, n_r, n_phi) = {want}; got {t.shape}")
+    return t
+
+
+def shade_diskmovie(hits, n_hits, metric, disk, dmap, movie, texels, t_obs, base=None, channels=None, want=("rgb", "rgba")):
+    """The frame of a disk movie at observer time t_obs from stored hits (lt_shade_diskmovie).  dmap: an ltrace.DiskMap,
+    movie: an ltrace.DiskMovie, texels (n_frames, n_r, n_phi) float32; everything else as shade_diskmap.  -> dict(rgb, rgba)."""
+    hits, nh = _hit_arrays(hits, n_hits)
+    tex = _movie_array(dmap, movie, texels)
+    R, W, m = hits.shape[:3]
+    return _shade_frame(load().lt_shade_diskmovie, hits, nh, R, W,
+                        (m, C.byref(metric), C.byref(disk), C.byref(dmap), C.byref(movie), _np_ptr(tex), float(t_obs)), base, channels, want)
+
+
+def shade_diskmovie_dev(d_hits, d_n_hits, rows, width, max_images, metric, disk, dmap, movie, d_texels, t_obs, d_base=0, channels=3,
+                        d_rgb=0, d_rgba=0):
+    """Device-pointer form of shade_diskmovie (lt_shade_diskmovie_dev): d_texels holds movie.n_frames x dmap.n_r x dmap.n_phi
+    float32; enqueues on the default stream."""
+    _check(load().lt_shade_diskmovie_dev(_p(d_hits), _p(d_n_hits), rows, width, max_images, C.byref(metric), C.byref(disk),
+                                         C.byref(dmap), C.byref(movie), _p(d_texels), float(t_obs), _p(d_base), channels, _p(d_rgb),
+                                         _p(d_rgba)))
+
+
+def shade_diskmovie_aa(hits, n_hits, samples, metric, disk, dmap, movie, texels, t_obs, base=None, channels=None, want=("rgb", "rgba")):
+    """The supersampled frame of a disk movie (lt_shade_diskmovie_aa): shade_diskmovie() of the FINE records
+    (rows S, W S, max_images, 4) and base (rows S, W S[, 3]), resolved S x S -> 1 on the GPU.  -> dict(rgb (rows, W[, 3]),
+    rgba (rows, W, 4)); ValueError where the fine shape is no multiple of samples."""
+    hits, nh = _hit_arrays(hits, n_hits)
+    tex = _movie_array(dmap, movie, texels)
+    R, W, S = _fine_shape(hits, samples)
+    return _shade_frame(load().lt_shade_diskmovie_aa, hits, nh, R, W,
+                        (S, hits.shape[2], C.byref(metric), C.byref(disk), C.byref(dmap), C.byref(movie), _np_ptr(tex), float(t_obs)), base,
+                        channels, want)
+
+
+def shade_diskmovie_aa_dev(d_hits, d_n_hits, rows, width, samples, max_images, metric, disk, dmap, movie, d_texels, t_obs, d_base=0,
+                           channels=3, d_rgb=0, d_rgba=0):
+    """Device-pointer form of shade_diskmovie_aa (lt_shade_diskmovie_aa_dev): rows, width of the OUTPUT; enqueues on the
+    default stream."""
+    _check(load().lt_shade_diskmovie_aa_dev(_p(d_hits), _p(d_n_hits), rows, width, samples, max_images, C.byref(metric),
+                                            C.byref(disk), C.byref(dmap), C.byref(movie), _p(d_texels), float(t_obs), _p(d_base),
+                                            channels, _p(d_rgb), _p(d_rgba)))
+
+
+def diskmovie_lightcurve(hits, n_hits, metric, disk, dmap, movie, texels, t_start, dt, n_times):
+    """The movie's light curve (lt_diskmovie_lightcurve) -> (n_times, 3) float64: per time the sums of e, e ix, e iy."""
+    hits, nh = _hit_arrays(hits, n_hits)
+    tex = _movie_array(dmap, movie, texels)
+    R, W, m = hits.shape[:3]
+    out = np.empty((int(n_times), 3))
+    _check(load().lt_diskmovie_lightcurve(_np_ptr(hits), _np_ptr(nh), R, W, m, C.byref(metric), C.byref(disk), C.byref(dmap),
+                                          C.byref(movie), _np_ptr(tex), float(t_start), float(dt), int(n_times), _np_ptr(out)))
+    return out
+
+
+def diskmovie_lightcurve_dev(d_hits, d_n_hits, rows, width, max_images, metric, disk, dmap, movie, d_texels, t_start, dt, n_times, d_out):
+    """Device-pointer form of diskmovie_lightcurve (lt_diskmovie_lightcurve_dev); enqueues on the default stream."""
+    _check(load().lt_diskmovie_lightcurve_dev(_p(d_hits), _p(d_n_hits), rows, width, max_images, C.byref(metric), C.byref(disk),
+                                              C.byref(dmap), C.byref(movie), _p(d_texels), float(t_start), float(dt), int(n_times),
+                                              _p(d_out)))
+
+
+def diskmovie_spectrum(hits, n_hits, metric, disk, dmap, movie, texels, spec, t_start, dt, n_times):
+    """The movie's dynamic spectrum (lt_diskmovie_spectrum) -> (n_times, planes, n_bins + 2) float64 at t_start + i dt."""
+    records = _hit_arrays(hits, n_hits)
+    tex = _movie_array(dmap, movie, texels)
+    return _spectrum(load().lt_diskmovie_spectrum, records, (C.byref(metric), C.byref(disk), C.byref(dmap), C.byref(movie), _np_ptr(tex)),
+                     spec, _times(t_start, dt, n_times))
+
+
+def diskmovie_spectrum_dev(d_hits, d_n_hits, rows, width, max_images, metric, disk, dmap, movie, d_texels, spec, t_start, dt, n_times,
+                           d_out):
+    """Device-pointer form of diskmovie_spectrum (lt_diskmovie_spectrum_dev); enqueues on the default stream."""
+    _check(load().lt_diskmovie_spectrum_dev(_p(d_hits), _p(d_n_hits), rows, width, max_images, C.byref(metric), C.byref(disk),
+                                            C.byref(dmap), C.byref(movie), _p(d_texels), C.byref(spec), *_times(t_start, dt, n_times),
+                                            _p(d_out)))
+
+
+def diskmovie_visibility(hits, n_hits, metric, disk, dmap, movie, texels, uv, split_orders, t_start, dt, n_times):
+    """The movie's visibilities (lt_diskmovie_visibility) -> (n_times, planes, n_baselines) complex128 at t_start + i dt."""
+    records = _hit_arrays(hits, n_hits)
+    tex = _movie_array(dmap, movie, texels)
+    return _visibility(load().lt_diskmovie_visibility, records,
+                       (C.byref(metric), C.byref(disk), C.byref(dmap), C.byref(movie), _np_ptr(tex)), uv, split_orders,
+                       _times(t_start, dt, n_times))
+
+
+def diskmovie_visibility_dev(d_hits, d_n_hits, rows, width, max_images, metric, disk, dmap, movie, d_texels, uv, split_orders, t_start, dt,
+                             n_times, d_out):
+    """Device-pointer form of diskmovie_visibility (lt_diskmovie_visibility_dev); uv stays a host array."""
+    _visibility_dev(load().lt_diskmovie_visibility_dev, (d_hits, d_n_hits), (rows, width, max_images),
+                    (C.byref(metric), C.byref(disk), C.byref(dmap), C.byref(movie), _p(d_texels)), uv, split_orders,
+                    _times(t_start, dt, n_times), d_out)
 
 
 # ---- polarized visibilities (lt_disk_visibility_stokes, lt_hotspot_visibility_stokes) -------------------------------------
