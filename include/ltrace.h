@@ -990,8 +990,8 @@ int lt_diskmap_lightcurve(const float *hits, const uint8_t *n_hits, int32_t R, i
  * disk.Spectrum / disk.spectrum_bin / disk.disk_spectrum / disk.hotspot_spectrum / disk.diskmap_spectrum (Python)       *
  * state the rule in numpy.                                                                                       *
  *                                                                                                               *
- * Out of scope: the thermal continuum and any rest-frame shape other than a line, polarized spectra, logarithmic        *
- * grids, per-pixel spectra, lt_render_multi and the multi-process path, adaptive sampling.                          */
+ * Out of scope: any rest-frame shape other than a line (the thermal continuum has its own section), polarized          *
+ * spectra, logarithmic grids, per-pixel spectra, lt_render_multi and the multi-process path, adaptive sampling.        */
 #define LT_SPECTRUM_MAX_BINS 512
 #define LT_SPECTRUM_BLOCKS 256
 #define LT_SPECTRUM_WORKSPACE_BYTES (64 << 20)
@@ -1273,6 +1273,101 @@ int lt_hotspot_visibility_stokes(const float *hits, const uint8_t *n_hits, const
                                  int32_t max_images, const lt_metric *metric, const lt_disk *disk, const lt_hotspot *spot,
                                  const lt_bfield *field, const double *uv, int32_t n_baselines, int32_t split_orders,
                                  double t_start, double dt, int32_t n_times, double *out);
+
+/* ---- thermal continuum: a radial flux table, its multi-colour blackbody spectrum and band images ------------------- *
+ * Every product above shades the disk with one fixed law, exposure g^4 (r_in / r)^q, and has no frequency.  These      *
+ * entry points give the disk a temperature: a radial flux profile F(r) -- Novikov-Thorne's, or any other the caller    *
+ * tabulates -- makes every stored hit a blackbody at T = t_max F^(1/4), hardened by a colour-correction factor and     *
+ * shifted by the hit's g.  lt_disk_thermal_spectrum is the multi-colour blackbody spectrum the continuum-fitting       *
+ * method measures spin from, lt_shade_thermal the image in up to LT_THERMAL_MAX_BANDS narrow bands.  Two more          *
+ * reductions over the records of lt_trace_disk_hits; nothing is traced again, and the disk's q and exposure are not    *
+ * looked at beyond their refusals.                                                                                     *
+ *                                                                                                                      *
+ * Emitter.  lt_thermal and a float64 table flux[n_r]: node i sits at r_min + i (r_max - r_min) / (n_r - 1).  The FLUX  *
+ * is tabulated and not the temperature: near the ISCO the flux is about quadratic in sqrt(r) - sqrt(r_isco), so linear *
+ * interpolation holds, where the temperature has an infinite slope.  t_max is a frequency (k T / h at flux = 1), so    *
+ * are the nu below, and 2 h / c^2 = 1.                                                                                 *
+ *                                                                                                                      *
+ * The rule, per stored slot (the stored slots are the re-shades': the first min(n_hits, max_images), or the leading    *
+ * slots whose r is not NaN when n_hits is NULL), in float64 from the stored float32 (r, g), in exactly these steps --  *
+ * each is one rounded operation or an explicit fma, whatever the compiler may contract:                                *
+ *   1. r = (double)r32, g = (double)g32.  The slot emits nothing if g is NaN or g <= 0, or if r is NaN, r < r_min or r *
+ *      > r_max (the float32 value compared exactly against the doubles).                                               *
+ *   2. v = (r - r_min) inv_dr, a subtraction and then a product, with inv_dr = (n_r - 1) / (r_max - r_min) computed    *
+ *      once on the host;  i0 = min((int)floor(v), n_r - 2);  w = v - i0, a subtraction of the rounded v.               *
+ *   3. F = fma(w, flux[i0 + 1] - flux[i0], flux[i0]).  The slot emits nothing where !(F > 0).                          *
+ *   4. T = t_max sqrt(sqrt(F));  c = 1.0 / ((g f_col) T).  A = exposure / ((f_col f_col) (f_col f_col)) is the same    *
+ *      for every slot and computed once on the host.                                                                   *
+ *   5. The observed specific intensity through this slot at frequency nu is nu^3 A / expm1(nu c), nu c rounded: this   *
+ *      is exposure g^3 f_col^-4 B_{nu/g}(f_col T) with B_nu(T) = nu^3 / expm1(nu / T), the g^3 of the invariant I_nu / *
+ *      nu^3 cancelling against (nu / g)^3; integrated over nu it is (pi^4 / 15) exposure g^4 T^4, the bolometric g^4   *
+ *      of the other products.  The factor nu^3 is applied once per sum, not per term: a sum S of quotients becomes     *
+ *      ((nu nu) nu) S, three rounded products.                                                                         *
+ * expm1 is the only operation whose result the device library may round differently from another statement of the      *
+ * rule. Where nu c overflows expm1 the term is +0.                                                                     *
+ *                                                                                                                      *
+ * Frequencies.  nu is n_freq float64 values, each finite and > 0, in any order.  They are not checked: nu = 0 gives    *
+ * NaN where a slot emits (0 times infinity) and +0 elsewhere, a negative nu the formula's value with nu^3 < 0          *
+ * (positive, or -0 where nothing emits), a NaN gives NaN.  Nor are the flux values: a NaN or non-positive F emits      *
+ * nothing (step 3).                                                                                                    *
+ *                                                                                                                      *
+ * lt_disk_thermal_spectrum.  out: float64 (planes, n_freq), the flux density summed over all pixels and stored slots;  *
+ * planes is 1, or max_images with split_orders: plane j then holds the hits stored in slot j.  n_freq <=               *
+ * LT_THERMAL_MAX_FREQS.  A plane without an emitting slot is exactly +0.0. Order of every sum (it depends on R, W,     *
+ * max_images and the records alone; no floating-point atomics anywhere, so a result is the same bits run after run,    *
+ * whatever other frequencies are asked for with it and in whatever order). Workgroup b of LT_SPECTRUM_BLOCKS walks the *
+ * chunks of 256 pixels p = 256 (b + k LT_SPECTRUM_BLOCKS) + i, k ascending (the light curve's stride order), and adds  *
+ * to its sum of a plane and frequency, which starts at 0, the quotients A / expm1(nu c) of the chunk's emitting slots  *
+ * ordered by wavefront i div 64, then lane i mod 64, then slot -- that is, in ascending i and then slot.  After its    *
+ * last chunk it multiplies by nu^3.  The final stage adds the LT_SPECTRUM_BLOCKS partial sums, b ascending.  The       *
+ * partials, at most LT_SPECTRUM_BLOCKS x 8 x 1024 x 8 B = 16 MiB, live in the spectra's grow-only workspace, in one    *
+ * batch.                                                                                                               *
+ *                                                                                                                      *
+ * lt_shade_thermal.  out: float32 (n_freq, R, W), plane-major, n_freq <= LT_THERMAL_MAX_BANDS.  Per pixel and band the *
+ * quotients of the pixel's emitting slots are added in slot order in float64, the sum is multiplied by nu^3 and        *
+ * rounded once to float32.  No base, no clamp, no colour ramp: a pixel without an emitting slot is exactly +0.0.       *
+ * split_orders is refused.  The image is linear in the records, so a supersampled image is the S x S mean of the fine  *
+ * one per plane (aa.resolve on the host).                                                                              *
+ *                                                                                                                      *
+ * Refusals, in this order: those of lt_disk_spectrum up to and including the disk's q / exposure; then                 *
+ * LT_ERR_INVALID_ARG for a null thermal / flux / nu; the struct's fields in the struct's order (the range, t_max,      *
+ * f_col, exposure, n_r; split_orders for lt_shade_thermal); n_freq outside 0 ... the limit; and a null out.  n_freq =  *
+ * 0 is LT_OK and writes nothing, even with a null out.  The outputs of a refused call are untouched. disk.ThermalDisk  *
+ * / disk.novikov_thorne_flux / disk.thermal_coeffs / disk.thermal_spectrum / disk.shade_thermal (Python) state the     *
+ * rule in numpy.                                                                                                       *
+ *                                                                                                                      *
+ * Out of scope: limb darkening and returning radiation, absolute units and a conversion from an accretion rate to      *
+ * t_max, thermal light for the spot, the map and the movie, visibilities per frequency, a fused supersampled form,     *
+ * lt_render_multi and the multi-process path, replacing the (r_in / r)^q law in the existing frames.                   */
+#define LT_THERMAL_MAX_NODES 65536
+#define LT_THERMAL_MAX_FREQS 1024
+#define LT_THERMAL_MAX_BANDS 16
+
+typedef struct lt_thermal {
+    double r_min, r_max;  /* node i sits at r_min + i (r_max - r_min)/(n_r - 1); 0 < r_min < r_max, finite */
+    double t_max;         /* T = t_max * flux^(1/4), as a frequency (kT/h); > 0, finite */
+    double f_col;         /* colour-correction (hardening) factor; > 0, finite; default 1 */
+    double exposure;      /* >= 0, finite */
+    int32_t n_r;          /* 2 ... LT_THERMAL_MAX_NODES */
+    int32_t split_orders; /* nonzero: one plane per stored slot (image order); lt_shade_thermal refuses it */
+} lt_thermal;
+void lt_default_thermal(lt_thermal *thermal); /* 6 ... 20, t_max 1, f_col 1, exposure 1, 2 nodes, not split */
+
+/* The _dev forms take DEVICE pointers for the records, flux, nu and the output and enqueue on the default stream; the
+ * others HOST pointers, staged like the spectra.  flux: thermal->n_r float64; nu: n_freq float64.
+ * lt_disk_thermal_spectrum: out (planes, n_freq) float64.  lt_shade_thermal: out (n_freq, R, W) float32. */
+int lt_disk_thermal_spectrum_dev(const float *d_hits, const uint8_t *d_n_hits, int32_t R, int32_t W, int32_t max_images,
+                                 const lt_metric *metric, const lt_disk *disk, const lt_thermal *thermal,
+                                 const double *d_flux, const double *d_nu, int32_t n_freq, double *d_out);
+int lt_disk_thermal_spectrum(const float *hits, const uint8_t *n_hits, int32_t R, int32_t W, int32_t max_images,
+                             const lt_metric *metric, const lt_disk *disk, const lt_thermal *thermal, const double *flux,
+                             const double *nu, int32_t n_freq, double *out);
+int lt_shade_thermal_dev(const float *d_hits, const uint8_t *d_n_hits, int32_t R, int32_t W, int32_t max_images,
+                         const lt_metric *metric, const lt_disk *disk, const lt_thermal *thermal, const double *d_flux,
+                         const double *d_nu, int32_t n_freq, float *d_out);
+int lt_shade_thermal(const float *hits, const uint8_t *n_hits, int32_t R, int32_t W, int32_t max_images,
+                     const lt_metric *metric, const lt_disk *disk, const lt_thermal *thermal, const double *flux,
+                     const double *nu, int32_t n_freq, float *out);
 
 /* ---- supersampled (anti-aliased) frames, resolved on the GPU ------------------------------------------- *
  * Every frame above is one ray per pixel, taken at the pixel's corner.  These entry points trace S x S rays per       *

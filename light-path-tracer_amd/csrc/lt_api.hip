@@ -18,6 +18,7 @@
 #include "lt_visibility.hpp"
 #include "lt_visibility_stokes.hpp"
 #include "lt_diskmovie.hpp"
+#include "lt_thermal.hpp"
 #ifdef LT_PROBES
 #include "lt_probe.hpp"
 #endif
@@ -2302,3 +2303,4 @@ extern "C" int lt_scatter_rows_indexed_dev(const void *d_rows, void *d_full, con
 #include "lt_api_visibility.inc"
 #include "lt_api_visibility_stokes.inc"
 #include "lt_api_diskmovie.inc"
+#include "lt_api_thermal.inc"

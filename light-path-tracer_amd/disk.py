@@ -25,6 +25,11 @@ The same weights taken with a phase per pixel give what an interferometer measur
 visibility_phase is the phase rule, and disk_visibility / hotspot_visibility / diskmap_visibility the complex
 visibilities per image order (lt_*_visibility).  disk_visibility_stokes / hotspot_visibility_stokes carry the polarization
 records through the same sums (I, Q, U per baseline; lt_*_visibility_stokes), and fractional_polarization divides them.
+
+The thermal continuum gives the disk a temperature: novikov_thorne_flux is the relativistic thin disk's radial flux,
+ThermalDisk a tabulated flux profile with its temperature scale, thermal_coeffs the rule that makes a stored hit a
+blackbody, and thermal_spectrum / shade_thermal the multi-colour blackbody spectrum and the band images
+(lt_disk_thermal_spectrum, lt_shade_thermal).
 """
 from dataclasses import dataclass
 from typing import Optional
@@ -1022,3 +1027,204 @@ def fractional_polarization(V):
     i, q, u = V[..., 0, :], V[..., 1, :], V[..., 2, :]
     with np.errstate(invalid="ignore", divide="ignore"):
         return np.where(i == 0, np.nan + 0j, (q + 1j * u) / np.where(i == 0, 1.0, i))
+
+
+# ---- thermal continuum (lt_disk_thermal_spectrum, lt_shade_thermal) ----------------------------------------------------------
+THERMAL_MAX_NODES, THERMAL_MAX_FREQS, THERMAL_MAX_BANDS = 65536, 1024, 16
+
+
+def _nt_roots(astar):
+    """(x1, x2, x3) of Page & Thorne (1974) eq. 15n: the roots of x^3 - 3 x + 2 a*.  x2 = 2 cos((acos a* + pi) / 3) is taken
+    as 2 sin(asin(a*) / 3), the same number, which is exactly 0 at a* = 0 and keeps its relative accuracy near it."""
+    ac = np.arccos(astar)
+    return 2.0 * np.cos((ac - np.pi) / 3.0), 2.0 * np.sin(np.arcsin(astar) / 3.0), -2.0 * np.cos(ac / 3.0)
+
+
+def novikov_thorne_terms(M, a, r):
+    """The terms of the bracket of Page & Thorne (1974) eq. 15n at radii r, stacked on a new first axis (6, ...):
+    x, -x0, -(3/2) a* ln(x / x0) and the three root terms -3 (x_i - a*)^2 / (x_i (x_i - x_j)(x_i - x_k)) ln((x - x_i) /
+    (x0 - x_i)); x = sqrt(r / M), x0 = sqrt(r_isco / M), a* = a / M.  The x2 term is 0 at a* = 0, its limit.
+    novikov_thorne_flux adds them; their absolute sum over the bracket is the flux's condition number (the bracket cancels
+    towards the ISCO)."""
+    M, a = float(M), float(a)
+    astar = a / M
+    x = np.sqrt(np.asarray(r, dtype=np.float64) / M)
+    x0 = np.sqrt(float(isco(M, a)) / M)
+    roots = _nt_roots(astar)
+    terms = [x, np.full_like(x, -x0), -1.5 * astar * np.log(x / x0)]
+    for i in range(3):
+        xi, xj, xk = roots[i], roots[(i + 1) % 3], roots[(i + 2) % 3]
+        if xi == 0.0:
+            terms.append(np.zeros_like(x))
+            continue
+        coeff = 3.0 * (xi - astar) ** 2 / (xi * (xi - xj) * (xi - xk))
+        terms.append(-coeff * np.log((x - xi) / (x0 - xi)))
+    return np.stack(terms)
+
+
+def novikov_thorne_flux(M, a, r):
+    """The Novikov-Thorne flux of a relativistic thin disk around a Kerr hole, Page & Thorne (1974) eq. 15n with an
+    accretion rate of 1 (G = c = 1): the energy per unit proper time and proper area a face of the disk radiates at r,
+        F = 3 / (8 pi M^2) 1 / (x^4 (x^3 - 3 x + 2 a*)) [bracket],    x = sqrt(r / M),  a* = a / M
+    (novikov_thorne_terms has the bracket).  The disk orbits in +phi, so a < 0 is the retrograde disk.  F = 0 for
+    r <= r_isco: no torque at the inner edge.  |a| < M."""
+    M, a = float(M), float(a)
+    r = np.asarray(r, dtype=np.float64)
+    r_in = float(isco(M, a))
+    inside = r > r_in
+    rr = np.where(inside, r, 2.0 * r_in)                                  # (a placeholder outside the ISCO where F is not evaluated)
+    x = np.sqrt(rr / M)
+    bracket = novikov_thorne_terms(M, a, rr).sum(axis=0)
+    F = 3.0 / (8.0 * np.pi * M * M) / (x ** 4 * (x ** 3 - 3.0 * x + 2.0 * a / M)) * bracket
+    return np.where(inside, np.maximum(F, 0.0), 0.0)
+
+
+@dataclass
+class ThermalDisk:
+    """The thermal emitter (include/ltrace.h, "thermal continuum"): a radial flux table -- flux (n_r,) float64, node i at
+    r_min + i (r_max - r_min) / (n_r - 1), linearly interpolated -- and a temperature scale T = t_max flux^(1/4), t_max a
+    frequency (k T / h where flux = 1).  f_col: the colour-correction (hardening) factor; exposure: the brightness scale;
+    split_orders: one plane per stored slot (image order) in the spectrum."""
+    flux: np.ndarray
+    r_min: float
+    r_max: float
+    t_max: float = 1.0
+    f_col: float = 1.0
+    exposure: float = 1.0
+    split_orders: bool = False
+
+    def __post_init__(self):
+        flux = np.array(self.flux, dtype=np.float64)
+        if flux.ndim != 1 or not 2 <= flux.size <= THERMAL_MAX_NODES:
+            raise ValueError(f"ThermalDisk: flux must be (n_r,), n_r 2 ... {THERMAL_MAX_NODES}")
+        if not (0.0 < self.r_min < self.r_max and np.isfinite(self.r_max)):
+            raise ValueError("ThermalDisk needs 0 < r_min < r_max, both finite")
+        if not (self.t_max > 0.0 and np.isfinite(self.t_max) and self.f_col > 0.0 and np.isfinite(self.f_col)):
+            raise ValueError("ThermalDisk: t_max and f_col must be positive and finite")
+        if not (self.exposure >= 0.0 and np.isfinite(self.exposure)):
+            raise ValueError("ThermalDisk: exposure must be finite, >= 0")
+        self.flux = np.ascontiguousarray(flux)
+        self.r_min, self.r_max, self.t_max, self.f_col = float(self.r_min), float(self.r_max), float(self.t_max), float(self.f_col)
+        self.exposure, self.split_orders = float(self.exposure), bool(self.split_orders)
+
+    @property
+    def n_r(self):
+        return self.flux.size
+
+    def nodes(self):
+        """The radii of the table's nodes, (n_r,)."""
+        return self.r_min + np.arange(self.n_r) * (self.r_max - self.r_min) / (self.n_r - 1)
+
+    def planes(self, max_images):
+        return int(max_images) if self.split_orders else 1
+
+    def to_lt(self):
+        """The lt_thermal struct of this emitter (ltrace.Thermal); the table itself is passed beside it."""
+        import ltrace
+        return ltrace.default_thermal(r_min=self.r_min, r_max=self.r_max, t_max=self.t_max, f_col=self.f_col, exposure=self.exposure,
+                                      n_r=self.n_r, split_orders=int(self.split_orders))
+
+    @classmethod
+    def novikov_thorne(cls, M, a, r_out, n_r=4096, t_max=1.0, f_col=1.0, exposure=1.0, split_orders=False):
+        """The Novikov-Thorne disk from isco(M, a) to r_out on n_r nodes: novikov_thorne_flux divided by its largest node,
+        so that t_max is the peak effective temperature (as a frequency).  The first node, the ISCO, is 0."""
+        r_in = float(isco(M, a))
+        nodes = r_in + np.arange(int(n_r)) * (float(r_out) - r_in) / (int(n_r) - 1)
+        flux = novikov_thorne_flux(M, a, nodes)
+        flux[0] = 0.0
+        return cls(flux / flux.max(), r_in, float(r_out), t_max=t_max, f_col=f_col, exposure=exposure, split_orders=split_orders)
+
+
+def _two_sum(a, b):
+    s = a + b
+    bb = s - a
+    return s, (a - (s - bb)) + (b - bb)
+
+
+def _two_prod(a, b):
+    p = a * b
+    ca, cb = 134217729.0 * a, 134217729.0 * b
+    ah, bh = ca - (ca - a), cb - (cb - b)
+    al, bl = a - ah, b - bh
+    return p, ((ah * bh - p) + ah * bl + al * bh) + al * bl
+
+
+def fma(a, b, c):
+    """round(a b + c) with ONE rounding, float64, vectorised: numpy has no fused multiply-add, so this is Boldo and
+    Melquiond's emulation -- the exact product and sum as pairs (Dekker, Knuth), the two low parts added with rounding to
+    odd, and the high part added last.  Exact unless an intermediate overflows or the product's low part underflows
+    (|a b| below 2^-969), which the tables here stay far from."""
+    a, b, c = np.broadcast_arrays(np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64), np.asarray(c, dtype=np.float64))
+    uh, ul = _two_prod(a, b)
+    th, tl = _two_sum(c, uh)
+    v, e = _two_sum(tl, ul)
+    even = (np.ascontiguousarray(v).view(np.int64) & 1) == 0
+    v = np.where((e != 0.0) & even, np.nextafter(v, np.where(e > 0.0, np.inf, -np.inf)), v)
+    return th + v
+
+
+def thermal_coeffs(hits, n_hits, thermal):
+    """The header's steps 1 to 4 for every slot of hits (..., max_images, 4) float32 -> (A, c, emits): A the call's
+    amplitude exposure / f_col^4 (a float), c and emits (..., max_images): the slot's light at frequency nu is
+    nu^3 A / expm1(nu c) where emits, and nothing elsewhere (c = 0 there).  Every operation is the header's, in its order
+    and rounded as there (the interpolation by fma above)."""
+    h = np.asarray(hits, dtype=np.float32)
+    m = h.shape[-2]
+    r, g = h[..., 0].astype(np.float64), h[..., 2].astype(np.float64)
+    flux, n_r = thermal.flux, thermal.n_r
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        emits = (_stored(h, n_hits)[..., None] > np.arange(m)) & (g > 0.0) & (r >= thermal.r_min) & (r <= thermal.r_max)
+        inv_dr = float(n_r - 1) / (thermal.r_max - thermal.r_min)
+        v = (np.where(emits, r, thermal.r_min) - thermal.r_min) * inv_dr
+        i0 = np.clip(np.floor(v).astype(np.int64), 0, n_r - 2)
+        w = v - i0.astype(np.float64)
+        F = fma(w, flux[i0 + 1] - flux[i0], flux[i0])
+        emits = emits & (F > 0.0)
+        T = thermal.t_max * np.sqrt(np.sqrt(np.where(emits, F, 1.0)))
+        c = 1.0 / ((np.where(emits, g, 1.0) * thermal.f_col) * T)
+    A = thermal.exposure / ((thermal.f_col * thermal.f_col) * (thermal.f_col * thermal.f_col))
+    return A, np.where(emits, c, 0.0), emits
+
+
+def thermal_term(nu, A, c):
+    """Step 5 without its nu^3: A / expm1(nu c), the product rounded to float64 first."""
+    with np.errstate(over="ignore", divide="ignore", invalid="ignore"):
+        return A / np.expm1(nu * c)
+
+
+def _frequencies(nu, limit):
+    nu = np.asarray(nu, dtype=np.float64).ravel()
+    if nu.size > limit:
+        raise ValueError(f"at most {limit} frequencies")
+    return nu
+
+
+def thermal_spectrum(hits, n_hits, thermal, nu):
+    """lt_disk_thermal_spectrum restated: (planes, n_freq) float64, per plane and frequency ((nu nu) nu) times the sum of
+    A / expm1(nu c) over the emitting slots of all pixels (the order of the sum is numpy's, not the kernel's); planes is 1,
+    or max_images with thermal.split_orders."""
+    nu = _frequencies(nu, THERMAL_MAX_FREQS)
+    A, c, emits = thermal_coeffs(hits, n_hits, thermal)
+    out = np.zeros((thermal.planes(c.shape[-1]), nu.size))
+    for plane in range(out.shape[0]):
+        cp = c[..., plane][emits[..., plane]] if thermal.split_orders else c[emits]
+        for k in range(0, nu.size, 8):
+            f = nu[k:k + 8, None]
+            out[plane, k:k + 8] = ((f[:, 0] * f[:, 0]) * f[:, 0]) * thermal_term(f, A, cp[None, :]).sum(axis=-1)
+    return out
+
+
+def shade_thermal(hits, n_hits, thermal, nu):
+    """lt_shade_thermal restated: (n_freq, R, W) float32 band images -- per pixel and band the emitting slots' A / expm1(nu c)
+    added in slot order in float64, times (nu nu) nu, rounded once to float32.  A pixel without an emitting slot is +0.0."""
+    if thermal.split_orders:
+        raise ValueError("shade_thermal: a band image has one plane per band; split_orders must be off")
+    nu = _frequencies(nu, THERMAL_MAX_BANDS)
+    A, c, emits = thermal_coeffs(hits, n_hits, thermal)
+    out = np.zeros((nu.size,) + c.shape[:-1], dtype=np.float32)
+    for b, f in enumerate(nu):
+        total = np.zeros(c.shape[:-1])
+        for j in range(c.shape[-1]):
+            total = total + np.where(emits[..., j], thermal_term(f, A, np.where(emits[..., j], c[..., j], 1.0)), 0.0)
+        out[b] = (((f * f) * f) * total).astype(np.float32)
+    return out

@@ -303,7 +303,8 @@ def render_frame(source_image, metric, r_obs, fov, psi=(0.0, 0.0), theta_obs=np.
 
 
 def render_sequence(source_image, metric, r_obs, fov, disk, hotspot, times, shape=None, psi=(0.0, 0.0), theta_obs=np.pi / 2,
-                    integrator=None, precision=None, bfield=None, samples=None, diskmap=None, spectrum=None, baselines=None):
+                    integrator=None, precision=None, bfield=None, samples=None, diskmap=None, spectrum=None, baselines=None,
+                    thermal=None, frequencies=None, bands=None):
     """A moving picture from ONE trace: an optically thin disk (disk.TransparentDisk) with a hot spot (disk.HotSpot) on a
     circular orbit, at the observer times `times`.  The rays are traced once with the light-travel time of every hit
     (lt_trace_disk_hits); each frame is a re-shade of the stored hits (lt_shade_hotspot) over `base`, the lensed
@@ -339,7 +340,16 @@ def render_sequence(source_image, metric, r_obs, fov, disk, hotspot, times, shap
     spot's polarized visibilities (I, Q, U; lt_hotspot_visibility_stokes), and `disk_visibility_stokes` (planes, 3,
     n_baselines), the stationary disk's (lt_disk_visibility_stokes), recentred and scaled like `visibility`; their I plane
     is `visibility` / `disk_visibility`, and disk.fractional_polarization gives (Q~ + i U~) / I~.
+    thermal (disk.ThermalDisk) with frequencies (up to 1024 float64, > 0): the result gains `thermal_spectrum` (planes,
+    n_freq) float64, the stationary disk's thermal continuum at those frequencies (lt_disk_thermal_spectrum; planes is 1, or
+    max_images with thermal.split_orders), and `thermal_frequencies`; with `samples` it is the fine records' divided by S^2,
+    as `disk_spectrum`.  bands (up to 16 frequencies): the result also gains `thermal_bands` (n_bands, H, W) float32, the
+    unclamped band images (lt_shade_thermal; with `samples` the fine images resolved S x S -> 1 per plane by aa.resolve).
     One GPU, every row traced; sequences are not adaptively sampled."""
+    if thermal is not None and frequencies is None and bands is None:
+        raise ValueError("render_sequence: thermal needs frequencies= (the spectrum) or bands= (the band images)")
+    if thermal is None and (frequencies is not None or bands is not None):
+        raise ValueError("render_sequence: frequencies= and bands= belong to thermal=ThermalDisk(...)")
     if diskmap is not None and hotspot is not None:
         raise ValueError("render_sequence: a disk map together with a hot spot is out of scope; pass hotspot=None")
     if diskmap is not None and bfield is not None:
@@ -380,7 +390,9 @@ def render_sequence(source_image, metric, r_obs, fov, disk, hotspot, times, shap
     else:
         traced = ltrace.trace_disk_hits(cam, met, opts, d, max_images=m, want=("hits", "n_hits"))
     if diskmap is not None:
-        return _sequence_diskmap(traced, met, d, diskmap, times, dt, base, S, spectrum, baselines)
+        out = _sequence_diskmap(traced, met, d, diskmap, times, dt, base, S, spectrum, baselines)
+        _sequence_thermal(out, traced, met, d, thermal, frequencies, bands, S)
+        return out
     frames, rgba = [], []
     for t in times:
         if S is None:
@@ -419,6 +431,7 @@ def render_sequence(source_image, metric, r_obs, fov, disk, hotspot, times, shap
             k = 1 if S is None else S
             shape = (traced["hits"].shape[0] // k, traced["hits"].shape[1] // k)
             out.update(visibility_stokes=baselines.recentre(dyn, shape, k), disk_visibility_stokes=baselines.recentre(still, shape, k))
+    _sequence_thermal(out, traced, met, d, thermal, frequencies, bands, S)
     if S is not None:
         out["samples"] = S
     return out
@@ -437,6 +450,24 @@ def _sequence_spectra(out, traced, met, d, sp, dyn, S):
     line = ltrace.disk_spectrum(traced["hits"], traced["n_hits"], met, d, sp)
     scale = np.float64(1 if S is None else S * S)
     out.update(spectrum=dyn / scale, disk_spectrum=line / scale)
+
+
+def _sequence_thermal(out, traced, met, d, thermal, frequencies, bands, S):
+    """render_sequence's `thermal_spectrum` (in output-pixel units, as `disk_spectrum`) and `thermal_bands`."""
+    if thermal is None:
+        return
+    th = thermal.to_lt()
+    if frequencies is not None:
+        nu = np.asarray(frequencies, dtype=np.float64).ravel()
+        sp = ltrace.thermal_spectrum(traced["hits"], traced["n_hits"], met, d, th, thermal.flux, nu)
+        out.update(thermal_spectrum=sp / np.float64(1 if S is None else S * S), thermal_frequencies=nu)
+    if bands is not None:
+        th.split_orders = 0                                   # (the planes of a band image are its bands)
+        img = ltrace.shade_thermal(traced["hits"], traced["n_hits"], met, d, th, thermal.flux, bands)
+        if S is not None and img.shape[0]:
+            import aa
+            img = np.stack([aa.resolve(plane, S) for plane in img])
+        out["thermal_bands"] = img
 
 
 def _table_emitter(diskmap):
@@ -492,6 +523,43 @@ def spectrum_from_args(args):
     if args.spectrum[2] != int(args.spectrum[2]):
         raise ValueError("--spectrum: N_BINS must be a whole number")
     return Spectrum(args.spectrum[0], args.spectrum[1], int(args.spectrum[2]), split_orders=args.spectrum_orders)
+
+
+def thermal_from_args(args, disk=None, M=1.0, a=0.0):
+    """(disk.ThermalDisk, frequencies or None, bands or None) of --thermal T_MAX [F_COL] with --thermal-frequencies NU_MIN
+    NU_MAX N (log-spaced) and / or --thermal-bands NU ..., or None: the Novikov-Thorne disk of (M, a) from the ISCO to the
+    disk's outer edge.  Refused without a sequence and without the optically thin disk, as --spectrum is."""
+    from disk import ThermalDisk, THERMAL_MAX_BANDS, THERMAL_MAX_FREQS
+    if args.thermal is None:
+        if args.thermal_frequencies is not None or args.thermal_bands is not None:
+            raise ValueError("--thermal-frequencies / --thermal-bands need --thermal T_MAX [F_COL]")
+        return None
+    if args.hotspot is None and args.bfield is None and args.disk_map is None:
+        raise ValueError("--thermal shades the stored hits of a sequence; use it with --hotspot or --disk-map (and --disk-images N)")
+    if len(args.thermal) > 2:
+        raise ValueError("--thermal takes T_MAX [F_COL]")
+    if args.thermal_frequencies is None and args.thermal_bands is None:
+        raise ValueError("--thermal needs --thermal-frequencies NU_MIN NU_MAX N and / or --thermal-bands NU ...")
+    nu = None
+    if args.thermal_frequencies is not None:
+        lo, hi, n = args.thermal_frequencies
+        if n != int(n) or not 1 <= n <= THERMAL_MAX_FREQS:
+            raise ValueError(f"--thermal-frequencies: N must be a whole number, 1 ... {THERMAL_MAX_FREQS}")
+        if not (0.0 < lo <= hi and np.isfinite(hi)):
+            raise ValueError("--thermal-frequencies: 0 < NU_MIN <= NU_MAX, both finite")
+        nu = np.exp(np.linspace(np.log(lo), np.log(hi), int(n)))
+        nu[0], nu[-1] = (lo, hi) if n > 1 else (lo, lo)
+    bands = None
+    if args.thermal_bands is not None:
+        bands = np.asarray(args.thermal_bands, dtype=np.float64)
+        if bands.size > THERMAL_MAX_BANDS or not np.all((bands > 0.0) & np.isfinite(bands)):
+            raise ValueError(f"--thermal-bands: 1 ... {THERMAL_MAX_BANDS} frequencies, each finite and > 0")
+    if disk is None:
+        return None, nu, bands                                # (checked only: the table needs the disk's outer edge)
+    if not hasattr(disk, "max_images"):
+        raise ValueError("--thermal needs --disk-images N")
+    t_max, f_col = float(args.thermal[0]), float(args.thermal[1]) if len(args.thermal) == 2 else 1.0
+    return ThermalDisk.novikov_thorne(M, a, disk.r_out, t_max=t_max, f_col=f_col), nu, bands
 
 
 def baselines_from_args(args):
@@ -565,10 +633,14 @@ def main_sequence(args, disk):
     and the grid's edges as .npy.
     --visibility N U_MAX ANGLE_DEG [--visibility-orders]: also the complex visibilities of the moving emitter and of the disk
     on N baselines of 0 ... U_MAX cycles per pixel along ANGLE_DEG, and the baselines, as .npy; together with --bfield also
-    the polarized visibilities (I, Q, U per baseline) of the spot and of the disk."""
+    the polarized visibilities (I, Q, U per baseline) of the spot and of the disk.
+    --thermal T_MAX [F_COL] with --thermal-frequencies NU_MIN NU_MAX N and / or --thermal-bands NU ...: also the disk's thermal
+    continuum of a Novikov-Thorne flux profile -- its spectrum at N log-spaced frequencies with the frequencies, and the
+    unclamped band images -- as .npy."""
     from disk import BField, HotSpot
     spec = spectrum_from_args(args)
     base_lines = baselines_from_args(args)
+    thermal_from_args(args)                                   # (its refusals that need no disk come before the others')
     if args.disk_map is not None and args.hotspot is not None:
         raise ValueError("--disk-map: a map together with --hotspot is out of scope; use one of them")
     if args.disk_map is not None and args.bfield is not None:
@@ -592,9 +664,11 @@ def main_sequence(args, disk):
     else:
         spot, n = HotSpot(exposure=0.0), 1
     field = BField(*args.bfield, pol_frac=args.pol_frac) if args.bfield is not None else None
+    thermal, nu, bands = thermal_from_args(args, disk, args.M, args.a) or (None, None, None)
     out = render_sequence(None, metric, args.r_obs * metric.M, fov, disk, spot, t0 + dt * np.arange(n), shape=(height, width),
                           psi=(np.radians(args.psi_y), np.radians(args.psi_x)), theta_obs=np.radians(args.theta_obs), bfield=field,
-                          samples=args.samples, diskmap=dmap, spectrum=spec, baselines=base_lines)
+                          samples=args.samples, diskmap=dmap, spectrum=spec, baselines=base_lines, thermal=thermal, frequencies=nu,
+                          bands=bands)
     stem = args.output[:-4] if args.output.lower().endswith(".png") else args.output
     for i in range(n):
         write_png_rgba8(f"{stem}_{i:04d}.png", out["rgba"][i])
@@ -621,6 +695,15 @@ def main_sequence(args, disk):
               f"{stem}_visibility.npy (per time), {stem}_disk_visibility.npy (the disk's), {stem}_baselines.npy")
         if field is not None:
             print(f"Polarized visibilities (I, Q, U) -> {stem}_visibility_stokes.npy (per time), {stem}_disk_visibility_stokes.npy (the disk's)")
+    if thermal is not None:
+        if nu is not None:
+            np.save(stem + "_thermal_spectrum.npy", out["thermal_spectrum"])
+            np.save(stem + "_thermal_frequencies.npy", out["thermal_frequencies"])
+        if bands is not None:
+            np.save(stem + "_thermal_bands.npy", out["thermal_bands"])
+        print(f"Thermal continuum: Novikov-Thorne disk, t_max {thermal.t_max:g}, f_col {thermal.f_col:g} -> "
+              + ", ".join(([f"{stem}_thermal_spectrum.npy, {stem}_thermal_frequencies.npy"] if nu is not None else [])
+                          + ([f"{stem}_thermal_bands.npy"] if bands is not None else [])))
     if args.samples is not None:
         print(f"Supersampling: {args.samples} x {args.samples} rays per pixel, every frame resolved on the GPU")
     print(f"{'Hot spot' if dmap is None else 'Disk map' if dmap.texels.ndim == 2 else 'Disk movie'}: one trace ({out['stats']['integrate_ms']:.2f} ms), {n} frames -> {stem}_0000.png ..., light curve -> "
@@ -916,6 +999,14 @@ def build_parser():
                          "0 ... U_MAX (<= 0.5) cycles per pixel along ANGLE_DEG, about the frame's centre; writes them per time, the "
                          "disk's own and the baselines as .npy; with --bfield also the polarized ones (I, Q, U per baseline)")
     ap.add_argument("--visibility-orders", action="store_true", help="--visibility: one plane per image order instead of one for all")
+    ap.add_argument("--thermal", type=float, nargs="+", default=None, metavar="T_MAX [F_COL]",
+                    help="with --hotspot / --disk-map: the disk's thermal continuum from the stored hits, a Novikov-Thorne flux profile "
+                         "from the ISCO to the disk's outer edge with peak temperature T_MAX (as a frequency, k T / h) and "
+                         "colour-correction factor F_COL (default: 1)")
+    ap.add_argument("--thermal-frequencies", type=float, nargs=3, default=None, metavar=("NU_MIN", "NU_MAX", "N"),
+                    help="--thermal: the spectrum at N (1 ... 1024) log-spaced frequencies; writes it and the frequencies as .npy")
+    ap.add_argument("--thermal-bands", type=float, nargs="+", default=None, metavar="NU",
+                    help="--thermal: the unclamped image at each of up to 16 frequencies; writes them as one .npy (n_bands, H, W)")
     return ap
 
 
@@ -931,6 +1022,7 @@ if __name__ == "__main__":
         disk = ThinDisk(r_in=args.disk_rin, r_out=args.disk_rout, q=args.disk_q, exposure=args.disk_exposure)
     spectrum_from_args(args)                                  # (refuses --spectrum without a sequence)
     baselines_from_args(args)                                 # (and --visibility)
+    thermal_from_args(args)                                   # (and --thermal)
     if args.hotspot is not None or args.bfield is not None or args.disk_map is not None:
         main_sequence(args, disk)
         sys.exit(0)

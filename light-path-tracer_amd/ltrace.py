@@ -108,6 +108,16 @@ VISIBILITY_MAX_BASELINES, VISIBILITY_BLOCKS, VISIBILITY_BATCH_TERMS, VISIBILITY_
 VISIBILITY_STOKES_BATCH_PAIRS = 5
 
 
+class Thermal(C.Structure):
+    """lt_thermal: the range and size of a radial flux table, the temperature scale t_max (a frequency), the
+    colour-correction factor and the brightness of the disk's thermal continuum."""
+    _fields_ = [("r_min", C.c_double), ("r_max", C.c_double), ("t_max", C.c_double), ("f_col", C.c_double), ("exposure", C.c_double),
+                ("n_r", C.c_int32), ("split_orders", C.c_int32)]
+
+
+THERMAL_MAX_NODES, THERMAL_MAX_FREQS, THERMAL_MAX_BANDS = 65536, 1024, 16
+
+
 class BField(C.Structure):
     """lt_bfield: the field's components in the emitter's frame and the polarization fraction."""
     _fields_ = [("b_r", C.c_double), ("b_phi", C.c_double), ("b_z", C.c_double), ("pol_frac", C.c_double)]
@@ -370,6 +380,14 @@ SIGNATURES = {
     "lt_aa_adaptive_plan": (C.c_int, [C.POINTER(Camera), C.POINTER(Metric), C.POINTER(Opts), C.POINTER(AAAdaptive),
                                       C.POINTER(Disk), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
 }
+
+
+# the thermal continuum: (hits, n_hits, R, W, max_images, metric, disk, thermal, flux, nu, n_freq, out)
+SIGNATURES["lt_default_thermal"] = (None, [C.POINTER(Thermal)])
+for _name in ("lt_disk_thermal_spectrum", "lt_shade_thermal"):
+    for _suffix in ("", "_dev"):
+        SIGNATURES[_name + _suffix] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Metric), C.POINTER(Disk),
+                                                 C.POINTER(Thermal), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p])
 
 
 def _movie_signature(name):
@@ -1692,6 +1710,63 @@ def diskmap_spectrum_dev(d_hits, d_n_hits, rows, width, max_images, metric, disk
     """Device-pointer form of diskmap_spectrum (lt_diskmap_spectrum_dev); enqueues on the default stream."""
     _check(load().lt_diskmap_spectrum_dev(_p(d_hits), _p(d_n_hits), rows, width, max_images, C.byref(metric), C.byref(disk),
                                           C.byref(dmap), _p(d_texels), C.byref(spec), *_times(t_start, dt, n_times), _p(d_out)))
+
+
+# ---- thermal continuum (lt_disk_thermal_spectrum, lt_shade_thermal) -----------------------------------------------------------
+def default_thermal(**kw):
+    """lt_thermal with the library's defaults (r 6 ... 20, t_max 1, f_col 1, exposure 1, 2 nodes, not split); keywords override."""
+    t = Thermal()
+    load().lt_default_thermal(C.byref(t))
+    for k, v in kw.items():
+        setattr(t, k, v)
+    return t
+
+
+def _thermal_arrays(thermal, flux, nu, limit):
+    """(flux, nu) as the library reads them; a table that is not the struct's n_r, or more frequencies than an output is
+    sized for, never reach it."""
+    flux = np.ascontiguousarray(flux, dtype=np.float64)
+    if flux.shape != (int(thermal.n_r),):
+        raise ValueError(f"flux must be (n_r,) = ({int(thermal.n_r)},), got {flux.shape}")
+    nu = np.ascontiguousarray(nu, dtype=np.float64).ravel()
+    if nu.size > limit:
+        raise ValueError(f"at most {limit} frequencies, got {nu.size}")
+    return flux, nu
+
+
+def thermal_spectrum(hits, n_hits, metric, disk, thermal, flux, nu):
+    """The disk's thermal spectrum from stored hits (lt_disk_thermal_spectrum) -> (planes, n_freq) float64, the flux density
+    at the frequencies nu summed over all pixels and stored slots; plane j the image order j with thermal.split_orders."""
+    hits, nh = _hit_arrays(hits, n_hits)
+    R, W, m = hits.shape[:3]
+    flux, nu = _thermal_arrays(thermal, flux, nu, THERMAL_MAX_FREQS)
+    out = np.empty((min(m, DISK_MAX_IMAGES) if thermal.split_orders else 1, nu.size))
+    _check(load().lt_disk_thermal_spectrum(_np_ptr(hits), _np_ptr(nh), R, W, m, C.byref(metric), C.byref(disk), C.byref(thermal),
+                                           _np_ptr(flux), _np_ptr(nu), nu.size, _np_ptr(out)))
+    return out
+
+
+def thermal_spectrum_dev(d_hits, d_n_hits, rows, width, max_images, metric, disk, thermal, d_flux, d_nu, n_freq, d_out):
+    """Device-pointer form of thermal_spectrum (lt_disk_thermal_spectrum_dev); enqueues on the default stream."""
+    _check(load().lt_disk_thermal_spectrum_dev(_p(d_hits), _p(d_n_hits), rows, width, max_images, C.byref(metric), C.byref(disk),
+                                               C.byref(thermal), _p(d_flux), _p(d_nu), n_freq, _p(d_out)))
+
+
+def shade_thermal(hits, n_hits, metric, disk, thermal, flux, nu):
+    """The disk's thermal band images from stored hits (lt_shade_thermal) -> (n_bands, rows, W) float32, unclamped."""
+    hits, nh = _hit_arrays(hits, n_hits)
+    R, W, m = hits.shape[:3]
+    flux, nu = _thermal_arrays(thermal, flux, nu, THERMAL_MAX_BANDS)
+    out = np.empty((nu.size, R, W), dtype=np.float32)
+    _check(load().lt_shade_thermal(_np_ptr(hits), _np_ptr(nh), R, W, m, C.byref(metric), C.byref(disk), C.byref(thermal), _np_ptr(flux),
+                                   _np_ptr(nu), nu.size, _np_ptr(out)))
+    return out
+
+
+def shade_thermal_dev(d_hits, d_n_hits, rows, width, max_images, metric, disk, thermal, d_flux, d_nu, n_freq, d_out):
+    """Device-pointer form of shade_thermal (lt_shade_thermal_dev); enqueues on the default stream."""
+    _check(load().lt_shade_thermal_dev(_p(d_hits), _p(d_n_hits), rows, width, max_images, C.byref(metric), C.byref(disk), C.byref(thermal),
+                                       _p(d_flux), _p(d_nu), n_freq, _p(d_out)))
 
 
 # ---- visibilities (lt_disk_visibility, lt_hotspot_visibility, lt_diskmap_visibility) ---------------------------------------
