@@ -1369,6 +1369,92 @@ int lt_shade_thermal(const float *hits, const uint8_t *n_hits, int32_t R, int32_
                      const lt_metric *metric, const lt_disk *disk, const lt_thermal *thermal, const double *flux,
                      const double *nu, int32_t n_freq, float *out);
 
+/* ---- reverberation: the disk's response to a flash, a delay-energy transfer function ------------------------------- *
+ * Every product above asks what the disk looks like at an observer time.  X-ray timing asks the converse: a compact    *
+ * source above the hole flashes once -- when, and at what energy, does the disk's echo arrive?  The answer is the 2-D  *
+ * transfer function psi(tau, g): the stored hits binned by the redshift factor g AND by the delay tau between the      *
+ * direct flash and the echo through that hit.  Summed over tau it is the broadened line (lt_disk_spectrum's, with the  *
+ * emissivity below); summed over g the impulse response.  One more reduction over the records of lt_trace_disk_hits;   *
+ * nothing is traced again.  Of lt_disk only `exposure` is used; its q is not looked at beyond its refusal.             *
+ *                                                                                                                      *
+ * Emitter.  lt_transfer and two float64 tables of n_r nodes, node i at r_min + i (r_max - r_min) / (n_r - 1):          *
+ * delay[i], the coordinate time light takes from the source to the disk at that radius, and emis[i], what the disk     *
+ * re-emits there per unit of the flash, any non-negative profile.  The physics of the source lives in the tables alone *
+ * (disk.lamppost_tables builds them for a point source on the spin axis); t_ref, the direct flash's own arrival time   *
+ * at the camera, is subtracted from every delay.                                                                       *
+ *                                                                                                                      *
+ * The rule, per stored slot (the stored slots are the re-shades': the first min(n_hits, max_images), or the leading    *
+ * slots whose r is not NaN when n_hits is NULL), in float64 from the stored float32 (r, g, dt), in exactly these steps *
+ * -- each is one rounded operation or an explicit fma, whatever the compiler may contract:                             *
+ *   1. r = (double)r32, g = (double)g32, dt = (double)dt32.  The slot contributes nothing if g is NaN or g <= 0, if dt *
+ *      is NaN, or if r is off the table, !(r >= r_min && r <= r_max) (a NaN r included).                               *
+ *   2. v = (r - r_min) inv_dr, a subtraction and then a rounded product, with inv_dr = (n_r - 1) / (r_max - r_min)     *
+ *      computed once on the host;  i0 = min((int)v, n_r - 2);  w = v - i0, a subtraction of the rounded v.             *
+ *   3. eps = fma(w, emis[i0 + 1] - emis[i0], emis[i0]).  The slot contributes nothing where !(eps > 0).                *
+ *      t_ld = fma(w, delay[i0 + 1] - delay[i0], delay[i0]).                                                            *
+ *   4. tau = (t_ld + dt) - t_ref, two rounded operations.  Its bin is the spectrum's rule on the delay grid:           *
+ *          inv_dtau = n_tau / (tau_max - tau_min)          (computed once on the host)                                 *
+ *          k_tau = tau < tau_min ? 0 : tau >= tau_max ? n_tau + 1                                                      *
+ *                                    : 1 + min((int)floor((tau - tau_min) * inv_dtau), n_tau - 1)                      *
+ *      a subtraction followed by a multiplication.  Column 0 is the underflow, column n_tau + 1 the overflow, bin      *
+ *      k = 1 ... n_tau is half-open.  A NaN tau (a NaN table node) contributes nothing.  The bin of g, k_g, is         *
+ *      lt_spectrum's, unchanged ("energy-resolved light"), with its underflow and overflow columns.                    *
+ *   5. The weight is (exposure ((g g) (g g))) eps: g^4 bracketed as the disk's own intensity brackets it, then two     *
+ *      rounded products from the left.  A weight of exactly 0 is not added.                                            *
+ *                                                                                                                      *
+ * Output.  float64 (planes, n_tau + 2, n_bins + 2); planes is 1, or max_images with spec->split_orders: plane j then   *
+ * holds the hits stored in slot j.  Key = (plane (n_tau + 2) + k_tau) (n_bins + 2) + k_g.  An empty key is exactly     *
+ * +0.0.  The keys are capped: planes (n_tau + 2) (n_bins + 2) <= LT_TRANSFER_MAX_KEYS, which makes the                 *
+ * LT_SPECTRUM_BLOCKS partials exactly the spectra's workspace of LT_SPECTRUM_WORKSPACE_BYTES, in one batch.  A finer   *
+ * grid is several calls on adjacent delay ranges: the bin rule makes them tile exactly -- every tau falls into the     *
+ * same bin of the part as of the whole -- when the ranges share inv_dtau, each part's tau_min is the whole's tau_min   *
+ * plus a whole number of bins, and tau - tau_min and its product with inv_dtau are exact in both (tau_min = 0 and a    *
+ * bin width that is a power of two make it so).  Where the subtraction or the product rounds, a tau within that one    *
+ * rounding below an edge between two parts is in the whole's upper bin and in the lower part's last one: the part      *
+ * clamps at its end, the whole has no end there.  This is lt_spectrum's rule and as rare as a g on an edge's last bit. *
+ *                                                                                                                      *
+ * Order of every sum: the spectra's, word for word.  Workgroup b of LT_SPECTRUM_BLOCKS walks the chunks of 256 pixels  *
+ * p = 256 (b + c LT_SPECTRUM_BLOCKS) + i, c ascending.  Within a chunk, wavefront w = i div 64 adds, for every slot j, *
+ * the weights of a key over its 64 lanes l = i mod 64 with the butterfly l ^ 32, l ^ 16, ... l ^ 1 (lanes without that *
+ * key add +0.0, which changes no bit).  The owner of a key adds these sums to the workgroup's accumulator ordered by   *
+ * w, then j; the final stage adds the LT_SPECTRUM_BLOCKS partials per key, b ascending.  The order depends on R, W and *
+ * max_images alone: not on how the kernel divides the key space among workgroups, nor on which other keys exist, so a  *
+ * key's bits are the same in a small grid and inside a large one.  No floating-point atomics anywhere.                 *
+ *                                                                                                                      *
+ * Supersampled records.  Called with the fine records (R S, W S) the result divided by S^2 is in output-pixel units,   *
+ * as the spectra's (image_lens.render_sequence does so).                                                               *
+ *                                                                                                                      *
+ * Refusals, in this order: those of lt_disk_spectrum up to and including the disk's q / exposure; the grid's (a null   *
+ * spec, the g range, n_bins); then LT_ERR_INVALID_ARG for a null transfer; the tau range (finite, tau_min < tau_max);  *
+ * n_tau; n_r; the r range (0 < r_min < r_max, finite); a non-finite t_ref; a null delay / emis; the key cap; and a     *
+ * null out.  The outputs of a refused call are untouched.  disk.TransferGrid / disk.transfer_bin / disk.disk_transfer  *
+ * (Python) state the rule in numpy; disk.Lamppost / disk.lamppost_tables build the tables of a lamp-post corona.       *
+ *                                                                                                                      *
+ * Out of scope: off-axis or extended coronae, the ionisation state and a rest-frame reflection spectrum other than a   *
+ * line, returning radiation, the response of the spot, the map or the movie, polarized or per-pixel responses,         *
+ * logarithmic delay grids, lt_render_multi and the multi-process path, adaptive sampling.                              */
+#define LT_TRANSFER_MAX_TAU 1024
+#define LT_TRANSFER_MAX_KEYS 32768
+
+typedef struct lt_transfer {
+    double tau_min, tau_max; /* the delay grid's ends, finite, tau_min < tau_max (tau_min may be negative) */
+    int32_t n_tau;           /* 1 ... LT_TRANSFER_MAX_TAU */
+    int32_t n_r;             /* nodes of the two tables, 2 ... LT_THERMAL_MAX_NODES */
+    double r_min, r_max;     /* node i sits at r_min + i (r_max - r_min)/(n_r - 1); 0 < r_min < r_max, finite */
+    double t_ref;            /* subtracted from every delay: the direct flash's own arrival time at the camera; finite */
+} lt_transfer;
+void lt_default_transfer(lt_transfer *transfer); /* tau 0 ... 256, 64 bins, 2 nodes on 6 ... 20, t_ref 0 */
+
+/* The _dev form takes DEVICE pointers for the records, the two tables and the output and enqueues on the default
+ * stream; the other HOST pointers, staged like lt_disk_thermal_spectrum.  delay, emis: transfer->n_r float64 each.
+ * out: (planes, n_tau + 2, n_bins + 2) float64. */
+int lt_disk_transfer_dev(const float *d_hits, const uint8_t *d_n_hits, int32_t R, int32_t W, int32_t max_images,
+                         const lt_metric *metric, const lt_disk *disk, const lt_spectrum *spec, const lt_transfer *transfer,
+                         const double *d_delay, const double *d_emis, double *d_out);
+int lt_disk_transfer(const float *hits, const uint8_t *n_hits, int32_t R, int32_t W, int32_t max_images,
+                     const lt_metric *metric, const lt_disk *disk, const lt_spectrum *spec, const lt_transfer *transfer,
+                     const double *delay, const double *emis, double *out);
+
 /* ---- supersampled (anti-aliased) frames, resolved on the GPU ------------------------------------------- *
  * Every frame above is one ray per pixel, taken at the pixel's corner.  These entry points trace S x S rays per       *
  * pixel and write only the resolved pixels: nothing of the S^2 times larger frame crosses PCIe or stays in memory.    *

@@ -1,0 +1,162 @@
+// lt_transfer.hpp -- the disk's reverberation response from the stored hits of lt_trace_disk_hits (include/ltrace.h,
+// "reverberation"): a histogram of float64 weights over the keys (image order, bin of the delay tau, bin of g), the
+// 2-D transfer function of a flash above the disk.  The spectra's reduction (lt_spectrum.hpp) over a key space eight
+// times the one spectrum_partial keeps in LDS: up to TR_MAX_KEYS = 32 768 keys against SP_MAX_KEYS = 4 112.
+//
+// First stage (k_disk_transfer_partial; grid (SP_BLOCKS, key tiles), 256 work-items).  Tile T owns the keys
+// [TR_TILE T, TR_TILE (T + 1)).  A workgroup walks its pixels in chunks of 256 in the light curve's stride order and
+// evaluates the header's steps 1 to 5 for every stored slot of its chunk -- a table interpolation and four products,
+// repeated once per tile -- and then runs the spectrum's two phases on the slots whose key lies in its tile.
+//   Phase one: slot by slot a wavefront adds the weights of every key of the tile the slot holds with the butterfly
+//   over the lanes and appends one entry (key - TR_TILE T, sum) per key to its segment of LDS.
+//   Phase two: work-item i alone owns the tile's keys = i (mod 256); every work-item scans the four segments in order
+//   -- all lanes read the same entry, a broadcast -- and adds the entries it owns.
+// After the last chunk the workgroup writes its accumulators into its partial, at the tile's place.
+// Final stage: k_sum_blocks of lt_spectrum.hpp as it is, row = the keys of the call.
+//
+// Why a key's bits do not depend on the tiling.  The butterfly for a key adds the weights of the lanes that hold this
+// key and +0.0 for every other lane, whatever those lanes hold; a slot's keys outside the tile are therefore simply
+// absent lanes, as they are for every other key of the slot inside the tile.  The merge of a key is complete -- all of
+// a wavefront's lanes with that key in one butterfly, in the one workgroup that owns the key -- and its entries reach
+// the owner in the order (wavefront, slot) in every tiling.  What must not happen is a key merged in parts (two
+// entries of one wavefront and slot for one key): the sum of the parts brackets differently.  The loop below takes
+// the leader's key and removes every lane with that key from `todo`, as spectrum_partial does.
+//
+// Phase one is written again here and not shared with spectrum_partial: that function's entry carries the key itself
+// and its loop has no tile, and splitting it would recompile the three spectrum kernels.
+//
+// LDS is sized by the launch (transfer_lds_bytes): TR_TILE x 8 (accumulators) + 4 x 64 max_images x (8 + 4) (entries)
+// + 16 = 57 360 B at eight images, 42 000 B at three: two workgroups share a CU's 160 KiB at eight images, three at
+// three.  The scan reads four keys per ds_read_b128; the entries' keys start 16-byte aligned (TR_TILE x 8 and
+// 4 x 64 max_images x 8 are multiples of 16) and every segment is 256 max_images bytes long.  The two tables are read
+// through __restrict__ global pointers: at most 65 536 x 16 B, they stay in L2.
+#pragma once
+#include "lt_spectrum.hpp"
+#include "lt_thermal.hpp"
+
+namespace lt {
+
+constexpr int TR_MAX_TAU = 1024;   // LT_TRANSFER_MAX_TAU
+constexpr int TR_MAX_KEYS = 32768; // LT_TRANSFER_MAX_KEYS
+constexpr int TR_TILE = 4096;      // keys one workgroup accumulates
+
+inline size_t transfer_lds_bytes(int max_images) { return (size_t)TR_TILE * 8 + (size_t)4 * 64 * max_images * 12 + 16; }
+static_assert((TR_TILE * 8 + 4 * 64 * DISK_MAX_IMAGES * 12 + 16) * 2 <= 160 * 1024, "two workgroups share a CU at eight images");
+static_assert(TR_TILE % 256 == 0 && TR_MAX_KEYS % TR_TILE == 0, "an owner's keys are those = its index (mod 256) in every tile");
+
+struct TransferShade {
+    double tau_min, tau_max, inv_dtau; // inv_dtau = n_tau / (tau_max - tau_min), from the host
+    double r_min, r_max, inv_dr;       // inv_dr = (n_r - 1) / (r_max - r_min), from the host
+    double t_ref, exposure;
+    int n_tau, n_r;
+};
+
+// Step 4's delay, (t_ld + dt) - t_ref: two rounded operations (t_ld comes from an explicit fma, which nothing here may
+// absorb).
+__device__ __forceinline__ double transfer_delay(double t_ld, double dt, double t_ref)
+{
+#pragma clang fp contract(off)
+    const double arrival = t_ld + dt;
+    return arrival - t_ref;
+}
+
+// Column of a delay: 0 the underflow, n_tau + 1 the overflow, else the half-open bin; spectrum_bin's rule on the delay
+// grid.  A subtraction and then a multiplication: nothing to contract.  tau is not NaN here.
+__device__ __forceinline__ int transfer_bin(const TransferShade &tr, double tau)
+{
+    if (tau < tr.tau_min) return 0;
+    if (tau >= tr.tau_max) return tr.n_tau + 1;
+    const int k = (int)floor((tau - tr.tau_min) * tr.inv_dtau);
+    return 1 + max(min(k, tr.n_tau - 1), 0);
+}
+
+// The header's steps 1 to 5 for one stored slot: whether it contributes, and then its columns and its weight.  Every
+// operation is rounded as the header states it: v's product is kept from fusing into the subtraction that makes w (the
+// empty asm, as in thermal_coeff), the interpolations are explicit fmas, the weight is products alone.  The index is
+// clamped before it is used, whatever r holds.
+__device__ __forceinline__ bool transfer_slot(const TransferShade &tr, const SpectrumGrid &sg, const double *__restrict__ delay,
+                                              const double *__restrict__ emis, const float *rec, int *k_tau, int *k_g, double *weight)
+{
+    const double r = (double)rec[0], g = (double)rec[2], dt = (double)rec[3];
+    if (!(g > 0.0) || dt != dt || !(r >= tr.r_min) || !(r <= tr.r_max)) return false; // (a NaN fails every comparison)
+    double v = (r - tr.r_min) * tr.inv_dr;
+    asm("" : "+v"(v));
+    const int i0 = max(min((int)v, tr.n_r - 2), 0);
+    const double w = v - (double)i0;
+    const double e0 = emis[i0], e1 = emis[i0 + 1];
+    const double eps = fma(w, e1 - e0, e0);
+    if (!(eps > 0.0)) return false;
+    const double d0 = delay[i0], d1 = delay[i0 + 1];
+    const double tau = transfer_delay(fma(w, d1 - d0, d0), dt, tr.t_ref);
+    if (tau != tau) return false;
+    *k_tau = transfer_bin(tr, tau);
+    *k_g = spectrum_bin(sg, rec[2]);
+    const double g2 = g * g;
+    *weight = tr.exposure * (g2 * g2) * eps; // (exposure ((g g) (g g))) eps: disk_intensity's bracketing
+    return true;
+}
+
+__global__ void __launch_bounds__(256) k_disk_transfer_partial(const float *__restrict__ hits, const uint8_t *__restrict__ n_hits, int64_t n_px,
+                                                               int max_images, TransferShade tr, SpectrumGrid sg,
+                                                               const double *__restrict__ delay, const double *__restrict__ emis,
+                                                               int n_keys, double *__restrict__ partial)
+{
+    const int t = (int)threadIdx.x, wave = t >> 6, lane = t & 63;
+    const int cols = sg.n_bins + 2, rows = tr.n_tau + 2;
+    const int first = (int)blockIdx.y * TR_TILE; // this tile's keys: first ... first + TR_TILE - 1
+    const int seg = 64 * max_images;             // entries of one wavefront's segment: at most one per lane and slot
+    double *sh_acc = (double *)sp_lds, *sh_w = sh_acc + TR_TILE;
+    int *sh_key = (int *)(sh_w + 4 * seg), *sh_cnt = sh_key + 4 * seg;
+    for (int k = t; k < TR_TILE; k += 256) sh_acc[k] = 0.0;
+    for (int64_t base = (int64_t)blockIdx.x * 256; base < n_px; base += (int64_t)256 * SP_BLOCKS) {
+        // phase one: this wavefront's entries, slot by slot, one per key of this tile
+        const int64_t p = base + t;
+        const float *rec = hits + (p < n_px ? p : 0) * max_images * 4;
+        const int ns = p < n_px ? stored_slots(rec, n_hits, p, max_images) : 0;
+        int cnt = 0;
+        for (int j = 0; j < max_images; ++j) {
+            double w = 0.0;
+            int key = -1;
+            if (j < ns) {
+                int k_tau, k_g;
+                if (transfer_slot(tr, sg, delay, emis, rec + j * 4, &k_tau, &k_g, &w))
+                    key = min(((sg.planes > 1 ? j * rows : 0) + k_tau) * cols + k_g, n_keys - 1) - first;
+            }
+            // (a weight of exactly 0 is not added; a key of another tile is another workgroup's: an absent lane here)
+            const bool has = !(w == 0.0) && key >= 0 && key < TR_TILE;
+            for (uint64_t todo = __ballot(has); todo;) {
+                const int leader = __ffsll((unsigned long long)todo) - 1;
+                const int k = __shfl(key, leader);
+                const bool mine = has && key == k;
+                const double sum = wave_sum(mine ? w : 0.0);
+                if (lane == leader) {
+                    sh_key[wave * seg + cnt] = k;
+                    sh_w[wave * seg + cnt] = sum;
+                }
+                ++cnt;
+                todo &= ~__ballot(mine);
+            }
+        }
+        if (lane == 0) sh_cnt[wave] = cnt;
+        __syncthreads();
+        // phase two: the owner of a key adds its entries in order
+        for (int s = 0; s < 4; ++s) {
+            const int n = sh_cnt[s];
+            const int *kk = sh_key + s * seg;
+            const double *ww = sh_w + s * seg;
+            for (int e = 0; e < n; e += 4) {
+                const int4 k4 = *(const int4 *)(kk + e);
+                if ((k4.x & 255) == t) sh_acc[k4.x] += ww[e]; // (e < n)
+                if (e + 1 < n && (k4.y & 255) == t) sh_acc[k4.y] += ww[e + 1];
+                if (e + 2 < n && (k4.z & 255) == t) sh_acc[k4.z] += ww[e + 2];
+                if (e + 3 < n && (k4.w & 255) == t) sh_acc[k4.w] += ww[e + 3];
+            }
+        }
+        __syncthreads();
+    }
+    __syncthreads(); // (a workgroup without a chunk: the zeroes above)
+    double *mine = partial + (int64_t)blockIdx.x * n_keys + first;
+    for (int k = t; k < TR_TILE && first + k < n_keys; k += 256) mine[k] = sh_acc[k];
+}
+
+} // namespace lt

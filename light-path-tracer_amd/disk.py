@@ -30,6 +30,11 @@ The thermal continuum gives the disk a temperature: novikov_thorne_flux is the r
 ThermalDisk a tabulated flux profile with its temperature scale, thermal_coeffs the rule that makes a stored hit a
 blackbody, and thermal_spectrum / shade_thermal the multi-colour blackbody spectrum and the band images
 (lt_disk_thermal_spectrum, lt_shade_thermal).
+
+Reverberation bins the records by delay as well as by g: TransferGrid is the delay grid, transfer_bin its bin rule and
+disk_transfer the delay-energy transfer function of a flash above the disk (lt_disk_transfer); Lamppost / lamppost_tables
+trace a point source on the spin axis to the two radial tables the rule reads, and impulse_response, reverberation_line
+and lag_frequency reduce a transfer function further.
 """
 from dataclasses import dataclass
 from typing import Optional
@@ -1228,3 +1233,271 @@ def shade_thermal(hits, n_hits, thermal, nu):
             total = total + np.where(emits[..., j], thermal_term(f, A, np.where(emits[..., j], c[..., j], 1.0)), 0.0)
         out[b] = (((f * f) * f) * total).astype(np.float32)
     return out
+
+
+# ---- reverberation (lt_disk_transfer) ---------------------------------------------------------------------------------------------
+TRANSFER_MAX_TAU, TRANSFER_MAX_KEYS = 1024, 32768
+
+
+@dataclass
+class TransferGrid:
+    """A linear grid in the delay tau between the direct flash and its echo (include/ltrace.h, "reverberation"): n_tau
+    half-open bins on [tau_min, tau_max), an underflow row before them and an overflow row after.  tau_min may be negative."""
+    tau_min: float = 0.0
+    tau_max: float = 256.0
+    n_tau: int = 64
+
+    def __post_init__(self):
+        if not (np.isfinite(self.tau_min) and np.isfinite(self.tau_max) and self.tau_min < self.tau_max):
+            raise ValueError("TransferGrid needs tau_min < tau_max, both finite")
+        if int(self.n_tau) != self.n_tau or not 1 <= self.n_tau <= TRANSFER_MAX_TAU:
+            raise ValueError(f"TransferGrid n_tau must be 1 ... {TRANSFER_MAX_TAU}")
+        self.tau_min, self.tau_max, self.n_tau = float(self.tau_min), float(self.tau_max), int(self.n_tau)
+
+    def edges(self):
+        """The n_tau + 1 edges of the bins proper, tau_min ... tau_max (rows 1 ... n_tau of a transfer function)."""
+        e = self.tau_min + (self.tau_max - self.tau_min) * np.arange(self.n_tau + 1) / self.n_tau
+        e[-1] = self.tau_max
+        return e
+
+    def centres(self):
+        e = self.edges()
+        return 0.5 * (e[:-1] + e[1:])
+
+    def to_lt(self, r_min, r_max, n_r, t_ref):
+        """The lt_transfer struct of this grid and of tables of n_r nodes on [r_min, r_max] (ltrace.Transfer)."""
+        import ltrace
+        return ltrace.default_transfer(tau_min=self.tau_min, tau_max=self.tau_max, n_tau=self.n_tau, n_r=int(n_r), r_min=float(r_min),
+                                       r_max=float(r_max), t_ref=float(t_ref))
+
+
+def transfer_bin(tau, grid):
+    """The header's step 4, vectorised: the row (int64) of every float64 delay; 0 the underflow, n_tau + 1 the overflow,
+    -1 for a NaN (it contributes nothing)."""
+    x = np.asarray(tau, dtype=np.float64)
+    inv_dtau = grid.n_tau / (grid.tau_max - grid.tau_min)
+    nan = np.isnan(x)
+    with np.errstate(invalid="ignore", over="ignore"):
+        inner = np.floor((np.where(nan | np.isinf(x), grid.tau_min, x) - grid.tau_min) * inv_dtau)
+    k = 1 + np.minimum(np.clip(inner, 0, grid.n_tau).astype(np.int64), grid.n_tau - 1)
+    k = np.where(x < grid.tau_min, 0, np.where(x >= grid.tau_max, grid.n_tau + 1, k))
+    return np.where(nan, -1, k)
+
+
+def transfer_slots(hits, n_hits, exposure, spec, grid, r_min, r_max, delay, emis, t_ref):
+    """The header's steps 1 to 5 for every slot of hits (..., max_images, 4) float32 -> (on, k_tau, k_g, weight), each
+    (..., max_images): which slots contribute, their row and column, and their weight (0 where nothing contributes).  Every
+    operation is the header's, in its order and rounded as there (the interpolations by fma)."""
+    h = np.asarray(hits, dtype=np.float32)
+    m = h.shape[-2]
+    r, g, dt = h[..., 0].astype(np.float64), h[..., 2].astype(np.float64), h[..., 3].astype(np.float64)
+    delay, emis = np.asarray(delay, dtype=np.float64), np.asarray(emis, dtype=np.float64)
+    n_r = delay.size
+    if delay.shape != (n_r,) or emis.shape != (n_r,) or n_r < 2:
+        raise ValueError("delay and emis must both be (n_r,), n_r >= 2")
+    r_min, r_max, t_ref, exposure = float(r_min), float(r_max), float(t_ref), float(exposure)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        on = (_stored(h, n_hits)[..., None] > np.arange(m)) & (g > 0.0) & ~np.isnan(dt) & (r >= r_min) & (r <= r_max)      # step 1
+        inv_dr = float(n_r - 1) / (r_max - r_min)
+        v = (np.where(on, r, r_min) - r_min) * inv_dr                                                                    # step 2
+        i0 = np.clip(v.astype(np.int64), 0, n_r - 2)
+        w = v - i0.astype(np.float64)
+        eps = fma(w, emis[i0 + 1] - emis[i0], emis[i0])                                                                  # step 3
+        on = on & (eps > 0.0)
+        t_ld = fma(w, delay[i0 + 1] - delay[i0], delay[i0])
+        tau = (t_ld + np.where(on, dt, 0.0)) - t_ref                                                                     # step 4
+        k_tau = transfer_bin(tau, grid)
+        on = on & (k_tau >= 0)
+        k_g = spectrum_bin(h[..., 2], spec)
+        g2 = g * g
+        weight = np.where(on, exposure * (g2 * g2) * np.where(on, eps, 0.0), 0.0)                                        # step 5
+        on = on & ~(weight == 0.0)
+    return on, np.where(on, k_tau, 0), np.where(on, k_g, 0), weight
+
+
+def disk_transfer(hits, n_hits, exposure, spec, grid, r_min, r_max, delay, emis, t_ref):
+    """lt_disk_transfer restated: the delay-energy transfer function, (planes, n_tau + 2, n_bins + 2) float64 -- per stored
+    slot exposure g^4 eps(r) added to the key (image order, row of tau = t_ld(r) + dt - t_ref, column of g); the order of
+    the sums is numpy's, not the kernel's.  planes is 1, or max_images with spec.split_orders."""
+    on, k_tau, k_g, weight = transfer_slots(hits, n_hits, exposure, spec, grid, r_min, r_max, delay, emis, t_ref)
+    m = on.shape[-1]
+    rows, cols, planes = grid.n_tau + 2, spec.n_bins + 2, spec.planes(m)
+    if planes * rows * cols > TRANSFER_MAX_KEYS:
+        raise ValueError(f"disk_transfer: planes (n_tau + 2) (n_bins + 2) = {planes * rows * cols} keys exceed {TRANSFER_MAX_KEYS}")
+    plane = np.broadcast_to(np.arange(m), on.shape) if spec.split_orders else np.zeros(on.shape, dtype=np.int64)
+    key = ((plane * rows + k_tau) * cols + k_g)[on]
+    return np.bincount(key, weights=weight[on], minlength=planes * rows * cols).reshape(planes, rows, cols)
+
+
+def impulse_response(tf):
+    """A transfer function summed over g: (..., n_tau + 2), the echo's light per delay row (both underflows included)."""
+    return np.asarray(tf, dtype=np.float64).sum(axis=-1)
+
+
+def reverberation_line(tf):
+    """A transfer function summed over tau: (..., n_bins + 2), the broadened line of the same emissivity."""
+    return np.asarray(tf, dtype=np.float64).sum(axis=-2)
+
+
+def lag_frequency(tf, grid, freqs, g_lo, g_hi, reflection_fraction=1.0):
+    """The lag-frequency spectrum of the band of g columns [g_lo, g_hi) of a transfer function against the flash itself:
+    arg(1 + R FT[psi](f)) / (2 pi f), psi the band's response over the delay bins proper divided by its sum, R the
+    reflection fraction and FT a plain sum over the bin centres, sum_k psi_k exp(2 pi i f tau_k).  Planes are added.
+    -> (len(freqs),) float64; a positive lag is the echo trailing the flash."""
+    tf = np.asarray(tf, dtype=np.float64)
+    tf = tf.reshape((-1,) + tf.shape[-2:]).sum(axis=0)
+    psi = tf[1:-1, int(g_lo):int(g_hi)].sum(axis=1)
+    if not psi.sum() > 0.0:
+        raise ValueError("lag_frequency: the band holds no light on the delay grid")
+    psi = psi / psi.sum()
+    f = np.asarray(freqs, dtype=np.float64).ravel()
+    ft = (psi[None, :] * np.exp(2j * np.pi * f[:, None] * grid.centres()[None, :])).sum(axis=1)
+    return np.angle(1.0 + float(reflection_fraction) * ft) / (2.0 * np.pi * f)
+
+
+@dataclass
+class Lamppost:
+    """A point source on the spin axis of a Kerr hole (M, a) at Boyer-Lindquist radius h, at rest and isotropic in the
+    local static frame: the lamp-post corona.  Its photons have p_phi = 0 exactly; they are launched from (r = h, theta =
+    theta0) with a small theta0 -- the axis itself is a coordinate singularity -- at local angles delta from the outward
+    radial direction and integrated with the metric's own 8-D geodesic_equations (metrics.Kerr), host-side float64.
+    n_r, n_rays: the size of the tables render_sequence asks for and the rays they are interpolated from."""
+    M: float = 1.0
+    a: float = 0.0
+    h: float = 6.0
+    theta0: float = 1e-4                                       # (the source sits h theta0 off the axis: the delays move by that much)
+    rtol: float = 1e-10
+    n_r: int = 256
+    n_rays: int = 128
+
+    def __post_init__(self):
+        self.M, self.a, self.h = float(self.M), float(self.a), float(self.h)
+        if not (self.M > 0.0 and abs(self.a) <= self.M):
+            raise ValueError("Lamppost needs M > 0 and |a| <= M")
+        if not self.h > 1.05 * (self.M + np.sqrt(self.M * self.M - self.a * self.a)):
+            raise ValueError("Lamppost: h must lie outside the horizon")
+
+    def _metric(self):
+        from metrics import Kerr
+        return Kerr(M=self.M, a=self.a)
+
+    def lapse(self):
+        """sqrt(Delta(h) / (h^2 + a^2)): the source's clock against coordinate time, its photons' E_infinity / E_local."""
+        return float(np.sqrt((self.h * self.h - 2.0 * self.M * self.h + self.a * self.a) / (self.h * self.h + self.a * self.a)))
+
+    def initial_state(self, cos_delta):
+        """The 8-D state (t, r, theta, phi, p_t, p_r, p_theta, p_phi) of the photon with E = 1 emitted at the local angle
+        delta from the outward radial direction, in the zero-angular-momentum frame at (h, theta0) -- the static frame on the
+        axis: p^(r) = E_loc cos delta, p^(theta) = E_loc sin delta, p^(phi) = 0."""
+        M, a, r, th = self.M, self.a, self.h, self.theta0
+        c = float(cos_delta)
+        s = np.sqrt(max(1.0 - c * c, 0.0))
+        Sigma = r * r + a * a * np.cos(th) ** 2
+        Delta = r * r - 2.0 * M * r + a * a
+        A = (r * r + a * a) ** 2 - a * a * Delta * np.sin(th) ** 2
+        e_loc = np.sqrt(A / (Sigma * Delta))
+        return [0.0, r, th, 0.0, -1.0, c * e_loc * np.sqrt(Sigma / Delta), s * e_loc * np.sqrt(Sigma), 0.0]
+
+    def ray(self, cos_delta, r_far, to_equator=True):
+        """solve_ivp's result for one photon: integrated until it crosses the equator downwards (to_equator), passes r_far
+        outwards, or comes within 2 % of the horizon.  t_events: [equator crossings, r_far crossings, captures]."""
+        from scipy.integrate import solve_ivp
+        met = self._metric()
+        equator = lambda lam, y: y[2] - 0.5 * np.pi
+        equator.terminal, equator.direction = bool(to_equator), 1.0
+        far = lambda lam, y: y[1] - r_far
+        far.terminal, far.direction = True, 1.0
+        captured = lambda lam, y: y[1] - 1.02 * met.r_plus
+        captured.terminal, captured.direction = True, -1.0
+        return solve_ivp(met.geodesic_equations, (0.0, 50.0 * (r_far + self.h)), self.initial_state(cos_delta), method="DOP853",
+                         rtol=self.rtol, atol=1e-3 * self.rtol, events=(equator, far, captured))
+
+    def crossing(self, cos_delta, r_far):
+        """(r, t) of the photon's first crossing of the equatorial plane, or (nan, nan) if it escapes or is captured first."""
+        sol = self.ray(cos_delta, r_far)
+        if sol.t_events[0].size == 0:
+            return np.nan, np.nan
+        y = sol.y_events[0][0]
+        return float(y[1]), float(y[0])
+
+    def illumination(self, r_min, r_max, n_rays=None):
+        """(cos delta, r, t), each (n_rays,): n_rays photons uniform in cos delta whose equatorial crossings cover [r_min,
+        r_max], r ascending.  A coarse fan over all directions brackets the range first."""
+        n_rays = int(self.n_rays if n_rays is None else n_rays)
+        r_far = 4.0 * max(float(r_max), self.h) + 100.0 * self.M
+        coarse = np.linspace(-1.0, 1.0, 131)[1:-1]
+        rc = np.array([self.crossing(c, r_far)[0] for c in coarse])
+        inner = np.flatnonzero(rc <= r_min)
+        if inner.size == 0:
+            raise ValueError("Lamppost: no photon reaches the disk inside r_min")
+        lo = int(inner[-1])
+        outer = np.flatnonzero((rc >= r_max) & (np.arange(rc.size) > lo))
+        if outer.size == 0:
+            raise ValueError("Lamppost: no photon reaches the disk beyond r_max")
+        hi = int(outer[0])
+        if np.any(np.isnan(rc[lo:hi + 1])) or np.any(np.diff(rc[lo:hi + 1]) <= 0.0):
+            raise ValueError("Lamppost: the crossing radius is not monotone in cos delta over the table's range")
+        c = np.linspace(coarse[lo], coarse[hi], n_rays)
+        rt = np.array([self.crossing(x, r_far) for x in c])
+        if np.any(np.isnan(rt)) or np.any(np.diff(rt[:, 0]) <= 0.0):
+            raise ValueError("Lamppost: the crossing radius is not monotone in cos delta over the table's range")
+        return c, rt[:, 0], rt[:, 1]
+
+    def tables(self, r_min, r_max, n_r=None, n_rays=None):
+        """(delay, emis), each (n_r,) float64, on the uniform nodes of [r_min, r_max]: lamppost_tables of this source."""
+        return lamppost_tables(self.M, self.a, self.h, r_min, r_max, self.n_r if n_r is None else n_r, n_rays=n_rays, source=self)
+
+    def t_ref(self, r_obs, theta_obs):
+        """The direct flash's arrival time at the camera at (r_obs, theta_obs): the coordinate time of the photon of the same
+        family whose polar angle on reaching r = r_obs is theta_obs, found by brentq on cos delta."""
+        from scipy.optimize import brentq
+        r_obs, theta_obs = float(r_obs), float(theta_obs)
+        if not r_obs > self.h:
+            raise ValueError("Lamppost.t_ref: the camera must lie outside the source's radius")
+        arrival = {}
+
+        def miss(c):
+            sol = self.ray(c, r_obs, to_equator=False)
+            if sol.t_events[1].size == 0:
+                return np.pi                                   # (captured: as far from the axis as an angle gets)
+            y = sol.y_events[1][0]
+            arrival[c] = float(y[0])
+            return float(y[2]) - theta_obs
+
+        hi = 1.0
+        if miss(hi) >= 0.0:
+            return arrival[hi]                                 # (a camera on the axis itself)
+        lo = hi
+        while miss(lo) < 0.0:
+            hi, lo = lo, lo - 0.05
+            if lo <= -1.0:
+                raise ValueError("Lamppost.t_ref: no direct ray reaches the camera")
+        c = brentq(miss, lo, hi, xtol=1e-14, rtol=1e-14)
+        miss(c)
+        return arrival[c]
+
+
+def lamppost_tables(M, a, h, r_min, r_max, n_r, n_rays=None, source=None):
+    """The two float64 tables of lt_disk_transfer for a lamp-post corona (Lamppost) on the n_r uniform nodes of [r_min,
+    r_max] -> (delay, emis): delay the coordinate time from the source to the disk at the node, interpolated from the
+    rays' crossings; emis = g_ld^2 |d cos delta / dr| / (gamma sqrt(g_rr g_phiphi)) at the equator -- the photons the ring
+    [r, r + dr] receives per proper area of the orbiting gas, each shifted by g_ld = u^t(r) sqrt(Delta(h) / (h^2 + a^2)) in
+    energy and again in rate -- with gamma the Lorentz factor of the Keplerian gas against the zero-angular-momentum
+    frame.  The normalisation is free: the disk's exposure sets it.  The interpolation is monotone cubic (pchip) in r."""
+    from scipy.interpolate import PchipInterpolator
+    src = source if source is not None else Lamppost(M, a, h)
+    M, a = src.M, src.a
+    r_min, r_max, n_r = float(r_min), float(r_max), int(n_r)
+    c, rr, tt = src.illumination(r_min, r_max, n_rays)
+    nodes = r_min + np.arange(n_r) * (r_max - r_min) / (n_r - 1)
+    nodes[-1] = min(nodes[-1], rr[-1])                        # (rounding of the last node, inside the fan's last crossing)
+    delay = PchipInterpolator(rr, tt)(nodes)
+    dc_dr = PchipInterpolator(rr, c).derivative()(nodes)
+    Delta = nodes * nodes - 2.0 * M * nodes + a * a
+    A = (nodes * nodes + a * a) ** 2 - a * a * Delta
+    g_rr, g_pp = nodes * nodes / Delta, A / (nodes * nodes)
+    v = (omega(M, a, nodes) - 2.0 * M * a * nodes / A) * np.sqrt(g_pp) / np.sqrt(nodes * nodes * Delta / A)
+    gamma = 1.0 / np.sqrt(1.0 - v * v)
+    g_ld = u_t(M, a, nodes) * src.lapse()
+    emis = g_ld * g_ld * np.abs(dc_dr) / (gamma * np.sqrt(g_rr * g_pp))
+    return np.ascontiguousarray(delay), np.ascontiguousarray(emis)

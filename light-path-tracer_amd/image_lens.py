@@ -304,7 +304,7 @@ def render_frame(source_image, metric, r_obs, fov, psi=(0.0, 0.0), theta_obs=np.
 
 def render_sequence(source_image, metric, r_obs, fov, disk, hotspot, times, shape=None, psi=(0.0, 0.0), theta_obs=np.pi / 2,
                     integrator=None, precision=None, bfield=None, samples=None, diskmap=None, spectrum=None, baselines=None,
-                    thermal=None, frequencies=None, bands=None):
+                    thermal=None, frequencies=None, bands=None, lamppost=None, transfer=None):
     """A moving picture from ONE trace: an optically thin disk (disk.TransparentDisk) with a hot spot (disk.HotSpot) on a
     circular orbit, at the observer times `times`.  The rays are traced once with the light-travel time of every hit
     (lt_trace_disk_hits); each frame is a re-shade of the stored hits (lt_shade_hotspot) over `base`, the lensed
@@ -345,7 +345,16 @@ def render_sequence(source_image, metric, r_obs, fov, disk, hotspot, times, shap
     max_images with thermal.split_orders), and `thermal_frequencies`; with `samples` it is the fine records' divided by S^2,
     as `disk_spectrum`.  bands (up to 16 frequencies): the result also gains `thermal_bands` (n_bands, H, W) float32, the
     unclamped band images (lt_shade_thermal; with `samples` the fine images resolved S x S -> 1 per plane by aa.resolve).
+    lamppost (disk.Lamppost) with transfer (disk.TransferGrid) and spectrum (the g axis): the result gains `transfer`
+    (planes, n_tau + 2, n_bins + 2) float64, the disk's delay-energy response to a flash of that source (lt_disk_transfer;
+    planes as the spectrum's; with `samples` the fine records' divided by S^2), `transfer_tau_edges` (n_tau + 1,) and
+    `transfer_tables` (3, n_r): the nodes' radii, delay and emis, traced on the host from the disk's inner edge to r_out,
+    and `transfer_t_ref`, the direct flash's arrival time at the camera that every delay is counted from.
     One GPU, every row traced; sequences are not adaptively sampled."""
+    if (lamppost is None) != (transfer is None):
+        raise ValueError("render_sequence: lamppost=Lamppost(...) and transfer=TransferGrid(...) go together")
+    if lamppost is not None and spectrum is None:
+        raise ValueError("render_sequence: a transfer function needs spectrum=Spectrum(...) for its g axis")
     if thermal is not None and frequencies is None and bands is None:
         raise ValueError("render_sequence: thermal needs frequencies= (the spectrum) or bands= (the band images)")
     if thermal is None and (frequencies is not None or bands is not None):
@@ -392,6 +401,7 @@ def render_sequence(source_image, metric, r_obs, fov, disk, hotspot, times, shap
     if diskmap is not None:
         out = _sequence_diskmap(traced, met, d, diskmap, times, dt, base, S, spectrum, baselines)
         _sequence_thermal(out, traced, met, d, thermal, frequencies, bands, S)
+        _sequence_transfer(out, traced, met, d, disk, lamppost, transfer, spectrum, r_obs, theta_obs, S)
         return out
     frames, rgba = [], []
     for t in times:
@@ -432,6 +442,7 @@ def render_sequence(source_image, metric, r_obs, fov, disk, hotspot, times, shap
             shape = (traced["hits"].shape[0] // k, traced["hits"].shape[1] // k)
             out.update(visibility_stokes=baselines.recentre(dyn, shape, k), disk_visibility_stokes=baselines.recentre(still, shape, k))
     _sequence_thermal(out, traced, met, d, thermal, frequencies, bands, S)
+    _sequence_transfer(out, traced, met, d, disk, lamppost, transfer, spectrum, r_obs, theta_obs, S)
     if S is not None:
         out["samples"] = S
     return out
@@ -468,6 +479,21 @@ def _sequence_thermal(out, traced, met, d, thermal, frequencies, bands, S):
             import aa
             img = np.stack([aa.resolve(plane, S) for plane in img])
         out["thermal_bands"] = img
+
+
+def _sequence_transfer(out, traced, met, d, disk, lamppost, transfer, spectrum, r_obs, theta_obs, S):
+    """render_sequence's `transfer` (in output-pixel units, as `disk_spectrum`), `transfer_tau_edges` and `transfer_tables`."""
+    if lamppost is None:
+        return
+    if (lamppost.M, lamppost.a) != (float(met.M), float(met.a)):
+        raise ValueError("render_sequence: the lamp post's hole (M, a) is not the metric's")
+    r_min, r_max = disk.inner_edge(met.M, met.a), float(disk.r_out)
+    delay, emis = lamppost.tables(r_min, r_max)
+    lt = transfer.to_lt(r_min, r_max, delay.size, lamppost.t_ref(r_obs, theta_obs))
+    tf = ltrace.disk_transfer(traced["hits"], traced["n_hits"], met, d, spectrum.to_lt(), lt, delay, emis)
+    nodes = r_min + np.arange(delay.size) * (r_max - r_min) / (delay.size - 1)
+    out.update(transfer=tf / np.float64(1 if S is None else S * S), transfer_tau_edges=transfer.edges(),
+               transfer_tables=np.stack([nodes, delay, emis]), transfer_t_ref=float(lt.t_ref))
 
 
 def _table_emitter(diskmap):
@@ -562,6 +588,28 @@ def thermal_from_args(args, disk=None, M=1.0, a=0.0):
     return ThermalDisk.novikov_thorne(M, a, disk.r_out, t_max=t_max, f_col=f_col), nu, bands
 
 
+def transfer_from_args(args, disk=None, M=1.0, a=0.0):
+    """(disk.Lamppost, disk.TransferGrid) of --lamppost H --transfer TAU_MIN TAU_MAX N, or None: the g axis is --spectrum's.
+    Refused without a sequence, without --spectrum and without the optically thin disk."""
+    from disk import Lamppost, TransferGrid
+    if args.lamppost is None and args.transfer is None:
+        return None
+    if args.lamppost is None or args.transfer is None:
+        raise ValueError("--lamppost H and --transfer TAU_MIN TAU_MAX N go together")
+    if args.hotspot is None and args.bfield is None and args.disk_map is None:
+        raise ValueError("--transfer bins the stored hits of a sequence; use it with --hotspot or --disk-map (and --disk-images N)")
+    if args.spectrum is None:
+        raise ValueError("--transfer needs --spectrum G_MIN G_MAX N_BINS for its g axis")
+    if args.transfer[2] != int(args.transfer[2]):
+        raise ValueError("--transfer: N must be a whole number")
+    grid = TransferGrid(args.transfer[0], args.transfer[1], int(args.transfer[2]))
+    if disk is None:
+        return None, grid                                      # (checked only: the source needs the hole)
+    if not hasattr(disk, "max_images"):
+        raise ValueError("--transfer needs --disk-images N")
+    return Lamppost(M, a, args.lamppost * M), grid
+
+
 def baselines_from_args(args):
     """The disk.Baselines of --visibility N U_MAX ANGLE_DEG [--visibility-orders], or None; refused without a sequence."""
     from disk import Baselines
@@ -636,11 +684,14 @@ def main_sequence(args, disk):
     the polarized visibilities (I, Q, U per baseline) of the spot and of the disk.
     --thermal T_MAX [F_COL] with --thermal-frequencies NU_MIN NU_MAX N and / or --thermal-bands NU ...: also the disk's thermal
     continuum of a Novikov-Thorne flux profile -- its spectrum at N log-spaced frequencies with the frequencies, and the
-    unclamped band images -- as .npy."""
+    unclamped band images -- as .npy.
+    --lamppost H --transfer TAU_MIN TAU_MAX N (with --spectrum for the g axis): also the disk's delay-energy response to a
+    flash of a source on the axis at r = H M, the delay grid's edges and the two radial tables, as .npy."""
     from disk import BField, HotSpot
     spec = spectrum_from_args(args)
     base_lines = baselines_from_args(args)
     thermal_from_args(args)                                   # (its refusals that need no disk come before the others')
+    transfer_from_args(args)
     if args.disk_map is not None and args.hotspot is not None:
         raise ValueError("--disk-map: a map together with --hotspot is out of scope; use one of them")
     if args.disk_map is not None and args.bfield is not None:
@@ -665,10 +716,11 @@ def main_sequence(args, disk):
         spot, n = HotSpot(exposure=0.0), 1
     field = BField(*args.bfield, pol_frac=args.pol_frac) if args.bfield is not None else None
     thermal, nu, bands = thermal_from_args(args, disk, args.M, args.a) or (None, None, None)
+    lamp, tgrid = transfer_from_args(args, disk, args.M, args.a) or (None, None)
     out = render_sequence(None, metric, args.r_obs * metric.M, fov, disk, spot, t0 + dt * np.arange(n), shape=(height, width),
                           psi=(np.radians(args.psi_y), np.radians(args.psi_x)), theta_obs=np.radians(args.theta_obs), bfield=field,
                           samples=args.samples, diskmap=dmap, spectrum=spec, baselines=base_lines, thermal=thermal, frequencies=nu,
-                          bands=bands)
+                          bands=bands, lamppost=lamp, transfer=tgrid)
     stem = args.output[:-4] if args.output.lower().endswith(".png") else args.output
     for i in range(n):
         write_png_rgba8(f"{stem}_{i:04d}.png", out["rgba"][i])
@@ -704,6 +756,12 @@ def main_sequence(args, disk):
         print(f"Thermal continuum: Novikov-Thorne disk, t_max {thermal.t_max:g}, f_col {thermal.f_col:g} -> "
               + ", ".join(([f"{stem}_thermal_spectrum.npy, {stem}_thermal_frequencies.npy"] if nu is not None else [])
                           + ([f"{stem}_thermal_bands.npy"] if bands is not None else [])))
+    if lamp is not None:
+        np.save(stem + "_transfer.npy", out["transfer"])
+        np.save(stem + "_transfer_tau_edges.npy", out["transfer_tau_edges"])
+        np.save(stem + "_transfer_tables.npy", out["transfer_tables"])
+        print(f"Reverberation: lamp post at h = {lamp.h:g}, {tgrid.n_tau} delay bins in [{tgrid.tau_min:g}, {tgrid.tau_max:g}) x {spec.n_bins} bins "
+              f"of g, t_ref {out['transfer_t_ref']:.4f} -> {stem}_transfer.npy, {stem}_transfer_tau_edges.npy, {stem}_transfer_tables.npy")
     if args.samples is not None:
         print(f"Supersampling: {args.samples} x {args.samples} rays per pixel, every frame resolved on the GPU")
     print(f"{'Hot spot' if dmap is None else 'Disk map' if dmap.texels.ndim == 2 else 'Disk movie'}: one trace ({out['stats']['integrate_ms']:.2f} ms), {n} frames -> {stem}_0000.png ..., light curve -> "
@@ -1007,6 +1065,12 @@ def build_parser():
                     help="--thermal: the spectrum at N (1 ... 1024) log-spaced frequencies; writes it and the frequencies as .npy")
     ap.add_argument("--thermal-bands", type=float, nargs="+", default=None, metavar="NU",
                     help="--thermal: the unclamped image at each of up to 16 frequencies; writes them as one .npy (n_bands, H, W)")
+    ap.add_argument("--lamppost", type=float, default=None, metavar="H",
+                    help="with --transfer: a point source on the spin axis at r = H (in M) that flashes once, the lamp-post corona")
+    ap.add_argument("--transfer", type=float, nargs=3, default=None, metavar=("TAU_MIN", "TAU_MAX", "N"),
+                    help="with --lamppost, --spectrum and --hotspot / --disk-map: the disk's delay-energy transfer function from the stored "
+                         "hits on N (1 ... 1024) delay bins by --spectrum's g bins (--spectrum-orders: per image order; at most 32768 "
+                         "keys in all); writes it, the delay edges and the radial tables (radius, delay, emissivity) as .npy")
     return ap
 
 
@@ -1023,6 +1087,7 @@ if __name__ == "__main__":
     spectrum_from_args(args)                                  # (refuses --spectrum without a sequence)
     baselines_from_args(args)                                 # (and --visibility)
     thermal_from_args(args)                                   # (and --thermal)
+    transfer_from_args(args)                                  # (and --lamppost / --transfer)
     if args.hotspot is not None or args.bfield is not None or args.disk_map is not None:
         main_sequence(args, disk)
         sys.exit(0)

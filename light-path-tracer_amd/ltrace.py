@@ -118,6 +118,16 @@ class Thermal(C.Structure):
 THERMAL_MAX_NODES, THERMAL_MAX_FREQS, THERMAL_MAX_BANDS = 65536, 1024, 16
 
 
+class Transfer(C.Structure):
+    """lt_transfer: the delay grid of a transfer function, the range and size of its two radial tables (delay, emis) and
+    the direct flash's arrival time t_ref that every delay is counted from."""
+    _fields_ = [("tau_min", C.c_double), ("tau_max", C.c_double), ("n_tau", C.c_int32), ("n_r", C.c_int32),
+                ("r_min", C.c_double), ("r_max", C.c_double), ("t_ref", C.c_double)]
+
+
+TRANSFER_MAX_TAU, TRANSFER_MAX_KEYS = 1024, 32768
+
+
 class BField(C.Structure):
     """lt_bfield: the field's components in the emitter's frame and the polarization fraction."""
     _fields_ = [("b_r", C.c_double), ("b_phi", C.c_double), ("b_z", C.c_double), ("pol_frac", C.c_double)]
@@ -388,6 +398,14 @@ for _name in ("lt_disk_thermal_spectrum", "lt_shade_thermal"):
     for _suffix in ("", "_dev"):
         SIGNATURES[_name + _suffix] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Metric), C.POINTER(Disk),
                                                  C.POINTER(Thermal), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p])
+
+
+# the reverberation response: (hits, n_hits, R, W, max_images, metric, disk, spec, transfer, delay, emis, out)
+SIGNATURES["lt_default_transfer"] = (None, [C.POINTER(Transfer)])
+for _suffix in ("", "_dev"):
+    SIGNATURES["lt_disk_transfer" + _suffix] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Metric),
+                                                          C.POINTER(Disk), C.POINTER(Spectrum), C.POINTER(Transfer), C.c_void_p, C.c_void_p,
+                                                          C.c_void_p])
 
 
 def _movie_signature(name):
@@ -1767,6 +1785,54 @@ def shade_thermal_dev(d_hits, d_n_hits, rows, width, max_images, metric, disk, t
     """Device-pointer form of shade_thermal (lt_shade_thermal_dev); enqueues on the default stream."""
     _check(load().lt_shade_thermal_dev(_p(d_hits), _p(d_n_hits), rows, width, max_images, C.byref(metric), C.byref(disk), C.byref(thermal),
                                        _p(d_flux), _p(d_nu), n_freq, _p(d_out)))
+
+
+# ---- reverberation (lt_disk_transfer) -----------------------------------------------------------------------------------------
+def default_transfer(**kw):
+    """lt_transfer with the library's defaults (tau 0 ... 256, 64 bins, 2 nodes on r 6 ... 20, t_ref 0); keywords override."""
+    t = Transfer()
+    load().lt_default_transfer(C.byref(t))
+    for k, v in kw.items():
+        setattr(t, k, v)
+    return t
+
+
+def transfer_keys(spec, transfer, max_images):
+    """Keys of a transfer function's output, planes (n_tau + 2) (n_bins + 2); at most TRANSFER_MAX_KEYS."""
+    return spectrum_planes(spec, max_images) * (int(transfer.n_tau) + 2) * (int(spec.n_bins) + 2)
+
+
+def _transfer_tables(transfer, delay, emis):
+    """(delay, emis) as the library reads them; a table that is not the struct's n_r never reaches it."""
+    tables = []
+    for name, table in (("delay", delay), ("emis", emis)):
+        table = np.ascontiguousarray(table, dtype=np.float64)
+        if table.shape != (int(transfer.n_r),):
+            raise ValueError(f"{name} must be (n_r,) = ({int(transfer.n_r)},), got {table.shape}")
+        tables.append(table)
+    return tables
+
+
+def disk_transfer(hits, n_hits, metric, disk, spec, transfer, delay, emis):
+    """The disk's delay-energy transfer function from stored hits (lt_disk_transfer) -> (planes, n_tau + 2, n_bins + 2)
+    float64: per image order (with spec.split_orders; else one plane) and delay bin the line's histogram over g; row and
+    column 0 the underflows, the last the overflows."""
+    hits, nh = _hit_arrays(hits, n_hits)
+    R, W, m = hits.shape[:3]
+    delay, emis = _transfer_tables(transfer, delay, emis)
+    if transfer_keys(spec, transfer, min(max(m, 0), DISK_MAX_IMAGES)) > TRANSFER_MAX_KEYS or not 1 <= int(transfer.n_tau) <= TRANSFER_MAX_TAU:
+        out = np.empty((1, 1, 1))                              # (the library refuses this grid: an output it will not touch)
+    else:
+        out = np.empty((spectrum_planes(spec, m), int(transfer.n_tau) + 2, min(max(int(spec.n_bins), 0), SPECTRUM_MAX_BINS) + 2))
+    _check(load().lt_disk_transfer(_np_ptr(hits), _np_ptr(nh), R, W, m, C.byref(metric), C.byref(disk), C.byref(spec), C.byref(transfer),
+                                   _np_ptr(delay), _np_ptr(emis), _np_ptr(out)))
+    return out
+
+
+def disk_transfer_dev(d_hits, d_n_hits, rows, width, max_images, metric, disk, spec, transfer, d_delay, d_emis, d_out):
+    """Device-pointer form of disk_transfer (lt_disk_transfer_dev); enqueues on the default stream."""
+    _check(load().lt_disk_transfer_dev(_p(d_hits), _p(d_n_hits), rows, width, max_images, C.byref(metric), C.byref(disk), C.byref(spec),
+                                       C.byref(transfer), _p(d_delay), _p(d_emis), _p(d_out)))
 
 
 # ---- visibilities (lt_disk_visibility, lt_hotspot_visibility, lt_diskmap_visibility) ---------------------------------------
