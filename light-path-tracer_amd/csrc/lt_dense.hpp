@@ -49,8 +49,14 @@ __device__ __forceinline__ void rhs8_sc(const DenseConsts &k, const double *y, d
         for (int i = 0; i < 8; ++i) d[i] = 0.0;
         return;
     }
-    double s2 = s * s;
-    if (k.floor_sin2 && s2 < 1e-15) s2 = 1e-15;
+    double s2 = s * s, sc = s * c;
+    if (k.floor_sin2 && wave_any(s2 < 1e-15)) { // (within 3.2e-8 rad of the axis: a wave-uniform branch that is next to never taken)
+        // the reference floors sin^2 but divides its p_theta' by the sine itself, cos L^2 / (r^2 s2 sin) (metrics.py:787):
+        // with the floor acting, sin cos / s2^2 is not that
+        const bool fl = s2 < 1e-15;
+        sc = fl ? c * (1e-15 / s) : sc;
+        s2 = fl ? 1e-15 : s2;
+    }
     const double r2 = r * r, ra = r2 + k.a2;
     const double Sigma = r2 + k.a2 * c * c, Delta = ra - 2.0 * k.M * r;
     // one division for the three reciprocals (each float64 division is ~12 instructions around a quarter-rate v_rcp_f64)
@@ -67,7 +73,7 @@ __device__ __forceinline__ void rhs8_sc(const DenseConsts &k, const double *y, d
     d[4] = 0.0;
     // -(F_r - 2H Sigma_r) / (2 Sigma) and -(F_theta - 2H Sigma_theta) / (2 Sigma) with the factor 1/2 folded in
     d[5] = -iS * ((r - k.M) * (pr * pr + PD * PD) - r * (2.0 * E * PD + H2));
-    d[6] = iS * (s * c) * (Ds * (2.0 * k.a * E + Ds) - H2 * k.a2);
+    d[6] = iS * sc * (Ds * (2.0 * k.a * E + Ds) - H2 * k.a2);
     d[7] = 0.0;
 }
 
@@ -304,7 +310,11 @@ __global__ void __launch_bounds__(64, LT_DENSE_WAVES) k_dense_tracks(DenseConsts
         rhs8_near(k, tmp, y[2], s0, c0, k6, ss, cc);
 #pragma unroll
         for (int c = 0; c < 8; ++c) yn[c] = dense_cyclic(c) ? y[c] : y[c] + hh * (f[c] * B1 + k3[c] * B3 + k4[c] * B4 + k5[c] * B5 + k6[c] * B6);
-        rhs8_near(k, yn, y[2], s0, c0, k7, sn, cn);
+        // The candidate's own sincos, not a rotation of the base pair: (sn, cn) becomes the NEXT step's base pair, and a pair
+        // rotated from step to step drifts -- after a hundred steps by tens of ulps of the sine, which next to the axis
+        // (p_theta' ~ 1 / sin^3) was 150 to 320 units of a step's bound (tests/test_gpu_dense_blocks.py).
+        M<double>::sincos(yn[2], sn, cn);
+        rhs8_sc(k, yn, sn, cn, k7);
     };
     double h = 0, t_new = 0;
     double min_step = 0;

@@ -195,6 +195,78 @@ static double brent_root(const EvCtx *c, double xa, double xb)
     return xcur;
 }
 
+/* ------------------------------------------------------------------------------------------------
+ * The loop body, block by block: what lto_integrate_dense below runs, exported so that the tests can hold
+ * each block to a longdouble restatement (tests/dense_blocks.py) -- the pattern of lto_dp45_attempt / lto_dp45_decide.
+ * ---------------------------------------------------------------------------------------------- */
+/* select_initial_step (Hairer II.4), order of the error estimator = 4: one right-hand side at y + h0 f.  Returns h_abs. */
+double lto_dense_initial_step(int kind, double M, double a, const double *y, const double *f, double lambda_max, double rtol,
+                              double atol, double max_step)
+{
+    double sc[8], v[8], y1[8], f1[8];
+    for (int i = 0; i < 8; ++i) sc[i] = atol + fabs(y[i]) * rtol;
+    for (int i = 0; i < 8; ++i) v[i] = y[i] / sc[i];
+    double d0 = rms8(v);
+    for (int i = 0; i < 8; ++i) v[i] = f[i] / sc[i];
+    double d1 = rms8(v);
+    double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
+    h0 = fmin(h0, lambda_max);
+    for (int i = 0; i < 8; ++i) y1[i] = y[i] + h0 * f[i];
+    lto_rhs8(kind, M, a, y1, f1);
+    for (int i = 0; i < 8; ++i) v[i] = (f1[i] - f[i]) / sc[i];
+    double d2 = rms8(v) / h0;
+    double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? fmax(1e-6, h0 * 1e-3) : pow(0.01 / fmax(d1, d2), 1.0 / 5);
+    return fmin(fmin(100 * h0, h1), fmin(lambda_max, max_step));
+}
+
+/* One attempt of size h from (y, f = rhs(y)): six right-hand sides.  -> y_new, f_new = rhs(y_new), the RMS error norm and
+ * the dense-output coefficients Q (8 x 4, row-major) = K^T P of this step. */
+void lto_dense_attempt(int kind, double M, double a, const double *y, const double *f, double h, double rtol, double atol,
+                       double *y_new, double *f_new, double *out_err, double *out_Q)
+{
+    double K[7][8];
+    memcpy(K[0], f, 8 * sizeof(double));
+    for (int s = 1; s < 6; ++s) {
+        double ys[8];
+        for (int i = 0; i < 8; ++i) {
+            double d = 0;
+            for (int j = 0; j < s; ++j) d += K[j][i] * DP_A[s][j];
+            ys[i] = y[i] + d * h;
+        }
+        lto_rhs8(kind, M, a, ys, K[s]);
+    }
+    for (int i = 0; i < 8; ++i) {
+        double d = 0;
+        for (int j = 0; j < 6; ++j) d += K[j][i] * DP_B[j];
+        y_new[i] = y[i] + h * d;
+    }
+    lto_rhs8(kind, M, a, y_new, f_new);
+    memcpy(K[6], f_new, 8 * sizeof(double));
+    double e[8];
+    for (int i = 0; i < 8; ++i) {
+        double d = 0;
+        for (int j = 0; j < 7; ++j) d += K[j][i] * DP_E[j];
+        e[i] = d * h / (atol + fmax(fabs(y[i]), fabs(y_new[i])) * rtol);
+    }
+    *out_err = rms8(e);
+    for (int i = 0; i < 8; ++i)
+        for (int j = 0; j < 4; ++j) {
+            double d = 0;
+            for (int s = 0; s < 7; ++s) d += K[s][i] * DP_P[s][j];
+            out_Q[i * 4 + j] = d;
+        }
+}
+
+/* The terminal event r = radius inside the accepted step t -> t_new = t + h from y with dense output Q: Brent's root on
+ * [t, t_new]; ye (8, nullable) = the dense output there.  Returns the root. */
+double lto_dense_event(const double *y, double t, double h, const double *Q, double radius, double t_new, double *ye)
+{
+    EvCtx c = {y, t, h, (double (*)[4])Q, radius};
+    double te = brent_root(&c, t, t_new);
+    if (ye) dense_eval(y, t, h, (double (*)[4])Q, te, ye);
+    return te;
+}
+
 /*
  * One track.  out_t[max_points], out_y[8][max_points] row-major (component-major, like solution.y).
  * Returns the number of points a complete record holds (may exceed max_points: then only the first
@@ -205,15 +277,20 @@ static double brent_root(const EvCtx *c, double xa, double xb)
  * lto_predict_attempts below -- the CPU twin of the dense kernel's length predictor -- and never by the record path. */
 static __thread double *g_step_h = NULL, *g_step_err = NULL;
 static __thread int64_t g_step_cap = 0, g_step_n = 0;
+/* Where the step that held the last track's terminal event would have ended (NaN: the track ended on no event): what the device
+ * writes into the slot past an event record (lt_dense.hpp), so that the whole step's dense output can be rebuilt. */
+static __thread double g_last_t_new = NAN;
+double lto_dense_last_t_new(void) { return g_last_t_new; }
 
 int64_t lto_integrate_dense(int kind, double M, double a, const double *state0, double lambda_max, double r_stop_inner,
                             double r_stop_outer, double rtol, double atol, double max_step, int64_t max_points,
                             double *out_t, double *out_y, int *out_status, int64_t *out_nfev)
 {
     Sys S = {kind, M, a, 0};
-    double t = 0, y[8], f[8], K[7][8], Q[8][4];
+    double t = 0, y[8], f[8], Q[8][4];
     memcpy(y, state0, sizeof y);
     int64_t n = 0;
+    g_last_t_new = NAN;
 #define PUSH(tt, yy)                                                                                                  \
     do {                                                                                                              \
         int64_t slot = n < max_points ? n : max_points - 1;                                                           \
@@ -222,24 +299,8 @@ int64_t lto_integrate_dense(int kind, double M, double a, const double *state0, 
     } while (0)
     PUSH(t, y);
     fun(&S, y, f);
-    /* select_initial_step (Hairer II.4), order of the error estimator = 4 */
-    double h_abs;
-    {
-        double sc[8], v[8], y1[8], f1[8];
-        for (int i = 0; i < 8; ++i) sc[i] = atol + fabs(y[i]) * rtol;
-        for (int i = 0; i < 8; ++i) v[i] = y[i] / sc[i];
-        double d0 = rms8(v);
-        for (int i = 0; i < 8; ++i) v[i] = f[i] / sc[i];
-        double d1 = rms8(v);
-        double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
-        h0 = fmin(h0, lambda_max);
-        for (int i = 0; i < 8; ++i) y1[i] = y[i] + h0 * f[i];
-        fun(&S, y1, f1);
-        for (int i = 0; i < 8; ++i) v[i] = (f1[i] - f[i]) / sc[i];
-        double d2 = rms8(v) / h0;
-        double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? fmax(1e-6, h0 * 1e-3) : pow(0.01 / fmax(d1, d2), 1.0 / 5);
-        h_abs = fmin(fmin(100 * h0, h1), fmin(lambda_max, max_step));
-    }
+    double h_abs = lto_dense_initial_step(kind, M, a, y, f, lambda_max, rtol, atol, max_step);
+    ++S.nfev;
     double g_in = y[1] - r_stop_inner, g_out = y[1] - r_stop_outer;
     int status = 0;
     while (t != lambda_max) {
@@ -255,30 +316,9 @@ int64_t lto_integrate_dense(int kind, double M, double a, const double *state0, 
             if (t_new - lambda_max > 0) t_new = lambda_max;
             h = t_new - t;
             h_abs = fabs(h);
-            memcpy(K[0], f, sizeof f);
-            for (int s = 1; s < 6; ++s) {
-                double ys[8];
-                for (int i = 0; i < 8; ++i) {
-                    double d = 0;
-                    for (int j = 0; j < s; ++j) d += K[j][i] * DP_A[s][j];
-                    ys[i] = y[i] + d * h;
-                }
-                fun(&S, ys, K[s]);
-            }
-            for (int i = 0; i < 8; ++i) {
-                double d = 0;
-                for (int j = 0; j < 6; ++j) d += K[j][i] * DP_B[j];
-                y_new[i] = y[i] + h * d;
-            }
-            fun(&S, y_new, f_new);
-            memcpy(K[6], f_new, sizeof f_new);
-            double e[8];
-            for (int i = 0; i < 8; ++i) {
-                double d = 0;
-                for (int j = 0; j < 7; ++j) d += K[j][i] * DP_E[j];
-                e[i] = d * h / (atol + fmax(fabs(y[i]), fabs(y_new[i])) * rtol);
-            }
-            double err = rms8(e);
+            double err;
+            lto_dense_attempt(kind, M, a, y, f, h, rtol, atol, y_new, f_new, &err, &Q[0][0]);
+            S.nfev += 6;
             if (err < 1) {
                 if (g_step_h && g_step_n < g_step_cap) { g_step_h[g_step_n] = h; g_step_err[g_step_n] = err; }
                 ++g_step_n;
@@ -290,25 +330,18 @@ int64_t lto_integrate_dense(int kind, double M, double a, const double *state0, 
             h_abs *= fmax(0.2, 0.9 * pow(err, -0.2)); /* a NaN error norm lands here too (nan < 1 is false) */
             rejected = 1;
         }
-        /* step accepted: dense output coefficients, events */
-        for (int i = 0; i < 8; ++i)
-            for (int j = 0; j < 4; ++j) {
-                double d = 0;
-                for (int s = 0; s < 7; ++s) d += K[s][i] * DP_P[s][j];
-                Q[i][j] = d;
-            }
+        /* step accepted: events on its dense output */
         double gn_in = y_new[1] - r_stop_inner, gn_out = y_new[1] - r_stop_outer;
         int hit_in = g_in >= 0 && gn_in <= 0, hit_out = g_out <= 0 && gn_out >= 0;
         if (hit_in || hit_out) {
-            EvCtx c = {y, t, h, Q, 0};
-            double root_in = 0, root_out = 0;
-            if (hit_in) { c.radius = r_stop_inner; root_in = brent_root(&c, t, t_new); }
-            if (hit_out) { c.radius = r_stop_outer; root_out = brent_root(&c, t, t_new); }
+            double root_in = 0, root_out = 0, ye_in[8], ye_out[8];
+            if (hit_in) root_in = lto_dense_event(y, t, h, &Q[0][0], r_stop_inner, t_new, ye_in);
+            if (hit_out) root_out = lto_dense_event(y, t, h, &Q[0][0], r_stop_outer, t_new, ye_out);
             int take_in = hit_in && (!hit_out || root_in <= root_out);
-            double te = take_in ? root_in : root_out, ye[8];
-            dense_eval(y, t, h, Q, te, ye);
-            PUSH(te, ye);
+            double te = take_in ? root_in : root_out;
+            PUSH(te, take_in ? ye_in : ye_out);
             status = take_in ? 1 : 2;
+            g_last_t_new = t_new;
             goto done;
         }
         g_in = gn_in; g_out = gn_out;

@@ -79,6 +79,14 @@ def lib():
         L.lto_dense_step_log.argtypes = [C.c_int, C.c_double, C.c_double, _dp] + [C.c_double] * 6 + [
             C.c_int64, _dp, _dp, C.POINTER(C.c_int), C.POINTER(C.c_int64)]
         L.lto_dense_step_log.restype = C.c_int64
+        L.lto_dense_initial_step.argtypes = [C.c_int, C.c_double, C.c_double, _dp, _dp] + [C.c_double] * 4
+        L.lto_dense_initial_step.restype = C.c_double
+        L.lto_dense_attempt.argtypes = [C.c_int, C.c_double, C.c_double, _dp, _dp] + [C.c_double] * 3 + [_dp] * 4
+        L.lto_dense_attempt.restype = None
+        L.lto_dense_event.argtypes = [_dp, C.c_double, C.c_double, _dp, C.c_double, C.c_double, _dp]
+        L.lto_dense_event.restype = C.c_double
+        L.lto_dense_last_t_new.argtypes = []
+        L.lto_dense_last_t_new.restype = C.c_double
         _LIB = L
     return _LIB
 
@@ -504,9 +512,10 @@ def rhs8(kind, M, a, state):
 
 
 def integrate_dense(kind, M, a, state0, lambda_max=1000.0, r_stop_inner=None, r_stop_outer=None,
-                    rtol=1e-8, atol=1e-10, max_step=1.0, max_points=4096):
+                    rtol=1e-8, atol=1e-10, max_step=1.0, max_points=4096, with_count=False):
     """geodesic_tracer.integrate_geodesic (geodesic_tracer.py:22-71) for one 8-D initial state.
-    -> (t (n,), y (8, n), status, nfev); status 1 capture event, 2 escape event, 0 lambda_max, -1 failed."""
+    -> (t (n,), y (8, n), status, nfev); status 1 capture event, 2 escape event, 0 lambda_max, -1 failed.
+    with_count: also the number of points the complete record holds (> max_points: truncated, last slot = final point)."""
     s0 = np.ascontiguousarray(state0, dtype=np.float64)
     t = np.empty(max_points, dtype=np.float64)
     y = np.empty((8, max_points), dtype=np.float64)
@@ -515,7 +524,58 @@ def integrate_dense(kind, M, a, state0, lambda_max=1000.0, r_stop_inner=None, r_
                                   float(r_stop_outer), float(rtol), float(atol), float(max_step), int(max_points),
                                   _ptr(t, _dp), _ptr(y, _dp), C.byref(st), C.byref(nfev))
     m = min(int(n), max_points)
-    return t[:m].copy(), y[:, :m].copy(), int(st.value), int(nfev.value)
+    out = (t[:m].copy(), y[:, :m].copy(), int(st.value), int(nfev.value))
+    return out + (int(n),) if with_count else out
+
+
+def rhs8_n(kind, M, a, states):
+    """rhs8 of n states (n, 8), row by row."""
+    st = np.ascontiguousarray(states, dtype=np.float64).reshape(-1, 8)
+    out = np.empty_like(st)
+    fn = lib().lto_rhs8
+    for i in range(st.shape[0]):
+        fn(int(kind), float(M), float(a), _ptr(st[i], _dp), _ptr(out[i], _dp))
+    return out
+
+
+def dense_initial_step(kind, M, a, y, f, lambda_max=1000.0, rtol=1e-8, atol=1e-10, max_step=1.0):
+    """Hairer's initial step of the dense loop (lto_dense_initial_step) for n rows: y, f = rhs8(y) (n, 8) -> h_abs (n,)."""
+    y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1, 8)
+    f = np.ascontiguousarray(f, dtype=np.float64).reshape(-1, 8)
+    fn = lib().lto_dense_initial_step
+    return np.array([fn(int(kind), float(M), float(a), _ptr(y[i], _dp), _ptr(f[i], _dp), float(lambda_max), float(rtol),
+                        float(atol), float(max_step)) for i in range(y.shape[0])])
+
+
+def dense_attempt(kind, M, a, y, f, h, rtol=1e-8, atol=1e-10):
+    """One attempt of the dense loop (lto_dense_attempt, the function lto_integrate_dense runs) for n rows: y, f (n, 8),
+    h (n,) -> dict(y_new (n, 8), f_new (n, 8), err (n,), Q (n, 8, 4))."""
+    y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1, 8)
+    f = np.ascontiguousarray(f, dtype=np.float64).reshape(-1, 8)
+    n = y.shape[0]
+    h = np.ascontiguousarray(np.broadcast_to(np.asarray(h, dtype=np.float64), (n,)))
+    yn, fn_, err, Q = np.empty_like(y), np.empty_like(y), np.empty(n), np.empty((n, 8, 4))
+    fn = lib().lto_dense_attempt
+    e = C.c_double(0)
+    for i in range(n):
+        fn(int(kind), float(M), float(a), _ptr(y[i], _dp), _ptr(f[i], _dp), float(h[i]), float(rtol), float(atol),
+           _ptr(yn[i], _dp), _ptr(fn_[i], _dp), C.byref(e), _ptr(Q[i], _dp))
+        err[i] = e.value
+    return dict(y_new=yn, f_new=fn_, err=err, Q=Q)
+
+
+def dense_last_t_new():
+    """Where the step that held the terminal event of this thread's last integrate_dense would have ended (NaN: no event)."""
+    return float(lib().lto_dense_last_t_new())
+
+
+def dense_event(y, t, h, Q, radius, t_new):
+    """The terminal event of one accepted step (lto_dense_event): y (8,), Q (8, 4) -> (te, ye (8,))."""
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    Q = np.ascontiguousarray(Q, dtype=np.float64)
+    ye = np.empty(8)
+    te = lib().lto_dense_event(_ptr(y, _dp), float(t), float(h), _ptr(Q, _dp), float(radius), float(t_new), _ptr(ye, _dp))
+    return float(te), ye
 
 
 def dense_predict_length(kind, M, a, state0, lambda_max=1000.0, r_stop_inner=None, r_stop_outer=None,
