@@ -126,7 +126,7 @@ extern "C" int lt_diskmovie_lightcurve(const float *hits, const uint8_t *n_hits,
     DiskMovieCall c;
     int rc = resolve_diskmovie(hits, R, W, max_images, metric, disk, map, movie, texels, &c);
     if (rc || (rc = check_n_times(n_times))) return rc;
-    return staged_hits_call(hits, n_hits, R, W, max_images, movie_texels(texels, map, movie), {out, (size_t)n_times, 24},
+    return staged_hits_call(hits, n_hits, R, W, max_images, {movie_texels(texels, map, movie)}, {out, (size_t)n_times, 24},
                             [&](void *const *in, void *const *out_) {
         return lt_diskmovie_lightcurve_dev((const float *)in[0], (const uint8_t *)in[1], R, W, max_images, metric, disk, map, movie,
                                            (const float *)in[2], t_start, dt, n_times, (double *)out_[0]);
@@ -155,7 +155,7 @@ extern "C" int lt_diskmovie_spectrum(const float *hits, const uint8_t *n_hits, i
     SpectrumGrid sg;
     int rc = resolve_diskmovie(hits, R, W, max_images, metric, disk, map, movie, texels, &c);
     if (rc || (rc = resolve_spectrum(spec, max_images, &sg)) || (rc = check_spectrum_times(t_start, dt, n_times))) return rc;
-    return staged_hits_call(hits, n_hits, R, W, max_images, movie_texels(texels, map, movie), {out, (size_t)n_times, spectrum_row_bytes(sg)},
+    return staged_hits_call(hits, n_hits, R, W, max_images, {movie_texels(texels, map, movie)}, {out, (size_t)n_times, spectrum_row_bytes(sg)},
                             [&](void *const *in, void *const *out_) {
         return lt_diskmovie_spectrum_dev((const float *)in[0], (const uint8_t *)in[1], R, W, max_images, metric, disk, map, movie,
                                          (const float *)in[2], spec, t_start, dt, n_times, (double *)out_[0]);
@@ -186,7 +186,7 @@ extern "C" int lt_diskmovie_visibility(const float *hits, const uint8_t *n_hits,
     DiskMovieCall c;
     int rc = resolve_diskmovie(hits, R, W, max_images, metric, disk, map, movie, texels, &c);
     if (rc || (rc = resolve_baselines(uv, n_baselines)) || (rc = check_spectrum_times(t_start, dt, n_times))) return rc;
-    return staged_hits_call(hits, n_hits, R, W, max_images, movie_texels(texels, map, movie),
+    return staged_hits_call(hits, n_hits, R, W, max_images, {movie_texels(texels, map, movie)},
                             {out, (size_t)n_times, visibility_row_bytes(max_images, n_baselines, split_orders)}, [&](void *const *in, void *const *out_) {
         return lt_diskmovie_visibility_dev((const float *)in[0], (const uint8_t *)in[1], R, W, max_images, metric, disk, map, movie,
                                            (const float *)in[2], uv, n_baselines, split_orders, t_start, dt, n_times, (double *)out_[0]);

@@ -44,20 +44,38 @@ static int check_times_and_out(double t_start, double dt, int32_t n_times, const
     return d_out ? LT_OK : fail(LT_ERR_INVALID_ARG, "null out");
 }
 
-// A host-pointer reduction through its _dev form (staged_call): the records, their counts and one more input -- the
-// polarization records, the map's texels, or {} for none (a null array stays null and takes no room) -- staged as in[0],
-// in[1], in[2], and the rows of `out` fetched.
+// A host-pointer reduction through its _dev form (staged_call): the records, their counts and the further inputs `more` --
+// none, one or two: the polarization records, the map's texels, the thermal and the transfer tables (a null array stays null
+// and takes no room) -- staged as in[0], in[1], in[2], in[3], and the rows of `out` fetched.
 template <typename Dev>
-static int staged_hits_call(const float *hits, const uint8_t *n_hits, int32_t R, int32_t W, int32_t max_images, const HostArray &more,
-                            const HostArray &out, Dev dev)
+static int staged_hits_call(const float *hits, const uint8_t *n_hits, int32_t R, int32_t W, int32_t max_images,
+                            std::initializer_list<HostArray> more, const HostArray &out, Dev dev)
 {
     const size_t n = (size_t)R * W;
-    return staged_call({{hits, n, (size_t)max_images * 16}, {n_hits, n, 1}, more}, {out}, dev);
+    HostArray ins[4] = {{hits, n, (size_t)max_images * 16}, {n_hits, n, 1}, {}, {}};
+    std::copy(more.begin(), more.end(), ins + 2);
+    return staged_call(ins, {out}, dev);
+}
+
+// The two stages of a reduction whose partials are (batch, block, row) in the slot's spectra workspace, on the default
+// stream: the workspace grown to batches x SP_BLOCKS x row doubles, first_stage(partial) -- the caller's launch --, then
+// k_sum_blocks of the batches' rows into d_out.
+template <typename FirstStage> static int launch_two_stage(unsigned batches, int row, double *d_out, FirstStage first_stage)
+{
+    StreamSlot *sl;
+    int rc;
+    if ((rc = get_slot(nullptr, &sl)) || (rc = grow(sl->spectrum, (size_t)batches * SP_BLOCKS * row * sizeof(double), nullptr))) return rc;
+    double *partial = (double *)sl->spectrum.p;
+    first_stage(partial);
+    k_sum_blocks<<<dim3((unsigned)((row + 255) / 256), batches), 256>>>(partial, row, (int64_t)batches * row, d_out);
+    HIP_TRY(hipGetLastError());
+    return LT_OK;
 }
 
 // A _dev spectrum behind its resolves: the refusals of the times and of a null out, then the times in batches whose
-// partials fit the slot's bounded workspace -- first_stage(grid, lds, first, partial) launches the emitter's kernel for the
-// times first ... first + grid.y - 1 -- each followed by k_sum_blocks into its rows.  A row does not depend on its batch.
+// partials fit the slot's bounded workspace (the first batch is the largest, so the workspace grows once) --
+// first_stage(grid, lds, first, partial) launches the emitter's kernel for the times first ... first + grid.y - 1 -- each
+// followed by k_sum_blocks into its rows.  A row does not depend on its batch.
 template <typename FirstStage>
 static int launch_spectrum(const SpectrumGrid &sg, int32_t max_images, double t_start, double dt, int32_t n_times, double *d_out,
                            FirstStage first_stage)
@@ -67,16 +85,13 @@ static int launch_spectrum(const SpectrumGrid &sg, int32_t max_images, double t_
     const int n_keys = (sg.n_bins + 2) * sg.planes;
     const size_t per_time = (size_t)SP_BLOCKS * n_keys * sizeof(double);
     const int32_t batch = (int32_t)std::min<size_t>((size_t)n_times, std::max<size_t>(1, (size_t)LT_SPECTRUM_WORKSPACE_BYTES / per_time));
-    StreamSlot *sl;
-    if ((rc = get_slot(nullptr, &sl)) || (rc = grow(sl->spectrum, (size_t)batch * per_time, nullptr))) return rc;
-    double *partial = (double *)sl->spectrum.p;
-    for (int32_t first = 0; first < n_times; first += batch) {
+    for (int32_t first = 0; first < n_times && !rc; first += batch) {
         const unsigned n = (unsigned)std::min(batch, n_times - first);
-        first_stage(dim3(SP_BLOCKS, n), spectrum_lds_bytes(n_keys, max_images), (int)first, partial);
-        k_sum_blocks<<<dim3((unsigned)((n_keys + 255) / 256), n), 256>>>(partial, n_keys, (int64_t)n * n_keys, d_out + (int64_t)first * n_keys);
+        rc = launch_two_stage(n, n_keys, d_out + (int64_t)first * n_keys, [&](double *partial) {
+            first_stage(dim3(SP_BLOCKS, n), spectrum_lds_bytes(n_keys, max_images), (int)first, partial);
+        });
     }
-    HIP_TRY(hipGetLastError());
-    return LT_OK;
+    return rc;
 }
 
 static size_t spectrum_row_bytes(const SpectrumGrid &sg) { return (size_t)(sg.n_bins + 2) * sg.planes * sizeof(double); }
@@ -165,7 +180,7 @@ extern "C" int lt_diskmap_spectrum(const float *hits, const uint8_t *n_hits, int
     SpectrumGrid sg;
     int rc = resolve_diskmap(hits, R, W, max_images, metric, disk, map, texels, &ds, &dm);
     if (rc || (rc = resolve_spectrum(spec, max_images, &sg)) || (rc = check_spectrum_times(t_start, dt, n_times))) return rc;
-    return staged_hits_call(hits, n_hits, R, W, max_images, {texels, (size_t)map->n_r * map->n_phi, 4},
+    return staged_hits_call(hits, n_hits, R, W, max_images, {{texels, (size_t)map->n_r * map->n_phi, 4}},
                             {out, (size_t)n_times, spectrum_row_bytes(sg)}, [&](void *const *in, void *const *out_) {
         return lt_diskmap_spectrum_dev((const float *)in[0], (const uint8_t *)in[1], R, W, max_images, metric, disk, map, (const float *)in[2],
                                        spec, t_start, dt, n_times, (double *)out_[0]);

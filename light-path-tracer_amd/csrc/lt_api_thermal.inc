@@ -52,15 +52,6 @@ static int check_freqs_and_out(int32_t n_freq, int32_t limit, const void *out)
     return out ? LT_OK : fail(LT_ERR_INVALID_ARG, "null out");
 }
 
-// staged_hits_call with two further inputs, in[2] and in[3].
-template <typename Dev>
-static int staged_hits_call(const float *hits, const uint8_t *n_hits, int32_t R, int32_t W, int32_t max_images, const HostArray &more,
-                            const HostArray &more2, const HostArray &out, Dev dev)
-{
-    const size_t n = (size_t)R * W;
-    return staged_call({{hits, n, (size_t)max_images * 16}, {n_hits, n, 1}, more, more2}, {out}, dev);
-}
-
 extern "C" int lt_disk_thermal_spectrum_dev(const float *d_hits, const uint8_t *d_n_hits, int32_t R, int32_t W, int32_t max_images,
                                             const lt_metric *metric, const lt_disk *disk, const lt_thermal *thermal, const double *d_flux,
                                             const double *d_nu, int32_t n_freq, double *d_out)
@@ -69,20 +60,16 @@ extern "C" int lt_disk_thermal_spectrum_dev(const float *d_hits, const uint8_t *
     int rc = resolve_thermal(d_hits, R, W, max_images, metric, disk, thermal, d_flux, d_nu, false, &ts);
     if (rc || (rc = check_freqs_and_out(n_freq, LT_THERMAL_MAX_FREQS, d_out)) || n_freq == 0) return rc;
     const int planes = thermal->split_orders ? max_images : 1;
-    const int row = planes * n_freq;
-    StreamSlot *sl;
-    if ((rc = get_slot(nullptr, &sl)) || (rc = grow(sl->spectrum, (size_t)SP_BLOCKS * row * sizeof(double), nullptr))) return rc;
-    double *partial = (double *)sl->spectrum.p;
     const dim3 grid(SP_BLOCKS, 1, (unsigned)((n_freq + 255) / 256));
     const size_t lds = thermal_lds_bytes(max_images);
-    if (planes > 1)
-        k_thermal_spectrum_partial<DISK_MAX_IMAGES><<<grid, 256, lds>>>(d_hits, d_n_hits, (int64_t)R * W, max_images, ts, d_flux, d_nu, n_freq,
-                                                                      planes, partial);
-    else
-        k_thermal_spectrum_partial<1><<<grid, 256, lds>>>(d_hits, d_n_hits, (int64_t)R * W, max_images, ts, d_flux, d_nu, n_freq, planes, partial);
-    k_sum_blocks<<<dim3((unsigned)((row + 255) / 256), 1), 256>>>(partial, row, (int64_t)row, d_out);
-    HIP_TRY(hipGetLastError());
-    return LT_OK;
+    return launch_two_stage(1, planes * n_freq, d_out, [&](double *partial) {
+        if (planes > 1)
+            k_thermal_spectrum_partial<DISK_MAX_IMAGES><<<grid, 256, lds>>>(d_hits, d_n_hits, (int64_t)R * W, max_images, ts, d_flux, d_nu, n_freq,
+                                                                          planes, partial);
+        else
+            k_thermal_spectrum_partial<1><<<grid, 256, lds>>>(d_hits, d_n_hits, (int64_t)R * W, max_images, ts, d_flux, d_nu, n_freq, planes,
+                                                              partial);
+    });
 }
 
 extern "C" int lt_disk_thermal_spectrum(const float *hits, const uint8_t *n_hits, int32_t R, int32_t W, int32_t max_images,
@@ -93,7 +80,7 @@ extern "C" int lt_disk_thermal_spectrum(const float *hits, const uint8_t *n_hits
     int rc = resolve_thermal(hits, R, W, max_images, metric, disk, thermal, flux, nu, false, &ts);
     if (rc || (rc = check_freqs_and_out(n_freq, LT_THERMAL_MAX_FREQS, out)) || n_freq == 0) return rc;
     const size_t planes = thermal->split_orders ? (size_t)max_images : 1;
-    return staged_hits_call(hits, n_hits, R, W, max_images, {flux, (size_t)thermal->n_r, 8}, {nu, (size_t)n_freq, 8},
+    return staged_hits_call(hits, n_hits, R, W, max_images, {{flux, (size_t)thermal->n_r, 8}, {nu, (size_t)n_freq, 8}},
                             {out, planes * (size_t)n_freq, 8}, [&](void *const *in, void *const *out_) {
         return lt_disk_thermal_spectrum_dev((const float *)in[0], (const uint8_t *)in[1], R, W, max_images, metric, disk, thermal,
                                             (const double *)in[2], (const double *)in[3], n_freq, (double *)out_[0]);
@@ -120,7 +107,7 @@ extern "C" int lt_shade_thermal(const float *hits, const uint8_t *n_hits, int32_
     ThermalShade ts;
     int rc = resolve_thermal(hits, R, W, max_images, metric, disk, thermal, flux, nu, true, &ts);
     if (rc || (rc = check_freqs_and_out(n_freq, LT_THERMAL_MAX_BANDS, out)) || n_freq == 0) return rc;
-    return staged_hits_call(hits, n_hits, R, W, max_images, {flux, (size_t)thermal->n_r, 8}, {nu, (size_t)n_freq, 8},
+    return staged_hits_call(hits, n_hits, R, W, max_images, {{flux, (size_t)thermal->n_r, 8}, {nu, (size_t)n_freq, 8}},
                             {out, (size_t)n_freq * (size_t)R * W, 4}, [&](void *const *in, void *const *out_) {
         return lt_shade_thermal_dev((const float *)in[0], (const uint8_t *)in[1], R, W, max_images, metric, disk, thermal,
                                     (const double *)in[2], (const double *)in[3], n_freq, (float *)out_[0]);

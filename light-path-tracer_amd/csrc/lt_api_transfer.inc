@@ -60,15 +60,11 @@ extern "C" int lt_disk_transfer_dev(const float *d_hits, const uint8_t *d_n_hits
     int n_keys;
     int rc = resolve_transfer(d_hits, R, W, max_images, metric, disk, spec, transfer, d_delay, d_emis, d_out, &sg, &ts, &n_keys);
     if (rc) return rc;
-    StreamSlot *sl;
-    if ((rc = get_slot(nullptr, &sl)) || (rc = grow(sl->spectrum, (size_t)SP_BLOCKS * n_keys * sizeof(double), nullptr))) return rc;
-    double *partial = (double *)sl->spectrum.p;
     const dim3 grid(SP_BLOCKS, (unsigned)((n_keys + TR_TILE - 1) / TR_TILE));
-    k_disk_transfer_partial<<<grid, 256, transfer_lds_bytes(max_images)>>>(d_hits, d_n_hits, (int64_t)R * W, max_images, ts, sg, d_delay, d_emis,
-                                                                           n_keys, partial);
-    k_sum_blocks<<<dim3((unsigned)((n_keys + 255) / 256), 1), 256>>>(partial, n_keys, (int64_t)n_keys, d_out);
-    HIP_TRY(hipGetLastError());
-    return LT_OK;
+    return launch_two_stage(1, n_keys, d_out, [&](double *partial) {
+        k_disk_transfer_partial<<<grid, 256, transfer_lds_bytes(max_images)>>>(d_hits, d_n_hits, (int64_t)R * W, max_images, ts, sg, d_delay,
+                                                                               d_emis, n_keys, partial);
+    });
 }
 
 extern "C" int lt_disk_transfer(const float *hits, const uint8_t *n_hits, int32_t R, int32_t W, int32_t max_images, const lt_metric *metric,
@@ -80,7 +76,7 @@ extern "C" int lt_disk_transfer(const float *hits, const uint8_t *n_hits, int32_
     int n_keys;
     int rc = resolve_transfer(hits, R, W, max_images, metric, disk, spec, transfer, delay, emis, out, &sg, &ts, &n_keys);
     if (rc) return rc;
-    return staged_hits_call(hits, n_hits, R, W, max_images, {delay, (size_t)transfer->n_r, 8}, {emis, (size_t)transfer->n_r, 8},
+    return staged_hits_call(hits, n_hits, R, W, max_images, {{delay, (size_t)transfer->n_r, 8}, {emis, (size_t)transfer->n_r, 8}},
                             {out, (size_t)n_keys, 8}, [&](void *const *in, void *const *out_) {
         return lt_disk_transfer_dev((const float *)in[0], (const uint8_t *)in[1], R, W, max_images, metric, disk, spec, transfer,
                                     (const double *)in[2], (const double *)in[3], (double *)out_[0]);

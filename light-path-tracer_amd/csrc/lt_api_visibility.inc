@@ -181,7 +181,7 @@ extern "C" int lt_diskmap_visibility(const float *hits, const uint8_t *n_hits, i
     DiskMapShade dm;
     int rc = resolve_diskmap(hits, R, W, max_images, metric, disk, map, texels, &ds, &dm);
     if (rc || (rc = resolve_baselines(uv, n_baselines)) || (rc = check_spectrum_times(t_start, dt, n_times))) return rc;
-    return staged_hits_call(hits, n_hits, R, W, max_images, {texels, (size_t)map->n_r * map->n_phi, 4},
+    return staged_hits_call(hits, n_hits, R, W, max_images, {{texels, (size_t)map->n_r * map->n_phi, 4}},
                             {out, (size_t)n_times, visibility_row_bytes(max_images, n_baselines, split_orders)}, [&](void *const *in, void *const *out_) {
         return lt_diskmap_visibility_dev((const float *)in[0], (const uint8_t *)in[1], R, W, max_images, metric, disk, map, (const float *)in[2], uv,
                                          n_baselines, split_orders, t_start, dt, n_times, (double *)out_[0]);

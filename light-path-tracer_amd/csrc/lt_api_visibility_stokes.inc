@@ -67,7 +67,7 @@ extern "C" int lt_disk_visibility_stokes(const float *hits, const uint8_t *n_hit
     DiskShade ds;
     int rc = resolve_disk_visibility(hits, R, W, max_images, metric, disk, &ds);
     if (rc || (rc = resolve_baselines(uv, n_baselines)) || (rc = resolve_visibility_stokes(pol, metric, field))) return rc;
-    return staged_hits_call(hits, n_hits, R, W, max_images, {pol, (size_t)R * W, (size_t)max_images * 16},
+    return staged_hits_call(hits, n_hits, R, W, max_images, {{pol, (size_t)R * W, (size_t)max_images * 16}},
                             {out, 1, visibility_stokes_row_bytes(max_images, n_baselines, split_orders)}, [&](void *const *in, void *const *out_) {
         return lt_disk_visibility_stokes_dev((const float *)in[0], (const uint8_t *)in[1], (const float *)in[2], R, W, max_images, metric, disk,
                                              field, uv, n_baselines, split_orders, (double *)out_[0]);
@@ -102,7 +102,7 @@ extern "C" int lt_hotspot_visibility_stokes(const float *hits, const uint8_t *n_
     if (rc || (rc = resolve_baselines(uv, n_baselines)) || (rc = resolve_visibility_stokes(pol, metric, field)) ||
         (rc = check_spectrum_times(t_start, dt, n_times)))
         return rc;
-    return staged_hits_call(hits, n_hits, R, W, max_images, {pol, (size_t)R * W, (size_t)max_images * 16},
+    return staged_hits_call(hits, n_hits, R, W, max_images, {{pol, (size_t)R * W, (size_t)max_images * 16}},
                             {out, (size_t)n_times, visibility_stokes_row_bytes(max_images, n_baselines, split_orders)},
                             [&](void *const *in, void *const *out_) {
         return lt_hotspot_visibility_stokes_dev((const float *)in[0], (const uint8_t *)in[1], (const float *)in[2], R, W, max_images, metric,

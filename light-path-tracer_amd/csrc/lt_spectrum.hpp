@@ -3,8 +3,8 @@
 // (image order, bin of g), for the stationary disk, the hot spot and the disk map.  The light curve's evaluation with a
 // reduction to up to SP_MAX_KEYS numbers in place of three, in a fixed order and without floating-point atomics.
 //
-// First stage (spectrum_partial; grid (SP_BLOCKS, times of this batch), 256 work-items).  A workgroup walks its pixels
-// in chunks of 256 in the light curve's stride order.  Phase one: every work-item evaluates (key, weight) of its pixel's
+// First stage (spectrum_partial over histogram_walk, the walk lt_transfer.hpp shares; grid (SP_BLOCKS, times of this
+// batch), 256 work-items).  A workgroup walks its pixels in chunks of 256 in the light curve's stride order.  Phase one: every work-item evaluates (key, weight) of its pixel's
 // stored slots; slot by slot its wavefront adds the non-zero weights of every key the slot holds with a butterfly over the
 // lanes (absent lanes add +0.0: a bracketing fixed by the lane indices) and appends one entry (key, sum) per key to the
 // wavefront's segment of LDS.  The 64 neighbouring pixels of a row share a few bins, so this leaves a few entries where
@@ -69,48 +69,56 @@ __device__ __forceinline__ double wave_sum(double v)
     return v;
 }
 
-// The first stage.  weight(rec): the emitter's unclamped intensity through one stored hit.  partial: this batch's
-// (time, block, key) sums.
-template <typename Weight>
-__device__ __forceinline__ void spectrum_partial(const float *__restrict__ hits, const uint8_t *__restrict__ n_hits, int64_t n_px,
-                                                 int max_images, const SpectrumGrid &sg, double *__restrict__ partial, Weight weight)
+// The first stage of a keyed histogram, for the spectra below and the transfer function (lt_transfer.hpp): the LDS carve-up,
+// the chunks in stride order, both phases and the write of the partial.  The workgroup keeps n_acc accumulators, for the keys
+// first ... first + n_acc - 1.  slot(rec, j, &key, &w) gives the key and the weight of stored slot j of a pixel, and leaves w
+// as it is, 0.0, where the slot does not contribute.  mine_at(&n_out) gives where this workgroup's partial starts and how
+// many of the accumulators it writes there; it is asked after the last chunk.  Tiled: other workgroups own other keys.
+// Both callables are shaped by measurement (profiles/histogram_fold_check.txt): a flag returned by slot and tested here cost
+// every kernel a compare and a select per slot, and the partial's address computed before the walk moved the loops by one
+// instruction and made the spectra of 4096 x 4096 records 0.4 to 0.8 % slower; as they are, the four spectrum kernels
+// have the registers, spills and code sizes of the bodies this walk replaced.  The lambdas capture by value, which
+// compiles here as capturing by reference does.
+// A slot contributes unless its weight is exactly 0 (a NaN weight is kept: it is the emitter's answer).  A key of another
+// tile is another workgroup's and an absent lane here, not an entry dropped after its butterfly: the butterfly for a key
+// adds the weights of the lanes that hold this key and +0.0 for every other lane, whatever those lanes hold, so the merge
+// of a key is complete -- all of a wavefront's lanes with that key in one butterfly, in the one workgroup that owns the
+// key -- and its entries reach the owner in the order (wavefront, slot) in every tiling.  What must not happen is a key
+// merged in parts (two entries of one wavefront and slot for one key): the sum of the parts brackets differently.  The
+// loop takes the leader's key and removes every lane with that key from `todo`.
+template <bool Tiled, typename Slot, typename Mine>
+__device__ __forceinline__ void histogram_walk(const float *__restrict__ hits, const uint8_t *__restrict__ n_hits, int64_t n_px,
+                                               int max_images, int n_acc, int first, Slot slot, Mine mine_at)
 {
     const int t = (int)threadIdx.x, wave = t >> 6, lane = t & 63;
-    const int cols = sg.n_bins + 2;
-    const int n_keys = min(cols * sg.planes, SP_MAX_KEYS);
     const int seg = 64 * max_images; // entries of one wavefront's segment: at most one per lane and slot
-    double *sh_acc = (double *)sp_lds, *sh_w = sh_acc + ((n_keys + 1) & ~1);
+    double *sh_acc = (double *)sp_lds, *sh_w = sh_acc + ((n_acc + 1) & ~1);
     int *sh_key = (int *)(sh_w + 4 * seg), *sh_cnt = sh_key + 4 * seg;
-    for (int k = t; k < n_keys; k += 256) sh_acc[k] = 0.0;
+    for (int k = t; k < n_acc; k += 256) sh_acc[k] = 0.0;
     for (int64_t base = (int64_t)blockIdx.x * 256; base < n_px; base += (int64_t)256 * SP_BLOCKS) {
-        // phase one: this wavefront's entries, slot by slot, one per key
+        // phase one: this wavefront's entries (key - first, sum), slot by slot, one per key
         const int64_t p = base + t;
         const float *rec = hits + (p < n_px ? p : 0) * max_images * 4;
         const int ns = p < n_px ? stored_slots(rec, n_hits, p, max_images) : 0;
         int cnt = 0;
         for (int j = 0; j < max_images; ++j) {
             double w = 0.0;
-            int key = 0;
-            if (j < ns) {
-                const float g32 = rec[j * 4 + 2];
-                if (g32 == g32) {
-                    w = weight(rec + j * 4);
-                    key = min((sg.planes > 1 ? j * cols : 0) + spectrum_bin(sg, g32), n_keys - 1);
-                }
-            }
-            const bool has = !(w == 0.0); // (a NaN weight is kept: it is the emitter's answer)
+            int key = first;
+            if (j < ns) slot(rec + j * 4, j, &key, &w);
+            key -= first;
+            const bool has = !(w == 0.0) && (!Tiled || (key >= 0 && key < n_acc));
             // one entry per key this slot holds in this wavefront: the neighbouring pixels of a row share a few bins
             for (uint64_t todo = __ballot(has); todo;) {
                 const int leader = __ffsll((unsigned long long)todo) - 1;
                 const int k = __shfl(key, leader);
-                const bool mine = has && key == k;
-                const double sum = wave_sum(mine ? w : 0.0);
+                const bool same = has && key == k;
+                const double sum = wave_sum(same ? w : 0.0);
                 if (lane == leader) {
                     sh_key[wave * seg + cnt] = k;
                     sh_w[wave * seg + cnt] = sum;
                 }
                 ++cnt;
-                todo &= ~__ballot(mine);
+                todo &= ~__ballot(same);
             }
         }
         if (lane == 0) sh_cnt[wave] = cnt;
@@ -131,8 +139,26 @@ __device__ __forceinline__ void spectrum_partial(const float *__restrict__ hits,
         __syncthreads();
     }
     __syncthreads(); // (a workgroup without a chunk: the zeroes above)
-    double *mine = partial + ((int64_t)blockIdx.y * SP_BLOCKS + blockIdx.x) * n_keys;
-    for (int k = t; k < n_keys; k += 256) mine[k] = sh_acc[k];
+    int n_out;
+    double *mine = mine_at(&n_out);
+    for (int k = t; k < n_out; k += 256) mine[k] = sh_acc[k];
+}
+
+// The spectra's first stage: one workgroup keeps every key.  weight(rec): the emitter's unclamped intensity through one
+// stored hit.  partial: this batch's (time, block, key) sums.
+template <typename Weight>
+__device__ __forceinline__ void spectrum_partial(const float *__restrict__ hits, const uint8_t *__restrict__ n_hits, int64_t n_px,
+                                                 int max_images, const SpectrumGrid &sg, double *__restrict__ partial, Weight weight)
+{
+    const int cols = sg.n_bins + 2;
+    const int n_keys = min(cols * sg.planes, SP_MAX_KEYS);
+    histogram_walk<false>(hits, n_hits, n_px, max_images, n_keys, 0,
+                          [=](const float *rec, int j, int *key, double *w) {
+        const float g32 = rec[2];
+        if (!(g32 == g32)) return; // (a NaN g has no bin)
+        *w = weight(rec);
+        *key = min((sg.planes > 1 ? j * cols : 0) + spectrum_bin(sg, g32), n_keys - 1);
+    }, [=](int *n_out) { *n_out = n_keys; return partial + ((int64_t)blockIdx.y * SP_BLOCKS + blockIdx.x) * n_keys; });
 }
 
 // The three emitters.  first: the index of this batch's first time (the disk has one row and no time).

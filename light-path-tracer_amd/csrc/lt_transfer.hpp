@@ -4,32 +4,21 @@
 // times the one spectrum_partial keeps in LDS: up to TR_MAX_KEYS = 32 768 keys against SP_MAX_KEYS = 4 112.
 //
 // First stage (k_disk_transfer_partial; grid (SP_BLOCKS, key tiles), 256 work-items).  Tile T owns the keys
-// [TR_TILE T, TR_TILE (T + 1)).  A workgroup walks its pixels in chunks of 256 in the light curve's stride order and
-// evaluates the header's steps 1 to 5 for every stored slot of its chunk -- a table interpolation and four products,
-// repeated once per tile -- and then runs the spectrum's two phases on the slots whose key lies in its tile.
-//   Phase one: slot by slot a wavefront adds the weights of every key of the tile the slot holds with the butterfly
-//   over the lanes and appends one entry (key - TR_TILE T, sum) per key to its segment of LDS.
-//   Phase two: work-item i alone owns the tile's keys = i (mod 256); every work-item scans the four segments in order
-//   -- all lanes read the same entry, a broadcast -- and adds the entries it owns.
-// After the last chunk the workgroup writes its accumulators into its partial, at the tile's place.
+// [TR_TILE T, TR_TILE (T + 1)).  A workgroup evaluates the header's steps 1 to 5 for every stored slot of its chunks -- a
+// table interpolation and four products, repeated once per tile -- and hands the slot's key and weight to the spectra's
+// walk (histogram_walk of lt_spectrum.hpp), which keeps the slots whose key lies in the tile, runs its two phases on them
+// and writes the accumulators into the workgroup's partial, at the tile's place.
 // Final stage: k_sum_blocks of lt_spectrum.hpp as it is, row = the keys of the call.
 //
-// Why a key's bits do not depend on the tiling.  The butterfly for a key adds the weights of the lanes that hold this
-// key and +0.0 for every other lane, whatever those lanes hold; a slot's keys outside the tile are therefore simply
-// absent lanes, as they are for every other key of the slot inside the tile.  The merge of a key is complete -- all of
-// a wavefront's lanes with that key in one butterfly, in the one workgroup that owns the key -- and its entries reach
-// the owner in the order (wavefront, slot) in every tiling.  What must not happen is a key merged in parts (two
-// entries of one wavefront and slot for one key): the sum of the parts brackets differently.  The loop below takes
-// the leader's key and removes every lane with that key from `todo`, as spectrum_partial does.
-//
-// Phase one is written again here and not shared with spectrum_partial: that function's entry carries the key itself
-// and its loop has no tile, and splitting it would recompile the three spectrum kernels.
+// Why a key's bits do not depend on the tiling: a slot's keys outside the tile are absent lanes of the walk's butterfly, as
+// they are for every other key of the slot inside the tile, and a key is merged whole in the one workgroup that owns it
+// (the walk's comment has the argument).
 //
 // LDS is sized by the launch (transfer_lds_bytes): TR_TILE x 8 (accumulators) + 4 x 64 max_images x (8 + 4) (entries)
 // + 16 = 57 360 B at eight images, 42 000 B at three: two workgroups share a CU's 160 KiB at eight images, three at
-// three.  The scan reads four keys per ds_read_b128; the entries' keys start 16-byte aligned (TR_TILE x 8 and
-// 4 x 64 max_images x 8 are multiples of 16) and every segment is 256 max_images bytes long.  The two tables are read
-// through __restrict__ global pointers: at most 65 536 x 16 B, they stay in L2.
+// three.  The entries' keys start 16-byte aligned (TR_TILE x 8 and 4 x 64 max_images x 8 are multiples of 16) and every
+// segment is 256 max_images bytes long.  The two tables are read through __restrict__ global pointers: at most
+// 65 536 x 16 B, they stay in L2.
 #pragma once
 #include "lt_spectrum.hpp"
 #include "lt_thermal.hpp"
@@ -101,62 +90,14 @@ __global__ void __launch_bounds__(256) k_disk_transfer_partial(const float *__re
                                                                const double *__restrict__ delay, const double *__restrict__ emis,
                                                                int n_keys, double *__restrict__ partial)
 {
-    const int t = (int)threadIdx.x, wave = t >> 6, lane = t & 63;
     const int cols = sg.n_bins + 2, rows = tr.n_tau + 2;
     const int first = (int)blockIdx.y * TR_TILE; // this tile's keys: first ... first + TR_TILE - 1
-    const int seg = 64 * max_images;             // entries of one wavefront's segment: at most one per lane and slot
-    double *sh_acc = (double *)sp_lds, *sh_w = sh_acc + TR_TILE;
-    int *sh_key = (int *)(sh_w + 4 * seg), *sh_cnt = sh_key + 4 * seg;
-    for (int k = t; k < TR_TILE; k += 256) sh_acc[k] = 0.0;
-    for (int64_t base = (int64_t)blockIdx.x * 256; base < n_px; base += (int64_t)256 * SP_BLOCKS) {
-        // phase one: this wavefront's entries, slot by slot, one per key of this tile
-        const int64_t p = base + t;
-        const float *rec = hits + (p < n_px ? p : 0) * max_images * 4;
-        const int ns = p < n_px ? stored_slots(rec, n_hits, p, max_images) : 0;
-        int cnt = 0;
-        for (int j = 0; j < max_images; ++j) {
-            double w = 0.0;
-            int key = -1;
-            if (j < ns) {
-                int k_tau, k_g;
-                if (transfer_slot(tr, sg, delay, emis, rec + j * 4, &k_tau, &k_g, &w))
-                    key = min(((sg.planes > 1 ? j * rows : 0) + k_tau) * cols + k_g, n_keys - 1) - first;
-            }
-            // (a weight of exactly 0 is not added; a key of another tile is another workgroup's: an absent lane here)
-            const bool has = !(w == 0.0) && key >= 0 && key < TR_TILE;
-            for (uint64_t todo = __ballot(has); todo;) {
-                const int leader = __ffsll((unsigned long long)todo) - 1;
-                const int k = __shfl(key, leader);
-                const bool mine = has && key == k;
-                const double sum = wave_sum(mine ? w : 0.0);
-                if (lane == leader) {
-                    sh_key[wave * seg + cnt] = k;
-                    sh_w[wave * seg + cnt] = sum;
-                }
-                ++cnt;
-                todo &= ~__ballot(mine);
-            }
-        }
-        if (lane == 0) sh_cnt[wave] = cnt;
-        __syncthreads();
-        // phase two: the owner of a key adds its entries in order
-        for (int s = 0; s < 4; ++s) {
-            const int n = sh_cnt[s];
-            const int *kk = sh_key + s * seg;
-            const double *ww = sh_w + s * seg;
-            for (int e = 0; e < n; e += 4) {
-                const int4 k4 = *(const int4 *)(kk + e);
-                if ((k4.x & 255) == t) sh_acc[k4.x] += ww[e]; // (e < n)
-                if (e + 1 < n && (k4.y & 255) == t) sh_acc[k4.y] += ww[e + 1];
-                if (e + 2 < n && (k4.z & 255) == t) sh_acc[k4.z] += ww[e + 2];
-                if (e + 3 < n && (k4.w & 255) == t) sh_acc[k4.w] += ww[e + 3];
-            }
-        }
-        __syncthreads();
-    }
-    __syncthreads(); // (a workgroup without a chunk: the zeroes above)
-    double *mine = partial + (int64_t)blockIdx.x * n_keys + first;
-    for (int k = t; k < TR_TILE && first + k < n_keys; k += 256) mine[k] = sh_acc[k];
+    histogram_walk<true>(hits, n_hits, n_px, max_images, TR_TILE, first,
+                         [=](const float *rec, int j, int *key, double *w) {
+        int k_tau, k_g;
+        if (transfer_slot(tr, sg, delay, emis, rec, &k_tau, &k_g, w)) // (which leaves w alone where it returns false)
+            *key = min(((sg.planes > 1 ? j * rows : 0) + k_tau) * cols + k_g, n_keys - 1);
+    }, [=](int *n_out) { *n_out = min(TR_TILE, n_keys - first); return partial + (int64_t)blockIdx.x * n_keys + first; });
 }
 
 } // namespace lt

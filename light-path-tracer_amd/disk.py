@@ -468,29 +468,40 @@ class Spectrum:
         return 0.5 * (e[:-1] + e[1:]) * float(E_rest)
 
 
+def _linear_bin(x, lo, hi, n):
+    """The bin rule of both grids, vectorised over float64 x: n half-open bins on [lo, hi) -> int64 column; 0 the
+    underflow, n + 1 the overflow, -1 for a NaN.  An infinity or a NaN is replaced before the floor."""
+    inv_d = n / (hi - lo)
+    nan = np.isnan(x)
+    with np.errstate(invalid="ignore", over="ignore"):
+        inner = np.floor((np.where(nan | np.isinf(x), lo, x) - lo) * inv_d)
+    k = 1 + np.minimum(np.clip(inner, 0, n).astype(np.int64), n - 1)
+    k = np.where(x < lo, 0, np.where(x >= hi, n + 1, k))
+    return np.where(nan, -1, k)
+
+
 def spectrum_bin(g, spec):
     """The header's bin rule, vectorised: the column (int64) of every g, float32 as stored, evaluated in float64;
     0 the underflow, n_bins + 1 the overflow, -1 for a NaN (skipped)."""
-    x = np.asarray(g, dtype=np.float32).astype(np.float64)
-    inv_dg = spec.n_bins / (spec.g_max - spec.g_min)
-    nan = np.isnan(x)
-    with np.errstate(invalid="ignore", over="ignore"):
-        inner = np.floor((np.where(nan | np.isinf(x), spec.g_min, x) - spec.g_min) * inv_dg)
-    k = 1 + np.minimum(np.clip(inner, 0, spec.n_bins).astype(np.int64), spec.n_bins - 1)
-    k = np.where(x < spec.g_min, 0, np.where(x >= spec.g_max, spec.n_bins + 1, k))
-    return np.where(nan, -1, k)
+    return _linear_bin(np.asarray(g, dtype=np.float32).astype(np.float64), spec.g_min, spec.g_max, spec.n_bins)
+
+
+def _keyed_sum(on, plane_slots, k_row, rows, k_col, cols, weights):
+    """(planes, rows, cols) float64: the weights of the slots `on` (..., max_images) added to the key (plane . rows + row)
+    . cols + column; plane_slots: one plane per slot (image order) instead of one for all.  The order is numpy's."""
+    m = on.shape[-1]
+    planes = m if plane_slots else 1
+    plane = np.broadcast_to(np.arange(m), on.shape) if plane_slots else np.zeros(on.shape, dtype=np.int64)
+    key = ((plane * rows + k_row) * cols + k_col)[on]
+    return np.bincount(key, weights=np.asarray(weights, dtype=np.float64)[on], minlength=planes * rows * cols).reshape(planes, rows, cols)
 
 
 def _bin_weights(hits, n_hits, spec, weights):
     """One row (planes, n_bins + 2) float64: weights (R, W, max_images) of the stored slots of hits binned by their g."""
     hits = np.asarray(hits)
-    m = hits.shape[-2]
     k = spectrum_bin(hits[..., 2], spec)
-    on = (_stored(hits, n_hits)[..., None] > np.arange(m)) & (k >= 0)
-    cols = spec.n_bins + 2
-    plane = np.broadcast_to(np.arange(m), k.shape) if spec.split_orders else np.zeros(k.shape, dtype=np.int64)
-    key = (plane * cols + k)[on]
-    return np.bincount(key, weights=np.asarray(weights, dtype=np.float64)[on], minlength=spec.planes(m) * cols).reshape(spec.planes(m), cols)
+    on = (_stored(hits, n_hits)[..., None] > np.arange(hits.shape[-2])) & (k >= 0)
+    return _keyed_sum(on, spec.split_orders, 0, 1, k, spec.n_bins + 2, weights)[:, 0]
 
 
 def spot_intensity(M, a, hits, spot, t_obs):
@@ -1274,14 +1285,7 @@ class TransferGrid:
 def transfer_bin(tau, grid):
     """The header's step 4, vectorised: the row (int64) of every float64 delay; 0 the underflow, n_tau + 1 the overflow,
     -1 for a NaN (it contributes nothing)."""
-    x = np.asarray(tau, dtype=np.float64)
-    inv_dtau = grid.n_tau / (grid.tau_max - grid.tau_min)
-    nan = np.isnan(x)
-    with np.errstate(invalid="ignore", over="ignore"):
-        inner = np.floor((np.where(nan | np.isinf(x), grid.tau_min, x) - grid.tau_min) * inv_dtau)
-    k = 1 + np.minimum(np.clip(inner, 0, grid.n_tau).astype(np.int64), grid.n_tau - 1)
-    k = np.where(x < grid.tau_min, 0, np.where(x >= grid.tau_max, grid.n_tau + 1, k))
-    return np.where(nan, -1, k)
+    return _linear_bin(np.asarray(tau, dtype=np.float64), grid.tau_min, grid.tau_max, grid.n_tau)
 
 
 def transfer_slots(hits, n_hits, exposure, spec, grid, r_min, r_max, delay, emis, t_ref):
@@ -1324,9 +1328,7 @@ def disk_transfer(hits, n_hits, exposure, spec, grid, r_min, r_max, delay, emis,
     rows, cols, planes = grid.n_tau + 2, spec.n_bins + 2, spec.planes(m)
     if planes * rows * cols > TRANSFER_MAX_KEYS:
         raise ValueError(f"disk_transfer: planes (n_tau + 2) (n_bins + 2) = {planes * rows * cols} keys exceed {TRANSFER_MAX_KEYS}")
-    plane = np.broadcast_to(np.arange(m), on.shape) if spec.split_orders else np.zeros(on.shape, dtype=np.int64)
-    key = ((plane * rows + k_tau) * cols + k_g)[on]
-    return np.bincount(key, weights=weight[on], minlength=planes * rows * cols).reshape(planes, rows, cols)
+    return _keyed_sum(on, spec.split_orders, k_tau, rows, k_g, cols, weight)
 
 
 def impulse_response(tf):

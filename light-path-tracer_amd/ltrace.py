@@ -452,10 +452,21 @@ def require_gpu():
         raise LtraceError(ERR_NO_DEVICE, "no HIP device visible; this package has no CPU path")
 
 
-def default_opts(**kw):
-    o = Opts()
-    load().lt_default_opts(C.byref(o))
+def _default(struct, fn, kw, names=None):
+    """A `struct` filled by the library's `fn` (an lt_default_*), then the keywords set in their order; names: {keyword:
+    {name: value}} for the keywords that may be given by name."""
+    s = struct()
+    getattr(load(), fn)(C.byref(s))
     for k, v in kw.items():
+        if names and k in names and isinstance(v, str):
+            v = names[k][v]
+        setattr(s, k, v)
+    return s
+
+
+def default_opts(**kw):
+    o = _default(Opts, "lt_default_opts", {})
+    for k, v in kw.items():                      # (block_owner sets n_blocks as well: the keywords keep their order)
         if k == "integrator" and isinstance(v, str):
             v = INTEGRATORS[v]
         if k == "schedule" and isinstance(v, str):
@@ -952,12 +963,7 @@ def shade(cam, background, fa, winding=None, loop_around=False, want_rgba=False)
 
 
 def default_dense_opts(**kw):
-    o = DenseOpts()
-    load().lt_default_dense_opts(C.byref(o))
-    for k, v in kw.items():
-        if v is not None:
-            setattr(o, k, v)
-    return o
+    return _default(DenseOpts, "lt_default_dense_opts", {k: v for k, v in kw.items() if v is not None})
 
 
 def integrate_dense(metric, state0, opts=None):
@@ -1073,13 +1079,7 @@ def shutdown():
 def default_disk(**kw):
     """lt_disk with the library's defaults (r_in = ISCO, r_out = 20, q = 3, exposure = 1); keywords override.
     r_in=None means the ISCO."""
-    d = Disk()
-    load().lt_default_disk(C.byref(d))
-    for k, v in kw.items():
-        if k == "r_in" and v is None:
-            v = 0.0
-        setattr(d, k, v)
-    return d
+    return _default(Disk, "lt_default_disk", {k: 0.0 if k == "r_in" and v is None else v for k, v in kw.items()})
 
 
 def kerr_isco(M, a):
@@ -1340,11 +1340,7 @@ def disk_shade_probe(metric, r, phi=0.0, xi=0.0, g=np.nan, r_in=0.0, q=3.0, expo
 
 def default_hotspot(**kw):
     """lt_hotspot with the library's defaults (r_spot 8, phi0 0, sigma 1, exposure 1, with_disk 1); keywords override."""
-    h = HotSpot()
-    load().lt_default_hotspot(C.byref(h))
-    for k, v in kw.items():
-        setattr(h, k, v)
-    return h
+    return _default(HotSpot, "lt_default_hotspot", kw)
 
 
 def _hit_arrays(hits, n_hits):
@@ -1414,11 +1410,7 @@ def hotspot_lightcurve_dev(d_hits, d_n_hits, rows, width, max_images, metric, di
 # ---- linear polarization (lt_trace_disk_pol, lt_shade_stokes, lt_hotspot_lightcurve_stokes) ------------------------
 def default_bfield(**kw):
     """lt_bfield with the library's defaults ((b_r, b_phi, b_z) = (0, 0, 1), pol_frac 0.7); keywords override."""
-    b = BField()
-    load().lt_default_bfield(C.byref(b))
-    for k, v in kw.items():
-        setattr(b, k, v)
-    return b
+    return _default(BField, "lt_default_bfield", kw)
 
 
 def trace_disk_pol(cam, metric, opts, disk, field, max_images=3,
@@ -1577,13 +1569,7 @@ MAP_ROTATIONS = {"kepler": MAP_KEPLERIAN, "rigid": MAP_RIGID}
 def default_diskmap(**kw):
     """lt_diskmap with the library's defaults (r_min 6, r_max 20, omega_p 0, exposure 1, 1 x 1 texels, Keplerian,
     with_disk 1); keywords override (rotation: "kepler" / "rigid" or the LT_MAP_* value)."""
-    m = DiskMap()
-    load().lt_default_diskmap(C.byref(m))
-    for k, v in kw.items():
-        if k == "rotation" and isinstance(v, str):
-            v = MAP_ROTATIONS[v]
-        setattr(m, k, v)
-    return m
+    return _default(DiskMap, "lt_default_diskmap", kw, {"rotation": MAP_ROTATIONS})
 
 
 def _texel_array(dmap, texels):
@@ -1653,11 +1639,7 @@ def diskmap_lightcurve_dev(d_hits, d_n_hits, rows, width, max_images, metric, di
 # ---- energy-resolved light (lt_disk_spectrum, lt_hotspot_spectrum, lt_diskmap_spectrum) ---------------------------------
 def default_spectrum(**kw):
     """lt_spectrum with the library's defaults (g 0.0625 ... 1.5625, 96 bins, not split); keywords override."""
-    s = Spectrum()
-    load().lt_default_spectrum(C.byref(s))
-    for k, v in kw.items():
-        setattr(s, k, v)
-    return s
+    return _default(Spectrum, "lt_default_spectrum", kw)
 
 
 def spectrum_planes(spec, max_images):
@@ -1733,19 +1715,20 @@ def diskmap_spectrum_dev(d_hits, d_n_hits, rows, width, max_images, metric, disk
 # ---- thermal continuum (lt_disk_thermal_spectrum, lt_shade_thermal) -----------------------------------------------------------
 def default_thermal(**kw):
     """lt_thermal with the library's defaults (r 6 ... 20, t_max 1, f_col 1, exposure 1, 2 nodes, not split); keywords override."""
-    t = Thermal()
-    load().lt_default_thermal(C.byref(t))
-    for k, v in kw.items():
-        setattr(t, k, v)
-    return t
+    return _default(Thermal, "lt_default_thermal", kw)
+
+
+def _radial_table(name, table, n_r):
+    """A radial table as the library reads it: float64, contiguous, (n_r,); one that is not the struct's n_r never reaches it."""
+    table = np.ascontiguousarray(table, dtype=np.float64)
+    if table.shape != (int(n_r),):
+        raise ValueError(f"{name} must be (n_r,) = ({int(n_r)},), got {table.shape}")
+    return table
 
 
 def _thermal_arrays(thermal, flux, nu, limit):
-    """(flux, nu) as the library reads them; a table that is not the struct's n_r, or more frequencies than an output is
-    sized for, never reach it."""
-    flux = np.ascontiguousarray(flux, dtype=np.float64)
-    if flux.shape != (int(thermal.n_r),):
-        raise ValueError(f"flux must be (n_r,) = ({int(thermal.n_r)},), got {flux.shape}")
+    """(flux, nu) as the library reads them; more frequencies than an output is sized for never reach it."""
+    flux = _radial_table("flux", flux, thermal.n_r)
     nu = np.ascontiguousarray(nu, dtype=np.float64).ravel()
     if nu.size > limit:
         raise ValueError(f"at most {limit} frequencies, got {nu.size}")
@@ -1790,11 +1773,7 @@ def shade_thermal_dev(d_hits, d_n_hits, rows, width, max_images, metric, disk, t
 # ---- reverberation (lt_disk_transfer) -----------------------------------------------------------------------------------------
 def default_transfer(**kw):
     """lt_transfer with the library's defaults (tau 0 ... 256, 64 bins, 2 nodes on r 6 ... 20, t_ref 0); keywords override."""
-    t = Transfer()
-    load().lt_default_transfer(C.byref(t))
-    for k, v in kw.items():
-        setattr(t, k, v)
-    return t
+    return _default(Transfer, "lt_default_transfer", kw)
 
 
 def transfer_keys(spec, transfer, max_images):
@@ -1803,14 +1782,8 @@ def transfer_keys(spec, transfer, max_images):
 
 
 def _transfer_tables(transfer, delay, emis):
-    """(delay, emis) as the library reads them; a table that is not the struct's n_r never reaches it."""
-    tables = []
-    for name, table in (("delay", delay), ("emis", emis)):
-        table = np.ascontiguousarray(table, dtype=np.float64)
-        if table.shape != (int(transfer.n_r),):
-            raise ValueError(f"{name} must be (n_r,) = ({int(transfer.n_r)},), got {table.shape}")
-        tables.append(table)
-    return tables
+    """(delay, emis) as the library reads them."""
+    return _radial_table("delay", delay, transfer.n_r), _radial_table("emis", emis, transfer.n_r)
 
 
 def disk_transfer(hits, n_hits, metric, disk, spec, transfer, delay, emis):
@@ -1934,13 +1907,7 @@ MOVIE_BOUNDARIES = {"hold": MOVIE_HOLD, "loop": MOVIE_LOOP}
 def default_diskmovie(**kw):
     """lt_diskmovie with the library's defaults (t0 0, dt_frame 1, 1 frame, hold); keywords override (boundary: "hold" /
     "loop" or the LT_MOVIE_* value)."""
-    mv = DiskMovie()
-    load().lt_default_diskmovie(C.byref(mv))
-    for k, v in kw.items():
-        if k == "boundary" and isinstance(v, str):
-            v = MOVIE_BOUNDARIES[v]
-        setattr(mv, k, v)
-    return mv
+    return _default(DiskMovie, "lt_default_diskmovie", kw, {"boundary": MOVIE_BOUNDARIES})
 
 
 def _movie_array(dmap, movie, texels):
@@ -2107,9 +2074,7 @@ def _aa_keywords(a, kw):
 
 def default_aa(**kw):
     """lt_aa with the library's defaults (samples = 2, plain mode, 3 images, automatic bands); keywords override."""
-    a = AA()
-    load().lt_default_aa(C.byref(a))
-    return _aa_keywords(a, kw)
+    return _aa_keywords(_default(AA, "lt_default_aa", {}), kw)
 
 
 def _fine_background(cam, samples, background):
@@ -2174,9 +2139,7 @@ def aa_band_bytes(cam, metric, opts, aa, disk=None):
 def default_aa_adaptive(**kw):
     """lt_aa_adaptive with the library's defaults (samples_lo = 1, samples_hi = 4, plain mode, 3 images, automatic
     bands and chunks, contrast = 0.0625); keywords override."""
-    a = AAAdaptive()
-    load().lt_default_aa_adaptive(C.byref(a))
-    return _aa_keywords(a, kw)
+    return _aa_keywords(_default(AAAdaptive, "lt_default_aa_adaptive", {}), kw)
 
 
 def render_aa_adaptive(cam, metric, opts, adaptive, disk=None, background_lo=None, background_hi=None,
