@@ -1369,6 +1369,85 @@ int lt_shade_thermal(const float *hits, const uint8_t *n_hits, int32_t R, int32_
                      const lt_metric *metric, const lt_disk *disk, const lt_thermal *thermal, const double *flux,
                      const double *nu, int32_t n_freq, float *out);
 
+/* ---- polarized thermal continuum: a scattering atmosphere's limb darkening and its Stokes I, Q, U ----------------- *
+ * The thermal continuum above treats every hit as an isotropic, unpolarized blackbody.  A thin disk's surface is a    *
+ * scattering atmosphere (Chandrasekhar): its light is limb-darkened and linearly polarized parallel to the surface,   *
+ * by up to 11.7 % at grazing emission, and because the hot inner disk's light is swung round by the hole the net      *
+ * angle turns with energy -- what X-ray polarimetry measures.  These entry points are lt_disk_thermal_spectrum and    *
+ * lt_shade_thermal with a weight per slot and Stokes parameter.  Nothing is traced again, and no record is new.       *
+ *                                                                                                                     *
+ * Records.  pol: float32 (R, W, max_images, 4), (q, u, sin zeta, mu) per slot as lt_trace_disk_pol writes them,       *
+ * TRACED WITH THE FIELD (0, 0, 1): the polarization rule takes the electric vector along k^ x b^, which for a field   *
+ * along the disk's normal is k^ x e_(z), the direction perpendicular to the plane of the normal and the ray -- the    *
+ * scattering atmosphere's --, and mu = |k^ . e_(z)| is the cosine both tables below depend on.  The call cannot see   *
+ * which field was traced: records of another field give that field's angles.  sin zeta and the field's pol_frac play  *
+ * no part.                                                                                                            *
+ *                                                                                                                     *
+ * Atmosphere.  lt_atmosphere and two float64 tables of n_mu nodes, node i at mu_i = i / (n_mu - 1): limb[i], the      *
+ * limb-darkening factor h(mu), 1 meaning isotropic, and poldeg[i], the polarization degree delta(mu).  Neither table  *
+ * is checked, as flux is not.                                                                                         *
+ *                                                                                                                     *
+ * The rule, per stored slot.  Steps 1 to 5 of the thermal continuum stay exactly as they are.  After them:            *
+ *   6. mu = (double)pol[3].  The slot emits nothing unless mu >= 0 && mu <= 1 (a NaN fails).  v = mu (double)(n_mu -  *
+ *      1), one rounded product;  i0 = max(min((int)floor(v), n_mu - 2), 0);  w = v - i0; h = fma(w, limb[i0 + 1] -    *
+ *      limb[i0], limb[i0]);  d = fma(w, poldeg[i0 + 1] - poldeg[i0], poldeg[i0]).                                     *
+ *   7. w_I = h,  w_Q = (h d) (double)pol[0],  w_U = (h d) (double)pol[1], every product rounded.                      *
+ *   8. With t = A / expm1(nu c) as in step 5, each of the three sums takes S = fma(w_X, t, S), an explicit fma, in    *
+ *      the order of lt_disk_thermal_spectrum -- chunk, then wavefront, lane and slot --; afterwards ((nu nu) nu) S,   *
+ *      and the final stage adds the LT_SPECTRUM_BLOCKS partials, b ascending.                                         *
+ * Consequences.  With limb identically 1 (and every stored mu in [0, 1]) the I plane has the bits of                  *
+ * lt_disk_thermal_spectrum, because fma(1, t, S) = S + t, and the band images' I plane those of lt_shade_thermal.     *
+ * With poldeg identically 0 (and h >= 0) Q and U are exactly +0.0.  A frequency's result does not depend on the other *
+ * frequencies or on their order, and the same bits come out run after run: no floating-point atomics anywhere.        *
+ *                                                                                                                     *
+ * lt_disk_thermal_spectrum_stokes.  out: float64 (planes, 3, n_freq), the Stokes axis (I, Q, U); planes and n_freq as *
+ * lt_disk_thermal_spectrum.  A plane without an emitting slot is exactly +0.0 in all three.  The partials, at most    *
+ * LT_SPECTRUM_BLOCKS x 8 x 3 x 1024 x 8 B = 48 MiB, live in the spectra's grow-only workspace, in one batch.          *
+ *                                                                                                                     *
+ * lt_shade_thermal_stokes.  out: float32 (n_freq, 3, R, W), plane-major, n_freq <= LT_THERMAL_MAX_BANDS.  Per pixel,  *
+ * band and Stokes parameter the emitting slots' terms are added in slot order in float64 by step 8's fma, the sum is  *
+ * multiplied by nu^3 and rounded once to float32, as lt_shade_thermal does.  split_orders is refused.                 *
+ *                                                                                                                     *
+ * Refusals, in this order: everything lt_disk_thermal_spectrum / lt_shade_thermal refuses up to and including the     *
+ * struct's fields (split_orders for the band images), in their order; then LT_ERR_INVALID_ARG for a null pol /        *
+ * atmosphere / limb / poldeg; n_mu outside 2 ... LT_ATMOSPHERE_MAX_NODES; n_freq outside 0 ... the limit; and a null  *
+ * out.  n_freq = 0 is LT_OK and writes nothing, even with a null out.  The outputs of a refused call are untouched.   *
+ * disk.Atmosphere / disk.atmosphere_weights / disk.thermal_spectrum_stokes / disk.shade_thermal_stokes /              *
+ * disk.polarization_degree_angle (Python) state the rule in numpy.                                                    *
+ *                                                                                                                     *
+ * Out of scope: returning radiation, ionised or absorbing atmospheres, Stokes V, the atmosphere for the spot, the map *
+ * and the movie, visibilities per frequency, a fused supersampled form, lt_render_multi.                             */
+#define LT_ATMOSPHERE_MAX_NODES 4096
+
+typedef struct lt_atmosphere {
+    int32_t n_mu;     /* nodes of the two tables, node i at mu = i / (n_mu - 1); 2 ... LT_ATMOSPHERE_MAX_NODES */
+    int32_t reserved; /* not looked at */
+} lt_atmosphere;
+
+/* The _dev forms take DEVICE pointers for the records, the tables, nu and the output and enqueue on the default stream;
+ * the others HOST pointers, staged like lt_disk_thermal_spectrum.  pol: (R, W, max_images, 4) float32; flux:
+ * thermal->n_r float64; limb, poldeg: atmosphere->n_mu float64 each; nu: n_freq float64.
+ * lt_disk_thermal_spectrum_stokes: out (planes, 3, n_freq) float64.  lt_shade_thermal_stokes: out (n_freq, 3, R, W)
+ * float32. */
+int lt_disk_thermal_spectrum_stokes_dev(const float *d_hits, const uint8_t *d_n_hits, const float *d_pol, int32_t R,
+                                        int32_t W, int32_t max_images, const lt_metric *metric, const lt_disk *disk,
+                                        const lt_thermal *thermal, const double *d_flux, const lt_atmosphere *atmosphere,
+                                        const double *d_limb, const double *d_poldeg, const double *d_nu, int32_t n_freq,
+                                        double *d_out);
+int lt_disk_thermal_spectrum_stokes(const float *hits, const uint8_t *n_hits, const float *pol, int32_t R, int32_t W,
+                                    int32_t max_images, const lt_metric *metric, const lt_disk *disk,
+                                    const lt_thermal *thermal, const double *flux, const lt_atmosphere *atmosphere,
+                                    const double *limb, const double *poldeg, const double *nu, int32_t n_freq,
+                                    double *out);
+int lt_shade_thermal_stokes_dev(const float *d_hits, const uint8_t *d_n_hits, const float *d_pol, int32_t R, int32_t W,
+                                int32_t max_images, const lt_metric *metric, const lt_disk *disk, const lt_thermal *thermal,
+                                const double *d_flux, const lt_atmosphere *atmosphere, const double *d_limb,
+                                const double *d_poldeg, const double *d_nu, int32_t n_freq, float *d_out);
+int lt_shade_thermal_stokes(const float *hits, const uint8_t *n_hits, const float *pol, int32_t R, int32_t W,
+                            int32_t max_images, const lt_metric *metric, const lt_disk *disk, const lt_thermal *thermal,
+                            const double *flux, const lt_atmosphere *atmosphere, const double *limb, const double *poldeg,
+                            const double *nu, int32_t n_freq, float *out);
+
 /* ---- reverberation: the disk's response to a flash, a delay-energy transfer function ------------------------------- *
  * Every product above asks what the disk looks like at an observer time.  X-ray timing asks the converse: a compact    *
  * source above the hole flashes once -- when, and at what energy, does the disk's echo arrive?  The answer is the 2-D  *

@@ -2304,4 +2304,5 @@ extern "C" int lt_scatter_rows_indexed_dev(const void *d_rows, void *d_full, con
 #include "lt_api_visibility_stokes.inc"
 #include "lt_api_diskmovie.inc"
 #include "lt_api_thermal.inc"
+#include "lt_api_thermal_stokes.inc"
 #include "lt_api_transfer.inc"

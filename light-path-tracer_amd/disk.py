@@ -29,7 +29,10 @@ records through the same sums (I, Q, U per baseline; lt_*_visibility_stokes), an
 The thermal continuum gives the disk a temperature: novikov_thorne_flux is the relativistic thin disk's radial flux,
 ThermalDisk a tabulated flux profile with its temperature scale, thermal_coeffs the rule that makes a stored hit a
 blackbody, and thermal_spectrum / shade_thermal the multi-colour blackbody spectrum and the band images
-(lt_disk_thermal_spectrum, lt_shade_thermal).
+(lt_disk_thermal_spectrum, lt_shade_thermal).  Atmosphere gives the disk's surface a scattering atmosphere -- limb darkening
+and a polarization degree, both tabulated on mu --, atmosphere_weights is the rule that turns a polarization record into the
+three Stokes weights, thermal_spectrum_stokes / shade_thermal_stokes carry them through the same sums
+(lt_disk_thermal_spectrum_stokes, lt_shade_thermal_stokes), and polarization_degree_angle divides the result.
 
 Reverberation bins the records by delay as well as by g: TransferGrid is the delay grid, transfer_bin its bin rule and
 disk_transfer the delay-energy transfer function of a flash above the disk (lt_disk_transfer); Lamppost / lamppost_tables
@@ -1244,6 +1247,126 @@ def shade_thermal(hits, n_hits, thermal, nu):
             total = total + np.where(emits[..., j], thermal_term(f, A, np.where(emits[..., j], c[..., j], 1.0)), 0.0)
         out[b] = (((f * f) * f) * total).astype(np.float32)
     return out
+
+
+# ---- polarized thermal continuum (lt_disk_thermal_spectrum_stokes, lt_shade_thermal_stokes) ----------------------------------
+ATMOSPHERE_MAX_NODES = 4096
+
+
+@dataclass
+class Atmosphere:
+    """A scattering atmosphere on the disk's surface (include/ltrace.h, "polarized thermal continuum"): two float64 tables of
+    n_mu nodes, node i at mu = i / (n_mu - 1), linearly interpolated -- limb, the limb-darkening factor h(mu) with 1 meaning
+    isotropic, and poldeg, the polarization degree delta(mu) of light leaving at the cosine mu to the normal.  The light is
+    polarized parallel to the surface: the records it weights are those traced with the field (0, 0, 1)."""
+    limb: np.ndarray
+    poldeg: np.ndarray
+
+    def __post_init__(self):
+        limb, poldeg = np.array(self.limb, dtype=np.float64), np.array(self.poldeg, dtype=np.float64)
+        if limb.ndim != 1 or limb.shape != poldeg.shape or not 2 <= limb.size <= ATMOSPHERE_MAX_NODES:
+            raise ValueError(f"Atmosphere: limb and poldeg must both be (n_mu,), n_mu 2 ... {ATMOSPHERE_MAX_NODES}")
+        self.limb, self.poldeg = np.ascontiguousarray(limb), np.ascontiguousarray(poldeg)
+
+    @property
+    def n_mu(self):
+        return self.limb.size
+
+    def nodes(self):
+        """The cosines of the tables' nodes, (n_mu,)."""
+        return np.arange(self.n_mu) / float(self.n_mu - 1)
+
+    def to_lt(self):
+        """The lt_atmosphere struct of these tables (ltrace.Atmosphere); the tables themselves are passed beside it."""
+        import ltrace
+        return ltrace.Atmosphere(self.n_mu, 0)
+
+    @classmethod
+    def isotropic(cls, n_mu=2):
+        """No atmosphere: h = 1 and delta = 0 at every node.  The I plane is then the unpolarized continuum's, Q and U are 0."""
+        return cls(np.ones(int(n_mu)), np.zeros(int(n_mu)))
+
+    @classmethod
+    def chandrasekhar(cls, n_mu=257):
+        """A pure electron-scattering atmosphere by a closed-form fit: h proportional to 1 + 2.3 mu - 0.3 mu^2, normalized so that
+        2 int_0^1 h mu dmu = 1 (h = (1 + 2.3 mu - 0.3 mu^2) / (143 / 60): the atmosphere redistributes the flux and does not
+        change it), and delta = 0.1171 (1 - mu) / (1 + 3.582 mu), 11.71 % at grazing emission and 0 along the normal.
+        The fit's coefficients are quoted from memory of the literature and were not checked against Chandrasekhar's table
+        when this was written: callers who hold the table pass it to Atmosphere(limb, poldeg) themselves."""
+        mu = np.arange(int(n_mu)) / float(int(n_mu) - 1)
+        return cls((1.0 + 2.3 * mu - 0.3 * mu * mu) / (143.0 / 60.0), 0.1171 * (1.0 - mu) / (1.0 + 3.582 * mu))
+
+
+def atmosphere_weights(pol, atmosphere):
+    """The header's steps 6 and 7 for every slot of pol (..., max_images, 4) float32 (q, u, sin zeta, mu) -> (w, ok): w
+    (..., max_images, 3) float64, the weights (w_I, w_Q, w_U) = (h, (h d) q, (h d) u) with h and d interpolated at mu by fma,
+    and ok (..., max_images), whether the slot's mu lies in [0, 1] (w = 0 elsewhere).  Every operation is the header's, in
+    its order and rounded as there."""
+    p = np.asarray(pol, dtype=np.float32).astype(np.float64)
+    mu, n = p[..., 3], atmosphere.n_mu
+    with np.errstate(invalid="ignore"):
+        ok = (mu >= 0.0) & (mu <= 1.0)
+    v = np.where(ok, mu, 0.0) * float(n - 1)
+    i0 = np.clip(np.floor(v).astype(np.int64), 0, n - 2)
+    wt = v - i0.astype(np.float64)
+    limb, poldeg = atmosphere.limb, atmosphere.poldeg
+    h = fma(wt, limb[i0 + 1] - limb[i0], limb[i0])
+    d = fma(wt, poldeg[i0 + 1] - poldeg[i0], poldeg[i0])
+    hd = h * d
+    with np.errstate(invalid="ignore"):
+        w = np.stack([h, hd * p[..., 0], hd * p[..., 1]], axis=-1)
+    return np.where(ok[..., None], w, 0.0), ok
+
+
+def thermal_spectrum_stokes(hits, n_hits, pol, thermal, atmosphere, nu):
+    """lt_disk_thermal_spectrum_stokes restated: (planes, 3, n_freq) float64, per plane, Stokes parameter (I, Q, U) and frequency
+    ((nu nu) nu) times the sum of w_X A / expm1(nu c) over the emitting slots of all pixels (the products are rounded and the
+    order of the sum is numpy's, where the kernel adds by fma in its own order); planes as thermal_spectrum's."""
+    nu = _frequencies(nu, THERMAL_MAX_FREQS)
+    A, c, emits = thermal_coeffs(hits, n_hits, thermal)
+    w, ok = atmosphere_weights(pol, atmosphere)
+    emits = emits & ok
+    out = np.zeros((thermal.planes(c.shape[-1]), 3, nu.size))
+    for plane in range(out.shape[0]):
+        on = emits[..., plane] if thermal.split_orders else emits
+        cp, wp = (c[..., plane][on], w[..., plane, :][on]) if thermal.split_orders else (c[on], w[on])
+        for k in range(0, nu.size, 8):
+            f = nu[k:k + 8, None]
+            t = thermal_term(f, A, cp[None, :])
+            for x in range(3):
+                out[plane, x, k:k + 8] = ((f[:, 0] * f[:, 0]) * f[:, 0]) * (wp[None, :, x] * t).sum(axis=-1)
+    return out
+
+
+def shade_thermal_stokes(hits, n_hits, pol, thermal, atmosphere, nu):
+    """lt_shade_thermal_stokes restated: (n_freq, 3, R, W) float32 band images -- per pixel, band and Stokes parameter the emitting
+    slots' w_X A / expm1(nu c) added in slot order in float64 by fma, times (nu nu) nu, rounded once to float32."""
+    if thermal.split_orders:
+        raise ValueError("shade_thermal_stokes: a band image has one plane per band; split_orders must be off")
+    nu = _frequencies(nu, THERMAL_MAX_BANDS)
+    A, c, emits = thermal_coeffs(hits, n_hits, thermal)
+    w, ok = atmosphere_weights(pol, atmosphere)
+    emits = emits & ok
+    out = np.zeros((nu.size, 3) + c.shape[:-1], dtype=np.float32)
+    for b, f in enumerate(nu):
+        total = np.zeros((3,) + c.shape[:-1])
+        for j in range(c.shape[-1]):
+            t = np.where(emits[..., j], thermal_term(f, A, np.where(emits[..., j], c[..., j], 1.0)), 0.0)
+            for s_ in range(3):
+                total[s_] = np.where(emits[..., j], fma(w[..., j, s_], t, total[s_]), total[s_])
+        out[b] = (((f * f) * f) * total).astype(np.float32)
+    return out
+
+
+def polarization_degree_angle(iqu, axis=-2):
+    """(sqrt(Q^2 + U^2) / I, atan2(U, Q) / 2) of Stokes parameters whose axis `axis` is (I, Q, U) -- the last but one of
+    thermal_spectrum_stokes' (planes, 3, n_freq); axis=1 for the band images' (n_bands, 3, R, W).  The degree is NaN where I is
+    0; the angle, in radians in (-pi/2, pi/2], is counted from the screen's e_1 towards e_2 as (q, u) of the records are."""
+    iqu = np.moveaxis(np.asarray(iqu, dtype=np.float64), axis, 0)
+    i, q, u = iqu[0], iqu[1], iqu[2]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        deg = np.where(i == 0, np.nan, np.hypot(q, u) / np.where(i == 0, 1.0, i))
+    return deg, 0.5 * np.arctan2(u, q)
 
 
 # ---- reverberation (lt_disk_transfer) ---------------------------------------------------------------------------------------------

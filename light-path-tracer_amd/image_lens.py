@@ -304,7 +304,7 @@ def render_frame(source_image, metric, r_obs, fov, psi=(0.0, 0.0), theta_obs=np.
 
 def render_sequence(source_image, metric, r_obs, fov, disk, hotspot, times, shape=None, psi=(0.0, 0.0), theta_obs=np.pi / 2,
                     integrator=None, precision=None, bfield=None, samples=None, diskmap=None, spectrum=None, baselines=None,
-                    thermal=None, frequencies=None, bands=None, lamppost=None, transfer=None):
+                    thermal=None, frequencies=None, bands=None, lamppost=None, transfer=None, atmosphere=None):
     """A moving picture from ONE trace: an optically thin disk (disk.TransparentDisk) with a hot spot (disk.HotSpot) on a
     circular orbit, at the observer times `times`.  The rays are traced once with the light-travel time of every hit
     (lt_trace_disk_hits); each frame is a re-shade of the stored hits (lt_shade_hotspot) over `base`, the lensed
@@ -345,6 +345,13 @@ def render_sequence(source_image, metric, r_obs, fov, disk, hotspot, times, shap
     max_images with thermal.split_orders), and `thermal_frequencies`; with `samples` it is the fine records' divided by S^2,
     as `disk_spectrum`.  bands (up to 16 frequencies): the result also gains `thermal_bands` (n_bands, H, W) float32, the
     unclamped band images (lt_shade_thermal; with `samples` the fine images resolved S x S -> 1 per plane by aa.resolve).
+    atmosphere (disk.Atmosphere) with thermal: the disk's surface is a scattering atmosphere.  The rays are traced with the
+    polarization records of the field (0, 0, 1) (lt_trace_disk_pol; a bfield given as well must point along (0, 0, +-1),
+    whose records are the same), and the result gains `thermal_spectrum_stokes` (planes, 3, n_freq) float64
+    (lt_disk_thermal_spectrum_stokes) and `thermal_bands_stokes` (n_bands, 3, H, W) float32 (lt_shade_thermal_stokes), the
+    Stokes axis (I, Q, U), divided or resolved with `samples` exactly as the thermal entries are, and `pol`.
+    `thermal_spectrum` and `thermal_bands` stay the isotropic, unpolarized ones; disk.polarization_degree_angle divides.
+    A map is not polarized: atmosphere with diskmap is refused.
     lamppost (disk.Lamppost) with transfer (disk.TransferGrid) and spectrum (the g axis): the result gains `transfer`
     (planes, n_tau + 2, n_bins + 2) float64, the disk's delay-energy response to a flash of that source (lt_disk_transfer;
     planes as the spectrum's; with `samples` the fine records' divided by S^2), `transfer_tau_edges` (n_tau + 1,) and
@@ -359,6 +366,12 @@ def render_sequence(source_image, metric, r_obs, fov, disk, hotspot, times, shap
         raise ValueError("render_sequence: thermal needs frequencies= (the spectrum) or bands= (the band images)")
     if thermal is None and (frequencies is not None or bands is not None):
         raise ValueError("render_sequence: frequencies= and bands= belong to thermal=ThermalDisk(...)")
+    if atmosphere is not None and thermal is None:
+        raise ValueError("render_sequence: atmosphere= belongs to thermal=ThermalDisk(...)")
+    if atmosphere is not None and diskmap is not None:
+        raise ValueError("render_sequence: a disk map is not polarized; pass atmosphere=None")
+    if atmosphere is not None and bfield is not None and not (bfield.b_r == 0.0 and bfield.b_phi == 0.0 and abs(bfield.b_z) > 0.0):
+        raise ValueError("render_sequence: an atmosphere's polarization is that of the field (0, 0, +-1); pass such a bfield or none")
     if diskmap is not None and hotspot is not None:
         raise ValueError("render_sequence: a disk map together with a hot spot is out of scope; pass hotspot=None")
     if diskmap is not None and bfield is not None:
@@ -394,8 +407,9 @@ def render_sequence(source_image, metric, r_obs, fov, disk, hotspot, times, shap
     d, spot = disk.to_lt(), hotspot.to_lt() if diskmap is None else None
     m = int(getattr(disk, "max_images", 3))
     field = bfield.to_lt() if bfield is not None else None
-    if field is not None:
-        traced = ltrace.trace_disk_pol(cam, met, opts, d, field, max_images=m, want=("hits", "n_hits", "pol"))
+    if field is not None or atmosphere is not None:
+        normal = field if field is not None else ltrace.default_bfield(b_r=0.0, b_phi=0.0, b_z=1.0)
+        traced = ltrace.trace_disk_pol(cam, met, opts, d, normal, max_images=m, want=("hits", "n_hits", "pol"))
     else:
         traced = ltrace.trace_disk_hits(cam, met, opts, d, max_images=m, want=("hits", "n_hits"))
     if diskmap is not None:
@@ -441,7 +455,7 @@ def render_sequence(source_image, metric, r_obs, fov, disk, hotspot, times, shap
             k = 1 if S is None else S
             shape = (traced["hits"].shape[0] // k, traced["hits"].shape[1] // k)
             out.update(visibility_stokes=baselines.recentre(dyn, shape, k), disk_visibility_stokes=baselines.recentre(still, shape, k))
-    _sequence_thermal(out, traced, met, d, thermal, frequencies, bands, S)
+    _sequence_thermal(out, traced, met, d, thermal, frequencies, bands, S, atmosphere)
     _sequence_transfer(out, traced, met, d, disk, lamppost, transfer, spectrum, r_obs, theta_obs, S)
     if S is not None:
         out["samples"] = S
@@ -463,8 +477,9 @@ def _sequence_spectra(out, traced, met, d, sp, dyn, S):
     out.update(spectrum=dyn / scale, disk_spectrum=line / scale)
 
 
-def _sequence_thermal(out, traced, met, d, thermal, frequencies, bands, S):
-    """render_sequence's `thermal_spectrum` (in output-pixel units, as `disk_spectrum`) and `thermal_bands`."""
+def _sequence_thermal(out, traced, met, d, thermal, frequencies, bands, S, atmosphere=None):
+    """render_sequence's `thermal_spectrum` (in output-pixel units, as `disk_spectrum`) and `thermal_bands`, and with an
+    atmosphere their Stokes forms, scaled and resolved the same way."""
     if thermal is None:
         return
     th = thermal.to_lt()
@@ -479,6 +494,21 @@ def _sequence_thermal(out, traced, met, d, thermal, frequencies, bands, S):
             import aa
             img = np.stack([aa.resolve(plane, S) for plane in img])
         out["thermal_bands"] = img
+    if atmosphere is None:
+        return
+    out["pol"] = traced["pol"]
+    rec = (traced["hits"], traced["n_hits"], traced["pol"], met, d)
+    if frequencies is not None:
+        th.split_orders = int(thermal.split_orders)
+        sp = ltrace.thermal_spectrum_stokes(*rec, th, thermal.flux, atmosphere.limb, atmosphere.poldeg, nu)
+        out["thermal_spectrum_stokes"] = sp / np.float64(1 if S is None else S * S)
+    if bands is not None:
+        th.split_orders = 0
+        img = ltrace.shade_thermal_stokes(*rec, th, thermal.flux, atmosphere.limb, atmosphere.poldeg, bands)
+        if S is not None and img.shape[0]:
+            import aa
+            img = np.stack([np.stack([aa.resolve(plane, S) for plane in band]) for band in img])
+        out["thermal_bands_stokes"] = img
 
 
 def _sequence_transfer(out, traced, met, d, disk, lamppost, transfer, spectrum, r_obs, theta_obs, S):
@@ -588,6 +618,21 @@ def thermal_from_args(args, disk=None, M=1.0, a=0.0):
     return ThermalDisk.novikov_thorne(M, a, disk.r_out, t_max=t_max, f_col=f_col), nu, bands
 
 
+def atmosphere_from_args(args):
+    """disk.Atmosphere of --thermal-atmosphere chandrasekhar|isotropic, or None.  Refused without --thermal, with a map (which
+    is not polarized) and with a --bfield that does not point along the disk's normal."""
+    from disk import Atmosphere
+    if args.thermal_atmosphere is None:
+        return None
+    if args.thermal is None:
+        raise ValueError("--thermal-atmosphere needs --thermal T_MAX [F_COL]")
+    if args.disk_map is not None:
+        raise ValueError("--thermal-atmosphere: a map is not polarized; use it with --hotspot or --bfield 0 0 1")
+    if args.bfield is not None and not (args.bfield[0] == 0.0 and args.bfield[1] == 0.0 and args.bfield[2] != 0.0):
+        raise ValueError("--thermal-atmosphere: the atmosphere's polarization is that of --bfield 0 0 1; use that field or none")
+    return Atmosphere.chandrasekhar() if args.thermal_atmosphere == "chandrasekhar" else Atmosphere.isotropic()
+
+
 def transfer_from_args(args, disk=None, M=1.0, a=0.0):
     """(disk.Lamppost, disk.TransferGrid) of --lamppost H --transfer TAU_MIN TAU_MAX N, or None: the g axis is --spectrum's.
     Refused without a sequence, without --spectrum and without the optically thin disk."""
@@ -684,13 +729,15 @@ def main_sequence(args, disk):
     the polarized visibilities (I, Q, U per baseline) of the spot and of the disk.
     --thermal T_MAX [F_COL] with --thermal-frequencies NU_MIN NU_MAX N and / or --thermal-bands NU ...: also the disk's thermal
     continuum of a Novikov-Thorne flux profile -- its spectrum at N log-spaced frequencies with the frequencies, and the
-    unclamped band images -- as .npy.
+    unclamped band images -- as .npy.  --thermal-atmosphere chandrasekhar|isotropic: also the continuum of a scattering
+    atmosphere -- the Stokes spectrum, the polarization degree and angle per frequency and the Stokes band images -- as .npy.
     --lamppost H --transfer TAU_MIN TAU_MAX N (with --spectrum for the g axis): also the disk's delay-energy response to a
     flash of a source on the axis at r = H M, the delay grid's edges and the two radial tables, as .npy."""
     from disk import BField, HotSpot
     spec = spectrum_from_args(args)
     base_lines = baselines_from_args(args)
     thermal_from_args(args)                                   # (its refusals that need no disk come before the others')
+    atmos = atmosphere_from_args(args)
     transfer_from_args(args)
     if args.disk_map is not None and args.hotspot is not None:
         raise ValueError("--disk-map: a map together with --hotspot is out of scope; use one of them")
@@ -720,7 +767,7 @@ def main_sequence(args, disk):
     out = render_sequence(None, metric, args.r_obs * metric.M, fov, disk, spot, t0 + dt * np.arange(n), shape=(height, width),
                           psi=(np.radians(args.psi_y), np.radians(args.psi_x)), theta_obs=np.radians(args.theta_obs), bfield=field,
                           samples=args.samples, diskmap=dmap, spectrum=spec, baselines=base_lines, thermal=thermal, frequencies=nu,
-                          bands=bands, lamppost=lamp, transfer=tgrid)
+                          bands=bands, lamppost=lamp, transfer=tgrid, atmosphere=atmos)
     stem = args.output[:-4] if args.output.lower().endswith(".png") else args.output
     for i in range(n):
         write_png_rgba8(f"{stem}_{i:04d}.png", out["rgba"][i])
@@ -756,6 +803,16 @@ def main_sequence(args, disk):
         print(f"Thermal continuum: Novikov-Thorne disk, t_max {thermal.t_max:g}, f_col {thermal.f_col:g} -> "
               + ", ".join(([f"{stem}_thermal_spectrum.npy, {stem}_thermal_frequencies.npy"] if nu is not None else [])
                           + ([f"{stem}_thermal_bands.npy"] if bands is not None else [])))
+        if atmos is not None:
+            from disk import polarization_degree_angle
+            if nu is not None:
+                np.save(stem + "_thermal_spectrum_stokes.npy", out["thermal_spectrum_stokes"])
+                np.save(stem + "_thermal_polarization.npy", np.stack(polarization_degree_angle(out["thermal_spectrum_stokes"]), axis=-2))
+            if bands is not None:
+                np.save(stem + "_thermal_bands_stokes.npy", out["thermal_bands_stokes"])
+            print(f"Scattering atmosphere ({args.thermal_atmosphere}), Stokes I, Q, U -> "
+                  + ", ".join(([f"{stem}_thermal_spectrum_stokes.npy, {stem}_thermal_polarization.npy (degree, angle per frequency)"]
+                               if nu is not None else []) + ([f"{stem}_thermal_bands_stokes.npy"] if bands is not None else [])))
     if lamp is not None:
         np.save(stem + "_transfer.npy", out["transfer"])
         np.save(stem + "_transfer_tau_edges.npy", out["transfer_tau_edges"])
@@ -1065,6 +1122,9 @@ def build_parser():
                     help="--thermal: the spectrum at N (1 ... 1024) log-spaced frequencies; writes it and the frequencies as .npy")
     ap.add_argument("--thermal-bands", type=float, nargs="+", default=None, metavar="NU",
                     help="--thermal: the unclamped image at each of up to 16 frequencies; writes them as one .npy (n_bands, H, W)")
+    ap.add_argument("--thermal-atmosphere", choices=("chandrasekhar", "isotropic"), default=None,
+                    help="--thermal: the disk's surface is a scattering atmosphere: also writes the Stokes spectrum (planes, 3, N), the "
+                         "polarization degree and angle per frequency and the Stokes band images (n_bands, 3, H, W) as .npy")
     ap.add_argument("--lamppost", type=float, default=None, metavar="H",
                     help="with --transfer: a point source on the spin axis at r = H (in M) that flashes once, the lamp-post corona")
     ap.add_argument("--transfer", type=float, nargs=3, default=None, metavar=("TAU_MIN", "TAU_MAX", "N"),

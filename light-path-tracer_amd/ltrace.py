@@ -118,6 +118,14 @@ class Thermal(C.Structure):
 THERMAL_MAX_NODES, THERMAL_MAX_FREQS, THERMAL_MAX_BANDS = 65536, 1024, 16
 
 
+class Atmosphere(C.Structure):
+    """lt_atmosphere: the size of a scattering atmosphere's two tables on mu (limb, poldeg), node i at mu = i / (n_mu - 1)."""
+    _fields_ = [("n_mu", C.c_int32), ("reserved", C.c_int32)]
+
+
+ATMOSPHERE_MAX_NODES = 4096
+
+
 class Transfer(C.Structure):
     """lt_transfer: the delay grid of a transfer function, the range and size of its two radial tables (delay, emis) and
     the direct flash's arrival time t_ref that every delay is counted from."""
@@ -398,6 +406,13 @@ for _name in ("lt_disk_thermal_spectrum", "lt_shade_thermal"):
     for _suffix in ("", "_dev"):
         SIGNATURES[_name + _suffix] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Metric), C.POINTER(Disk),
                                                  C.POINTER(Thermal), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p])
+
+# the polarized thermal continuum: (hits, n_hits, pol, R, W, max_images, metric, disk, thermal, flux, atmosphere, limb, poldeg, nu, n_freq, out)
+for _name in ("lt_disk_thermal_spectrum_stokes", "lt_shade_thermal_stokes"):
+    for _suffix in ("", "_dev"):
+        SIGNATURES[_name + _suffix] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Metric),
+                                                 C.POINTER(Disk), C.POINTER(Thermal), C.c_void_p, C.POINTER(Atmosphere), C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_int32, C.c_void_p])
 
 
 # the reverberation response: (hits, n_hits, R, W, max_images, metric, disk, spec, transfer, delay, emis, out)
@@ -2058,6 +2073,59 @@ def hotspot_visibility_stokes_dev(d_hits, d_n_hits, d_pol, rows, width, max_imag
     """Device-pointer form of hotspot_visibility_stokes (lt_hotspot_visibility_stokes_dev); uv stays a host array."""
     _visibility_dev(load().lt_hotspot_visibility_stokes_dev, (d_hits, d_n_hits, d_pol), (rows, width, max_images),
                     (C.byref(metric), C.byref(disk), C.byref(spot), C.byref(field)), uv, split_orders, _times(t_start, dt, n_times), d_out)
+
+
+# ---- polarized thermal continuum (lt_disk_thermal_spectrum_stokes, lt_shade_thermal_stokes) --------------------------------
+def _atmosphere_tables(limb, poldeg):
+    """(lt_atmosphere, limb, poldeg) as the library reads them: two float64 tables of one size, 2 ... ATMOSPHERE_MAX_NODES nodes."""
+    limb, poldeg = np.ascontiguousarray(limb, dtype=np.float64), np.ascontiguousarray(poldeg, dtype=np.float64)
+    if limb.ndim != 1 or limb.shape != poldeg.shape or not 2 <= limb.size <= ATMOSPHERE_MAX_NODES:
+        raise ValueError(f"limb and poldeg must both be (n_mu,), n_mu 2 ... {ATMOSPHERE_MAX_NODES}; got {limb.shape} and {poldeg.shape}")
+    return Atmosphere(limb.size, 0), limb, poldeg
+
+
+def thermal_spectrum_stokes(hits, n_hits, pol, metric, disk, thermal, flux, limb, poldeg, nu):
+    """The thermal spectrum of a scattering atmosphere from stored hits (lt_disk_thermal_spectrum_stokes) -> (planes, 3, n_freq)
+    float64, the Stokes axis (I, Q, U); pol the (rows, W, max_images, 4) records of trace_disk_pol for the field (0, 0, 1), limb
+    and poldeg the atmosphere's tables on mu, the rest as thermal_spectrum.  With limb = 1 the I plane has thermal_spectrum's bits."""
+    hits, nh, pol = _pol_records(hits, n_hits, pol)
+    R, W, m = hits.shape[:3]
+    flux, nu = _thermal_arrays(thermal, flux, nu, THERMAL_MAX_FREQS)
+    atm, limb, poldeg = _atmosphere_tables(limb, poldeg)
+    out = np.empty((min(m, DISK_MAX_IMAGES) if thermal.split_orders else 1, 3, nu.size))
+    _check(load().lt_disk_thermal_spectrum_stokes(_np_ptr(hits), _np_ptr(nh), _np_ptr(pol), R, W, m, C.byref(metric), C.byref(disk),
+                                                  C.byref(thermal), _np_ptr(flux), C.byref(atm), _np_ptr(limb), _np_ptr(poldeg), _np_ptr(nu),
+                                                  nu.size, _np_ptr(out)))
+    return out
+
+
+def thermal_spectrum_stokes_dev(d_hits, d_n_hits, d_pol, rows, width, max_images, metric, disk, thermal, d_flux, n_mu, d_limb, d_poldeg, d_nu,
+                                n_freq, d_out):
+    """Device-pointer form of thermal_spectrum_stokes (lt_disk_thermal_spectrum_stokes_dev); enqueues on the default stream."""
+    _check(load().lt_disk_thermal_spectrum_stokes_dev(_p(d_hits), _p(d_n_hits), _p(d_pol), rows, width, max_images, C.byref(metric),
+                                                      C.byref(disk), C.byref(thermal), _p(d_flux), C.byref(Atmosphere(int(n_mu), 0)),
+                                                      _p(d_limb), _p(d_poldeg), _p(d_nu), n_freq, _p(d_out)))
+
+
+def shade_thermal_stokes(hits, n_hits, pol, metric, disk, thermal, flux, limb, poldeg, nu):
+    """The band images of a scattering atmosphere from stored hits (lt_shade_thermal_stokes) -> (n_bands, 3, rows, W) float32,
+    unclamped, the Stokes axis (I, Q, U).  With limb = 1 the I planes have shade_thermal's bits."""
+    hits, nh, pol = _pol_records(hits, n_hits, pol)
+    R, W, m = hits.shape[:3]
+    flux, nu = _thermal_arrays(thermal, flux, nu, THERMAL_MAX_BANDS)
+    atm, limb, poldeg = _atmosphere_tables(limb, poldeg)
+    out = np.empty((nu.size, 3, R, W), dtype=np.float32)
+    _check(load().lt_shade_thermal_stokes(_np_ptr(hits), _np_ptr(nh), _np_ptr(pol), R, W, m, C.byref(metric), C.byref(disk), C.byref(thermal),
+                                          _np_ptr(flux), C.byref(atm), _np_ptr(limb), _np_ptr(poldeg), _np_ptr(nu), nu.size, _np_ptr(out)))
+    return out
+
+
+def shade_thermal_stokes_dev(d_hits, d_n_hits, d_pol, rows, width, max_images, metric, disk, thermal, d_flux, n_mu, d_limb, d_poldeg, d_nu,
+                             n_freq, d_out):
+    """Device-pointer form of shade_thermal_stokes (lt_shade_thermal_stokes_dev); enqueues on the default stream."""
+    _check(load().lt_shade_thermal_stokes_dev(_p(d_hits), _p(d_n_hits), _p(d_pol), rows, width, max_images, C.byref(metric), C.byref(disk),
+                                              C.byref(thermal), _p(d_flux), C.byref(Atmosphere(int(n_mu), 0)), _p(d_limb), _p(d_poldeg),
+                                              _p(d_nu), n_freq, _p(d_out)))
 
 
 # ---- supersampled frames (lt_render_aa) ---------------------------------------------------------------------------
