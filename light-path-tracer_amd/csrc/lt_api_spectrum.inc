@@ -45,14 +45,14 @@ static int check_times_and_out(double t_start, double dt, int32_t n_times, const
 }
 
 // A host-pointer reduction through its _dev form (staged_call): the records, their counts and the further inputs `more` --
-// none, one or two: the polarization records, the map's texels, the thermal and the transfer tables (a null array stays null
-// and takes no room) -- staged as in[0], in[1], in[2], in[3], and the rows of `out` fetched.
+// none to five: the polarization records, the map's texels, the thermal, the atmosphere's and the transfer tables (a null
+// array stays null and takes no room) -- staged as in[0], in[1], in[2] ... in[6], and the rows of `out` fetched.
 template <typename Dev>
 static int staged_hits_call(const float *hits, const uint8_t *n_hits, int32_t R, int32_t W, int32_t max_images,
                             std::initializer_list<HostArray> more, const HostArray &out, Dev dev)
 {
     const size_t n = (size_t)R * W;
-    HostArray ins[4] = {{hits, n, (size_t)max_images * 16}, {n_hits, n, 1}, {}, {}};
+    HostArray ins[7] = {{hits, n, (size_t)max_images * 16}, {n_hits, n, 1}};
     std::copy(more.begin(), more.end(), ins + 2);
     return staged_call(ins, {out}, dev);
 }

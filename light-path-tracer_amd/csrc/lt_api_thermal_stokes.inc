@@ -1,10 +1,11 @@
 // lt_api_thermal_stokes.inc -- included at the end of lt_api.hip, after lt_api_thermal.inc.
 //
 // Host side of the polarized thermal continuum (include/ltrace.h, "polarized thermal continuum"): the refusals in the
-// header's order -- the thermal continuum's through its struct (resolve_thermal), then the polarization records and the
-// atmosphere's pointers, n_mu, n_freq and the output (check_freqs_and_out) --, and the launches of lt_thermal_stokes.hpp on
-// the default stream.  The host forms stage seven inputs, more than staged_hits_call holds, so they go through staged_call
-// itself (staged_thermal_stokes_call), with the records first, as it has them.
+// header's order -- the thermal continuum's through its struct, then the polarization records and the atmosphere's
+// pointers, n_mu, n_freq and the output: resolve_thermal with resolve_atmosphere in its middle --, and the launches of
+// lt_thermal_stokes.hpp on the default stream.  The host forms stage seven inputs through staged_hits_call, the polarization
+// records first among the further ones, as in lt_api_visibility_stokes.inc: in[0] ... in[6] are hits, n_hits, pol, flux,
+// limb, poldeg, nu.
 
 #include "lt_thermal_stokes.hpp"
 
@@ -12,7 +13,7 @@ static_assert(ATM_MAX_NODES == LT_ATMOSPHERE_MAX_NODES, "lt_thermal_stokes.hpp r
 static_assert((size_t)LT_SPECTRUM_BLOCKS * LT_DISK_MAX_IMAGES * 3 * LT_THERMAL_MAX_FREQS * sizeof(double) <= (size_t)LT_SPECTRUM_WORKSPACE_BYTES,
               "the partials of the most planes, three Stokes parameters and the most frequencies fit the spectra's workspace in one batch");
 
-// The refusals behind resolve_thermal's and before the frequencies': the pointers, then n_mu.
+// The refusals behind resolve_thermal's own and before the frequencies': the pointers, then n_mu.
 static int resolve_atmosphere(const void *pol, const lt_atmosphere *atm, const double *limb, const double *poldeg, AtmosphereShade *as)
 {
     if (!pol || !atm || !limb || !poldeg) return fail(LT_ERR_INVALID_ARG, "null pol / atmosphere / limb / poldeg");
@@ -29,33 +30,14 @@ extern "C" int lt_disk_thermal_spectrum_stokes_dev(const float *d_hits, const ui
 {
     ThermalShade ts;
     AtmosphereShade as;
-    int rc = resolve_thermal(d_hits, R, W, max_images, metric, disk, thermal, d_flux, d_nu, false, &ts);
-    if (rc || (rc = resolve_atmosphere(d_pol, atmosphere, d_limb, d_poldeg, &as)) ||
-        (rc = check_freqs_and_out(n_freq, LT_THERMAL_MAX_FREQS, d_out)) || n_freq == 0)
-        return rc;
-    const int planes = thermal->split_orders ? max_images : 1;
-    const dim3 grid(SP_BLOCKS, 1, (unsigned)((n_freq + 255) / 256));
+    const int rc = resolve_thermal(d_hits, R, W, max_images, metric, disk, thermal, d_flux, d_nu, false, n_freq, d_out, &ts,
+                                   [&]() { return resolve_atmosphere(d_pol, atmosphere, d_limb, d_poldeg, &as); });
+    if (rc || n_freq == 0) return rc;
     const size_t lds = thermal_stokes_lds_bytes(max_images);
-    return launch_two_stage(1, planes * 3 * n_freq, d_out, [&](double *partial) {
-        if (planes > 1)
-            k_thermal_spectrum_stokes_partial<DISK_MAX_IMAGES><<<grid, 256, lds>>>(d_hits, d_n_hits, d_pol, (int64_t)R * W, max_images, ts, d_flux,
+    return launch_thermal_spectrum(thermal, max_images, n_freq, 3, d_out, [&](auto np, dim3 grid, int planes, double *partial) {
+        k_thermal_spectrum_stokes_partial<decltype(np)::value><<<grid, 256, lds>>>(d_hits, d_n_hits, d_pol, (int64_t)R * W, max_images, ts, d_flux,
                                                                                  as, d_nu, n_freq, planes, partial);
-        else
-            k_thermal_spectrum_stokes_partial<1><<<grid, 256, lds>>>(d_hits, d_n_hits, d_pol, (int64_t)R * W, max_images, ts, d_flux, as, d_nu,
-                                                                     n_freq, planes, partial);
     });
-}
-
-// A host form through its _dev form: the seven inputs staged, the records first as staged_hits_call has them -- in[0] ...
-// in[6] are hits, n_hits, pol, flux, limb, poldeg, nu.
-template <typename Dev>
-static int staged_thermal_stokes_call(const float *hits, const uint8_t *n_hits, const float *pol, int32_t R, int32_t W, int32_t max_images,
-                                      const lt_thermal *thermal, const double *flux, const lt_atmosphere *atmosphere, const double *limb,
-                                      const double *poldeg, const double *nu, int32_t n_freq, const HostArray &out, Dev dev)
-{
-    const size_t n = (size_t)R * W, n_mu = (size_t)atmosphere->n_mu;
-    return staged_call({{hits, n, (size_t)max_images * 16}, {n_hits, n, 1}, {pol, n, (size_t)max_images * 16}, {flux, (size_t)thermal->n_r, 8},
-                        {limb, n_mu, 8}, {poldeg, n_mu, 8}, {nu, (size_t)n_freq, 8}}, {out}, dev);
 }
 
 extern "C" int lt_disk_thermal_spectrum_stokes(const float *hits, const uint8_t *n_hits, const float *pol, int32_t R, int32_t W,
@@ -65,13 +47,13 @@ extern "C" int lt_disk_thermal_spectrum_stokes(const float *hits, const uint8_t 
 {
     ThermalShade ts;
     AtmosphereShade as;
-    int rc = resolve_thermal(hits, R, W, max_images, metric, disk, thermal, flux, nu, false, &ts);
-    if (rc || (rc = resolve_atmosphere(pol, atmosphere, limb, poldeg, &as)) || (rc = check_freqs_and_out(n_freq, LT_THERMAL_MAX_FREQS, out)) ||
-        n_freq == 0)
-        return rc;
-    const size_t planes = thermal->split_orders ? (size_t)max_images : 1;
-    return staged_thermal_stokes_call(hits, n_hits, pol, R, W, max_images, thermal, flux, atmosphere, limb, poldeg, nu, n_freq,
-                                      {out, planes * 3 * (size_t)n_freq, 8}, [&](void *const *in, void *const *out_) {
+    const int rc = resolve_thermal(hits, R, W, max_images, metric, disk, thermal, flux, nu, false, n_freq, out, &ts,
+                                   [&]() { return resolve_atmosphere(pol, atmosphere, limb, poldeg, &as); });
+    if (rc || n_freq == 0) return rc;
+    const size_t planes = thermal->split_orders ? (size_t)max_images : 1, n_mu = (size_t)atmosphere->n_mu;
+    return staged_hits_call(hits, n_hits, R, W, max_images, {{pol, (size_t)R * W, (size_t)max_images * 16}, {flux, (size_t)thermal->n_r, 8},
+                            {limb, n_mu, 8}, {poldeg, n_mu, 8}, {nu, (size_t)n_freq, 8}}, {out, planes * 3 * (size_t)n_freq, 8},
+                            [&](void *const *in, void *const *out_) {
         return lt_disk_thermal_spectrum_stokes_dev((const float *)in[0], (const uint8_t *)in[1], (const float *)in[2], R, W, max_images, metric,
                                                    disk, thermal, (const double *)in[3], atmosphere, (const double *)in[4],
                                                    (const double *)in[5], (const double *)in[6], n_freq, (double *)out_[0]);
@@ -85,10 +67,9 @@ extern "C" int lt_shade_thermal_stokes_dev(const float *d_hits, const uint8_t *d
 {
     ThermalShade ts;
     AtmosphereShade as;
-    int rc = resolve_thermal(d_hits, R, W, max_images, metric, disk, thermal, d_flux, d_nu, true, &ts);
-    if (rc || (rc = resolve_atmosphere(d_pol, atmosphere, d_limb, d_poldeg, &as)) ||
-        (rc = check_freqs_and_out(n_freq, LT_THERMAL_MAX_BANDS, d_out)) || n_freq == 0)
-        return rc;
+    const int rc = resolve_thermal(d_hits, R, W, max_images, metric, disk, thermal, d_flux, d_nu, true, n_freq, d_out, &ts,
+                                   [&]() { return resolve_atmosphere(d_pol, atmosphere, d_limb, d_poldeg, &as); });
+    if (rc || n_freq == 0) return rc;
     const int64_t n_px = (int64_t)R * W;
     k_shade_thermal_stokes<<<(unsigned)((n_px + 255) / 256), 256>>>(d_hits, d_n_hits, d_pol, n_px, max_images, ts, d_flux, as, d_nu, n_freq, d_out);
     HIP_TRY(hipGetLastError());
@@ -102,12 +83,13 @@ extern "C" int lt_shade_thermal_stokes(const float *hits, const uint8_t *n_hits,
 {
     ThermalShade ts;
     AtmosphereShade as;
-    int rc = resolve_thermal(hits, R, W, max_images, metric, disk, thermal, flux, nu, true, &ts);
-    if (rc || (rc = resolve_atmosphere(pol, atmosphere, limb, poldeg, &as)) || (rc = check_freqs_and_out(n_freq, LT_THERMAL_MAX_BANDS, out)) ||
-        n_freq == 0)
-        return rc;
-    return staged_thermal_stokes_call(hits, n_hits, pol, R, W, max_images, thermal, flux, atmosphere, limb, poldeg, nu, n_freq,
-                                      {out, (size_t)n_freq * 3 * (size_t)R * W, 4}, [&](void *const *in, void *const *out_) {
+    const int rc = resolve_thermal(hits, R, W, max_images, metric, disk, thermal, flux, nu, true, n_freq, out, &ts,
+                                   [&]() { return resolve_atmosphere(pol, atmosphere, limb, poldeg, &as); });
+    if (rc || n_freq == 0) return rc;
+    const size_t n_mu = (size_t)atmosphere->n_mu;
+    return staged_hits_call(hits, n_hits, R, W, max_images, {{pol, (size_t)R * W, (size_t)max_images * 16}, {flux, (size_t)thermal->n_r, 8},
+                            {limb, n_mu, 8}, {poldeg, n_mu, 8}, {nu, (size_t)n_freq, 8}}, {out, (size_t)n_freq * 3 * (size_t)R * W, 4},
+                            [&](void *const *in, void *const *out_) {
         return lt_shade_thermal_stokes_dev((const float *)in[0], (const uint8_t *)in[1], (const float *)in[2], R, W, max_images, metric, disk,
                                            thermal, (const double *)in[3], atmosphere, (const double *)in[4], (const double *)in[5],
                                            (const double *)in[6], n_freq, (float *)out_[0]);

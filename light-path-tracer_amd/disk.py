@@ -1218,19 +1218,48 @@ def _frequencies(nu, limit):
     return nu
 
 
+def _thermal_planes(thermal, nu, A, c, emits, w=None):
+    """The plane loop of both spectra -> (planes, n_freq), or (planes, 3, n_freq) with the slots' weights w (..., max_images,
+    3): per plane and frequency ((nu nu) nu) times the sum of the emitting slots' terms, each times its weight where given."""
+    out = np.zeros((thermal.planes(c.shape[-1]),) + (() if w is None else (3,)) + (nu.size,))
+    for plane in range(out.shape[0]):
+        on = emits[..., plane] if thermal.split_orders else emits
+        cp = c[..., plane][on] if thermal.split_orders else c[on]
+        wp = None if w is None else w[..., plane, :][on] if thermal.split_orders else w[on]
+        for k in range(0, nu.size, 8):
+            f = nu[k:k + 8, None]
+            t = thermal_term(f, A, cp[None, :])
+            if w is None:
+                out[plane, k:k + 8] = ((f[:, 0] * f[:, 0]) * f[:, 0]) * t.sum(axis=-1)
+            else:
+                for x in range(3):
+                    out[plane, x, k:k + 8] = ((f[:, 0] * f[:, 0]) * f[:, 0]) * (wp[None, :, x] * t).sum(axis=-1)
+    return out
+
+
+def _thermal_bands(nu, A, c, emits, w=None):
+    """The band loop of both band images -> (n_freq, R, W) float32, or (n_freq, 3, R, W) with the slots' weights w: the emitting
+    slots' terms added in slot order in float64, S + t, or S = fma(w_X, t, S) where given; times (nu nu) nu; one rounding."""
+    out = np.zeros((nu.size,) + (() if w is None else (3,)) + c.shape[:-1], dtype=np.float32)
+    for b, f in enumerate(nu):
+        total = np.zeros(out.shape[1:])
+        for j in range(c.shape[-1]):
+            t = np.where(emits[..., j], thermal_term(f, A, np.where(emits[..., j], c[..., j], 1.0)), 0.0)
+            if w is None:
+                total = total + t
+            else:
+                for s_ in range(3):
+                    total[s_] = np.where(emits[..., j], fma(w[..., j, s_], t, total[s_]), total[s_])
+        out[b] = (((f * f) * f) * total).astype(np.float32)
+    return out
+
+
 def thermal_spectrum(hits, n_hits, thermal, nu):
     """lt_disk_thermal_spectrum restated: (planes, n_freq) float64, per plane and frequency ((nu nu) nu) times the sum of
     A / expm1(nu c) over the emitting slots of all pixels (the order of the sum is numpy's, not the kernel's); planes is 1,
     or max_images with thermal.split_orders."""
     nu = _frequencies(nu, THERMAL_MAX_FREQS)
-    A, c, emits = thermal_coeffs(hits, n_hits, thermal)
-    out = np.zeros((thermal.planes(c.shape[-1]), nu.size))
-    for plane in range(out.shape[0]):
-        cp = c[..., plane][emits[..., plane]] if thermal.split_orders else c[emits]
-        for k in range(0, nu.size, 8):
-            f = nu[k:k + 8, None]
-            out[plane, k:k + 8] = ((f[:, 0] * f[:, 0]) * f[:, 0]) * thermal_term(f, A, cp[None, :]).sum(axis=-1)
-    return out
+    return _thermal_planes(thermal, nu, *thermal_coeffs(hits, n_hits, thermal))
 
 
 def shade_thermal(hits, n_hits, thermal, nu):
@@ -1239,14 +1268,7 @@ def shade_thermal(hits, n_hits, thermal, nu):
     if thermal.split_orders:
         raise ValueError("shade_thermal: a band image has one plane per band; split_orders must be off")
     nu = _frequencies(nu, THERMAL_MAX_BANDS)
-    A, c, emits = thermal_coeffs(hits, n_hits, thermal)
-    out = np.zeros((nu.size,) + c.shape[:-1], dtype=np.float32)
-    for b, f in enumerate(nu):
-        total = np.zeros(c.shape[:-1])
-        for j in range(c.shape[-1]):
-            total = total + np.where(emits[..., j], thermal_term(f, A, np.where(emits[..., j], c[..., j], 1.0)), 0.0)
-        out[b] = (((f * f) * f) * total).astype(np.float32)
-    return out
+    return _thermal_bands(nu, *thermal_coeffs(hits, n_hits, thermal))
 
 
 # ---- polarized thermal continuum (lt_disk_thermal_spectrum_stokes, lt_shade_thermal_stokes) ----------------------------------
@@ -1325,17 +1347,7 @@ def thermal_spectrum_stokes(hits, n_hits, pol, thermal, atmosphere, nu):
     nu = _frequencies(nu, THERMAL_MAX_FREQS)
     A, c, emits = thermal_coeffs(hits, n_hits, thermal)
     w, ok = atmosphere_weights(pol, atmosphere)
-    emits = emits & ok
-    out = np.zeros((thermal.planes(c.shape[-1]), 3, nu.size))
-    for plane in range(out.shape[0]):
-        on = emits[..., plane] if thermal.split_orders else emits
-        cp, wp = (c[..., plane][on], w[..., plane, :][on]) if thermal.split_orders else (c[on], w[on])
-        for k in range(0, nu.size, 8):
-            f = nu[k:k + 8, None]
-            t = thermal_term(f, A, cp[None, :])
-            for x in range(3):
-                out[plane, x, k:k + 8] = ((f[:, 0] * f[:, 0]) * f[:, 0]) * (wp[None, :, x] * t).sum(axis=-1)
-    return out
+    return _thermal_planes(thermal, nu, A, c, emits & ok, w)
 
 
 def shade_thermal_stokes(hits, n_hits, pol, thermal, atmosphere, nu):
@@ -1346,16 +1358,7 @@ def shade_thermal_stokes(hits, n_hits, pol, thermal, atmosphere, nu):
     nu = _frequencies(nu, THERMAL_MAX_BANDS)
     A, c, emits = thermal_coeffs(hits, n_hits, thermal)
     w, ok = atmosphere_weights(pol, atmosphere)
-    emits = emits & ok
-    out = np.zeros((nu.size, 3) + c.shape[:-1], dtype=np.float32)
-    for b, f in enumerate(nu):
-        total = np.zeros((3,) + c.shape[:-1])
-        for j in range(c.shape[-1]):
-            t = np.where(emits[..., j], thermal_term(f, A, np.where(emits[..., j], c[..., j], 1.0)), 0.0)
-            for s_ in range(3):
-                total[s_] = np.where(emits[..., j], fma(w[..., j, s_], t, total[s_]), total[s_])
-        out[b] = (((f * f) * f) * total).astype(np.float32)
-    return out
+    return _thermal_bands(nu, A, c, emits & ok, w)
 
 
 def polarization_degree_angle(iqu, axis=-2):

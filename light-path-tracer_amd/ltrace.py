@@ -1750,16 +1750,37 @@ def _thermal_arrays(thermal, flux, nu, limit):
     return flux, nu
 
 
+def _atmosphere_tables(limb, poldeg):
+    """(lt_atmosphere, limb, poldeg) as the library reads them: two float64 tables of one size, 2 ... ATMOSPHERE_MAX_NODES nodes."""
+    limb, poldeg = np.ascontiguousarray(limb, dtype=np.float64), np.ascontiguousarray(poldeg, dtype=np.float64)
+    if limb.ndim != 1 or limb.shape != poldeg.shape or not 2 <= limb.size <= ATMOSPHERE_MAX_NODES:
+        raise ValueError(f"limb and poldeg must both be (n_mu,), n_mu 2 ... {ATMOSPHERE_MAX_NODES}; got {limb.shape} and {poldeg.shape}")
+    return Atmosphere(limb.size, 0), limb, poldeg
+
+
+def _thermal(fn, records, metric, disk, thermal, flux, nu, bands, atmosphere=None):
+    """One host-form thermal product fn of the checked records (the polarization records behind them with an atmosphere =
+    (limb, poldeg)): the tables and frequencies as the library reads them, and the output -- (planes, n_freq) float64 of a
+    spectrum, (n_bands, rows, W) float32 of band images, with an atmosphere a Stokes axis of 3 before the last axis or two."""
+    R, W, m = records[0].shape[:3]
+    flux, nu = _thermal_arrays(thermal, flux, nu, THERMAL_MAX_BANDS if bands else THERMAL_MAX_FREQS)
+    atm, stokes = (), ()
+    if atmosphere is not None:
+        a, limb, poldeg = _atmosphere_tables(*atmosphere)
+        atm, stokes = (C.byref(a), _np_ptr(limb), _np_ptr(poldeg)), (3,)
+    if bands:
+        out = np.empty((nu.size,) + stokes + (R, W), dtype=np.float32)
+    else:
+        out = np.empty((min(m, DISK_MAX_IMAGES) if thermal.split_orders else 1,) + stokes + (nu.size,))
+    _check(fn(*map(_np_ptr, records), R, W, m, C.byref(metric), C.byref(disk), C.byref(thermal), _np_ptr(flux), *atm, _np_ptr(nu), nu.size,
+              _np_ptr(out)))
+    return out
+
+
 def thermal_spectrum(hits, n_hits, metric, disk, thermal, flux, nu):
     """The disk's thermal spectrum from stored hits (lt_disk_thermal_spectrum) -> (planes, n_freq) float64, the flux density
     at the frequencies nu summed over all pixels and stored slots; plane j the image order j with thermal.split_orders."""
-    hits, nh = _hit_arrays(hits, n_hits)
-    R, W, m = hits.shape[:3]
-    flux, nu = _thermal_arrays(thermal, flux, nu, THERMAL_MAX_FREQS)
-    out = np.empty((min(m, DISK_MAX_IMAGES) if thermal.split_orders else 1, nu.size))
-    _check(load().lt_disk_thermal_spectrum(_np_ptr(hits), _np_ptr(nh), R, W, m, C.byref(metric), C.byref(disk), C.byref(thermal),
-                                           _np_ptr(flux), _np_ptr(nu), nu.size, _np_ptr(out)))
-    return out
+    return _thermal(load().lt_disk_thermal_spectrum, _hit_arrays(hits, n_hits), metric, disk, thermal, flux, nu, False)
 
 
 def thermal_spectrum_dev(d_hits, d_n_hits, rows, width, max_images, metric, disk, thermal, d_flux, d_nu, n_freq, d_out):
@@ -1770,13 +1791,7 @@ def thermal_spectrum_dev(d_hits, d_n_hits, rows, width, max_images, metric, disk
 
 def shade_thermal(hits, n_hits, metric, disk, thermal, flux, nu):
     """The disk's thermal band images from stored hits (lt_shade_thermal) -> (n_bands, rows, W) float32, unclamped."""
-    hits, nh = _hit_arrays(hits, n_hits)
-    R, W, m = hits.shape[:3]
-    flux, nu = _thermal_arrays(thermal, flux, nu, THERMAL_MAX_BANDS)
-    out = np.empty((nu.size, R, W), dtype=np.float32)
-    _check(load().lt_shade_thermal(_np_ptr(hits), _np_ptr(nh), R, W, m, C.byref(metric), C.byref(disk), C.byref(thermal), _np_ptr(flux),
-                                   _np_ptr(nu), nu.size, _np_ptr(out)))
-    return out
+    return _thermal(load().lt_shade_thermal, _hit_arrays(hits, n_hits), metric, disk, thermal, flux, nu, True)
 
 
 def shade_thermal_dev(d_hits, d_n_hits, rows, width, max_images, metric, disk, thermal, d_flux, d_nu, n_freq, d_out):
@@ -2076,27 +2091,12 @@ def hotspot_visibility_stokes_dev(d_hits, d_n_hits, d_pol, rows, width, max_imag
 
 
 # ---- polarized thermal continuum (lt_disk_thermal_spectrum_stokes, lt_shade_thermal_stokes) --------------------------------
-def _atmosphere_tables(limb, poldeg):
-    """(lt_atmosphere, limb, poldeg) as the library reads them: two float64 tables of one size, 2 ... ATMOSPHERE_MAX_NODES nodes."""
-    limb, poldeg = np.ascontiguousarray(limb, dtype=np.float64), np.ascontiguousarray(poldeg, dtype=np.float64)
-    if limb.ndim != 1 or limb.shape != poldeg.shape or not 2 <= limb.size <= ATMOSPHERE_MAX_NODES:
-        raise ValueError(f"limb and poldeg must both be (n_mu,), n_mu 2 ... {ATMOSPHERE_MAX_NODES}; got {limb.shape} and {poldeg.shape}")
-    return Atmosphere(limb.size, 0), limb, poldeg
-
-
 def thermal_spectrum_stokes(hits, n_hits, pol, metric, disk, thermal, flux, limb, poldeg, nu):
     """The thermal spectrum of a scattering atmosphere from stored hits (lt_disk_thermal_spectrum_stokes) -> (planes, 3, n_freq)
     float64, the Stokes axis (I, Q, U); pol the (rows, W, max_images, 4) records of trace_disk_pol for the field (0, 0, 1), limb
     and poldeg the atmosphere's tables on mu, the rest as thermal_spectrum.  With limb = 1 the I plane has thermal_spectrum's bits."""
-    hits, nh, pol = _pol_records(hits, n_hits, pol)
-    R, W, m = hits.shape[:3]
-    flux, nu = _thermal_arrays(thermal, flux, nu, THERMAL_MAX_FREQS)
-    atm, limb, poldeg = _atmosphere_tables(limb, poldeg)
-    out = np.empty((min(m, DISK_MAX_IMAGES) if thermal.split_orders else 1, 3, nu.size))
-    _check(load().lt_disk_thermal_spectrum_stokes(_np_ptr(hits), _np_ptr(nh), _np_ptr(pol), R, W, m, C.byref(metric), C.byref(disk),
-                                                  C.byref(thermal), _np_ptr(flux), C.byref(atm), _np_ptr(limb), _np_ptr(poldeg), _np_ptr(nu),
-                                                  nu.size, _np_ptr(out)))
-    return out
+    return _thermal(load().lt_disk_thermal_spectrum_stokes, _pol_records(hits, n_hits, pol), metric, disk, thermal, flux, nu, False,
+                    (limb, poldeg))
 
 
 def thermal_spectrum_stokes_dev(d_hits, d_n_hits, d_pol, rows, width, max_images, metric, disk, thermal, d_flux, n_mu, d_limb, d_poldeg, d_nu,
@@ -2110,14 +2110,7 @@ def thermal_spectrum_stokes_dev(d_hits, d_n_hits, d_pol, rows, width, max_images
 def shade_thermal_stokes(hits, n_hits, pol, metric, disk, thermal, flux, limb, poldeg, nu):
     """The band images of a scattering atmosphere from stored hits (lt_shade_thermal_stokes) -> (n_bands, 3, rows, W) float32,
     unclamped, the Stokes axis (I, Q, U).  With limb = 1 the I planes have shade_thermal's bits."""
-    hits, nh, pol = _pol_records(hits, n_hits, pol)
-    R, W, m = hits.shape[:3]
-    flux, nu = _thermal_arrays(thermal, flux, nu, THERMAL_MAX_BANDS)
-    atm, limb, poldeg = _atmosphere_tables(limb, poldeg)
-    out = np.empty((nu.size, 3, R, W), dtype=np.float32)
-    _check(load().lt_shade_thermal_stokes(_np_ptr(hits), _np_ptr(nh), _np_ptr(pol), R, W, m, C.byref(metric), C.byref(disk), C.byref(thermal),
-                                          _np_ptr(flux), C.byref(atm), _np_ptr(limb), _np_ptr(poldeg), _np_ptr(nu), nu.size, _np_ptr(out)))
-    return out
+    return _thermal(load().lt_shade_thermal_stokes, _pol_records(hits, n_hits, pol), metric, disk, thermal, flux, nu, True, (limb, poldeg))
 
 
 def shade_thermal_stokes_dev(d_hits, d_n_hits, d_pol, rows, width, max_images, metric, disk, thermal, d_flux, n_mu, d_limb, d_poldeg, d_nu,

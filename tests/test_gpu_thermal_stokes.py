@@ -162,6 +162,29 @@ def test_dev_forms_equal_the_host_forms():
     assert d_img.get().tobytes() == bands(hits, n_hits, pol, met, dk, flat, atm, nu).tobytes()
 
 
+def test_whole_and_halved_walks_give_the_same_bits():
+    """Four images are the most whose lists the polarized first stage holds in LDS at once, five the fewest it walks in
+    halves, and no case has four.  A: the strip's first four slots.  B: A behind a fifth slot of NaN, which stores and emits
+    nothing.  The two are the same records, so the spectra must agree in every bit -- 257 frequencies: two passes, the second
+    with one owner -- and B's fifth plane is exactly +0.0.  The unpolarized spectrum, one path for both, says the same."""
+    c, hits, n_hits, met, dk, _ = setup("strip")
+    a_hits, a_pol = np.ascontiguousarray(hits[:, :, :4]), np.ascontiguousarray(stokes_pol("strip")[:, :, :4])
+    pad = np.full((c.R, c.W, 1, 4), np.nan, dtype=np.float32)
+    b_hits, b_pol = np.concatenate([a_hits, pad], axis=2), np.concatenate([a_pol, pad], axis=2)
+    assert a_hits.shape[2] == 4 and b_hits.shape[2] == 5
+    atm, nu = make_atmosphere(), frequencies(257)
+    for split in (False, True):
+        td = make_thermal("strip", split)
+        for counts in (np.minimum(n_hits, 4).astype(np.uint8), None):
+            stokes = [spectrum(h, counts, p, met, dk, td, atm, nu) for h, p in ((a_hits, a_pol), (b_hits, b_pol))]
+            plain = [ltrace.thermal_spectrum(h, counts, met, dk, td.to_lt(), td.flux, nu) for h in (a_hits, b_hits)]
+            for a, b in (stokes, plain):
+                assert a.shape[0] == (4 if split else 1) and b.shape[0] == (5 if split else 1)
+                assert b[:a.shape[0]].tobytes() == a.tobytes(), (split, counts is None, a.ndim)
+                assert not split or (np.all(b[4] == 0.0) and not np.any(np.signbit(b[4])))
+            assert np.count_nonzero(stokes[0][:, 0]) > 0 and np.count_nonzero(stokes[0][:, 1:]) > 0 and np.count_nonzero(plain[0]) > 0
+
+
 # ---- 3. exact zeros -----------------------------------------------------------------------------------------------------------------
 def test_records_that_emit_nothing_give_exact_zeros():
     c, hits, n_hits, met, dk, td = setup("mid", True)

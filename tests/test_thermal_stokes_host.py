@@ -246,6 +246,24 @@ def test_isotropic_is_the_unpolarized_continuum():
     assert np.all(dim[0, 0][warm] < diskmod.thermal_spectrum(hits, n_hits, make_thermal(name), nu)[0][warm])
 
 
+def test_a_fifth_slot_of_nan_changes_no_bit():
+    """The records of tests/test_gpu_thermal_stokes.py's whole-and-halved case are one set of records to the numpy
+    statements too: the strip's first four slots, and the same behind a fifth slot of NaN."""
+    hits, n_hits = thermal_records("strip")
+    a_hits, a_pol = hits[:, :, :4], stokes_pol("strip")[:, :, :4]
+    pad = np.full(a_hits.shape[:2] + (1, 4), np.nan, dtype=np.float32)
+    b_hits, b_pol = np.concatenate([a_hits, pad], axis=2), np.concatenate([a_pol, pad], axis=2)
+    nu = frequencies(9)
+    for split in (False, True):
+        td = make_thermal("strip", split)
+        for counts in (np.minimum(n_hits, 4).astype(np.uint8), None):
+            a = diskmod.thermal_spectrum_stokes(a_hits, counts, a_pol, td, make_atmosphere(), nu)
+            b = diskmod.thermal_spectrum_stokes(b_hits, counts, b_pol, td, make_atmosphere(), nu)
+            assert b[:a.shape[0]].tobytes() == a.tobytes() and a.shape[0] == (4 if split else 1) and b.shape[0] == (5 if split else 1)
+            assert not split or (np.all(b[4] == 0.0) and not np.any(np.signbit(b[4])))
+            assert np.count_nonzero(a[:, 0]) > 0 and np.count_nonzero(a[:, 1:]) > 0
+
+
 def test_slots_that_emit_nothing_are_exact_zeros():
     hits, n_hits = synth(6, 9, 3, 5, 2.4, 20.0)
     n_hits[:] = 3

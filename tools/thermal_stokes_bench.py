@@ -35,7 +35,7 @@ import ltrace  # noqa: E402
 COUNTS = (64, 256, 1024)
 # VGPRs of k_thermal_spectrum_stokes_partial<1> / <8> beside k_thermal_spectrum_partial<1> / <8> and the scratch bytes a lane
 # (the launch bound holds <8> to 128 registers, five spill); LDS bytes of a workgroup and the workgroups a CU's 160 KiB and
-# its 512 VGPRs per SIMD hold, at 3 and 8 images
+# its 512 VGPRs per SIMD hold, at 3 and 8 images (confirmed unchanged by profiles/thermal_fold_check.txt, part B)
 RESOURCES = dict(vgprs=dict(stokes_whole=95, stokes_split=128, thermal_whole=93, thermal_split=107),
                  scratch_bytes=dict(stokes_whole=0, stokes_split=24, thermal_whole=0, thermal_split=0),
                  lds_bytes={"3": dict(stokes=25360, thermal=6928), "8": dict(stokes=33808, thermal=18448)},
