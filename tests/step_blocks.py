@@ -201,6 +201,23 @@ def inside_cut_class(a, n, seed=0):
 
 
 STEP_CLASSES = ("far", "mid", "band", "near", "pole_approach")
+BAND_R = (1.3, 4.0)      # radial range of `band`, in r_plus
+NEAR_R = (1.05, 1.2)     # ... and of `near`, which exists up to NEAR_MAX_SPIN only
+NEAR_MAX_SPIN = 0.9
+
+
+def step_r_min(a):
+    """The smallest radius the step classes cover at spin a, hence the smallest at which K_STEP was derived: the inner edge
+    of `near`, or of `band` at the spins `near` does not exist at.  Below it no bound for one float32 step is stated
+    anywhere: nothing here says that the kernel's step is sound there, nor that it is not."""
+    return (NEAR_R[0] if abs(a) <= NEAR_MAX_SPIN else BAND_R[0]) * r_plus(a)
+
+
+def fast_step_valid(a, out):
+    """The validity test of the branch-free step on lt_kerr_step_probe's report `out` (min_r, max_d), with the r_cut the
+    float32 kernels use: a lane for which it fails takes the checked step."""
+    with np.errstate(invalid="ignore"):
+        return (out["min_r"] > float(np.float32(r_plus(a) * 1.001))) & (out["max_d"] <= 0.25)
 
 
 def step_class(name, a, n, seed=0, rounded=True):
@@ -215,11 +232,11 @@ def step_class(name, a, n, seed=0, rounded=True):
     elif name == "mid":
         (st, L), h, refine = _states(rng, n, 4.2 * rp, 20.0, *th), 1.0, 0
     elif name == "band":
-        (st, L), h, refine = _states(rng, n, 1.3 * rp, 4.0 * rp, *th), 0.1, 0
+        (st, L), h, refine = _states(rng, n, BAND_R[0] * rp, BAND_R[1] * rp, *th), 0.1, 0
     elif name == "near":
-        if a > 0.9:
+        if a > NEAR_MAX_SPIN:
             return None
-        (st, L), h, refine = _states(rng, n, 1.05 * rp, 1.2 * rp, *th), 0.05, 0
+        (st, L), h, refine = _states(rng, n, NEAR_R[0] * rp, NEAR_R[1] * rp, *th), 0.05, 0
     elif name == "pole_approach":
         (st, L), h, refine = _states(rng, n, 5.0, 50.0, 0.05, 0.3), 0.5, 1
         L *= np.sin(st[:, 1])  # (a ray this close to the axis has |L| <~ b sin theta)

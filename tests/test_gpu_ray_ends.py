@@ -4,7 +4,8 @@
 against the oracle's own functions, in the units of tests/ray_ends.py.  Every bound is a constant that
 tests/test_ray_ends_host.py derives on the CPU from the oracle and longdouble alone; the device is held to twice it.
 
-Whole rays stay under the statistics of test_gpu_parity.py; this file says which operation is wrong.
+Whole production rays are held to their replay through these probes, bit for bit, by test_gpu_ray_replay.py (against the
+reference they stay under the statistics of test_gpu_parity.py); this file says which operation is wrong.
 
 MEASURED on the MI355X: profiles/ray_ends_<build id>.json (LT_RAY_ENDS_MEASURE=path writes it), DESIGN.md 2.1.
 """

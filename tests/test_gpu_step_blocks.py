@@ -333,7 +333,7 @@ def step(a, c, form, precision=32, n=None):
 
 def valid(a, out):
     """The validity test of the branch-free step, with the r_cut the kernels use."""
-    return (out["min_r"] > float(np.float32(sb.r_plus(a) * 1.001))) & (out["max_d"] <= 0.25)
+    return sb.fast_step_valid(a, out)
 
 
 STEP_SETS = sb.STEP_CLASSES + ("eq_band", "fallback")
